@@ -61,6 +61,9 @@ def parse_args(argv=None):
     ap.add_argument("--live-traffic", type=int, default=1, help="N = 1, config sizes: collect the headline rooflines' `traffic` in this run (two rocprofv3 --pmc child passes)")
     ap.add_argument("--dry", type=int, default=0, help="1: no device work -- rank spawn, slab planes, halo sizes, workspace bytes per rank, the compact line (CPU only)")
     ap.add_argument("--full-out", default="", help="path of the full result object (default gpurun_out/bench_full.json; '-' = do not write)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the headline workload's last timed step computed (K values, residual R, solution dx, solver residuals) as DIR/<name>.npy "
+                         "(float64; a fixed seeded sample of an array above its share of the 64 MB budget, with the sampled positions beside it)")
     return ap.parse_args(argv)
 
 
@@ -120,6 +123,35 @@ def self_launch(n_ranks: int) -> int:
     return 0
 
 
+DUMP_SEED = 0x5EED
+# entries kept per array (float64 values + their float64 positions when sampled): 2 x 8 B x (1.5 + 1 + 1) M = 56 MB of the 64 MB budget
+DUMP_KEEP = {"K": 1_500_000, "R": 1_000_000, "dx": 1_000_000}
+
+
+def output_dumper(dump_dir):
+    """-> on_last callback of Bench.run_workload: writes DIR/<name>.npy of the last timed step.  An array longer than its DUMP_KEEP share is sampled
+    at positions drawn from a fixed seed (sorted, depend only on the array's length), written as <name>_index.npy; the values are what the caller's
+    arrays hold at those positions.  stats.npy = [initial_res, final_res, iterations, spmv_count] of the last solve."""
+    import numpy as np
+    import torch
+
+    def dump(K, R, dx, st):
+        os.makedirs(dump_dir, exist_ok=True)
+        for name, t in (("K", K), ("R", R), ("dx", dx)):
+            n = t.numel()
+            keep = DUMP_KEEP[name]
+            if n > keep:
+                idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, size=keep, dtype=np.int64))
+                vals = t[torch.from_numpy(idx).to(t.device)]
+                np.save(os.path.join(dump_dir, f"{name}_index.npy"), idx.astype(np.float64))
+            else:
+                vals = t
+            np.save(os.path.join(dump_dir, f"{name}.npy"), vals.detach().to("cpu", torch.float64).numpy())
+        np.save(os.path.join(dump_dir, "stats.npy"),
+                np.array([st.initial_res, st.final_res, st.iterations, st.spmv_count], dtype=np.float64))
+    return dump
+
+
 def emit(out, args):
     """Write the full object beside the line, print the line (rank 0)."""
     path = args.full_out or os.path.join("gpurun_out", "bench_full.json")
@@ -163,7 +195,8 @@ def main():
     if not args.remainder:
         _lib.check(_lib.lib.mfem_debug_set_remainder(0))
 
-    main_res = B.run_workload(cfg, base, args.n, args.steps, args.warmup, want_csr=True)
+    dump = output_dumper(args.dump_outputs) if args.dump_outputs and rank == 0 else None  # (N > 1: rank 0's slab)
+    main_res = B.run_workload(cfg, base, args.n, args.steps, args.warmup, want_csr=True, on_last=dump)
     out = {"errors": []}
     if rank == 0:
         out.update(B.headline_object(main_res, cfg, args.config))

@@ -376,9 +376,10 @@ class Bench:
         return comm
 
     # ---- one workload ----------------------------------------------------------------------------------------------------------------------------
-    def run_workload(self, cfg, ckey, N, steps, warmup, want_csr, strong=None, iters=None):
+    def run_workload(self, cfg, ckey, N, steps, warmup, want_csr, strong=None, iters=None, on_last=None):
         """One workload of config `ckey`, `steps` timed steps: weak scaling = an (N * world) x N x N mesh (an N-thick slab per rank), strong scaling =
-        the N^3 mesh cut into `world` slabs along i."""
+        the N^3 mesh cut into `world` slabs along i.  on_last(K, R, dx, stats), if given, sees what the last timed step computed, after the timed region
+        and before anything else overwrites it."""
         args, ctx, dev, world, rank, dist, use_comm, host_comm, state = (self.args, self.ctx, self.dev, self.world, self.rank, self.dist, self.use_comm,
                                                                          self.host_comm, self.state)
         strong = self.strong if strong is None else strong
@@ -496,6 +497,8 @@ class Bench:
             t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if host_comm else dev)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
+        if on_last is not None and st is not None:
+            on_last(K, R, dx_last, st)
         # one "DOF update" = one Krylov step on one unknown: a CG iteration (1 SpMV), or one SpMV-equivalent step of BiCGStab(2) / IDR(s)
         updates = iters_done if cfg["solver"] == "cg" else spmvs_done
         res = {"N": N, "nx_global": nx_global, "n_global": n_global, "nnz": A.nnz, "n_local": A.n, "elapsed": elapsed, "iters": iters,

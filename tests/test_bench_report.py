@@ -140,3 +140,34 @@ def test_dry_plan_nnz_is_the_lattice_stencil():
     hex27 = sum(bench_dry.slab_plan(dict(order=2, fields=1, solver="cg"), 8, 2, r, True)["nnz"] for r in range(2))
     # hex-27 8^3: per direction 9 corner points (2 x 3 + 7 x 5) + 8 mid points x 3 = 65 couplings
     assert hex27 == 65 ** 3
+
+
+def test_dump_outputs_writes_whole_or_seeded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: arrays within their share are written whole; a longer one as a sample at seeded positions that depend only on its
+    length (two runs, two builds: the same positions), every file float64, the whole dump within 64 MB at the real shares."""
+    import numpy as np
+    import torch
+
+    import bench
+
+    assert 16 * sum(bench.DUMP_KEEP.values()) + 4 * 128 <= 64 * 2 ** 20
+    monkeypatch.setattr(bench, "DUMP_KEEP", {"K": 100, "R": 1000, "dx": 1000})
+    K = torch.arange(5000, dtype=torch.float64) * 0.5
+    R = torch.linspace(-1.0, 1.0, 300, dtype=torch.float64)
+    dx = torch.ones(300, dtype=torch.float64)
+
+    class St:
+        initial_res, final_res, iterations, spmv_count = 2.0, 1e-3, 40, 41
+
+    for d in ("a", "b"):
+        bench.output_dumper(str(tmp_path / d))(K, R, dx, St())
+    a, b = tmp_path / "a", tmp_path / "b"
+    assert sorted(p.name for p in a.iterdir()) == ["K.npy", "K_index.npy", "R.npy", "dx.npy", "stats.npy"]
+    for p in a.iterdir():
+        x, y = np.load(p), np.load(b / p.name)
+        assert x.dtype == np.float64 and np.array_equal(x, y), p.name
+    idx = np.load(a / "K_index.npy")
+    assert idx.shape == (100,) and np.all(np.diff(idx) >= 0) and 0 <= idx.min() and idx.max() < 5000
+    assert np.array_equal(np.load(a / "K.npy"), idx * 0.5)
+    assert np.array_equal(np.load(a / "R.npy"), R.numpy()) and np.array_equal(np.load(a / "dx.npy"), dx.numpy())
+    assert np.load(a / "stats.npy").tolist() == [2.0, 1e-3, 40.0, 41.0]

@@ -200,3 +200,25 @@ def test_self_launch_ends_the_other_ranks_when_one_dies():
                        timeout=300, env=e, cwd=ROOT)
     assert r.returncode != 0 and "ranks failed" in r.stderr, r.stderr[-2000:]
     assert time.time() - t0 < 200
+
+
+def test_dump_outputs_of_the_timed_path(tmp_path):
+    """--dump-outputs: what the headline workload's last timed step computed, twice with the same arguments.  The inputs are the same, so the matrix
+    and the residual agree and the solution agrees to the solver's rounding; the files match the line (sizes, last solve's residuals)."""
+    import numpy as np
+
+    outs = []
+    for d in ("a", "b"):
+        out = run_bench(["--n", "16", "--iters", "30", "--dump-outputs", str(tmp_path / d)] + SMALL)
+        _common(out, 1)
+        outs.append(out)
+    a, b = tmp_path / "a", tmp_path / "b"
+    assert sorted(p.name for p in a.iterdir()) == ["K.npy", "R.npy", "dx.npy", "stats.npy"]
+    n = 17 ** 3
+    K, R, dx, st = (np.load(a / f) for f in ("K.npy", "R.npy", "dx.npy", "stats.npy"))
+    assert K.dtype == R.dtype == dx.dtype == st.dtype == np.float64
+    assert K.shape == (outs[0]["config"]["nnz"],) and R.shape == dx.shape == (n,)
+    assert np.all(np.isfinite(K)) and np.all(np.isfinite(dx)) and np.abs(dx).max() > 0
+    assert st[0] == outs[0]["config"]["initial_res"] and st[1] == outs[0]["config"]["final_res"] and st[2] == 30
+    assert np.allclose(np.load(b / "K.npy"), K, rtol=1e-13, atol=0) and np.allclose(np.load(b / "R.npy"), R, rtol=1e-13, atol=0)
+    assert np.allclose(np.load(b / "dx.npy"), dx, rtol=1e-9, atol=1e-12 * np.abs(dx).max())
