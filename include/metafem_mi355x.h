@@ -456,7 +456,8 @@ int mfem_mesh_assemble_elements(mfem_context ctx, int32_t dim, int32_t itg, int3
  * into (zero it first; facet terms are added by mfem_mesh_assemble_facets before or after).
  * adj_ptr [ncp + 1], adj [nel * itp]: for every control point the (element * itp + local node id) pairs that reference it,
  * 0-based, ascending.  A = the pattern of mfem_pattern_build for n_fields fields.  MFEM_ERR_UNSUPPORTED if a row is longer
- * than 2048 entries or the scratch (nel * itp^2 * blocks * 8 B) exceeds 16 GiB: use mfem_mesh_assemble_elements then. */
+ * than 2048 entries, the scratch (nel * itp^2 * blocks * 8 B) exceeds its budget, n_fields > 4 or an element's table does not fit one
+ * wave's LDS: use mfem_mesh_assemble_elements then. */
 int mfem_mesh_assemble_elements_rows(mfem_context ctx, int32_t dim, int32_t itg, int32_t itp, int64_t nel, int64_t ncp,
                                      const double* ref_itp_vals, const double* itg_weight, const double* coords,
                                      const int32_t* controlpoint_IDs, int32_t index_base, int32_t n_terms,
@@ -474,7 +475,8 @@ int mfem_mesh_assemble_elements_rows_set(mfem_context ctx, int32_t dim, int32_t 
  * b, the position of node(el, b) among the control points coupled to i -- the column offset inside every field segment of a
  * row of node i (the role the reference's sparse_IDs_by_el plays for its scatter, read unit-stride by the row-owner pass).
  * MFEM_ERR_UNSUPPORTED when an element lists one control point twice (collapsed elements): the row-owner pass assumes distinct
- * positions per element; use mfem_mesh_assemble_elements there. */
+ * positions per element; and for more than 4 fields (the pattern takes up to 8): the row-owner pass gathers up to 4 x 4 blocks.  Use
+ * mfem_mesh_assemble_elements there. */
 int mfem_mesh_row_ranks(mfem_context ctx, int32_t itp, int64_t nel, int64_t ncp, int32_t n_fields, mfem_csr A,
                         const int64_t* adj_ptr, const int32_t* adj, const int32_t* controlpoint_IDs, int32_t index_base,
                         uint16_t* ranks);

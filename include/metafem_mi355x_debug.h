@@ -104,6 +104,13 @@ int mfem_debug_graph_comm_count(void);
 /* ^ key "hex27": mfem_debug_set("hex27", a, b) with (int two_pass) = (a[, b]) */
 /* number of mfem_mesh_assemble_elements_rows calls that ran the row-owner form (process-wide) */
 int64_t mfem_debug_mesh_rows_count(void);
+/* variants of the fused mesh assembly launched so far (process-wide), one bit per (dim, mode, kind): bit ((dim - 2) * 3 + mode) * 9 + kind, mode 0
+ * values + gradients, 1 gradients only, 2 values only; kind 0/1 colour batches with the dense coefficient rows / the term list, 2/3 the same with FP64
+ * atomics, 4/5 the same in the row-owner scratch form (elements of fewer than 16 nodes), 6 row-owner with 16+ nodes, 7 staged row-owner, 8 staged with
+ * every term pairing a word with itself.  reset != 0 clears the set after reading it. */
+int64_t mfem_debug_mesh_variants(int32_t reset);
+/* number of mfem_op_var_batch (kernel 0) / mfem_op_res_batch (kernel 1) calls that took the wave-per-item form (process-wide) */
+int64_t mfem_debug_op_wave_count(int32_t kernel);
 /* 128-row blocks of the sliced layout (mode 3) that are field-periodic -- col[f P + t] = col[t] + f shift: one column slot per node is read for the F
  * column fields -- (-1: null handle; 0: none / not planned) */
 int64_t mfem_debug_sell_periodic_blocks(mfem_csr A);

@@ -135,6 +135,8 @@ SIGNATURES = {
     "mfem_debug_hex27_mixed_count": (c_int64, []),
     "mfem_debug_hex27_rows_count": (c_int64, []),
     "mfem_debug_mesh_rows_count": (c_int64, []),
+    "mfem_debug_mesh_variants": (c_int64, [c_int32]),
+    "mfem_debug_op_wave_count": (c_int64, [c_int32]),
     "mfem_debug_bsell_fields": (c_int, [P]),
     "mfem_debug_bsell_spmv_count": (c_int64, []),
     "mfem_debug_sell_periodic_blocks": (c_int64, [P]),

@@ -425,6 +425,21 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_mesh_assemble(MeshItems V, Const
   }  // items of this wave
 }
 
+// Launched variants of k_mesh_assemble, one bit per (dim, mode, kind): bit ((dim - 2) * 3 + mode) * MV_KINDS + kind, mode 0 values + gradients /
+// 1 gradients only / 2 values only (ma_launch), kind the output form and the pair loop it runs (mfem_debug_mesh_variants; tests/test_gpu_mesh_oracle.py)
+enum {
+  MV_COLOUR_TM, MV_COLOUR_LIST,  // OUT 0: colour batches, dense coefficient rows (TM) | the term list walked
+  MV_ATOMIC_TM, MV_ATOMIC_LIST,  // OUT 1: FP64 atomics
+  MV_ROWS_TM, MV_ROWS_LIST,      // OUT 2, not staged, fewer than 16 nodes: a pair per lane
+  MV_ROWS_TA4,                   // OUT 2, not staged, 16+ nodes: four dual nodes per lane, the term list walked
+  MV_STAGE, MV_STAGE_DIAG,       // OUT 2, STAGE (and DIAGT)
+  MV_KINDS
+};
+static std::atomic<unsigned long long> g_mesh_variants{0};
+extern "C" int64_t mfem_debug_mesh_variants(int32_t reset) {
+  return (int64_t)(reset ? g_mesh_variants.exchange(0) : g_mesh_variants.load());
+}
+
 static int ma_launch(mfem_context_s* ctx, int dim, const MeshItems& V, const ConstTerms& T, const int32_t* slots,
                      int64_t block_stride, double* K, int64_t n_items, int n_colours, const int64_t* colour_offsets,
                      int scratch_blocks = 0) {
@@ -439,7 +454,7 @@ static int ma_launch(mfem_context_s* ctx, int dim, const MeshItems& V, const Con
   const int NS = mode == 2 ? 1 : mode == 1 ? dim : 1 + dim;
   const size_t per_wave = sizeof(double) * ((size_t)V.itg * V.itp * NS + (size_t)V.itg * (1 + dim * dim) + (size_t)V.itp * dim);
   // the row-owner form on elements with a table worth staging (16+ nodes): persistent workgroups, the reference table in LDS (k_mesh_assemble: STAGE)
-  const bool stage = scratch_blocks > 0 && !V.eindex && !V.order && V.itp >= g_mesh_stage_min_itp && n_colours == 0;
+  bool stage = scratch_blocks > 0 && !V.eindex && !V.order && V.itp >= g_mesh_stage_min_itp && n_colours == 0;
   TermMatrix TM;
   memset(&TM, 0, sizeof(TM));
   {
@@ -459,18 +474,34 @@ static int ma_launch(mfem_context_s* ctx, int dim, const MeshItems& V, const Con
   }
   bool diag = true;  // every term pairs a word with itself
   for (int i = 0; i < T.n; ++i) diag = diag && T.ds[i] == T.bs[i];
-  const size_t shared_ref = stage ? sizeof(double) * ((size_t)V.itg * V.itp * (1 + dim) + (size_t)scratch_blocks * (diag ? NS : NS * NS)) : 0;
+  const size_t staged_ref = sizeof(double) * ((size_t)V.itg * V.itp * (1 + dim) + (size_t)scratch_blocks * (diag ? NS : NS * NS));
+  const size_t staged_cap = 96 * 1024;  // (a workgroup may take up to 160 KB on gfx950; two staged workgroups per CU at hex-20)
+  // the staged form only where its shared table and one wave fit (hex-27 with 64 Gauss points and values + gradients does not): the non-staged row-owner form otherwise
+  if (stage && staged_ref + per_wave > staged_cap) stage = false;
+  const size_t shared_ref = stage ? staged_ref : 0;
   int waves = 4;
-  const size_t lds_cap = stage ? 96 * 1024 : 64 * 1024;  // (a workgroup may take up to 160 KB on gfx950; two staged workgroups per CU at hex-20)
+  const size_t lds_cap = stage ? staged_cap : 64 * 1024;
   while (waves > 1 && shared_ref + per_wave * waves > lds_cap) waves >>= 1;
+  // (the scatter form the host then takes has the same one-wave limit: it refuses such an element below with MFEM_ERR_INVALID, it does not rescue it)
+  if (shared_ref + per_wave * waves > lds_cap && scratch_blocks > 0) {
+    mfem_set_error("element table of %zu bytes per wave: too large for the row-owner mesh assembly; use mfem_mesh_assemble_elements", per_wave);
+    return MFEM_ERR_UNSUPPORTED;
+  }
   MFEM_REQUIRE(shared_ref + per_wave * waves <= lds_cap, "element table too large for the fused mesh assembly (about 2 * itg * itp * (1 + dim) doubles must fit 64 KB)");
   const size_t ldsb = shared_ref + per_wave * waves;
   const bool atomic = n_colours == 0;
   const int out_mode = scratch_blocks > 0 ? 2 : atomic ? 1 : 0;
+  // the code path of k_mesh_assemble this launch takes (mfem_debug_mesh_variants): the instantiation, and inside it the pair loop's form
+  const int kind = stage ? (diag ? MV_STAGE_DIAG : MV_STAGE)
+                 : out_mode == 2 ? (V.itp >= 16 ? MV_ROWS_TA4 : TM.nruns > 0 ? MV_ROWS_TM : MV_ROWS_LIST)
+                 : out_mode == 1 ? (TM.nruns > 0 ? MV_ATOMIC_TM : MV_ATOMIC_LIST)
+                 : (TM.nruns > 0 ? MV_COLOUR_TM : MV_COLOUR_LIST);
+  const unsigned long long variant_bit = 1ull << (((dim - 2) * 3 + mode) * MV_KINDS + kind);
   const int nbatch = atomic ? 1 : n_colours;
   for (int c = 0; c < nbatch; ++c) {
     const int64_t a = atomic ? 0 : colour_offsets[c], b = atomic ? n_items : colour_offsets[c + 1];
     if (b <= a) continue;
+    g_mesh_variants.fetch_or(variant_bit);
     int grid = (int)((b - a + waves - 1) / waves);
     if (stage) {  // persistent: what is resident (LDS-bound: 160 KB per CU)
       const int per_cu = (int)(160 * 1024 / (ldsb > 0 ? ldsb : 1));
@@ -614,7 +645,11 @@ extern "C" int mfem_mesh_row_ranks(mfem_context ctx, int32_t itp, int64_t nel, i
                                    const int64_t* adj_ptr, const int32_t* adj, const int32_t* controlpoint_IDs,
                                    int32_t index_base, uint16_t* ranks) try {
   MFEM_REQUIRE(ctx && A && adj_ptr && adj && controlpoint_IDs && ranks, "null argument");
-  MFEM_REQUIRE(itp > 0 && nel >= 0 && ncp > 0 && n_fields >= 1 && n_fields <= 4, "bad sizes");
+  MFEM_REQUIRE(itp > 0 && nel >= 0 && ncp > 0 && n_fields >= 1, "bad sizes");
+  if (n_fields > 4) {
+    mfem_set_error("%d fields: the row-owner assembly takes 1..4; use mfem_mesh_assemble_elements", n_fields);
+    return MFEM_ERR_UNSUPPORTED;
+  }
   MFEM_REQUIRE(A->n == (int64_t)n_fields * ncp, "pattern rows != n_fields * ncp");
   MFEM_REQUIRE(A->max_row_nnz / n_fields < 65536, "more than 65535 coupled control points per row");
   if (nel == 0) return MFEM_OK;
@@ -804,7 +839,11 @@ static int mesh_rows(mfem_context_s* ctx, int32_t dim, int32_t itg, int32_t itp,
   MFEM_REQUIRE(ctx && A, "null handle");
   MFEM_REQUIRE(dim == 2 || dim == 3, "dim must be 2 or 3");
   MFEM_REQUIRE(itg > 0 && itp > 0 && nel >= 0 && ncp > 0, "bad sizes");
-  MFEM_REQUIRE(n_fields >= 1 && n_fields <= 4, "1..4 fields");
+  MFEM_REQUIRE(n_fields >= 1, "n_fields must be >= 1");
+  if (n_fields > 4) {  // (GatherBlocks holds 4 x 4 blocks)
+    mfem_set_error("%d fields: the row-owner assembly takes 1..4; use mfem_mesh_assemble_elements", n_fields);
+    return MFEM_ERR_UNSUPPORTED;
+  }
   MFEM_REQUIRE(index_base == 0 || index_base == 1, "index_base must be 0 or 1");
   MFEM_REQUIRE(A->n == (int64_t)n_fields * ncp, "pattern rows != n_fields * ncp");
   if (nel == 0) return MFEM_OK;

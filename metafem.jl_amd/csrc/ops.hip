@@ -331,6 +331,12 @@ struct SlabUse {
   int lo, n;  // the slabs lo .. lo + n - 1 (first to last one a term uses: contiguous in an item's table) are copied
 };
 typedef double op_d2 __attribute__((ext_vector_type(2)));
+// LDS doubles of one wave, rounded up to an even count: every wave's block (sm + w * per_wave) starts on a 16-byte boundary, so op_stage's 16-byte stores
+// are aligned on the LDS side too (hex-20 residual: 540 slab doubles per word + 27 per term -- odd for an odd number of terms)
+__host__ __device__ __forceinline__ size_t op_wave_doubles(size_t n) { return (n + 1) & ~(size_t)1; }
+// calls of mfem_op_var_batch / mfem_op_res_batch that took the wave form (process-wide; tests)
+static std::atomic<long long> g_op_var_wave_count{0}, g_op_res_wave_count{0};
+extern "C" int64_t mfem_debug_op_wave_count(int32_t kernel) { return kernel == 0 ? g_op_var_wave_count.load() : g_op_res_wave_count.load(); }
 // `count` doubles from global memory to LDS, 8 loads of a lane in flight (a plain copy loop of unknown trip count compiles to load - wait - store per
 // trip: 27 round trips per hex-20 item); 16-byte loads when both sides allow
 __device__ __forceinline__ void op_stage(double* __restrict__ dst, const double* __restrict__ src, int count, int lane) {
@@ -376,7 +382,7 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_op_res_batch_wave(OpView V, ResT
   extern __shared__ double sm[];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
   const int tab = V.itg * V.itp;
-  const size_t per_wave = (size_t)U.n * tab + (size_t)T.n * V.itg;
+  const size_t per_wave = op_wave_doubles((size_t)U.n * tab + (size_t)T.n * V.itg);
   double* S = sm + (size_t)w * per_wave;  // [slab][a][q]
   double* Vq = S + (size_t)U.n * tab;     // [term][q]
   // the terms: lane i holds term i
@@ -435,7 +441,7 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_op_var_batch_wave(OpView V, VarT
   extern __shared__ double sm[];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
   const int tab = V.itg * V.itp;
-  const size_t per_wave = (size_t)U.n * tab + (size_t)T.n * V.itp;
+  const size_t per_wave = op_wave_doubles((size_t)U.n * tab + (size_t)T.n * V.itp);
   double* S = sm + (size_t)w * per_wave;  // [slab][a][q]
   double* Xa = S + (size_t)U.n * tab;     // [term][a]: the nodal values of the term's source vector
   int my_slot = 0;
@@ -549,10 +555,11 @@ extern "C" int mfem_op_res_batch(mfem_context ctx, const mfem_op_layout* L, cons
       sd_hi = terms[i].dual_sd > sd_hi ? terms[i].dual_sd : sd_hi;
     }
     const SlabUse U{sd_lo, sd_hi - sd_lo + 1};
-    const size_t per_wave = sizeof(double) * ((size_t)U.n * L->itg * L->itp + (size_t)n_terms * L->itg);
+    const size_t per_wave = sizeof(double) * op_wave_doubles((size_t)U.n * L->itg * L->itp + (size_t)n_terms * L->itg);
     if (g_op_wave_forms && L->itp >= g_op_wave_min_itp && L->itp <= 64 && n_terms <= 64 && per_wave * 4 <= 80 * 1024 && n_threads >= (g_op_wave_forms == 2 ? 1 : 256)) {
       const size_t ldsb = per_wave * 4;
       const int per_cu = (int)(160 * 1024 / ldsb);
+      ++g_op_res_wave_count;
       return for_each_batch(L, n_threads, [&](int64_t a, int64_t b) -> int {
         int grid = (int)((b - a + 3) / 4);
         const int cap = ctx->num_cus * (per_cu < 1 ? 1 : per_cu > 4 ? 4 : per_cu);
@@ -609,10 +616,11 @@ extern "C" int mfem_op_var_batch(mfem_context ctx, const mfem_op_layout* L, cons
       sd_hi = terms[i].sd > sd_hi ? terms[i].sd : sd_hi;
     }
     const SlabUse U{sd_lo, sd_hi - sd_lo + 1};
-    const size_t per_wave = sizeof(double) * ((size_t)U.n * L->itg * L->itp + (size_t)n_terms * L->itp);
+    const size_t per_wave = sizeof(double) * op_wave_doubles((size_t)U.n * L->itg * L->itp + (size_t)n_terms * L->itp);
     if (g_op_wave_forms && L->itp >= g_op_wave_min_itp && L->itg <= 64 && n_terms <= 64 && per_wave * 4 <= 80 * 1024 && n_threads >= (g_op_wave_forms == 2 ? 1 : 256)) {
       const size_t ldsb = per_wave * 4;
       const int per_cu = (int)(160 * 1024 / ldsb);
+      ++g_op_var_wave_count;
       int gridw = (int)((n_threads + 3) / 4);
       const int cap = ctx->num_cus * (per_cu < 1 ? 1 : per_cu > 4 ? 4 : per_cu);
       if (gridw > cap) gridw = cap;
