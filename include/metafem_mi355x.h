@@ -150,7 +150,8 @@ typedef enum {
   MFEM_SOLVER_CG = 0,          /* added (not in the reference, F5); symmetric definite K only */
   MFEM_SOLVER_BICGSTABL_GS = 1,/* bicgstabl_GS!  linear_solver/03_BiCGstabl.jl:18-96 */
   MFEM_SOLVER_IDRS = 2,        /* idrs!          linear_solver/04_IDRs.jl:26-95 */
-  MFEM_SOLVER_CGS2 = 3         /* cgs2!          linear_solver/07_CGS.jl:54-105 */
+  MFEM_SOLVER_CGS2 = 3,        /* cgs2!          linear_solver/07_CGS.jl:54-105 */
+  MFEM_SOLVER_GMRES = 4        /* gmres!         linear_solver/05_GMRES.jl:48-100 (one rank only) */
 } mfem_solver_kind;
 
 typedef enum {
@@ -168,7 +169,7 @@ typedef enum {
 typedef struct {
   int32_t method;        /* mfem_solver_kind */
   int32_t precond;       /* mfem_precond_kind.  For CG, JACOBI_* means M = |diag K| (standard PCG). */
-  int32_t l_or_s;        /* `s` kwarg: BiCGStab l (default 2) / IDR s (default 4) */
+  int32_t l_or_s;        /* `s` kwarg: BiCGStab l (default 2) / IDR s (default 4) / GMRES restart length (default 20); at most 32 */
   int32_t maxiter;       /* per pass */
   int32_t max_pass;      /* restart passes, iterative_Solve! default 4 */
   int32_t check_every;   /* host polls the device convergence flag every this many iterations (>=1) */

@@ -84,6 +84,9 @@ int mfem_debug_graph_comm_count(void);
 /* bicgstabl_GS!: 1 = the literal operation sequence of 03_BiCGstabl.jl:41-94 (one pass over the vectors per dot product and per update) instead of the
  * fused form (dot products produced by the SpMVs, the minimal-residual part on the Gram matrix of R[0..l], the updates of a sweep in one kernel). */
 /* ^ key "bicgstabl": mfem_debug_set("bicgstabl", a, b) with (int literal_sequence) = (a[, b]) */
+/* gmres!: 1 = the reference's modified Gram-Schmidt order of 05_GMRES.jl:65-68 (one dot product, then one update, per basis vector) instead of
+ * classical Gram-Schmidt applied twice (two block dot products and two fused updates per Arnoldi step): the same numbers in exact arithmetic. */
+/* ^ key "gmres": mfem_debug_set("gmres", a, b) with (int literal_mgs) = (a[, b]) */
 /* persistent workgroups per CU of the streaming vector kernels (axpy family, fused CG updates, dots); default 3. */
 /* ^ key "vec_grid": mfem_debug_set("vec_grid", a, b) with (int workgroups_per_cu) = (a[, b]) */
 /* Multi-rank SpMV: 1 (default) the halo exchange runs on a second stream beside the rows that read no ghost column and the

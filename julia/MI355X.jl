@@ -57,7 +57,7 @@ ctx() = (isassigned(CTX) || (CTX[] = Context(0)); CTX[].h)
 
 # ---- struct mirrors of include/metafem_mi355x.h (isbits, C layout) ---------------------------------------------------------
 Base.@kwdef struct SolveOptions           # == mfem_solve_options
-    method::Int32 = 2                     # 0 cg (new), 1 bicgstabl_GS!, 2 idrs!, 3 cgs2!
+    method::Int32 = 2                     # 0 cg (new), 1 bicgstabl_GS!, 2 idrs!, 3 cgs2!, 4 gmres!
     precond::Int32 = 1                    # 0 Identity, 1 Pr_Jacobi!, 2 Pr_Jacobi!(normalized_by_column = true)
     l_or_s::Int32 = 0                     # the `s` kwarg
     maxiter::Int32 = 2000
@@ -196,7 +196,7 @@ function FEM_rand!(x::ROCVector{Float64}; seed::UInt64 = 0x5EED, stream_id::Inte
 end
 
 # ---- S1: the linear-solver seam --------------------------------------------------------------------------------------------
-const SOLVER_ID = Dict(:cg! => 0, :bicgstabl_GS! => 1, :idrs! => 2, :cgs2! => 3)
+const SOLVER_ID = Dict(:cg! => 0, :bicgstabl_GS! => 1, :idrs! => 2, :cgs2! => 3, :gmres! => 4)
 const PR_ID = Dict(:Identity => 0, :Pr_Jacobi! => 1)      # (install! passes nameof(Pr_func!))
 const PL_ID = Dict(:Identity => 0, :Pl_Jacobi => 1)      # cylinder_flow/3D_MetaFEM_Script.jl:90 passes Pl_func = Pl_Jacobi
 

@@ -31,10 +31,10 @@ from ._lib import (ElasticityParams, MetaFEMError, OpLayout, SolveOptions, Solve
 
 __all__ = ["Context", "FEM_SpMat_CSR", "mul_", "dot", "nrm2", "axpby_", "FEM_rand", "normalized_norm",
            "iterative_Solve", "Brick", "make_Brick", "ThermalDomain", "MetaFEMError", "SolveStats",
-           "cg_", "bicgstabl_GS_", "idrs_", "cgs2_", "FACE_BITS"]
+           "cg_", "bicgstabl_GS_", "idrs_", "cgs2_", "gmres_", "FACE_BITS"]
 
 # solver / preconditioner selectors (the reference passes Julia functions: Sv_func! = idrs! ...)
-cg_, bicgstabl_GS_, idrs_, cgs2_ = 0, 1, 2, 3
+cg_, bicgstabl_GS_, idrs_, cgs2_, gmres_ = 0, 1, 2, 3, 4
 Identity, Pr_Jacobi_, Pr_Jacobi_colnorm_ = 0, 1, 2
 Pl_Jacobi_, Pl_Jacobi_rownorm_ = 1, 2  # Pl_func selectors (02_Preconditioner.jl:155-168)
 
@@ -239,6 +239,8 @@ def iterative_Solve(A: FEM_SpMat_CSR, K_vals: torch.Tensor, residue: torch.Tenso
                     scale_in_place: bool = False, shadow: Optional[torch.Tensor] = None, cg_variant: int = 0
                     ) -> Tuple[torch.Tensor, SolveStats]:
     """iterative_Solve!(globalfield; Sv_func!, Pr_func!, Pl_func, max_pass, maxiter, s) (02_Preconditioner.jl:32-76).
+    Sv_func: cg_ (added), bicgstabl_GS_ (03_BiCGstabl.jl), idrs_ (04_IDRs.jl), cgs2_ (07_CGS.jl) or gmres_ (05_GMRES.jl:48-100: restarted
+    GMRES, one rank only).  s: BiCGStab l (0: 2), IDR s (0: 4) or the GMRES restart length (0: 20, the reference's default); at most 32.
     Pl_func: Identity, Pl_Jacobi_ (:155-168) or Pl_Jacobi_rownorm_ (normalized_by_row = true).
     cg_variant (cg_ only): 0 auto, 1 classic recurrence, 2 single reduction group per iteration (Chronopoulos-Gear), 3 classic
     recurrence carrying the preconditioned residual (one vector stream less per iteration), 4 plain CG on the symmetrically Jacobi-scaled

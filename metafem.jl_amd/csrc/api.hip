@@ -322,6 +322,7 @@ int mfem_debug_set_layout_min_rows(int64_t, int64_t);
 int mfem_debug_set_graphs(int, int64_t);
 int mfem_debug_set_idrs(int);
 int mfem_debug_set_bicgstabl(int);
+int mfem_debug_set_gmres(int);
 int mfem_debug_set_vec_grid(int);
 int mfem_debug_set_halo_overlap(int);
 int mfem_debug_set_hex27(int);
@@ -350,6 +351,7 @@ extern "C" int mfem_debug_set(const char* key, int64_t a, int64_t b) try {
   if (k == "graphs") return mfem_debug_set_graphs((int)a, b);
   if (k == "idrs") return mfem_debug_set_idrs((int)a);
   if (k == "bicgstabl") return mfem_debug_set_bicgstabl((int)a);
+  if (k == "gmres") return mfem_debug_set_gmres((int)a);
   if (k == "vec_grid") return mfem_debug_set_vec_grid((int)a);
   if (k == "halo_overlap") return mfem_debug_set_halo_overlap((int)a);
   if (k == "hex27") return mfem_debug_set_hex27((int)a);

@@ -51,6 +51,7 @@ struct KrylovVecs {
   double* w[3 * MFEM_MAX_S + 8];
   int nwork;
   bool x_zero = false;  // x is still the zero vector a solve starts from (x0 = 0, 02_Preconditioner.jl:45): the first pass's r = b - A x is b itself
+  double* gm = nullptr;  // gmres!: H, y and the block-dot partials (mfem_gmres_workspace_bytes)
 };
 
 int mfem_fill(mfem_context_s* ctx, int64_t n, double v, double* x);
@@ -68,6 +69,9 @@ int mfem_cgs2_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Krylo
                    double tol, int64_t n_global, int* iters_out, int* spmv_out);
 int mfem_idrs_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o,
                    int s, double tol, int64_t n_global, int* iters_out, int* spmv_out);
+int mfem_gmres_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o,
+                    int s, double tol, int64_t n_global, int* iters_out, int* spmv_out);
+size_t mfem_gmres_workspace_bytes();
 
 // ---- hipGraph replay of one solver cycle -------------------------------------------------------------------------
 // The Krylov drivers keep every recurrence scalar on the device and guard their kernels with the DONE flag, so the kernel

@@ -805,14 +805,16 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
                        const mfem_solve_options* o, mfem_solve_stats* stats, bool allow_lat, int64_t n_global_in) {
   MFEM_REQUIRE(A->n == 0 || (vals && b && x_out), "null array");
   MFEM_REQUIRE(o->maxiter >= 0 && o->max_pass >= 1, "maxiter >= 0 and max_pass >= 1 required");
-  MFEM_REQUIRE(o->method >= MFEM_SOLVER_CG && o->method <= MFEM_SOLVER_CGS2, "unknown method");
+  MFEM_REQUIRE(o->method >= MFEM_SOLVER_CG && o->method <= MFEM_SOLVER_GMRES, "unknown method");
   MFEM_REQUIRE(o->precond >= MFEM_PRECOND_NONE && o->precond <= MFEM_PRECOND_JACOBI_RIGHT_COLNORM, "unknown precond");
   MFEM_REQUIRE(o->left_precond >= MFEM_LEFT_NONE && o->left_precond <= MFEM_LEFT_JACOBI_ROWNORM, "unknown left_precond");
   MFEM_REQUIRE(!(o->left_precond && o->method == MFEM_SOLVER_CG), "left Jacobi would break the symmetry CG needs");
   if (stats) memset(stats, 0, sizeof(*stats));
   const int64_t n = A->n;
   if (n == 0) return MFEM_OK;
-  const int s_param = o->l_or_s > 0 ? o->l_or_s : (o->method == MFEM_SOLVER_IDRS ? 4 : 2);
+  // gmres!: s = 20 by default (05_GMRES.jl:48).  No multi-rank form: it would need an all-reduce of up to s + 1 scalars per orthogonalisation pass
+  MFEM_REQUIRE(!(o->method == MFEM_SOLVER_GMRES && ctx->comm), "gmres! runs on one rank only: no communicator may be attached");
+  const int s_param = o->l_or_s > 0 ? o->l_or_s : (o->method == MFEM_SOLVER_IDRS ? 4 : o->method == MFEM_SOLVER_GMRES ? 20 : 2);
   MFEM_REQUIRE(o->cg_variant >= 0 && o->cg_variant <= 4, "cg_variant must be 0 (auto), 1 (classic), 2 (single reduction), 3 (classic, preconditioned residual carried) or 4 (plain CG on the symmetrically scaled matrix)");
   // rows of the whole system (one all-reduce per solve with a communicator: every rank must take the same decisions below)
   int64_t n_global = n_global_in >= 0 ? n_global_in : n;
@@ -842,6 +844,7 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
     case MFEM_SOLVER_BICGSTABL_GS: nwork = 2 * (s_param + 1) + 1; break;
     case MFEM_SOLVER_IDRS: nwork = 3 * s_param + 4; break;
     case MFEM_SOLVER_CGS2: nwork = 9; break;
+    case MFEM_SOLVER_GMRES: nwork = s_param + 2; break;  // r, Q_1 .. Q_(s+1)
   }
   const bool is_cg = o->method == MFEM_SOLVER_CG;
   const bool jac = o->precond != MFEM_PRECOND_NONE;
@@ -895,6 +898,8 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
   if (lat_bytes > layout_bytes) layout_bytes = lat_bytes;
   if (lat8_bytes > layout_bytes) layout_bytes = lat8_bytes;
   size_t total = vec_bytes * (4 + nwork) + csr_copy_bytes + layout_bytes;
+  const size_t gm_offset = align_up(total, 256);  // gmres!: H, y and the block-dot partials behind everything else
+  if (o->method == MFEM_SOLVER_GMRES) total = gm_offset + mfem_gmres_workspace_bytes();
   int rc = mfem_ws_reserve(ctx, total);
   if (rc) return rc;
   char* base = (char*)ctx->ws;
@@ -908,6 +913,7 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
   double* dinv_buf = (double*)(base + 3 * vec_bytes);
   for (int i = 0; i < nwork; ++i) V.w[i] = (double*)(base + (4 + i) * vec_bytes);
   V.nwork = nwork;
+  if (o->method == MFEM_SOLVER_GMRES) V.gm = (double*)(base + gm_offset);
   double* vals_work = vals;
   // right Jacobi scaling of a working copy: the scaling kernel writes the copy straight from the caller's values (no copy pass first)
   const bool scaled_copy = need_copy && jac && !is_cg;
@@ -1232,6 +1238,9 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
         break;
       case MFEM_SOLVER_CGS2:
         rc = mfem_cgs2_pass(ctx, A, vals_work, V, o, tol_factor * o->converge_tol, n_global, &it, &spmvs);
+        break;
+      case MFEM_SOLVER_GMRES:
+        rc = mfem_gmres_pass(ctx, A, vals_work, V, o, s_param, tol_factor * o->converge_tol, n_global, &it, &spmvs);
         break;
       default:
         mfem_set_error("unknown solver method %d", o->method);
