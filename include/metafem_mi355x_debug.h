@@ -76,6 +76,8 @@ double mfem_debug_lat8_asymmetry(mfem_csr A);
 /* ^ key "graphs": mfem_debug_set("graphs", a, b) with (int on, int64_t max_n) = (a[, b]) */
 /* cycles captured with a communicator attached so far (process-wide) */
 int mfem_debug_graph_comm_count(void);
+/* cycle graphs launched by mfem_solve so far (process-wide; the launch right after a capture counts too): 0 more after a solve = it ran as direct launches */
+long long mfem_debug_graph_launch_count(void);
 /* idrs!: 1 = the literal bi-orthogonalisation loop of 04_IDRs.jl:62-66 (k dependent dot products and 2 k vector updates per inner step) instead of
  * the merged form (one multi-dot pass, the alphas by forward substitution with M, one vector kernel): the same numbers in exact arithmetic.
  * Round 6 -- bits: 1 = the literal loop (above); 2 = shadow vectors as U(0,1) vectors from mfem_rand, streamed (the default until round 5; now P is the

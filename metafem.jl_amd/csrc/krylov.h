@@ -108,11 +108,13 @@ inline uint64_t mfem_csr_graph_key(uint64_t key, const mfem_csr_s* A) {
 
 extern std::atomic<int> mfem_graph_comm_broken;
 extern std::atomic<long long> mfem_graph_comm_captures;
+extern std::atomic<long long> mfem_graph_launches;
 template <class Body>
 inline int mfem_cycle_run(mfem_context_s* ctx, uint64_t key, Body body) {
   if (!ctx->graph_active) return body();
   for (int i = 0; i < MFEM_GRAPH_SLOTS; ++i)
     if (ctx->graph_exec[i] && ctx->graph_key[i] == key) {
+      ++mfem_graph_launches;
       MFEM_CHECK_HIP(hipGraphLaunch(ctx->graph_exec[i], ctx->stream));
       return MFEM_OK;
     }
@@ -156,6 +158,7 @@ inline int mfem_cycle_run(mfem_context_s* ctx, uint64_t key, Body body) {
   if (ctx->comm) ++mfem_graph_comm_captures;
   ctx->graph_exec[slot] = exec;
   ctx->graph_key[slot] = key;
+  ++mfem_graph_launches;
   MFEM_CHECK_HIP(hipGraphLaunch(exec, ctx->stream));
   return MFEM_OK;
 }

@@ -723,6 +723,7 @@ extern "C" int mfem_debug_set_cg_single_max_rows(int64_t rows) try {
 } MFEM_API_CATCH("mfem_debug_set_cg_single_max_rows")
 std::atomic<int> mfem_graph_comm_broken{0};    // a capture with RCCL calls failed once: never tried again in this process
 std::atomic<long long> mfem_graph_comm_captures{0};  // cycles captured with a communicator attached (tests)
+std::atomic<long long> mfem_graph_launches{0};       // cycle graphs launched, first launches after a capture included (tests)
 static std::atomic<int> g_graphs{1};             // hipGraph replay of solver cycles (mfem_debug_set_graphs)
 static std::atomic<int64_t> g_graph_max_n{4000000};  // above this size kernels are long enough that launch latency is hidden anyway
 // Cycle graphs WITH a communicator (round 6): off unless asked for -- MFEM_GRAPH_COMM=1 in the environment or bit 1 of
@@ -741,6 +742,7 @@ static bool graph_comm_wanted() {
   return v == 1;
 }
 extern "C" int mfem_debug_graph_comm_count(void) { return (int)mfem_graph_comm_captures; }
+extern "C" long long mfem_debug_graph_launch_count(void) { return mfem_graph_launches; }
 extern "C" int mfem_debug_set_graphs(int on, int64_t max_n) try {
   ++mfem_debug_epoch;
   g_graphs = (on & 1) ? 1 : 0;

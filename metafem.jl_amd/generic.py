@@ -200,7 +200,7 @@ class GenericDomain:
         self.x, self.dx, self.x_star, self.residue = z(nglob), z(nglob), z(nglob), z(n)
         self.K_linear = z(self.A.nnz)
         # K_total = K_linear + the nonlinear gradient terms (05_CodeGenerator.jl:282-283).  A form without nonlinear gradient terms never adds anything: its
-        # K_total IS K_linear (the same storage; the solver reads K, it does not scale it in place) -- no second nnz-sized array (15 GB for hex-20
+        # K_total IS K_linear (the same storage, unless K_total_private asks for a copy a solver may scale in place) -- no second nnz-sized array (15 GB for hex-20
         # elasticity at 96^3), no copy per Newton step
         self._K_total_aliases = not any(wf.nonlinear_gradients for wf in [domain_wf] + [b[-1] for b in boundaries])
         self.K_total = self.K_linear if self._K_total_aliases else z(self.A.nnz)
@@ -213,6 +213,11 @@ class GenericDomain:
         self.K_params = [1.0]  # static: alpha_0 * beta_0 (04_Time_Domain.jl:13-17)
         self.t, self.dt = 0.0, 1.0
         self.linear_solver: Optional[Callable] = None
+        # A linear_solver that writes into K_total -- iterative_Solve(..., scale_in_place=True) column-scales it (Pr_Jacobi!, 02_Preconditioner.jl:118)
+        # -- needs K_total_private = True when K_total aliases K_linear: K_total then gets storage of its own, filled from K_linear at every Newton
+        # iteration as the reference does (05_CodeGenerator.jl:282-283).  Otherwise the solve would scale K_linear itself and the next iteration of the
+        # step would solve with the scaled matrix.  Off by default, so that solvers that only read K keep the memory of the alias.
+        self.K_total_private = False
         self.history: List[float] = []
 
     # -- assemble_X! / dessemble_X! (03_GlobalAssembly.jl:44-75)
@@ -409,7 +414,9 @@ class GenericDomain:
 
     def K_nonlinear_func(self):
         self.residue.zero_()
-        if not self._K_total_aliases:
+        if self.K_total_private and self.K_total is self.K_linear:
+            self.K_total = torch.empty_like(self.K_linear)
+        if self.K_total is not self.K_linear:
             self.K_total.copy_(self.K_linear)  # 05_CodeGenerator.jl:282-283
         for wf, g in self._parts():
             env: dict = {}

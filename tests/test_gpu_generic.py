@@ -464,3 +464,45 @@ def test_wave_forms_of_the_batched_operators_on_small_meshes(mf, case):
     assert np.abs(od.residue).max() > 0
     assert np.abs(got - od.residue).max() <= 1e-11 * np.abs(od.residue).max()
 
+
+
+@pytest.mark.parametrize("private", [False, True])
+def test_scale_in_place_solver_sees_the_unscaled_matrix_at_every_newton_iteration(mf, private):
+    """A linear form keeps K_total as K_linear's storage.  A solver that column-scales K_total in place (iterative_Solve(..., scale_in_place=True),
+    Pr_Jacobi!) would hand the next Newton iteration of the step a scaled matrix; the reference re-copies K_total from K_linear at every iteration
+    (05_CodeGenerator.jl:282-283).  With K_total_private the domain does the same, and the step follows the oracle's: a few fixed BiCGStab(2) sweeps per
+    Newton iteration, so that Newton needs several iterations.  The default keeps the alias (no second nnz-sized array)."""
+    import torch
+    from oracle import fem, mesh as om, problems, reference_element as re_, solvers
+
+    n = (7, 6, 5)
+    disc = re_.initialize_classical_element(3, "CUBE", 1, 1, 3)
+    msh = om.lattice_mesh((1.0, 1.0, 1.0), n, disc)
+    fac = om.boundary_facets_structured((1.0, 1.0, 1.0), n, 3)
+    od = fem.FEMDomain(msh, disc, 1, problems.thermal_domain(3, 0.6), [(fac, problems.thermal_convection(25.0, 293.15))])
+    od.controlpoints["s"] = np.full(msh.ncp, 1600.0)
+    od.converge_tol = 1e-9
+    od.linear_solver = lambda d: solvers.iterative_solve(d.pattern.rowptr, d.pattern.colidx, d.K_total, d.residue, 1e-300,
+                                                         Sv_func=solvers.bicgstabl_gs, maxiter=7, max_pass=1, s=2, seed=3)
+    hist_o = od.update_one_step(max_iter=4)
+
+    gd = _gpu_domain(mf, od, "Lagrange", 1, 3)
+    gd.controlpoints["s"] = torch.full((msh.ncp,), 1600.0, dtype=torch.float64, device="cuda")
+    gd.converge_tol = 1e-9
+    gd.K_total_private = private
+    gd.linear_solver = lambda g: mf.iterative_Solve(g.A, g.K_total, g.residue, 1e-300, Sv_func=mf.bicgstabl_GS_, maxiter=7, max_pass=1, s=2, seed=3,
+                                                    scale_in_place=True)[0]
+    assert gd.K_total is gd.K_linear  # a linear form: no storage of its own until a solve asks for it
+    hist = gd.update_OneStep(max_iter=4)
+    assert len(hist_o) >= 3 and hist_o[1] > od.converge_tol  # the linear solves are incomplete: Newton iterates
+    if not private:
+        # the alias: the first solve column-scaled K_linear itself, the second iteration solved with K D^-1 and the step left the oracle's path
+        assert gd.K_total is gd.K_linear
+        assert len(hist) != len(hist_o) or not np.allclose(hist, hist_o, rtol=1e-6)
+        return
+    assert gd.K_total is not gd.K_linear
+    assert np.allclose(gd.K_linear.cpu().numpy(), od.K_linear, rtol=0, atol=1e-12 * np.abs(od.K_linear).max())  # K_linear is never scaled
+    assert len(hist) == len(hist_o)
+    assert np.allclose(hist, hist_o, rtol=1e-8, atol=1e-12 * hist_o[0])
+    x = gd.x.cpu().numpy()
+    assert np.abs(x - od.x).max() <= 1e-9 * np.abs(od.x).max()
