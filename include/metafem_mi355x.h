@@ -79,6 +79,13 @@ int mfem_csr_replan(mfem_context ctx, mfem_csr A);
 /* y = alpha*A*x + beta*y : mul!(b, A, x, alpha, beta), misc/04_GPU_Utils.jl:131 (CUSPARSE mv! 'N'). */
 int mfem_spmv_csr(mfem_context ctx, mfem_csr A, const double* vals, const double* x, double* y,
                   double alpha, double beta);
+/* y = alpha*A'*x + beta*y : tmul!(y, A, x), misc/04_GPU_Utils.jl:132 (CUSPARSE mv! 'T').  x has n entries, y has ncols (mfem_csr_ncols).
+ * Deterministic (no floating-point atomics): the first call transposes the pattern on the device (a stable sort: every transposed row
+ * lists its entries in increasing row order of A) and caches the plan on the handle -- (ncols + 1) * 8 + nnz * 8 bytes below 2^31
+ * entries (nnz * 12 above), plus an nnz * 8 value buffer this call gathers `vals` into; mfem_csr_replan and mfem_csr_destroy drop it.
+ * Any index_base, 32- or 64-bit rowptr, unsorted columns, patterns that are not structurally symmetric.  Repeated calls are bitwise identical. */
+int mfem_spmv_csr_t(mfem_context ctx, mfem_csr A, const double* vals, const double* x, double* y,
+                    double alpha, double beta);
 /* y = a*x + b*y  (the broadcast axpy family of every solver body, e.g. 03_BiCGstabl.jl:50,57). */
 int mfem_axpby(mfem_context ctx, int64_t n, double a, const double* x, double b, double* y);
 /* *out [host] = sum x_i*y_i  (LinearAlgebra.dot on CuArray -> CUBLAS dot; 03_BiCGstabl.jl:45). */
@@ -151,8 +158,21 @@ typedef enum {
   MFEM_SOLVER_BICGSTABL_GS = 1,/* bicgstabl_GS!  linear_solver/03_BiCGstabl.jl:18-96 */
   MFEM_SOLVER_IDRS = 2,        /* idrs!          linear_solver/04_IDRs.jl:26-95 */
   MFEM_SOLVER_CGS2 = 3,        /* cgs2!          linear_solver/07_CGS.jl:54-105 */
-  MFEM_SOLVER_GMRES = 4        /* gmres!         linear_solver/05_GMRES.jl:48-100 (one rank only) */
+  MFEM_SOLVER_GMRES = 4,       /* gmres!         linear_solver/05_GMRES.jl:48-100 (one rank only) */
+  MFEM_SOLVER_CGS = 5,         /* cgs!           linear_solver/07_CGS.jl:13-52 (one rank only) */
+  MFEM_SOLVER_TFQMR = 6,       /* tfqmr!         linear_solver/08_QMR.jl:3-74 (one rank only; checkiter in l_or_s) */
+  MFEM_SOLVER_LSQR = 7         /* lsqr!          linear_solver/06_LSQR.jl:10-70 (one rank only; uses A', see mfem_spmv_csr_t) */
 } mfem_solver_kind;
+/* mfem_solve_stats.spmv_count per pass of the three solvers above, it = the pass's returned iteration count (>= 1), x0 = [x != 0 at the
+ * start of the pass] (the first pass starts from r = b: 0), +1 for the true residual the restart wrapper computes after every pass:
+ *   cgs!    x0 + 2 (it - 1) + 1                      (A u and the true residual b - A x of every iteration, :45-47)
+ *   tfqmr!  x0 + 1 + 2 (it - 1) + checks + 1         (A p at the start; A v and A p per iteration; checks = the iterations 2 .. it with
+ *                                                    iter % checkiter == 0 and iter <= maxiter, each one true residual; none with
+ *                                                    fixed_iterations)
+ *   lsqr!   x0 + 1 + sum over the it - 1 iterations of (2 + [beta != 0]) + 1   (A' u at the start; A v, A' u unless beta == 0, the true
+ *                                                    residual per iteration: transposed products count like the others)
+ * A pass that finds r converged at once (it = 0) counts x0 + 1.  A solve on the symmetric lattice tiles (modes 4 and 5) adds one product per
+ * recheck of its residual on the caller's CSR values (one for a single pass). */
 
 typedef enum {
   MFEM_PRECOND_NONE = 0,            /* Identity, 02_Preconditioner.jl:78-86 */
@@ -169,7 +189,9 @@ typedef enum {
 typedef struct {
   int32_t method;        /* mfem_solver_kind */
   int32_t precond;       /* mfem_precond_kind.  For CG, JACOBI_* means M = |diag K| (standard PCG). */
-  int32_t l_or_s;        /* `s` kwarg: BiCGStab l (default 2) / IDR s (default 4) / GMRES restart length (default 20); at most 32 */
+  int32_t l_or_s;        /* `s` kwarg: BiCGStab l (default 2) / IDR s (default 4) / GMRES restart length (default 20); at most 32.
+                            tfqmr!: `checkiter` (default 200, any positive value): the true residual is tested every checkiter iterations.
+                            Ignored by cgs2!, cgs! and lsqr! (and by cg!). */
   int32_t maxiter;       /* per pass */
   int32_t max_pass;      /* restart passes, iterative_Solve! default 4 */
   int32_t check_every;   /* host polls the device convergence flag every this many iterations (>=1) */

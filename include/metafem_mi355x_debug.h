@@ -221,6 +221,9 @@ long long mfem_debug_bsell_spmv_count(void);
 /* ^ key "mesh_abl": mfem_debug_set("mesh_abl", a, b) with (int bits) = (a[, b]) */
 int mfem_debug_remainder_info(mfem_csr A, int64_t* rows /* [host] */, int64_t* entries /* [host] */, double* asym_before /* [host] */);
 long long mfem_debug_rem_spmv_count(void);
+/* The transpose plan of mfem_spmv_csr_t / lsqr! (spmv_t.hip): returns 1 if the pattern holds one (bytes = its device bytes, build_ms = the host
+ * time its build took, synchronised), 0 if not (both 0). */
+int mfem_debug_csr_tplan(mfem_csr A, int64_t* bytes /* [host] */, double* build_ms /* [host] */);
 
 #ifdef __cplusplus
 }

@@ -9,7 +9,7 @@
 # What it replaces (SURVEY.md section 8b):
 #   S1  fem_domain.linear_solver(globalfield)          solver/01_Types.jl:166, called solver/04_Time_Domain.jl:76
 #       -> iterative_Solve!(gf; Sv_func!, Pl_func, ...) linear_solver/02_Preconditioner.jl:32-76          => mfem_solve
-#       mul! / dot / norm / FEM_rand                    misc/04_GPU_Utils.jl:131,22; LinearAlgebra         => mfem_spmv_csr, mfem_dot, ...
+#       mul! / tmul! / dot / norm / FEM_rand            misc/04_GPU_Utils.jl:131,132,22; LinearAlgebra     => mfem_spmv_csr, mfem_spmv_csr_t, mfem_dot, ...
 #   S2  K_linear_func / K_nonlinear_func closures       solver/01_Types.jl:164-165 (assigned 05_CodeGenerator.jl:287-288)
 #                                                                                                          => mfem_brick_assemble_* / _residual_*
 #   S3  _Var_Basic / _Kval_Basic / _Res_Basic           solver/06_FEM_Kernel.jl:1,28,65                    => mfem_op_var / _kval / _res
@@ -57,9 +57,9 @@ ctx() = (isassigned(CTX) || (CTX[] = Context(0)); CTX[].h)
 
 # ---- struct mirrors of include/metafem_mi355x.h (isbits, C layout) ---------------------------------------------------------
 Base.@kwdef struct SolveOptions           # == mfem_solve_options
-    method::Int32 = 2                     # 0 cg (new), 1 bicgstabl_GS!, 2 idrs!, 3 cgs2!, 4 gmres!
+    method::Int32 = 2                     # 0 cg (new), 1 bicgstabl_GS!, 2 idrs!, 3 cgs2!, 4 gmres!, 5 cgs!, 6 tfqmr!, 7 lsqr!
     precond::Int32 = 1                    # 0 Identity, 1 Pr_Jacobi!, 2 Pr_Jacobi!(normalized_by_column = true)
-    l_or_s::Int32 = 0                     # the `s` kwarg
+    l_or_s::Int32 = 0                     # the `s` kwarg (tfqmr!: checkiter)
     maxiter::Int32 = 2000
     max_pass::Int32 = 4
     check_every::Int32 = 32
@@ -174,6 +174,13 @@ function mul!(b::ROCVector{Float64}, M::SpMat_CSR, x::ROCVector{Float64}, alpha:
     return b
 end
 
+"tmul!(b, A, x): b = A'*x  (misc/04_GPU_Utils.jl:132, CUSPARSE mv! 'T'); b has the pattern's ncols entries."
+function tmul!(b::ROCVector{Float64}, M::SpMat_CSR, x::ROCVector{Float64}, alpha::Number = 1.0, beta::Number = 0.0)
+    check(ccall((:mfem_spmv_csr_t, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64),
+                ctx(), M.A.h, dptr(M.vals), dptr(x), dptr(b), Float64(alpha), Float64(beta)))
+    return b
+end
+
 function dot(x::ROCVector{Float64}, y::ROCVector{Float64})
     out = Ref{Float64}(0.0)
     check(ccall((:mfem_dot, lib), Cint, (Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ref{Float64}), ctx(), length(x), dptr(x), dptr(y), out))
@@ -196,12 +203,13 @@ function FEM_rand!(x::ROCVector{Float64}; seed::UInt64 = 0x5EED, stream_id::Inte
 end
 
 # ---- S1: the linear-solver seam --------------------------------------------------------------------------------------------
-const SOLVER_ID = Dict(:cg! => 0, :bicgstabl_GS! => 1, :idrs! => 2, :cgs2! => 3, :gmres! => 4)
+const SOLVER_ID = Dict(:cg! => 0, :bicgstabl_GS! => 1, :idrs! => 2, :cgs2! => 3, :gmres! => 4, :cgs! => 5, :tfqmr! => 6, :lsqr! => 7)
 const PR_ID = Dict(:Identity => 0, :Pr_Jacobi! => 1)      # (install! passes nameof(Pr_func!))
 const PL_ID = Dict(:Identity => 0, :Pl_Jacobi => 1)      # cylinder_flow/3D_MetaFEM_Script.jl:90 passes Pl_func = Pl_Jacobi
 
 """
-    iterative_Solve!(globalfield; Sv_func! = :idrs!, Pr_func! = :Pr_Jacobi!, Pl_func = :Identity, max_pass = 4, maxiter = 2000, s = 0)
+    iterative_Solve!(globalfield; Sv_func! = :idrs!, Pr_func! = :Pr_Jacobi!, Pl_func = :Identity, max_pass = 4, maxiter = 2000, s = 0,
+                     checkiter = 200)
 
 Same contract as linear_solver/02_Preconditioner.jl:32-76: reads `basicfield_size, K_J_ptr, K_J, K_val_ids, K_total, residue,
 converge_tol`, returns a NEW device vector (x0 = 0, right-Jacobi un-scaled at exit, up to `max_pass` restarts with the true residual
@@ -209,7 +217,8 @@ recomputed in between, absolute tolerance on norm(r)/sqrt(n)).  Install with
 `fem_domain.linear_solver = gf -> MI355X.iterative_Solve!(gf; Sv_func! = :idrs!, maxiter = 2000, max_pass = 10, s = 8)`.
 """
 function iterative_Solve!(gf; Sv_func!::Symbol = :idrs!, Pr_func!::Symbol = :Pr_Jacobi!, Pl_func::Symbol = :Identity,
-                          max_pass = 4, maxiter = 2000, s = 0, normalized_by_column::Bool = false, seed::UInt64 = 0x5EED)
+                          max_pass = 4, maxiter = 2000, s = 0, normalized_by_column::Bool = false, seed::UInt64 = 0x5EED,
+                          checkiter::Integer = 200)
     n = gf.basicfield_size
     A = get!(PATTERNS, objectid(gf.K_J_ptr)) do       # one handle per assemble_Global_Variables! (the arrays are written once)
         CSRPattern(gf.K_J_ptr, gf.K_J, n)
@@ -219,7 +228,8 @@ function iterative_Solve!(gf; Sv_func!::Symbol = :idrs!, Pr_func!::Symbol = :Pr_
     K_vals = gf.K_val_ids isa UnitRange ? gf.K_total : gf.K_total[gf.K_val_ids]
     x = AMDGPU.zeros(Float64, n)
     pr = Pr_func! == :Pr_Jacobi! ? (normalized_by_column ? 2 : 1) : 0
-    opts = Ref(SolveOptions(method = SOLVER_ID[Sv_func!], precond = pr, l_or_s = s, maxiter = maxiter, max_pass = max_pass,
+    l_or_s = Sv_func! == :tfqmr! ? checkiter : s        # tfqmr! (08_QMR.jl:4) carries checkiter where the others carry s
+    opts = Ref(SolveOptions(method = SOLVER_ID[Sv_func!], precond = pr, l_or_s = l_or_s, maxiter = maxiter, max_pass = max_pass,
                             converge_tol = gf.converge_tol, seed = seed, left_precond = PL_ID[Pl_func]))
     stats = Ref{SolveStats}()
     check(ccall((:mfem_solve, lib), Cint,

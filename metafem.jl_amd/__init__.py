@@ -29,12 +29,12 @@ import torch
 from . import _lib
 from ._lib import (ElasticityParams, MetaFEMError, OpLayout, SolveOptions, SolveStats, ThermalParams, check, lib)
 
-__all__ = ["Context", "FEM_SpMat_CSR", "mul_", "dot", "nrm2", "axpby_", "FEM_rand", "normalized_norm",
+__all__ = ["Context", "FEM_SpMat_CSR", "mul_", "tmul_", "dot", "nrm2", "axpby_", "FEM_rand", "normalized_norm",
            "iterative_Solve", "Brick", "make_Brick", "ThermalDomain", "MetaFEMError", "SolveStats",
-           "cg_", "bicgstabl_GS_", "idrs_", "cgs2_", "gmres_", "FACE_BITS"]
+           "cg_", "bicgstabl_GS_", "idrs_", "cgs2_", "gmres_", "cgs_", "tfqmr_", "lsqr_", "FACE_BITS"]
 
 # solver / preconditioner selectors (the reference passes Julia functions: Sv_func! = idrs! ...)
-cg_, bicgstabl_GS_, idrs_, cgs2_, gmres_ = 0, 1, 2, 3, 4
+cg_, bicgstabl_GS_, idrs_, cgs2_, gmres_, cgs_, tfqmr_, lsqr_ = 0, 1, 2, 3, 4, 5, 6, 7
 Identity, Pr_Jacobi_, Pr_Jacobi_colnorm_ = 0, 1, 2
 Pl_Jacobi_, Pl_Jacobi_rownorm_ = 1, 2  # Pl_func selectors (02_Preconditioner.jl:155-168)
 
@@ -168,6 +168,16 @@ def mul_(b: torch.Tensor, A: FEM_SpMat_CSR, vals: torch.Tensor, x: torch.Tensor,
     return b
 
 
+def tmul_(b: torch.Tensor, A: FEM_SpMat_CSR, vals: torch.Tensor, x: torch.Tensor, alpha: float = 1.0, beta: float = 0.0):
+    """tmul!(b, A, x): b = alpha*A'*x + beta*b (04_GPU_Utils.jl:132, CUSPARSE mv! 'T').  x has A.n entries, b has A.ncols.
+    The first call transposes the pattern on the device and caches the plan on the handle (replan() drops it)."""
+    _need(vals, torch.float64, "vals", A.nnz)
+    _need(x, torch.float64, "x", A.n)
+    _need(b, torch.float64, "b", A.ncols)
+    check(lib.mfem_spmv_csr_t(A.ctx._h, A._h, _ptr(vals), _ptr(x), _ptr(b), alpha, beta))
+    return b
+
+
 def dot(x: torch.Tensor, y: torch.Tensor, ctx: Optional[Context] = None) -> float:
     ctx = ctx or default_context()
     _need(x, torch.float64, "x")
@@ -236,11 +246,13 @@ def iterative_Solve(A: FEM_SpMat_CSR, K_vals: torch.Tensor, residue: torch.Tenso
                     Sv_func: int = idrs_, Pr_func: int = Pr_Jacobi_, Pl_func: int = Identity, max_pass: int = 4,
                     maxiter: int = 2000,
                     s: int = 0, seed: int = 0x5EED, check_every: int = 32, fixed_iterations: bool = False,
-                    scale_in_place: bool = False, shadow: Optional[torch.Tensor] = None, cg_variant: int = 0
-                    ) -> Tuple[torch.Tensor, SolveStats]:
+                    scale_in_place: bool = False, shadow: Optional[torch.Tensor] = None, cg_variant: int = 0,
+                    checkiter: int = 200) -> Tuple[torch.Tensor, SolveStats]:
     """iterative_Solve!(globalfield; Sv_func!, Pr_func!, Pl_func, max_pass, maxiter, s) (02_Preconditioner.jl:32-76).
-    Sv_func: cg_ (added), bicgstabl_GS_ (03_BiCGstabl.jl), idrs_ (04_IDRs.jl), cgs2_ (07_CGS.jl) or gmres_ (05_GMRES.jl:48-100: restarted
-    GMRES, one rank only).  s: BiCGStab l (0: 2), IDR s (0: 4) or the GMRES restart length (0: 20, the reference's default); at most 32.
+    Sv_func: cg_ (added), bicgstabl_GS_ (03_BiCGstabl.jl), idrs_ (04_IDRs.jl), cgs2_ (07_CGS.jl:54-105), gmres_ (05_GMRES.jl:48-100: restarted
+    GMRES), cgs_ (07_CGS.jl:13-52), tfqmr_ (08_QMR.jl:3-74) or lsqr_ (06_LSQR.jl:10-70: products with A and A'); the last four on one
+    rank only.  s: BiCGStab l (0: 2), IDR s (0: 4) or the GMRES restart length (0: 20, the reference's default); at most 32.
+    checkiter (tfqmr_ only, the reference's kwarg, default 200): the true residual is tested every checkiter iterations.
     Pl_func: Identity, Pl_Jacobi_ (:155-168) or Pl_Jacobi_rownorm_ (normalized_by_row = true).
     cg_variant (cg_ only): 0 auto, 1 classic recurrence, 2 single reduction group per iteration (Chronopoulos-Gear), 3 classic
     recurrence carrying the preconditioned residual (one vector stream less per iteration), 4 plain CG on the symmetrically Jacobi-scaled
@@ -251,6 +263,10 @@ def iterative_Solve(A: FEM_SpMat_CSR, K_vals: torch.Tensor, residue: torch.Tenso
     _need(K_vals, torch.float64, "K_vals", A.nnz)
     _need(residue, torch.float64, "residue", A.n)
     x = torch.empty(A.n, dtype=torch.float64, device=residue.device)
+    if Sv_func == tfqmr_:
+        if checkiter < 1:
+            raise MetaFEMError("checkiter must be >= 1")
+        s = checkiter
     o = SolveOptions(method=Sv_func, precond=Pr_func, l_or_s=s, maxiter=maxiter, max_pass=max_pass,
                      check_every=check_every, converge_tol=converge_tol, seed=seed,
                      fixed_iterations=1 if fixed_iterations else 0, scale_in_place=1 if scale_in_place else 0,

@@ -123,6 +123,7 @@ SIGNATURES = {
     "mfem_csr_create": (c_int, [P, c_int64, c_int64, P, c_int, P, c_int, C.POINTER(P)]),
     "mfem_csr_destroy": (c_int, [P]),
     "mfem_spmv_csr": (c_int, [P, P, P, P, P, c_double, c_double]),
+    "mfem_spmv_csr_t": (c_int, [P, P, P, P, P, c_double, c_double]),
     "mfem_axpby": (c_int, [P, c_int64, c_double, P, c_double, P]),
     "mfem_dot": (c_int, [P, c_int64, P, P, C.POINTER(c_double)]),
     "mfem_nrm2": (c_int, [P, c_int64, P, C.POINTER(c_double)]),
@@ -213,6 +214,7 @@ SIGNATURES = {
     "mfem_debug_ws_trial_log": (c_int, [P, C.POINTER(C.c_double)]),
     "mfem_debug_remainder_info": (c_int, [P, C.POINTER(c_int64), C.POINTER(c_int64), C.POINTER(C.c_double)]),
     "mfem_debug_rem_spmv_count": (C.c_longlong, []),
+    "mfem_debug_csr_tplan": (c_int, [P, C.POINTER(c_int64), C.POINTER(C.c_double)]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

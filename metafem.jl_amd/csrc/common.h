@@ -238,7 +238,23 @@ struct mfem_csr_s {
   size_t rem_sort_bytes;
   double rem_asym_before;       // what the probe measured on the tiles alone (the asymmetry the remainder repairs)
   int64_t rem_last_rows, rem_last_ent;  // what the last ACCEPTED remainder of the last probe held (0: none) -- survives the unbind at the end of a solve (tests, bench.py)
+  // transposed pattern for A' x (spmv_t.hip): built by the first mfem_spmv_csr_t or lsqr! solve, dropped by replan / destroy
+  struct mfem_tplan_s* tplan;
 };
+// The transpose plan of a pattern (spmv_t.hip): AT is an internal CSR handle over the owned transposed arrays (rows = the columns of A,
+// int64 row pointers, 0-based), perm maps its slots to A's slots (int32 below 2^31 entries, int64 above).
+struct mfem_tplan_s {
+  mfem_csr_s* AT;
+  void* perm;
+  int perm_bits;
+  double* vals;      // values buffer of mfem_spmv_csr_t (allocated by its first call; lsqr! gathers into its workspace instead)
+  int64_t bytes;     // device bytes of the plan (row pointers, columns, perm)
+  double build_ms;   // host time of the build, synchronised
+};
+int mfem_tplan_get(mfem_context_s* ctx, mfem_csr_s* A, mfem_tplan_s** out);
+void mfem_tplan_free(mfem_csr_s* A);
+// valsT[k] = (src ? src[perm[k]] : valsT[k]) / d1[i] / d2[i] over the slots of transposed row i; d1, d2 may be null
+int mfem_tplan_gather(mfem_context_s* ctx, const mfem_tplan_s* P, const double* src, double* valsT, const double* d1, const double* d2);
 bool mfem_rem_enabled();
 bool mfem_rem_diag();
 void mfem_rem_clear(mfem_csr_s* A);

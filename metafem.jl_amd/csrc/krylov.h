@@ -52,6 +52,8 @@ struct KrylovVecs {
   int nwork;
   bool x_zero = false;  // x is still the zero vector a solve starts from (x0 = 0, 02_Preconditioner.jl:45): the first pass's r = b - A x is b itself
   double* gm = nullptr;  // gmres!: H, y and the block-dot partials (mfem_gmres_workspace_bytes)
+  mfem_csr_s* AT = nullptr;  // lsqr!: the transposed pattern (spmv_t.hip) and its working values Pl(A_r)' (mfem_solve)
+  double* valsT = nullptr;
 };
 
 int mfem_fill(mfem_context_s* ctx, int64_t n, double v, double* x);
@@ -72,6 +74,13 @@ int mfem_idrs_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Krylo
 int mfem_gmres_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o,
                     int s, double tol, int64_t n_global, int* iters_out, int* spmv_out);
 size_t mfem_gmres_workspace_bytes();
+// krylov_next.hip: cgs!, tfqmr! (checkiter = the l_or_s of the options, default 200), lsqr! (products with A' through V.AT / V.valsT)
+int mfem_cgs_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o,
+                  double tol, int64_t n_global, int* iters_out, int* spmv_out);
+int mfem_tfqmr_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o,
+                    int checkiter, double tol, int64_t n_global, int* iters_out, int* spmv_out);
+int mfem_lsqr_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o,
+                   double tol, int64_t n_global, int* iters_out, int* spmv_out);
 
 // ---- hipGraph replay of one solver cycle -------------------------------------------------------------------------
 // The Krylov drivers keep every recurrence scalar on the device and guard their kernels with the DONE flag, so the kernel

@@ -807,7 +807,7 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
                        const mfem_solve_options* o, mfem_solve_stats* stats, bool allow_lat, int64_t n_global_in) {
   MFEM_REQUIRE(A->n == 0 || (vals && b && x_out), "null array");
   MFEM_REQUIRE(o->maxiter >= 0 && o->max_pass >= 1, "maxiter >= 0 and max_pass >= 1 required");
-  MFEM_REQUIRE(o->method >= MFEM_SOLVER_CG && o->method <= MFEM_SOLVER_GMRES, "unknown method");
+  MFEM_REQUIRE(o->method >= MFEM_SOLVER_CG && o->method <= MFEM_SOLVER_LSQR, "unknown method");
   MFEM_REQUIRE(o->precond >= MFEM_PRECOND_NONE && o->precond <= MFEM_PRECOND_JACOBI_RIGHT_COLNORM, "unknown precond");
   MFEM_REQUIRE(o->left_precond >= MFEM_LEFT_NONE && o->left_precond <= MFEM_LEFT_JACOBI_ROWNORM, "unknown left_precond");
   MFEM_REQUIRE(!(o->left_precond && o->method == MFEM_SOLVER_CG), "left Jacobi would break the symmetry CG needs");
@@ -816,7 +816,12 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
   if (n == 0) return MFEM_OK;
   // gmres!: s = 20 by default (05_GMRES.jl:48).  No multi-rank form: it would need an all-reduce of up to s + 1 scalars per orthogonalisation pass
   MFEM_REQUIRE(!(o->method == MFEM_SOLVER_GMRES && ctx->comm), "gmres! runs on one rank only: no communicator may be attached");
-  const int s_param = o->l_or_s > 0 ? o->l_or_s : (o->method == MFEM_SOLVER_IDRS ? 4 : o->method == MFEM_SOLVER_GMRES ? 20 : 2);
+  // cgs!, tfqmr!, lsqr!: one rank as well (lsqr!'s transposed product would need the halo reduction of mfem_halo_reduce)
+  MFEM_REQUIRE(!(o->method >= MFEM_SOLVER_CGS && ctx->comm), "cgs!, tfqmr! and lsqr! run on one rank only: no communicator may be attached");
+  // tfqmr!: l_or_s carries checkiter, 200 by default (08_QMR.jl:4), not bounded by MFEM_MAX_S
+  const bool is_tfqmr = o->method == MFEM_SOLVER_TFQMR;
+  const int s_param = o->l_or_s > 0 ? o->l_or_s
+                                    : (o->method == MFEM_SOLVER_IDRS ? 4 : o->method == MFEM_SOLVER_GMRES ? 20 : is_tfqmr ? 200 : 2);
   MFEM_REQUIRE(o->cg_variant >= 0 && o->cg_variant <= 4, "cg_variant must be 0 (auto), 1 (classic), 2 (single reduction), 3 (classic, preconditioned residual carried) or 4 (plain CG on the symmetrically scaled matrix)");
   // rows of the whole system (one all-reduce per solve with a communicator: every rank must take the same decisions below)
   int64_t n_global = n_global_in >= 0 ? n_global_in : n;
@@ -836,7 +841,7 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
   const int world_ranks = mfem_comm_world(ctx);
   const bool cg_single = o->method == MFEM_SOLVER_CG &&
                          (o->cg_variant == 2 || (o->cg_variant == 0 && world_ranks > 1 && n_global / world_ranks < g_cg_single_max_rows));
-  MFEM_REQUIRE(s_param <= MFEM_MAX_S, "l_or_s too large");
+  MFEM_REQUIRE(is_tfqmr || s_param <= MFEM_MAX_S, "l_or_s too large");
   // x may carry ghost entries behind the owned rows (slab decomposition)
   const int64_t ghosts = ctx->comm ? 2 * ctx->halo_plane_len * ctx->halo_fields : 0;
   const int64_t nv = (int64_t)align_up((size_t)(n + ghosts), 32);  // padded vector length (even => d2 kernels)
@@ -847,6 +852,16 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
     case MFEM_SOLVER_IDRS: nwork = 3 * s_param + 4; break;
     case MFEM_SOLVER_CGS2: nwork = 9; break;
     case MFEM_SOLVER_GMRES: nwork = s_param + 2; break;  // r, Q_1 .. Q_(s+1)
+    case MFEM_SOLVER_CGS: nwork = 6; break;    // r, r0, u, p, s, v
+    case MFEM_SOLVER_TFQMR: nwork = 9; break;  // r, r0, r_cgs, p, q, u, v, d, tmp
+    case MFEM_SOLVER_LSQR: nwork = 5; break;   // r, u, v, w, tmp
+  }
+  // lsqr!: the transposed pattern, planned on the first lsqr! solve (or mfem_spmv_csr_t) and kept on the handle
+  const bool is_lsqr = o->method == MFEM_SOLVER_LSQR;
+  mfem_tplan_s* tplan = nullptr;
+  if (is_lsqr) {
+    const int rct = mfem_tplan_get(ctx, A, &tplan);
+    if (rct) return rct;
   }
   const bool is_cg = o->method == MFEM_SOLVER_CG;
   const bool jac = o->precond != MFEM_PRECOND_NONE;
@@ -902,6 +917,7 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
   size_t total = vec_bytes * (4 + nwork) + csr_copy_bytes + layout_bytes;
   const size_t gm_offset = align_up(total, 256);  // gmres!: H, y and the block-dot partials behind everything else
   if (o->method == MFEM_SOLVER_GMRES) total = gm_offset + mfem_gmres_workspace_bytes();
+  if (is_lsqr) total = gm_offset + (size_t)A->nnz * sizeof(double);  // lsqr!: the values of the transposed working matrix, behind everything else
   int rc = mfem_ws_reserve(ctx, total);
   if (rc) return rc;
   char* base = (char*)ctx->ws;
@@ -916,6 +932,10 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
   for (int i = 0; i < nwork; ++i) V.w[i] = (double*)(base + (4 + i) * vec_bytes);
   V.nwork = nwork;
   if (o->method == MFEM_SOLVER_GMRES) V.gm = (double*)(base + gm_offset);
+  if (is_lsqr) {
+    V.AT = tplan->AT;
+    V.valsT = (double*)(base + gm_offset);
+  }
   double* vals_work = vals;
   // right Jacobi scaling of a working copy: the scaling kernel writes the copy straight from the caller's values (no copy pass first)
   const bool scaled_copy = need_copy && jac && !is_cg;
@@ -926,6 +946,12 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
   const double* vals_src = scaled_copy ? vals : vals_work;  // what the scaling is computed from
   MFEM_CHECK_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   MFEM_CHECK_HIP(hipMemcpyAsync(V.b, b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  // lsqr!'s A' is built from the caller's values, not from the working matrix (see below).  scale_in_place overwrites them: gather them first.
+  const bool gather_early = is_lsqr && o->scale_in_place && (jac || left);
+  if (gather_early) {
+    rc = mfem_tplan_gather(ctx, tplan, vals, V.valsT, nullptr, nullptr);
+    if (rc) return rc;
+  }
 
   struct EllGuard {  // whatever gets bound below is released on every way out of this function
     mfem_csr_s* A;
@@ -1060,6 +1086,14 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
     if (rc) return rc;
     hipLaunchKernelGGL(k_div, dim3(mfem_vec_grid(ctx, n)), dim3(MFEM_BLOCK), 0, ctx->stream, n, V.b, dl, V.b);
     MFEM_CHECK_LAUNCH();
+  }
+  // lsqr!: the reference's v = Pl(tmul!(A_r, u)) (06_LSQR.jl:23-24, 42-43) is P A_r' u, A_r = A C the Pr_Jacobi!-scaled matrix (C = 1 / d) and
+  // P = 1 / dl the left scaling taken from A_r -- not the transpose of the row-scaled working matrix (P A_r)' = A_r' P.  Row i of the transposed
+  // working matrix is therefore (a(j, i) / d_i) / dl_i, gathered from the caller's values on every path: the fused-scale layouts keep no scaled
+  // CSR copy, the lattice tiles apply the right scaling to x, and scale_in_place has overwritten them (gathered above, divided here).
+  if (is_lsqr) {
+    rc = mfem_tplan_gather(ctx, tplan, gather_early ? nullptr : vals, V.valsT, jac ? V.d : nullptr, left ? dl : nullptr);
+    if (rc) return rc;
   }
 
   // bind the slot-major copy: every mfem_spmv_launch(A, vals_work, ...) below runs the ELL kernel
@@ -1243,6 +1277,15 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
         break;
       case MFEM_SOLVER_GMRES:
         rc = mfem_gmres_pass(ctx, A, vals_work, V, o, s_param, tol_factor * o->converge_tol, n_global, &it, &spmvs);
+        break;
+      case MFEM_SOLVER_CGS:
+        rc = mfem_cgs_pass(ctx, A, vals_work, V, o, tol_factor * o->converge_tol, n_global, &it, &spmvs);
+        break;
+      case MFEM_SOLVER_TFQMR:
+        rc = mfem_tfqmr_pass(ctx, A, vals_work, V, o, s_param, tol_factor * o->converge_tol, n_global, &it, &spmvs);
+        break;
+      case MFEM_SOLVER_LSQR:
+        rc = mfem_lsqr_pass(ctx, A, vals_work, V, o, tol_factor * o->converge_tol, n_global, &it, &spmvs);
         break;
       default:
         mfem_set_error("unknown solver method %d", o->method);

@@ -894,6 +894,7 @@ int mfem_csr_plan(mfem_context_s* ctx, mfem_csr_s* A) {
 
 // everything the handle derived from the borrowed pattern arrays (not the arrays themselves)
 static void csr_drop_plans(mfem_csr_s* A) {
+  mfem_tplan_free(A);
   mfem_ell_unbind(A);
   mfem_sell_unbind(A);
   mfem_lat27_unbind(A);
@@ -1028,6 +1029,7 @@ extern "C" int mfem_csr_destroy(mfem_csr A) try {
   if (!A) return MFEM_OK;
   // a cached cycle graph holds this pattern's arrays in its kernel arguments
   if (A->ctx && mfem_context_alive(A->ctx)) mfem_graphs_invalidate(A->ctx);
+  mfem_tplan_free(A);
   mfem_ell_free(A);
   mfem_sell_free(A);
   mfem_rem_free(A);
