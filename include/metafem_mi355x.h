@@ -163,16 +163,25 @@ typedef enum {
   MFEM_SOLVER_TFQMR = 6,       /* tfqmr!         linear_solver/08_QMR.jl:3-74 (one rank only; checkiter in l_or_s) */
   MFEM_SOLVER_LSQR = 7         /* lsqr!          linear_solver/06_LSQR.jl:10-70 (one rank only; uses A', see mfem_spmv_csr_t) */
 } mfem_solver_kind;
-/* mfem_solve_stats.spmv_count per pass of the three solvers above, it = the pass's returned iteration count (>= 1), x0 = [x != 0 at the
- * start of the pass] (the first pass starts from r = b: 0), +1 for the true residual the restart wrapper computes after every pass:
- *   cgs!    x0 + 2 (it - 1) + 1                      (A u and the true residual b - A x of every iteration, :45-47)
- *   tfqmr!  x0 + 1 + 2 (it - 1) + checks + 1         (A p at the start; A v and A p per iteration; checks = the iterations 2 .. it with
+/* mfem_solve_stats.spmv_count per pass, it = the pass's returned iteration count, x0 = [x != 0 at the start of the pass] (the first pass starts
+ * from r = b: 0), +1 for the true residual the restart wrapper computes after every pass.  Every solver counts the products that ran, on the
+ * device (cg!: from its iteration count), so a cycle replayed after the stop and the unrun rest of a cut-off IDR(s) cycle count nothing:
+ *   cg!             x0 + it + 1                      (A p per iteration; cg_variant 1, 3, 4, and 0 unless it picks the next form)
+ *   cg! (1 reduction) x0 + 1 + it + 1                (cg_variant 2, or 0 with a communicator: A u before the first iteration, then one per
+ *                                                    iteration -- also when the start has converged, it = 0)
+ *   bicgstabl_GS!(l) x0 + 2 (it - 1) + 1             (it = 1 + l per sweep; 2 l products per sweep)
+ *   idrs!(s)        x0 + it + 1                      (one product per step, the step that stops the pass included: maxiter = 200 runs 200)
+ *   cgs2!           x0 + 2 (it - 1) + 1              (A w and the true residual b - A x of every iteration, :96-98)
+ *   gmres!(s)       x0 + (it - 1) + c + 1            (s Arnoldi products per cycle, k in a cycle cut short by an exact breakdown at step k;
+ *                                                    c = the cycles that end with their true residual: all, unless the last broke down)
+ *   cgs!            x0 + 2 (it - 1) + 1              (A u and the true residual b - A x of every iteration, :45-47)
+ *   tfqmr!          x0 + 1 + 2 (it - 1) + checks + 1 (A p at the start; A v and A p per iteration; checks = the iterations 2 .. it with
  *                                                    iter % checkiter == 0 and iter <= maxiter, each one true residual; none with
  *                                                    fixed_iterations)
- *   lsqr!   x0 + 1 + sum over the it - 1 iterations of (2 + [beta != 0]) + 1   (A' u at the start; A v, A' u unless beta == 0, the true
+ *   lsqr!           x0 + 1 + sum over the it - 1 iterations of (2 + [beta != 0]) + 1   (A' u at the start; A v, A' u unless beta == 0, the true
  *                                                    residual per iteration: transposed products count like the others)
- * A pass that finds r converged at once (it = 0) counts x0 + 1.  A solve on the symmetric lattice tiles (modes 4 and 5) adds one product per
- * recheck of its residual on the caller's CSR values (one for a single pass). */
+ * A pass that finds r converged at once (it = 0) counts x0 + 1 (single-reduction cg!: x0 + 2).  A solve on the symmetric lattice tiles (modes 4
+ * and 5) adds one product per recheck of its residual on the caller's CSR values (one for a single pass). */
 
 typedef enum {
   MFEM_PRECOND_NONE = 0,            /* Identity, 02_Preconditioner.jl:78-86 */

@@ -9,8 +9,9 @@ enum {
   S_RZ0 = 0, S_RZ1 = 1, S_RR = 2, S_PAP = 3, S_TMP0 = 4, S_TMP1 = 5, S_TMP2 = 6, S_TMP3 = 7,
   S_SOLVER = 16  // solver-private block [16, 240)
 };
-// device flags (ctx->d_flags)
-enum { F_DONE = 0, F_ITER = 1, F_AUX = 2 };
+// device flags (ctx->d_flags): the stop flag, the iteration count, the products of the pass (every solver but cg!, which derives them from its
+// iteration count), one solver-private flag
+enum { F_DONE = 0, F_ITER = 1, F_SPMV = 2, F_AUX = 3 };
 
 // 1 / d to ~1 ulp for a normal, non-zero d: v_rcp_f64 (about 24 good bits) + two Newton steps -- 5 instructions where the IEEE
 // division sequence takes ~14.  Used where r = z / dinv only feeds the dot products of the z-carrying recurrences.
@@ -65,22 +66,14 @@ int mfem_true_residual(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, c
 int mfem_pass_residual(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, const KrylovVecs& V, double* r, double* d_rr, int* spmv_out);
 int mfem_read_scalars(mfem_context_s* ctx, int first, int count);
 int mfem_read_flags(mfem_context_s* ctx);
-int mfem_bicgstabl_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V,
-                        const mfem_solve_options* o, int l, double tol, int64_t n_global, int* iters_out, int* spmv_out);
-int mfem_cgs2_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o,
-                   double tol, int64_t n_global, int* iters_out, int* spmv_out);
-int mfem_idrs_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o,
-                   int s, double tol, int64_t n_global, int* iters_out, int* spmv_out);
-int mfem_gmres_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o,
-                    int s, double tol, int64_t n_global, int* iters_out, int* spmv_out);
+// One pass of a solver (the method table of solve_inner): s = l_or_s or the method's default (unused by the methods without one); the pass's
+// iteration count to *iters_out, the products that ran added to *spmv_out (include/metafem_mi355x.h: mfem_solve_stats.spmv_count)
+typedef int mfem_pass_fn(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o, int s, double tol,
+                         int64_t n_global, int* iters_out, int* spmv_out);
+mfem_pass_fn mfem_bicgstabl_pass, mfem_cgs2_pass, mfem_idrs_pass, mfem_gmres_pass;
+// krylov_next.hip: cgs!, tfqmr! (checkiter = s, default 200), lsqr! (products with A' through V.AT / V.valsT)
+mfem_pass_fn mfem_cgs_pass, mfem_tfqmr_pass, mfem_lsqr_pass;
 size_t mfem_gmres_workspace_bytes();
-// krylov_next.hip: cgs!, tfqmr! (checkiter = the l_or_s of the options, default 200), lsqr! (products with A' through V.AT / V.valsT)
-int mfem_cgs_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o,
-                  double tol, int64_t n_global, int* iters_out, int* spmv_out);
-int mfem_tfqmr_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o,
-                    int checkiter, double tol, int64_t n_global, int* iters_out, int* spmv_out);
-int mfem_lsqr_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o,
-                   double tol, int64_t n_global, int* iters_out, int* spmv_out);
 
 // ---- hipGraph replay of one solver cycle -------------------------------------------------------------------------
 // The Krylov drivers keep every recurrence scalar on the device and guard their kernels with the DONE flag, so the kernel
@@ -112,6 +105,17 @@ inline uint64_t mfem_csr_graph_key(uint64_t key, const mfem_csr_s* A) {
   key = mfem_hash(key, A->rem_active);
   if (A->rem_active) { key = mfem_hash(key, A->rem_nrows); key = mfem_hash(key, A->rem_rows); key = mfem_hash(key, A->rem_col); key = mfem_hash(key, A->rem_val); }
   key = mfem_hash(key, mfem_debug_epoch.load());
+  return key;
+}
+
+// Where the key of every pass's captured cycle starts: the method, the matrix, the working values, vectors and options its kernels bake in.
+// Each solver appends what else its cycle depends on.
+inline uint64_t mfem_pass_key(int method, const mfem_csr_s* A, const double* vals, const KrylovVecs& V, double tol, int64_t n_global,
+                              const mfem_solve_options* o) {
+  uint64_t key = mfem_hash(MFEM_HASH_SEED, method);
+  key = mfem_csr_graph_key(key, A); key = mfem_hash(key, vals); key = mfem_hash(key, V.w[0]); key = mfem_hash(key, V.x);
+  key = mfem_hash(key, V.b); key = mfem_hash(key, V.nv); key = mfem_hash(key, tol); key = mfem_hash(key, n_global);
+  key = mfem_hash(key, o->maxiter); key = mfem_hash(key, o->fixed_iterations);
   return key;
 }
 

@@ -336,8 +336,8 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_cg_pupdate(CgArgs a, int cur, co
   }
 }
 
-static int cg_solve_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V,
-                         const mfem_solve_options* o, double tol, int64_t n_global, int* iters_out, int* spmv_out) {
+static int cg_solve_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o, int, double tol,
+                         int64_t n_global, int* iters_out, int* spmv_out) {
   // V.x (current iterate), V.b ; work: r, p, Ap, dinv
   double* S = ctx->d_scalars;
   int32_t* F = ctx->d_flags;
@@ -380,11 +380,8 @@ static int cg_solve_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals,
   MFEM_CHECK_LAUNCH();
   const int check = o->check_every > 0 ? o->check_every : 32;
   const int nt = !g_cg_streaming ? 0 : (nv >= 40000000 ? 1 : 2);  // (see cg_ld / cg_st: loads only while a vector is within reach of the Infinity Cache)
-  uint64_t key = mfem_hash(MFEM_HASH_SEED, (int)MFEM_SOLVER_CG);
-  key = mfem_csr_graph_key(key, A); key = mfem_hash(key, vals); key = mfem_hash(key, V.w[0]); key = mfem_hash(key, V.x);
-  key = mfem_hash(key, dinv); key = mfem_hash(key, nv); key = mfem_hash(key, tol); key = mfem_hash(key, n_global);
-  key = mfem_hash(key, o->maxiter); key = mfem_hash(key, o->fixed_iterations); key = mfem_hash(key, a.zrec);
-  key = mfem_hash(key, V.cg_s); key = mfem_hash(key, a.smax2); key = mfem_hash(key, a.gate2);
+  uint64_t key = mfem_pass_key(MFEM_SOLVER_CG, A, vals, V, tol, n_global, o);
+  key = mfem_hash(key, dinv); key = mfem_hash(key, a.zrec); key = mfem_hash(key, V.cg_s); key = mfem_hash(key, a.smax2); key = mfem_hash(key, a.gate2);
   const bool lat_fused = mfem_lat27_cg_fused(ctx, A, vals);  // (lattice tiles of the hex-27 matrix, one rank: pass 2 inside the residual update)
   key = mfem_hash(key, (int)lat_fused);
   int it = 0;
@@ -459,17 +456,17 @@ static int cg_solve_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals,
         return r2 ? r2 : iteration(1);
       });
       if (rc) return rc;
-      *spmv_out += 2;
     }
     for (; k < burst; ++k, ++it) {
       rc = iteration(it);
       if (rc) return rc;
-      ++*spmv_out;
     }
   }
   rc = mfem_read_flags(ctx);
   if (rc) return rc;
+  // every iteration that runs (k_cg_pupdate: F_ITER + 1 unless DONE) has one product, A p; converged at k_cg_init_fin: 0 iterations, 0 products
   *iters_out = ctx->h_flags[4 * (it & 1) + F_ITER];
+  *spmv_out += *iters_out;
   return MFEM_OK;
 }
 
@@ -607,8 +604,8 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_cgcg_update(CgArgs a, const d2_t
   }
 }
 
-static int cgcg_solve_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V,
-                           const mfem_solve_options* o, double tol, int64_t n_global, int* iters_out, int* spmv_out) {
+static int cgcg_solve_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o, int, double tol,
+                           int64_t n_global, int* iters_out, int* spmv_out) {
   double* S = ctx->d_scalars;
   int32_t* F = ctx->d_flags;
   double *r = V.w[0], *p = V.w[1], *sv = V.w[2], *u = V.w[3], *w = V.w[4];
@@ -654,15 +651,11 @@ static int cgcg_solve_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* val
   int np1 = 0;
   rc = mfem_spmv_halo(ctx, A, vals, u, w, 1.0, 0.0, u, part1, &np1, nullptr);
   if (rc) return rc;
-  ++*spmv_out;
   rc = scalars(np1, 1);
   if (rc) return rc;
   const int check = o->check_every > 0 ? o->check_every : 32;
-  uint64_t key = mfem_hash(MFEM_HASH_SEED, (int)MFEM_SOLVER_CG + 64);
-  key = mfem_csr_graph_key(key, A); key = mfem_hash(key, vals); key = mfem_hash(key, V.w[0]); key = mfem_hash(key, V.x);
-  key = mfem_hash(key, dinv); key = mfem_hash(key, nv); key = mfem_hash(key, tol); key = mfem_hash(key, n_global);
-  key = mfem_hash(key, o->maxiter); key = mfem_hash(key, o->fixed_iterations);
-  key = mfem_hash(key, V.cg_s); key = mfem_hash(key, a.smax2); key = mfem_hash(key, a.gate2);
+  uint64_t key = mfem_pass_key(MFEM_SOLVER_CG + 64, A, vals, V, tol, n_global, o);
+  key = mfem_hash(key, dinv); key = mfem_hash(key, V.cg_s); key = mfem_hash(key, a.smax2); key = mfem_hash(key, a.gate2);
   auto iteration = [&]() -> int {
     hipLaunchKernelGGL(k_cgcg_update, dim3(G), dim3(MFEM_BLOCK), 0, ctx->stream, a, (const d2_t*)w, (const d2_t*)dinv, (d2_t*)u,
                        (d2_t*)p, (d2_t*)sv, (d2_t*)V.x, (d2_t*)r, S, F, part2);
@@ -684,12 +677,13 @@ static int cgcg_solve_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* val
     for (int k = 0; k < burst; ++k, ++it) {
       rc = mfem_cycle_run(ctx, key, iteration);  // every iteration has the same kernel arguments: one captured cycle
       if (rc) return rc;
-      ++*spmv_out;
     }
   }
   rc = mfem_read_flags(ctx);
   if (rc) return rc;
+  // the initial A u runs whatever the start finds (unguarded), then every iteration that runs (k_cgcg_scal: F_ITER + 1 unless DONE) has one, A u
   *iters_out = ctx->h_flags[F_ITER];
+  *spmv_out += 1 + *iters_out;
   return MFEM_OK;
 }
 
@@ -763,6 +757,31 @@ extern "C" int mfem_debug_set_recheck_scale(double scale) try {
 static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double* b, double* x_out,
                        const mfem_solve_options* o, mfem_solve_stats* stats, bool allow_lat = true, int64_t n_global_in = -1);
 
+// The solvers, per mfem_solver_kind: the l_or_s a zero selects, the work vectors for it, whether a communicator is refused, the pass
+struct KrylovMethod {
+  const char* name;
+  int default_s;
+  int max_s;  // (tfqmr!: l_or_s is checkiter, not a vector count)
+  int (*nwork)(int s);
+  bool one_rank;
+  mfem_pass_fn* pass;
+};
+static const KrylovMethod k_methods[] = {
+    {"cg!", 2, MFEM_MAX_S, [](int) { return 3; }, false, cg_solve_pass},  // r, p, Ap
+    {"bicgstabl_GS!", 2, MFEM_MAX_S, [](int l) { return 2 * (l + 1) + 1; }, false, mfem_bicgstabl_pass},  // R[0..l], U[0..l], r~
+    {"idrs!", 4, MFEM_MAX_S, [](int s) { return 3 * s + 4; }, false, mfem_idrs_pass},
+    {"cgs2!", 2, MFEM_MAX_S, [](int) { return 9; }, false, mfem_cgs2_pass},
+    // gmres!: s = 20 by default (05_GMRES.jl:48).  No multi-rank form: it would need an all-reduce of up to s + 1 scalars per orthogonalisation pass
+    {"gmres!", 20, MFEM_MAX_S, [](int s) { return s + 2; }, true, mfem_gmres_pass},  // r, Q_1 .. Q_(s+1)
+    // cgs!, tfqmr!, lsqr!: one rank as well (lsqr!'s transposed product would need the halo reduction of mfem_halo_reduce)
+    {"cgs!", 2, MFEM_MAX_S, [](int) { return 6; }, true, mfem_cgs_pass},  // r, r0, u, p, s, v
+    {"tfqmr!", 200, INT32_MAX, [](int) { return 9; }, true, mfem_tfqmr_pass},  // r, r0, r_cgs, p, q, u, v, d, tmp; checkiter 200 by default (08_QMR.jl:4)
+    {"lsqr!", 2, MFEM_MAX_S, [](int) { return 5; }, true, mfem_lsqr_pass},  // r, u, v, w, tmp
+};
+// cg! with one reduction group per iteration (cgcg_solve_pass): r, p, s, u, w
+static const KrylovMethod k_cg_single = {"cg!", 2, MFEM_MAX_S, [](int) { return 5; }, false, cgcg_solve_pass};
+static_assert(sizeof(k_methods) / sizeof(k_methods[0]) == MFEM_SOLVER_LSQR + 1, "one row per mfem_solver_kind");
+
 extern "C" int mfem_solve(mfem_context ctx, mfem_csr A, double* vals, const double* b, double* x_out,
                           const mfem_solve_options* o, mfem_solve_stats* stats) try {
   MFEM_REQUIRE(ctx && A && o, "null argument");
@@ -814,14 +833,12 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
   if (stats) memset(stats, 0, sizeof(*stats));
   const int64_t n = A->n;
   if (n == 0) return MFEM_OK;
-  // gmres!: s = 20 by default (05_GMRES.jl:48).  No multi-rank form: it would need an all-reduce of up to s + 1 scalars per orthogonalisation pass
-  MFEM_REQUIRE(!(o->method == MFEM_SOLVER_GMRES && ctx->comm), "gmres! runs on one rank only: no communicator may be attached");
-  // cgs!, tfqmr!, lsqr!: one rank as well (lsqr!'s transposed product would need the halo reduction of mfem_halo_reduce)
-  MFEM_REQUIRE(!(o->method >= MFEM_SOLVER_CGS && ctx->comm), "cgs!, tfqmr! and lsqr! run on one rank only: no communicator may be attached");
-  // tfqmr!: l_or_s carries checkiter, 200 by default (08_QMR.jl:4), not bounded by MFEM_MAX_S
-  const bool is_tfqmr = o->method == MFEM_SOLVER_TFQMR;
-  const int s_param = o->l_or_s > 0 ? o->l_or_s
-                                    : (o->method == MFEM_SOLVER_IDRS ? 4 : o->method == MFEM_SOLVER_GMRES ? 20 : is_tfqmr ? 200 : 2);
+  const KrylovMethod* method = &k_methods[o->method];
+  if (method->one_rank && ctx->comm) {
+    mfem_set_error("%s runs on one rank only: no communicator may be attached", method->name);
+    return MFEM_ERR_INVALID;
+  }
+  const int s_param = o->l_or_s > 0 ? o->l_or_s : method->default_s;
   MFEM_REQUIRE(o->cg_variant >= 0 && o->cg_variant <= 4, "cg_variant must be 0 (auto), 1 (classic), 2 (single reduction), 3 (classic, preconditioned residual carried) or 4 (plain CG on the symmetrically scaled matrix)");
   // rows of the whole system (one all-reduce per solve with a communicator: every rank must take the same decisions below)
   int64_t n_global = n_global_in >= 0 ? n_global_in : n;
@@ -839,23 +856,14 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
   // no multi-GPU box): above it -- 512^3 per rank: 0.2 ms of stream against 0.03 ms of all-reduce per iteration -- the classic recurrence runs with a
   // communicator too.  Decided on n_global / world: the same on every rank.
   const int world_ranks = mfem_comm_world(ctx);
-  const bool cg_single = o->method == MFEM_SOLVER_CG &&
-                         (o->cg_variant == 2 || (o->cg_variant == 0 && world_ranks > 1 && n_global / world_ranks < g_cg_single_max_rows));
-  MFEM_REQUIRE(is_tfqmr || s_param <= MFEM_MAX_S, "l_or_s too large");
+  if (o->method == MFEM_SOLVER_CG &&
+      (o->cg_variant == 2 || (o->cg_variant == 0 && world_ranks > 1 && n_global / world_ranks < g_cg_single_max_rows)))
+    method = &k_cg_single;
+  MFEM_REQUIRE(s_param <= method->max_s, "l_or_s too large");
   // x may carry ghost entries behind the owned rows (slab decomposition)
   const int64_t ghosts = ctx->comm ? 2 * ctx->halo_plane_len * ctx->halo_fields : 0;
   const int64_t nv = (int64_t)align_up((size_t)(n + ghosts), 32);  // padded vector length (even => d2 kernels)
-  int nwork = 0;
-  switch (o->method) {
-    case MFEM_SOLVER_CG: nwork = cg_single ? 5 : 3; break;
-    case MFEM_SOLVER_BICGSTABL_GS: nwork = 2 * (s_param + 1) + 1; break;
-    case MFEM_SOLVER_IDRS: nwork = 3 * s_param + 4; break;
-    case MFEM_SOLVER_CGS2: nwork = 9; break;
-    case MFEM_SOLVER_GMRES: nwork = s_param + 2; break;  // r, Q_1 .. Q_(s+1)
-    case MFEM_SOLVER_CGS: nwork = 6; break;    // r, r0, u, p, s, v
-    case MFEM_SOLVER_TFQMR: nwork = 9; break;  // r, r0, r_cgs, p, q, u, v, d, tmp
-    case MFEM_SOLVER_LSQR: nwork = 5; break;   // r, u, v, w, tmp
-  }
+  const int nwork = method->nwork(s_param);
   // lsqr!: the transposed pattern, planned on the first lsqr! solve (or mfem_spmv_csr_t) and kept on the handle
   const bool is_lsqr = o->method == MFEM_SOLVER_LSQR;
   mfem_tplan_s* tplan = nullptr;
@@ -1261,36 +1269,7 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
   };
   for (;;) {
     int it = 0;
-    switch (o->method) {
-      case MFEM_SOLVER_CG:
-        rc = cg_single ? cgcg_solve_pass(ctx, A, vals_work, V, o, tol_factor * o->converge_tol, n_global, &it, &spmvs)
-                       : cg_solve_pass(ctx, A, vals_work, V, o, tol_factor * o->converge_tol, n_global, &it, &spmvs);
-        break;
-      case MFEM_SOLVER_BICGSTABL_GS:
-        rc = mfem_bicgstabl_pass(ctx, A, vals_work, V, o, s_param, tol_factor * o->converge_tol, n_global, &it, &spmvs);
-        break;
-      case MFEM_SOLVER_IDRS:
-        rc = mfem_idrs_pass(ctx, A, vals_work, V, o, s_param, tol_factor * o->converge_tol, n_global, &it, &spmvs);
-        break;
-      case MFEM_SOLVER_CGS2:
-        rc = mfem_cgs2_pass(ctx, A, vals_work, V, o, tol_factor * o->converge_tol, n_global, &it, &spmvs);
-        break;
-      case MFEM_SOLVER_GMRES:
-        rc = mfem_gmres_pass(ctx, A, vals_work, V, o, s_param, tol_factor * o->converge_tol, n_global, &it, &spmvs);
-        break;
-      case MFEM_SOLVER_CGS:
-        rc = mfem_cgs_pass(ctx, A, vals_work, V, o, tol_factor * o->converge_tol, n_global, &it, &spmvs);
-        break;
-      case MFEM_SOLVER_TFQMR:
-        rc = mfem_tfqmr_pass(ctx, A, vals_work, V, o, s_param, tol_factor * o->converge_tol, n_global, &it, &spmvs);
-        break;
-      case MFEM_SOLVER_LSQR:
-        rc = mfem_lsqr_pass(ctx, A, vals_work, V, o, tol_factor * o->converge_tol, n_global, &it, &spmvs);
-        break;
-      default:
-        mfem_set_error("unknown solver method %d", o->method);
-        rc = MFEM_ERR_INVALID;
-    }
+    rc = method->pass(ctx, A, vals_work, V, o, s_param, tol_factor * o->converge_tol, n_global, &it, &spmvs);
     if (rc) return rc;
     V.x_zero = false;
     total_iters += it;

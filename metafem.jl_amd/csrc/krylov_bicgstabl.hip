@@ -33,9 +33,8 @@ enum {
   B_DOT = B_TAU + BL_MAXL * BL_MAXL  // scratch for batched dots [KK_MAX_DOTS]
 };
 
-struct BlArgs {
-  double n_inv, tol;
-  int32_t maxiter, fixed, l;
+struct BlArgs : KrylovArgs {
+  int32_t l;
 };
 
 __global__ void kb_init(BlArgs a, double* __restrict__ S, int32_t* __restrict__ F) {
@@ -43,10 +42,7 @@ __global__ void kb_init(BlArgs a, double* __restrict__ S, int32_t* __restrict__ 
   S[B_OMEGA] = 1.0;
   S[B_RHO0] = 1.0;
   S[B_ALPHA] = 0.0;
-  F[F_ITER] = 1;  // "iter = 1" (:25)
-  const bool conv = !a.fixed && sqrt(S[S_RR] * a.n_inv) <= a.tol;
-  F[F_DONE] = conv ? 1 : 0;
-  if (conv) F[F_ITER] = 0;  // "(r_norm <= tol) && return 0" (:24)
+  kk_start(kk_converged(a, S[S_RR]), F);  // "iter = 1" (:25), or "(r_norm <= tol) && return 0" (:24)
 }
 
 __global__ void kb_sweep_begin(double* __restrict__ S, const int32_t* __restrict__ F) {
@@ -100,15 +96,16 @@ __global__ void kb_gamma(int l, double* __restrict__ S, const int32_t* __restric
     S[B_GPP + j] = S[B_G + j + 1] + d;
   }
 }
-// iter += l; stop test on R[1] (:93-94); S[B_DOT] = R[1].R[1]
+// iter += l; stop test on R[1] (:93-94); S[B_DOT] = R[1].R[1].  The sweep's 2 l products ran.
 __global__ void kb_sweep_end(FoldArg fa, BlArgs a, double* __restrict__ S, int32_t* __restrict__ F) {
   if (F[F_DONE]) return;
   kk_fold_dev(fa, S);
   if (threadIdx.x != 0) return;
   const int iter = F[F_ITER] + a.l;
   F[F_ITER] = iter;
+  F[F_SPMV] += 2 * a.l;
   S[S_RR] = S[B_DOT];
-  if ((!a.fixed && sqrt(S[B_DOT] * a.n_inv) <= a.tol) || iter >= a.maxiter) F[F_DONE] = 1;
+  if (kk_converged(a, S[B_DOT]) || iter >= a.maxiter) F[F_DONE] = 1;
 }
 
 // ---- fused form ------------------------------------------------------------------------------------------------------------------------
@@ -252,35 +249,20 @@ __global__ __launch_bounds__(MFEM_BLOCK) void kb_final(int64_t n2, int64_t n_own
     partials[gridDim.x + blockIdx.x] = b1;
   }
 }
-// iter += l; stop test on R[1] (:93-94); S[B_END] = R[1]' R[1], S[B_END + 1] = r~' R[1]
+// iter += l; stop test on R[1] (:93-94); S[B_END] = R[1]' R[1], S[B_END + 1] = r~' R[1].  The sweep's 2 l products ran.
 __global__ void kb_sweep_end2(FoldArg fa, BlArgs a, double* __restrict__ S, int32_t* __restrict__ F) {
   if (F[F_DONE]) return;
   kk_fold_dev(fa, S);
   if (threadIdx.x != 0) return;
   const int iter = F[F_ITER] + a.l;
   F[F_ITER] = iter;
+  F[F_SPMV] += 2 * a.l;
   S[S_RR] = S[B_END];
-  if ((!a.fixed && sqrt(S[B_END] * a.n_inv) <= a.tol) || iter >= a.maxiter) F[F_DONE] = 1;
+  if (kk_converged(a, S[B_END]) || iter >= a.maxiter) F[F_DONE] = 1;
 }
 
-#define RC(x)            \
-  do {                   \
-    int _rc = (x);       \
-    if (_rc) return _rc; \
-  } while (0)
-#define K1F(kernel, ...)                                                               \
-  do {                                                                                 \
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(MFEM_BLOCK), 0, ctx->stream, __VA_ARGS__); \
-    MFEM_CHECK_LAUNCH();                                                               \
-  } while (0)
-#define K1(kernel, ...)                                                       \
-  do {                                                                        \
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(1), 0, ctx->stream, __VA_ARGS__); \
-    MFEM_CHECK_LAUNCH();                                                      \
-  } while (0)
-
-int mfem_bicgstabl_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V,
-                        const mfem_solve_options* o, int l, double tol, int64_t n_global, int* iters_out, int* spmv_out) {
+int mfem_bicgstabl_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o, int l, double tol,
+                        int64_t n_global, int* iters_out, int* spmv_out) {
   MFEM_REQUIRE(l >= 1 && l <= BL_MAXL, "bicgstabl_GS: 1 <= s <= 8 supported");
   double* S = ctx->d_scalars;
   int32_t* F = ctx->d_flags;
@@ -289,7 +271,7 @@ int mfem_bicgstabl_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, 
   double** U = V.w + (l + 1);    // U[0..l]
   double* shadow = V.w[2 * (l + 1)];
   KK k{ctx, nv, V.n, mfem_vec_grid(ctx, nv), S, F, ctx->stream};
-  BlArgs a{1.0 / (double)n_global, tol, o->maxiter, o->fixed_iterations, l};
+  const BlArgs a{kk_args(tol, n_global, o), l};
 
   // r = b - A x ; Pl(r) (identity)   (:19-21)
   RC(mfem_pass_residual(ctx, A, vals, V, R[0], S + S_RR, spmv_out));
@@ -303,16 +285,6 @@ int mfem_bicgstabl_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, 
   for (int i = 1; i <= l; ++i) MFEM_CHECK_HIP(hipMemsetAsync(R[i], 0, sizeof(double) * nv, ctx->stream));
   for (int i = 0; i <= l; ++i) MFEM_CHECK_HIP(hipMemsetAsync(U[i], 0, sizeof(double) * nv, ctx->stream));
 
-  const int check = o->check_every > 0 ? o->check_every : 32;
-  int sweeps_since_poll = 0;
-  RC(mfem_read_flags(ctx));
-  int host_iter = 1;
-  uint64_t key = mfem_hash(MFEM_HASH_SEED, (int)MFEM_SOLVER_BICGSTABL_GS);
-  key = mfem_hash(key, l); key = mfem_csr_graph_key(key, A); key = mfem_hash(key, vals); key = mfem_hash(key, V.w[0]);
-  key = mfem_hash(key, V.x); key = mfem_hash(key, nv); key = mfem_hash(key, tol); key = mfem_hash(key, n_global);
-  key = mfem_hash(key, o->maxiter); key = mfem_hash(key, o->fixed_iterations);
-  int dummy_spmv = 0;
-  int* const spmv_cnt = &dummy_spmv;
   auto sweep = [&]() -> int {  // one BiCGStab(l) sweep: 2 l SpMVs, constant kernel arguments
     K1(kb_sweep_begin, S, F);
     // ---- BiCG part (:43-62)
@@ -321,11 +293,11 @@ int mfem_bicgstabl_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, 
       RC(k.dot1_partials(shadow, R[j], B_DOT, &fa));
       K1F(kb_beta, fa, S, F);
       for (int i = 0; i <= j; ++i) RC(k.lin2(coef_imm(1.0), R[i], coef_dev(B_BETA, -1.0), U[i], U[i]));  // U[i] = R[i] - beta U[i]
-      RC(k.spmv(A, vals, U[j], U[j + 1], spmv_cnt));
+      RC(k.spmv(A, vals, U[j], U[j + 1]));
       RC(k.dot1_partials(shadow, U[j + 1], B_DOT, &fa));
       K1F(kb_alpha, fa, S, F);
       for (int i = 0; i <= j; ++i) RC(k.axpby(coef_dev(B_ALPHA, -1.0), U[i + 1], coef_imm(1.0), R[i]));  // R[i] -= alpha U[i+1]
-      RC(k.spmv(A, vals, R[j], R[j + 1], spmv_cnt));
+      RC(k.spmv(A, vals, R[j], R[j + 1]));
       RC(k.axpby(coef_dev(B_ALPHA), U[0], coef_imm(1.0), V.x));  // x += alpha U[1]
     }
     // ---- MR part, modified Gram-Schmidt (:64-71)
@@ -372,7 +344,6 @@ int mfem_bicgstabl_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, 
   };
   auto spmv_dot = [&](double* xin, double* yout, const double* dotw, int out, FoldArg* fa) -> int {  // y = A x ; S[out] = dotw' y
     int np = 0;
-    ++*spmv_cnt;
     RC(mfem_spmv_halo(ctx, A, vals, xin, yout, 1.0, 0.0, dotw, dotw ? ctx->d_partials : nullptr, &np, F));
     *fa = FoldArg{nullptr, 0, 0, out};
     return dotw ? reduce_to(ctx->d_partials, np, 1, out, fa) : MFEM_OK;
@@ -394,15 +365,13 @@ int mfem_bicgstabl_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, 
       VecList LU;
       LU.m = j + 1;
       for (int i = 0; i <= j; ++i) { LU.a[i] = (d2_t*)U[i]; LU.b[i] = (const d2_t*)R[i]; }
-      hipLaunchKernelGGL(kb_ulist, dim3(k.G), dim3(MFEM_BLOCK), 0, ctx->stream, nv / 2, LU, S, F);
-      MFEM_CHECK_LAUNCH();
+      KV(kb_ulist, nv / 2, LU, S, F);
       RC(spmv_dot(U[j], U[j + 1], shadow, B_DOT, &fa));
       K1F(kb_alpha, fa, S, F);
       VecList LR;
       LR.m = j + 1;
       for (int i = 0; i <= j; ++i) { LR.a[i] = (d2_t*)R[i]; LR.b[i] = (const d2_t*)U[i + 1]; }
-      hipLaunchKernelGGL(kb_rlist, dim3(k.G), dim3(MFEM_BLOCK), 0, ctx->stream, nv / 2, LR, (const d2_t*)U[0], (d2_t*)V.x, S, F);
-      MFEM_CHECK_LAUNCH();
+      KV(kb_rlist, nv / 2, LR, (const d2_t*)U[0], (d2_t*)V.x, S, F);
       RC(spmv_dot(R[j], R[j + 1], (j + 1 < l) ? shadow : nullptr, B_DOT, &fa));
     }
     // Gram matrix of R[0..l]: Z[p][q], 0 <= p <= q <= l, q >= 1, in passes of KK_MAX_DOTS dot products; the scalar kernel of the last pass runs the MR part
@@ -427,37 +396,21 @@ int mfem_bicgstabl_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, 
     FinalList FL;
     FL.l = l;
     for (int i = 0; i <= l; ++i) { FL.R[i] = (const d2_t*)R[i]; FL.U[i] = (const d2_t*)U[i]; }
-    hipLaunchKernelGGL(kb_final, dim3(k.G), dim3(MFEM_BLOCK), 0, ctx->stream, nv / 2, V.n, FL, (d2_t*)R[0], (d2_t*)U[0], (d2_t*)V.x, (const d2_t*)shadow,
-                       S, F, ctx->d_partials);
-    MFEM_CHECK_LAUNCH();
+    KV(kb_final, nv / 2, V.n, FL, (d2_t*)R[0], (d2_t*)U[0], (d2_t*)V.x, (const d2_t*)shadow, S, F, ctx->d_partials);
     FoldArg fe;
     RC(reduce_to(ctx->d_partials, k.G, 2, B_END, &fe));
     K1F(kb_sweep_end2, fe, a, S, F);
     return MFEM_OK;
   };
-  bool first_sweep = true;
   // The Gram-matrix form of the minimal-residual part squares the condition of R[1..l] (= A^k r: ever more parallel): fine for l <= 2 (the default and
   // what the elasticity examples use; 1e-11 from the literal loop after three sweeps, also at l = 4), visibly worse at l = 6 (1e-8): larger l keep the
   // literal sequence with its modified Gram-Schmidt on the vectors.
   const bool literal = g_bicgstabl_literal || l > 2;
-  key = mfem_hash(key, literal ? 1 : 0);
-  while (!ctx->h_flags[F_DONE]) {
-    if (literal) {
-      RC(mfem_cycle_run(ctx, key, sweep));
-    } else if (first_sweep) {  // (its kernel sequence differs from the later sweeps': not a cached cycle)
-      RC(sweep_fused(true));
-      first_sweep = false;
-    } else {
-      RC(mfem_cycle_run(ctx, key, [&]() -> int { return sweep_fused(false); }));
-    }
-    *spmv_out += 2 * l;
-    host_iter += l;
-    if (++sweeps_since_poll * l >= check || host_iter >= o->maxiter) {
-      RC(mfem_read_flags(ctx));
-      sweeps_since_poll = 0;
-    }
-  }
-  RC(mfem_read_flags(ctx));
-  *iters_out = ctx->h_flags[F_ITER];
-  return MFEM_OK;
+  uint64_t key = mfem_pass_key(MFEM_SOLVER_BICGSTABL_GS, A, vals, V, tol, n_global, o);
+  key = mfem_hash(key, l); key = mfem_hash(key, literal ? 1 : 0);
+  // the fused form's first sweep runs directly: its kernel sequence differs from the later sweeps' (not a cached cycle)
+  auto variant = [&](int c, int64_t) { return !literal && c == 0 ? KC_DIRECT : KC_MAIN; };
+  auto cycle = [&](int v) -> int { return literal ? sweep() : sweep_fused(v == KC_DIRECT); };
+  // (kb_sweep_end / kb_sweep_end2 stop once the iteration count reaches maxiter)
+  return kk_drive(ctx, o, key, l, o->maxiter, cycle, variant, iters_out, spmv_out);
 }

@@ -25,11 +25,10 @@ enum {
 static_assert(GM_H2 + GM_LD <= GM_PART, "gmres region layout");
 size_t mfem_gmres_workspace_bytes() { return sizeof(double) * (size_t)GM_DOUBLES; }
 
-enum { F_GM_SPMV = F_AUX, F_GM_WIDTH = 3 };  // SpMVs of this pass; columns of the cycle after an exact breakdown (0: none)
+enum { F_GM_WIDTH = F_AUX };  // columns of the cycle after an exact breakdown (0: none)
 
-struct GmArgs {
-  double n_inv, tol;
-  int32_t maxiter, fixed, s;
+struct GmArgs : KrylovArgs {
+  int32_t s;
 };
 struct GmBasis {
   const d2_t* q[MFEM_MAX_S];
@@ -37,12 +36,8 @@ struct GmBasis {
 
 // r = b - A x is in place and S[S_RR] = r.r: iter = 1, or 0 iterations if normalized_norm(r) <= tol (:49-52)
 __global__ void kg_init(GmArgs a, const double* __restrict__ S, int32_t* __restrict__ F) {
-  F[F_ITER] = 1;
-  F[F_GM_SPMV] = 0;
+  kk_start(S[S_RR] == 0.0 || kk_converged(a, S[S_RR]), F);
   F[F_GM_WIDTH] = 0;
-  const bool conv = S[S_RR] == 0.0 || (!a.fixed && sqrt(S[S_RR] * a.n_inv) <= a.tol);
-  F[F_DONE] = conv ? 1 : 0;
-  if (conv) F[F_ITER] = 0;
 }
 
 // y = 0, y[1] = |r| ; Q1 = r / |r|  (:56-58, :94-96)
@@ -255,7 +250,7 @@ __global__ void kg_cycle_end(GmArgs a, int32_t* __restrict__ F) {
   const int width = F[F_GM_WIDTH];
   if (width) {
     F[F_ITER] += width;
-    F[F_GM_SPMV] += width;
+    F[F_SPMV] += width;
     F[F_DONE] = 1;
     return;
   }
@@ -264,8 +259,8 @@ __global__ void kg_cycle_end(GmArgs a, int32_t* __restrict__ F) {
 // after it (S[S_RR] = r.r): stop if normalized_norm(r) <= tol || iter > maxiter (:91)
 __global__ void kg_cycle_test(GmArgs a, const double* __restrict__ S, int32_t* __restrict__ F) {
   if (F[F_DONE]) return;
-  F[F_GM_SPMV] += a.s + 1;
-  if ((!a.fixed && sqrt(S[S_RR] * a.n_inv) <= a.tol) || F[F_ITER] > a.maxiter) F[F_DONE] = 1;
+  F[F_SPMV] += a.s + 1;
+  if (kk_converged(a, S[S_RR]) || F[F_ITER] > a.maxiter) F[F_DONE] = 1;
 }
 
 static std::atomic<int> g_gmres_literal{0};
@@ -274,17 +269,6 @@ extern "C" int mfem_debug_set_gmres(int literal_mgs) try {
   g_gmres_literal = literal_mgs ? 1 : 0;
   return MFEM_OK;
 } MFEM_API_CATCH("mfem_debug_set_gmres")
-
-#define RC(x)            \
-  do {                   \
-    int _rc = (x);       \
-    if (_rc) return _rc; \
-  } while (0)
-#define K1(kernel, ...)                                                       \
-  do {                                                                        \
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(1), 0, ctx->stream, __VA_ARGS__); \
-    MFEM_CHECK_LAUNCH();                                                      \
-  } while (0)
 
 #define GM_CASES(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) \
   X(17) X(18) X(19) X(20) X(21) X(22) X(23) X(24) X(25) X(26) X(27) X(28) X(29) X(30) X(31) X(32)
@@ -341,29 +325,20 @@ int mfem_gmres_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Kryl
   double* part_nrm = part + (int64_t)MFEM_MAX_S * MFEM_MAX_PARTIALS;
   const int G = mfem_vec_grid(ctx, nv);
   const bool literal = g_gmres_literal != 0;
-  GmArgs a{1.0 / (double)n_global, tol, o->maxiter, o->fixed_iterations, s};
+  const GmArgs a{kk_args(tol, n_global, o), s};
   KK k{ctx, nv, n, G, S, F, ctx->stream};
 
   RC(mfem_pass_residual(ctx, A, vals, V, r, S + S_RR, spmv_out));  // :49-51
   K1(kg_init, a, S, F);
-  const int check = o->check_every > 0 ? o->check_every : 32;
-  int since = 0, host_iter = 1;
-  RC(mfem_read_flags(ctx));
-  uint64_t key = mfem_hash(MFEM_HASH_SEED, (int)MFEM_SOLVER_GMRES);
-  key = mfem_hash(key, s); key = mfem_csr_graph_key(key, A); key = mfem_hash(key, vals); key = mfem_hash(key, V.w[0]);
-  key = mfem_hash(key, V.x); key = mfem_hash(key, V.b); key = mfem_hash(key, V.gm); key = mfem_hash(key, nv); key = mfem_hash(key, tol);
-  key = mfem_hash(key, n_global); key = mfem_hash(key, o->maxiter); key = mfem_hash(key, o->fixed_iterations); key = mfem_hash(key, (int)literal);
-  int dummy_spmv = 0;  // (the device counts this pass's products in F_GM_SPMV: a replayed cycle behind DONE runs none of them)
   // one cycle: s Arnoldi steps (s SpMVs), the least-squares solve, x += Q y and the true residual -- constant kernel arguments
-  auto cycle = [&]() -> int {
-    hipLaunchKernelGGL(kg_start, dim3(G), dim3(MFEM_BLOCK), 0, ctx->stream, nv / 2, (const d2_t*)r, (d2_t*)Q[0], y, s, S, F);
-    MFEM_CHECK_LAUNCH();
+  auto cycle = [&](int) -> int {
+    KV(kg_start, nv / 2, (const d2_t*)r, (d2_t*)Q[0], y, s, S, F);
     GmBasis B;
     for (int j = 0; j < s; ++j) B.q[j] = (const d2_t*)Q[j];
     for (int kk = 1; kk <= s; ++kk) {  // Q_(kk+1) = A Q_kk, orthogonalised against Q_1..Q_kk into column kk of H (:61-80)
       double* w = Q[kk];
       double* col = H + GM_LD * (kk - 1);
-      RC(k.spmv(A, vals, Q[kk - 1], w, &dummy_spmv));
+      RC(k.spmv(A, vals, Q[kk - 1], w));
       const double* nrm_part = part_nrm;
       if (literal) {  // the reference's order: for each j one dot product, then one update (:65-68)
         for (int j = 0; j < kk; ++j) {
@@ -400,17 +375,8 @@ int mfem_gmres_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Kryl
     K1(kg_cycle_test, a, S, F);
     return MFEM_OK;
   };
-  while (!ctx->h_flags[F_DONE]) {
-    RC(mfem_cycle_run(ctx, key, cycle));
-    host_iter += s;
-    since += s;
-    if (since >= check || host_iter > o->maxiter) {  // (check_every counts iterations, as for the other solvers: a poll every ceil(check / s) cycles)
-      RC(mfem_read_flags(ctx));
-      since = 0;
-    }
-  }
-  RC(mfem_read_flags(ctx));
-  *iters_out = ctx->h_flags[F_ITER];
-  *spmv_out += ctx->h_flags[F_GM_SPMV];
-  return MFEM_OK;
+  uint64_t key = mfem_pass_key(MFEM_SOLVER_GMRES, A, vals, V, tol, n_global, o);
+  key = mfem_hash(key, s); key = mfem_hash(key, V.gm); key = mfem_hash(key, (int)literal);
+  // (kg_cycle_test stops once the iteration count passes maxiter; check_every counts iterations, a poll every ceil(check / s) cycles)
+  return kk_drive(ctx, o, key, s, (int64_t)o->maxiter + 1, cycle, kc_main, iters_out, spmv_out);
 }

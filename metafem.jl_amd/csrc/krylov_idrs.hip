@@ -30,9 +30,8 @@ enum {
 };
 static_assert(I_AL + IS_MAXS <= MFEM_NSCALARS, "IDR(s) scalars do not fit the device scalar block");
 
-struct IdArgs {
-  double n_inv, tol;
-  int32_t maxiter, fixed, s;
+struct IdArgs : KrylovArgs {
+  int32_t s;
 };
 
 __global__ void ki_init(IdArgs a, double* __restrict__ S, int32_t* __restrict__ F) {
@@ -40,10 +39,7 @@ __global__ void ki_init(IdArgs a, double* __restrict__ S, int32_t* __restrict__ 
     for (int i = 0; i < a.s; ++i) S[I_M + i + IS_MAXS * j] = (i == j) ? 1.0 : 0.0;  // M = I (:38)
   for (int i = 0; i < a.s; ++i) S[I_F + i] = S[I_C + i] = 0.0;
   S[I_OMEGA] = 1.0;
-  F[F_ITER] = 1;
-  const bool conv = !a.fixed && sqrt(S[S_RR] * a.n_inv) <= a.tol;
-  F[F_DONE] = conv ? 1 : 0;
-  if (conv) F[F_ITER] = 0;
+  kk_start(kk_converged(a, S[S_RR]), F);
 }
 // f[first + t] = dots[t]
 // beta_k >= 0: this was the last chunk of column k of M -> also beta = f[k] / M[k,k]   (:73)
@@ -61,14 +57,15 @@ __global__ void ki_alpha(FoldArg fa, int i, double* __restrict__ S, const int32_
   if (threadIdx.x != 0) return;
   S[I_ALPHA] = S[I_DOT] / S[I_M + i + IS_MAXS * i];
 }
-// stop test after the inner step, then f[k+1:] -= beta*M[k+1:,k]; iter += 1   (:79-81); S[I_DOT] = r.r
+// stop test after the inner step, then f[k+1:] -= beta*M[k+1:,k]; iter += 1   (:79-81); S[I_DOT] = r.r.  The step's one product ran.
 __global__ void ki_step_end(FoldArg fa, IdArgs a, int k, double* __restrict__ S, int32_t* __restrict__ F, int f_done = 0) {
   if (F[F_DONE]) return;
   kk_fold_dev(fa, S);
   if (threadIdx.x != 0) return;
   S[S_RR] = S[I_DOT];
+  F[F_SPMV] += 1;
   const int iter = F[F_ITER];
-  if ((!a.fixed && sqrt(S[I_DOT] * a.n_inv) <= a.tol) || iter >= a.maxiter) {
+  if (kk_converged(a, S[I_DOT]) || iter >= a.maxiter) {
     F[F_DONE] = 1;
     return;
   }
@@ -350,22 +347,6 @@ __global__ __launch_bounds__(MFEM_BLOCK) void ki_update_combine(int64_t n2, int6
   if (threadIdx.x == 0) partials[blockIdx.x] = b;
 }
 
-#define RC(x)            \
-  do {                   \
-    int _rc = (x);       \
-    if (_rc) return _rc; \
-  } while (0)
-#define K1F(kernel, ...)                                                               \
-  do {                                                                                 \
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(MFEM_BLOCK), 0, ctx->stream, __VA_ARGS__); \
-    MFEM_CHECK_LAUNCH();                                                               \
-  } while (0)
-#define K1(kernel, ...)                                                       \
-  do {                                                                        \
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(1), 0, ctx->stream, __VA_ARGS__); \
-    MFEM_CHECK_LAUNCH();                                                      \
-  } while (0)
-
 int mfem_idrs_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o,
                    int s, double tol, int64_t n_global, int* iters_out, int* spmv_out) {
   MFEM_REQUIRE(s >= 1 && s <= IS_MAXS, "idrs: 1 <= s <= 32 supported");
@@ -378,7 +359,7 @@ int mfem_idrs_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Krylo
   double** U = V.w + 4 + s;
   double** G = V.w + 4 + 2 * s;
   KK k{ctx, nv, V.n, mfem_vec_grid(ctx, nv), S, F, ctx->stream};
-  IdArgs a{1.0 / (double)n_global, tol, o->maxiter, o->fixed_iterations, s};
+  const IdArgs a{kk_args(tol, n_global, o), s};
 
   RC(mfem_pass_residual(ctx, A, vals, V, r, S + S_RR, spmv_out));  // :27-29
   K1(ki_init, a, S, F);
@@ -392,26 +373,15 @@ int mfem_idrs_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Krylo
       MFEM_CHECK_HIP(hipMemcpyAsync(P[i], ctx->shadow + (int64_t)i * V.n, sizeof(double) * V.n, hipMemcpyDeviceToDevice, ctx->stream));
     else if (g_idrs_uniform)
       RC(mfem_rand(ctx, V.n, o->seed, (uint32_t)i, P[i]));
-    else if (!signs) {
-      hipLaunchKernelGGL(kk_sign_vector, dim3(k.G), dim3(MFEM_BLOCK), 0, ctx->stream, V.n, o->seed, i, P[i]);
-      MFEM_CHECK_LAUNCH();
-    }
+    else if (!signs)
+      KV(kk_sign_vector, V.n, o->seed, i, P[i]);
     MFEM_CHECK_HIP(hipMemsetAsync(U[i], 0, sizeof(double) * nv, ctx->stream));
     MFEM_CHECK_HIP(hipMemsetAsync(G[i], 0, sizeof(double) * nv, ctx->stream));
   }
   MFEM_CHECK_HIP(hipMemsetAsync(Ar, 0, sizeof(double) * nv, ctx->stream));
 
-  const int check = o->check_every > 0 ? o->check_every : 32;
-  int since_poll = 0, host_iter = 1;
-  RC(mfem_read_flags(ctx));
-  uint64_t key = mfem_hash(MFEM_HASH_SEED, (int)MFEM_SOLVER_IDRS);
-  key = mfem_hash(key, s); key = mfem_csr_graph_key(key, A); key = mfem_hash(key, vals); key = mfem_hash(key, V.w[0]);
-  key = mfem_hash(key, V.x); key = mfem_hash(key, nv); key = mfem_hash(key, tol); key = mfem_hash(key, n_global);
-  key = mfem_hash(key, o->maxiter); key = mfem_hash(key, o->fixed_iterations); key = mfem_hash(key, g_idrs_literal);
-  key = mfem_hash(key, (int)signs); key = mfem_hash(key, (int)fused); key = mfem_hash(key, o->seed);
-  int dummy_spmv = 0;
   // one IDR cycle = s steps in G_j + the step into G_j+1: s + 1 SpMVs, constant kernel arguments
-  auto cycle = [&](int* spmv_cnt) -> int {
+  auto cycle = [&](int) -> int {
     // f = P' r  (:43-45)
     for (int i0 = 0; i0 < s; i0 += KK_MAX_DOTS) {
       DotList L;
@@ -444,7 +414,7 @@ int mfem_idrs_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Krylo
 #undef KI_COMBINE
       MFEM_CHECK_LAUNCH();
       }
-      RC(k.spmv(A, vals, U[kk], G[kk], spmv_cnt));  // :59
+      RC(k.spmv(A, vals, U[kk], G[kk]));  // :59
       if (g_idrs_literal) {
         for (int i = 0; i < kk; ++i) {                 // bi-orthogonalise (:62-66)
           FoldArg fa;
@@ -531,7 +501,7 @@ int mfem_idrs_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Krylo
       }
     }
     // r in G_j+1  (:85-93)
-    RC(k.spmv(A, vals, r, Ar, spmv_cnt));
+    RC(k.spmv(A, vals, r, Ar));
     DotList L;
     L.m = 3;
     L.x[0] = (const d2_t*)Ar; L.y[0] = (const d2_t*)Ar;
@@ -546,17 +516,9 @@ int mfem_idrs_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Krylo
     K1F(ki_step_end, fe, a, -1, S, F);
     return MFEM_OK;
   };
-  while (!ctx->h_flags[F_DONE]) {
-    RC(mfem_cycle_run(ctx, key, [&]() -> int { return cycle(&dummy_spmv); }));
-    *spmv_out += s + 1;
-    host_iter += s + 1;
-    since_poll += s + 1;
-    if (since_poll >= check || host_iter >= o->maxiter) {
-      RC(mfem_read_flags(ctx));
-      since_poll = 0;
-    }
-  }
-  RC(mfem_read_flags(ctx));
-  *iters_out = ctx->h_flags[F_ITER];
-  return MFEM_OK;
+  uint64_t key = mfem_pass_key(MFEM_SOLVER_IDRS, A, vals, V, tol, n_global, o);
+  key = mfem_hash(key, s); key = mfem_hash(key, g_idrs_literal); key = mfem_hash(key, (int)signs); key = mfem_hash(key, (int)fused);
+  key = mfem_hash(key, o->seed);
+  // (ki_step_end stops at the step whose iteration count reaches maxiter: by host iteration maxiter + 1, the steps launched + 1)
+  return kk_drive(ctx, o, key, s + 1, (int64_t)o->maxiter + 1, cycle, kc_main, iters_out, spmv_out);
 }

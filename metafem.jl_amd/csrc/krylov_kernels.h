@@ -7,6 +7,46 @@
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
 
+// launch helpers of the drivers: RC returns a failed status; K1 / K1F launch a scalar kernel on one thread / one workgroup (a K1F kernel folds the
+// partials of a FoldArg), KV a vector kernel on the grid of the KK `k` in scope
+#define RC(x)            \
+  do {                   \
+    int _rc = (x);       \
+    if (_rc) return _rc; \
+  } while (0)
+#define K1(kernel, ...)                                                       \
+  do {                                                                        \
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(1), 0, ctx->stream, __VA_ARGS__); \
+    MFEM_CHECK_LAUNCH();                                                      \
+  } while (0)
+#define K1F(kernel, ...)                                                               \
+  do {                                                                                 \
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(MFEM_BLOCK), 0, ctx->stream, __VA_ARGS__); \
+    MFEM_CHECK_LAUNCH();                                                               \
+  } while (0)
+#define KV(kernel, ...)                                                                   \
+  do {                                                                                    \
+    hipLaunchKernelGGL(kernel, dim3(k.G), dim3(MFEM_BLOCK), 0, ctx->stream, __VA_ARGS__); \
+    MFEM_CHECK_LAUNCH();                                                                  \
+  } while (0)
+
+// What the stop and convergence tests of every solver but cg! read; IdArgs, BlArgs and GmArgs add their cycle length.
+struct KrylovArgs {
+  double n_inv, tol;
+  int32_t maxiter, fixed;
+};
+static inline KrylovArgs kk_args(double tol, int64_t n_global, const mfem_solve_options* o) {
+  return KrylovArgs{1.0 / (double)n_global, tol, o->maxiter, o->fixed_iterations};
+}
+// normalized_norm(r) <= tol, from rr = r.r; never in a pass of fixed iterations
+__device__ __forceinline__ bool kk_converged(const KrylovArgs& a, double rr) { return !a.fixed && sqrt(rr * a.n_inv) <= a.tol; }
+// the flags at the start of a pass (r = b - A x in place): iteration 1 and no product yet, or DONE after 0 iterations when r has converged
+__device__ __forceinline__ void kk_start(bool conv, int32_t* __restrict__ F) {
+  F[F_DONE] = conv ? 1 : 0;
+  F[F_ITER] = conv ? 0 : 1;
+  F[F_SPMV] = 0;
+}
+
 // coefficient = sign * S[slot]  (slot >= 0)   or   the immediate `value` (slot < 0)
 struct Coef {
   double value;
@@ -320,8 +360,39 @@ struct KK {
     L.y[0] = (const d2_t*)y;
     return dots(L, out);
   }
-  int spmv(mfem_csr_s* A, const double* vals, double* x, double* y, int* spmv_count) const {
-    ++*spmv_count;  // with a communicator: the halo exchange of x runs beside the rows that need no ghost entry
+  // y = A x, skipped once DONE is set (the solver's scalar kernels count it); with a communicator the halo exchange of x runs beside the rows that
+  // need no ghost entry
+  int spmv(mfem_csr_s* A, const double* vals, double* x, double* y) const {
     return mfem_spmv_halo(ctx, A, vals, x, y, 1.0, 0.0, nullptr, nullptr, nullptr, F);
   }
 };
+
+// The host loop of every solver but cg!: replay the solver's cycle until the device sets DONE, then report its iteration and product counts.
+// A cycle advances the device's iteration count by `step` (from 1).  The flags are read every check_every iterations and after every cycle from
+// host iteration `last` on -- where the device's stop rule has fired in a pass of fixed iterations, which so launches no cycle behind its last
+// one.  The schedule depends on these counts alone: with a communicator every rank launches the same cycles.  variant(cycle index, host
+// iteration after the cycle) gives each cycle's form: KC_MAIN, the captured cycle; KC_ALT, a second captured form; KC_DIRECT, direct launches.
+enum { KC_MAIN, KC_ALT, KC_DIRECT };
+static inline int kc_main(int, int64_t) { return KC_MAIN; }
+template <class Cycle, class Variant>
+static int kk_drive(mfem_context_s* ctx, const mfem_solve_options* o, uint64_t key, int step, int64_t last, Cycle cycle, Variant variant,
+                    int* iters_out, int* spmv_out) {
+  const int check = o->check_every > 0 ? o->check_every : 32;
+  int64_t host_iter = 1;
+  int c = 0;
+  for (;;) {
+    RC(mfem_read_flags(ctx));
+    if (ctx->h_flags[F_DONE]) break;
+    int since = 0;
+    do {
+      const int v = variant(c++, host_iter + step);
+      if (v == KC_DIRECT) RC(cycle(v));
+      else RC(mfem_cycle_run(ctx, key ^ (v == KC_ALT ? 0x9E3779B97F4A7C15ull : 0ull), [&]() { return cycle(v); }));
+      host_iter += step;
+      since += step;
+    } while (since < check && host_iter < last);
+  }
+  *iters_out = ctx->h_flags[F_ITER];
+  *spmv_out += ctx->h_flags[F_SPMV];
+  return MFEM_OK;
+}

@@ -1,25 +1,19 @@
 // cgs!, tfqmr! and lsqr!  -- reference linear_solver/07_CGS.jl:13-52, 08_QMR.jl:3-74 and 06_LSQR.jl:10-70, statement for statement.
 // cgs! is the alternative line to cgs2! in examples/incompressible_flow/lid_driven_cavity_flow/2D_Script.jl:98, the docs pick tfqmr! for
-// incompressible flow (07_CGS.jl:6-7) and call lsqr! the most robust of the set.  As in krylov_cgs2.hip every scalar stays on the device,
-// the kernels are guarded by the DONE flag and one iteration is captured and replayed as a graph; the host only polls the flag.
-// The products of an iteration are counted on the device (F_NX_SPMV), so stats->spmv_count is exact whenever the host polls.
+// incompressible flow (07_CGS.jl:6-7) and call lsqr! the most robust of the set.  As in the other solvers every scalar stays on the device,
+// the kernels are guarded by the DONE flag and one iteration is captured and replayed as a graph (kk_drive); the host only polls the flag,
+// and the products are counted on the device.
 // One rank only (mfem_solve refuses a communicator): the vector kernels below sum their dot products over the whole (zero-padded) vector.
 #include "krylov_kernels.h"
 
-enum { F_NX_SPMV = F_AUX, F_NX_SKIP = 3 };  // products of this pass; lsqr!: the beta == 0 branch (or DONE) -- the done flag of the A' u product
-
-struct NxArgs {
-  double n_inv, tol;
-  int32_t maxiter, fixed;
-};
+enum { F_NX_SKIP = F_AUX };  // lsqr!: the beta == 0 branch (or DONE) -- the done flag of the A' u product
 
 // r = Pl(b - A x) is in place and S[S_RR] = r.r: iter = 1, or 0 iterations if normalized_norm(r) <= tol.  `init_products` run after
 // this kernel unless the pass ends here (tfqmr!: A p, lsqr!: A' u).
-__device__ void nx_init(const NxArgs& a, const double* __restrict__ S, int32_t* __restrict__ F, int init_products) {
-  const bool conv = !a.fixed && sqrt(S[S_RR] * a.n_inv) <= a.tol;
-  F[F_DONE] = conv ? 1 : 0;
-  F[F_ITER] = conv ? 0 : 1;
-  F[F_NX_SPMV] = conv ? 0 : init_products;
+__device__ void nx_init(const KrylovArgs& a, const double* __restrict__ S, int32_t* __restrict__ F, int init_products) {
+  const bool conv = kk_converged(a, S[S_RR]);
+  kk_start(conv, F);
+  F[F_SPMV] = conv ? 0 : init_products;
   F[F_NX_SKIP] = conv ? 1 : 0;
 }
 
@@ -38,7 +32,7 @@ __device__ __forceinline__ void nx_partial(double acc, double* __restrict__ part
 // cgs!  (07_CGS.jl:13-52)
 enum { CS_RHO = S_SOLVER + 0, CS_ALPHA, CS_BETA, CS_DOT = S_SOLVER + 8 };
 
-__global__ void kcs_init(NxArgs a, double* __restrict__ S, int32_t* __restrict__ F) {
+__global__ void kcs_init(KrylovArgs a, double* __restrict__ S, int32_t* __restrict__ F) {
   nx_init(a, S, F, 0);
   S[CS_RHO] = S[CS_ALPHA] = S[CS_BETA] = 1.0;  // :24
 }
@@ -82,12 +76,12 @@ __global__ __launch_bounds__(MFEM_BLOCK) void kcs_px(int64_t n2, const d2_t* __r
   }
 }
 // iter += 1 ; stop if normalized_norm(r) <= tol || iter > maxiter  (:49-50); A u and the true residual ran
-__global__ void kcs_end(NxArgs a, const double* __restrict__ S, int32_t* __restrict__ F) {
+__global__ void kcs_end(KrylovArgs a, const double* __restrict__ S, int32_t* __restrict__ F) {
   if (F[F_DONE]) return;
   const int iter = F[F_ITER] + 1;
   F[F_ITER] = iter;
-  F[F_NX_SPMV] += 2;
-  if ((!a.fixed && sqrt(S[S_RR] * a.n_inv) <= a.tol) || iter > a.maxiter) F[F_DONE] = 1;
+  F[F_SPMV] += 2;
+  if (kk_converged(a, S[S_RR]) || iter > a.maxiter) F[F_DONE] = 1;
 }
 
 // =====================================================================================================================================
@@ -95,7 +89,7 @@ __global__ void kcs_end(NxArgs a, const double* __restrict__ S, int32_t* __restr
 enum { TQ_ALPHA = S_SOLVER + 0, TQ_BETA, TQ_RHO, TQ_RNORM, TQ_TAU, TQ_THETA, TQ_ETA, TQ_C1, TQ_E1, TQ_C2, TQ_E2, TQ_DOT = S_SOLVER + 16 };
 
 // r_norm = tau = norm(r) ; rho = dot(r, r) ; theta = eta = 0  (:28-30)
-__global__ void ktq_init(NxArgs a, double* __restrict__ S, int32_t* __restrict__ F) {
+__global__ void ktq_init(KrylovArgs a, double* __restrict__ S, int32_t* __restrict__ F) {
   nx_init(a, S, F, 1);
   S[TQ_ALPHA] = S[TQ_BETA] = 1.0;
   S[TQ_RNORM] = S[TQ_TAU] = sqrt(S[S_RR]);
@@ -186,17 +180,17 @@ __global__ __launch_bounds__(MFEM_BLOCK) void ktq_update(int64_t n2, const d2_t*
   }
 }
 // iter += 1 ; iter > maxiter ends the pass (:65-66); A v and A p ran
-__global__ void ktq_end(NxArgs a, int32_t* __restrict__ F) {
+__global__ void ktq_end(KrylovArgs a, int32_t* __restrict__ F) {
   if (F[F_DONE]) return;
   const int iter = F[F_ITER] + 1;
   F[F_ITER] = iter;
-  F[F_NX_SPMV] += 2;
+  F[F_SPMV] += 2;
   if (iter > a.maxiter) F[F_DONE] = 1;
 }
 // iter % checkiter == 0: the true residual r = Pl(b - A x) just ran (:67-71)
-__global__ void ktq_check(NxArgs a, const double* __restrict__ S, int32_t* __restrict__ F) {
+__global__ void ktq_check(KrylovArgs a, const double* __restrict__ S, int32_t* __restrict__ F) {
   if (F[F_DONE]) return;
-  F[F_NX_SPMV] += 1;
+  F[F_SPMV] += 1;
   if (sqrt(S[S_RR] * a.n_inv) <= a.tol) F[F_DONE] = 1;
 }
 
@@ -206,7 +200,7 @@ __global__ void ktq_check(NxArgs a, const double* __restrict__ S, int32_t* __res
 enum { LQ_ALPHA = S_SOLVER + 0, LQ_BETA, LQ_PHIBAR, LQ_RHOBAR, LQ_PHIR, LQ_THETAR, LQ_VDIV, LQ_DOT = S_SOLVER + 8 };
 
 // beta = norm(u) (u = r: :18-19)
-__global__ void klq_init(NxArgs a, double* __restrict__ S, int32_t* __restrict__ F) {
+__global__ void klq_init(KrylovArgs a, double* __restrict__ S, int32_t* __restrict__ F) {
   nx_init(a, S, F, 1);
   S[LQ_BETA] = sqrt(S[S_RR]);
 }
@@ -301,88 +295,37 @@ __global__ __launch_bounds__(MFEM_BLOCK) void klq_xw(int64_t n2, d2_t* __restric
   }
 }
 // iter += 1 ; the true residual just ran ; stop if normalized_norm(r) <= tol || iter > maxiter  (:62-67)
-__global__ void klq_end(NxArgs a, const double* __restrict__ S, int32_t* __restrict__ F) {
+__global__ void klq_end(KrylovArgs a, const double* __restrict__ S, int32_t* __restrict__ F) {
   if (F[F_DONE]) return;
   const int iter = F[F_ITER] + 1;
   F[F_ITER] = iter;
-  F[F_NX_SPMV] += F[F_NX_SKIP] ? 2 : 3;
-  if ((!a.fixed && sqrt(S[S_RR] * a.n_inv) <= a.tol) || iter > a.maxiter) {
+  F[F_SPMV] += F[F_NX_SKIP] ? 2 : 3;
+  if (kk_converged(a, S[S_RR]) || iter > a.maxiter) {
     F[F_DONE] = 1;
     F[F_NX_SKIP] = 1;  // (the A' u product of a replay after DONE is skipped too)
   }
 }
 
 // =====================================================================================================================================
-#define RC(x)            \
-  do {                   \
-    int _rc = (x);       \
-    if (_rc) return _rc; \
-  } while (0)
-#define K1F(kernel, ...)                                                               \
-  do {                                                                                 \
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(MFEM_BLOCK), 0, ctx->stream, __VA_ARGS__); \
-    MFEM_CHECK_LAUNCH();                                                               \
-  } while (0)
-#define K1(kernel, ...)                                                       \
-  do {                                                                        \
-    hipLaunchKernelGGL(kernel, dim3(1), dim3(1), 0, ctx->stream, __VA_ARGS__); \
-    MFEM_CHECK_LAUNCH();                                                      \
-  } while (0)
-#define KV(kernel, ...)                                                              \
-  do {                                                                               \
-    hipLaunchKernelGGL(kernel, dim3(k.G), dim3(MFEM_BLOCK), 0, ctx->stream, __VA_ARGS__); \
-    MFEM_CHECK_LAUNCH();                                                             \
-  } while (0)
-
-static uint64_t nx_key(int method, mfem_csr_s* A, const double* vals, const KrylovVecs& V, double tol, int64_t n_global, const mfem_solve_options* o) {
-  uint64_t key = mfem_hash(MFEM_HASH_SEED, method);
-  key = mfem_csr_graph_key(key, A); key = mfem_hash(key, vals); key = mfem_hash(key, V.w[0]); key = mfem_hash(key, V.x);
-  key = mfem_hash(key, V.b); key = mfem_hash(key, V.nv); key = mfem_hash(key, tol); key = mfem_hash(key, n_global);
-  key = mfem_hash(key, o->maxiter); key = mfem_hash(key, o->fixed_iterations);
-  return key;
-}
-
-// The host loop every solver here shares: replay `step` (variant `alt` when alt_due(host iteration after the step)) until the device says DONE,
-// polling every check_every iterations and once the host's count passes maxiter.
-template <class Step, class Due>
-static int nx_drive(mfem_context_s* ctx, const mfem_solve_options* o, uint64_t key, Step step, Due alt_due, int* iters_out, int* spmv_out) {
-  const int check = o->check_every > 0 ? o->check_every : 32;
-  int since = 0, host_iter = 1;
-  RC(mfem_read_flags(ctx));
-  while (!ctx->h_flags[F_DONE]) {
-    const bool alt = alt_due(host_iter + 1);
-    RC(mfem_cycle_run(ctx, key ^ (alt ? 0x9E3779B97F4A7C15ull : 0ull), [&]() { return step(alt); }));
-    ++host_iter;
-    if (++since >= check || host_iter > o->maxiter) {
-      RC(mfem_read_flags(ctx));
-      since = 0;
-    }
-  }
-  RC(mfem_read_flags(ctx));
-  *iters_out = ctx->h_flags[F_ITER];
-  *spmv_out += ctx->h_flags[F_NX_SPMV];
-  return MFEM_OK;
-}
-
-int mfem_cgs_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o, double tol,
+// (all three: the stop rule iter > maxiter fires by host iteration maxiter + 1)
+int mfem_cgs_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o, int, double tol,
                   int64_t n_global, int* iters_out, int* spmv_out) {
   double* S = ctx->d_scalars;
   int32_t* F = ctx->d_flags;
   const int64_t nv = V.nv;
   double *r = V.w[0], *r0 = V.w[1], *u = V.w[2], *p = V.w[3], *s = V.w[4], *v = V.w[5];
   KK k{ctx, nv, V.n, mfem_vec_grid(ctx, nv), S, F, ctx->stream};
-  NxArgs a{1.0 / (double)n_global, tol, o->maxiter, o->fixed_iterations};
+  const KrylovArgs a = kk_args(tol, n_global, o);
   RC(mfem_pass_residual(ctx, A, vals, V, r, S + S_RR, spmv_out));  // :14-17
   K1(kcs_init, a, S, F);
   MFEM_CHECK_HIP(hipMemcpyAsync(r0, r, sizeof(double) * nv, hipMemcpyDeviceToDevice, ctx->stream));  // r0 = copy(r)
   for (double* z : {u, p, s, v}) MFEM_CHECK_HIP(hipMemsetAsync(z, 0, sizeof(double) * nv, ctx->stream));
-  int uncounted = 0;  // (the device counts the products)
-  auto step = [&](bool) -> int {
+  auto step = [&](int) -> int {
     FoldArg fa;
     RC(k.dot1_partials(r, r0, CS_DOT, &fa));
     K1F(kcs_beta, fa, S, F);
     KV(kcs_su, nv / 2, (const d2_t*)r, (const d2_t*)p, (d2_t*)s, (d2_t*)u, S, F);
-    RC(k.spmv(A, vals, u, v, &uncounted));
+    RC(k.spmv(A, vals, u, v));
     RC(k.dot1_partials(v, r0, CS_DOT, &fa));
     K1F(kcs_alpha, fa, S, F);
     KV(kcs_px, nv / 2, (const d2_t*)s, (const d2_t*)v, (d2_t*)p, (d2_t*)V.x, S, F);
@@ -391,7 +334,8 @@ int mfem_cgs_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Krylov
     K1(kcs_end, a, S, F);
     return MFEM_OK;
   };
-  return nx_drive(ctx, o, nx_key(MFEM_SOLVER_CGS, A, vals, V, tol, n_global, o), step, [](int) { return false; }, iters_out, spmv_out);
+  return kk_drive(ctx, o, mfem_pass_key(MFEM_SOLVER_CGS, A, vals, V, tol, n_global, o), 1, (int64_t)o->maxiter + 1, step, kc_main, iters_out,
+                  spmv_out);
 }
 
 int mfem_tfqmr_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o, int checkiter,
@@ -401,37 +345,37 @@ int mfem_tfqmr_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Kryl
   const int64_t nv = V.nv;
   double *r = V.w[0], *r0 = V.w[1], *rc = V.w[2], *p = V.w[3], *q = V.w[4], *u = V.w[5], *v = V.w[6], *d = V.w[7], *tmp = V.w[8];
   KK k{ctx, nv, V.n, mfem_vec_grid(ctx, nv), S, F, ctx->stream};
-  NxArgs a{1.0 / (double)n_global, tol, o->maxiter, o->fixed_iterations};
+  const KrylovArgs a = kk_args(tol, n_global, o);
   RC(mfem_pass_residual(ctx, A, vals, V, r, S + S_RR, spmv_out));  // :4-7
   K1(ktq_init, a, S, F);
   for (double* z : {r0, rc, p, u}) MFEM_CHECK_HIP(hipMemcpyAsync(z, r, sizeof(double) * nv, hipMemcpyDeviceToDevice, ctx->stream));  // :22-25
   for (double* z : {q, d, tmp}) MFEM_CHECK_HIP(hipMemsetAsync(z, 0, sizeof(double) * nv, ctx->stream));
-  int uncounted = 0;
-  RC(k.spmv(A, vals, p, v, &uncounted));  // v = Pl(A p)  (:26-27)
-  auto step = [&](bool check) -> int {
+  RC(k.spmv(A, vals, p, v));  // v = Pl(A p)  (:26-27)
+  auto step = [&](int form) -> int {
     FoldArg fa;
     RC(k.dot1_partials(v, r0, TQ_DOT, &fa));
     K1F(ktq_alpha, fa, S, F);
     KV(ktq_qv, nv / 2, (const d2_t*)u, (d2_t*)v, (d2_t*)q, S, F);
-    RC(k.spmv(A, vals, v, tmp, &uncounted));
+    RC(k.spmv(A, vals, v, tmp));
     KV(ktq_rcgs, V.n, nv / 2, (const d2_t*)tmp, (const d2_t*)r0, (d2_t*)rc, ctx->d_partials, S, F);
     K1F(ktq_scalars, FoldArg{ctx->d_partials, k.G, 2, TQ_DOT}, S, F);
     KV(ktq_update, nv / 2, (const d2_t*)rc, (const d2_t*)q, (d2_t*)u, (d2_t*)d, (d2_t*)p, (d2_t*)V.x, S, F);
-    RC(k.spmv(A, vals, p, v, &uncounted));
+    RC(k.spmv(A, vals, p, v));
     K1(ktq_end, a, F);
-    if (check) {  // (iter % checkiter == 0: the only iterations that compute a residual)
+    if (form == KC_ALT) {  // (iter % checkiter == 0: the only iterations that compute a residual)
       RC(mfem_true_residual(ctx, A, vals, V.b, V.x, r, nv, S + S_RR));
       K1(ktq_check, a, S, F);
     }
     return MFEM_OK;
   };
-  uint64_t key = nx_key(MFEM_SOLVER_TFQMR, A, vals, V, tol, n_global, o);
+  uint64_t key = mfem_pass_key(MFEM_SOLVER_TFQMR, A, vals, V, tol, n_global, o);
   key = mfem_hash(key, checkiter);
   const bool fixed = o->fixed_iterations != 0;
-  return nx_drive(ctx, o, key, step, [&](int iter) { return !fixed && iter % checkiter == 0; }, iters_out, spmv_out);
+  auto variant = [&](int, int64_t iter) { return !fixed && iter % checkiter == 0 ? KC_ALT : KC_MAIN; };
+  return kk_drive(ctx, o, key, 1, (int64_t)o->maxiter + 1, step, variant, iters_out, spmv_out);
 }
 
-int mfem_lsqr_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o, double tol,
+int mfem_lsqr_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o, int, double tol,
                    int64_t n_global, int* iters_out, int* spmv_out) {
   MFEM_REQUIRE(V.AT && (V.valsT || V.AT->nnz == 0), "lsqr!: the transposed working matrix is missing");
   double* S = ctx->d_scalars;
@@ -439,7 +383,7 @@ int mfem_lsqr_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Krylo
   const int64_t nv = V.nv;
   double *r = V.w[0], *u = V.w[1], *v = V.w[2], *w = V.w[3], *tmp = V.w[4];
   KK k{ctx, nv, V.n, mfem_vec_grid(ctx, nv), S, F, ctx->stream};
-  NxArgs a{1.0 / (double)n_global, tol, o->maxiter, o->fixed_iterations};
+  const KrylovArgs a = kk_args(tol, n_global, o);
   RC(mfem_pass_residual(ctx, A, vals, V, r, S + S_RR, spmv_out));  // :11-14
   K1(klq_init, a, S, F);
   for (double* z : {u, v, w, tmp}) MFEM_CHECK_HIP(hipMemsetAsync(z, 0, sizeof(double) * nv, ctx->stream));
@@ -450,10 +394,9 @@ int mfem_lsqr_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Krylo
   RC(k.dot1_partials(v, v, LQ_DOT, &fa0));
   K1F(klq_start, fa0, S, F);
   KV(klq_vw, nv / 2, (d2_t*)v, (d2_t*)w, S, F);
-  int uncounted = 0;
   const FoldArg fa{ctx->d_partials, k.G, 1, LQ_DOT};
-  auto step = [&](bool) -> int {
-    RC(k.spmv(A, vals, v, tmp, &uncounted));                                                        // tmp = A v
+  auto step = [&](int) -> int {
+    RC(k.spmv(A, vals, v, tmp));                                                        // tmp = A v
     KV(klq_lin_norm, V.n, nv / 2, (const d2_t*)tmp, (d2_t*)u, ctx->d_partials, (int)LQ_ALPHA, S, F, (int)F_DONE);  // u = Pl(tmp) - alpha u
     K1F(klq_beta, fa, S, F);                                                                         // beta = norm(u)
     KV(klq_uscale, nv / 2, (const d2_t*)u, (d2_t*)u, S, F, (int)F_NX_SKIP);                         // u ./= beta
@@ -465,7 +408,7 @@ int mfem_lsqr_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Krylo
     K1(klq_end, a, S, F);
     return MFEM_OK;
   };
-  uint64_t key = nx_key(MFEM_SOLVER_LSQR, A, vals, V, tol, n_global, o);
+  uint64_t key = mfem_pass_key(MFEM_SOLVER_LSQR, A, vals, V, tol, n_global, o);
   key = mfem_csr_graph_key(key, V.AT); key = mfem_hash(key, V.valsT);
-  return nx_drive(ctx, o, key, step, [](int) { return false; }, iters_out, spmv_out);
+  return kk_drive(ctx, o, key, 1, (int64_t)o->maxiter + 1, step, kc_main, iters_out, spmv_out);
 }
