@@ -522,6 +522,54 @@ int mfem_mesh_assemble_facets(mfem_context ctx, int32_t dim, int32_t itg_b, int3
                               double* K_val, const int32_t* facetIDs, int64_t n_items, int32_t n_colours,
                               const int64_t* colour_offsets);
 
+/* ---- fused residual on unstructured meshes (affine terms; new) --------------------------------------------------------
+ * The generic residual (mfem_op_var_batch + mfem_op_res_batch) reads the per-element physical tables of update_BasicElements.
+ * For residual terms that are AFFINE in the fields and the nodal externals -- every residual of the linear example forms --
+ * these entry points compute geometry, the words at the Gauss points and the terms on the fly, straight from coordinates,
+ * connectivity and the nodal arrays; no table is read or needed.
+ * A symbol is a word of a nodal array:  u(q) = sum_a D^word N_a(q) x[shift + cp(a, el)]  (x_star at time level td and field
+ * position pos: shift = td * n_fields * ncp + pos * ncp; a nodal external: shift 0).
+ * A term is  dual word (dual_pos, dual_sd)  x  v(q),  v = c0 + sum_p coef_p [n_normal_p] u_sym_p   (sym_p = -1: the constant 1;
+ * normal_p = j >= 0: the factor n_j of the outward normal, facets only).  Semantics = mfem_op_res with vals = v * w_q det_q
+ * (the surface det on facets), summed over the terms, to round-off.
+ * Pass 1 writes the element vectors to a library-owned scratch (n_items * itp * dual fields * 8 bytes), pass 2 gives every
+ * (dual field, control point) to a lane that adds the point's entries, in the order of its adjacency list, to
+ * residue[dual_pos * ncp + node]: residue is ACCUMULATED into; no atomics, bitwise reproducible.
+ * adj_ptr [ncp + 1], adj: for every control point the (item * itp + local node id) pairs that reference it, 0-based, ascending
+ * (elements: item = element; facets: item = facet, node = a node of the facet's host element).  A collapsed element (a node
+ * listed twice) has both entries.  MFEM_ERR_UNSUPPORTED beyond the caps below, for more than 8 dual fields or 128 distinct
+ * (symbol, normal) pairs per launch, and when one wave's tables exceed 64 KB of LDS: use the operator path then. */
+#define MFEM_RES_MAX_SYMBOLS 16
+#define MFEM_RES_MAX_TERMS 48
+#define MFEM_RES_MAX_PAIRS 8
+typedef struct {
+  int32_t word;             /* 0 = value, 1 + j = d/dx_j */
+  int32_t reserved;
+  int64_t shift;
+  const double* x;          /* [device] x_star or a nodal external */
+} mfem_res_symbol;
+typedef struct {
+  int32_t dual_pos, dual_sd;
+  int32_t n_pairs;          /* 0 .. MFEM_RES_MAX_PAIRS */
+  int32_t reserved;
+  double c0;
+  int32_t sym[8];           /* symbol index, or -1 = the constant 1 */
+  int32_t normal[8];        /* -1, or j: times n_j (facets) */
+  double coef[8];
+} mfem_affine_term;
+int mfem_mesh_residual_elements(mfem_context ctx, int32_t dim, int32_t itg, int32_t itp, int64_t nel, int64_t ncp,
+                                const double* ref_itp_vals, const double* itg_weight, const double* coords,
+                                const int32_t* controlpoint_IDs, int32_t index_base, int32_t n_symbols,
+                                const mfem_res_symbol* symbols, int32_t n_terms, const mfem_affine_term* terms,
+                                const int64_t* adj_ptr, const int32_t* adj, double* residue);
+/* The same on boundary facets (inputs of mfem_mesh_assemble_facets); weight = w_q * surface det, normals on the fly. */
+int mfem_mesh_residual_facets(mfem_context ctx, int32_t dim, int32_t itg_b, int32_t itp, int32_t n_face_ids, int64_t n_facets,
+                              int64_t ncp, const double* bdy_ref_itp_vals, const double* bdy_itg_weights,
+                              const double* bdy_tangent_directions, const double* coords, const int32_t* controlpoint_IDs,
+                              const int32_t* element_ID, const int32_t* element_eindex, int32_t index_base, int32_t n_symbols,
+                              const mfem_res_symbol* symbols, int32_t n_terms, const mfem_affine_term* terms,
+                              const int64_t* adj_ptr, const int32_t* adj, double* residue);
+
 /* ---- multi-GPU (new; the reference is single-GPU, F6) ------------------------------------ */
 /* 128-byte RCCL unique id, created on rank 0 and shipped to the other ranks by the host
  * (torch.distributed / MPI / a file).  */

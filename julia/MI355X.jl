@@ -138,6 +138,24 @@ struct ConstTerm                          # == mfem_const_term
     coef::Float64
 end
 
+struct ResSymbol                          # == mfem_res_symbol
+    word::Int32
+    reserved::Int32
+    shift::Int64
+    x::Ptr{Cvoid}
+end
+
+struct AffineTerm                         # == mfem_affine_term
+    dual_pos::Int32
+    dual_sd::Int32
+    n_pairs::Int32
+    reserved::Int32
+    c0::Float64
+    sym::NTuple{8, Int32}
+    normal::NTuple{8, Int32}
+    coef::NTuple{8, Float64}
+end
+
 # ---- S1 primitives: FEM_SpMat_CSR, mul!, dot, norm, FEM_rand ----------------------------------------------------------------
 """
 CSR pattern handle (no values): what `FEM_SpMat_CSR(K_J_ptr, K_J, K_vals, dims)` (misc/04_GPU_Utils.jl:120) wraps.
@@ -373,6 +391,39 @@ function assemble_const_terms!(K_linear, dim, itg, itp, nel, ncp, ref_itp_vals, 
                  Ptr{ConstTerm}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
                 ctx(), dim, itg, itp, nel, ncp, dptr(ref_itp_vals), dptr(itg_weight), dptr(coords), dptr(controlpoint_IDs), 1,
                 length(terms), terms, n_fields, A.h, dptr(adj_ptr), dptr(adj), dptr(ranks), dptr(K_linear)))
+end
+
+"""
+Unstructured meshes: the residual terms of an integration domain that are affine in the fields and nodal externals, in one call with geometry
+on the fly (no update_BasicElements tables).  `symbols`: words of x_star (shift = td * n_fields * ncp + pos * ncp) or of nodal externals (shift 0);
+`terms`: dual word x (c0 + sum_p coef_p [n_normal_p] symbol_p), normal = -1 on elements.  `adj_ptr`, `adj`: the adjacency of `row_ranks!`.
+residue is ACCUMULATED into.  Returns false (nothing added) on MFEM_ERR_UNSUPPORTED: the generated operator updater takes the terms then.
+"""
+function residual_affine_terms!(residue, dim, itg, itp, nel, ncp, ref_itp_vals, itg_weight, coords, controlpoint_IDs,
+                                symbols::Vector{ResSymbol}, terms::Vector{AffineTerm}, adj_ptr, adj)
+    rc = ccall((:mfem_mesh_residual_elements, lib), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Int32, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32,
+                Ptr{ResSymbol}, Int32, Ptr{AffineTerm}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+               ctx(), dim, itg, itp, nel, ncp, dptr(ref_itp_vals), dptr(itg_weight), dptr(coords), dptr(controlpoint_IDs), 1,
+               length(symbols), symbols, length(terms), terms, dptr(adj_ptr), dptr(adj), dptr(residue))
+    rc == -3 && return false
+    check(rc)
+    return true
+end
+
+"""The same on boundary facets (element_ID / element_eindex 1-based; `adj` lists (facet * itp + local node) per control point)."""
+function residual_affine_facets!(residue, dim, itg_b, itp, n_face_ids, nf, ncp, bdy_ref_itp_vals, bdy_itg_weights, bdy_tangent_directions,
+                                 coords, controlpoint_IDs, element_ID, element_eindex, symbols::Vector{ResSymbol}, terms::Vector{AffineTerm},
+                                 adj_ptr, adj)
+    rc = ccall((:mfem_mesh_residual_facets, lib), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+                Ptr{Cvoid}, Int32, Int32, Ptr{ResSymbol}, Int32, Ptr{AffineTerm}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+               ctx(), dim, itg_b, itp, n_face_ids, nf, ncp, dptr(bdy_ref_itp_vals), dptr(bdy_itg_weights), dptr(bdy_tangent_directions),
+               dptr(coords), dptr(controlpoint_IDs), dptr(element_ID), dptr(element_eindex), 1, length(symbols), symbols, length(terms), terms,
+               dptr(adj_ptr), dptr(adj), dptr(residue))
+    rc == -3 && return false
+    check(rc)
+    return true
 end
 
 function row_ranks!(ranks::ROCArray{UInt16}, itp, nel, ncp, n_fields, A::CSRPattern, adj_ptr, adj, controlpoint_IDs)

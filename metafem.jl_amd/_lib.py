@@ -94,6 +94,18 @@ class ConstTerm(C.Structure):
 MAX_BATCH_TERMS = 48
 
 
+class ResSymbol(C.Structure):
+    _fields_ = [("word", c_int32), ("reserved", c_int32), ("shift", c_int64), ("x", C.c_void_p)]
+
+
+class AffineTerm(C.Structure):
+    _fields_ = [("dual_pos", c_int32), ("dual_sd", c_int32), ("n_pairs", c_int32), ("reserved", c_int32), ("c0", c_double),
+                ("sym", c_int32 * 8), ("normal", c_int32 * 8), ("coef", c_double * 8)]
+
+
+MAX_RES_SYMBOLS, MAX_RES_TERMS, MAX_RES_PAIRS = 16, 48, 8  # MFEM_RES_MAX_*
+
+
 ALLREDUCE_CB = C.CFUNCTYPE(c_int, c_void_p, C.POINTER(c_double), c_int32)
 EXCHANGE_CB = C.CFUNCTYPE(c_int, c_void_p, C.POINTER(c_double), C.POINTER(c_double), C.POINTER(c_double), C.POINTER(c_double), c_int64)
 
@@ -197,6 +209,11 @@ SIGNATURES = {
     "mfem_mesh_row_ranks": (c_int, [P, c_int32, c_int64, c_int64, c_int32, P, P, P, P, c_int32, P]),
     "mfem_mesh_assemble_facets": (c_int, [P, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, P, P, P, c_int32,
                                           c_int32, C.POINTER(ConstTerm), P, c_int64, P, P, c_int64, c_int32, C.POINTER(c_int64)]),
+    "mfem_mesh_residual_elements": (c_int, [P, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, c_int32, c_int32,
+                                            C.POINTER(ResSymbol), c_int32, C.POINTER(AffineTerm), P, P, P]),
+    "mfem_mesh_residual_facets": (c_int, [P, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, P, P, P, c_int32,
+                                          c_int32, C.POINTER(ResSymbol), c_int32, C.POINTER(AffineTerm), P, P, P]),
+    "mfem_debug_mesh_residual_count": (c_int64, []),
     "mfem_comm_unique_id": (c_int, [P]),
     "mfem_comm_create": (c_int, [P, c_int32, c_int32, P, C.POINTER(P)]),
     "mfem_comm_destroy": (c_int, [P]),

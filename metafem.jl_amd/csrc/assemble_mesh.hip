@@ -14,7 +14,7 @@
 //      the q loop runs once per pair, not once per term;
 //   4. the sums of the terms of one sparse block are added to K through the slot table of mfem_pattern_build --
 //      plain read-modify-write inside a colour (no two elements of a colour share a control point), FP64 atomics otherwise.
-#include "common.h"
+#include "mesh_geometry.h"
 
 #define MA_MAX_TERMS 48
 struct ConstTerms {
@@ -32,50 +32,9 @@ struct TermMatrix {
   double c[MA_MAX_RUNS][16];
 };
 
-struct MeshItems {
-  int itg, itp;
-  int64_t ncp;
-  const double* ref;     // [n_face_ids][itg, itp, 1 + dim]
-  int64_t ref_stride;
-  const double* wq;      // [n_face_ids][itg]
-  int64_t w_stride;
-  const double* tan;     // facets: [n_face_ids][itg, dim, dim - 1]; elements: nullptr
-  int64_t tan_stride;
-  const double* coords;  // SoA
-  const int32_t* cp;     // [itp, nel]
-  const int32_t* host_el;   // facets: element of item h; elements: nullptr
-  const int32_t* eindex;    // facets: local face id of item h
-  const int32_t* order;     // item processed by work unit t (colour order); nullptr = identity
-  int base;
-};
-
 int g_mesh_stage_min_itp = 16;  // mfem_debug_set("mesh_stage_min_itp"): elements from this many nodes take the staged persistent form of the row-owner kernel
 int g_mesh_term_matrix = 1;  // mfem_debug_set("mesh_term_matrix"): 0 = the non-staged element kernel walks the term list (A/B)
 int g_mesh_abl = 0;  // mfem_debug_set("mesh_abl"): ablation of k_mesh_assemble phases (tools/u20_assembly_ab.py): 1 no pair products, 2 no stores, 4 no geometry, 8 no table, 16 no coordinate gather
-
-template <int DIM>
-__device__ __forceinline__ double ma_inv(const double (&J)[3][3], double (&I)[3][3]) {
-  if (DIM == 2) {
-    const double det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-    I[0][0] = J[1][1] / det;
-    I[0][1] = -J[0][1] / det;
-    I[1][0] = -J[1][0] / det;
-    I[1][1] = J[0][0] / det;
-    return det;
-  }
-  const double det = J[0][0] * J[1][1] * J[2][2] - J[0][0] * J[1][2] * J[2][1] - J[0][1] * J[1][0] * J[2][2] +
-                     J[0][1] * J[1][2] * J[2][0] + J[0][2] * J[1][0] * J[2][1] - J[0][2] * J[1][1] * J[2][0];
-  I[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) / det;
-  I[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) / det;
-  I[0][2] = (J[0][1] * J[1][2] - J[1][1] * J[0][2]) / det;
-  I[1][0] = (J[1][2] * J[2][0] - J[2][2] * J[1][0]) / det;
-  I[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) / det;
-  I[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) / det;
-  I[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) / det;
-  I[2][1] = (J[0][1] * J[2][0] - J[2][1] * J[0][0]) / det;
-  I[2][2] = (J[0][0] * J[1][1] - J[1][0] * J[0][1]) / det;
-  return det;
-}
 
 // S0 = first physical-table slot the terms use (0 value, 1 first derivative), NS = number of consecutive slots from S0:
 // (0, 1 + DIM) everything, (1, DIM) gradients only, (0, 1) values only.
@@ -137,77 +96,12 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_mesh_assemble(MeshItems V, Const
   __builtin_amdgcn_wave_barrier();
   // ---- geometry per Gauss point (lane <-> q)
   const bool split_j = STAGE && 2 * itg <= 64;  // (hex-20 / hex-27 with 27 Gauss points: two lane groups share a point's Jacobian sum, half the nodes each)
-  for (int q0 = 0; q0 < ((abl & 4) ? 0 : itg); q0 += 64) {
-    const int hq = split_j ? lane / itg : 0, q = split_j ? lane - hq * itg : q0 + lane;
-    const int half = split_j ? (itp + 1) >> 1 : itp;
-    const int a_lo = hq < 2 ? hq * half : 0, a_hi = hq < 2 ? (a_lo + half < itp ? a_lo + half : itp) : 0;
-    const bool qon = q < itg;
-    double J[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-    for (int a = a_lo; a < a_hi; ++a) {
-#pragma unroll
-      for (int m = 0; m < DIM; ++m) {
-        const double r = R[(qon ? q : 0) + itg * (a + itp * (1 + m))];
-#pragma unroll
-        for (int i = 0; i < DIM; ++i) J[i][m] += r * X[a * DIM + i];
-      }
-    }
-    if (split_j) {
-#pragma unroll
-      for (int i = 0; i < DIM; ++i)
-#pragma unroll
-        for (int m = 0; m < DIM; ++m) J[i][m] += __shfl_down(J[i][m], itg);  // (group 0 takes group 1's half)
-    }
-    if (!qon || hq != 0) continue;
-    double I[3][3];
-    const double det = ma_inv<DIM>(J, I);
-#pragma unroll
-    for (int m = 0; m < DIM; ++m)
-#pragma unroll
-      for (int s = 0; s < DIM; ++s) Ji[q * DIM * DIM + m * DIM + s] = I[m][s];
-    if (!V.eindex) {
-      wd[q] = V.wq[q] * det;
-    } else {  // surface weight: |J t1 x J t2| (3-D) or |J t1| (2-D)   4_Update_Integrator.jl:163-227
-      const double* Tn = V.tan + (int64_t)f * V.tan_stride;
-      double tg[3][2] = {{0, 0}, {0, 0}, {0, 0}};
-#pragma unroll
-      for (int i = 0; i < DIM; ++i)
-#pragma unroll
-        for (int k = 0; k < DIM - 1; ++k)
-#pragma unroll
-          for (int m = 0; m < DIM; ++m) tg[i][k] += J[i][m] * Tn[q + itg * (m + DIM * k)];
-      double ld;
-      if (DIM == 2) {
-        ld = sqrt(tg[0][0] * tg[0][0] + tg[1][0] * tg[1][0]);
-      } else {
-        const double r0 = tg[1][0] * tg[2][1] - tg[2][0] * tg[1][1];
-        const double r1 = -tg[0][0] * tg[2][1] + tg[2][0] * tg[0][1];
-        const double r2 = tg[0][0] * tg[1][1] - tg[1][0] * tg[0][1];
-        ld = sqrt(r0 * r0 + r1 * r1 + r2 * r2);
-      }
-      wd[q] = V.wq[(int64_t)f * V.w_stride + q] * ld;
-    }
-  }
+  mg_geometry<DIM>(V, R, X, f, lane, (abl & 4) ? 0 : itg, split_j, Ji, wd, nullptr);
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_s_waitcnt(0xC07F);
   __builtin_amdgcn_wave_barrier();
   // ---- physical table T[q][a][s - S0]  (lane <-> (q, a))
-  for (int i = lane; i < ((abl & 8) ? 0 : itg * itp); i += 64) {
-    const int q = i % itg, a = i / itg;
-    double* o = Tt + ((size_t)q * itp + a) * NS;
-    if (S0 == 0) o[0] = R[q + itg * a];
-    if (NS > 1 || S0 == 1) {
-      double r[3];
-#pragma unroll
-      for (int m = 0; m < DIM; ++m) r[m] = R[q + itg * (a + itp * (1 + m))];
-#pragma unroll
-      for (int s = 0; s < DIM; ++s) {
-        double v = 0.0;
-#pragma unroll
-        for (int m = 0; m < DIM; ++m) v += r[m] * Ji[q * DIM * DIM + m * DIM + s];
-        o[(1 - S0) + s] = v;
-      }
-    }
-  }
+  mg_table<DIM, S0, NS>(R, Ji, Tt, itg, itp, lane, (abl & 8) ? 0 : itg * itp);
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_s_waitcnt(0xC07F);
   __builtin_amdgcn_wave_barrier();

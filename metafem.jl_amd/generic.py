@@ -23,6 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
+from .affine import AffineResidual, affine_residual  # noqa: F401  (the residual-side generalisation of constant_coefficient)
 
 
 @dataclass
@@ -90,13 +91,29 @@ def constant_coefficient(fn) -> Optional[float]:
 
 
 class _Group:
-    """Integration hosts of one launch family (the elements, or the facets of one boundary group)."""
+    """Integration hosts of one launch family (the elements, or the facets of one boundary group).  The geometry tables of the
+    operator path (vals, weights, normals: update_BasicElements / update_BasicBoundary) are built by `build` on first access."""
 
-    def __init__(self, vals, weights, host_ids, el_ids, itg, normals=None, colour_offsets=None, facet_el=None, facet_eidx=None):
-        self.vals, self.weights, self.host_ids, self.el_ids, self.itg = vals, weights, host_ids, el_ids, itg
-        self.normals, self.colour_offsets = normals, colour_offsets
+    def __init__(self, build, host_ids, el_ids, itg, colour_offsets=None, facet_el=None, facet_eidx=None):
+        self._build, self._tables = build, None
+        self.host_ids, self.el_ids, self.itg = host_ids, el_ids, itg
+        self.colour_offsets = colour_offsets
         self.facet_el, self.facet_eidx = facet_el, facet_eidx  # boundary groups: element / local face id of every facet
         self.n = el_ids.numel()
+        self.adj = None  # (adj_ptr, adj) of the fused residual, built on first use
+
+    def tables(self):
+        if self._tables is None:
+            self._tables = self._build()
+        return self._tables
+
+    vals = property(lambda self: self.tables()[0])
+    weights = property(lambda self: self.tables()[1])
+    normals = property(lambda self: self.tables()[2])
+
+    @property
+    def table_bytes(self) -> int:
+        return 0 if self._tables is None else sum(t.numel() * t.element_size() for t in self._tables if t is not None)
 
 
 class GenericDomain:
@@ -105,7 +122,7 @@ class GenericDomain:
     def __init__(self, ctx, space, coords: np.ndarray, cp_ids: np.ndarray, n_fields: int, domain_wf: WeakForm,
                  boundaries: Sequence[Tuple[np.ndarray, np.ndarray, WeakForm]],
                  element_colours: Optional[np.ndarray] = None, max_time_level: int = 0, dissipative: bool = True,
-                 batched: bool = True, fused: bool = True, row_owner: bool = True):
+                 batched: bool = True, fused: bool = True, row_owner: bool = True, fused_residual: bool = False):
         """coords [ncp, dim]; cp_ids [itp, nel] 0-based (controlpoint_IDs in basis order); boundaries =
         [(element_ID[nf], element_eindex[nf] 0-based local face ids, WeakForm)].  element_colours (optional):
         a colour per element such that same-colour elements share no control point -> atomics-free scatter with a fixed
@@ -121,6 +138,11 @@ class GenericDomain:
         # row_owner = True: the fused element assembly runs in its row-owner form (mfem_mesh_assemble_elements_rows: element
         # matrices -> scratch -> one wave per CSR row; no atomics, fixed summation order); False: scatter through the slot table
         self.row_owner = row_owner
+        # fused_residual = True: residual terms affine in the fields and externals (affine.affine_residual) go through
+        # mfem_mesh_residual_elements / _facets (geometry on the fly, one launch per integration domain); the other terms keep the
+        # operator path, and the geometry tables it reads are built only if some group still needs them (table_bytes)
+        self.fused_residual = fused_residual
+        self._affine_cache: Dict[Tuple[int, int], Tuple[Tuple[float, float], list]] = {}
         dev = f"cuda:{ctx.device}"
         self.dev = dev
         dim = space.dim
@@ -141,10 +163,13 @@ class GenericDomain:
         flat = np.ascontiguousarray(cp_ids.T).ravel()
         self._adj = i32(np.argsort(flat, kind="stable"))
         self._adj_ptr = torch.tensor(np.concatenate([[0], np.cumsum(np.bincount(flat, minlength=ncp))]), dtype=torch.int64, device=dev)
-        vals = torch.empty(space.itg * itp * nsd * nel, dtype=torch.float64, device=dev)
-        w = torch.empty(space.itg * nel, dtype=torch.float64, device=dev)
-        check(lib.mfem_update_basic_elements(ctx._h, dim, space.itg, itp, nel, ncp, ref.data_ptr(), f64(space.itg_weight).data_ptr(),
-                                             self.coords.data_ptr(), self.cp.data_ptr(), 1, vals.data_ptr(), w.data_ptr()))
+
+        def element_tables():
+            vals = torch.empty(space.itg * itp * nsd * nel, dtype=torch.float64, device=dev)
+            w = torch.empty(space.itg * nel, dtype=torch.float64, device=dev)
+            check(lib.mfem_update_basic_elements(ctx._h, dim, space.itg, itp, nel, ncp, ref.data_ptr(), self._itgw.data_ptr(),
+                                                 self.coords.data_ptr(), self.cp.data_ptr(), 1, vals.data_ptr(), w.data_ptr()))
+            return vals, w, None
         auto_colours = isinstance(element_colours, str)
         if auto_colours:
             if element_colours != "auto":
@@ -158,7 +183,7 @@ class GenericDomain:
         else:
             order, offs = np.arange(nel), None
         ids = i32(order + 1)
-        self.groups = [_Group(vals, w, ids, ids, space.itg, colour_offsets=offs)]
+        self.groups = [_Group(element_tables, ids, ids, space.itg, colour_offsets=offs)]
         nface = space.bdy_ref_itp_vals.shape[0]
         bref = f64(np.concatenate([space.bdy_ref_itp_vals[f].ravel(order="F") for f in range(nface)]))
         bw = f64(space.bdy_itg_weights.ravel())
@@ -166,13 +191,16 @@ class GenericDomain:
         self._bref, self._bw, self._btan, self._nface = bref, bw, btan, nface
         for el, eidx, _ in boundaries:
             nf = len(el)
-            fv = torch.empty(space.itg_b * itp * nsd * nf, dtype=torch.float64, device=dev)
-            fw = torch.empty(space.itg_b * nf, dtype=torch.float64, device=dev)
-            fn = torch.empty(space.itg_b * dim * nf, dtype=torch.float64, device=dev)
             eld, eid = i32(np.asarray(el) + 1), i32(np.asarray(eidx) + 1)
-            check(lib.mfem_update_basic_boundary(ctx._h, dim, space.itg_b, itp, nface, nf, ncp, bref.data_ptr(), bw.data_ptr(),
-                                                 btan.data_ptr(), self.coords.data_ptr(), self.cp.data_ptr(), eld.data_ptr(),
-                                                 eid.data_ptr(), 1, fv.data_ptr(), fw.data_ptr(), fn.data_ptr()))
+
+            def facet_tables(nf=nf, eld=eld, eid=eid):
+                fv = torch.empty(space.itg_b * itp * nsd * nf, dtype=torch.float64, device=dev)
+                fw = torch.empty(space.itg_b * nf, dtype=torch.float64, device=dev)
+                fn = torch.empty(space.itg_b * dim * nf, dtype=torch.float64, device=dev)
+                check(lib.mfem_update_basic_boundary(ctx._h, dim, space.itg_b, itp, nface, nf, ncp, bref.data_ptr(), bw.data_ptr(),
+                                                     btan.data_ptr(), self.coords.data_ptr(), self.cp.data_ptr(), eld.data_ptr(),
+                                                     eid.data_ptr(), 1, fv.data_ptr(), fw.data_ptr(), fn.data_ptr()))
+                return fv, fw, fn.view(nf, dim, space.itg_b)
             if auto_colours and nf > 0:
                 # boundary operators touch every node of the host element (05_CodeGenerator.jl:175-189): colour the facets
                 # by their hosts' node sets (two facets of one element conflict automatically)
@@ -180,12 +208,14 @@ class GenericDomain:
                 forder = np.argsort(fcol, kind="stable")
                 foffs = np.concatenate([[0], np.cumsum(np.bincount(fcol, minlength=int(fcol.max()) + 1))])
                 host = i32(forder + 1)
-                self.groups.append(_Group(fv, fw, host, i32(np.asarray(el)[forder] + 1), space.itg_b,
-                                          normals=fn.view(nf, dim, space.itg_b), colour_offsets=foffs, facet_el=eld, facet_eidx=eid))
+                self.groups.append(_Group(facet_tables, host, i32(np.asarray(el)[forder] + 1), space.itg_b, colour_offsets=foffs,
+                                          facet_el=eld, facet_eidx=eid))
                 continue
             host = i32(np.arange(nf) + 1)
-            self.groups.append(_Group(fv, fw, host, eld, space.itg_b, normals=fn.view(nf, dim, space.itg_b), facet_el=eld,
-                                      facet_eidx=eid))
+            self.groups.append(_Group(facet_tables, host, eld, space.itg_b, facet_el=eld, facet_eidx=eid))
+        if not fused_residual:  # (the operator path reads the tables at every residual: built here, as they always were)
+            for g in self.groups:
+                g.tables()
         # ---- assemble_Global_Variables!
         from . import assemble_SparseID  # late import: package root defines it
 
@@ -412,13 +442,82 @@ class GenericDomain:
             K.zero_()
             self._K_fresh = False
 
+    @property
+    def table_bytes(self) -> int:
+        """Bytes of geometry tables (vals, weights, normals of every group) currently allocated."""
+        return sum(g.table_bytes for g in self.groups)
+
+    def _affine_terms(self, i: int, wf: WeakForm):
+        """[AffineResidual or None] per residual term of part i, for the current t / dt (re-analysed when they change)."""
+        key = (float(self.t), float(self.dt))
+        hit = self._affine_cache.get(i)
+        if hit is None or hit[0] != key:
+            from .affine import affine_residual
+
+            hit = (key, [affine_residual(t, wf, t=key[0], dt=key[1]) for t in wf.residues])
+            self._affine_cache[i] = hit
+        return hit[1]
+
+    def _residual_adj(self, g: _Group):
+        if g.facet_el is None:
+            return self._adj_ptr, self._adj
+        if g.adj is None:  # facets: (facet * itp + local node) per control point of the host elements, ascending
+            flat = (self.cp[(g.facet_el - 1).long()] - 1).reshape(-1).long()
+            adj = torch.sort(flat, stable=True)[1].to(torch.int32)
+            ptr = torch.zeros(self.ncp + 1, dtype=torch.int64, device=self.dev)
+            ptr[1:] = torch.cumsum(torch.bincount(flat, minlength=self.ncp), 0)
+            g.adj = (ptr, adj)
+        return g.adj
+
+    def _residual_fused(self, g: _Group, descs) -> bool:
+        """One fused residual launch for the affine terms of a group; False (nothing added) if they exceed the caps."""
+        from .affine import CapsExceeded, pack_affine
+
+        def source(k):
+            if k[0] == "x":
+                _, pos, td, word = k
+                return word, td * self.basicfield_size + pos * self.ncp, self.x_star.data_ptr()
+            x = self.controlpoints[k[1]]
+            if x.dtype != torch.float64 or not x.is_contiguous() or x.numel() < self.ncp or x.device != self.x_star.device:
+                raise CapsExceeded(f"external {k[1]!r}: not a contiguous float64 device array of ncp entries")
+            return k[2], 0, x.data_ptr()
+
+        try:
+            syms, nsym, terms, nterm, _ = pack_affine(descs, source)
+        except CapsExceeded:
+            return False
+        ptr, adj = self._residual_adj(g)
+        if g.facet_el is None:
+            rc = lib.mfem_mesh_residual_elements(self.ctx._h, self.dim, self.space.itg, self.itp, self.nel, self.ncp, self._ref.data_ptr(),
+                                                 self._itgw.data_ptr(), self.coords.data_ptr(), self.cp.data_ptr(), 1, nsym, syms, nterm,
+                                                 terms, ptr.data_ptr(), adj.data_ptr(), self.residue.data_ptr())
+        else:
+            rc = lib.mfem_mesh_residual_facets(self.ctx._h, self.dim, self.space.itg_b, self.itp, self._nface, g.facet_el.numel(), self.ncp,
+                                               self._bref.data_ptr(), self._bw.data_ptr(), self._btan.data_ptr(), self.coords.data_ptr(),
+                                               self.cp.data_ptr(), g.facet_el.data_ptr(), g.facet_eidx.data_ptr(), 1, nsym, syms, nterm,
+                                               terms, ptr.data_ptr(), adj.data_ptr(), self.residue.data_ptr())
+        if rc == -3:  # MFEM_ERR_UNSUPPORTED (caps, LDS): the operator path takes these terms
+            return False
+        check(rc)
+        return True
+
     def K_nonlinear_func(self):
         self.residue.zero_()
         if self.K_total_private and self.K_total is self.K_linear:
             self.K_total = torch.empty_like(self.K_linear)
         if self.K_total is not self.K_linear:
             self.K_total.copy_(self.K_linear)  # 05_CodeGenerator.jl:282-283
-        for wf, g in self._parts():
+        for i, (wf, g) in enumerate(self._parts()):
+            residues = wf.residues
+            if self.fused_residual and not residues and not wf.nonlinear_gradients:
+                continue  # (nothing to add: the operator path would only build the tables)
+            if self.fused_residual and residues:
+                descs = self._affine_terms(i, wf)
+                aff = [d for d in descs if d is not None]
+                if aff and self._residual_fused(g, aff):
+                    residues = [t for t, d in zip(wf.residues, descs) if d is None]
+                if not residues and not wf.nonlinear_gradients:
+                    continue
             env: dict = {}
             if self.batched:
                 tg = self._var_many(g, [(s, td * self.basicfield_size + pos * self.ncp, self.x_star) for _, pos, s, td in wf.inner_vars])
@@ -426,14 +525,14 @@ class GenericDomain:
                     env[name] = t
                 self._externals(wf, g, env)
                 w = self._w(g)
-                self._res_many(g, wf.residues, env, w)
+                self._res_many(g, residues, env, w)
                 self._kval_many(g, wf.nonlinear_gradients, env, w, self.K_total)
                 continue
             for name, pos, s, td in wf.inner_vars:  # declare_Innervar_GPU (:1-13)
                 env[name] = self._var(g, s, td * self.basicfield_size + pos * self.ncp, self.x_star)
             self._externals(wf, g, env)
             w = self._w(g)
-            for t in wf.residues:
+            for t in residues:
                 self._res(g, t, self._vals(t.fn, env, w))
             for t in wf.nonlinear_gradients:
                 self._kval(g, t, self._vals(t.fn, env, w, self.K_params[t.td_order]), self.K_total)
