@@ -5,12 +5,18 @@ Metric (BASELINE.json): DOF-updates/s = n_DOF x Krylov iterations / (t_assembly 
 (solver/04_Time_Domain.jl:59-80) runs for one Newton step with a capped solver: fused K + matrix-free R + `--iters` Krylov steps (bench_legs.py).
 
 --config c2 (default): 3-D thermal conduction, linear hex-8, Jacobi-PCG; N = 1 workload = the size the north_star's target is quoted on, 512^3
-    (135 005 697 DOF, nnz 3.63e9, int64 row pointers).  The default N = 1 invocation also runs configs[1] (256^3), configs[2] (c3: hex-8 elasticity,
-    bicgstabl_GS!(2)), configs[3] (c4: hex-27, CG) + the FP64-MFMA roofline of the hex-27 Ke kernels, the reference's own solver / boundary-condition path
-    (idrs!(8); Nitsche-Dirichlet nonsymmetric K), a Newton-sized step and the unstructured hex-20 path for a few timed steps each.
+    (135 005 697 DOF, nnz 3.63e9, int64 row pointers).
 --config c3 | c4 | ref_idrs8 | nitsche_c2 | nitsche_c4: that leg alone, at any N.
+A plain run does what the headline needs and nothing else: set up, warm up, time the steps, check the last timed solve, --dump-outputs, the line.
+Its `roofline` is the Krylov loop's SpMV as timed inside the steps, priced with the committed counter file.
+--full: everything else as well, each measured after the headline.  With the default N = 1 invocation that is configs[1] (256^3), configs[2]
+    (c3: hex-8 elasticity, bicgstabl_GS!(2)), configs[3] (c4: hex-27, CG) + the FP64-MFMA roofline of the hex-27 Ke kernels, the reference's own
+    solver / boundary-condition path (idrs!(8); Nitsche-Dirichlet nonsymmetric K), a Newton-sized step, the unstructured hex-20 / tet-10 paths, the
+    CSR kernel behind mul! on the hex-8 and hex-27 matrices, the HBM counters of the headline kernels collected in the run and the CPU baseline;
+    with N > 1 and weak scaling, the strong-scaling leg.
 N > 1: `--scaling weak` (default) = an --n thick slab per rank; `--scaling strong` = the config's n^3 mesh cut into N slabs.  `--dry 1`: everything except
-device work (rank spawn, slab planes, halo sizes, workspace bytes per rank, the compact line) -- runs without a GPU (tests/test_bench_report.py at world 8).
+device work (rank spawn, slab planes, halo sizes, workspace bytes per rank, the compact line) -- runs without a GPU (tests/test_bench_report.py at world 8);
+its plan includes the strong-scaling leg of a --full run.
 
 Output: rank 0 prints ONE compact JSON line (<= 8 KB: bench_report.compact_line -- contract keys, `roofline`, `cpu_baseline`, one small object per leg) and
 writes the full result object (notes, sources, per-leg rooflines, time_to_tol, ...) to the side file the line names in `full`.  A failing SECONDARY leg
@@ -34,31 +40,34 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the side measurements the options below select (other configs and sizes, per-kernel rooflines, "
+                         "counters collected in the run, the CPU baseline, the strong-scaling leg); without it a run times the headline workload alone")
     ap.add_argument("--config", choices=["c2", "c3", "c4", "nitsche_c2", "nitsche_c4", "ref_idrs8"], default="c2")
     ap.add_argument("--n", type=int, default=0, help="elements per side of the per-GPU mesh (0 = the config's size: 512 / 128 / 128)")
     ap.add_argument("--iters", type=int, default=200, help="Krylov iterations per step (BiCGStab(2) / IDR(s): SpMV-equivalent steps)")
-    ap.add_argument("--cpu-n", type=int, default=192, help="elements per side of the CPU-baseline sample (0 = skip)")
+    ap.add_argument("--cpu-n", type=int, default=192, help="--full: elements per side of the CPU-baseline sample (0 = skip)")
     ap.add_argument("--cpu-repeats", type=int, default=3, help="timed CPU steps (the median is reported)")
-    ap.add_argument("--secondary-n", type=int, default=256, help="c2 at N = 1: also run this mesh size (configs[1]) for a few steps (0 = skip)")
+    ap.add_argument("--secondary-n", type=int, default=256, help="--full, c2 at N = 1: also run this mesh size (configs[1]) for a few steps (0 = skip)")
     ap.add_argument("--secondary-steps", type=int, default=5)
-    ap.add_argument("--hex27-n", type=int, default=128, help="c2 at N = 1: CSR-kernel roofline on the hex-27 matrix of this size (0 = skip)")
+    ap.add_argument("--hex27-n", type=int, default=128, help="--full, c2 at N = 1: CSR-kernel roofline on the hex-27 matrix of this size (0 = skip)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
-    ap.add_argument("--secondary-configs", type=int, default=1, help="c2 at N = 1, default size: also run configs[2], configs[3] and the hex-27 Ke MFMA roofline (0 = skip)")
+    ap.add_argument("--secondary-configs", type=int, default=1, help="--full, c2 at N = 1, default size: also run configs[2], configs[3] and the hex-27 Ke MFMA roofline (0 = skip)")
     ap.add_argument("--secondary-config-n", type=int, default=0,
                     help="elements per side of the secondary legs of the default line (0 = the configs' own sizes; a smaller value makes the legs run at any --n: "
                          "functional checks of the line's schema)")
-    ap.add_argument("--ref-legs", type=int, default=1, help="c2 at N = 1, default size: also run the reference's own solver / boundary-condition path (0 = skip)")
+    ap.add_argument("--ref-legs", type=int, default=1, help="--full, c2 at N = 1, default size: also run the reference's own solver / boundary-condition path (0 = skip)")
     ap.add_argument("--newton-like", type=int, default=20, help="secondary 256^3 leg: also time assembly + a solve of this many iterations (0 = skip)")
-    ap.add_argument("--tet10-n", type=int, default=64, help="c2 at N = 1, default size: the unstructured legs on a 10-node tetrahedron mesh (an n^3 brick cut into tetrahedra), thermal and "
+    ap.add_argument("--tet10-n", type=int, default=64, help="--full, c2 at N = 1, default size: the unstructured legs on a 10-node tetrahedron mesh (an n^3 brick cut into tetrahedra), thermal and "
                     "3-field elasticity with idrs!(8); 0 = skip")
-    ap.add_argument("--u20-n", type=int, default=96, help="c2 at N = 1, default size: unstructured serendipity hex-20 legs (thermal, elasticity) of this many elements "
+    ap.add_argument("--u20-n", type=int, default=96, help="--full, c2 at N = 1, default size: unstructured serendipity hex-20 legs (thermal, elasticity) of this many elements "
                                                           "per side through mfem_pattern_build + mfem_mesh_assemble_elements_rows + idrs!(8) (0 = skip)")
     ap.add_argument("--time-to-tol", type=int, default=1, help="c3 legs: also solve the same system to 1e-8 ||r0|| with bicgstabl_GS!(2), idrs!(8), cg! (0 = skip)")
-    ap.add_argument("--strong-leg", type=int, default=1, help="N > 1, weak: also time THE config's n^3 mesh cut into N slabs -> `strong_scaling` (0 = skip)")
+    ap.add_argument("--strong-leg", type=int, default=1, help="--full, N > 1, weak: also time THE config's n^3 mesh cut into N slabs -> `strong_scaling` (0 = skip)")
     ap.add_argument("--strong-leg-timeout", type=float, default=240.0)
     ap.add_argument("--remainder", type=int, default=1, help="0: switch the skew remainder of the lattice tiles off (A/B of profiles/r05_nitsche_ab.txt)")
     ap.add_argument("--ws-trial", type=int, default=1, help="1: opt in to the library's workspace placement trial (mfem_debug_set_ws_trial); 0 = as the library ships")
-    ap.add_argument("--live-traffic", type=int, default=1, help="N = 1, config sizes: collect the headline rooflines' `traffic` in this run (two rocprofv3 --pmc child passes)")
+    ap.add_argument("--live-traffic", type=int, default=1, help="--full, N = 1, config sizes: collect the headline rooflines' `traffic` in this run (two rocprofv3 --pmc child passes)")
     ap.add_argument("--dry", type=int, default=0, help="1: no device work -- rank spawn, slab planes, halo sizes, workspace bytes per rank, the compact line (CPU only)")
     ap.add_argument("--full-out", default="", help="path of the full result object (default gpurun_out/bench_full.json; '-' = do not write)")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
@@ -180,8 +189,6 @@ def main():
 
     import ctypes as C
 
-    import torch
-
     import bench_legs as L
     from metafem_jl_amd import _lib
 
@@ -189,14 +196,14 @@ def main():
     if args.n <= 0:
         args.n = cfg["n"]
     B = L.Bench(args)
-    rank, world = B.rank, B.world
+    rank = B.rank
     if args.ws_trial:
         _lib.check(_lib.lib.mfem_debug_set_ws_trial(1))
     if not args.remainder:
         _lib.check(_lib.lib.mfem_debug_set_remainder(0))
 
     dump = output_dumper(args.dump_outputs) if args.dump_outputs and rank == 0 else None  # (N > 1: rank 0's slab)
-    main_res = B.run_workload(cfg, base, args.n, args.steps, args.warmup, want_csr=True, on_last=dump)
+    main_res = B.run_workload(cfg, base, args.n, args.steps, args.warmup, want_csr=args.full, on_last=dump)
     out = {"errors": []}
     if rank == 0:
         out.update(B.headline_object(main_res, cfg, args.config))
@@ -210,6 +217,24 @@ def main():
             out["remainder"] = main_res["remainder"]
         if "csr_kernel" in main_res:
             out["roofline"]["csr_kernel"] = main_res["csr_kernel"]  # the north_star's own number: the CSR kernel behind mul! on this matrix, this run
+
+    if args.full:
+        side_legs(B, L, args, cfg, base, main_res, out)
+    if rank == 0:
+        out.setdefault("cpu_baseline", None)
+        if not out["errors"]:
+            del out["errors"]
+        C.CDLL(None).fflush(None)
+        emit(out, args)
+    B.close()
+
+
+def side_legs(B, L, args, cfg, base, main_res, out):
+    """--full: every measurement after the headline, added to its object `out` (complete when this starts); each leg is guarded, so that only the
+    headline can fail the run."""
+    import torch
+
+    rank, world = B.rank, B.world
 
     def guarded(key, fn):
         """A secondary leg never takes the line down: its failure is the leg's object."""
@@ -334,11 +359,6 @@ def main():
                                                   "assembly; the CPU sample is a smaller mesh, see cpu_baseline.sample)"}
                 return cb
             guarded("cpu_baseline", cpu)
-        if not out["errors"]:
-            del out["errors"]
-        C.CDLL(None).fflush(None)
-        emit(out, args)
-    B.close()
 
 
 if __name__ == "__main__":

@@ -61,7 +61,7 @@ def _common(out, n_gpus, steps=1, scaling="weak"):
 
 
 def test_single_gpu_line_has_every_object():
-    out = run_bench(["--n", "40", "--steps", "2", "--warmup", "1", "--secondary-n", "24", "--secondary-steps", "1", "--hex27-n", "8", "--cpu-n", "12",
+    out = run_bench(["--full", "--n", "40", "--steps", "2", "--warmup", "1", "--secondary-n", "24", "--secondary-steps", "1", "--hex27-n", "8", "--cpu-n", "12",
                      "--cpu-repeats", "1", "--iters", "30"])
     _common(out, 1, steps=2)
     assert out["config"]["n_dof"] == 41 ** 3 and out["config"]["krylov_steps_per_step"] == 30
@@ -86,8 +86,19 @@ def test_single_gpu_line_has_every_object():
     assert nl["iterations"] == 20 and nl["ms_per_step"] > 0 and nl["solve_ms"] > 0 and line["newton_like"]["per_solve_ms"] == pytest.approx(nl["per_solve_ms"], rel=1e-3)
 
 
+def test_plain_run_times_the_headline_alone():
+    """Without --full the run is the headline workload alone: none of the side legs the options select by default (256^3, CPU baseline, hex-27 CSR
+    roofline) and no CSR-kernel roofline of its own matrix; the line still carries the Krylov loop's roofline and the checked residuals."""
+    out = run_bench(["--n", "40", "--steps", "2", "--warmup", "1", "--iters", "30"])
+    _common(out, 1, steps=2)
+    assert out["config"]["final_res"] < out["config"]["initial_res"] and out["config"]["final_res_recomputed"] is not None
+    assert out["cpu_baseline"] is None and "vs_cpu_baseline" not in out and "newton_like" not in out
+    assert not [k for k in out if k.startswith(("secondary_", "roofline_hex27", "strong_scaling"))]
+    assert "csr_kernel" not in out["roofline"] and "csr_kernel_hex27" not in out["roofline"]
+
+
 def test_two_ranks_on_one_gpu_through_the_host_transport():
-    out = run_bench(["--gpus", "2", "--n", "48"] + SMALL, env={"MFEM_BENCH_HOST_COMM": "1"})
+    out = run_bench(["--full", "--gpus", "2", "--n", "48"] + SMALL, env={"MFEM_BENCH_HOST_COMM": "1"})
     _common(out, 2)
     assert out["config"]["n_dof"] == 97 * 49 * 49 and "slab decomposition x2" in out["config"]["parallelism"]
     assert out["cpu_baseline"] is None
@@ -119,9 +130,9 @@ def test_strong_scaling_cuts_the_one_gpu_mesh_into_slabs():
 
 
 def test_default_line_carries_all_four_configs():
-    """The default invocation (c2, N = 1) also runs configs[2] and configs[3] and the FP64-MFMA roofline of the hex-27 Ke kernels, so the driver's
+    """With --full the default invocation (c2, N = 1) also runs configs[2] and configs[3] and the FP64-MFMA roofline of the hex-27 Ke kernels, so the driver's
     one line carries all four configs; here at reduced sizes (--secondary-config-n)."""
-    out = run_bench(["--n", "32", "--steps", "1", "--warmup", "1", "--secondary-n", "0", "--hex27-n", "0", "--cpu-n", "0", "--iters", "40",
+    out = run_bench(["--full", "--n", "32", "--steps", "1", "--warmup", "1", "--secondary-n", "0", "--hex27-n", "0", "--cpu-n", "0", "--iters", "40",
                      "--secondary-config-n", "12", "--secondary-steps", "2"])
     _common(out, 1)
     for key, ndof, metric in (("secondary_c3", 3 * 13 ** 3, "elasticity"), ("secondary_c4", 25 ** 3, "hex-27")):
@@ -160,7 +171,7 @@ def test_c3_c4_legs_with_two_ranks(config, n, iters, ndof):
 
 @pytest.mark.parametrize("config,n,ndof", [("c3", 24, 3 * 25 ** 3), ("c4", 12, 25 ** 3), ("nitsche_c2", 24, 25 ** 3), ("ref_idrs8", 24, 25 ** 3)])
 def test_c3_c4_legs_single_gpu(config, n, ndof):
-    out = run_bench(["--config", config, "--n", str(n), "--iters", "40"] + SMALL)
+    out = run_bench(["--full", "--config", config, "--n", str(n), "--iters", "40"] + SMALL)
     _common(out, 1)
     assert out["config"]["n_dof"] == ndof and "csr_kernel" in out["roofline"]
 
@@ -168,7 +179,7 @@ def test_c3_c4_legs_single_gpu(config, n, ndof):
 def test_traffic_is_collected_in_the_run_at_a_config_size():
     """At a config's own size bench.py observes the HBM counters itself: two rocprofv3 --pmc child passes (FETCH_SIZE, WRITE_SIZE) on the
     workload's leg; `traffic_source` says so and the calibration kernel's known bytes are met.  (c3 at 128^3: the smallest such leg.)"""
-    out = run_bench(["--config", "c3", "--steps", "1", "--warmup", "0", "--iters", "40"], timeout=1200)
+    out = run_bench(["--full", "--config", "c3", "--steps", "1", "--warmup", "0", "--iters", "40"], timeout=1200)
     _common(out, 1)
     for obj in (out["roofline"], out["roofline"]["csr_kernel"]):
         assert obj["traffic"] and obj["traffic_source"].startswith("collected in this run"), obj.get("traffic_source")
