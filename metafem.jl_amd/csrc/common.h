@@ -264,13 +264,6 @@ int mfem_rem_build(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, int n
 int mfem_rem_apply(mfem_context_s* ctx, mfem_csr_s* A, const double* x, const double* dsc, double* y, double alpha, const double* dotw,
                    double* partials, int* n_partials, const int32_t* done_flag);
 int64_t mfem_rem_design_bytes(const mfem_csr_s* A);
-int mfem_lat8_plan(mfem_context_s* ctx, mfem_csr_s* A);
-bool mfem_lat8_for_method(const mfem_csr_s* A, bool is_cg);  // one-field matrices: only the solvers that work on A D^-1 (cg! keeps the bitwise patch sweep)
-size_t mfem_lat8_bytes(const mfem_csr_s* A);
-// binds symmetric values, or -- allow_rem -- values whose asymmetry a sparse remainder (spmv_rem.hip) repairs; scratch: 3 n doubles
-int mfem_lat8_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, double* scratch, bool allow_rem = false);
-void mfem_lat8_unbind(mfem_csr_s* A);
-bool mfem_lat8_bound(const mfem_csr_s* A, const double* vals);
 int mfem_spmv_lat8_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, const double* x, double* y, double alpha, double beta,
                           const double* dotw, double* partials, int* n_partials, const int32_t* done_flag, int part);
 int64_t mfem_lat8_design_bytes(const mfem_csr_s* A);
@@ -284,39 +277,41 @@ static inline int mfem_lat_first_ghost_layer(int m0, int gw, int nti, bool has_u
   t = t <= 0 ? 0 : (t + 7) / 8;
   return t < nti ? t : nti;
 }
-int mfem_lat27_plan(mfem_context_s* ctx, mfem_csr_s* A);
-size_t mfem_lat27_bytes(const mfem_csr_s* A);
-int mfem_lat27_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, double* scratch, bool allow_rem = false);
 // rem_fields > 0: rows above the gate may be repaired by a remainder built for that many fields (then *asym is the measure of tiles + remainder and
 // A->rem_active is set); 0: symmetric values only
 int mfem_sym_probe(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* scratch, double amax, void (*unbind)(mfem_csr_s*),
                    void (*rebind)(mfem_csr_s*, void*), void* cookie, double* asym, int rem_fields = 0);
-void mfem_lat27_unbind(mfem_csr_s* A);
-bool mfem_lat27_bound(const mfem_csr_s* A, const double* vals);
 int mfem_spmv_lat27_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, const double* x, double* y, double alpha,
                            double beta, const double* dotw, double* partials, int* n_partials, const int32_t* done_flag, int part);
 int64_t mfem_lat27_design_bytes(const mfem_csr_s* A);
 int64_t mfem_lat27_entries(const mfem_csr_s* A);
 int mfem_node_block_fields(mfem_context_s* ctx, mfem_csr_s* A);  // fills A->nb_F (spmv_sell.hip)
-int mfem_sell_plan(mfem_context_s* ctx, mfem_csr_s* A);
-size_t mfem_sell_vals_bytes(const mfem_csr_s* A);
-int mfem_sell_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc);
-void mfem_sell_unbind(mfem_csr_s* A);
-void mfem_sell_free(mfem_csr_s* A);
 int mfem_spmv_sell_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, const double* x, double* y, double alpha,
                           double beta, const double* dotw, double* partials, int* n_partials, const int32_t* done_flag, int part);
-bool mfem_sell_bound(const mfem_csr_s* A, const double* vals);  // the sliced layout (rows permuted; ghost-reading rows sorted last) serves these values
-int mfem_ell_plan(mfem_context_s* ctx, mfem_csr_s* A);
-size_t mfem_ell_vals_bytes(const mfem_csr_s* A);
-int mfem_ell_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, const double* ssym = nullptr);
-bool mfem_dia_layout_planned(const mfem_csr_s* A);  // mfem_ell_bind would make the diagonal-slotted copy (mode 2)
-bool mfem_symp_wanted(const mfem_csr_s* A);  // the symmetric patch sweep (mode 2) would be tried for this pattern
-void mfem_ell_unbind(mfem_csr_s* A);
 int mfem_ell_diag(mfem_context_s* ctx, mfem_csr_s* A, double* d);
-void mfem_ell_free(mfem_csr_s* A);
 int mfem_spmv_ell_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, const double* x, double* y, double alpha,
                          double beta, const double* dotw, double* partials, int* n_partials, const int32_t* done_flag,
                          const SpmvPart& part);
+
+// The solver layouts of a pattern (layout.hip): which copy of the values a solve runs on, and its binding and release.  The values are the
+// mode numbers of mfem_csr_solver_layout: the CSR tile kernel on the caller's values (no copy), slot-major copy with explicit columns / with
+// diagonal-slotted regular blocks (spmv_ell.hip), row-sorted sliced ELL (spmv_sell.hip), symmetric lattice tiles (spmv_lat27.hip, spmv_lat8.hip)
+enum mfem_layout : int32_t { MFEM_LAYOUT_CSR = 0, MFEM_LAYOUT_ELL = 1, MFEM_LAYOUT_DIA = 2, MFEM_LAYOUT_SELL = 3, MFEM_LAYOUT_LAT27 = 4, MFEM_LAYOUT_LAT8 = 5 };
+// What a pattern offers a solve: a tile layout (taken if the values pass its symmetry probe) and a row layout, each with the workspace bytes of
+// its copy (MFEM_LAYOUT_CSR, 0: none)
+struct mfem_layout_plan_s {
+  mfem_layout tile, rows;
+  size_t tile_bytes, rows_bytes;
+};
+int mfem_layout_plan(mfem_context_s* ctx, mfem_csr_s* A, bool is_cg, bool allow_tiles, mfem_layout_plan_s* P);
+// Releases whatever is bound, then copies `vals` into buf in `mode` and binds the copy (mfem_layout_bound tells whether it was taken).  dsc: right
+// Jacobi scaling (nullptr: none); ssym: symmetric scaling of the diagonal-slotted copy (ELL / DIA only); scratch: 3 n doubles for a tile layout's
+// symmetry probe, left dirty; allow_rem: the tiles may carry a sparse remainder (spmv_rem.hip)
+int mfem_layout_bind(mfem_context_s* ctx, mfem_csr_s* A, mfem_layout mode, const double* vals, double* buf, const double* dsc, const double* ssym,
+                     double* scratch, bool allow_rem);
+mfem_layout mfem_layout_bound(const mfem_csr_s* A, const double* vals);  // the layout that serves products with these values (CSR: none)
+void mfem_layout_unbind(mfem_csr_s* A);
+void mfem_layout_drop(mfem_csr_s* A);  // frees and resets every layout's plan (unbound first)
 
 int mfem_ws_reserve(mfem_context_s* ctx, size_t bytes);
 int mfem_ws_next_candidate(mfem_context_s* ctx);

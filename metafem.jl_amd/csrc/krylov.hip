@@ -881,52 +881,28 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
   const bool need_copy_unfused = ((jac && !is_cg) || left) && !o->scale_in_place;
   // workspace: x, b (padded copies), d, dinv (CG) / left scaling dl, work vectors, optional matrix copy
   const size_t vec_bytes = (size_t)nv * sizeof(double);
-  // Symmetric lattice tiles first (spmv_lat27.hip: the hex-27 lattice matrix; spmv_lat8.hip: the 3-field 27-point matrix), one rank, solver on
-  // the unscaled or right-scaled matrix: taken if this solve's values are symmetric (decided by the bind).  A right Jacobi scaling is applied to x
-  // there, not to the stored matrix.  While a pattern's values have never been refused, the other layouts are not even planned (their inspections
-  // and column copies cost 20 - 40 ms and 2 - 4 GB at the BASELINE sizes); the first refusal plans them and this function starts over.
-  int rc_plan = MFEM_OK;
-  size_t lat_bytes = 0, lat8_bytes = 0;
-  if (allow_lat && !left && (is_cg || !jac || fused_scale)) {  // (both also on slab patterns: the plans read the pattern's lattice hint)
-    rc_plan = mfem_lat27_plan(ctx, A);
-    if (rc_plan) return rc_plan;
-    lat_bytes = mfem_lat27_bytes(A);
-    if (!lat_bytes && mfem_lat8_for_method(A, is_cg)) {  // (asked first: the plan's entry-by-entry check of the pattern costs 27 ms at 512^3)
-      rc_plan = mfem_lat8_plan(ctx, A);
-      if (rc_plan) return rc_plan;
-      if (mfem_lat8_for_method(A, is_cg)) lat8_bytes = mfem_lat8_bytes(A);  // (again: the plan may have inferred the number of fields)
-    }
-  }
-  const bool lat_only = (lat_bytes || lat8_bytes) && !A->lat_refused;
-  // slot-major copy of the working values for near-uniform rows (spmv_ell.hip), made once per solve after the scaling
-  size_t ell_bytes = 0, sell_bytes = 0;
-  if (!lat_only) {
-    rc_plan = mfem_ell_plan(ctx, A);
-    if (rc_plan) return rc_plan;
-    ell_bytes = mfem_ell_vals_bytes(A);
-    if (!ell_bytes && A->ell_state != 1) {  // rows of uneven length: row-sorted sliced layout
-      rc_plan = mfem_sell_plan(ctx, A);
-      if (rc_plan) return rc_plan;
-      sell_bytes = mfem_sell_vals_bytes(A);
-    }
-  }
+  // Solver layouts (layout.hip): symmetric lattice tiles first, one rank, solver on the unscaled or right-scaled matrix -- taken if this solve's
+  // values are symmetric (decided by the bind); a right Jacobi scaling is applied to x there, not to the stored matrix.  While a pattern's values have
+  // never been refused, the row layouts are not even planned; the first refusal plans them and this function starts over.  A row layout's copy of the
+  // working values is made once per solve after the scaling.
+  mfem_layout_plan_s lp;
+  int rc = mfem_layout_plan(ctx, A, is_cg, allow_lat && !left && (is_cg || !jac || fused_scale), &lp);
+  if (rc) return rc;
   // (the CSR kernel of small systems reads the caller's array: it needs the scaled copy.  Planned tiles keep the scaling fused -- they take the caller's
   // UNSCALED values and apply a right scaling to x; should they refuse the values with no other layout to carry the fused scaling, the solve starts
   // over without them, below)
-  fused_scale = fused_scale && (ell_bytes || sell_bytes || lat_bytes || lat8_bytes);
+  fused_scale = fused_scale && (lp.tile || lp.rows);
   const bool need_copy = need_copy_unfused && !fused_scale;
   // The tiles are never bound from a scaled working copy (it lives in the workspace and is filled only further down); cannot happen with the rule
   // above, kept as the invariant's guard
-  if (need_copy && jac && !is_cg) lat_bytes = lat8_bytes = 0;
+  if (need_copy && jac && !is_cg) lp = mfem_layout_plan_s{MFEM_LAYOUT_CSR, lp.rows, 0, lp.rows_bytes};
   const size_t csr_copy_bytes = need_copy ? align_up((size_t)A->nnz * sizeof(double), 256) : 0;
-  size_t layout_bytes = ell_bytes > sell_bytes ? ell_bytes : sell_bytes;  // (one of the two is 0)
-  if (lat_bytes > layout_bytes) layout_bytes = lat_bytes;
-  if (lat8_bytes > layout_bytes) layout_bytes = lat8_bytes;
+  const size_t layout_bytes = lp.tile_bytes > lp.rows_bytes ? lp.tile_bytes : lp.rows_bytes;
   size_t total = vec_bytes * (4 + nwork) + csr_copy_bytes + layout_bytes;
   const size_t gm_offset = align_up(total, 256);  // gmres!: H, y and the block-dot partials behind everything else
   if (o->method == MFEM_SOLVER_GMRES) total = gm_offset + mfem_gmres_workspace_bytes();
   if (is_lsqr) total = gm_offset + (size_t)A->nnz * sizeof(double);  // lsqr!: the values of the transposed working matrix, behind everything else
-  int rc = mfem_ws_reserve(ctx, total);
+  rc = mfem_ws_reserve(ctx, total);
   if (rc) return rc;
   char* base = (char*)ctx->ws;
   MFEM_CHECK_HIP(hipMemsetAsync(base, 0, vec_bytes * (4 + nwork), ctx->stream));
@@ -947,6 +923,7 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
   double* vals_work = vals;
   // right Jacobi scaling of a working copy: the scaling kernel writes the copy straight from the caller's values (no copy pass first)
   const bool scaled_copy = need_copy && jac && !is_cg;
+  double* lay = (double*)(base + vec_bytes * (4 + nwork) + csr_copy_bytes);  // the layout copy
   if (need_copy) {
     vals_work = (double*)(base + vec_bytes * (4 + nwork));
     if (!scaled_copy) MFEM_CHECK_HIP(hipMemcpyAsync(vals_work, vals, (size_t)A->nnz * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
@@ -961,29 +938,19 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
     if (rc) return rc;
   }
 
-  struct EllGuard {  // whatever gets bound below is released on every way out of this function
-    mfem_csr_s* A;
-    ~EllGuard() {
-      mfem_ell_unbind(A);
-      mfem_sell_unbind(A);
-      mfem_lat27_unbind(A);
-      mfem_lat8_unbind(A);
-    }
-  } ell_guard{A};
+  struct LayoutGuard { mfem_csr_s* A; ~LayoutGuard() { mfem_layout_unbind(A); } } layout_guard{A};  // whatever gets bound below is released on every way out
   // symmetric lattice tiles: bound first, before anything is communicated (a refusal starts this function over) -- the Jacobi step below then takes
   // |diag| from the CSR values; only the pointer of the column scaling is handed over here, the SpMVs read it after it has been filled.
   // (the first three work vectors serve the bind's probe product and are cleared again)
-  bool lat8_bound = false;
-  if (lat_bytes || lat8_bytes) {
-    double* lay = (double*)(base + vec_bytes * (4 + nwork) + csr_copy_bytes);
+  bool tiles_bound = false;
+  if (lp.tile) {
     // (values that are nonsymmetric in a few rows only -- Nitsche / SUPG faces -- keep the tiles and carry a sparse remainder, spmv_rem.hip; not for cg!,
     // which is not defined on such a matrix: its refusal keeps the reproducible layouts)
-    rc = lat_bytes ? mfem_lat27_bind(ctx, A, vals_work, lay, fused_scale ? V.d : nullptr, V.w[0], !is_cg)
-                   : mfem_lat8_bind(ctx, A, vals_work, lay, fused_scale ? V.d : nullptr, V.w[0], !is_cg);
+    rc = mfem_layout_bind(ctx, A, lp.tile, vals_work, lay, fused_scale ? V.d : nullptr, nullptr, V.w[0], !is_cg);
     if (rc) return rc;
     MFEM_CHECK_HIP(hipMemsetAsync(V.w[0], 0, vec_bytes * 3, ctx->stream));
-    lat8_bound = mfem_lat27_bound(A, vals_work) || mfem_lat8_bound(A, vals_work);  // (either of the two)
-    if (!lat8_bound && (lat_only || (fused_scale && !ell_bytes && !sell_bytes))) {
+    tiles_bound = mfem_layout_bound(A, vals_work) == lp.tile;
+    if (!tiles_bound && (!A->lat_refused || (fused_scale && !lp.rows))) {
       // refused: no other layout was planned beside the tiles (first refusal on this pattern), or none exists at this size to carry the fused
       // scaling -- start over without the tiles (the other layouts get planned; a scaled copy is made where the CSR kernel serves)
       // (lat_refused only makes later solves on this pattern plan the other layouts up front -- the tiles are still tried first by every solve, and
@@ -995,7 +962,7 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
 
   // Pr = Pr_func!(A)   (02_Preconditioner.jl:38, 103-120)
   V.dinv = nullptr;
-  bool ell_bound = false;
+  bool rows_bound = false;
   // cg_variant 4: plain CG on S^-1 A S^-1, S = sqrt|diag A| -- the Jacobi-preconditioned iteration in the variables S x, without the stream of
   // 1 / d in its vector kernels (8 instead of 9 per iteration).  The scaling is folded into the diagonal-slotted layout copy (mode 2: plain or
   // mirrored kernels alike -- a bitwise symmetric matrix stays one), one rank; otherwise the classic recurrence below runs.
@@ -1004,7 +971,7 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
   // (auto: not for passes of fewer than 64 iterations -- the scaled copy and its S vectors cost 1.2 ms more per solve at 256^3 than the plain
   // path, an iteration saves 0.026 ms there: tools/cg_per_solve.py)
   if (jac && is_cg && (o->cg_variant == 4 || (o->cg_variant == 0 && o->maxiter >= 64)) && o->precond != MFEM_PRECOND_JACOBI_RIGHT_COLNORM && !left &&
-      ell_bytes && !lat8_bound && mfem_dia_layout_planned(A)) {
+      lp.rows == MFEM_LAYOUT_DIA && !tiles_bound) {
     rc = mfem_fill(ctx, n, 1.0, V.d);
     if (!rc) rc = mfem_jacobi_diag_launch(ctx, A, vals_work, V.d, 0);
     if (rc) return rc;
@@ -1017,14 +984,14 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
       rc = mfem_comm_halo(ctx, dinv_buf);
       if (rc) return rc;
     }
-    rc = mfem_ell_bind(ctx, A, vals_work, (double*)(base + vec_bytes * (4 + nwork) + csr_copy_bytes), nullptr, dinv_buf);  // (synchronises: the check's verdict)
+    rc = mfem_layout_bind(ctx, A, lp.rows, vals_work, lay, nullptr, dinv_buf, nullptr, false);  // (synchronises: the check's verdict)
     if (rc) return rc;
     MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 12, d_stat, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
     MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
     double s_min = 0.0;
     memcpy(&s_max, ctx->h_flags + 12, sizeof(double));
     memcpy(&s_min, ctx->h_flags + 14, sizeof(double));
-    bool ok = A->ell_vals && A->ell_bound_mode == 2 && s_min > 0.0 && s_max < __builtin_huge_val();
+    bool ok = mfem_layout_bound(A, vals_work) == MFEM_LAYOUT_DIA && s_min > 0.0 && s_max < __builtin_huge_val();
     if (ctx->comm) {  // every rank iterates on the same system: scaled only if all of them can
       ctx->h_scalars[S_TMP0] = ok ? 1.0 : 0.0;
       MFEM_CHECK_HIP(hipMemcpyAsync(ctx->d_scalars + S_TMP0, ctx->h_scalars + S_TMP0, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
@@ -1036,24 +1003,24 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
     }
     if (ok) {
       cg_scaled = true;
-      ell_bound = true;
+      rows_bound = true;
       V.cg_s = V.d;
       V.cg_smax = s_max;
       V.cg_smin = s_min;
       hipLaunchKernelGGL(k_mul, dim3(mfem_vec_grid(ctx, n)), dim3(MFEM_BLOCK), 0, ctx->stream, n, V.b, dinv_buf, V.b);  // b^ = S^-1 b
       MFEM_CHECK_LAUNCH();
     } else {
-      mfem_ell_unbind(A);  // (no diagonal-slotted copy after all, or a zero / non-finite diagonal: the classic recurrence on an unscaled copy)
+      mfem_layout_unbind(A);  // (no diagonal-slotted copy after all, or a zero / non-finite diagonal: the classic recurrence on an unscaled copy)
     }
   }
   if (jac && !cg_scaled) {
     if (o->precond == MFEM_PRECOND_JACOBI_RIGHT_COLNORM && !is_cg) {
       rc = mfem_jacobi2_by_column(ctx, A, vals_src, V.d);
-    } else if (is_cg && ell_bytes && !lat8_bound) {
+    } else if (is_cg && (lp.rows == MFEM_LAYOUT_ELL || lp.rows == MFEM_LAYOUT_DIA) && !tiles_bound) {
       // CG does not scale the matrix: transpose first and read |diag| from the copy (n values instead of all nonzeros)
-      rc = mfem_ell_bind(ctx, A, vals_work, (double*)(base + vec_bytes * (4 + nwork) + csr_copy_bytes), nullptr);
-      if (!rc && A->ell_vals) {
-        ell_bound = true;
+      rc = mfem_layout_bind(ctx, A, lp.rows, vals_work, lay, nullptr, nullptr, nullptr, false);
+      if (!rc && mfem_layout_bound(A, vals_work) != MFEM_LAYOUT_CSR) {
+        rows_bound = true;
         rc = mfem_ell_diag(ctx, A, V.d);
       } else if (!rc) {
         rc = mfem_fill(ctx, n, 1.0, V.d);
@@ -1104,21 +1071,13 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
     if (rc) return rc;
   }
 
-  // bind the slot-major copy: every mfem_spmv_launch(A, vals_work, ...) below runs the ELL kernel
+  // bind the row layout's copy: every mfem_spmv_launch(A, vals_work, ...) below runs its kernel
   // (fused_scale: vals_work is the caller's unscaled array and only names the bound values; every SpMV below runs on the scaled copy)
-  if (ell_bytes && !ell_bound && !lat8_bound) {
-    rc = mfem_ell_bind(ctx, A, vals_work, (double*)(base + vec_bytes * (4 + nwork) + csr_copy_bytes), fused_scale ? V.d : nullptr);
+  if (lp.rows && !rows_bound && !tiles_bound) {
+    rc = mfem_layout_bind(ctx, A, lp.rows, vals_work, lay, fused_scale ? V.d : nullptr, nullptr, nullptr, false);
     if (rc) return rc;
-    if (fused_scale && !A->ell_vals) {
+    if (fused_scale && mfem_layout_bound(A, vals_work) == MFEM_LAYOUT_CSR) {
       mfem_set_error("solver layout could not be bound for the fused Jacobi scaling");
-      return MFEM_ERR_INVALID;
-    }
-  }
-  if (sell_bytes && !lat8_bound) {
-    rc = mfem_sell_bind(ctx, A, vals_work, (double*)(base + vec_bytes * (4 + nwork) + csr_copy_bytes), fused_scale ? V.d : nullptr);
-    if (rc) return rc;
-    if (fused_scale && !A->sell_vals) {
-      mfem_set_error("sliced layout could not be bound for the fused Jacobi scaling");
       return MFEM_ERR_INVALID;
     }
   }
@@ -1242,7 +1201,7 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
   // carried, repairs the rows above it): a residual the caller is told -- and a residual that ENDS the passes -- must not come from that copy.  One
   // product with the CSR kernel on the caller's own values: ||b - A x_out|| / sqrt(n), x_out = Pr(x) (one rank: x_out carries no ghost
   // entries; not in benchmark mode, where bench.py does the same recomputation outside its timed region).  V.w[0] is free between passes.
-  const bool csr_recheck = lat8_bound && !ctx->comm && !o->fixed_iterations;
+  const bool csr_recheck = tiles_bound && !ctx->comm && !o->fixed_iterations;
   bool res_from_csr = false;
   double prev_csr_res = -1.0;  // the caller's residual at the previous recheck that did not end the passes
   auto csr_true_residual = [&](double* out) -> int {

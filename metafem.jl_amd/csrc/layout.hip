@@ -1,0 +1,126 @@
+// The solver layouts of a CSR handle, planned, bound and released here only: mfem_solve (krylov.hip), the layout query and the diagnostic product
+// below take the same rules.  At most one layout is bound at a time; which one serves a product is read off the per-layout pointers, never cached
+// beside them: the tile binds' symmetry probe (mfem_sym_probe) unbinds and rebinds the tiles through callbacks of its own.  Nothing here issues a
+// collective: a refusal of the tiles is a rank-local verdict (krylov.hip: solve_inner).
+#include "blas1.h"
+#include "layouts.h"
+
+// The symmetric lattice tiles first: the hex-27 tiles, else the F-field tiles.  While a pattern's values have never been refused by the tiles, the
+// row layouts are not even planned (their inspections and column copies cost 20 - 40 ms and 2 - 4 GB at the BASELINE sizes).  Then the slot-major
+// copy for near-uniform rows, else the row-sorted sliced layout.
+int mfem_layout_plan(mfem_context_s* ctx, mfem_csr_s* A, bool is_cg, bool allow_tiles, mfem_layout_plan_s* P) {
+  *P = mfem_layout_plan_s{MFEM_LAYOUT_CSR, MFEM_LAYOUT_CSR, 0, 0};
+  int rc = MFEM_OK;
+  if (allow_tiles) {  // (both also on slab patterns: the plans read the pattern's lattice hint)
+    rc = mfem_lat27_plan(ctx, A);
+    if (rc) return rc;
+    P->tile_bytes = mfem_lat27_bytes(A);
+    if (P->tile_bytes) {
+      P->tile = MFEM_LAYOUT_LAT27;
+    } else if (mfem_lat8_for_method(A, is_cg)) {  // (asked first: the plan's entry-by-entry check of the pattern costs 27 ms at 512^3)
+      rc = mfem_lat8_plan(ctx, A);
+      if (rc) return rc;
+      if (mfem_lat8_for_method(A, is_cg)) P->tile_bytes = mfem_lat8_bytes(A);  // (again: the plan may have inferred the number of fields)
+      if (P->tile_bytes) P->tile = MFEM_LAYOUT_LAT8;
+    }
+  }
+  if (P->tile_bytes && !A->lat_refused) return MFEM_OK;
+  rc = mfem_ell_plan(ctx, A);
+  if (rc) return rc;
+  P->rows_bytes = mfem_ell_vals_bytes(A);
+  if (P->rows_bytes) {
+    P->rows = mfem_dia_layout_planned(A) ? MFEM_LAYOUT_DIA : MFEM_LAYOUT_ELL;
+    return MFEM_OK;
+  }
+  rc = mfem_sell_plan(ctx, A);  // rows of uneven length
+  if (rc) return rc;
+  P->rows_bytes = mfem_sell_vals_bytes(A);
+  if (P->rows_bytes) P->rows = MFEM_LAYOUT_SELL;
+  return MFEM_OK;
+}
+
+int mfem_layout_bind(mfem_context_s* ctx, mfem_csr_s* A, mfem_layout mode, const double* vals, double* buf, const double* dsc, const double* ssym,
+                     double* scratch, bool allow_rem) {
+  mfem_layout_unbind(A);
+  switch (mode) {
+    case MFEM_LAYOUT_CSR: return MFEM_OK;
+    case MFEM_LAYOUT_ELL:
+    case MFEM_LAYOUT_DIA: return mfem_ell_bind(ctx, A, vals, buf, dsc, ssym);
+    case MFEM_LAYOUT_SELL: return mfem_sell_bind(ctx, A, vals, buf, dsc);
+    case MFEM_LAYOUT_LAT27: return mfem_lat27_bind(ctx, A, vals, buf, dsc, scratch, allow_rem);
+    case MFEM_LAYOUT_LAT8: return mfem_lat8_bind(ctx, A, vals, buf, dsc, scratch, allow_rem);
+  }
+  return MFEM_OK;
+}
+
+mfem_layout mfem_layout_bound(const mfem_csr_s* A, const double* vals) {
+  if (A->lat8_vals && vals == A->lat8_src) return MFEM_LAYOUT_LAT8;
+  if (A->ell_vals && vals == A->ell_src) return A->ell_bound_mode == 2 ? MFEM_LAYOUT_DIA : MFEM_LAYOUT_ELL;
+  if (A->lat27_vals && vals == A->lat27_src) return MFEM_LAYOUT_LAT27;
+  if (A->sell_vals && vals == A->sell_src) return MFEM_LAYOUT_SELL;
+  return MFEM_LAYOUT_CSR;
+}
+
+void mfem_layout_unbind(mfem_csr_s* A) {
+  mfem_ell_unbind(A);
+  mfem_sell_unbind(A);
+  mfem_lat27_unbind(A);
+  mfem_lat8_unbind(A);
+}
+
+void mfem_layout_drop(mfem_csr_s* A) {
+  mfem_layout_unbind(A);
+  mfem_ell_free(A);
+  mfem_sell_free(A);
+  mfem_rem_free(A);
+  A->lat27_state = A->lat8_state = A->lat_refused = A->sym_state = A->symp_state = 0;
+  if (A->lat_inferred) {  // (a hint read off the arrays goes with them)
+    A->lat_fields = A->lat_m0 = A->lat_m1 = A->lat_m2 = A->lat_plo = A->lat_gw = 0;
+    A->lat_inferred = 0;
+  }
+}
+
+// What the Krylov loop of the next mfem_solve will run on this pattern: 0 = CSR tile kernel, 1 = slot-major copy with explicit
+// columns, 2 = slot-major copy with diagonal-slotted regular blocks, 3 = row-sorted sliced layout, 4 / 5 = symmetric lattice tiles (one rank;
+// the values of each solve decide, modes 3 / 2 serve it otherwise).  Answers for cg!.  Plans what it reports if that has not happened yet.
+extern "C" int mfem_csr_solver_layout(mfem_context ctx, mfem_csr A, int32_t* mode, int32_t* slots, int64_t* padded_rows,
+                                      int64_t* regular_rows) try {
+  MFEM_REQUIRE(ctx && A, "null handle");
+  mfem_layout_plan_s P;
+  const int rc = mfem_layout_plan(ctx, A, true, true, &P);
+  if (rc) return rc;
+  const mfem_layout m = P.tile != MFEM_LAYOUT_CSR ? P.tile : P.rows;
+  const bool ell = m == MFEM_LAYOUT_ELL || m == MFEM_LAYOUT_DIA;
+  if (mode) *mode = m;
+  if (slots) *slots = ell ? A->ell_K : m >= MFEM_LAYOUT_SELL ? A->max_row_nnz : 0;
+  if (padded_rows) *padded_rows = ell ? A->ell_npad : m == MFEM_LAYOUT_SELL ? (A->bsell_F > 0 ? A->sell_nblk * 64 * A->bsell_F : A->sell_nblk * 128) : 0;
+  if (regular_rows) *regular_rows = m == MFEM_LAYOUT_DIA ? (int64_t)A->dia_regular_blocks * 128 : 0;
+  return MFEM_OK;
+} MFEM_API_CATCH("mfem_csr_solver_layout")
+
+// y = alpha A x + beta y through the layout mfem_solve would use for this pattern with cg! (the one-off conversion of `vals` included): the tiles if
+// these values pass their probe, the row layout otherwise.  A test / diagnostic entry point -- production SpMVs of caller-supplied values go
+// through mfem_spmv_csr.
+extern "C" int mfem_spmv_solver_layout(mfem_context ctx, mfem_csr A, const double* vals, const double* x, double* y, double alpha,
+                                       double beta) try {
+  MFEM_REQUIRE(ctx && A, "null handle");
+  MFEM_REQUIRE(A->n == 0 || (x && y && (A->nnz == 0 || vals)), "null vector");
+  if (A->n == 0) return MFEM_OK;
+  struct Release { mfem_csr_s* A; ~Release() { mfem_layout_unbind(A); } } release{A};  // nothing stays bound on any way out
+  mfem_layout_plan_s P;
+  int rc = mfem_layout_plan(ctx, A, true, true, &P);
+  if (rc) return rc;
+  if (P.tile != MFEM_LAYOUT_CSR) {
+    const size_t lay = (P.tile_bytes + 255) & ~(size_t)255;
+    rc = mfem_ws_reserve(ctx, lay + (2 * (size_t)A->n + (size_t)(A->ncols > A->n ? A->ncols : A->n)) * sizeof(double));
+    if (!rc) rc = mfem_layout_bind(ctx, A, P.tile, vals, (double*)ctx->ws, nullptr, nullptr, (double*)((char*)ctx->ws + lay), mfem_rem_diag());
+    if (rc) return rc;
+  }
+  if (mfem_layout_bound(A, vals) == MFEM_LAYOUT_CSR) {  // no tiles, or they refused these values: the row layout (planned now if it was not)
+    rc = mfem_layout_plan(ctx, A, true, false, &P);
+    if (!rc && P.rows != MFEM_LAYOUT_CSR) rc = mfem_ws_reserve(ctx, P.rows_bytes);
+    if (!rc && P.rows != MFEM_LAYOUT_CSR) rc = mfem_layout_bind(ctx, A, P.rows, vals, (double*)ctx->ws, nullptr, nullptr, nullptr, false);
+    if (rc) return rc;
+  }
+  return mfem_spmv_launch(ctx, A, vals, x, y, alpha, beta, nullptr, nullptr, nullptr, nullptr);
+} MFEM_API_CATCH("mfem_spmv_solver_layout")

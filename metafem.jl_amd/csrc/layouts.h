@@ -1,0 +1,25 @@
+// The per-layout planning, binding and release of the solver layouts.  Internal to layout.hip, which chooses among them, and to the files
+// that implement them (spmv_ell.hip, spmv_sell.hip, spmv_lat27.hip, spmv_lat8.hip): every other file goes through mfem_layout_* (common.h).
+#pragma once
+#include "common.h"
+
+int mfem_lat8_plan(mfem_context_s* ctx, mfem_csr_s* A);
+bool mfem_lat8_for_method(const mfem_csr_s* A, bool is_cg);  // one-field matrices: only the solvers that work on A D^-1 (cg! keeps the bitwise patch sweep)
+size_t mfem_lat8_bytes(const mfem_csr_s* A);
+int mfem_lat8_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, double* scratch, bool allow_rem);
+void mfem_lat8_unbind(mfem_csr_s* A);
+int mfem_lat27_plan(mfem_context_s* ctx, mfem_csr_s* A);
+size_t mfem_lat27_bytes(const mfem_csr_s* A);
+int mfem_lat27_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, double* scratch, bool allow_rem);
+void mfem_lat27_unbind(mfem_csr_s* A);
+int mfem_sell_plan(mfem_context_s* ctx, mfem_csr_s* A);
+size_t mfem_sell_vals_bytes(const mfem_csr_s* A);
+int mfem_sell_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc);
+void mfem_sell_unbind(mfem_csr_s* A);
+void mfem_sell_free(mfem_csr_s* A);
+int mfem_ell_plan(mfem_context_s* ctx, mfem_csr_s* A);
+size_t mfem_ell_vals_bytes(const mfem_csr_s* A);
+int mfem_ell_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, const double* ssym);
+bool mfem_dia_layout_planned(const mfem_csr_s* A);  // mfem_ell_bind would make the diagonal-slotted copy (mode 2)
+void mfem_ell_unbind(mfem_csr_s* A);
+void mfem_ell_free(mfem_csr_s* A);

@@ -895,22 +895,7 @@ int mfem_csr_plan(mfem_context_s* ctx, mfem_csr_s* A) {
 // everything the handle derived from the borrowed pattern arrays (not the arrays themselves)
 static void csr_drop_plans(mfem_csr_s* A) {
   mfem_tplan_free(A);
-  mfem_ell_unbind(A);
-  mfem_sell_unbind(A);
-  mfem_lat27_unbind(A);
-  mfem_lat8_unbind(A);
-  A->lat8_state = 0;
-  A->lat_refused = 0;
-  if (A->lat_inferred) {  // (a hint read off the arrays goes with them)
-    A->lat_fields = A->lat_m0 = A->lat_m1 = A->lat_m2 = A->lat_plo = A->lat_gw = 0;
-    A->lat_inferred = 0;
-  }
-  mfem_ell_free(A);
-  mfem_sell_free(A);
-  mfem_rem_free(A);
-  A->lat27_state = 0;
-  A->sym_state = 0;
-  A->symp_state = 0;
+  mfem_layout_drop(A);
   if (A->rb_rows) hipFree(A->rb_rows);
   if (A->cw_elide) hipFree(A->cw_elide);
   if (A->diag_off) hipFree(A->diag_off);
@@ -1030,9 +1015,7 @@ extern "C" int mfem_csr_destroy(mfem_csr A) try {
   // a cached cycle graph holds this pattern's arrays in its kernel arguments
   if (A->ctx && mfem_context_alive(A->ctx)) mfem_graphs_invalidate(A->ctx);
   mfem_tplan_free(A);
-  mfem_ell_free(A);
-  mfem_sell_free(A);
-  mfem_rem_free(A);
+  mfem_layout_drop(A);
   if (A->rb_rows) hipFree(A->rb_rows);
   if (A->cw_elide) hipFree(A->cw_elide);
   if (A->diag_off) hipFree(A->diag_off);
@@ -1109,7 +1092,8 @@ int mfem_spmv_halo(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, doubl
   ProfScope prof{ctx, -1};
   int rc = prof.begin();
   if (rc) return rc;
-  if (mfem_lat8_bound(A, vals) || mfem_lat27_bound(A, vals)) {
+  const mfem_layout bound = mfem_layout_bound(A, vals);
+  if (bound == MFEM_LAYOUT_LAT27 || bound == MFEM_LAYOUT_LAT8) {
     // lattice tiles split by i-LAYERS of tiles, not by row zones: the layers that stage no ghost plane run beside the exchange (part 1), the top
     // layers and the gather pass -- which reads the lower ghost planes for the first owned rows -- after it (part 2)
     rc = mfem_comm_halo_begin(ctx, x);
@@ -1177,17 +1161,17 @@ static int spmv_launch_inner(mfem_context_s* ctx, mfem_csr_s* A, const double* v
                              const int32_t* done_flag, const SpmvPart& part) {
   if (n_partials) *n_partials = 0;
   if (A->n == 0) return MFEM_OK;
-  if (!ctx->force_csr) {
-    const int l8 = mfem_spmv_lat8_launch(ctx, A, vals, x, y, alpha, beta, dotw, partials, n_partials, done_flag, part.part);
-    if (l8 != 0) return l8 < 0 ? l8 : MFEM_OK;
-    const int e = mfem_spmv_ell_launch(ctx, A, vals, x, y, alpha, beta, dotw, partials, n_partials, done_flag, part);
-    if (e != 0) return e < 0 ? e : MFEM_OK;
-    const int lt = mfem_spmv_lat27_launch(ctx, A, vals, x, y, alpha, beta, dotw, partials, n_partials, done_flag, part.part);
-    if (lt != 0) return lt < 0 ? lt : MFEM_OK;
+  int launched = 0;  // (a layout launcher returns 1 if it launched, < 0 on error)
+  switch (ctx->force_csr ? MFEM_LAYOUT_CSR : mfem_layout_bound(A, vals)) {
+    case MFEM_LAYOUT_CSR: break;
+    case MFEM_LAYOUT_ELL:
+    case MFEM_LAYOUT_DIA: launched = mfem_spmv_ell_launch(ctx, A, vals, x, y, alpha, beta, dotw, partials, n_partials, done_flag, part); break;
     // (the sliced layout splits by BLOCKS: its ghost-reading rows are sorted behind all others, whatever the zones say)
-    const int sl = mfem_spmv_sell_launch(ctx, A, vals, x, y, alpha, beta, dotw, partials, n_partials, done_flag, part.part);
-    if (sl != 0) return sl < 0 ? sl : MFEM_OK;
+    case MFEM_LAYOUT_SELL: launched = mfem_spmv_sell_launch(ctx, A, vals, x, y, alpha, beta, dotw, partials, n_partials, done_flag, part.part); break;
+    case MFEM_LAYOUT_LAT27: launched = mfem_spmv_lat27_launch(ctx, A, vals, x, y, alpha, beta, dotw, partials, n_partials, done_flag, part.part); break;
+    case MFEM_LAYOUT_LAT8: launched = mfem_spmv_lat8_launch(ctx, A, vals, x, y, alpha, beta, dotw, partials, n_partials, done_flag, part.part); break;
   }
+  if (launched != 0) return launched < 0 ? launched : MFEM_OK;
   const int base = A->index_base;
   // default: wave-private row-transposing tiles of a fixed row count when a wave's 64 / tpr rows fill its LDS block reasonably (rows of
   // near-uniform length: 256^3 hex-8 1.06 ms against 1.19 ms for the product tile); wave tiles cut by nonzeros otherwise (hex-27's

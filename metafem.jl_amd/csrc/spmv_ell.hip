@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "blas1.h"
+#include "layouts.h"
 
 // Blocked slot-major layout ("sliced ELL"): rows are grouped in blocks of ELL_B = 128 (the rows of one wave at two rows per
 // lane); block b stores its K slots one after the other, element (row r, slot s) at  b * K * 128 + s * 128 + (r & 127).
@@ -1629,7 +1630,6 @@ static bool symp_wanted(const mfem_csr_s* A) {
   return (int64_t)(A->symp_p1 - A->symp_p0) * A->symp_PL >= 24000000 || A->symp_m2 > 256;
 }
 static int symp_nseg(const mfem_context_s* ctx, const mfem_csr_s* A);
-bool mfem_symp_wanted(const mfem_csr_s* A) { return symp_wanted(A); }
 bool mfem_dia_layout_planned(const mfem_csr_s* A) { return A->ell_state == 1 && g_ell_enable && A->dia_state == 1 && g_dia_enable; }
 static SympGeom symp_geom(const mfem_context_s* ctx, const mfem_csr_s* A) {
   SympGeom G;
@@ -2034,26 +2034,26 @@ extern "C" int mfem_csr_solver_layout_entries(mfem_context ctx, mfem_csr A, int6
   if (rc) return rc;
   int64_t e = A->nnz;
   int sym = 0;
-  if (mode == 1 || mode == 2) e = (int64_t)A->ell_K * A->ell_npad;
-  if (mode == 3) e = A->sell_total;
-  if (mode == 4) {
-    e = mfem_lat27_entries(A);
-    sym = 3;
-  }
-  if (mode == 5) {
-    e = mfem_lat8_entries(A);
-    sym = 3;
-  }
-  if (mode == 2 && symp_wanted(A)) {
-    sym = 2;
-    // the rows outside the swept planes read their K slots; the sweep reads symp_pairs value pairs
-    const int64_t swept = (int64_t)(A->symp_p1 - A->symp_p0) * A->symp_PL;
-    e = (int64_t)A->ell_K * (A->ell_npad - swept) + symp_count_entries(A, symp_nseg(ctx, A));
-  } else if (mode == 2 && sym27_wanted(A)) {
-    sym = 1;
-    const int gs = sym27_grid(ctx, A, nullptr);
-    const int64_t nch = A->sym_c1 - A->sym_c0;
-    e -= (nch - gs) * A->sym_mx + nch * A->sym_myz;
+  switch ((mfem_layout)mode) {
+    case MFEM_LAYOUT_CSR: break;
+    case MFEM_LAYOUT_ELL: e = (int64_t)A->ell_K * A->ell_npad; break;
+    case MFEM_LAYOUT_DIA:
+      e = (int64_t)A->ell_K * A->ell_npad;
+      if (symp_wanted(A)) {
+        sym = 2;
+        // the rows outside the swept planes read their K slots; the sweep reads symp_pairs value pairs
+        const int64_t swept = (int64_t)(A->symp_p1 - A->symp_p0) * A->symp_PL;
+        e = (int64_t)A->ell_K * (A->ell_npad - swept) + symp_count_entries(A, symp_nseg(ctx, A));
+      } else if (sym27_wanted(A)) {
+        sym = 1;
+        const int gs = sym27_grid(ctx, A, nullptr);
+        const int64_t nch = A->sym_c1 - A->sym_c0;
+        e -= (nch - gs) * A->sym_mx + nch * A->sym_myz;
+      }
+      break;
+    case MFEM_LAYOUT_SELL: e = A->sell_total; break;
+    case MFEM_LAYOUT_LAT27: e = mfem_lat27_entries(A); sym = 3; break;
+    case MFEM_LAYOUT_LAT8: e = mfem_lat8_entries(A); sym = 3; break;
   }
   if (entries) *entries = e;
   if (symmetric_sweep) *symmetric_sweep = sym;
@@ -2070,118 +2070,29 @@ extern "C" int mfem_csr_solver_layout_bytes(mfem_context ctx, mfem_csr A, int64_
   if (rc) return rc;
   rc = mfem_csr_solver_layout_entries(ctx, A, &ent, &sym);
   if (rc) return rc;
-  int64_t b = ent * 8 + A->n * 16;
-  if (mode == 0) b = A->nnz * 12 + A->n * 16 + (A->n + 1) * (A->rowptr_bits / 8);
-  if (mode == 1) b = ent * 12 + A->n * 16;
-  if (mode == 3) {  // sliced layout: padded slots; blocks whose 128 rows share one diagonal list read it instead of their column stream
-    const double reg = A->sell_nblk > 0 ? (double)A->sell_regular_blocks / (double)A->sell_nblk : 0.0;
-    // field-periodic blocks (round 6) read one column slot per node and F values: 1 / F of their column stream
-    const double per = (A->sell_nblk > 0 && A->sell_fields > 1) ? (double)A->sell_periodic_blocks / (double)A->sell_nblk : 0.0;
-    const double colfrac = (1.0 - reg - per) + (A->sell_fields > 1 ? per / (double)A->sell_fields : 0.0);
-    b = A->sell_total * 8 + (int64_t)(colfrac * (double)A->sell_total) * 4 + A->n * 16 + A->n * 4;  // + the row permutation
-    if (A->bsell_F > 0) b = A->sell_total * 8 + A->bsell_slots * 4 + A->n * 16 + A->bsell_ncp * 4;  // node-blocked: one column per F x F values
-  }
-  if (mode == 4) b = mfem_lat27_design_bytes(A);
-  if (mode == 5) b = mfem_lat8_design_bytes(A);
-  if (mode == 2) {
-    b += (A->n > reg ? A->n - reg : 0) * (int64_t)slots * 4;  // rows in generic blocks read their columns
-    if (sym == 2) {  // the sweep stages a (4 + 2) x (32 + 2) neighbourhood of x per step instead of reading each swept entry once
-      const int64_t swept = (int64_t)(A->symp_p1 - A->symp_p0) * A->symp_PL;
-      b += symp_steps(A) * (int64_t)SP_XN * 8 - swept * 8;
+  int64_t b = 0;
+  switch ((mfem_layout)mode) {
+    case MFEM_LAYOUT_CSR: b = A->nnz * 12 + A->n * 16 + (A->n + 1) * (A->rowptr_bits / 8); break;
+    case MFEM_LAYOUT_ELL: b = ent * 12 + A->n * 16; break;
+    case MFEM_LAYOUT_DIA:
+      b = ent * 8 + A->n * 16 + (A->n > reg ? A->n - reg : 0) * (int64_t)slots * 4;  // (rows in generic blocks read their columns)
+      if (sym == 2) {  // the sweep stages a (4 + 2) x (32 + 2) neighbourhood of x per step instead of reading each swept entry once
+        const int64_t swept = (int64_t)(A->symp_p1 - A->symp_p0) * A->symp_PL;
+        b += symp_steps(A) * (int64_t)SP_XN * 8 - swept * 8;
+      }
+      break;
+    case MFEM_LAYOUT_SELL: {  // sliced layout: padded slots; blocks whose 128 rows share one diagonal list read it instead of their column stream
+      const double regf = A->sell_nblk > 0 ? (double)A->sell_regular_blocks / (double)A->sell_nblk : 0.0;
+      // field-periodic blocks (round 6) read one column slot per node and F values: 1 / F of their column stream
+      const double per = (A->sell_nblk > 0 && A->sell_fields > 1) ? (double)A->sell_periodic_blocks / (double)A->sell_nblk : 0.0;
+      const double colfrac = (1.0 - regf - per) + (A->sell_fields > 1 ? per / (double)A->sell_fields : 0.0);
+      b = A->sell_total * 8 + (int64_t)(colfrac * (double)A->sell_total) * 4 + A->n * 16 + A->n * 4;  // + the row permutation
+      if (A->bsell_F > 0) b = A->sell_total * 8 + A->bsell_slots * 4 + A->n * 16 + A->bsell_ncp * 4;  // node-blocked: one column per F x F values
+      break;
     }
+    case MFEM_LAYOUT_LAT27: b = mfem_lat27_design_bytes(A); break;
+    case MFEM_LAYOUT_LAT8: b = mfem_lat8_design_bytes(A); break;
   }
   *bytes = b;
   return MFEM_OK;
 } MFEM_API_CATCH("mfem_csr_solver_layout_bytes")
-
-// What the Krylov loop of the next mfem_solve will run on this pattern: 0 = CSR tile kernel, 1 = slot-major copy with explicit
-// columns, 2 = slot-major copy with diagonal-slotted regular blocks, 3 = row-sorted sliced layout, 4 / 5 = symmetric lattice tiles (one rank;
-// the values of each solve decide, modes 3 / 2 serve it otherwise).  Plans what it reports if that has not happened yet.
-extern "C" int mfem_csr_solver_layout(mfem_context ctx, mfem_csr A, int32_t* mode, int32_t* slots, int64_t* padded_rows,
-                                      int64_t* regular_rows) try {
-  MFEM_REQUIRE(ctx && A, "null handle");
-  int rc = MFEM_OK, m = 0;
-  // the lattice-tile layouts are looked at first: where they apply, the others are planned only on demand (krylov.hip)
-  rc = mfem_lat27_plan(ctx, A);
-  if (rc) return rc;
-  if (mfem_lat27_bytes(A)) m = 4;
-  if (m == 0 && mfem_lat8_for_method(A, true)) {  // (asked first, as mfem_solve does: a one-field brick pattern answers for cg! = mode 2, and the plan's
-    rc = mfem_lat8_plan(ctx, A);                   //  entry-by-entry check of the pattern costs 27 ms at 512^3 -- VERDICT r4 item 8)
-    if (rc) return rc;
-    if (mfem_lat8_bytes(A) && mfem_lat8_for_method(A, true)) m = 5;
-  }
-  if (m == 0) {
-    rc = mfem_ell_plan(ctx, A);
-    if (rc) return rc;
-    if (mfem_ell_vals_bytes(A)) m = (A->dia_state == 1 && g_dia_enable) ? 2 : 1;
-    if (m == 0 && !(A->ell_state == 1 && g_ell_enable)) {
-      rc = mfem_sell_plan(ctx, A);
-      if (rc) return rc;
-      if (mfem_sell_vals_bytes(A)) m = 3;
-    }
-  }
-  if (mode) *mode = m;
-  if (slots) *slots = (m == 1 || m == 2) ? A->ell_K : m >= 3 ? A->max_row_nnz : 0;
-  if (padded_rows) *padded_rows = (m == 1 || m == 2) ? A->ell_npad : m == 3 ? (A->bsell_F > 0 ? A->sell_nblk * 64 * A->bsell_F : A->sell_nblk * 128) : 0;
-  if (regular_rows) *regular_rows = m == 2 ? (int64_t)A->dia_regular_blocks * 128 : 0;
-  return MFEM_OK;
-} MFEM_API_CATCH("mfem_csr_solver_layout")
-
-// y = alpha A x + beta y through the layout mfem_solve would use for this pattern (the one-off conversion of `vals` included):
-// a test / diagnostic entry point -- production SpMVs of caller-supplied values go through mfem_spmv_csr.
-extern "C" int mfem_spmv_solver_layout(mfem_context ctx, mfem_csr A, const double* vals, const double* x, double* y, double alpha,
-                                       double beta) try {
-  MFEM_REQUIRE(ctx && A, "null handle");
-  MFEM_REQUIRE(A->n == 0 || (x && y && (A->nnz == 0 || vals)), "null vector");
-  if (A->n == 0) return MFEM_OK;
-  int rc = MFEM_OK;
-  bool bound = false;
-  {  // lattice tiles, if the structure allows them and these values are symmetric
-    rc = mfem_lat27_plan(ctx, A);
-    if (rc) return rc;
-    size_t lb = mfem_lat27_bytes(A);
-    const bool is27 = lb != 0;
-    if (!lb && mfem_lat8_for_method(A, true)) {
-      rc = mfem_lat8_plan(ctx, A);
-      if (rc) return rc;
-      if (mfem_lat8_for_method(A, true)) lb = mfem_lat8_bytes(A);
-    }
-    if (lb) {
-      const size_t lay = (lb + 255) & ~(size_t)255;
-      rc = mfem_ws_reserve(ctx, lay + (2 * (size_t)A->n + (size_t)(A->ncols > A->n ? A->ncols : A->n)) * sizeof(double));
-      if (rc) return rc;
-      double* scratch = (double*)((char*)ctx->ws + lay);
-      rc = is27 ? mfem_lat27_bind(ctx, A, vals, (double*)ctx->ws, nullptr, scratch, mfem_rem_diag())
-                : mfem_lat8_bind(ctx, A, vals, (double*)ctx->ws, nullptr, scratch, mfem_rem_diag());
-      if (rc) return rc;
-      bound = mfem_lat27_bound(A, vals) || mfem_lat8_bound(A, vals);
-    }
-  }
-  if (!bound) {
-    rc = mfem_ell_plan(ctx, A);
-    if (rc) return rc;
-    const size_t bytes = mfem_ell_vals_bytes(A);
-    if (bytes) {
-      rc = mfem_ws_reserve(ctx, bytes);
-      if (rc) return rc;
-      rc = mfem_ell_bind(ctx, A, vals, (double*)ctx->ws, nullptr, nullptr);
-      if (rc) return rc;
-    } else {
-      rc = mfem_sell_plan(ctx, A);
-      if (rc) return rc;
-      const size_t sb = mfem_sell_vals_bytes(A);
-      if (sb) {
-        rc = mfem_ws_reserve(ctx, sb);
-        if (rc) return rc;
-        rc = mfem_sell_bind(ctx, A, vals, (double*)ctx->ws, nullptr);
-        if (rc) return rc;
-      }
-    }
-  }
-  rc = mfem_spmv_launch(ctx, A, vals, x, y, alpha, beta, nullptr, nullptr, nullptr, nullptr);
-  mfem_ell_unbind(A);
-  mfem_sell_unbind(A);
-  mfem_lat27_unbind(A);
-  mfem_lat8_unbind(A);
-  return rc;
-} MFEM_API_CATCH("mfem_spmv_solver_layout")

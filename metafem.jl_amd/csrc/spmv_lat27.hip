@@ -25,6 +25,7 @@
 //   * y differs from the CSR kernel's by round-off (other summation order), and the order in which the waves of a workgroup add into
 //     an LDS cell is not fixed: results are reproducible to ~1e-16 relative, not bitwise (mfem_debug_set_lat27(0) selects the sliced layout).
 #include "blas1.h"
+#include "layouts.h"
 #include "spmv_lat_tables.h"
 #include "krylov.h"  // scalar / flag slots of the Krylov loop (the fused CG update below)
 
@@ -1148,8 +1149,6 @@ int mfem_lat27_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, doub
   return MFEM_OK;
 }
 
-bool mfem_lat27_bound(const mfem_csr_s* A, const double* vals) { return A->lat27_vals && vals == A->lat27_src; }
-
 void mfem_lat27_unbind(mfem_csr_s* A) {
   if (A->lat27_vals) A->rem_active = 0;  // (the remainder belongs to the bind)
   A->lat27_vals = nullptr;
@@ -1235,7 +1234,7 @@ int64_t mfem_lat27_entries(const mfem_csr_s* A) { return (int64_t)lat27_read_dou
 
 // ---- the fused CG iteration (krylov.hip, cg_solve_pass): pass 1 alone (mfem_spmv_halo with y = nullptr), the dot-product partials, pass 2 + residual update
 bool mfem_lat27_cg_fused(const mfem_context_s* ctx, const mfem_csr_s* A, const double* vals) {
-  return g_lat27_cg_fused && mfem_lat27_bound(A, vals) && !A->lat27_dsc && !ctx->comm && !A->rem_active;
+  return g_lat27_cg_fused && A->lat27_vals && vals == A->lat27_src && !A->lat27_dsc && !ctx->comm && !A->rem_active;
 }
 const double* mfem_lat27_dot_partials(const mfem_csr_s* A, int* np) {
   const Lat27Geom G = lat27_geom(A);

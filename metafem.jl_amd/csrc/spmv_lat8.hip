@@ -18,6 +18,7 @@
 //     the CSR kernel, mfem_sym_probe in spmv_lat27.hip, within 4e-13 of the largest entry; the diagonal-slotted layout serves the solve otherwise).  Results equal the CSR kernel's to round-off, not
 //     bitwise, and not bitwise from run to run (order of the LDS adds of different waves).  mfem_debug_set_lat8(0) switches the layout off.
 #include "blas1.h"
+#include "layouts.h"
 #include "spmv_lat_tables.h"
 
 #define L8_TI 8
@@ -701,8 +702,6 @@ int mfem_lat8_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, doubl
   A->lat8_scaled = dsc ? 1 : 0;
   return MFEM_OK;
 }
-
-bool mfem_lat8_bound(const mfem_csr_s* A, const double* vals) { return A->lat8_vals && vals == A->lat8_src; }
 
 void mfem_lat8_unbind(mfem_csr_s* A) {
   if (A->lat8_vals) A->rem_active = 0;  // (the remainder belongs to the bind)

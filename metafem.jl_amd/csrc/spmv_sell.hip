@@ -15,6 +15,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "blas1.h"
+#include "layouts.h"
 
 #define SELL_B 128
 typedef double s_d2 __attribute__((ext_vector_type(2)));
@@ -1067,8 +1068,6 @@ int mfem_sell_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, doubl
   A->sell_src = vals;
   return MFEM_OK;
 }
-
-bool mfem_sell_bound(const mfem_csr_s* A, const double* vals) { return A->sell_vals && vals == A->sell_src; }
 
 void mfem_sell_unbind(mfem_csr_s* A) {
   A->sell_vals = nullptr;
