@@ -35,11 +35,16 @@ int mfem_debug_set(const char* key, int64_t a, int64_t b);
  * over the XCDs instead of a contiguous eighth each | bit 25: no column-offset inspection of the row-block tiles (before the pattern is
  * created), persistent workgroups per CU. */
 /* ^ key "spmv": mfem_debug_set("spmv", a, b) with (int xcd_aware, int grid_mult) = (a[, b]) */
-/* modes 1/2: bit 0 on/off; bit 1 never use diagonal slots; bits 4-7 / 16-19 kernel variants; bits 8-15 workgroups per CU;
- * bit 20 XCD-contiguous row chunks; bit 22 symmetric sweep kernels off; bit 23 the workgroup-tile sweep (k_spmv_sym27) instead of
- * the wave-private patch sweep (k_spmv_symp);
- * bits 24-25 workgroup size of the diagonal-slotted kernel (0: 256, 1: 512, 2: 1024, 3: 128); bit 26 rows outside the swept planes
- * in a launch of their own; bit 27 the patch-major copy made from the slot-major copy in a second pass. */
+/* modes 1/2: bit 0 on/off; bit 1 never use diagonal slots; bits 8-15 workgroups per CU of the per-row kernels; bits 16-19: the value 8 = the
+ * diagonal-slotted per-row kernel without the shared x loads of consecutive diagonals (and no sweep); bit 20 XCD-contiguous row chunks; bit 22
+ * symmetric sweep kernels off; bit 23 the workgroup-tile sweep (k_spmv_sym27) instead of the wave-private patch sweep (k_spmv_symp); bit 26 rows
+ * outside the swept planes in a launch of their own; bit 27 the patch-major copy made from the slot-major copy in a second pass; bit 28 the layout
+ * copy without its software pipeline; bit 29 the swept rows by the copy's row tiles instead of k_symp_fill; bit 30 the symmetry of the swept rows
+ * by the check pass instead of the fill's fingerprint.
+ * RETIRED, accepted and ignored: bits 4-7 (variants of k_spmv_ell), every value of bits 16-19 other than 8 (variants of k_spmv_dia) and bits 24-25
+ * (workgroup size of k_spmv_dia) -- the sweeps of round 1 (profiles/r01_spmv_sweep.txt) chose the kernels that remain.
+ * These knobs are read when a layout is BOUND (every mfem_solve and mfem_spmv_solver_layout binds its own): a product runs the kernel its bind
+ * recorded; only the launch geometry (bits 8-15, 20, 26) is read per product.  Set them before the solve. */
 /* ^ key "ell": mfem_debug_set("ell", a, b) with (int enable) = (a[, b]) */
 /* mode 3: bit 0 on/off; bit 1 always read explicit columns; bit 2 every XCD walks a contiguous eighth of the blocks; bits 4-7 (x 8 = R)
  * rows sorted inside lattice regions of R^3 points when the pattern carries a lattice hint (mfem_brick_pattern) -- both measured slower than

@@ -154,35 +154,33 @@ struct mfem_csr_s {
   // slab info (multi-GPU): rows = owned nodes, x has ghost planes; 0 for single GPU
   int64_t x_offset;  // offset of the first owned entry inside the local x (per field)
   int64_t ncols;     // columns the pattern addresses: n, or n + ghost entries for a slab pattern (0 = n)
-  // slot-major padded copy for near-uniform rows (spmv_ell.hip): ell_state 0 = not planned, -1 = not eligible, 1 = ready
+  // slot-major padded copy for near-uniform rows (spmv_ell.hip; shared declarations: spmv_ell.h): ell_state 0 = not planned, -1 = not eligible, 1 = ready
   int ell_state, ell_K;
   int64_t ell_npad;
   int32_t* ell_cols;        // owned, [K][npad], 0-based
   const double* ell_src;    // the CSR-ordered values the bound copy mirrors (identity of the `vals` argument)
   double* ell_vals;         // not owned (solver workspace), [K][npad]
-  // diagonal-slotted variant (all entries on <= 32 diagonals): dia_state 0 = not inspected, -1 = no, 1 = yes
+  // diagonal-slotted variant (spmv_dia.hip; all entries on <= 32 diagonals): dia_state 0 = not inspected, -1 = no, 1 = yes
   int dia_state, dia_classes;
-  void* dia_dev;            // owned, device copy of the diagonal lists (DiaOffsets, spmv_ell.hip)
+  void* dia_dev;            // owned, device copy of the diagonal lists (DiaOffsets, spmv_ell.h)
   int32_t* dia_flags;       // owned, one int per 128-row block: 1 = regular (diagonal-slotted), 0 = explicit columns
   int32_t dia_regular_blocks;
   int dia_triples;          // the diagonals come in runs of three consecutive offsets
-  // symmetric sweep variant of the diagonal-slotted SpMV (27-point lattice stencil): sym_state 0 = not inspected, -1 = no, 1 = structure ok
+  // symmetric sweep variant of the diagonal-slotted SpMV (spmv_sym.hip; 27-point lattice stencil): sym_state 0 = not inspected, -1 = no, 1 = structure ok
   int sym_state;
   int64_t sym_c0, sym_c1;   // chunks (512 rows) [c0, c1) whose blocks are all regular
   int sym_cls;              // the diagonal list (class) with the lattice form
   int sym_S;                // chunks per lattice plane (rounded): a workgroup sweeps chunks c, c + S, c + 2 S, ...
-  int sym_bound;            // 1 = the bound values passed the bitwise symmetry check of this bind
   int64_t sym_mx, sym_myz;  // matrix entries per chunk the sweep kernel takes from LDS: previous-plane diagonals / in-chunk -y, -z
   int ell_bound_mode;       // 0 none, 1 slot-major with explicit columns, 2 diagonal-slotted
-  // wave-private (j, k)-patch form of the symmetric sweep (spmv_ell.hip: k_spmv_symp): symp_state 0 = not inspected, -1 = no, 1 = structure ok
+  int dia_kernel;           // mode 2: the product kernel the bound values got, after their symmetry verdict (DiaKernel, spmv_ell.h; 0 = nothing bound)
+  // wave-private (j, k)-patch form of the symmetric sweep (spmv_sym.hip: k_spmv_symp): symp_state 0 = not inspected, -1 = no, 1 = structure ok
   int symp_state;
   int symp_m1, symp_m2;     // lattice lines per plane, points per line
   int64_t symp_PL;          // rows per lattice plane (m1 * m2)
   int symp_p0, symp_p1;     // regular lattice planes [p0, p1) (plane = row / PL): the rows the sweep computes
   int symp_NS, symp_NPk;    // strips of 4 lines, patches of 32 points per line
-  double* symp_vals;        // not owned (solver workspace, behind ell_vals): [plane - p0][patch][27 x 128 + edge block]
-  int symp_bound;           // 1 = the bound values passed the bitwise symmetry check of the mirrored pairs
-  int64_t symp_pairs;       // value pairs (16 bytes) one SpMV of the sweep reads from memory (accounting)
+  double* symp_vals;        // not owned (solver workspace, behind ell_vals): [plane - p0][patch][27 x 128 + edge block]; set while dia_kernel is the patch sweep
   // row-sorted sliced ELL for rows of uneven length (spmv_sell.hip): sell_state 0 = not planned, -1 = no, 1 = ready
   int sell_state;
   int64_t sell_total, sell_nblk;
@@ -295,7 +293,7 @@ int mfem_spmv_ell_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* vals,
 
 // The solver layouts of a pattern (layout.hip): which copy of the values a solve runs on, and its binding and release.  The values are the
 // mode numbers of mfem_csr_solver_layout: the CSR tile kernel on the caller's values (no copy), slot-major copy with explicit columns / with
-// diagonal-slotted regular blocks (spmv_ell.hip), row-sorted sliced ELL (spmv_sell.hip), symmetric lattice tiles (spmv_lat27.hip, spmv_lat8.hip)
+// diagonal-slotted regular blocks (spmv_ell.hip, spmv_dia.hip and the sweeps of spmv_sym.hip), row-sorted sliced ELL (spmv_sell.hip), symmetric lattice tiles (spmv_lat27.hip, spmv_lat8.hip)
 enum mfem_layout : int32_t { MFEM_LAYOUT_CSR = 0, MFEM_LAYOUT_ELL = 1, MFEM_LAYOUT_DIA = 2, MFEM_LAYOUT_SELL = 3, MFEM_LAYOUT_LAT27 = 4, MFEM_LAYOUT_LAT8 = 5 };
 // What a pattern offers a solve: a tile layout (taken if the values pass its symmetry probe) and a row layout, each with the workspace bytes of
 // its copy (MFEM_LAYOUT_CSR, 0: none)

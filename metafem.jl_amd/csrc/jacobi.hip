@@ -11,7 +11,7 @@ typedef double d2_t __attribute__((ext_vector_type(2)));
 typedef int i2_t __attribute__((ext_vector_type(2)));
 
 // mode 0: d[r] = |K_rr| (rows without a stored diagonal keep their preset value; so do rows whose stored diagonal is exactly
-//         0 -- the reference would take |0| and divide by it; the solver layouts of spmv_ell.hip cannot tell a stored zero
+//         0 -- the reference would take |0| and divide by it; the solver layouts of spmv_ell.hip / spmv_dia.hip cannot tell a stored zero
 //         from a padding slot, so every layout applies this one guarded rule)
 // mode 1: d[r] = sqrt(sum_j K_rj^2)
 template <typename RP>

@@ -1,4 +1,4 @@
-// The solver layouts of a CSR handle, planned, bound and released here only: mfem_solve (krylov.hip), the layout query and the diagnostic product
+// The solver layouts of a CSR handle, planned, bound, released and accounted for here only: mfem_solve (krylov.hip), the layout query and the diagnostic product
 // below take the same rules.  At most one layout is bound at a time; which one serves a product is read off the per-layout pointers, never cached
 // beside them: the tile binds' symmetry probe (mfem_sym_probe) unbinds and rebinds the tiles through callbacks of its own.  Nothing here issues a
 // collective: a refusal of the tiles is a rank-local verdict (krylov.hip: solve_inner).
@@ -97,6 +97,37 @@ extern "C" int mfem_csr_solver_layout(mfem_context ctx, mfem_csr A, int32_t* mod
   if (regular_rows) *regular_rows = m == MFEM_LAYOUT_DIA ? (int64_t)A->dia_regular_blocks * 128 : 0;
   return MFEM_OK;
 } MFEM_API_CATCH("mfem_csr_solver_layout")
+
+// The accounting of the planned solver layout, per layout (layouts.h).  Entries: matrix entries (8-byte values) one SpMV reads from memory; sweep: 0 none,
+// 1 / 2 the structure allows the workgroup-tile / patch sweep of mode 2 (whether it runs is decided per solve by the bitwise symmetry check of the
+// values), 3 symmetric tiles.  Bytes: what one SpMV moves by design (bench.py's roofline numerator) -- matrix entries, 4-byte columns where the kernel
+// reads them, x as often as the kernel fetches it from memory by design, y once.
+static int layout_account(mfem_context ctx, mfem_csr A, int64_t* entries, int32_t* sweep, int64_t* bytes) {
+  int32_t mode = 0, sym = 0;
+  const int rc = mfem_csr_solver_layout(ctx, A, &mode, nullptr, nullptr, nullptr);
+  if (rc) return rc;
+  int64_t e = A->nnz, b = A->nnz * 12 + A->n * 16 + (A->n + 1) * (A->rowptr_bits / 8);
+  switch ((mfem_layout)mode) {
+    case MFEM_LAYOUT_CSR: break;
+    case MFEM_LAYOUT_ELL:
+    case MFEM_LAYOUT_DIA: e = mfem_ell_entries(ctx, A, &sym); b = mfem_ell_design_bytes(ctx, A); break;
+    case MFEM_LAYOUT_SELL: e = mfem_sell_entries(A); b = mfem_sell_design_bytes(A); break;
+    case MFEM_LAYOUT_LAT27: e = mfem_lat27_entries(A); b = mfem_lat27_design_bytes(A); sym = 3; break;
+    case MFEM_LAYOUT_LAT8: e = mfem_lat8_entries(A); b = mfem_lat8_design_bytes(A); sym = 3; break;
+  }
+  if (entries) *entries = e;
+  if (sweep) *sweep = sym;
+  if (bytes) *bytes = b;
+  return MFEM_OK;
+}
+extern "C" int mfem_csr_solver_layout_entries(mfem_context ctx, mfem_csr A, int64_t* entries, int32_t* symmetric_sweep) try {
+  MFEM_REQUIRE(ctx && A, "null argument");
+  return layout_account(ctx, A, entries, symmetric_sweep, nullptr);
+} MFEM_API_CATCH("mfem_csr_solver_layout_entries")
+extern "C" int mfem_csr_solver_layout_bytes(mfem_context ctx, mfem_csr A, int64_t* bytes) try {
+  MFEM_REQUIRE(ctx && A && bytes, "null argument");
+  return layout_account(ctx, A, nullptr, nullptr, bytes);
+} MFEM_API_CATCH("mfem_csr_solver_layout_bytes")
 
 // y = alpha A x + beta y through the layout mfem_solve would use for this pattern with cg! (the one-off conversion of `vals` included): the tiles if
 // these values pass their probe, the row layout otherwise.  A test / diagnostic entry point -- production SpMVs of caller-supplied values go

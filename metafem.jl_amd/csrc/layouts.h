@@ -1,5 +1,6 @@
-// The per-layout planning, binding and release of the solver layouts.  Internal to layout.hip, which chooses among them, and to the files
-// that implement them (spmv_ell.hip, spmv_sell.hip, spmv_lat27.hip, spmv_lat8.hip): every other file goes through mfem_layout_* (common.h).
+// The per-layout planning, binding, release and accounting of the solver layouts.  Internal to layout.hip, which chooses among them, and to the
+// files that implement them (spmv_ell.hip with spmv_dia.hip, spmv_sym.hip; spmv_sell.hip; spmv_lat27.hip; spmv_lat8.hip): every
+// other file goes through mfem_layout_* (common.h).  Accounting of the tiles: mfem_lat27_entries / _design_bytes and the lat8 twins (common.h).
 #pragma once
 #include "common.h"
 
@@ -17,9 +18,13 @@ size_t mfem_sell_vals_bytes(const mfem_csr_s* A);
 int mfem_sell_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc);
 void mfem_sell_unbind(mfem_csr_s* A);
 void mfem_sell_free(mfem_csr_s* A);
+int64_t mfem_sell_entries(const mfem_csr_s* A);       // matrix entries (8-byte values) one SpMV reads from memory
+int64_t mfem_sell_design_bytes(const mfem_csr_s* A);  // bytes one SpMV moves by design
 int mfem_ell_plan(mfem_context_s* ctx, mfem_csr_s* A);
 size_t mfem_ell_vals_bytes(const mfem_csr_s* A);
 int mfem_ell_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, const double* ssym);
 bool mfem_dia_layout_planned(const mfem_csr_s* A);  // mfem_ell_bind would make the diagonal-slotted copy (mode 2)
 void mfem_ell_unbind(mfem_csr_s* A);
 void mfem_ell_free(mfem_csr_s* A);
+int64_t mfem_ell_entries(const mfem_context_s* ctx, const mfem_csr_s* A, int32_t* sweep);  // modes 1 and 2; *sweep: 2 / 1 = the structure allows the patch / the tile sweep
+int64_t mfem_ell_design_bytes(const mfem_context_s* ctx, const mfem_csr_s* A);

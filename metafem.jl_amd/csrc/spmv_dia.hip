@@ -1,0 +1,746 @@
+// Mode 2 of the slot-major solver layout (spmv_ell.hip, spmv_ell.h): the diagonal-slotted copy -- the inspection of the pattern, the per-solve
+// copy of the values (k_dia_vals, k_symp_fill), the per-row product kernel.  The symmetric sweeps on the same copy: spmv_sym.hip.
+#include "blas1.h"
+#include "spmv_ell.h"
+
+// ---------------------------------------------------------------------------------------------------------------
+// Diagonal-slotted blocks.  When every entry of the matrix sits on one of D <= 32 diagonals (col - row in a fixed sorted
+// offset list: any lattice stencil -- 27 for the hex-8 scalar operator), slot s of a row is "the entry on diagonal s"
+// (zero if the row has none) instead of "the s-th entry".  A 128-row block whose rows only touch in-range positions is
+// then REGULAR: the column of (row r, slot s) is r + off[s], the column stream is not read at all, and the gather is a
+// unit-stride 16-byte load.  Blocks that contain rows pointing outside [0, n_x) on some diagonal (first / last rows) or
+// entries off the diagonal list (ghost columns of a slab) stay on the generic slot-major path with explicit columns.
+// The detection is an inspection of the caller's CSR pattern; nothing about the mesh is assumed.
+// ---------------------------------------------------------------------------------------------------------------
+
+// flags[b] = c + 1 when every row of the 128-row block b is regular for class c: all its entries sit on the class's
+// diagonals and r + off[s] is a valid x index for EVERY listed diagonal (so the kernel may load x there even where the
+// row has no entry); 0 otherwise.  nreg counts the regular blocks.
+template <typename RP>
+__global__ __launch_bounds__(128) void k_dia_flags(int64_t n, int64_t nx, const RP* __restrict__ rowptr,
+                                                     const int32_t* __restrict__ col, int base,
+                                                     const DiaOffsets* __restrict__ Op, int32_t* __restrict__ flags,
+                                                     int32_t* __restrict__ nreg) {
+  const DiaOffsets& O = *Op;
+  __shared__ int ok_mask;
+  for (int64_t blk = blockIdx.x; blk * 128 < n; blk += gridDim.x) {
+    if (threadIdx.x == 0) ok_mask = (1 << O.ncls) - 1;
+    __syncthreads();
+    const int64_t r = blk * 128 + threadIdx.x;
+    int mask = 0;
+    if (r < n) {
+      const int64_t lo = (int64_t)rowptr[r] - base, hi = (int64_t)rowptr[r + 1] - base;
+      for (int c = 0; c < O.ncls; ++c) {
+        const int D = O.D[c];
+        bool ok = r + O.off[c][0] >= 0 && r + O.off[c][D - 1] < nx;
+        int s = 0;
+        int64_t last = INT64_MIN;
+        for (int64_t j = lo; j < hi && ok; ++j) {  // columns strictly ascending, offsets ascending: merge
+          const int64_t d = (int64_t)col[j] - base - r;
+          if (d <= last) ok = false;  // unsorted or duplicate columns: only the explicit-column path sums every entry
+          last = d;
+          while (s < D && O.off[c][s] < d) ++s;
+          if (s == D || O.off[c][s] != d) ok = false;
+        }
+        if (ok) mask |= 1 << c;
+      }
+    }  // rows past n (partial last block): mask 0 -> generic path
+    atomicAnd(&ok_mask, mask);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int m = ok_mask;
+      flags[blk] = m ? __ffs(m) : 0;
+      if (m) atomicAdd(nreg, 1);
+    }
+    __syncthreads();
+  }
+}
+
+// values in diagonal slots + per-block regular flag (regular: every row r of the block has 0 <= r + off[s] < nx for all s).
+// With pv != nullptr the rows of the swept lattice planes [Gm.p0, Gm.p1) go straight to the patch-major copy of the patch sweep (layout:
+// k_spmv_symp) -- their 27 slots, the edge block entries they own, and the diagonal alone to the slot-major copy (k_ell_diag reads it
+// there) -- instead of through the slot-major copy and a second pass (k_symp_bind): 1.97 + 1.85 ms -> one pass at 256^3.
+// LPR = lanes per row: 1 (64 rows per wave tile) or 2 (32 rows); SYM: the symmetrically scaled copy -- its own instantiation, so that the plain
+// copy's code is what it was (2.4 ms at 256^3; 2.7 with the test for the scaling in it)
+template <typename RP, int LPR, bool SYM, bool PIPE>
+__global__ __launch_bounds__(MFEM_BLOCK) void k_dia_vals(int64_t n, int64_t npad, int K, const RP* __restrict__ rowptr,
+                                                           const int32_t* __restrict__ col, const double* __restrict__ vals,
+                                                           int base, const DiaOffsets* __restrict__ Op,
+                                                           const int32_t* __restrict__ flags, double* __restrict__ out, SympGeom Gm,
+                                                           double* __restrict__ pv, const double* __restrict__ dsc,
+                                                           const double* __restrict__ ssym, int fast) {
+  // ssym != nullptr: the copy is S^-1 A S^-1 with ssym = 1 / S, entry * (ssym[row] * ssym[column]) with the PRODUCT of the two factors formed
+  // first -- a mirrored pair is then multiplied by the same number, so a bitwise symmetric matrix stays bitwise symmetric (the scaled CG,
+  // cg_variant 4).  (Multiplying by reciprocals, not dividing: 27 divisions per row cost more than the rest of the placement.)
+  // dsc != nullptr: the copy is the right-Jacobi-scaled matrix, entry / dsc[its column] (Mat_Div_Jacobi folded into this pass; the
+  // columns are then read for every tile)
+  const DiaOffsets& O = *Op;
+  extern __shared__ double lds[];
+  const int64_t slo = pv ? (int64_t)Gm.p0 * Gm.PL : 0, shi = pv ? (int64_t)Gm.p1 * Gm.PL : 0;  // swept rows
+  const int spNP = Gm.NS * Gm.NPk;
+  const int64_t spT = (int64_t)spNP * (Gm.p1 - Gm.p0);
+  // LPR = 2: a wave takes 32 rows at a time, two lanes per row -- lanes 0..31 walk their row's entries forward through the first half of
+  // the diagonal list, lanes 32..63 walk them backward through the second half.  A lane per row (64 rows per tile) needs 12 x 64 x K
+  // bytes of staging per wave: two waves per CU on 81-entry rows (4.0 ms per bind at C3 against 3.4 ms with two lanes); on 27-entry
+  // rows six waves per CU are enough and the lane per row is faster (2.4 against 2.7 ms at 256^3).
+  constexpr int RT = 64 / LPR, SH = LPR == 2 ? 5 : 6;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), nw = blockDim.x >> 6;  // (w: wave-uniform, known to the compiler)
+  const int half = LPR == 2 ? lane >> 5 : 0, rl = lane & (RT - 1);
+  double* T = lds + (size_t)w * RT * K;
+  // columns are staged only for the Jacobi scaling pass (dsc); the placement below needs them for the few tiles that are not `full`
+  // (mesh boundary) and reads those from memory -- 8 instead of 12 bytes of LDS per staged entry, half as many more waves per CU
+  int32_t* Tc = reinterpret_cast<int32_t*>(lds + (size_t)nw * RT * K) + (size_t)w * RT * K;
+  const bool stage_cols = !PIPE && dsc != nullptr;
+  const int64_t ntiles = npad >> SH;
+  constexpr int NB = 28;
+  // Software pipeline (round 4; a lane per row, rows of at most NB entries, no scaling pass -- the 27-diagonal lattice copies of C2): the NEXT tile's
+  // values are loaded into registers before the current tile is placed, so a wave keeps one tile of loads in flight while it reads LDS and issues
+  // its 27 scattered stores -- each wave had one memory round trip per tile with nothing else outstanding (10 waves per CU).
+  constexpr bool pipe = PIPE;  // (chosen at the launch: LPR == 1, no scaling pass, K <= NB)
+  const int64_t tstride = (int64_t)gridDim.x * nw;
+  double tvn[NB];
+  int64_t s0n = 0;
+  int cntn = 0;
+  auto tile_span = [&](int64_t t, int64_t& s0_, int& cnt_) {
+    const int64_t q0 = t << SH, qend = (q0 + RT < n) ? q0 + RT : n;
+    s0_ = q0 < n ? (int64_t)rowptr[q0] - base : 0;
+    cnt_ = q0 < n ? (int)((int64_t)rowptr[qend] - base - s0_) : 0;
+  };
+  auto prefetch = [&]() {
+#pragma unroll
+    for (int u = 0; u < NB; ++u) {
+      const int i = lane + 64 * u;
+#if defined(DV_ABL) && DV_ABL == 2   // (ablation: no value loads)
+      tvn[u] = (double)i;
+#else
+      tvn[u] = i < cntn ? __builtin_nontemporal_load(vals + s0n + i) : 0.0;
+#endif
+    }
+  };
+  if (pipe) {
+    const int64_t t0 = (int64_t)blockIdx.x * nw + w;
+    if (t0 < ntiles) {
+      tile_span(t0, s0n, cntn);
+      prefetch();
+    }
+  }
+  // fast != 0: the swept rows are filled by k_symp_fill (below) -- this launch visits only the tiles that hold other rows (the tiles [sk0, sk1) lie inside the
+  // swept range and are stepped over) and leaves the swept rows of the tiles it visits alone
+  const int64_t sk0 = fast ? (slo + RT - 1) >> SH : 0, sk1 = fast ? (shi >> SH > sk0 ? shi >> SH : sk0) : 0;
+  for (int64_t tix = (int64_t)blockIdx.x * nw + w; tix < ntiles - (sk1 - sk0); tix += tstride) {
+    const int64_t tile = tix < sk0 ? tix : tix + (sk1 - sk0);
+    const int64_t r0 = tile << SH, r = r0 + rl;
+    const int64_t rend = (r0 + RT < n) ? r0 + RT : n;
+    int64_t lo = 0;
+    int len = 0;
+    if (r < n) {
+      lo = (int64_t)rowptr[r] - base;
+      len = (int)((int64_t)rowptr[r + 1] - base - lo);
+    }
+    int64_t s0;
+    int cnt;  // <= RT D
+    int64_t s0_next = 0;
+    int cnt_next = 0;
+    if (pipe) {
+      s0 = s0n;
+      cnt = cntn;
+      if (tile + tstride < ntiles) tile_span(tile + tstride, s0_next, cnt_next);  // (these row pointers arrive beside the values in flight)
+    } else {
+      s0 = r0 < n ? (int64_t)rowptr[r0] - base : 0;
+      cnt = r0 < n ? (int)((int64_t)rowptr[rend] - base - s0) : 0;
+    }
+    const int cls = __builtin_amdgcn_readfirstlane(flags[tile >> (7 - SH)]) - 1;
+    // a tile of a regular block whose rows all have every diagonal of the class (cnt = RT D: away from the mesh boundary, nearly all
+    // tiles): entry s of a row IS its slot s -- the columns are not needed, a third of the kernel's reads
+    const bool full = cls >= 0 && cnt == RT * O.D[cls];
+    if (pipe) {
+#pragma unroll
+      for (int u = 0; u < NB; ++u) {
+        const int i = lane + 64 * u;
+        if (i < cnt) T[i] = tvn[u];
+      }
+      s0n = s0_next;
+      cntn = cnt_next;
+      if (tile + tstride < ntiles) prefetch();  // in flight until the next trip's LDS stores
+    }
+    // staging: all loads of a lane are issued before the first LDS store.  28 in flight per lane: a 64-row tile of 27-entry rows (27 per lane) is
+    // ONE memory round trip, a 32-row tile of 81-entry rows two (SQ counters of the version with batches of 8: 79 % of the wave cycles waiting,
+    // ~10 waves per CU with 4 KB in flight each)
+    if constexpr (!PIPE)
+    for (int i0 = lane; i0 < cnt; i0 += 64 * NB) {
+      double tv[NB];
+      int32_t tc[NB];
+#pragma unroll
+      for (int u = 0; u < NB; ++u) {
+        const int i = i0 + 64 * u;
+        tv[u] = i < cnt ? vals[s0 + i] : 0.0;
+        tc[u] = (i < cnt && stage_cols) ? col[s0 + i] : 0;
+      }
+#pragma unroll
+      for (int u = 0; u < NB; ++u) {
+        const int i = i0 + 64 * u;
+        if (i < cnt) {
+          T[i] = tv[u];
+          if (stage_cols) Tc[i] = tc[u] - base;
+        }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    if (!PIPE && dsc) {
+      // right Jacobi scaling of the staged tile, entry / dsc[column]: the gathers of 16 entries per lane are in flight together -- one more
+      // memory round trip per batch of 1024 entries (dividing inside the staging loop above made every batch of its loads wait twice)
+      __builtin_amdgcn_wave_barrier();
+      for (int i0 = lane; i0 < cnt; i0 += 64 * 16) {
+        double dd[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+          const int i = i0 + 64 * u;
+          dd[u] = i < cnt ? dsc[Tc[i]] : 1.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+          const int i = i0 + 64 * u;
+          if (i < cnt) T[i] /= dd[u];
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_s_waitcnt(0xC07F);
+    }
+    const int off0 = (int)(lo - s0);
+    const int dir = half ? -1 : 1;
+    double sr = 1.0;
+    if constexpr (SYM) sr = r < n ? ssym[r] : 1.0;
+    auto sym_scaled = [&](double a, int64_t c) -> double {
+      if constexpr (SYM) return a * (sr * ssym[c]);
+      else return a;
+    };
+    auto colat = [&](int j) -> int64_t { return stage_cols ? (int64_t)Tc[off0 + j] : (int64_t)col[lo + j] - base; };
+    if (cls >= 0 && r0 < shi && r0 + RT > slo) {  // a tile with swept rows (all of them in regular blocks of the 27-diagonal lattice class)
+      const bool sw = r >= slo && r < shi;
+      if (fast && sw) len = 0;  // (k_symp_fill's row: nothing is stored for it below)
+      int line = 0, pcol = 0;
+      int64_t mainoff = 0, lowoff = 0, edgeoff = 0;
+      if (sw) {
+        const int p = (int)(r / Gm.PL), rem = (int)(r - (int64_t)p * Gm.PL), jj = rem / Gm.m2, kk = rem - jj * Gm.m2;
+        line = jj % SP_L;
+        pcol = kk % SP_W;
+        const int64_t step = (int64_t)(p - Gm.p0) * spNP + (jj / SP_L) * Gm.NPk + kk / SP_W;
+        mainoff = step * SP_MAIN + line * SP_W + pcol;
+        lowoff = spT * SP_MAIN + step * SP_LOW + line * SP_W + pcol;
+        edgeoff = step * SP_MAIN + 14 * SP_ROWS;
+      }
+      int j = half ? len - 1 : 0;
+#pragma unroll
+      for (int t = 0; t < (LPR == 2 ? 14 : 27); ++t) {  // forward lanes: slots 0..13 (all 27 with a lane per row), backward lanes: slots 26..14
+        const int sl = half ? 26 - t : t;
+        const bool act = half == 0 || t < 13;
+        double v = 0.0;
+        if (act && j >= 0 && j < len && (full || colat(j) - r == O.off[cls][sl])) {
+          v = sym_scaled(T[off0 + j], r + O.off[cls][sl]);
+          j += dir;
+        }
+        if (!act) continue;
+        if (!sw) {
+          DIA_ST(out + ell_base(r, K) + sl * ELL_B, v);
+        } else if (!fast) {
+          DIA_ST(pv + (sl < 13 ? lowoff + sl * SP_ROWS : mainoff + (sl - 13) * SP_ROWS), v);
+          if (sl == 13) out[ell_base(r, K) + 13 * ELL_B] = v;  // the diagonal (offset 0 is the 14th of the 27 lattice offsets)
+          if (half == 0 && t < 13) {                           // the edge block entry the row owns for this lower slot, if any
+            const int e = sp_edge_of(t, line, pcol);
+            if (e >= 0) pv[edgeoff + e] = v;
+          }
+        }
+      }
+    } else if (cls >= 0) {  // regular 128-row block of class cls: slot s = diagonal s
+      const int D = O.D[cls], Dh = LPR == 2 ? (D + 1) >> 1 : D;
+      if (half == 0) {
+        int j = 0;
+        for (int sl = 0; sl < Dh; ++sl) {
+          double v = 0.0;
+          if (j < len && (full || colat(j) - r == O.off[cls][sl])) {
+            v = sym_scaled(T[off0 + j], r + O.off[cls][sl]);
+            ++j;
+          }
+          DIA_ST(out + ell_base(r, K) + sl * ELL_B, v);
+        }
+      } else {
+        int j = len - 1;
+        for (int sl = D - 1; sl >= Dh; --sl) {
+          double v = 0.0;
+          if (j >= 0 && (full || colat(j) - r == O.off[cls][sl])) {
+            v = sym_scaled(T[off0 + j], r + O.off[cls][sl]);
+            --j;
+          }
+          DIA_ST(out + ell_base(r, K) + sl * ELL_B, v);
+        }
+      }
+    } else {                 // generic block: slot s = s-th entry, columns come from ell_cols
+      for (int sl = half; sl < K; sl += LPR) out[ell_base(r, K) + sl * ELL_B] = sl < len ? sym_scaled(T[off0 + sl], colat(sl)) : 0.0;
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// The swept rows of the patch-major copy: a workgroup of two waves per patch step (plane, strip of SP_L lines, patch column), a wave per pair of lattice lines,
+// lane = line * SP_W + column -- 64 rows whose CSR values are two contiguous runs (one per line: 6.9 KB when all 32 rows have their 27 entries).  Every slot store of
+// a wave is ONE aligned 512-byte piece of the copy and the two halves of each 1 KB slot are written by the same workgroup; the step's edge block (318 entries owned by
+// rows of both waves) is gathered in LDS and written as one contiguous piece.  (k_dia_vals' tiles of 64 consecutive rows drift against the patch columns -- a
+// 513-point line is 16 patches + 1 point -- and wrote two or three unaligned pieces per slot and the edge entries one by one; tools/copy_probe.hip, 512^3, all stores:
+// 14.8 ms in that shape, 10.7 ms in this one; a plain aligned copy of the same bytes 9.4 ms.)  Two memory round trips per full tile -- the four row pointers of the
+// runs (scalar loads), then the 27 values + the 27 factors of the symmetric scaling per lane, all issued before the first wait; tiles with short rows (lattice edge)
+// or missing lines / columns take the general path: per-lane row pointers, masked staging, the short rows' columns decoded into slots (offset = di PL + dj m2 + dk,
+// guaranteed by dia_lattice_class below) and every row expanded to its 27 slots in LDS.
+template <typename RP, bool SYM>
+__global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                    const double* __restrict__ vals, int base, const DiaOffsets* __restrict__ Op, int cls,
+                                                    double* __restrict__ out, SympGeom Gm, double* __restrict__ pv, const double* __restrict__ ssym,
+                                                    unsigned long long* __restrict__ fp) {
+  const DiaOffsets& O = *Op;
+  extern __shared__ double lds[];
+  constexpr int RUN = SP_W * 27;  // entries of a full 32-row run
+  // Symmetry fingerprint (round 6; fp != nullptr): are the values this pass WRITES bitwise symmetric among the swept rows?  Every stored entry (r, c), c != r,
+  // both rows swept, adds  sign(c - r) * m(min, max) * bits(v)  to a 64-bit sum in wrap-around arithmetic, m a 64-bit hash of the unordered pair.  A
+  // symmetric copy cancels pair by pair -- exactly, in any order (integer sums commute: no atomics on doubles, no second pass); a copy with v_rc != v_cr
+  // anywhere leaves a non-zero sum unless the pairs' hashed multipliers conspire (2^-63 for a given matrix).  It replaces the separate check pass over the
+  // copy (k_spmv_symp<1>: 4.6 ms of the 21 ms a 512^3 solve spends outside its iterations); the pass is still there (bit 30 of the "ell" knob) and the
+  // test-suite compares the two verdicts.  Stricter than the pass (which looks at the pairs the sweep mirrors): never the other way round.
+  unsigned long long fsum = 0;
+  const int64_t sw_lo = (int64_t)Gm.p0 * Gm.PL, sw_hi = (int64_t)Gm.p1 * Gm.PL;
+  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (launched with two waves per workgroup)
+  double* T = lds + (size_t)w * (2 * RUN);
+  double* E = lds + 2 * (2 * RUN);  // the step's edge block (SP_EPAD entries; zero between steps: entries of rows outside the lattice and the padding stay 0)
+  const int spNP = Gm.NS * Gm.NPk;
+  const int64_t spT = (int64_t)spNP * (Gm.p1 - Gm.p0);
+  const int h = lane >> 5, c = lane & (SP_W - 1);
+  const int32_t PL = (int32_t)Gm.PL, m2 = Gm.m2;
+  auto uni64 = [](int64_t x) -> int64_t {  // (the same value in every lane: into scalar registers, so that what depends on it stays scalar)
+    const uint32_t xl = __builtin_amdgcn_readfirstlane((uint32_t)(uint64_t)x), xh = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
+    return (int64_t)(((uint64_t)xh << 32) | xl);
+  };
+  for (int i = threadIdx.x; i < SP_EPAD; i += 128) E[i] = 0.0;
+  __syncthreads();
+  for (int64_t step = blockIdx.x; step < spT; step += gridDim.x) {  // (every barrier below is reached by both waves: the trip count is the workgroup's)
+    const int kp = (int)(step % Gm.NPk);
+    const int64_t q = step / Gm.NPk;
+    const int strip = (int)(q % Gm.NS), pl = (int)(q / Gm.NS);
+    const int jj0 = strip * SP_L + 2 * w, kk0 = kp * SP_W;
+    const int ncol = m2 - kk0 < SP_W ? m2 - kk0 : SP_W, nlines = Gm.m1 - jj0 < 2 ? (Gm.m1 - jj0 < 1 ? 0 : 1) : 2;  // (the last strip may end before this wave's lines)
+    const int64_t rb = (int64_t)(Gm.p0 + pl) * Gm.PL + (int64_t)jj0 * m2 + kk0;  // lane 0's row
+    const int64_t rB = nlines == 2 ? rb + m2 : rb;                              // lane 32's row (no second line: the first again, nothing of it is used)
+    int64_t a0 = 0, a1 = 0, b0 = 0, b1 = 0;
+    if (nlines > 0) {
+      a0 = uni64((int64_t)rowptr[rb]) - base, a1 = uni64((int64_t)rowptr[rb + ncol]) - base;
+      b0 = uni64((int64_t)rowptr[rB]) - base, b1 = uni64((int64_t)rowptr[rB + ncol]) - base;
+    }
+    const bool full = ncol == SP_W && nlines == 2 && a1 - a0 == RUN && b1 - b0 == RUN;
+    const bool valid = c < ncol && h < nlines;
+    const int64_t r = rb + (int64_t)h * m2 + c;
+    const int line = 2 * w + h;
+    double* const pm = pv + step * SP_MAIN + line * SP_W + c;
+    double* const plo = pv + spT * SP_MAIN + step * SP_LOW + line * SP_W + c;
+    double* const pe = pv + step * SP_MAIN + 14 * SP_ROWS;
+    const double* Tr = T + lane * 27;
+    double sc[27];
+    double srow = 1.0;
+    uint32_t present = 0x7FFFFFFu;
+    if (full) {
+      double tv[27];
+      const double* vA = vals + a0 + lane;
+      const double* vB = vals + b0 + lane - RUN;
+      const double* v13 = h ? vB : vA;  // entries 832 .. 895 of the tile: the first run ends at 864
+#pragma unroll
+      for (int u = 0; u < 27; ++u) tv[u] = __builtin_nontemporal_load((u < 13 ? vA : u == 13 ? v13 : vB) + 64 * u);
+      if constexpr (SYM) {
+        srow = ssym[r];
+#pragma unroll
+        for (int u = 0; u < 27; ++u) sc[u] = ssym[r + O.off[cls][u]];
+      }
+#pragma unroll
+      for (int u = 0; u < 27; ++u) T[lane + 64 * u] = tv[u];
+      __builtin_amdgcn_wave_barrier();
+    } else {
+      int64_t lo = 0;
+      int len = 0;
+      if (valid) {
+        lo = (int64_t)rowptr[r] - base;
+        len = (int)((int64_t)rowptr[r + 1] - base - lo);
+      }
+      const int cntA = (int)(a1 - a0), cntB = nlines == 2 ? (int)(b1 - b0) : 0;  // <= RUN each (regular blocks: at most 27 entries per row)
+      {
+        double ta[14], tb[14];
+#pragma unroll
+        for (int u = 0; u < 14; ++u) {
+          const int i = lane + 64 * u;
+          ta[u] = i < cntA ? __builtin_nontemporal_load(vals + a0 + i) : 0.0;
+          tb[u] = i < cntB ? __builtin_nontemporal_load(vals + b0 + i) : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < 14; ++u) {
+          const int i = lane + 64 * u;
+          if (i < cntA) T[i] = ta[u];
+          if (i < cntB) T[RUN + i] = tb[u];
+        }
+      }
+      // the columns of the short rows (their entries are decoded into slots below; a row of 27 entries has entry s in slot s)
+      int32_t cj[27];
+      const bool shortrow = valid && len < 27;
+#pragma unroll
+      for (int j = 0; j < 27; ++j) cj[j] = (shortrow && j < len) ? col[lo + j] - base : 0;
+      __builtin_amdgcn_wave_barrier();
+      const int off0 = h * RUN + (int)(lo - (h ? b0 : a0));
+      double ev[27];
+#pragma unroll
+      for (int j = 0; j < 27; ++j) ev[j] = j < len ? T[off0 + j] : 0.0;
+      __builtin_amdgcn_wave_barrier();  // every lane holds its entries: the staging area may now be overwritten by the expanded rows
+      present = 0;
+      if (shortrow) {
+#pragma unroll
+        for (int sl = 0; sl < 27; ++sl) T[lane * 27 + sl] = 0.0;
+      }
+#pragma unroll
+      for (int j = 0; j < 27; ++j) {
+        if (j < len) {
+          int sl = j;
+          if (shortrow) {
+            const int32_t d = cj[j] - (int32_t)r;
+            const int di = (2 * d > PL) - (2 * d < -PL);
+            const int32_t d1 = d - di * PL;
+            const int dj = (2 * d1 > m2) - (2 * d1 < -m2);
+            sl = 9 * (di + 1) + 3 * (dj + 1) + (d1 - dj * m2 + 1);
+          }
+          T[lane * 27 + sl] = ev[j];
+          present |= 1u << sl;
+        }
+      }
+      __builtin_amdgcn_wave_barrier();
+      if constexpr (SYM) {
+        srow = valid ? ssym[r] : 1.0;
+#pragma unroll
+        for (int u = 0; u < 27; ++u) sc[u] = valid ? ssym[r + O.off[cls][u]] : 1.0;
+      }
+    }
+    if (valid) {
+#pragma unroll
+      for (int sl = 0; sl < 27; ++sl) {
+        double v = 0.0;
+        if (present >> sl & 1u) {
+          v = Tr[sl];
+          if constexpr (SYM) v = v * (srow * sc[sl]);  // (the product of the two factors first: a mirrored pair is multiplied by the same number)
+          if (fp && sl != 13) {
+            const int64_t cc = r + O.off[cls][sl];
+            if (cc >= sw_lo && cc < sw_hi) {
+              const uint64_t lo_ = (uint64_t)(sl < 13 ? cc : r), hi_ = (uint64_t)(sl < 13 ? r : cc);
+              uint64_t z = lo_ * 0x9E3779B97F4A7C15ull + hi_ * 0xD1B54A32D192ED03ull + 0x2545F4914F6CDD1Dull;
+              z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+              z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+              z = (z ^ (z >> 31)) | 1ull;
+              const unsigned long long t = z * (unsigned long long)__double_as_longlong(v);
+              fsum += sl < 13 ? (0ull - t) : t;
+            }
+          }
+        }
+        if (sl < 13) {
+          DIA_ST(plo + sl * SP_ROWS, v);
+          const int e = sp_edge_of(sl, line, c);
+          if (e >= 0) E[e] = v;
+        } else {
+          DIA_ST(pm + (sl - 13) * SP_ROWS, v);
+          if (sl == 13) DIA_ST(out + ell_base(r, K) + 13 * ELL_B, v);  // the diagonal also to the slot-major copy (k_ell_diag reads it there)
+        }
+      }
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < SP_EPAD; i += 128) {
+      DIA_ST(pe + i, E[i]);
+      E[i] = 0.0;
+    }
+    __syncthreads();
+  }
+  if (fp) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) fsum += __shfl_down(fsum, o, MFEM_WAVE);
+    if (lane == 0 && fsum) atomicAdd(fp, fsum);
+  }
+}
+
+// lane <-> RPT (2 or 4) neighbouring rows; a wave covers one aligned block of 64 RPT rows; U diagonals per batch
+template <int RPT, int U, bool TRIPLES = false>
+__global__ __launch_bounds__(1024) void k_spmv_dia(int64_t n, int64_t npad, int K, const DiaOffsets* __restrict__ Op,
+                                                           const int32_t* __restrict__ flags, const int32_t* __restrict__ cols,
+                                                           const double* __restrict__ vals, const double* __restrict__ x,
+                                                           double* __restrict__ y, double alpha, double beta,
+                                                           const double* __restrict__ dotw, double* __restrict__ partials,
+                                                           const int32_t* __restrict__ done_flag, int xcd, SpmvPart part) {
+  __shared__ double red[16];
+  if (done_flag && done_flag[0]) return;
+  const DiaOffsets& O = *Op;
+  double dot_acc = 0.0;
+  // xcd > 0: workgroups with equal blockIdx % 8 share an XCD (round-robin dispatch); XCD x walks its own contiguous eighth of
+  // the rows, so the x window an L2 has to hold is an eighth of the vector instead of all of it
+  const int64_t rows_per_wg = (int64_t)blockDim.x * RPT;
+  const int64_t nchunks = (n + rows_per_wg - 1) / rows_per_wg;
+  int64_t chunk = blockIdx.x, chunk_end = nchunks, chunk_step = gridDim.x;
+  if (xcd & 1) {
+    const int64_t per = (nchunks + 7) / 8;
+    chunk = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
+    chunk_end = ((blockIdx.x & 7) + 1) * per < nchunks ? ((blockIdx.x & 7) + 1) * per : nchunks;
+    chunk_step = gridDim.x >> 3;
+  }
+  for (; chunk < chunk_end; chunk += chunk_step) {
+    const int64_t r = chunk * rows_per_wg + (int64_t)threadIdx.x * RPT;
+    if (r >= n) continue;
+    if (spmv_part_skip(part, chunk * rows_per_wg, (chunk + 1) * rows_per_wg)) continue;  // workgroup-uniform
+    dia_rows<RPT, U, TRIPLES>(r, n, npad, K, O, flags, cols, vals, x, y, alpha, beta, dotw, xcd, dot_acc);
+  }
+  if (partials) {
+    const double b = block_reduce_sum(dot_acc, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = b;
+  }
+}
+
+// the rows outside [skip_lo, skip_hi) through the plain per-row code on the slot-major copy (chunks that lie inside the range are not
+// visited, rows of straddling chunks are masked)
+template <bool TRIPLES>
+__global__ __launch_bounds__(MFEM_BLOCK) void k_spmv_dia_outside(int64_t n, int64_t npad, int K, const DiaOffsets* __restrict__ Op,
+                                                                   const int32_t* __restrict__ flags, const int32_t* __restrict__ cols,
+                                                                   const double* __restrict__ vals, const double* __restrict__ x,
+                                                                   double* __restrict__ y, double alpha, double beta,
+                                                                   const double* __restrict__ dotw, double* __restrict__ partials,
+                                                                   const int32_t* __restrict__ done_flag, int64_t skip_lo, int64_t skip_hi) {
+  __shared__ double red[16];
+  if (done_flag && done_flag[0]) return;
+  double dot_acc = 0.0;
+  const int64_t R = 2 * MFEM_BLOCK, nchunks = (n + R - 1) / R;
+  int64_t cA = (skip_lo + R - 1) / R, cB = skip_hi / R;
+  if (cB < cA) cB = cA;
+  for (int64_t q = blockIdx.x; q < cA + (nchunks - cB); q += gridDim.x) {
+    const int64_t ch = q < cA ? q : cB + (q - cA);
+    const int64_t r = ch * R + 2 * (int64_t)threadIdx.x;
+    if (r < n) dia_rows<2, 3, TRIPLES>(r, n, npad, K, *Op, flags, cols, vals, x, y, alpha, beta, dotw, 0, dot_acc, skip_lo, skip_hi);
+  }
+  if (partials) {
+    const double b = block_reduce_sum(dot_acc, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = b;
+  }
+}
+
+// lattice lines of odd length: the lane pair at the line's end holds the last point and a cell outside the lattice, which no row writes
+// and the sweep reads as a structurally absent entry -- an explicit zero in all 27 slots of every step of the last patch column
+__global__ __launch_bounds__(MFEM_BLOCK) void k_symp_zero_odd(SympGeom Gm, double* __restrict__ pv) {
+  const int NP = Gm.NS * Gm.NPk, nplanes = Gm.p1 - Gm.p0;
+  const int64_t T = (int64_t)NP * nplanes, cells = (int64_t)nplanes * Gm.NS * SP_L * 27;
+  const int col = Gm.m2 - (Gm.NPk - 1) * SP_W;  // first column past the line in the last patch column (odd, < SP_W)
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < cells; t += (int64_t)gridDim.x * blockDim.x) {
+    const int s = (int)(t % 27), line = (int)((t / 27) % SP_L);
+    const int64_t q = t / (27 * SP_L);
+    const int strip = (int)(q % Gm.NS), pl = (int)(q / Gm.NS);
+    const int64_t step = (int64_t)pl * NP + (int64_t)strip * Gm.NPk + (Gm.NPk - 1);
+    const int idx = line * SP_W + col;
+    if (s < 13) pv[T * SP_MAIN + step * SP_LOW + s * SP_ROWS + idx] = 0.0;
+    else pv[step * SP_MAIN + (s - 13) * SP_ROWS + idx] = 0.0;
+  }
+}
+
+// Candidate diagonal lists: the offsets of one full-length row from each of 8 windows along the matrix (a field-major multi-field matrix has
+// one list per field)
+static int dia_sample_lists(mfem_context_s* ctx, const mfem_csr_s* A, DiaOffsets& O) {
+  const int K = A->ell_K;
+  memset(&O, 0, sizeof(O));
+  for (int wdw = 0; wdw < 8 && O.ncls < DIA_MAXC; ++wdw) {
+    const int64_t centre = A->n * (2 * wdw + 1) / 16;
+    const int64_t w0 = centre > 1024 ? centre - 1024 : 0;
+    const int64_t wn = (A->n - w0) < 2048 ? (A->n - w0) : 2048;  // rows in the window
+    if (wn <= 0) continue;
+    mfem_host_alloc_probe();
+    const size_t rb = A->rowptr_bits / 8;  // the window's row pointers, in the pattern's width
+    std::vector<char> raw((size_t)(wn + 1) * rb);
+    MFEM_CHECK_HIP(hipMemcpyAsync(raw.data(), (const char*)A->rowptr + w0 * rb, raw.size(), hipMemcpyDeviceToHost, ctx->stream));
+    MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    auto win = [&](int64_t i) -> int64_t { return rb == 8 ? ((const int64_t*)raw.data())[i] : ((const int32_t*)raw.data())[i]; };
+    int64_t rm = -1;
+    for (int64_t i = 0; i < wn && rm < 0; ++i)
+      if (win(i + 1) - win(i) == K) rm = i;
+    if (rm < 0) continue;
+    int32_t cbuf[DIA_MAXD];
+    MFEM_CHECK_HIP(hipMemcpyAsync(cbuf, A->colidx + (win(rm) - A->index_base), sizeof(int32_t) * K, hipMemcpyDeviceToHost, ctx->stream));
+    MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    int32_t cand[DIA_MAXD];
+    for (int i = 0; i < K; ++i) cand[i] = (int32_t)((int64_t)cbuf[i] - A->index_base - (w0 + rm));
+    bool seen = false;
+    for (int c = 0; c < O.ncls && !seen; ++c) seen = memcmp(O.off[c], cand, sizeof(int32_t) * K) == 0;
+    if (!seen) {
+      memcpy(O.off[O.ncls], cand, sizeof(int32_t) * K);
+      O.D[O.ncls] = K;
+      ++O.ncls;
+    }
+  }
+  return MFEM_OK;
+}
+
+// Which list, if any, each 128-row block obeys: leaves the lists (A->dia_dev) and the flags (A->dia_flags) on the device, *nreg = regular blocks
+static int dia_flag_blocks(mfem_context_s* ctx, mfem_csr_s* A, const DiaOffsets& O, int32_t* nreg) {
+  const int64_t nblk = A->ell_npad / ELL_B;
+  const int64_t nx = A->n + (ctx->comm ? 2 * ctx->halo_plane_len * ctx->halo_fields : 0);  // length of the local x
+  MFEM_CHECK_HIP(hipMalloc(&A->dia_flags, sizeof(int32_t) * (size_t)nblk));
+  MFEM_CHECK_HIP(hipMalloc(&A->dia_dev, sizeof(DiaOffsets)));
+  MFEM_CHECK_HIP(hipMemcpyAsync(A->dia_dev, &O, sizeof(DiaOffsets), hipMemcpyHostToDevice, ctx->stream));
+  MFEM_CHECK_HIP(hipMemsetAsync(A->dia_flags, 0, sizeof(int32_t) * (size_t)nblk, ctx->stream));
+  int32_t* d_cnt = ctx->d_flags + 9;
+  MFEM_CHECK_HIP(hipMemsetAsync(d_cnt, 0, sizeof(int32_t), ctx->stream));
+  const int g2 = (int)(nblk < (int64_t)ctx->num_cus * 64 ? nblk : (int64_t)ctx->num_cus * 64);
+  mfem_by_rowptr(A, [&](auto t) {
+    hipLaunchKernelGGL(k_dia_flags<decltype(t)>, dim3(g2), dim3(128), 0, ctx->stream, A->n, nx, (const decltype(t)*)A->rowptr, A->colidx, A->index_base,
+                       (const DiaOffsets*)A->dia_dev, A->dia_flags, d_cnt);
+  });
+  MFEM_CHECK_LAUNCH();
+  MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 9, d_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));  // also orders the H2D copy of the caller's O
+  *nreg = ctx->h_flags[9];
+  return MFEM_OK;
+}
+
+// do the diagonals of every list come in runs of three consecutive offsets (o, o + 1, o + 2: the fastest lattice direction)?
+static bool dia_has_triples(const DiaOffsets& O, int K) {
+  if (K % 3 != 0) return false;
+  for (int c = 0; c < O.ncls; ++c)
+    for (int i = 0; i + 2 < K; i += 3)
+      if (O.off[c][i + 1] != O.off[c][i] + 1 || O.off[c][i + 2] != O.off[c][i] + 2) return false;
+  return true;
+}
+
+// the list with the form of the 27-point lattice stencil, offsets di PL + dj m2 + dk (a slab has further lists for the rows next to its ghost
+// planes); -1: none
+static int dia_lattice_class(const DiaOffsets& O, int K, int64_t* m2_out, int64_t* PL_out) {
+  for (int c = 0; c < O.ncls && K == 27; ++c) {
+    if (O.D[c] != 27 || O.off[c][13] != 0 || O.off[c][14] != 1) continue;
+    const int64_t m2 = *m2_out = O.off[c][16], PL = *PL_out = O.off[c][22];
+    bool lattice = m2 > 2 && PL > 2 * m2;
+    for (int q = 0; q < 27 && lattice; ++q)
+      if (O.off[c][q] != (q / 9 - 1) * PL + ((q / 3) % 3 - 1) * m2 + (q % 3 - 1)) lattice = false;
+    if (lattice) return c;
+  }
+  return -1;
+}
+
+// blocks [*lo, *hi): the longest run of whole blocks that are regular for list `cls` (both sweeps work on rows inside it)
+static void dia_longest_run(const std::vector<int32_t>& hf, int cls, int64_t n, int64_t* best_lo, int64_t* best_hi) {
+  const int64_t nblk = (int64_t)hf.size();
+  int64_t lo = -1;
+  *best_lo = *best_hi = 0;
+  for (int64_t b = 0; b <= nblk; ++b) {
+    const bool reg = b < nblk && hf[(size_t)b] == cls + 1 && (b + 1) * ELL_B <= n;
+    if (reg && lo < 0) lo = b;
+    if (!reg && lo >= 0) {
+      if (b - lo > *best_hi - *best_lo) { *best_lo = lo; *best_hi = b; }
+      lo = -1;
+    }
+  }
+}
+
+// Diagonal structure?  The layout is taken when at least half of the blocks are regular (the others run the explicit-column loop, as in mode 1).
+int mfem_dia_plan(mfem_context_s* ctx, mfem_csr_s* A) {
+  A->dia_state = -1;
+  const int K = A->ell_K;
+  if (K > DIA_MAXD) return MFEM_OK;
+  DiaOffsets O;
+  int rc = dia_sample_lists(ctx, A, O);
+  if (rc || O.ncls == 0) return rc;
+  int32_t nreg = 0;
+  rc = dia_flag_blocks(ctx, A, O, &nreg);
+  if (rc) return rc;
+  const int64_t nblk = A->ell_npad / ELL_B;
+  if ((double)nreg < 0.5 * (double)nblk) {
+    hipFree(A->dia_flags);
+    hipFree(A->dia_dev);
+    A->dia_flags = nullptr;
+    A->dia_dev = nullptr;
+    return MFEM_OK;
+  }
+  A->dia_state = 1;
+  A->dia_classes = O.ncls;
+  A->dia_regular_blocks = nreg;
+  A->dia_triples = dia_has_triples(O, K);
+  // 27-point lattice stencil: candidate for the symmetric sweeps
+  A->sym_state = -1;
+  int64_t m2 = 0, PL = 0;
+  const int lc = dia_lattice_class(O, K, &m2, &PL);
+  if (lc < 0) return MFEM_OK;
+  std::vector<int32_t> hf((size_t)nblk);
+  MFEM_CHECK_HIP(hipMemcpy(hf.data(), A->dia_flags, sizeof(int32_t) * (size_t)nblk, hipMemcpyDeviceToHost));
+  int64_t run_lo = 0, run_hi = 0;
+  dia_longest_run(hf, lc, A->n, &run_lo, &run_hi);
+  mfem_sym_plan(A, O.off[lc], lc, m2, PL, run_lo, run_hi);
+  return MFEM_OK;
+}
+
+// The copies of a bind: the slot-major copy of `vals` into buf; with pvals the rows of the swept planes G go straight to the patch-major copy there
+// instead -- by k_symp_fill (patch-aligned tiles) where its conditions hold, after k_dia_vals has done the other rows, else by k_dia_vals.
+// *fp_made: the fill left the symmetry fingerprint of the swept rows, asked for with want_fp, in d_flags[16..17].
+int mfem_dia_copy(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, const double* ssym, const SympGeom& G,
+                  double* pvals, bool want_fp, bool* fp_made) {
+  const DiaOffsets* O = (const DiaOffsets*)A->dia_dev;
+  if (pvals && (G.m2 & 1)) {  // lattice lines of odd length leave cells of the patch-major copy that no row writes
+    const int64_t cells = (int64_t)(G.p1 - G.p0) * G.NS * SP_L * 27;
+    hipLaunchKernelGGL(k_symp_zero_odd, dim3(mfem_grid_for(cells, MFEM_BLOCK, ctx->num_cus * 8)), dim3(MFEM_BLOCK), 0, ctx->stream, G, pvals);
+    MFEM_CHECK_LAUNCH();
+  }
+  // a lane per row while at least two waves of 64-row tiles fit 64 KB of staging (K <= 42: the 27-diagonal lattice); two lanes per row,
+  // 32-row tiles, beyond (the 81 diagonals of three fields)
+  const size_t eb = dsc ? 12 : 8;  // 8 B value (+ 4 B column for the scaling pass) per staged entry (<= rt K per tile)
+  const int lpr = eb * 64 * (size_t)A->ell_K * 2 > 64 * 1024 ? 2 : 1;
+  const int rt = 64 / lpr;
+  int wv = 2;  // two-wave workgroups: what fits a CU is then decided in steps of two waves (27 diagonals: 27.6 KB per workgroup, 5 per CU)
+  while (wv > 1 && eb * rt * (size_t)A->ell_K * wv > 64 * 1024) wv >>= 1;
+  const size_t ldsb = eb * rt * (size_t)A->ell_K * wv;
+  const int64_t nt = A->ell_npad / rt;
+  int g = (int)((nt + wv - 1) / wv);
+  if (g > ctx->num_cus * 16) g = ctx->num_cus * 16;
+  // k_symp_fill: a patch-major copy to fill, no column scaling pass, 32-bit row arithmetic, lattice lines and planes long enough for its column
+  // decoding (bit 29 of the "ell" knob turns it off)
+  const bool fast = lpr == 1 && !dsc && pvals && A->n < ((int64_t)1 << 31) && G.PL < ((int64_t)1 << 30) && G.m1 >= 3 && G.m2 >= 3 && g_ell.dia_fast;
+  // the software-pipelined staging: a lane per row, rows of at most 28 entries, no scaling pass (bit 28 turns it off)
+  const bool pipe = lpr == 1 && !dsc && A->ell_K <= 28 && g_ell.dia_pipe && !fast;
+  const int64_t ft = (int64_t)(G.p1 - G.p0) * G.NS * G.NPk;  // the fill: patch steps, one workgroup of two waves each
+  int gf = (int)(ft < (int64_t)ctx->num_cus * 20 ? ft : (int64_t)ctx->num_cus * 20);  // (5 workgroups are resident per CU: four rounds)
+  if (gf < 1) gf = 1;
+  unsigned long long* fpr = fast && want_fp ? (unsigned long long*)(ctx->d_flags + 16) : nullptr;
+  *fp_made = fpr != nullptr;
+  return mfem_by_rowptr(A, [&](auto t) -> int {
+    using RP = decltype(t);
+    auto kv = ssym ? k_dia_vals<RP, 1, true, false> : k_dia_vals<RP, 1, false, false>;
+    if (lpr == 2) kv = ssym ? k_dia_vals<RP, 2, true, false> : k_dia_vals<RP, 2, false, false>;
+    else if (pipe) kv = ssym ? k_dia_vals<RP, 1, true, true> : k_dia_vals<RP, 1, false, true>;
+    hipLaunchKernelGGL(kv, dim3(g), dim3(64 * wv), ldsb, ctx->stream, A->n, A->ell_npad, A->ell_K, (const RP*)A->rowptr, A->colidx, vals, A->index_base,
+                       O, A->dia_flags, buf, G, pvals, dsc, ssym, fast ? 1 : 0);
+    MFEM_CHECK_LAUNCH();
+    if (!fast) return MFEM_OK;
+    if (fpr) MFEM_CHECK_HIP(hipMemsetAsync(fpr, 0, sizeof(unsigned long long), ctx->stream));
+    const auto kf = ssym ? k_symp_fill<RP, true> : k_symp_fill<RP, false>;
+    hipLaunchKernelGGL(kf, dim3(gf), dim3(128), sizeof(double) * (2 * (2 * SP_W * 27) + SP_EPAD), ctx->stream, A->n, A->ell_K, (const RP*)A->rowptr,
+                       A->colidx, vals, A->index_base, O, A->sym_cls, buf, G, pvals, ssym, fpr);
+    MFEM_CHECK_LAUNCH();
+    return MFEM_OK;
+  });
+}
+
+// all rows by the plain per-row kernel, with the shared x loads of three consecutive diagonals (`triples`) or without; `cap` workgroups at most
+int mfem_dia_launch(mfem_context_s* ctx, mfem_csr_s* A, bool triples, int cap, const SpmvArgs& a) {
+  const int gd = mfem_grid_for((A->n + 1) / 2, MFEM_BLOCK, cap);
+  const auto k = triples ? k_spmv_dia<2, 3, true> : k_spmv_dia<2, 3, false>;
+  hipLaunchKernelGGL(k, dim3(gd), dim3(MFEM_BLOCK), 0, ctx->stream, A->n, A->ell_npad, A->ell_K, (const DiaOffsets*)A->dia_dev, A->dia_flags,
+                     A->ell_cols, A->ell_vals, a.x, a.y, a.alpha, a.beta, a.dotw, a.partials, a.done_flag, (int)g_ell.xcd, a.part);
+  MFEM_CHECK_LAUNCH();
+  if (a.n_partials && a.partials) *a.n_partials = gd;
+  return MFEM_OK;
+}
+// the rows outside [lo, hi) by the per-row code (the patch sweep's boundary part); *ngrid = its workgroups = the partial sums it wrote to `partials`
+int mfem_dia_launch_outside(mfem_context_s* ctx, mfem_csr_s* A, const SpmvArgs& a, double* partials, int64_t lo, int64_t hi, int* ngrid) {
+  const int64_t outside = (lo + 511) / 512 + (A->n - hi + 511) / 512 + 2;
+  *ngrid = (int)(outside < 1 ? 1 : outside < 1024 ? outside : 1024);
+  const auto k = A->dia_triples ? k_spmv_dia_outside<true> : k_spmv_dia_outside<false>;
+  hipLaunchKernelGGL(k, dim3(*ngrid), dim3(MFEM_BLOCK), 0, ctx->stream, A->n, A->ell_npad, A->ell_K, (const DiaOffsets*)A->dia_dev, A->dia_flags,
+                     A->ell_cols, A->ell_vals, a.x, a.y, a.alpha, a.beta, a.dotw, partials, a.done_flag, lo, hi);
+  MFEM_CHECK_LAUNCH();
+  return MFEM_OK;
+}

@@ -1,0 +1,214 @@
+// What the files of the slot-major solver layout share.  spmv_ell.hip: the entry points (layouts.h, common.h) and mode 1, explicit columns;
+// spmv_dia.hip: mode 2, the diagonal-slotted copy, its inspection and its per-row kernel; spmv_sym.hip: the two symmetric sweeps on that
+// copy.  Here: the layout's addressing, the diagonal lists, the per-row product code, the decoded "ell" knob word, the one
+// decision which kernel serves a diagonal-slotted copy, and the host functions one family offers another.  The library is one code object per
+// .hip file: a kernel is defined in one file and launched from that file only; other files call a host function.
+#pragma once
+#include <vector>
+
+#include "layouts.h"
+#include "spmv_symp.h"
+
+// Blocked slot-major layout ("sliced ELL"): rows are grouped in blocks of ELL_B = 128 (the rows of one wave at two rows per
+// lane); block b stores its K slots one after the other, element (row r, slot s) at  b * K * 128 + s * 128 + (r & 127).
+// A wave therefore reads ONE contiguous K-kilobyte chunk per block and the kernel as a whole walks memory front to back
+// like a copy, instead of K streams a full vector length apart.
+#define ELL_B 128
+__host__ __device__ __forceinline__ int64_t ell_base(int64_t r, int K) { return (r >> 7) * ((int64_t)K * ELL_B) + (r & (ELL_B - 1)); }
+
+typedef double e_d2 __attribute__((ext_vector_type(2)));
+typedef int e_i2 __attribute__((ext_vector_type(2)));
+typedef double u_d2 __attribute__((ext_vector_type(2), aligned(8)));
+
+// Several diagonal lists ("classes") may coexist: a 3-field matrix in field-major numbering has one list per row field
+// ((g - f) * n_nodes + stencil offset).  Each regular block belongs to one class.
+#define DIA_MAXD 96
+#define DIA_MAXC 4
+struct DiaOffsets {
+  int ncls;
+  int D[DIA_MAXC];
+  int32_t off[DIA_MAXC][DIA_MAXD];
+};
+
+// geometry of the wave-private patch sweep (k_spmv_symp, spmv_sym.hip)
+struct SympGeom {
+  int64_t PL, nx;
+  int m1, m2, p0, p1, NS, NPk;
+  int nseg;  // runs per patch: a run = one patch swept through nplanes / nseg consecutive planes
+};
+// the rows outside the swept planes, taken by the sweep's waves after their runs (unsplit SpMV): per-row code on the slot-major copy
+struct SympTail {
+  int on, K;
+  int64_t n, npad, lo, hi;  // rows [lo, hi) are the sweep's
+  const DiaOffsets* Op;
+  const int32_t* flags;
+  const int32_t* cols;
+  const double* ell;
+};
+
+// the copies are written as full coalesced streams and not read again by this kernel: nontemporal stores (per-solve work of C2 3.65 -> 3.3 ms)
+#if defined(DV_ABL) && DV_ABL == 1   // timing-only ablation builds (tools/ab_libs.sh; never in the product library): 1 = no stores (one per lane and tile
+#define DIA_ST(p, v) do { if ((v) == 1.2345e300) __builtin_nontemporal_store((v), (p)); } while (0)  // keeps the loads alive), 3 = plain instead of nontemporal stores
+#elif defined(DV_ABL) && DV_ABL == 3
+#define DIA_ST(p, v) (*(p) = (v))
+#else
+#define DIA_ST(p, v) __builtin_nontemporal_store((v), (p))
+#endif
+#define SYM_LD(p) __builtin_nontemporal_load(p)  // plain loads measured slower: 0.954 vs 0.928 ms per CG iteration at 256^3
+
+// The RPT rows r .. r + RPT - 1 of one lane (r a multiple of RPT; a wave covers aligned 128-row blocks): regular blocks by
+// diagonal, the others through their explicit columns.  Shared by the plain kernel and the symmetric sweep kernel (which
+// sends the chunks outside its regular range here).
+template <int RPT, int U, bool TRIPLES>
+__device__ __forceinline__ void dia_rows(int64_t r, int64_t n, int64_t npad, int K, const DiaOffsets& O,
+                                         const int32_t* __restrict__ flags, const int32_t* __restrict__ cols,
+                                         const double* __restrict__ vals, const double* __restrict__ x, double* __restrict__ y,
+                                         double alpha, double beta, const double* __restrict__ dotw, int xcd, double& dot_acc,
+                                         int64_t skip_lo = 0, int64_t skip_hi = 0) {  // rows in [skip_lo, skip_hi) belong to another launch
+  constexpr int H = RPT / 2;  // 16-byte pairs per lane
+  const double* v = vals + ell_base(r, K);
+  e_d2 acc[H];
+  double xself0 = 0.0, xself1 = 0.0;  // x[r], x[r + 1] when the kernel has loaded them anyway (fused w.y with w == x, as in CG)
+  bool have_self = false;
+#pragma unroll
+  for (int h = 0; h < H; ++h) acc[h] = (e_d2){0.0, 0.0};
+  // the wave's rows [b0, b0 + 64 RPT) are RPT / 2 aligned 128-row blocks: regular only if all of them are (wave-uniform)
+  const int64_t blk = r / (64 * RPT) * (RPT / 2);
+  const int cls = __builtin_amdgcn_readfirstlane(flags[blk]) - 1;  // wave-uniform: keeps the offset reads scalar
+  bool interior = cls >= 0;
+  if (RPT == 4) interior = interior && ((blk + 1) * 128 < npad) && flags[blk + 1] == cls + 1;
+  const int32_t* off = O.off[cls < 0 ? 0 : cls];
+  const int D = O.D[cls < 0 ? 0 : cls];
+  if (interior && TRIPLES && RPT == 2) {
+    // the diagonals come in runs of three consecutive offsets (o - 1, o, o + 1: the fastest lattice direction): the two
+    // rows of the lane need x[r + o - 1 .. r + o + 2] for the whole run -- two 16-byte loads instead of three
+    for (int s = 0; s < D; s += 3) {
+      const e_d2 va = __builtin_nontemporal_load(reinterpret_cast<const e_d2*>(v + s * ELL_B));
+      const e_d2 vb = __builtin_nontemporal_load(reinterpret_cast<const e_d2*>(v + (s + 1) * ELL_B));
+      const e_d2 vc = __builtin_nontemporal_load(reinterpret_cast<const e_d2*>(v + (s + 2) * ELL_B));
+      const u_d2* xp = reinterpret_cast<const u_d2*>(x + r + off[s]);
+      const u_d2 xa = xp[0], xb = xp[1];
+      acc[0].x += va.x != 0.0 ? va.x * xa.x : 0.0;
+      acc[0].y += va.y != 0.0 ? va.y * xa.y : 0.0;
+      acc[0].x += vb.x != 0.0 ? vb.x * xa.y : 0.0;
+      acc[0].y += vb.y != 0.0 ? vb.y * xb.x : 0.0;
+      acc[0].x += vc.x != 0.0 ? vc.x * xb.x : 0.0;
+      acc[0].y += vc.y != 0.0 ? vc.y * xb.y : 0.0;
+      if (off[s + 1] == 0) {  // the main diagonal's run: x[r], x[r + 1] are the lane's own entries (wave-uniform test)
+        xself0 = xa.y;
+        xself1 = xb.x;
+        have_self = true;
+      }
+    }
+  } else if (interior) {
+    int s = 0;
+    for (; s + U <= D; s += U) {
+      e_d2 vv[U][H];
+      u_d2 xx[U][H];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+          vv[u][h] = __builtin_nontemporal_load(reinterpret_cast<const e_d2*>(v + (s + u) * ELL_B) + h);
+          xx[u][h] = *(reinterpret_cast<const u_d2*>(x + r + off[s + u]) + h);
+        }
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int h = 0; h < H; ++h) {
+          // a zero slot stands for "no entry": it must not pick up a non-finite x from a position the CSR row never reads
+          acc[h].x += vv[u][h].x != 0.0 ? vv[u][h].x * xx[u][h].x : 0.0;
+          acc[h].y += vv[u][h].y != 0.0 ? vv[u][h].y * xx[u][h].y : 0.0;
+        }
+    }
+    for (; s < D; ++s)
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        const e_d2 vv = __builtin_nontemporal_load(reinterpret_cast<const e_d2*>(v + s * ELL_B) + h);
+        const u_d2 xx = *(reinterpret_cast<const u_d2*>(x + r + off[s]) + h);
+        acc[h].x += vv.x != 0.0 ? vv.x * xx.x : 0.0;
+        acc[h].y += vv.y != 0.0 ? vv.y * xx.y : 0.0;
+      }
+  } else {  // generic block (boundary rows, ghost columns): explicit columns, compact slots
+    const int32_t* c = cols + ell_base(r, K);
+    for (int s = 0; s < K; ++s)
+#pragma unroll
+      for (int h = 0; h < H; ++h) {
+        if (r + 2 * h >= npad) continue;
+        const e_d2 vv = __builtin_nontemporal_load(reinterpret_cast<const e_d2*>(v + s * ELL_B) + h);
+        const e_i2 cc = __builtin_nontemporal_load(reinterpret_cast<const e_i2*>(c + s * ELL_B) + h);
+        acc[h].x += vv.x * x[cc.x];
+        acc[h].y += vv.y * x[cc.y];
+      }
+  }
+#pragma unroll
+  for (int h = 0; h < H; ++h) {
+    const int64_t rr = r + 2 * h;
+    if (rr >= n) break;
+    double y0 = alpha * acc[h].x, y1 = alpha * acc[h].y;
+    const bool one = rr < skip_lo || rr >= skip_hi;
+    const bool two = rr + 1 < n && (rr + 1 < skip_lo || rr + 1 >= skip_hi);
+    if (beta != 0.0) {
+      if (one) y0 += beta * y[rr];
+      if (two) y1 += beta * y[rr + 1];
+    }
+    if (one) y[rr] = y0;
+    if (two) y[rr + 1] = y1;
+    if (dotw) {
+      if (RPT == 2 && have_self && dotw == x) {  // p.Ap of CG: p[r], p[r + 1] are already in registers
+        if (one) dot_acc += y0 * xself0;
+        if (two) dot_acc += y1 * xself1;
+      } else {
+        if (one) dot_acc += y0 * dotw[rr];
+        if (two) dot_acc += y1 * dotw[rr + 1];
+      }
+    }
+  }
+}
+
+// The "ell" knob word (mfem_debug_set_ell, spmv_ell.hip), decoded once by its setter.  Read when a layout is planned and bound -- a product
+// runs the kernel its bind recorded -- and, for the launch geometry alone (grid_mult, xcd, symp_tail), when a product is launched.
+struct EllKnobs {
+  std::atomic<int> enable{1};            // bit 0: modes 1 and 2 on
+  std::atomic<int> dia{1};               // bit 1 clears it: explicit columns even when the matrix is diagonal-structured
+  std::atomic<int> grid_mult{6};         // bits 8-15 (0 keeps the value): persistent workgroups per CU of the per-row kernels (profiles/r01_spmv_sweep.txt: 6 or 8)
+  std::atomic<int> shared_x{1};          // bits 16-19 = 8 clears it: the plain per-row kernel without the shared x loads of three consecutive diagonals, no sweep
+  std::atomic<int> xcd{0};               // bit 20: each XCD walks a contiguous eighth of the rows (k_spmv_dia; needs a grid that is a multiple of 8)
+  std::atomic<int> sym{1};               // bit 22 clears it: no symmetric sweep kernel
+  std::atomic<int> symp{1};              // bit 23 clears it: the workgroup-tile sweep (k_spmv_sym27) instead of the wave-private patch sweep (k_spmv_symp)
+  std::atomic<int> symp_tail{1};         // bit 26 clears it: the rows outside the swept planes in a launch of their own (as in a split SpMV)
+  std::atomic<int> symp_direct{1};       // bit 27 clears it: the patch-major copy made from the slot-major copy in a second pass (k_symp_bind)
+  std::atomic<int> dia_pipe{1};          // bit 28 clears it: the layout copy (k_dia_vals) without its software pipeline
+  std::atomic<int> dia_fast{1};          // bit 29 clears it: the swept rows by k_dia_vals' row tiles instead of k_symp_fill (then pipelined as in bit 28)
+  std::atomic<int> symp_fingerprint{1};  // bit 30 clears it: the symmetry of the swept rows by the check pass (k_spmv_symp<1>) instead of the fill's fingerprint
+};
+extern EllKnobs g_ell;
+extern std::atomic<int64_t> g_layout_min_rows_dia, g_layout_min_rows_cols;  // spmv_ell.hip
+
+// The product kernels of a diagonal-slotted copy: the per-row kernel k_spmv_dia without / with the shared x loads of three consecutive diagonals,
+// the workgroup-tile sweep, the patch sweep.  A bind records the one its values got in mfem_csr_s::dia_kernel.
+enum DiaKernel : int { DIA_NONE = 0, DIA_ROWS, DIA_ROWS_TRIPLES, DIA_SYM27, DIA_SYMP };
+// THE decision which of them a copy wants, from the plan and the knobs (spmv_ell.hip).  refused: the sweep whose symmetry check the values of this
+// bind have just failed -- the next choice; *direct: the patch sweep's copy of the swept planes is filled straight from the CSR values.
+DiaKernel mfem_dia_kernel_wanted(const mfem_csr_s* A, DiaKernel refused = DIA_NONE, bool* direct = nullptr);
+// a product y = alpha A x + beta y (+ partial sums of y . dotw), as mfem_spmv_ell_launch receives it
+struct SpmvArgs {
+  const double* x; double* y; double alpha, beta; const double* dotw; double* partials; int* n_partials; const int32_t* done_flag; const SpmvPart& part;
+};
+// f(int64_t{}) or f(int32_t{}): the width of the pattern's row pointers, for the kernels that are templates on it
+template <typename F> static inline auto mfem_by_rowptr(const mfem_csr_s* A, F&& f) { return A->rowptr_bits == 64 ? f(int64_t{}) : f(int32_t{}); }
+
+// spmv_dia.hip: inspection; the copies of a bind (pvals: the swept planes G straight to the patch-major copy); all rows / the rows outside [lo, hi)
+int mfem_dia_plan(mfem_context_s* ctx, mfem_csr_s* A);
+int mfem_dia_copy(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, const double* ssym, const SympGeom& G,
+                  double* pvals, bool want_fp, bool* fp_made);
+int mfem_dia_launch(mfem_context_s* ctx, mfem_csr_s* A, bool triples, int cap, const SpmvArgs& a);
+int mfem_dia_launch_outside(mfem_context_s* ctx, mfem_csr_s* A, const SpmvArgs& a, double* partials, int64_t lo, int64_t hi, int* ngrid);
+// spmv_sym.hip: the two sweeps k = DIA_SYM27, DIA_SYMP -- structure, size rule, geometry, accounting, the symmetry verdict of a bind, the product
+void mfem_sym_plan(mfem_csr_s* A, const int32_t* off, int lc, int64_t m2, int64_t PL, int64_t run_lo, int64_t run_hi);
+bool mfem_sym_wanted(const mfem_csr_s* A, DiaKernel k);
+SympGeom mfem_symp_geom(const mfem_context_s* ctx, const mfem_csr_s* A);
+int64_t mfem_symp_steps(const mfem_csr_s* A);
+int64_t mfem_sym_entries(const mfem_context_s* ctx, const mfem_csr_s* A, DiaKernel k);
+int mfem_sym_verdict(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const double* buf, double* pvals, const SympGeom& G, bool direct, bool fp_made, bool* ok);
+int mfem_sym_launch(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const SpmvArgs& a);

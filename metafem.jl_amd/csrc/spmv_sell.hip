@@ -1,6 +1,6 @@
 // Row-sorted sliced ELL (SELL-128-sigma with sigma = n) for the Krylov loop on matrices whose rows are NOT of near-uniform
 // length -- hex-27 (27 / 45 / 75 / 125 entries per row depending on the node type) and every unstructured mesh.  Solver layout
-// mode 3; the uniform case is spmv_ell.hip (modes 1 and 2), the caller-facing contract stays CSR.
+// mode 3; the uniform case is spmv_ell.hip (mode 1) and spmv_dia.hip with its sweeps (mode 2), the caller-facing contract stays CSR.
 //
 //   * inspector (once per pattern): rows are stably sorted by decreasing length (hipCUB radix sort of (max_len - len, row));
 //     rows of equal length keep their mesh order, so the x gathers of a 128-row block stay as local as in CSR order.  Block b
@@ -1067,6 +1067,17 @@ int mfem_sell_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, doubl
   A->sell_vals = buf;
   A->sell_src = vals;
   return MFEM_OK;
+}
+
+// accounting (mfem_csr_solver_layout_entries / _bytes): the padded slots; blocks whose 128 rows share one diagonal list read it instead of their column stream
+int64_t mfem_sell_entries(const mfem_csr_s* A) { return A->sell_total; }
+int64_t mfem_sell_design_bytes(const mfem_csr_s* A) {
+  if (A->bsell_F > 0) return A->sell_total * 8 + A->bsell_slots * 4 + A->n * 16 + A->bsell_ncp * 4;  // node-blocked: one column per F x F values
+  const double regf = A->sell_nblk > 0 ? (double)A->sell_regular_blocks / (double)A->sell_nblk : 0.0;
+  // field-periodic blocks (round 6) read one column slot per node and F values: 1 / F of their column stream
+  const double per = (A->sell_nblk > 0 && A->sell_fields > 1) ? (double)A->sell_periodic_blocks / (double)A->sell_nblk : 0.0;
+  const double colfrac = (1.0 - regf - per) + (A->sell_fields > 1 ? per / (double)A->sell_fields : 0.0);
+  return A->sell_total * 8 + (int64_t)(colfrac * (double)A->sell_total) * 4 + A->n * 16 + A->n * 4;  // + the row permutation
 }
 
 void mfem_sell_unbind(mfem_csr_s* A) {

@@ -1,0 +1,694 @@
+// The two symmetric sweeps on the diagonal-slotted copy (spmv_dia.hip makes the copies; which kernel a copy gets: mfem_dia_kernel_wanted,
+// spmv_ell.hip): the workgroup-tile sweep k_spmv_sym27 and the wave-private patch sweep k_spmv_symp, each with the check of the pairs it mirrors.
+// One file: the patch sweep's call of dia_rows with a row range to skip keeps that code general, and k_spmv_sym27's instructions as they were.
+#include "blas1.h"
+#include "spmv_ell.h"
+
+// ---------------------------------------------------------------------------------------------------------------
+// Symmetric sweep kernel for the 27-point lattice stencil (offsets di PL + dj m2 + dk).  For a symmetric matrix the entry of
+// row r on a lower diagonal -o equals the entry of row r - o on the upper diagonal +o.  A workgroup owns an in-plane tile
+// of 512 rows and sweeps it through consecutive lattice planes (chunks c, c + S, c + 2 S, ...): the nine upper diagonals
+// that point to the next plane are kept in LDS when they are loaded, and the next plane's rows read their nine
+// previous-plane (lower) diagonals from there instead of from HBM.  Same products, same summation order as the plain
+// diagonal-slotted kernel: the result is bitwise the same whenever the matrix is bitwise symmetric (checked at bind time).
+// ---------------------------------------------------------------------------------------------------------------
+#define SYM_ROWS 512                 // rows of a tile = 4 blocks of 128 (768 rows / 384 threads / 2 workgroups per CU mirror more but run at 1.07 instead of 0.93 ms per CG iteration)
+#define SYM_THREADS (SYM_ROWS / 2)
+#define SYM_WG_PER_CU 3              // 53 KB of LDS per workgroup
+__global__ __launch_bounds__(SYM_THREADS) void k_spmv_sym27(int64_t n, int64_t npad, int K, const DiaOffsets* __restrict__ Op,
+                                                             const int32_t* __restrict__ flags, const int32_t* __restrict__ cols,
+                                                             const double* __restrict__ vals, const double* __restrict__ x,
+                                                             double* __restrict__ y, double alpha, double beta,
+                                                             const double* __restrict__ dotw, double* __restrict__ partials,
+                                                             const int32_t* __restrict__ done_flag, int64_t c0, int64_t c1, int S, int nsteps, int cls, int gs,
+                                                             int part) {  // 0: sweep + the chunks outside it; 1: sweep only; 2: only the chunks outside the sweep (every row that reads a ghost column of a slab is among them)
+  __shared__ __attribute__((aligned(16))) double hist[9][SYM_ROWS];  // diagonals 18..26 (into the next plane) of the previous chunk
+  __shared__ __attribute__((aligned(16))) double exch[4][SYM_ROWS];  // diagonals 14..17 (+z, +y) of this chunk
+  __shared__ double red[16];
+  if (done_flag && done_flag[0]) return;
+  const int32_t* off = Op->off[cls];
+  const int tid = threadIdx.x;
+  double dot_acc = 0.0;
+  // gs workgroups over S tiles: tile t is swept by nseg (+ 1 for the first gs % S tiles) workgroups, each taking a contiguous
+  // range of the tile's nsteps plane steps
+  const int tile = blockIdx.x % S, seg = blockIdx.x / S;
+  const int nseg = gs / S + (tile < gs % S ? 1 : 0);
+  const int seg_len = part == 2 ? 0 : (nsteps + nseg - 1) / nseg;
+  bool have_hist = false;
+  e_d2 up_next[4] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
+  {
+    const int64_t chunk = c0 + tile + (int64_t)S * ((int64_t)seg * seg_len);
+    if (part != 2 && seg * seg_len < nsteps && chunk < c1) {
+      const double* v = vals + ell_base(chunk * SYM_ROWS + 2 * tid, K);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) up_next[u] = SYM_LD(reinterpret_cast<const e_d2*>(v + (14 + u) * ELL_B));
+    }
+  }
+  for (int it = 0; it < seg_len; ++it) {
+    const int step = seg * seg_len + it;
+    const int64_t chunk = c0 + tile + (int64_t)S * step;
+    if (step >= nsteps || chunk >= c1) break;  // workgroup-uniform
+    const int64_t r = chunk * SYM_ROWS + 2 * tid;
+    const double* v = vals + ell_base(r, K);
+    e_d2 acc = {0.0, 0.0};
+    // ---- the lane's own +z / +y diagonals first: the rows behind it in this chunk read them as their -z / -y diagonals
+    e_d2 up[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      up[u] = up_next[u];  // requested during the previous chunk (or before the loop)
+      *reinterpret_cast<e_d2*>(&exch[u][2 * tid]) = up[u];
+    }
+    __syncthreads();  // exch complete; also: every wave has finished writing the previous chunk's history
+    // a slot's value pair, mirrored from LDS (row `lp` of table `tab`) when both source rows are in it, else from the row itself
+    auto slot = [&](int s, const double* tab, int lp, bool ok) -> e_d2 {
+      e_d2 w;
+      if (ok && lp >= 0 && lp + 1 < SYM_ROWS) {
+        w.x = tab[lp];
+        w.y = tab[lp + 1];
+      } else {
+        w = SYM_LD(reinterpret_cast<const e_d2*>(v + s * ELL_B));
+      }
+      return w;
+    };
+#define SYM_RUN(va, vb, vc, s0)                                          \
+  {                                                                      \
+    const u_d2* xp = reinterpret_cast<const u_d2*>(x + r + off[s0]);     \
+    const u_d2 xa = xp[0], xb = xp[1];                                   \
+    acc.x += va.x != 0.0 ? va.x * xa.x : 0.0;                            \
+    acc.y += va.y != 0.0 ? va.y * xa.y : 0.0;                            \
+    acc.x += vb.x != 0.0 ? vb.x * xa.y : 0.0;                            \
+    acc.y += vb.y != 0.0 ? vb.y * xb.x : 0.0;                            \
+    acc.x += vc.x != 0.0 ? vc.x * xb.x : 0.0;                            \
+    acc.y += vc.y != 0.0 ? vc.y * xb.y : 0.0;                            \
+    if (s0 == 12) {                                                      \
+      xself0 = xa.y;                                                     \
+      xself1 = xb.x;                                                     \
+    }                                                                    \
+  }
+    double xself0 = 0.0, xself1 = 0.0;
+    // ---- the nine diagonals into the previous plane: entry (r, r + o) = entry (r + o, r) on diagonal 26 - s of row r + o,
+    //      kept in `hist` if that row was in the previous chunk of this sweep
+    const int lph = 2 * tid + S * SYM_ROWS;
+#pragma unroll
+    for (int s = 0; s < 9; s += 3) {
+      const e_d2 va = slot(s, hist[8 - s], lph + off[s], have_hist);
+      const e_d2 vb = slot(s + 1, hist[7 - s], lph + off[s + 1], have_hist);
+      const e_d2 vc = slot(s + 2, hist[6 - s], lph + off[s + 2], have_hist);
+      SYM_RUN(va, vb, vc, s);
+    }
+    {  // -y diagonals 9..11 <- +y diagonals 17..15 of the rows one lattice line behind, if those are in this chunk
+      const e_d2 va = slot(9, exch[3], 2 * tid + off[9], true);
+      const e_d2 vb = slot(10, exch[2], 2 * tid + off[10], true);
+      const e_d2 vc = slot(11, exch[1], 2 * tid + off[11], true);
+      SYM_RUN(va, vb, vc, 9);
+    }
+    {  // -z (12) <- +z (14) of the row before; main diagonal 13; +z from the registers
+      e_d2 va;
+      va.y = up[0].x;  // row r + 1: entry (r + 1, r) = entry (r, r + 1)
+      if (tid > 0) va.x = exch[0][2 * tid - 1];
+      else va.x = v[12 * ELL_B];
+      const e_d2 vb = SYM_LD(reinterpret_cast<const e_d2*>(v + 13 * ELL_B));
+      SYM_RUN(va, vb, up[0], 12);
+    }
+    SYM_RUN(up[1], up[2], up[3], 15);
+    if (it + 1 < seg_len && step + 1 < nsteps && chunk + S < c1) {  // the next chunk's +z / +y diagonals: their latency hides behind
+      const double* vn = vals + ell_base((chunk + S) * SYM_ROWS + 2 * tid, K);  // the rest of this chunk
+#pragma unroll
+      for (int u = 0; u < 4; ++u) up_next[u] = SYM_LD(reinterpret_cast<const e_d2*>(vn + (14 + u) * ELL_B));
+    }
+    __syncthreads();  // every wave is done reading hist and exch
+    // ---- the nine diagonals into the next plane: they also go to LDS for the next chunk of the sweep
+#pragma unroll
+    for (int s = 18; s < 27; s += 3) {
+      const e_d2 va = SYM_LD(reinterpret_cast<const e_d2*>(v + s * ELL_B));
+      const e_d2 vb = SYM_LD(reinterpret_cast<const e_d2*>(v + (s + 1) * ELL_B));
+      const e_d2 vc = SYM_LD(reinterpret_cast<const e_d2*>(v + (s + 2) * ELL_B));
+      SYM_RUN(va, vb, vc, s);
+      *reinterpret_cast<e_d2*>(&hist[s - 18][2 * tid]) = va;
+      *reinterpret_cast<e_d2*>(&hist[s - 17][2 * tid]) = vb;
+      *reinterpret_cast<e_d2*>(&hist[s - 16][2 * tid]) = vc;
+    }
+#undef SYM_RUN
+    have_hist = true;
+    double y0 = alpha * acc.x, y1 = alpha * acc.y;
+    if (beta != 0.0) {
+      y0 += beta * y[r];
+      y1 += beta * y[r + 1];
+    }
+    y[r] = y0;
+    y[r + 1] = y1;
+    if (dotw) {
+      if (dotw == x) dot_acc += y0 * xself0 + y1 * xself1;
+      else dot_acc += y0 * dotw[r] + y1 * dotw[r + 1];
+    }
+  }
+  // after its sweep every workgroup takes a share of the chunks outside the regular range (first / last lattice planes, ghost
+  // planes of a slab) through the plain per-row code: no extra workgroups, no tail behind the sweeps
+  if (part != 1) {
+    const int64_t nchunks = (n + SYM_ROWS - 1) / SYM_ROWS;
+    for (int64_t q = blockIdx.x;; q += gridDim.x) {
+      const int64_t ch = q < c0 ? q : c1 + (q - c0);
+      if (ch >= nchunks) break;
+      const int64_t r = ch * SYM_ROWS + 2 * tid;
+      if (r < n) dia_rows<2, 3, true>(r, n, npad, K, *Op, flags, cols, vals, x, y, alpha, beta, dotw, 0, dot_acc);
+    }
+  }
+  if (partials) {
+    const double b = block_reduce_sum(dot_acc, red);
+    if (threadIdx.x == 0) partials[blockIdx.x] = b;
+  }
+}
+
+// bad[0] |= 1 unless, for every row r of the regular chunk range and every lower diagonal s < 13 whose source row r + off[s]
+// is in the range too, entry (r, s) equals entry (r + off[s], 26 - s) bitwise: exactly the substitutions k_spmv_sym27 makes
+__global__ __launch_bounds__(MFEM_BLOCK) void k_sym27_check(int K, const DiaOffsets* __restrict__ Op, const double* __restrict__ vals,
+                                                              int64_t row_lo, int64_t row_hi, int cls, int32_t* __restrict__ bad) {
+  const int32_t* off = Op->off[cls];
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int fail = 0;
+  for (int64_t r = row_lo + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < row_hi; r += stride) {
+    const double* v = vals + ell_base(r, K);
+    for (int s = 0; s < 13; ++s) {
+      const int64_t rs = r + off[s];
+      if (rs < row_lo) continue;
+      const double a = v[s * ELL_B], b = vals[ell_base(rs, K) + (26 - s) * ELL_B];
+      if (__double_as_longlong(a) != __double_as_longlong(b) && !(a == 0.0 && b == 0.0)) fail = 1;
+    }
+  }
+  if (fail) atomicOr(bad, 1);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Symmetric sweep, wave-private patches (k_spmv_symp; default when the lattice form is recognised).  The workgroup-tile kernel
+// above cuts a lattice plane into contiguous 512-row ranges: a lattice line longer than the tile (512^3: 513 points) leaves
+// only the in-line diagonals mirrorable (31 %), and two workgroup barriers per chunk bound what three workgroups per CU can keep
+// in flight.  Here a WAVE owns a (j, k) patch of 4 lattice lines x 32 points (lane <-> two neighbouring points of one line) and
+// sweeps it through consecutive lattice planes with no workgroup barrier at all:
+//   * the matrix values of the swept planes live in a patch-major copy, made when the solve binds its values (k_symp_fill, spmv_dia.hip; k_symp_bind): what every
+//     step reads -- slots 13..26 and the edge block, 16.9 KB -- contiguous per step [plane][patch], the lower slots (read where a run
+//     starts and by the symmetry check) behind;
+//   * the upper diagonals of a step go to the wave's LDS block when they are loaded: +z / +y (slots 14..17) for the rows behind
+//     them in this plane, the nine next-plane diagonals (18..26) for the same patch one plane on -- 10.5 of the 13 lower
+//     diagonals of a row are mirrored from there whatever the line length (the rest: patch edges, read from the row's own slot);
+//   * x is staged per plane: the (4 + 2) x (32 + 2) neighbourhood of the patch enters LDS once and serves the 27 products of three
+//     consecutive steps -- four global loads per lane and step instead of eighteen gathers.
+// Same products, same summation order as the plain diagonal-slotted kernel (v_mul_f64 + v_add_f64, no contraction): y is bitwise the
+// same whenever the mirrored pairs are bitwise equal (MODE 1 checks exactly those pairs when the values are bound).
+//   * A halo cell of a mirror table (its source row belongs to another patch) is filled from the step's EDGE BLOCK -- the own
+//     slot-s entries of the rows at the patch rim, 318 doubles stored behind the step's 27 slots -- so that every lane reads every
+//     lower slot with the same two LDS loads; a step reads 14 slots x 1 KB + 2.5 KB of edge block + 1.6 KB of x.
+//   * Everything a step needs from memory is requested one step ahead into registers (its loads are in flight during the products
+//     of the current step); two wave-level barriers per step order the LDS phases.
+//   * Runs: a run = one patch through nplanes / nseg consecutive planes, one wave (one-wave workgroups, 7 per CU: 22.8 KB of LDS
+//     each); a run's first step has no history and fills the previous-plane tables from the rows' own slots.  XCD c (workgroups
+//     with blockIdx % 8 == c) sweeps a contiguous eighth of the patches, segment by segment, so neighbouring patches advance
+//     through the planes together on one L2 (512^3: CG iteration 7.29 -> 6.66 ms against arbitrary equal cuts of the step list).
+//   * Rows outside the swept planes (first / last lattice plane, the planes next to the ghost planes of a slab) come from the slot-major
+//     copy through the per-row code: the sweep's waves take them in 128-row units after their runs (unsplit SpMV: one launch, no tail);
+//     in a split (multi-rank) SpMV they are the boundary part, a launch of their own (k_spmv_dia_outside) after the halo has arrived.
+// Measured (CG iteration, tools/probe_sym.py): see mfem_sym_wanted().  What bounds it: 2.78 GB of fabric traffic per SpMV at 256^3
+// (2.61 GB by the count above) in 0.59 ms = 4.7 TB/s; the time does not depend on the number of resident waves (2 .. 7 per CU), the
+// y stores cost 0.1 ms of it (non-temporal 16-byte stores: -1.5 %), the edge block 0.07 ms, the x staging 0.03 ms
+// (profiles/r02_symp_experiments.txt).
+// ---------------------------------------------------------------------------------------------------------------
+
+__constant__ int32_t c_sp_ecell[SP_EPAD];  // edge block entry -> LDS cell of its mirror table (the two padding entries: a spare cell)
+static int symp_upload_tables(int device) {  // __constant__ data is per device
+  static bool done[64] = {};
+  if (device >= 0 && device < 64 && done[device]) return MFEM_OK;
+  int32_t h[SP_EPAD];
+  for (int e = 0; e < SP_EPAD; ++e) {
+    int s_, l_, c_, cell = 0;
+    h[e] = sp_edge(e, s_, l_, c_, cell) ? cell : SP_TAB;
+  }
+  MFEM_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_sp_ecell), h, sizeof(h)));
+  if (device >= 0 && device < 64) done[device] = true;
+  return MFEM_OK;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __restrict__ pv, const double* __restrict__ x,
+                                                   double* __restrict__ y, double alpha, double beta,
+                                                   const double* __restrict__ dotw, double* __restrict__ partials,
+                                                   const int32_t* __restrict__ done_flag, int32_t* __restrict__ bad, SympTail tail) {
+  __shared__ __attribute__((aligned(16))) double xs[3][SP_XL][SP_XW];
+  __shared__ __attribute__((aligned(16))) double tab[SP_TAB + 2];
+  if (done_flag && done_flag[0]) return;
+  const int lane = threadIdx.x, lj = lane / SP_PW, pk = lane % SP_PW, lb = lj * SP_LS + 2 * pk;
+  const int NP = Gm.NS * Gm.NPk, nplanes = Gm.p1 - Gm.p0;
+  // Runs and XCDs: workgroups with equal blockIdx % 8 share an XCD (round-robin dispatch; gridDim.x is a multiple of 8).  XCD c sweeps
+  // a contiguous eighth of the patches, segment by segment, so that the runs resident on it at any time are neighbouring patches at
+  // about the same plane: their overlapping x neighbourhoods meet in that XCD's L2.
+  const int xcd = blockIdx.x & 7, pc = NP / 8, prem = NP % 8, pcnt = pc + (xcd < prem ? 1 : 0), pfirst = xcd * pc + (xcd < prem ? xcd : prem);
+  // the LDS cells this lane fills from the edge block (5 entries per lane; table made on the host once: decoding 320 entries with
+  // sp_edge() at the top of every launch cost every wave a few thousand instructions)
+  int ecell[SP_EU];
+#pragma unroll
+  for (int u = 0; u < SP_EU; ++u) ecell[u] = c_sp_ecell[lane + 64 * u];
+  int cur_patch = -1, bp = 0, bc = 1, bn = 2;  // x ring: previous / current / next plane
+  bool have_hist = false, vx = false, vy = false;
+  int64_t rin = 0;       // in-plane row offset j * m2 + k of the lane's first row
+  int xo[SP_XU], xa[SP_XU];  // x staging: in-plane offset (may be negative) and LDS slot of the lane's neighbourhood points
+  double dot_acc = 0.0;
+  int fail = 0;
+  e_d2 cur[14];          // slots 13..26 of the step, requested one step ahead
+  double ed[SP_EU], xr[SP_XU];  // its edge block entries and the x neighbourhood of the plane after it
+  // x neighbourhood entry of plane `plane`: positions outside the vector's owned entries (beyond the last lattice line of the last
+  // plane) are only ever multiplied by structurally absent entries -- any finite value serves: clamp
+  auto xidx = [&](int plane, int u) -> int64_t {
+    int64_t idx = (int64_t)plane * Gm.PL + xo[u];
+    idx = idx < 0 ? 0 : idx;
+    return idx < Gm.nx ? idx : Gm.nx - 1;
+  };
+  auto request = [&](const double* v, int pnext) {
+    if (vx) {
+#pragma unroll
+      for (int u = 0; u < 14; ++u) cur[u] = SYM_LD(reinterpret_cast<const e_d2*>(v + 2 * lane + u * SP_ROWS));
+    } else {
+#pragma unroll
+      for (int u = 0; u < 14; ++u) cur[u] = (e_d2){0.0, 0.0};
+    }
+    if (MODE == 0) {
+#pragma unroll
+      for (int u = 0; u < SP_EU; ++u) ed[u] = SYM_LD(v + 14 * SP_ROWS + lane + 64 * u);  // the block is padded to SP_EPAD entries
+#pragma unroll
+      for (int u = 0; u < SP_XU - 1; ++u) xr[u] = x[xidx(pnext, u)];
+      xr[SP_XU - 1] = lane < SP_XN - 64 * (SP_XU - 1) ? x[xidx(pnext, SP_XU - 1)] : 0.0;
+    }
+  };
+  auto stage_x = [&](int buf, int plane) {
+    double* dst = &xs[buf][0][0];
+#pragma unroll
+    for (int u = 0; u < SP_XU - 1; ++u) dst[xa[u]] = x[xidx(plane, u)];
+    if (lane < SP_XN - 64 * (SP_XU - 1)) dst[xa[SP_XU - 1]] = x[xidx(plane, SP_XU - 1)];
+  };
+  for (int run = blockIdx.x >> 3; run < pcnt * Gm.nseg; run += gridDim.x >> 3) {
+  const int patch = pfirst + run % pcnt, seg = run / pcnt;
+  const int64_t t0 = (int64_t)patch * nplanes + (int64_t)nplanes * seg / Gm.nseg, t1 = (int64_t)patch * nplanes + (int64_t)nplanes * (seg + 1) / Gm.nseg;
+  cur_patch = -1;
+  for (int64_t t = t0; t < t1; ++t) {
+    const int p = Gm.p0 + (int)(t - (int64_t)patch * nplanes);
+    const int64_t step = (int64_t)(p - Gm.p0) * NP + patch;  // [plane][patch]: the runs of a segment advance plane by plane together
+    const double* v = pv + step * SP_MAIN;                                         // slots 13..26 + edge block of the step
+    const double* vlow = pv + (int64_t)NP * nplanes * SP_MAIN + step * SP_LOW;    // its slots 0..12
+    if (patch != cur_patch) {  // wave-uniform: a run or a patch starts -- nothing was requested ahead, no history
+      cur_patch = patch;
+      const int j0 = (patch / Gm.NPk) * SP_L, k0 = (patch % Gm.NPk) * SP_W;
+      const int j = j0 + lj, k = k0 + 2 * pk;
+      vx = j < Gm.m1 && k < Gm.m2;
+      vy = j < Gm.m1 && k + 1 < Gm.m2;
+      rin = (int64_t)j * Gm.m2 + k;
+#pragma unroll
+      for (int u = 0; u < SP_XU; ++u) {
+        const int tt = lane + 64 * u, xl = tt / SP_XC, xc = tt - SP_XC * xl;
+        xo[u] = (j0 - 1 + xl) * Gm.m2 + (k0 - 1 + xc);
+        xa[u] = xl * SP_XW + xc;  // (u = 3: only lanes < 12 belong to the neighbourhood)
+      }
+      have_hist = false;
+      __syncthreads();  // the previous patch's last products may still be reading the x ring
+      request(v, p + 1);
+      if (MODE == 0) {
+        stage_x(bp, p - 1);
+        stage_x(bc, p);
+        // no history: the row's own previous-plane slots go where the mirror reads would look for them
+#pragma unroll
+        for (int s = 0; s < 9; ++s) {
+          const e_d2 w = vx ? SYM_LD(reinterpret_cast<const e_d2*>(vlow + 2 * lane + s * SP_ROWS)) : (e_d2){0.0, 0.0};
+          double* c = tab + sp_tbase(s) + (sp_dj(s) + sp_adj(s)) * SP_LS + sp_dk(s) + 2 + lb;
+          c[0] = w.x;
+          c[1] = w.y;
+        }
+      }
+    }
+    // ---- phase B: this step's +z / +y slots, its edge entries and the next plane's x go to LDS
+#pragma unroll
+    for (int s = 9; s < 13; ++s) *reinterpret_cast<e_d2*>(tab + sp_tbase(s) + sp_adj(s) * SP_LS + 2 + lb) = cur[26 - s - 13];
+    e_d2 low[13];
+    if (MODE == 0) {
+#pragma unroll
+      for (int u = 0; u < SP_EU; ++u) tab[ecell[u]] = ed[u];
+      double* dst = &xs[bn][0][0];
+#pragma unroll
+      for (int u = 0; u < SP_XU - 1; ++u) dst[xa[u]] = xr[u];
+      if (lane < SP_XN - 64 * (SP_XU - 1)) dst[xa[SP_XU - 1]] = xr[SP_XU - 1];
+    } else {
+#pragma unroll
+      for (int s = 0; s < 13; ++s) low[s] = vx ? SYM_LD(reinterpret_cast<const e_d2*>(vlow + 2 * lane + s * SP_ROWS)) : (e_d2){0.0, 0.0};
+    }
+    // the step's own upper slots stay in `mine`; the next step of the same sweep is requested now and arrives during the products
+    e_d2 mine[14];
+#pragma unroll
+    for (int u = 0; u < 14; ++u) mine[u] = cur[u];
+    const bool more = t + 1 < t1 && p + 1 < Gm.p1;  // the next step continues this sweep
+    __syncthreads();  // one wave: orders its LDS writes before the reads of other lanes
+    if (more) request(v + (int64_t)NP * SP_MAIN, p + 2);
+    auto mirrored = [&](int s) -> e_d2 {
+      const double* c = tab + sp_tbase(s) + (sp_dj(s) + sp_adj(s)) * SP_LS + sp_dk(s) + 2 + lb;
+      e_d2 w;
+      w.x = c[0];
+      w.y = c[1];
+      return w;
+    };
+    e_d2 acc = {0.0, 0.0};
+    double xself0 = 0.0, xself1 = 0.0;
+    // products rounded, then added, in slot order: what the plain kernel computes.  A structurally absent entry is an explicit zero
+    // and every staged x is an owned entry of the vector (finite whenever x is), so its product is a signed zero that leaves the sum
+    // unchanged -- no select needed here.
+    auto run = [&](const e_d2& va, const e_d2& vb, const e_d2& vc, int buf, int dj, bool self) {
+#pragma clang fp contract(off)  // v_mul_f64 + v_add_f64 like the plain kernel, not v_fma_f64
+      const double* xp = &xs[buf][lj + 1 + dj][2 * pk];
+      const e_d2 xa2 = *reinterpret_cast<const e_d2*>(xp), xb2 = *reinterpret_cast<const e_d2*>(xp + 2);
+      acc.x = acc.x + va.x * xa2.x;
+      acc.y = acc.y + va.y * xa2.y;
+      acc.x = acc.x + vb.x * xa2.y;
+      acc.y = acc.y + vb.y * xb2.x;
+      acc.x = acc.x + vc.x * xb2.x;
+      acc.y = acc.y + vc.y * xb2.y;
+      if (self) {
+        xself0 = xa2.y;
+        xself1 = xb2.x;
+      }
+    };
+    if (MODE == 1) {
+      // exactly the pairs the sweep mirrors: source rows inside the patch, previous-plane slots only where a history exists
+#pragma unroll
+      for (int s = 0; s < 13; ++s) {
+        const int dj = sp_dj(s), dk = sp_dk(s);
+        const bool in = lj + dj >= 0 && lj + dj < SP_L && (dk < 0 ? pk > 0 : dk > 0 ? pk < SP_PW - 1 : true);
+        if (in && vx && (s >= 9 || have_hist)) {
+          const e_d2 m = mirrored(s);
+          if (__double_as_longlong(m.x) != __double_as_longlong(low[s].x) && !(m.x == 0.0 && low[s].x == 0.0)) fail = 1;
+          if (vy && __double_as_longlong(m.y) != __double_as_longlong(low[s].y) && !(m.y == 0.0 && low[s].y == 0.0)) fail = 1;
+        }
+      }
+    } else {
+      run(mirrored(0), mirrored(1), mirrored(2), bp, -1, false);
+      run(mirrored(3), mirrored(4), mirrored(5), bp, 0, false);
+      run(mirrored(6), mirrored(7), mirrored(8), bp, 1, false);
+      run(mirrored(9), mirrored(10), mirrored(11), bc, -1, false);
+      run(mirrored(12), mine[0], mine[1], bc, 0, true);
+      run(mine[2], mine[3], mine[4], bc, 1, false);
+    }
+    __syncthreads();  // every lane is done with the tables
+#pragma unroll
+    for (int s = 0; s < 9; ++s) *reinterpret_cast<e_d2*>(tab + sp_tbase(s) + sp_adj(s) * SP_LS + 2 + lb) = mine[26 - s - 13];
+    have_hist = true;
+    if (MODE == 0) {
+      run(mine[5], mine[6], mine[7], bn, -1, false);
+      run(mine[8], mine[9], mine[10], bn, 0, false);
+      run(mine[11], mine[12], mine[13], bn, 1, false);
+      const int64_t r = (int64_t)p * Gm.PL + rin;
+      double y0 = alpha * acc.x, y1 = alpha * acc.y;
+      if (beta != 0.0) {
+        if (vx) y0 += beta * y[r];
+        if (vy) y1 += beta * y[r + 1];
+      }
+      {
+        // one 16-byte store (8-byte aligned), non-temporal: 0.910 -> 0.896 ms per CG iteration at 256^3
+        if (vy) __builtin_nontemporal_store((u_d2){y0, y1}, reinterpret_cast<u_d2*>(y + r));
+        else if (vx) __builtin_nontemporal_store(y0, y + r);
+      }
+      if (dotw) {
+        if (dotw == x) {
+          if (vx) dot_acc += y0 * xself0;
+          if (vy) dot_acc += y1 * xself1;
+        } else {
+          if (vx) dot_acc += y0 * dotw[r];
+          if (vy) dot_acc += y1 * dotw[r + 1];
+        }
+      }
+      const int b = bp;
+      bp = bc;
+      bc = bn;
+      bn = b;
+    }
+    if (!more) cur_patch = -1;  // nothing requested: the next step (if any) starts like a run
+  }
+  }
+  if (MODE == 0 && tail.on) {
+    // 128-row units in front of and behind the swept planes (a unit straddling the boundary is masked row by row), shared among the waves
+    const int64_t UA = (tail.lo + 127) / 128, ub = tail.hi / 128, UB = (tail.n + 127) / 128 - ub;
+    for (int64_t u = blockIdx.x; u < UA + UB; u += gridDim.x) {
+      const int64_t r = (u < UA ? u : ub + (u - UA)) * 128 + 2 * lane;
+      if (r < tail.n)
+        dia_rows<2, 3, true>(r, tail.n, tail.npad, tail.K, *tail.Op, tail.flags, tail.cols, tail.ell, x, y, alpha, beta, dotw, 0, dot_acc,
+                             tail.lo, tail.hi);
+    }
+  }
+  if (MODE == 1) {
+    if (fail) atomicOr(bad, 1);
+  } else if (partials) {
+    const double w = wave_reduce_sum(dot_acc);
+    if (lane == 0) partials[blockIdx.x] = w;
+  }
+}
+
+// patch-major copy of the swept planes from the slot-major copy: per step [plane - p0][patch] the slots 13..26 + the edge block (main
+// part) and, behind all main parts, the slots 0..12 (low part), zero
+// where the patch sticks out of the lattice; one wave per (plane, patch)
+__global__ __launch_bounds__(MFEM_BLOCK) void k_symp_bind(SympGeom Gm, int K, const double* __restrict__ ell, double* __restrict__ pv) {
+  const int lane = threadIdx.x & 63, lj = lane / SP_PW, pk = lane % SP_PW;
+  const int NP = Gm.NS * Gm.NPk;
+  const int64_t T = (int64_t)NP * (Gm.p1 - Gm.p0);
+  for (int64_t t = (int64_t)blockIdx.x * (MFEM_BLOCK / 64) + (threadIdx.x >> 6); t < T; t += (int64_t)gridDim.x * (MFEM_BLOCK / 64)) {
+    const int nplanes = Gm.p1 - Gm.p0, patch = (int)(t / nplanes), p = Gm.p0 + (int)(t % nplanes);
+    const int j0 = (patch / Gm.NPk) * SP_L, k0 = (patch % Gm.NPk) * SP_W;
+    const int j = j0 + lj, k = k0 + 2 * pk;
+    const bool vx = j < Gm.m1 && k < Gm.m2, vy = j < Gm.m1 && k + 1 < Gm.m2;
+    const int64_t r = (int64_t)p * Gm.PL + (int64_t)j * Gm.m2 + k;
+    const int64_t b0 = ell_base(r, K), b1 = ell_base(r + 1, K);
+    const int64_t step = (int64_t)(p - Gm.p0) * NP + patch;
+    double* out = pv + step * SP_MAIN;
+    double* outlow = pv + T * SP_MAIN + step * SP_LOW;
+    for (int s0 = 0; s0 < 27; s0 += 9) {
+      e_d2 w[9];
+#pragma unroll
+      for (int u = 0; u < 9; ++u) {
+        w[u].x = vx ? ell[b0 + (s0 + u) * ELL_B] : 0.0;
+        w[u].y = vy ? ell[b1 + (s0 + u) * ELL_B] : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < 9; ++u) {
+        const int sl = s0 + u;  // slots 0..12 to the low part, 13..26 to the main part
+        double* dst = sl < 13 ? outlow + sl * SP_ROWS : out + (sl - 13) * SP_ROWS;
+        *reinterpret_cast<e_d2*>(dst + 2 * lane) = w[u];
+      }
+    }
+    for (int e = lane; e < SP_EPAD; e += 64) {
+      int s = 0, line = 0, col = 0, cell = 0;
+      double val = 0.0;
+      if (sp_edge(e, s, line, col, cell) && j0 + line < Gm.m1 && k0 + col < Gm.m2)
+        val = ell[ell_base((int64_t)p * Gm.PL + (int64_t)(j0 + line) * Gm.m2 + k0 + col, K) + s * ELL_B];
+      out[14 * SP_ROWS + e] = val;
+    }
+  }
+}
+
+// Structure of the tile sweep (once per pattern): list `lc` with offsets `off` has the lattice form with PL rows per plane; blocks [run_lo, run_hi)
+// are the longest run of regular blocks, cut here to whole chunks (4 blocks)
+static void sym27_plan(mfem_csr_s* A, const int32_t* off, int lc, int64_t PL, int64_t run_lo, int64_t run_hi) {
+  const int64_t Sc = (PL + SYM_ROWS / 2) / SYM_ROWS;  // chunks per plane, rounded: the tiles drift by PL - Sc * 512 rows per plane
+  if (Sc < 8 || Sc > MFEM_MAX_PARTIALS / 2) return;   // any drift between tile and plane: the mirrored-fraction rule below decides
+  const int64_t bpc = SYM_ROWS / ELL_B, c0 = (run_lo + bpc - 1) / bpc, c1 = run_hi / bpc;
+  if (c1 - c0 < 4 * Sc) return;
+  // entries per chunk that k_spmv_sym27 mirrors instead of loading (same lane pattern in every chunk)
+  int64_t mx = 0, myz = 0;
+  for (int t = 0; t < SYM_ROWS / 2; ++t) {
+    for (int q = 0; q < 9; ++q) {
+      const int64_t lp = 2 * t + Sc * SYM_ROWS + off[q];
+      if (lp >= 0 && lp + 1 < SYM_ROWS) mx += 2;
+    }
+    for (int q = 9; q < 12; ++q) {
+      const int64_t lp = 2 * t + off[q];
+      if (lp >= 0 && lp + 1 < SYM_ROWS) myz += 2;
+    }
+    myz += t > 0 ? 2 : 1;
+  }
+  // worth it from a quarter of the 13 lower diagonals mirrored (hex-8 256^3: 65 %; 512^3, where a 513-point lattice line is
+  // longer than the tile and only the dj = 0 and -z diagonals qualify: 31 %, CG iteration 8.70 -> 7.91 ms)
+  if (20 * (mx + myz) < 5 * 13 * SYM_ROWS) return;
+  A->sym_state = 1;
+  A->sym_c0 = c0;
+  A->sym_c1 = c1;
+  A->sym_S = (int)Sc;
+  A->sym_cls = lc;
+  A->sym_mx = mx;
+  A->sym_myz = myz;
+}
+// Structure of the patch sweep: the lattice planes (m2 points per line) that lie entirely in that run
+static void symp_plan(mfem_csr_s* A, int lc, int64_t m2, int64_t PL, int64_t run_lo, int64_t run_hi) {
+  A->symp_state = -1;
+  if (PL % m2 != 0 || PL / m2 < 2 || PL >= (int64_t)1 << 30) return;
+  const int64_t p0 = (run_lo * ELL_B + PL - 1) / PL, p1 = run_hi * ELL_B / PL;
+  // a swept row reads x[r - PL - m2 - 1 .. r + PL + m2 + 1]: plane p0 >= 1 and p1 <= (rows / PL) - 1 follow from the
+  // regular-block test (r + off in [0, nx) for every row of the block)
+  if (p1 - p0 < 4 || p0 < 1) return;
+  A->symp_state = 1;
+  A->symp_m2 = (int)m2;
+  A->symp_m1 = (int)(PL / m2);
+  A->symp_PL = PL;
+  A->symp_p0 = (int)p0;
+  A->symp_p1 = (int)p1;
+  A->symp_NS = (A->symp_m1 + SP_L - 1) / SP_L;
+  A->symp_NPk = (A->symp_m2 + SP_W - 1) / SP_W;
+  A->sym_cls = lc;
+}
+void mfem_sym_plan(mfem_csr_s* A, const int32_t* off, int lc, int64_t m2, int64_t PL, int64_t run_lo, int64_t run_hi) {
+  sym27_plan(A, off, lc, PL, run_lo, run_hi);
+  symp_plan(A, lc, m2, PL, run_lo, run_hi);
+}
+
+// Is sweep k wanted on this structure?  (mfem_debug_set_layout_min_rows(0, ...) lifts the size limits for the parity tests.)
+// Tile sweep: it needs ~2 workgroups per CU of >= 8 steps each to beat the plain kernel -- chunk ranges below ~2700 chunks (1.4 M rows, measured crossover
+// between 96^3 and 112^3) stay on the plain kernel.  Patch sweep: measured CG iteration, workgroup-tile sweep / patch sweep (tools/probe_sym.py): 128^3
+// 0.142 / 0.173 ms, 192^3 0.369 / 0.397, 256^3 0.896 / 0.896, 320^3 1.82 / 1.72, 384^3 3.28 / 2.89, 512^3 7.95 / 6.66 -- the patch sweep from 2.4e7 swept
+// rows on, or where a lattice line no longer fits the 512-row tile twice.
+bool mfem_sym_wanted(const mfem_csr_s* A, DiaKernel k) {
+  if (!g_ell.sym || !A->dia_triples) return false;
+  const bool all = g_layout_min_rows_dia == 0;
+  if (k == DIA_SYM27) return A->sym_state == 1 && (all || A->sym_c1 - A->sym_c0 >= 2700);
+  return A->symp_state == 1 && g_ell.symp && (all || (int64_t)(A->symp_p1 - A->symp_p0) * A->symp_PL >= 24000000 || A->symp_m2 > 256);
+}
+
+static int sym27_grid(const mfem_context_s* ctx, const mfem_csr_s* A, int64_t* nsteps_out) {
+  // 53 KB of LDS per workgroup: three per CU; equal segments for every tile and all workgroups resident in one round
+  // (645 workgroups of 51 steps beat 768 of 43 / 51 at 256^3: the longest segment sets the time)
+  const int64_t nsteps = (A->sym_c1 - A->sym_c0 + A->sym_S - 1) / A->sym_S;
+  const int resident = SYM_WG_PER_CU * ctx->num_cus;
+  int nseg = resident / A->sym_S;
+  if (nseg < 1) nseg = 1;
+  // tiles that cannot fill the resident slots in whole rounds (512^3: 514 tiles on 768 slots) are cut into ~2.7 rounds of shorter
+  // segments instead: 8.92 -> 7.91 ms per CG iteration there; at 256^3 (645 of 768) more segments change nothing
+  if ((int64_t)A->sym_S * nseg * 10 < (int64_t)resident * 8) nseg = (8 * ctx->num_cus + A->sym_S - 1) / A->sym_S;
+  while (nseg > 1 && (int64_t)A->sym_S * nseg > MFEM_MAX_PARTIALS - 512) --nseg;  // one partial sum per workgroup (+ <= 512 of the boundary part of a split SpMV)
+  if (nseg > nsteps / 8) nseg = (int)(nsteps / 8);  // a segment's first step has no history: keep segments >= 8 steps long
+  if (nseg < 1) nseg = 1;
+  if (nsteps_out) *nsteps_out = nsteps;
+  return A->sym_S * nseg;
+}
+// runs per patch: the smallest count that fills >= 90 % of the resident one-wave workgroups in whole rounds (a run's first step has no
+// history: runs stay >= 16 planes long)
+static int symp_nseg(const mfem_context_s* ctx, const mfem_csr_s* A) {
+  const int64_t NP = (int64_t)A->symp_NS * A->symp_NPk, slots = (int64_t)SP_WG_PER_CU * ctx->num_cus;
+  const int nplanes = A->symp_p1 - A->symp_p0;
+  int best = 1;
+  double best_eff = 0.0;
+  for (int ns = 1; ns <= (nplanes / 16 > 1 ? nplanes / 16 : 1) && ns <= 64; ++ns) {
+    const int64_t R = NP * ns, rounds = (R + slots - 1) / slots;
+    const double eff = (double)R / (double)(rounds * slots);
+    if (eff > best_eff + 1e-9) { best_eff = eff; best = ns; }
+    if (eff >= 0.9) { best = ns; break; }
+  }
+  return best;
+}
+SympGeom mfem_symp_geom(const mfem_context_s* ctx, const mfem_csr_s* A) {  // (nx = n: the sweep stages owned entries of x only -- swept rows reference no ghost column)
+  return SympGeom{A->symp_PL, A->n, A->symp_m1, A->symp_m2, A->symp_p0, A->symp_p1, A->symp_NS, A->symp_NPk, symp_nseg(ctx, A)};
+}
+int64_t mfem_symp_steps(const mfem_csr_s* A) { return (int64_t)A->symp_NS * A->symp_NPk * (A->symp_p1 - A->symp_p0); }
+static int symp_grid(const mfem_context_s* ctx, const mfem_csr_s* A) {
+  const int64_t NP = (int64_t)A->symp_NS * A->symp_NPk;
+  int64_t g = 8 * ((NP + 7) / 8) * symp_nseg(ctx, A);  // every XCD's share of the runs, padded to the largest share
+  int64_t cap = (int64_t)SP_WG_PER_CU * ctx->num_cus;
+  if (cap > MFEM_MAX_PARTIALS - 1024) cap = MFEM_MAX_PARTIALS - 1024;
+  cap &= ~(int64_t)7;
+  if (g > cap) g = cap;
+  return g < 8 ? 8 : (int)g;
+}
+
+// Matrix entries (8 B) one product by sweep k reads from memory.  Tile sweep: K per padded row less what it takes from LDS.  Patch sweep: the rows
+// outside the swept planes read their K slots; the sweep reads the 14 upper slots of every valid lane pair and the edge block per step + the nine
+// previous-plane slots wherever a run or a patch starts.
+int64_t mfem_sym_entries(const mfem_context_s* ctx, const mfem_csr_s* A, DiaKernel k) {
+  if (k == DIA_SYM27) {
+    const int64_t nch = A->sym_c1 - A->sym_c0;
+    return (int64_t)A->ell_K * A->ell_npad - ((nch - sym27_grid(ctx, A, nullptr)) * A->sym_mx + nch * A->sym_myz);
+  }
+  const int NP = A->symp_NS * A->symp_NPk, nplanes = A->symp_p1 - A->symp_p0, nseg = symp_nseg(ctx, A);
+  int64_t e = (int64_t)A->ell_K * (A->ell_npad - (int64_t)nplanes * A->symp_PL);
+  for (int patch = 0; patch < NP; ++patch) {
+    int64_t nv = 0;
+    for (int lane = 0; lane < 64; ++lane) {
+      const int j = (patch / A->symp_NPk) * SP_L + lane / SP_PW, kk = (patch % A->symp_NPk) * SP_W + 2 * (lane % SP_PW);
+      if (j < A->symp_m1 && kk < A->symp_m2) ++nv;
+    }
+    e += (28 * nv + SP_NE) * nplanes + 18 * nv * nseg;
+  }
+  return e;
+}
+
+static std::atomic<long long> g_symp_fp_checks{0};  // binds whose symmetry verdict came from the fill's fingerprint (tests)
+extern "C" long long mfem_debug_symp_fingerprint_count(void) { return g_symp_fp_checks; }
+
+// Are the pairs sweep k mirrors bitwise equal in the copies of this bind (buf: slot-major, pvals: patch-major)?  The patch sweep's copy is completed
+// first when it was not filled directly; its verdict is the fill's fingerprint when it made one (zero = symmetric among the swept rows), else a
+// check pass, as for the tile sweep.
+int mfem_sym_verdict(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const double* buf, double* pvals, const SympGeom& G, bool direct, bool fp_made, bool* ok) {
+  int32_t* d_bad = ctx->d_flags + 9;
+  if (k == DIA_SYMP) {
+    { const int rt = symp_upload_tables(ctx->device); if (rt) return rt; }
+    if (!direct) {
+      const int64_t T = mfem_symp_steps(A);
+      const int gb = (int)(T / 4 + 1 < (int64_t)ctx->num_cus * 32 ? T / 4 + 1 : (int64_t)ctx->num_cus * 32);
+      hipLaunchKernelGGL(k_symp_bind, dim3(gb), dim3(MFEM_BLOCK), 0, ctx->stream, G, A->ell_K, buf, pvals);
+      MFEM_CHECK_LAUNCH();
+    }
+    if (fp_made) {
+      MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 16, ctx->d_flags + 16, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+      MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+      unsigned long long fpv;
+      memcpy(&fpv, ctx->h_flags + 16, sizeof(fpv));
+      *ok = fpv == 0;
+      ++g_symp_fp_checks;
+      return MFEM_OK;
+    }
+  }
+  MFEM_CHECK_HIP(hipMemsetAsync(d_bad, 0, sizeof(int32_t), ctx->stream));
+  if (k == DIA_SYMP)
+    hipLaunchKernelGGL(k_spmv_symp<1>, dim3(symp_grid(ctx, A)), dim3(64), 0, ctx->stream, G, (const double*)pvals, (const double*)nullptr,
+                       (double*)nullptr, 0.0, 0.0, (const double*)nullptr, (double*)nullptr, (const int32_t*)nullptr, d_bad, SympTail{});
+  else
+    hipLaunchKernelGGL(k_sym27_check, dim3(ctx->num_cus * 8), dim3(MFEM_BLOCK), 0, ctx->stream, A->ell_K, (const DiaOffsets*)A->dia_dev, buf,
+                       A->sym_c0 * SYM_ROWS, A->sym_c1 * SYM_ROWS, A->sym_cls, d_bad);
+  MFEM_CHECK_LAUNCH();
+  MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 9, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  *ok = ctx->h_flags[9] == 0;
+  return MFEM_OK;
+}
+
+// The product by sweep k.  Tile sweep: the rows of the regular chunk range by the sweep, the rest by the per-row code in the same launch (part 2 of a
+// split SpMV: those chunks alone, after the halo has arrived, one workgroup each).  Patch sweep: the swept planes on the patch-major copy, the other
+// rows by the per-row code on the slot-major copy -- unsplit SpMV: the sweep's waves take them after their runs (bit 26 of the "ell" knob: a launch
+// of their own); split SpMV: part 1 = the sweep alone (it reads no ghost column), part 2 = the other rows in a launch of their own.
+int mfem_sym_launch(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const SpmvArgs& a) {
+  const DiaOffsets* O = (const DiaOffsets*)A->dia_dev;
+  int np = 0;
+  if (k == DIA_SYM27) {
+    int64_t nsteps = 0;
+    const int gs = sym27_grid(ctx, A, &nsteps);
+    const int64_t outside = (A->n + SYM_ROWS - 1) / SYM_ROWS - (A->sym_c1 - A->sym_c0);
+    np = a.part.part == 2 ? (int)(outside < 1 ? 1 : outside < 512 ? outside : 512) : gs;
+    hipLaunchKernelGGL(k_spmv_sym27, dim3(np), dim3(SYM_THREADS), 0, ctx->stream, A->n, A->ell_npad, A->ell_K, O, A->dia_flags, A->ell_cols, A->ell_vals,
+                       a.x, a.y, a.alpha, a.beta, a.dotw, a.partials, a.done_flag, A->sym_c0, A->sym_c1, A->sym_S, (int)nsteps, A->sym_cls, gs, a.part.part);
+    MFEM_CHECK_LAUNCH();
+  } else {
+    const SympGeom G = mfem_symp_geom(ctx, A);
+    const int64_t lo = (int64_t)G.p0 * G.PL, hi = (int64_t)G.p1 * G.PL;
+    SympTail tl{};
+    if (a.part.part == 0 && g_ell.symp_tail) tl = SympTail{1, A->ell_K, A->n, A->ell_npad, lo, hi, O, A->dia_flags, A->ell_cols, A->ell_vals};
+    if (a.part.part != 2) {
+      np = symp_grid(ctx, A);
+      hipLaunchKernelGGL(k_spmv_symp<0>, dim3(np), dim3(64), 0, ctx->stream, G, (const double*)A->symp_vals, a.x, a.y, a.alpha, a.beta, a.dotw,
+                         a.partials, a.done_flag, (int32_t*)nullptr, tl);
+      MFEM_CHECK_LAUNCH();
+    }
+    if (a.part.part == 2 || (a.part.part == 0 && !tl.on)) {
+      int go = 0;
+      const int rc = mfem_dia_launch_outside(ctx, A, a, a.partials ? a.partials + np : nullptr, lo, hi, &go);
+      if (rc) return rc;
+      np += go;
+    }
+  }
+  if (a.n_partials && a.partials) *a.n_partials = np;
+  return MFEM_OK;
+}

@@ -1,4 +1,4 @@
-// Geometry of the wave-private patch sweep (spmv_ell.hip: k_spmv_symp): patch shape, LDS mirror tables and the per-step edge block.
+// Geometry of the wave-private patch sweep (spmv_sym.hip: k_spmv_symp; the layout copy k_dia_vals of spmv_dia.hip places the same entries): patch shape, LDS mirror tables and the per-step edge block.
 // Host + device: tools/host_check_symp.cpp replays the table bookkeeping on the CPU (tests/test_host_checks.py).
 #pragma once
 #ifndef __HIPCC__

@@ -1,4 +1,4 @@
-// Timing probe for the per-solve layout copy (k_dia_vals, spmv_ell.hip): what does the memory system give a wave that reads a 64-row tile of a
+// Timing probe for the per-solve layout copy (k_dia_vals, spmv_dia.hip): what does the memory system give a wave that reads a 64-row tile of a
 // 27-entries-per-row CSR value stream (13 824 contiguous bytes), transposes it through LDS and writes 27 slot pieces?  Stand-alone (no library):
 //   hipcc --offload-arch=gfx950 -O3 -o /tmp/copy_probe tools/copy_probe.hip && /tmp/copy_probe [rows = 135005697]
 // Variants, each timed over the whole value array (best of 3):

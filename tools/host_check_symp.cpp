@@ -1,4 +1,4 @@
-// CPU replay of the mirror-table bookkeeping of the wave-private patch sweep (csrc/spmv_symp.h, k_spmv_symp in spmv_ell.hip) on a small
+// CPU replay of the mirror-table bookkeeping of the wave-private patch sweep (csrc/spmv_symp.h, k_spmv_symp in spmv_sym.hip) on a small
 // lattice with a symmetric 27-point operator: for every patch, plane, lane, row and lower slot the value the kernel would read from its
 // LDS tables (interior cells written from the upper slots of the source rows, halo cells from the edge block, run starts from the row's
 // own slots) must be the row's own entry; edge-block cells must be distinct halo cells, interior cells distinct non-halo cells.
