@@ -172,7 +172,7 @@ unsigned long long mfem_debug_ws_address(mfem_context ctx);
  * trial (the candidates' timing uses no collective).  bench.py opts in with --ws-trial 1 and says so in its line. */
 /* ^ key "ws_trial": mfem_debug_set("ws_trial", a, b) with (int on) = (a[, b]) */
 /* 1 (default): the two vector kernels of the classic CG recurrences use streaming (nontemporal) loads, and from 4e7 rows on streaming stores too
- * (csrc/krylov.hip: cg_ld / cg_st); 0: plain accesses.  Same values either way. */
+ * (csrc/krylov_cg.hip: cg_ld / cg_st); 0: plain accesses.  Same values either way. */
 /* ^ key "cg_streaming": mfem_debug_set("cg_streaming", a, b) with (int on) = (a[, b]) */
 /* cg_variant 0 (auto) with a communicator of more than one rank: the single-reduction CG (one all-reduce, 9 vector streams per iteration) below this many
  * rows per rank (n_global / world; default 2e7), the classic recurrence (two all-reduces, 8 streams) from there on -- at 512^3 per rank a vector stream

@@ -79,13 +79,13 @@ struct mfem_context_s {
   double* h_scalars;    // pinned, [256]
   int32_t* d_flags;     // [24] device flags (16-17: the symmetry fingerprint of k_symp_fill, 64 bits): 0-7 the Krylov loop's two banks (done, iteration count, ...); 9 mirrored-sweep check; 10 ring self-test; 11 mesh
                         // assembly; 12-15 one-shot statistics, each user clears the slots it reads before its launch and synchronises after it (layout binds:
-                        // 12-13 max |a| / symmetry measure, krylov.hip: 12-15 extremes of S, assemble_hex27.hip: 14 count of non-affine elements)
+                        // 12-13 max |a| / symmetry measure, krylov.hip (try_scaled_cg): 12-15 extremes of S, assemble_hex27.hip: 14 count of non-affine elements)
   int32_t* h_flags;     // pinned
   // generic workspace (grown on demand, never shrunk)
   void* ws;        // (ws_raw + the placement offset, see mfem_ws_reserve)
   void* ws_raw;    // what hipMalloc returned
   size_t ws_bytes;
-  // placement of a large workspace (krylov.hip, solve_inner): the solver SpMV runs at one of two speeds depending on the physical memory an
+  // placement of a large workspace (krylov.hip: ws_trial; the decision: solve_decide.h): the solver SpMV runs at one of two speeds depending on the physical memory an
   // allocation received (profiles/r03_placement_probe.txt); the first big solve on a workspace times it, tries ONE second allocation and keeps
   // the faster.  ws_try: candidates allocated after the first (the best so far kept in ws_alt*); 99: decided.
   int ws_try;
@@ -116,7 +116,7 @@ struct mfem_context_s {
   hipStream_t graph_stream;
   hipEvent_t graph_ev;
   int graph_active;   // set by mfem_solve for the duration of a solve when cycles may be captured
-  int force_csr;      // set while a product must run the CSR kernel on the caller's arrays whatever layout is bound (the residual a tile solve reports, krylov.hip)
+  int force_csr;      // set while a product must run the CSR kernel on the caller's arrays whatever layout is bound (the residual a tile solve reports, krylov.hip: csr_true_residual)
   int probe_active;   // set while a measuring product runs on this context (symmetry probe, placement trial): not an SpMV a solver asked for -- the usage counters skip it
 };
 #define MFEM_PROF_PAIRS 1024

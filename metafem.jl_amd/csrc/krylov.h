@@ -1,4 +1,4 @@
-// Shared declarations of the Krylov translation units.
+// Shared declarations of the Krylov translation units: the driver with what every solver uses (krylov.hip), one file per solver (krylov_*.hip).
 #pragma once
 #include "blas1.h"
 
@@ -60,17 +60,17 @@ struct KrylovVecs {
 int mfem_fill(mfem_context_s* ctx, int64_t n, double v, double* x);
 int mfem_sum_partials(mfem_context_s* ctx, const double* partials, int np, double* d_out);
 int mfem_true_residual(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, const double* b, const double* x,
-                       double* r, int64_t nv, double* d_rr);
+                       double* r, double* d_rr);
 // r = b - A x at the start of a pass; the SpMV is skipped while V.x_zero holds (r = b, r.r summed in the order the SpMV path sums it: the same bits).
 // *spmv_out is advanced only when a product ran.
 int mfem_pass_residual(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, const KrylovVecs& V, double* r, double* d_rr, int* spmv_out);
 int mfem_read_scalars(mfem_context_s* ctx, int first, int count);
 int mfem_read_flags(mfem_context_s* ctx);
-// One pass of a solver (the method table of solve_inner): s = l_or_s or the method's default (unused by the methods without one); the pass's
+// One pass of a solver (krylov.hip: k_methods, the driver's table of them): s = l_or_s or the method's default (unused by the methods without one); the pass's
 // iteration count to *iters_out, the products that ran added to *spmv_out (include/metafem_mi355x.h: mfem_solve_stats.spmv_count)
 typedef int mfem_pass_fn(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o, int s, double tol,
                          int64_t n_global, int* iters_out, int* spmv_out);
-mfem_pass_fn mfem_bicgstabl_pass, mfem_cgs2_pass, mfem_idrs_pass, mfem_gmres_pass;
+mfem_pass_fn mfem_cg_pass, mfem_cg_single_pass, mfem_bicgstabl_pass, mfem_cgs2_pass, mfem_idrs_pass, mfem_gmres_pass;  // (krylov_cg.hip: both cg! passes)
 // krylov_next.hip: cgs!, tfqmr! (checkiter = s, default 200), lsqr! (products with A' through V.AT / V.valsT)
 mfem_pass_fn mfem_cgs_pass, mfem_tfqmr_pass, mfem_lsqr_pass;
 size_t mfem_gmres_workspace_bytes();

@@ -105,7 +105,7 @@ int mfem_cgs2_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Krylo
     KV(kc_half2, nv / 2, (const d2_t*)t, (const d2_t*)c, (const d2_t*)v, (d2_t*)s, (d2_t*)u, (d2_t*)V.x, S, F);
     // r = b - A x (:96-98).  The kernels below are not DONE-guarded, which is harmless: once DONE is set x no longer
     // changes, so they recompute the same r.
-    RC(mfem_true_residual(ctx, A, vals, V.b, V.x, r, nv, S + S_RR));
+    RC(mfem_true_residual(ctx, A, vals, V.b, V.x, r, S + S_RR));
     K1(kc_end, a, S, F);
     return MFEM_OK;
   };

@@ -371,7 +371,7 @@ int mfem_gmres_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Kryl
     RC(gm_xupdate(ctx, G, s, nv, B, y, V.x, F));
     K1(kg_cycle_end, a, F);
     // r = b - A x (:88-90).  Not DONE-guarded, which is harmless: once DONE is set x no longer changes, so it recomputes the same r.
-    RC(mfem_true_residual(ctx, A, vals, V.b, V.x, r, nv, S + S_RR));
+    RC(mfem_true_residual(ctx, A, vals, V.b, V.x, r, S + S_RR));
     K1(kg_cycle_test, a, S, F);
     return MFEM_OK;
   };

@@ -330,7 +330,7 @@ int mfem_cgs_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Krylov
     K1F(kcs_alpha, fa, S, F);
     KV(kcs_px, nv / 2, (const d2_t*)s, (const d2_t*)v, (d2_t*)p, (d2_t*)V.x, S, F);
     // r = b - A x (:45-47); not DONE-guarded, harmless: once DONE is set x no longer changes
-    RC(mfem_true_residual(ctx, A, vals, V.b, V.x, r, nv, S + S_RR));
+    RC(mfem_true_residual(ctx, A, vals, V.b, V.x, r, S + S_RR));
     K1(kcs_end, a, S, F);
     return MFEM_OK;
   };
@@ -363,7 +363,7 @@ int mfem_tfqmr_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Kryl
     RC(k.spmv(A, vals, p, v));
     K1(ktq_end, a, F);
     if (form == KC_ALT) {  // (iter % checkiter == 0: the only iterations that compute a residual)
-      RC(mfem_true_residual(ctx, A, vals, V.b, V.x, r, nv, S + S_RR));
+      RC(mfem_true_residual(ctx, A, vals, V.b, V.x, r, S + S_RR));
       K1(ktq_check, a, S, F);
     }
     return MFEM_OK;
@@ -404,7 +404,7 @@ int mfem_lsqr_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, Krylo
     KV(klq_lin_norm, V.n, nv / 2, (const d2_t*)tmp, (d2_t*)v, ctx->d_partials, (int)LQ_BETA, S, F, (int)F_NX_SKIP);  // v = Pl(tmp) - beta v
     K1F(klq_rot, fa, S, F);
     KV(klq_xw, nv / 2, (d2_t*)v, (d2_t*)w, (d2_t*)V.x, S, F);
-    RC(mfem_true_residual(ctx, A, vals, V.b, V.x, r, nv, S + S_RR));                                 // r = Pl(b - A x)  (:64-66)
+    RC(mfem_true_residual(ctx, A, vals, V.b, V.x, r, S + S_RR));                                 // r = Pl(b - A x)  (:64-66)
     K1(klq_end, a, S, F);
     return MFEM_OK;
   };

@@ -1,7 +1,7 @@
-// The solver layouts of a CSR handle, planned, bound, released and accounted for here only: mfem_solve (krylov.hip), the layout query and the diagnostic product
+// The solver layouts of a CSR handle, planned, bound, released and accounted for here only: mfem_solve (the stages of its driver, krylov.hip), the layout query and the diagnostic product
 // below take the same rules.  At most one layout is bound at a time; which one serves a product is read off the per-layout pointers, never cached
 // beside them: the tile binds' symmetry probe (mfem_sym_probe) unbinds and rebinds the tiles through callbacks of its own.  Nothing here issues a
-// collective: a refusal of the tiles is a rank-local verdict (krylov.hip: solve_inner).
+// collective: a refusal of the tiles is a rank-local verdict (krylov.hip: bind_tiles, solve_inner).
 #include "blas1.h"
 #include "layouts.h"
 

@@ -309,7 +309,7 @@ static int dia_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, doub
 
 // Transpose CSR-ordered values into `buf` and route subsequent mfem_spmv_launch calls with these `vals` to this layout's kernels.
 // dsc (optional): right Jacobi column scaling applied on the way (copy = vals[j] / dsc[col[j]]): the Krylov loop then runs on the scaled
-// matrix without a scaled CSR copy ever existing (solve_inner).  `vals` stays the identity of the bound values.
+// matrix without a scaled CSR copy ever existing (krylov.hip: plan_layouts, bind_rows).  `vals` stays the identity of the bound values.
 int mfem_ell_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, const double* ssym) {
   mfem_ell_unbind(A);
   if (A->ell_state != 1 || !g_ell.enable || !buf) return MFEM_OK;

@@ -854,7 +854,7 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_lat27_gather_st(Lat27Geom G, con
 // The fused CG iteration on the lattice tiles (one rank): pass 2 and the residual update of Jacobi-CG in one kernel.  q = A p is needed twice in a CG iteration --
 // in p . q, which pass 1 now delivers (k_spmv_lat27: dotp), and in r -= alpha q -- so the sums over the covering blocks are formed here, used and never stored:
 // no y written and read back, no separate gather launch (3 of the iteration's vector streams and one launch less).  Staging and summation order are
-// k_lat27_gather_st's; the update arithmetic is k_cg_update's (krylov.hip), operation for operation.
+// k_lat27_gather_st's; the update arithmetic is k_cg_update's (krylov_cg.hip), operation for operation.
 __global__ __launch_bounds__(MFEM_BLOCK) void k_lat27_gather_cg(Lat27Geom G, const double* __restrict__ dump, LatCgUpdate U) {
   __shared__ double E[L27_ECELLS];
   __shared__ double red[4];
@@ -1232,7 +1232,7 @@ int64_t mfem_lat27_design_bytes(const mfem_csr_s* A) {
 }
 int64_t mfem_lat27_entries(const mfem_csr_s* A) { return (int64_t)lat27_read_doubles(lat27_geom(A)); }
 
-// ---- the fused CG iteration (krylov.hip, cg_solve_pass): pass 1 alone (mfem_spmv_halo with y = nullptr), the dot-product partials, pass 2 + residual update
+// ---- the fused CG iteration (krylov_cg.hip, mfem_cg_pass): pass 1 alone (mfem_spmv_halo with y = nullptr), the dot-product partials, pass 2 + residual update
 bool mfem_lat27_cg_fused(const mfem_context_s* ctx, const mfem_csr_s* A, const double* vals) {
   return g_lat27_cg_fused && A->lat27_vals && vals == A->lat27_src && !A->lat27_dsc && !ctx->comm && !A->rem_active;
 }

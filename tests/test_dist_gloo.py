@@ -1,7 +1,7 @@
 """N > 1 path on CPU: slab partition + halo protocol + all-reduce semantics with world_size 2/3 over gloo.
 
 Every rank extracts its slab of the global oracle system with the HOST restatement of the device numbering
-(metafem_jl_amd.parallel.slab_local_index), then runs the distributed Jacobi-PCG exactly as csrc/krylov.hip
+(metafem_jl_amd.parallel.slab_local_index), then runs the distributed Jacobi-PCG exactly as csrc/krylov_cg.hip
 sequences it (halo exchange of p before each SpMV, all-reduce of p.Ap and of (r.z, r.r)), and the gathered
 result must equal the single-rank oracle solve.
 """

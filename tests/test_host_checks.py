@@ -10,7 +10,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.parametrize("name", ["host_check_hex8", "host_check_symp", "host_check_lat"])
+@pytest.mark.parametrize("name", ["host_check_hex8", "host_check_symp", "host_check_lat", "host_check_solve"])
 def test_host_check(name, tmp_path):
     exe = str(tmp_path / name)
     subprocess.run(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "metafem.jl_amd", "csrc"),
