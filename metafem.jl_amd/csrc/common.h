@@ -14,6 +14,7 @@
 #include "../../include/metafem_mi355x.h"
 #include "../../include/metafem_mi355x_debug.h"
 #include "csr_decide.h"
+#include "sell_decide.h"
 
 #define MFEM_WAVE 64
 #define MFEM_BLOCK 256
@@ -48,6 +49,21 @@ void mfem_host_alloc_probe();
   } while (0)
 
 #define MFEM_CHECK_LAUNCH() MFEM_CHECK_HIP(hipGetLastError())
+
+// Owner of one device allocation, move-only: freed when it goes out of scope unless release() has handed the pointer on (to a handle).
+template <typename T> struct __attribute__((visibility("hidden"))) DevBuf {
+  T* p = nullptr;
+  DevBuf() = default;
+  DevBuf(DevBuf&& o) noexcept : p(o.release()) {}
+  DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = o.release(); } return *this; }
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { reset(); }
+  hipError_t alloc(size_t count) { reset(); return hipMalloc((void**)&p, sizeof(T) * count); }
+  void reset() { if (p) (void)hipFree(p); p = nullptr; }
+  T* release() { T* q = p; p = nullptr; return q; }
+  operator T*() const { return p; }
+};
 
 struct mfem_comm_s;
 
@@ -179,32 +195,12 @@ struct mfem_csr_s {
   int symp_p0, symp_p1;     // regular lattice planes [p0, p1) (plane = row / PL): the rows the sweep computes
   int symp_NS, symp_NPk;    // strips of 4 lines, patches of 32 points per line
   double* symp_vals;        // not owned (solver workspace, behind ell_vals): [plane - p0][patch][27 x 128 + edge block]; set while dia_kernel is the patch sweep
-  // row-sorted sliced ELL for rows of uneven length (spmv_sell.hip): sell_state 0 = not planned, -1 = no, 1 = ready
-  int sell_state;
-  int64_t sell_total, sell_nblk;
-  int64_t sell_nb_int;      // leading blocks without a ghost-reading row (= sell_nblk for a pattern without ghost columns): the interior part of a split SpMV
-  int32_t* sell_rowid;      // owned: sorted position -> row
-  int64_t* sell_ptr;        // owned: [nblk + 1] start of each 128-row block in the sliced arrays
-  int32_t* sell_cols;       // owned, [sell_total], 0-based
-  int32_t* sell_flags;      // owned, [nblk]: 1 = all 128 rows share one diagonal list
-  int32_t* sell_off;        // owned, [sell_total / 128]: that list, at ptr[b] / 128
-  int32_t sell_regular_blocks;
-  // field-periodic blocks (round 6): a field-major multi-field matrix repeats the node list of a row once per column field, shifted by the rows of a field;
-  // a block whose 128 rows have one length K = F * P and columns col[f * P + t] = col[t] + f * shift reads the first P slots' columns only
-  int32_t lat27_det;            // the bound copy of the hex-27 tiles is in the deterministic (lane = row, phase-major) form
-  int32_t sell_fields;          // F (0: none found)
-  int64_t sell_shift;           // column shift between two fields
-  int32_t sell_periodic_blocks;
-  int32_t sell_sig_sorted;      // 1: the diagonal-list signature took part in the row sort (lattice patterns); 0: mesh order within a length (unstructured)
-  // node-blocked form (round 6, "BSELL"): a field-major F-field matrix whose F rows of a node share the node's coupling list (every FEM pattern of
-  // mfem_pattern_build) -- a lane owns a NODE: per coupled node one column index, F gathers of x and F x F values.  bsell_F > 0: the sliced arrays are
-  // sell_rowid = sorted position -> node, sell_ptr = [node blocks + 1] in node slots x 64, sell_cols = node-level columns, sell_total = value entries
-  int32_t bsell_F;
-  int64_t bsell_ncp, bsell_slots;
-  const double* sell_src;
-  double* sell_vals;        // not owned (solver workspace), [sell_total]
+  // solver layout mode 3 for rows of uneven length: the row-sorted sliced layout (spmv_sell.hip) or its node-blocked form (spmv_bsell.hip) -- sell.form
+  // tells which, and each form has its own members; sell.state 0 = not planned, -1 = no, 1 = ready.  The record and the decisions: sell_decide.h
+  SellLayout sell;
   // symmetric lattice-tile layout of the hex-27 lattice matrix (spmv_lat27.hip): lat27_state 0 = not inspected, -1 = no, 1 = the pattern is the stencil
   int lat27_state;
+  int32_t lat27_det;        // the bound copy of the hex-27 tiles is in the deterministic (lane = row, phase-major) form
   const double* lat27_src;
   const double* lat27_dsc;  // not owned: right Jacobi scaling applied to x while it is staged (nullptr: none)
   double* lat27_vals;       // not owned (solver workspace): the stored (diagonal + upper) entries, unit by unit
@@ -284,7 +280,7 @@ int mfem_spmv_lat27_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* val
                            double beta, const double* dotw, double* partials, int* n_partials, const int32_t* done_flag, int part);
 int64_t mfem_lat27_design_bytes(const mfem_csr_s* A);
 int64_t mfem_lat27_entries(const mfem_csr_s* A);
-int mfem_node_block_fields(mfem_context_s* ctx, mfem_csr_s* A);  // fills A->nb_F (spmv_sell.hip)
+int mfem_node_block_fields(mfem_context_s* ctx, mfem_csr_s* A);  // fills A->nb_F (spmv_bsell.hip)
 int mfem_spmv_sell_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, const double* x, double* y, double alpha,
                           double beta, const double* dotw, double* partials, int* n_partials, const int32_t* done_flag, int part);
 int mfem_ell_diag(mfem_context_s* ctx, mfem_csr_s* A, double* d);
@@ -303,7 +299,7 @@ __attribute__((visibility("hidden"))) CsrKnobs mfem_csr_knobs();  // what mfem_d
 
 // The solver layouts of a pattern (layout.hip): which copy of the values a solve runs on, and its binding and release.  The values are the
 // mode numbers of mfem_csr_solver_layout: the CSR tile kernel on the caller's values (no copy), slot-major copy with explicit columns / with
-// diagonal-slotted regular blocks (spmv_ell.hip, spmv_dia.hip and the sweeps of spmv_sym.hip), row-sorted sliced ELL (spmv_sell.hip), symmetric lattice tiles (spmv_lat27.hip, spmv_lat8.hip)
+// diagonal-slotted regular blocks (spmv_ell.hip, spmv_dia.hip and the sweeps of spmv_sym.hip), row-sorted sliced ELL or its node-blocked form (spmv_sell.hip, spmv_bsell.hip), symmetric lattice tiles (spmv_lat27.hip, spmv_lat8.hip)
 enum mfem_layout : int32_t { MFEM_LAYOUT_CSR = 0, MFEM_LAYOUT_ELL = 1, MFEM_LAYOUT_DIA = 2, MFEM_LAYOUT_SELL = 3, MFEM_LAYOUT_LAT27 = 4, MFEM_LAYOUT_LAT8 = 5 };
 // What a pattern offers a solve: a tile layout (taken if the values pass its symmetry probe) and a row layout, each with the workspace bytes of
 // its copy (MFEM_LAYOUT_CSR, 0: none)

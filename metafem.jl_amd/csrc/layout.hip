@@ -57,7 +57,7 @@ mfem_layout mfem_layout_bound(const mfem_csr_s* A, const double* vals) {
   if (A->lat8_vals && vals == A->lat8_src) return MFEM_LAYOUT_LAT8;
   if (A->ell_vals && vals == A->ell_src) return A->ell_bound_mode == 2 ? MFEM_LAYOUT_DIA : MFEM_LAYOUT_ELL;
   if (A->lat27_vals && vals == A->lat27_src) return MFEM_LAYOUT_LAT27;
-  if (A->sell_vals && vals == A->sell_src) return MFEM_LAYOUT_SELL;
+  if (A->sell.vals && vals == A->sell.src) return MFEM_LAYOUT_SELL;
   return MFEM_LAYOUT_CSR;
 }
 
@@ -93,7 +93,7 @@ extern "C" int mfem_csr_solver_layout(mfem_context ctx, mfem_csr A, int32_t* mod
   const bool ell = m == MFEM_LAYOUT_ELL || m == MFEM_LAYOUT_DIA;
   if (mode) *mode = m;
   if (slots) *slots = ell ? A->ell_K : m >= MFEM_LAYOUT_SELL ? A->max_row_nnz : 0;
-  if (padded_rows) *padded_rows = ell ? A->ell_npad : m == MFEM_LAYOUT_SELL ? (A->bsell_F > 0 ? A->sell_nblk * 64 * A->bsell_F : A->sell_nblk * 128) : 0;
+  if (padded_rows) *padded_rows = ell ? A->ell_npad : m == MFEM_LAYOUT_SELL ? sell_padded_rows(A->sell) : 0;
   if (regular_rows) *regular_rows = m == MFEM_LAYOUT_DIA ? (int64_t)A->dia_regular_blocks * 128 : 0;
   return MFEM_OK;
 } MFEM_API_CATCH("mfem_csr_solver_layout")

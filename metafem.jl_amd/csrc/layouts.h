@@ -1,5 +1,5 @@
 // The per-layout planning, binding, release and accounting of the solver layouts.  Internal to layout.hip, which chooses among them, and to the
-// files that implement them (spmv_ell.hip with spmv_dia.hip, spmv_sym.hip; spmv_sell.hip; spmv_lat27.hip; spmv_lat8.hip): every
+// files that implement them (spmv_ell.hip with spmv_dia.hip, spmv_sym.hip; spmv_sell.hip with spmv_bsell.hip; spmv_lat27.hip; spmv_lat8.hip): every
 // other file goes through mfem_layout_* (common.h).  Accounting of the tiles: mfem_lat27_entries / _design_bytes and the lat8 twins (common.h).
 #pragma once
 #include "common.h"

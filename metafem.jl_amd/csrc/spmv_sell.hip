@@ -1,6 +1,7 @@
 // Row-sorted sliced ELL (SELL-128-sigma with sigma = n) for the Krylov loop on matrices whose rows are NOT of near-uniform
 // length -- hex-27 (27 / 45 / 75 / 125 entries per row depending on the node type) and every unstructured mesh.  Solver layout
 // mode 3; the uniform case is spmv_ell.hip (mode 1) and spmv_dia.hip with its sweeps (mode 2), the caller-facing contract stays CSR.
+// A field-major multi-field matrix on an unstructured mesh takes the node-blocked form of this layout instead: spmv_bsell.hip.
 //
 //   * inspector (once per pattern): rows are stably sorted by decreasing length (hipCUB radix sort of (max_len - len, row));
 //     rows of equal length keep their mesh order, so the x gathers of a 128-row block stay as local as in CSR order.  Block b
@@ -12,44 +13,27 @@
 //   * per solve: the working values are copied into that layout (one pass, like the reference's K_total[K_val_ids] gather).
 //   * SpMV: a wave owns a block, a lane two neighbouring sorted rows; value / column streams are unit-stride 16-byte / 8-byte
 //     loads, the row sum runs in registers in slot (= column) order, and y is written through the row permutation.
+// Every host decision -- eligibility, key layout, padding limits, thresholds, which instantiation a knob value gets -- is in sell_decide.h.
 #include <hipcub/hipcub.hpp>
 
 #include "blas1.h"
-#include "layouts.h"
+#include "spmv_sell.h"
 
-#define SELL_B 128
 typedef double s_d2 __attribute__((ext_vector_type(2)));
 typedef int s_i2 __attribute__((ext_vector_type(2)));
 
-extern std::atomic<int64_t> g_layout_min_rows_cols;  // spmv_ell.hip
-static std::atomic<int> g_sell_enable{1};
-static std::atomic<int> g_sell_offsets{1};  // blocks with one diagonal list skip their column stream
-static std::atomic<int> g_sell_window_log2{0};
-static std::atomic<int> g_sell_unroll{5};   // slots in flight per lane (bits 16-20 of mfem_debug_set_sell; 0 = default)
-static std::atomic<int> g_sell_wg_per_cu{8};
-static std::atomic<int> g_sell_region{0};   // edge of the lattice regions of the row sort (bits 4-7 of mfem_debug_set_sell x 8; 0 = global sort)
-static std::atomic<int> g_sell_xcd{0};      // bit 2: every XCD walks a contiguous eighth of the block list
-static std::atomic<int> g_sell_per_u{0};    // bits 21-22: node slots in flight in a field-periodic block of three fields (0: 3 -- the default --, 1: 2, 2: 4)
-static std::atomic<int> g_sell_periodic{1}; // bit 3: 0 = field-periodic blocks read their whole column stream (round 6 A/B)
-extern "C" int64_t mfem_debug_sell_periodic_blocks(mfem_csr A) { return A ? (int64_t)A->sell_periodic_blocks * (A->sell_fields > 0 ? 1 : 0) : -1; }
-extern "C" int mfem_debug_set_sell(int enable) try {  // bit 0: layout on/off; bit 1: always read explicit columns
+static std::atomic<int> g_sell_word{SELL_WORD_DEFAULT};  // the word of mfem_debug_set_sell (fields: SellKnobs)
+SellKnobs mfem_sell_knobs() { return sell_knobs_decode(g_sell_word); }
+extern "C" int mfem_debug_set_sell(int enable) try {
   ++mfem_debug_epoch;
-  g_sell_enable = enable & 1;
-  g_sell_offsets = (enable & 2) ? 0 : 1;
-  g_sell_xcd = (enable & 4) ? 1 : 0;
-  g_sell_periodic = (enable & 8) ? 0 : 1;
-  g_sell_per_u = (enable >> 21) & 3;
-  g_sell_region = ((enable >> 4) & 15) * 8;
-  g_sell_window_log2 = (enable >> 8) & 63;
-  g_sell_unroll = ((enable >> 16) & 31) ? ((enable >> 16) & 31) : 5;
-  g_sell_wg_per_cu = ((enable >> 24) & 31) ? ((enable >> 24) & 31) : 8;  // rows are sorted within windows of 2^w consecutive rows (0 = over the whole matrix)
+  g_sell_word = enable;
   return MFEM_OK;
 } MFEM_API_CATCH("mfem_debug_set_sell")
-
-struct SellRegions {  // lattice regions of the row sort (R = 0: none)
-  int R;
-  int64_t n_nodes, PL, m2, nri, nrj, nrk;
-};
+// (on a node-blocked pattern: every block reads one column per node)
+extern "C" int64_t mfem_debug_sell_periodic_blocks(mfem_csr A) {
+  if (!A) return -1;
+  return A->sell.form == SELL_NODE_BLOCKED ? (int64_t)(int32_t)A->sell.nblk : (int64_t)A->sell.rows.periodic_blocks * (A->sell.rows.fields > 0 ? 1 : 0);
+}
 
 template <typename RP>
 __global__ __launch_bounds__(MFEM_BLOCK) void k_sell_keys(int64_t n, const RP* __restrict__ rowptr, const int32_t* __restrict__ col,
@@ -302,296 +286,6 @@ __device__ __forceinline__ void sell_periodic_block(int Kb, int64_t shift, const
   }
 }
 
-// =====================================================================================================================================================
-// Node-blocked sliced layout ("BSELL", round 6) for field-major multi-field matrices on unstructured meshes: unknown (f, i) = f * ncp + i, and the rows
-// (0, i) .. (F - 1, i) of node i all list the nodes coupled to i, once per column field (what mfem_pattern_build makes for n_fields fields; checked entry
-// by entry by k_bsell_check).  The row-sorted layout above gives every ROW a lane: per value it reads a third of a column index (field-periodic blocks)
-// and gathers one x entry -- on hex-20 elasticity 96^3 the product moved 21.2 GB for 17.7 by design (x gathers that miss the L2s) at the HBM copy rate.
-// Here a lane owns a NODE: per coupled node ONE column index, F gathers of x and F x F values for the node's F row sums -- a ninth of the column stream,
-// a third of the gathers.  Nodes are stably sorted by their number of coupled nodes; a block is 64 nodes; slot t of a block holds, for each of its nodes,
-// the F x F values towards the node's t-th coupled node as F * F unit-stride runs of 64 doubles.
-// =====================================================================================================================================================
-static std::atomic<int> g_bsell_fill_quads{0};  // mfem_debug_set("bsell", 3): the layout copy by lane quads per row (the first form) instead of the LDS transpose
-static std::atomic<int> g_bsell_enable{1};  // bit 9 of mfem_debug_set_sell's word... (own key: mfem_debug_set("bsell", on))
-static std::atomic<long long> g_bsell_spmv_count{0};
-extern "C" int mfem_debug_set_bsell(int on) {
-  ++mfem_debug_epoch;
-  g_bsell_enable = (on & 1) ? 1 : 0;
-  g_bsell_fill_quads = (on & 2) ? 1 : 0;
-  return MFEM_OK;
-}
-extern "C" long long mfem_debug_bsell_spmv_count(void) { return g_bsell_spmv_count; }
-extern "C" int mfem_debug_bsell_fields(mfem_csr A) { return A ? A->bsell_F : -1; }
-
-// bad[0] != 0: some node's rows do not have the node-blocked form
-template <typename RP>
-__global__ __launch_bounds__(MFEM_BLOCK) void k_bsell_check(int64_t ncp, int F, const RP* __restrict__ rowptr, const int32_t* __restrict__ col, int base,
-                                                              int32_t* __restrict__ bad) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < ncp; i += stride) {
-    const int64_t lo0 = (int64_t)rowptr[i] - base;
-    const int len = (int)((int64_t)rowptr[i + 1] - base - lo0);
-    bool ok = len % F == 0;
-    const int L = len / F;
-    for (int t = 0; ok && t < L; ++t) {
-      const int64_t c = (int64_t)col[lo0 + t] - base;
-      ok = c >= 0 && c < ncp;
-    }
-    for (int f = 0; ok && f < F; ++f) {
-      const int64_t lo = (int64_t)rowptr[(int64_t)f * ncp + i] - base;
-      ok = (int)((int64_t)rowptr[(int64_t)f * ncp + i + 1] - base - lo) == len;
-      for (int g = 0; ok && g < F; ++g)
-        for (int t = 0; ok && t < L; ++t) ok = (int64_t)col[lo + (int64_t)g * L + t] == (int64_t)col[lo0 + t] + (int64_t)g * ncp;
-    }
-    if (!ok) *bad = 1;
-  }
-}
-template <typename RP>
-__global__ __launch_bounds__(MFEM_BLOCK) void k_bsell_keys(int64_t ncp, int F, int maxL, const RP* __restrict__ rowptr, uint32_t* __restrict__ keys,
-                                                             int32_t* __restrict__ ids) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < ncp; i += stride) {
-    keys[i] = (uint32_t)(maxL - (int)(((int64_t)rowptr[i + 1] - (int64_t)rowptr[i]) / F));
-    ids[i] = (int32_t)i;
-  }
-}
-// node slots x 64 of every block (its first node is its longest)
-template <typename RP>
-__global__ __launch_bounds__(MFEM_BLOCK) void k_bsell_block_sizes(int64_t nblk, int F, const RP* __restrict__ rowptr, const int32_t* __restrict__ nodeid,
-                                                                    int64_t* __restrict__ sizes) {
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; b < nblk; b += stride) {
-    const int64_t i = nodeid[b * 64];
-    sizes[b] = ((int64_t)rowptr[i + 1] - (int64_t)rowptr[i]) / F * 64;
-  }
-}
-// node-level columns, 0-based (padding: the node itself, with zero values)
-template <typename RP>
-__global__ __launch_bounds__(MFEM_BLOCK) void k_bsell_cols(int64_t ncp, int64_t nblk, int F, const RP* __restrict__ rowptr, const int32_t* __restrict__ col,
-                                                             int base, const int32_t* __restrict__ nodeid, const int64_t* __restrict__ ptr,
-                                                             int32_t* __restrict__ out) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t b = wave; b < nblk; b += nwaves) {
-    const int64_t p0 = ptr[b];
-    const int Kb = (int)((ptr[b + 1] - p0) / 64);
-    const int64_t ns = b * 64 + lane;
-    int64_t lo = 0, i = 0;
-    int L = 0;
-    if (ns < ncp) {
-      i = nodeid[ns];
-      lo = (int64_t)rowptr[i] - base;
-      L = (int)(((int64_t)rowptr[i + 1] - base - lo) / F);
-    }
-    for (int t = 0; t < Kb; ++t) out[p0 + (int64_t)t * 64 + lane] = t < L ? col[lo + t] - base : (int32_t)i;
-  }
-}
-// values into the node-blocked layout (once per solve).  A lane quad per CSR row, 16 consecutive sorted nodes of one row field per wave pass: the quad
-// reads 32 contiguous bytes of its row per step, the 16 rows' stores of one slot are 128 contiguous bytes.  dsc != nullptr: entry / dsc[its column].
-template <typename RP, int F>
-__global__ __launch_bounds__(MFEM_BLOCK) void k_bsell_fill(int64_t ncp, int64_t nblk, const RP* __restrict__ rowptr, const int32_t* __restrict__ nodeid,
-                                                             const int64_t* __restrict__ ptr, const double* __restrict__ src, int base,
-                                                             double* __restrict__ out, const int32_t* __restrict__ col, const double* __restrict__ dsc) {
-  const int lane = threadIdx.x & 63, g4 = lane & 3, q = lane >> 2;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t p = wave; p < nblk * F * 4; p += nwaves) {
-    const int64_t b = p / (F * 4);
-    const int rem = (int)(p - b * (F * 4)), f = rem >> 2, sub = rem & 3;
-    const int64_t p0 = ptr[b];
-    const int Kb = (int)((ptr[b + 1] - p0) / 64);
-    const int nl = sub * 16 + q;  // the node's lane in the product kernel
-    const int64_t ns = b * 64 + nl;
-    int64_t lo = 0;
-    int L = 0;
-    if (ns < ncp) {
-      const int64_t i = nodeid[ns];
-      lo = (int64_t)rowptr[(int64_t)f * ncp + i] - base;
-      L = (int)(((int64_t)rowptr[(int64_t)f * ncp + i + 1] - base - lo) / F);
-    }
-    double* o = out + p0 * (F * F) + (int64_t)(f * F) * 64 + nl;
-#pragma unroll
-    for (int g = 0; g < F; ++g) {
-      const double* sg = src + lo + (int64_t)g * L;
-      const int32_t* cg = col + lo + (int64_t)g * L;
-      double* og = o + (int64_t)g * 64;
-      int t = g4;
-      for (; t + 28 < Kb; t += 32) {  // eight loads of a lane in flight before the first store (four: 17.0 ms per bind of the hex-20 elasticity matrix at 96^3)
-        double t8[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int tu = t + 4 * u;
-          t8[u] = tu < L ? (dsc ? sg[tu] / dsc[cg[tu] - base] : sg[tu]) : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) og[(int64_t)(t + 4 * u) * (64 * F * F)] = t8[u];
-      }
-      for (; t + 12 < Kb; t += 16) {
-        double t4[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int tu = t + 4 * u;
-          t4[u] = tu < L ? (dsc ? sg[tu] / dsc[cg[tu] - base] : sg[tu]) : 0.0;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) og[(int64_t)(t + 4 * u) * (64 * F * F)] = t4[u];
-      }
-      for (; t < Kb; t += 4) og[(int64_t)t * (64 * F * F)] = t < L ? (dsc ? sg[t] / dsc[cg[t] - base] : sg[t]) : 0.0;
-    }
-  }
-}
-
-// The same copy through an LDS transpose (round 6, for coupling lists of up to BSELL_T_MAXL nodes): a workgroup takes (block, row field f, column field g);
-// its waves read the 64 nodes' g-segments of row (f, node) -- L contiguous values each, unit-stride lanes -- into LDS [node][t], then every slot t leaves
-// as ONE 512-byte run of 64 lanes.  The quad-per-row form above reads 32-byte pieces and writes 128-byte pieces, 8 bytes per lane: 16.3 ms for the 15 GB
-// of the hex-20 elasticity matrix at 96^3 (1.8 TB/s).
-#define BSELL_T_MAXL 127
-// (a first version with a workgroup per (block, f, g) ran at 15.3 ms: the copy is bound by the 1.9e9 gathers of dsc[column], not by its access pattern --
-// the divisor depends on the COLUMN (g, coupled node) alone, so a workgroup now takes (block, g), gathers the divisors once into registers and walks the F
-// row fields with them: a third of the gathers)
-template <typename RP, int F>
-__global__ __launch_bounds__(MFEM_BLOCK) void k_bsell_fill_t(int64_t ncp, int64_t nblk, const RP* __restrict__ rowptr, const int32_t* __restrict__ nodeid,
-                                                               const int64_t* __restrict__ ptr, const double* __restrict__ src, int base,
-                                                               double* __restrict__ out, const int32_t* __restrict__ col, const double* __restrict__ dsc,
-                                                               int ldl) {
-  extern __shared__ double tl[];  // [64][ldl] values, then [F][64] segment starts (int64), then [64] lengths (int)
-  int64_t* s_lo = reinterpret_cast<int64_t*>(tl + (size_t)64 * ldl);
-  int* s_L = reinterpret_cast<int*>(s_lo + F * 64);
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  for (int64_t job = blockIdx.x; job < nblk * F; job += gridDim.x) {
-    const int64_t b = job / F;
-    const int g = (int)(job - b * F);
-    const int64_t p0 = ptr[b];
-    const int Kb = (int)((ptr[b + 1] - p0) / 64);
-    if (tid < 64) {
-      const int64_t ns = b * 64 + tid;
-      int L = 0;
-      int64_t i = 0;
-      if (ns < ncp) {
-        i = nodeid[ns];
-        L = (int)(((int64_t)rowptr[i + 1] - (int64_t)rowptr[i]) / F);
-      }
-#pragma unroll
-      for (int f = 0; f < F; ++f) s_lo[f * 64 + tid] = ns < ncp ? (int64_t)rowptr[(int64_t)f * ncp + i] - base + (int64_t)g * L : 0;
-      s_L[tid] = L;
-    }
-    __syncthreads();
-    // the divisors of this wave's 16 nodes x 2 entries per lane (columns: from the node's first row -- every row field lists the same)
-    double dv[4][4][2];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int nl = w * 4 + 16 * q + u;
-        const int64_t lo = s_lo[nl];
-        const int L = s_L[nl];
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int t = lane + 64 * h;
-          dv[q][u][h] = (dsc && t < L) ? dsc[col[lo + t] - base] : 1.0;
-        }
-      }
-    for (int f = 0; f < F; ++f) {
-      // phase 1: a wave per node, four nodes' loads in flight
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        double v[4][2];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int nl = w * 4 + 16 * q + u;
-          const int64_t lo = s_lo[f * 64 + nl];
-          const int L = s_L[nl];
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const int t = lane + 64 * h;
-            v[u][h] = t < L ? src[lo + t] : 0.0;
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const int t = lane + 64 * h;
-            if (t < Kb) tl[(size_t)(w * 4 + 16 * q + u) * ldl + t] = dsc ? v[u][h] / dv[q][u][h] : v[u][h];  // (zeros behind a node's own list: the block's padding)
-          }
-      }
-      __syncthreads();
-      // phase 2: a slot per wave trip, lane = node
-      double* o = out + p0 * (F * F) + (int64_t)(f * F + g) * 64 + lane;
-      for (int t = w; t < Kb; t += 4) o[(int64_t)t * (64 * F * F)] = tl[(size_t)lane * ldl + t];
-      __syncthreads();
-    }
-  }
-}
-
-// y = alpha A x + beta y: a wave per block of 64 nodes, a lane per node, U node slots (their F x F values, column and F x entries) in flight
-template <int F, int U>
-__global__ __launch_bounds__(MFEM_BLOCK) void k_spmv_bsell(int64_t ncp, int64_t nblk, const int64_t* __restrict__ ptr, const int32_t* __restrict__ nodeid,
-                                                             const int32_t* __restrict__ cols, const double* __restrict__ vals, const double* __restrict__ x,
-                                                             double* __restrict__ y, double alpha, double beta, const double* __restrict__ dotw,
-                                                             double* __restrict__ partials, const int32_t* __restrict__ done_flag) {
-  __shared__ double red[4];
-  if (done_flag && done_flag[0]) return;
-  double dot_acc = 0.0;
-  const int lane = threadIdx.x & 63;
-  const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  constexpr int64_t SS = 64 * F * F;  // doubles per node slot of a block
-  for (int64_t b = wave; b < nblk; b += nwaves) {
-    const int64_t p0 = ptr[b];
-    const int Kb = (int)((ptr[b + 1] - p0) / 64);
-    const double* v = vals + p0 * (F * F) + lane;
-    const int32_t* c = cols + p0 + lane;
-    const int64_t ns = b * 64 + lane;
-    const int64_t node = ns < ncp ? nodeid[ns] : 0;
-    double acc[F];
-#pragma unroll
-    for (int f = 0; f < F; ++f) acc[f] = 0.0;
-    int t = 0;
-    for (; t + U <= Kb; t += U) {
-      int32_t cu[U];
-      double vv[U][F * F], xx[U][F];
-#pragma unroll
-      for (int u = 0; u < U; ++u) cu[u] = __builtin_nontemporal_load(c + (int64_t)(t + u) * 64);
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int m = 0; m < F * F; ++m) vv[u][m] = __builtin_nontemporal_load(v + (int64_t)(t + u) * SS + m * 64);
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int g = 0; g < F; ++g) xx[u][g] = x[(int64_t)cu[u] + (int64_t)g * ncp];
-#pragma unroll
-      for (int u = 0; u < U; ++u)
-#pragma unroll
-        for (int f = 0; f < F; ++f)
-#pragma unroll
-          for (int g = 0; g < F; ++g) acc[f] += vv[u][f * F + g] * xx[u][g];
-    }
-    for (; t < Kb; ++t) {
-      const int64_t cc = c[(int64_t)t * 64];
-#pragma unroll
-      for (int g = 0; g < F; ++g) {
-        const double xg = x[cc + (int64_t)g * ncp];
-#pragma unroll
-        for (int f = 0; f < F; ++f) acc[f] += __builtin_nontemporal_load(v + (int64_t)t * SS + (f * F + g) * 64) * xg;
-      }
-    }
-    if (ns < ncp) {
-#pragma unroll
-      for (int f = 0; f < F; ++f) {
-        const int64_t r = (int64_t)f * ncp + node;
-        double yv = alpha * acc[f];
-        if (beta != 0.0) yv += beta * y[r];
-        y[r] = yv;
-        if (dotw) dot_acc += yv * dotw[r];
-      }
-    }
-  }
-  if (partials) {
-    const double bsum = block_reduce_sum(dot_acc, red);
-    if (threadIdx.x == 0) partials[blockIdx.x] = bsum;
-  }
-}
-
 template <int SELL_U>
 __global__ __launch_bounds__(MFEM_BLOCK) void k_spmv_sell(int64_t n, int64_t nblk, const int64_t* __restrict__ ptr,
                                                             const int32_t* __restrict__ rowid, const int32_t* __restrict__ flags,
@@ -704,449 +398,258 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_spmv_sell(int64_t n, int64_t nbl
   }
 }
 
-#define SELL_CHECK(expr)                                                                    \
-  do {                                                                                      \
-    hipError_t _e = (expr);                                                                 \
-    if (_e != hipSuccess) {                                                                 \
-      mfem_set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(_e));  \
-      rc = MFEM_ERR_HIP;                                                                    \
-      goto done;                                                                            \
-    }                                                                                       \
-  } while (0)
+template <typename Key>
+int mfem_sell_sort_blocks(mfem_context_s* ctx, SellSortBufs<Key>& B, int64_t count, int bits, int64_t nblk, const SellBlockSizes& block_sizes,
+                          int64_t* total) {
+  DevBuf<char> tmp;
+  size_t tb = 0, tb2 = 0;
+  MFEM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, B.keys.p, B.keys2.p, B.ids.p, B.sorted.p, (int)count, 0, bits, ctx->stream));
+  MFEM_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, B.sizes.p, B.ptr.p, (int)(nblk + 1), ctx->stream));
+  if (tb2 > tb) tb = tb2;
+  MFEM_CHECK_HIP(tmp.alloc(tb));
+  MFEM_CHECK_HIP(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, B.keys.p, B.keys2.p, B.ids.p, B.sorted.p, (int)count, 0, bits, ctx->stream));
+  MFEM_CHECK_HIP(hipMemsetAsync(B.sizes.p, 0, sizeof(int64_t) * (size_t)(nblk + 1), ctx->stream));
+  block_sizes(B.sorted.p, B.sizes.p);
+  MFEM_CHECK_LAUNCH();
+  MFEM_CHECK_HIP(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, B.sizes.p, B.ptr.p, (int)(nblk + 1), ctx->stream));
+  MFEM_CHECK_HIP(hipMemcpyAsync(total, B.ptr.p + nblk, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+  MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  return MFEM_OK;
+}
+template int mfem_sell_sort_blocks<uint64_t>(mfem_context_s*, SellSortBufs<uint64_t>&, int64_t, int, int64_t, const SellBlockSizes&, int64_t*);
+template int mfem_sell_sort_blocks<uint32_t>(mfem_context_s*, SellSortBufs<uint32_t>&, int64_t, int, int64_t, const SellBlockSizes&, int64_t*);
 
-// A->nb_F: the field count F (4, 3, 2 tried in that order: the largest that fits -- four fields also read as two super-fields of two) for which the
-// pattern is node-blocked, 0 if none.  Once per pattern (the check reads every column index: 61 ms for the 1.9e9 entries of hex-20 elasticity at 96^3).
-int mfem_node_block_fields(mfem_context_s* ctx, mfem_csr_s* A) {
-  if (A->nb_F > 0 || A->nb_checked) return MFEM_OK;
-  A->nb_checked = 1;
-  A->nb_F = 0;
-  if (A->ncols > A->n || A->n < 2 || A->max_row_nnz < 2) return MFEM_OK;
-  const int cand[3] = {4, 3, 2};
-  int32_t* d_bad = ctx->d_flags + 9;
-  for (int ci = 0; ci < 3 && A->nb_F == 0; ++ci) {
-    const int f = cand[ci];
-    if (A->n % f != 0 || A->max_row_nnz % f != 0) continue;
-    const int64_t ncp = A->n / f;
-    MFEM_CHECK_HIP(hipMemsetAsync(d_bad, 0, sizeof(int32_t), ctx->stream));
-    const int grid = mfem_grid_for(ncp, MFEM_BLOCK, ctx->num_cus * 16);
-    if (A->rowptr_bits == 64)
-      hipLaunchKernelGGL(k_bsell_check<int64_t>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, ncp, f, (const int64_t*)A->rowptr, A->colidx, A->index_base, d_bad);
-    else
-      hipLaunchKernelGGL(k_bsell_check<int32_t>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, ncp, f, (const int32_t*)A->rowptr, A->colidx, A->index_base, d_bad);
+// What the stages of the row-sorted plan hand on.  Everything a stage allocates is owned here until sell_plan_rows hands it to the record.
+struct MFEM_SELL_LOCAL SellRowsPlan {
+  SellShape S;
+  SellKnobs K;
+  SellRegions G;
+  int64_t nblk, total;
+  SellSortBufs<uint64_t> B;
+  DevBuf<int32_t> cols, flags, off;
+  SellLayout::Rows R;  // (the counts; its pointers are set at the end)
+};
+static int32_t* sell_counter(mfem_context_s* ctx) { return ctx->d_flags + 9; }  // one-shot device counter of the stages, mirrored in ctx->h_flags[9]
+
+// stage 1: the sort keys (ghost flag | region or window | max_len - len | signature), the identity permutation, the count of ghost-reading rows
+static int sell_plan_keys(mfem_context_s* ctx, const mfem_csr_s* A, SellRowsPlan& W) {
+  const int64_t n = W.S.n;
+  const int grid = mfem_grid_for(n, MFEM_BLOCK, ctx->num_cus * 16);
+  const int rc = W.B.alloc(n, W.nblk);
+  if (rc) return rc;
+  MFEM_CHECK_HIP(hipMemsetAsync(sell_counter(ctx), 0, sizeof(int32_t), ctx->stream));
+  mfem_by_rowptr(A, [&](auto rp) {
+    using RP = decltype(rp);
+    hipLaunchKernelGGL(k_sell_keys<RP>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, n, (const RP*)A->rowptr, A->colidx, A->index_base, A->max_row_nnz,
+                       sell_window_shift(W.K), sell_len_bits(A->max_row_nnz), W.B.keys.p, W.B.ids.p, sell_counter(ctx), W.G);
+  });
+  MFEM_CHECK_LAUNCH();
+  MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 9, sell_counter(ctx), sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  return MFEM_OK;
+}
+// stage 2: signatures that do not repeat (unstructured patterns) stay out of the sort: rows of one length keep their mesh order
+static int sell_plan_signatures(mfem_context_s* ctx, SellRowsPlan& W) {
+  const int64_t n = W.S.n;
+  const int grid = mfem_grid_for(n, MFEM_BLOCK, ctx->num_cus * 16);
+  unsigned long long* d_rep = (unsigned long long*)(void*)W.B.sizes.p;  // (zeroed again by the sort before its own use)
+  unsigned long long h_rep = 0;
+  MFEM_CHECK_HIP(hipMemsetAsync(d_rep, 0, sizeof(unsigned long long), ctx->stream));
+  hipLaunchKernelGGL(k_sell_sig_repeats, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, n, W.B.keys.p, d_rep);
+  MFEM_CHECK_LAUNCH();
+  MFEM_CHECK_HIP(hipMemcpyAsync(&h_rep, d_rep, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+  MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  W.R.sig_sorted = sell_signatures_repeat(n, (int64_t)h_rep) ? 1 : 0;
+  if (!W.R.sig_sorted) {
+    hipLaunchKernelGGL(k_sell_clear_sig, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, n, W.B.keys.p);
     MFEM_CHECK_LAUNCH();
-    MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 9, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    if (ctx->h_flags[9] == 0) A->nb_F = f;
   }
   return MFEM_OK;
 }
-
-// Plans the node-blocked layout if the pattern has its form (F = 4, 3, 2 tried in that order).  A->bsell_F > 0 afterwards: taken.
-static int bsell_plan(mfem_context_s* ctx, mfem_csr_s* A) {
-  A->bsell_F = 0;
-  if (!g_bsell_enable || A->ncols > A->n || A->lat_fields > 0 || A->n < 64 * 4) return MFEM_OK;  // (slab patterns with ghost columns and lattice patterns keep the row-sorted form)
-  int rc = mfem_node_block_fields(ctx, A);
+// stage 3: the sort, K_b * 128 of every block and their prefix sums; then the interior blocks of a split product, from the ghost-reading rows
+static int sell_plan_sort(mfem_context_s* ctx, const mfem_csr_s* A, SellRowsPlan& W) {
+  const int rc = mfem_sell_sort_blocks<uint64_t>(ctx, W.B, W.S.n, sell_key_bits(W.S, W.K, W.G), W.nblk, [&](const int32_t* rowid, int64_t* sizes) {
+    mfem_by_rowptr(A, [&](auto rp) {
+      using RP = decltype(rp);
+      hipLaunchKernelGGL(k_sell_block_sizes<RP>, dim3(mfem_grid_for(W.nblk, MFEM_BLOCK, ctx->num_cus * 16)), dim3(MFEM_BLOCK), 0, ctx->stream, W.S.n, W.nblk,
+                         (const RP*)A->rowptr, rowid, sizes);
+    });
+  }, &W.total);
   if (rc) return rc;
-  const int F = A->nb_F;
-  if (F == 0 || A->n / F < 64) return MFEM_OK;
-  const int64_t ncp = A->n / F, nblk = (ncp + 63) / 64;
-  const int maxL = A->max_row_nnz / F;
-  uint32_t *keys = nullptr, *keys2 = nullptr;
-  int32_t *ids = nullptr, *nodeid = nullptr, *cols = nullptr;
-  int64_t *sizes = nullptr, *ptr = nullptr;
-  void* tmp = nullptr;
-  size_t tb = 0, tb2 = 0;
-  int64_t slots = 0;
-  const int grid = mfem_grid_for(ncp, MFEM_BLOCK, ctx->num_cus * 16);
-  int bits = 1;
-  while ((1 << bits) <= maxL && bits < 31) ++bits;
-  SELL_CHECK(hipMalloc(&keys, sizeof(uint32_t) * (size_t)ncp));
-  SELL_CHECK(hipMalloc(&keys2, sizeof(uint32_t) * (size_t)ncp));
-  SELL_CHECK(hipMalloc(&ids, sizeof(int32_t) * (size_t)ncp));
-  SELL_CHECK(hipMalloc(&nodeid, sizeof(int32_t) * (size_t)ncp));
-  SELL_CHECK(hipMalloc(&sizes, sizeof(int64_t) * (size_t)(nblk + 1)));
-  SELL_CHECK(hipMalloc(&ptr, sizeof(int64_t) * (size_t)(nblk + 1)));
-  if (A->rowptr_bits == 64)
-    hipLaunchKernelGGL(k_bsell_keys<int64_t>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, ncp, F, maxL, (const int64_t*)A->rowptr, keys, ids);
-  else
-    hipLaunchKernelGGL(k_bsell_keys<int32_t>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, ncp, F, maxL, (const int32_t*)A->rowptr, keys, ids);
-  SELL_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys, keys2, ids, nodeid, (int)ncp, 0, bits, ctx->stream));
-  SELL_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, sizes, ptr, (int)(nblk + 1), ctx->stream));
-  if (tb2 > tb) tb = tb2;
-  SELL_CHECK(hipMalloc(&tmp, tb));
-  SELL_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys, keys2, ids, nodeid, (int)ncp, 0, bits, ctx->stream));  // stable: nodes of one length keep their mesh order
-  SELL_CHECK(hipMemsetAsync(sizes, 0, sizeof(int64_t) * (size_t)(nblk + 1), ctx->stream));
-  if (A->rowptr_bits == 64)
-    hipLaunchKernelGGL(k_bsell_block_sizes<int64_t>, dim3(mfem_grid_for(nblk, MFEM_BLOCK, ctx->num_cus * 16)), dim3(MFEM_BLOCK), 0, ctx->stream, nblk, F,
-                       (const int64_t*)A->rowptr, nodeid, sizes);
-  else
-    hipLaunchKernelGGL(k_bsell_block_sizes<int32_t>, dim3(mfem_grid_for(nblk, MFEM_BLOCK, ctx->num_cus * 16)), dim3(MFEM_BLOCK), 0, ctx->stream, nblk, F,
-                       (const int32_t*)A->rowptr, nodeid, sizes);
-  SELL_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, sizes, ptr, (int)(nblk + 1), ctx->stream));
-  SELL_CHECK(hipMemcpyAsync(&slots, ptr + nblk, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  SELL_CHECK(hipStreamSynchronize(ctx->stream));
-  if ((double)slots * F * F <= 1.15 * (double)A->nnz + 128.0 * A->max_row_nnz * F) {
-    SELL_CHECK(hipMalloc(&cols, sizeof(int32_t) * (size_t)(slots > 0 ? slots : 1)));
-    const int g2 = mfem_grid_for(nblk * 64, MFEM_BLOCK, ctx->num_cus * 16);
-    if (A->rowptr_bits == 64)
-      hipLaunchKernelGGL(k_bsell_cols<int64_t>, dim3(g2), dim3(MFEM_BLOCK), 0, ctx->stream, ncp, nblk, F, (const int64_t*)A->rowptr, A->colidx, A->index_base,
-                         nodeid, ptr, cols);
-    else
-      hipLaunchKernelGGL(k_bsell_cols<int32_t>, dim3(g2), dim3(MFEM_BLOCK), 0, ctx->stream, ncp, nblk, F, (const int32_t*)A->rowptr, A->colidx, A->index_base,
-                         nodeid, ptr, cols);
-    if (hipGetLastError() != hipSuccess) {
-      mfem_set_error("k_bsell_cols launch failed");
-      rc = MFEM_ERR_HIP;
-      goto done;
+  W.R.nb_int = sell_nb_int(W.S, ctx->h_flags[9]);
+  return MFEM_OK;
+}
+// stage 4: the columns in the sliced layout
+static int sell_plan_cols(mfem_context_s* ctx, const mfem_csr_s* A, SellRowsPlan& W) {
+  MFEM_CHECK_HIP(W.cols.alloc((size_t)W.total));
+  const int g2 = mfem_grid_for(8 * W.nblk * 64, MFEM_BLOCK, ctx->num_cus * 16);
+  mfem_by_rowptr(A, [&](auto rp) {
+    using RP = decltype(rp);
+    hipLaunchKernelGGL((k_sell_fill<RP, int32_t, true>), dim3(g2), dim3(MFEM_BLOCK), 0, ctx->stream, W.S.n, W.nblk, (const RP*)A->rowptr, W.B.sorted.p,
+                       W.B.ptr.p, A->colidx, A->index_base, W.cols.p, (const int32_t*)nullptr, (const double*)nullptr);
+  });
+  MFEM_CHECK_LAUNCH();
+  return MFEM_OK;
+}
+// reads back the block count a stage's kernel left in the counter
+static int sell_read_counter(mfem_context_s* ctx, int32_t* count) {
+  MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 9, sell_counter(ctx), sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  *count = ctx->h_flags[9];
+  return MFEM_OK;
+}
+// stage 5: blocks with a single diagonal list
+static int sell_plan_regular(mfem_context_s* ctx, const mfem_csr_s* A, SellRowsPlan& W) {
+  MFEM_CHECK_HIP(W.flags.alloc((size_t)W.nblk));
+  MFEM_CHECK_HIP(W.off.alloc((size_t)(W.total / SELL_B + 1)));
+  MFEM_CHECK_HIP(hipMemsetAsync(sell_counter(ctx), 0, sizeof(int32_t), ctx->stream));
+  mfem_by_rowptr(A, [&](auto rp) {
+    using RP = decltype(rp);
+    hipLaunchKernelGGL(k_sell_block_flags<RP>, dim3(sell_inspect_grid(W.nblk, ctx->num_cus)), dim3(SELL_B), 0, ctx->stream, W.S.n, W.nblk, (const RP*)A->rowptr,
+                       A->colidx, A->index_base, W.B.sorted.p, W.B.ptr.p, W.flags.p, W.off.p, sell_counter(ctx));
+  });
+  MFEM_CHECK_LAUNCH();
+  return sell_read_counter(ctx, &W.R.regular_blocks);
+}
+// stage 6: field-periodic blocks among the others (k_sell_block_periodic), for the first field count that covers enough of the blocks
+static int sell_plan_periodic(mfem_context_s* ctx, const mfem_csr_s* A, SellRowsPlan& W) {
+  if (!sell_periodic_may_try(W.S, W.K, W.R.regular_blocks, W.nblk)) return MFEM_OK;
+  const int g3 = sell_inspect_grid(W.nblk, ctx->num_cus);
+  for (int ci = 0; ci < 3 && W.R.fields == 0; ++ci) {
+    const int F = SELL_PERIODIC_FIELDS[ci];
+    if (!sell_fields_divide(W.S, F)) continue;
+    MFEM_CHECK_HIP(hipMemsetAsync(sell_counter(ctx), 0, sizeof(int32_t), ctx->stream));
+    mfem_by_rowptr(A, [&](auto rp) {
+      using RP = decltype(rp);
+      hipLaunchKernelGGL(k_sell_block_periodic<RP>, dim3(g3), dim3(SELL_B), 0, ctx->stream, W.S.n, W.nblk, (const RP*)A->rowptr, A->colidx, A->index_base,
+                         W.B.sorted.p, W.B.ptr.p, F, W.S.n / F, W.flags.p, sell_counter(ctx));
+    });
+    MFEM_CHECK_LAUNCH();
+    int32_t count = 0;
+    const int rc = sell_read_counter(ctx, &count);
+    if (rc) return rc;
+    if (sell_periodic_taken(W.nblk, count)) {
+      W.R.fields = F;
+      W.R.shift = W.S.n / F;
+      W.R.periodic_blocks = count;
+    } else if (count > 0) {  // (a few blocks happened to fit: not taken -- back to "generic")
+      hipLaunchKernelGGL(k_sell_clear_flag2, dim3(g3), dim3(MFEM_BLOCK), 0, ctx->stream, W.nblk, W.flags.p);
+      MFEM_CHECK_LAUNCH();
     }
-    A->sell_rowid = nodeid;
-    A->sell_ptr = ptr;
-    A->sell_cols = cols;
-    A->sell_flags = nullptr;
-    A->sell_off = nullptr;
-    A->sell_total = slots * F * F;
-    A->sell_nblk = nblk;
-    A->sell_nb_int = nblk;
-    A->sell_regular_blocks = 0;
-    A->sell_fields = F;
-    A->sell_shift = ncp;
-    A->sell_periodic_blocks = (int32_t)nblk;
-    A->sell_sig_sorted = 0;
-    A->bsell_F = F;
-    A->bsell_ncp = ncp;
-    A->bsell_slots = slots;
-    nodeid = nullptr;
-    ptr = nullptr;
-    cols = nullptr;
   }
-done:
-  if (keys) hipFree(keys);
-  if (keys2) hipFree(keys2);
-  if (ids) hipFree(ids);
-  if (nodeid) hipFree(nodeid);
-  if (sizes) hipFree(sizes);
-  if (ptr) hipFree(ptr);
-  if (cols) hipFree(cols);
-  if (tmp) hipFree(tmp);
-  return rc;
+  return MFEM_OK;
+}
+// The row-sorted plan: fills *L (form SELL_ROW_SORTED) unless the padding is refused.
+static int sell_plan_rows(mfem_context_s* ctx, const mfem_csr_s* A, const SellShape& S, SellLayout* L) {
+  SellRowsPlan W{};
+  W.S = S;
+  W.K = mfem_sell_knobs();
+  W.G = sell_regions(S, W.K);
+  W.nblk = sell_blocks(S.n);
+  int rc = sell_plan_keys(ctx, A, W);
+  if (!rc) rc = sell_plan_signatures(ctx, W);
+  if (!rc) rc = sell_plan_sort(ctx, A, W);
+  if (rc || !sell_padding_ok(S, W.G, W.total)) return rc;
+  rc = sell_plan_cols(ctx, A, W);
+  if (!rc) rc = sell_plan_regular(ctx, A, W);
+  if (!rc) rc = sell_plan_periodic(ctx, A, W);
+  if (rc) return rc;
+  L->form = SELL_ROW_SORTED;
+  L->total = W.total;
+  L->nblk = W.nblk;
+  L->rows = W.R;
+  L->rows.rowid = W.B.sorted.release();
+  L->rows.ptr = W.B.ptr.release();
+  L->rows.cols = W.cols.release();
+  L->rows.flags = W.flags.release();
+  L->rows.off = W.off.release();
+  return MFEM_OK;
 }
 
-
-// sell_state: 0 not planned, -1 not eligible, 1 ready
+// The node-blocked form first (a multi-field matrix on an unstructured mesh), else the row-sorted one.  The record is built aside: the handle
+// gets it whole, and a plan that fails midway leaves the handle as mfem_sell_free does.
 int mfem_sell_plan(mfem_context_s* ctx, mfem_csr_s* A) {
-  if (A->sell_state != 0) return MFEM_OK;
-  if (A->n < g_layout_min_rows_cols) return MFEM_OK;  // launch-bound sizes stay on the CSR tile kernel: do not even sort
-  A->sell_state = -1;
-  if (A->n < SELL_B || A->nnz < 1 || A->max_row_nnz < 1 || A->n >= ((int64_t)1 << 31)) return MFEM_OK;
-  int rc = bsell_plan(ctx, A);  // the node-blocked form first: a multi-field matrix on an unstructured mesh
-  if (rc) return rc;
-  if (A->bsell_F > 0) {
-    A->sell_state = 1;
+  if (A->sell.state != 0) return MFEM_OK;
+  const SellShape S = mfem_sell_shape(A);
+  const int wanted = sell_state_wanted(S);
+  if (wanted != 1) {
+    A->sell.state = wanted;
     return MFEM_OK;
   }
-  const int64_t n = A->n, nblk = (n + SELL_B - 1) / SELL_B;
-  uint64_t *keys = nullptr, *keys2 = nullptr;
-  int32_t *ids = nullptr, *rowid = nullptr;
-  int64_t *sizes = nullptr, *ptr = nullptr;
-  void* tmp = nullptr;
-  size_t tb = 0, tb2 = 0;
-  int64_t total = 0;
-  int32_t n_ghost = 0;
-  int32_t* d_ghost = ctx->d_flags + 9;
-  const bool has_ghosts = A->ncols > A->n;
-  SellRegions G{};
-  uint64_t nwin = 1;
-  const int grid = mfem_grid_for(n, MFEM_BLOCK, ctx->num_cus * 16);
-  int lenbits = 1;
-  while ((1 << lenbits) <= A->max_row_nnz && lenbits < 31) ++lenbits;
-  const int wshift = g_sell_window_log2 > 0 ? g_sell_window_log2.load() : 63;
-  SELL_CHECK(hipMalloc(&keys, sizeof(uint64_t) * (size_t)n));
-  SELL_CHECK(hipMalloc(&ids, sizeof(int32_t) * (size_t)n));
-  SELL_CHECK(hipMalloc(&keys2, sizeof(uint64_t) * (size_t)n));
-  SELL_CHECK(hipMalloc(&rowid, sizeof(int32_t) * (size_t)n));
-  SELL_CHECK(hipMalloc(&sizes, sizeof(int64_t) * (size_t)(nblk + 1)));
-  SELL_CHECK(hipMalloc(&ptr, sizeof(int64_t) * (size_t)(nblk + 1)));
-  SELL_CHECK(hipMemsetAsync(d_ghost, 0, sizeof(int32_t), ctx->stream));
-  if (g_sell_region > 0 && g_sell_window_log2 == 0 && A->lat_m1 > 0 && A->lat_m2 > 0 && A->lat_fields > 0 && n % A->lat_fields == 0 &&
-      (n / A->lat_fields) % ((int64_t)A->lat_m1 * A->lat_m2) == 0) {
-    G.R = g_sell_region;
-    G.n_nodes = n / A->lat_fields;
-    G.PL = (int64_t)A->lat_m1 * A->lat_m2;
-    G.m2 = A->lat_m2;
-    G.nri = (G.n_nodes / G.PL + G.R - 1) / G.R;
-    G.nrj = (A->lat_m1 + G.R - 1) / G.R;
-    G.nrk = (A->lat_m2 + G.R - 1) / G.R;
-    nwin = (uint64_t)A->lat_fields * G.nri * G.nrj * G.nrk;
-  }
-  if (A->rowptr_bits == 64)
-    hipLaunchKernelGGL(k_sell_keys<int64_t>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, n, (const int64_t*)A->rowptr, A->colidx,
-                       A->index_base, A->max_row_nnz, wshift, lenbits, keys, ids, d_ghost, G);
-  else
-    hipLaunchKernelGGL(k_sell_keys<int32_t>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, n, (const int32_t*)A->rowptr, A->colidx,
-                       A->index_base, A->max_row_nnz, wshift, lenbits, keys, ids, d_ghost, G);
-  SELL_CHECK(hipMemcpyAsync(ctx->h_flags + 9, d_ghost, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  {
-    // signatures that do not repeat (unstructured patterns) stay out of the sort: rows of one length keep their mesh order
-    unsigned long long* d_rep = (unsigned long long*)(void*)sizes;  // (zeroed below before its own use)
-    unsigned long long h_rep = 0;
-    SELL_CHECK(hipMemsetAsync(d_rep, 0, sizeof(unsigned long long), ctx->stream));
-    hipLaunchKernelGGL(k_sell_sig_repeats, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, n, keys, d_rep);
-    SELL_CHECK(hipMemcpyAsync(&h_rep, d_rep, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    SELL_CHECK(hipStreamSynchronize(ctx->stream));
-    if ((int64_t)h_rep < n / 8) {
-      hipLaunchKernelGGL(k_sell_clear_sig, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, n, keys);
-      A->sell_sig_sorted = 0;
-    } else {
-      A->sell_sig_sorted = 1;
-    }
-  }
-  {
-    int bits = 32 + lenbits;  // the low word is the signature of the diagonal list
-    if (G.R > 0) {
-      while (bits < 63 && ((nwin - 1) >> (bits - 32 - lenbits))) ++bits;                     // region index on top
-    } else if (wshift < 63)
-      while (bits < 64 && ((uint64_t)(n - 1) >> wshift) >> (bits - 32 - lenbits)) ++bits;  // window index on top
-    if (has_ghosts) bits = 64;  // ... and the ghost-reading rows behind everything else
-    SELL_CHECK(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, keys, keys2, ids, rowid, (int)n, 0, bits, ctx->stream));
-    SELL_CHECK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb2, sizes, ptr, (int)(nblk + 1), ctx->stream));
-    if (tb2 > tb) tb = tb2;
-    SELL_CHECK(hipMalloc(&tmp, tb));
-    SELL_CHECK(hipcub::DeviceRadixSort::SortPairs(tmp, tb, keys, keys2, ids, rowid, (int)n, 0, bits, ctx->stream));  // stable
-  }
-  SELL_CHECK(hipMemsetAsync(sizes, 0, sizeof(int64_t) * (size_t)(nblk + 1), ctx->stream));
-  if (A->rowptr_bits == 64)
-    hipLaunchKernelGGL(k_sell_block_sizes<int64_t>, dim3(mfem_grid_for(nblk, MFEM_BLOCK, ctx->num_cus * 16)), dim3(MFEM_BLOCK), 0,
-                       ctx->stream, n, nblk, (const int64_t*)A->rowptr, rowid, sizes);
-  else
-    hipLaunchKernelGGL(k_sell_block_sizes<int32_t>, dim3(mfem_grid_for(nblk, MFEM_BLOCK, ctx->num_cus * 16)), dim3(MFEM_BLOCK), 0,
-                       ctx->stream, n, nblk, (const int32_t*)A->rowptr, rowid, sizes);
-  SELL_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp, tb, sizes, ptr, (int)(nblk + 1), ctx->stream));
-  SELL_CHECK(hipMemcpyAsync(&total, ptr + nblk, sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-  SELL_CHECK(hipStreamSynchronize(ctx->stream));
-  n_ghost = ctx->h_flags[9];
-  // (padding: up to one block of the longest rows at the tail; with ghost-reading rows sorted last, one more where they begin)
-  // (... and with lattice regions every region pads each of its row lengths to whole blocks: the regions are sized so that this stays small)
-  if ((double)total <= (G.R > 0 ? 1.25 : 1.15) * (double)A->nnz + (has_ghosts ? 256.0 : 128.0) * A->max_row_nnz) {
-    SELL_CHECK(hipMalloc(&A->sell_cols, sizeof(int32_t) * (size_t)total));
-    const int g2 = mfem_grid_for(8 * nblk * 64, MFEM_BLOCK, ctx->num_cus * 16);
-    if (A->rowptr_bits == 64)
-      hipLaunchKernelGGL((k_sell_fill<int64_t, int32_t, true>), dim3(g2), dim3(MFEM_BLOCK), 0, ctx->stream, n, nblk,
-                         (const int64_t*)A->rowptr, rowid, ptr, A->colidx, A->index_base, A->sell_cols, (const int32_t*)nullptr, (const double*)nullptr);
-    else
-      hipLaunchKernelGGL((k_sell_fill<int32_t, int32_t, true>), dim3(g2), dim3(MFEM_BLOCK), 0, ctx->stream, n, nblk,
-                         (const int32_t*)A->rowptr, rowid, ptr, A->colidx, A->index_base, A->sell_cols, (const int32_t*)nullptr, (const double*)nullptr);
-    if (hipGetLastError() != hipSuccess) {
-      mfem_set_error("k_sell_fill launch failed");
-      rc = MFEM_ERR_HIP;
-      goto done;
-    }
-    // blocks with a single diagonal list
-    {
-      int32_t* d_cnt = ctx->d_flags + 9;
-      SELL_CHECK(hipMalloc(&A->sell_flags, sizeof(int32_t) * (size_t)nblk));
-      SELL_CHECK(hipMalloc(&A->sell_off, sizeof(int32_t) * (size_t)(total / SELL_B + 1)));
-      SELL_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(int32_t), ctx->stream));
-      const int g3 = (int)(nblk < (int64_t)ctx->num_cus * 64 ? nblk : (int64_t)ctx->num_cus * 64);
-      if (A->rowptr_bits == 64)
-        hipLaunchKernelGGL(k_sell_block_flags<int64_t>, dim3(g3), dim3(SELL_B), 0, ctx->stream, n, nblk, (const int64_t*)A->rowptr,
-                           A->colidx, A->index_base, rowid, ptr, A->sell_flags, A->sell_off, d_cnt);
-      else
-        hipLaunchKernelGGL(k_sell_block_flags<int32_t>, dim3(g3), dim3(SELL_B), 0, ctx->stream, n, nblk, (const int32_t*)A->rowptr,
-                           A->colidx, A->index_base, rowid, ptr, A->sell_flags, A->sell_off, d_cnt);
-      SELL_CHECK(hipMemcpyAsync(ctx->h_flags + 9, d_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-      SELL_CHECK(hipStreamSynchronize(ctx->stream));
-      A->sell_regular_blocks = ctx->h_flags[9];
-      // field-periodic blocks among the others (k_sell_block_periodic): F = 3, 2, 4 fields of n / F rows each, the first F that covers a quarter of the blocks
-      A->sell_fields = 0;
-      A->sell_shift = 0;
-      A->sell_periodic_blocks = 0;
-      if (g_sell_periodic && !has_ghosts && A->sell_regular_blocks < nblk / 2) {
-        const int cand[3] = {3, 2, 4};
-        for (int ci = 0; ci < 3 && A->sell_fields == 0; ++ci) {
-          const int F = cand[ci];
-          if (n % F != 0 || A->max_row_nnz % F != 0) continue;
-          SELL_CHECK(hipMemsetAsync(d_cnt, 0, sizeof(int32_t), ctx->stream));
-          if (A->rowptr_bits == 64)
-            hipLaunchKernelGGL(k_sell_block_periodic<int64_t>, dim3(g3), dim3(SELL_B), 0, ctx->stream, n, nblk, (const int64_t*)A->rowptr, A->colidx,
-                               A->index_base, rowid, ptr, F, n / F, A->sell_flags, d_cnt);
-          else
-            hipLaunchKernelGGL(k_sell_block_periodic<int32_t>, dim3(g3), dim3(SELL_B), 0, ctx->stream, n, nblk, (const int32_t*)A->rowptr, A->colidx,
-                               A->index_base, rowid, ptr, F, n / F, A->sell_flags, d_cnt);
-          SELL_CHECK(hipMemcpyAsync(ctx->h_flags + 9, d_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-          SELL_CHECK(hipStreamSynchronize(ctx->stream));
-          if (ctx->h_flags[9] >= nblk / 4) {
-            A->sell_fields = F;
-            A->sell_shift = n / F;
-            A->sell_periodic_blocks = ctx->h_flags[9];
-          } else if (ctx->h_flags[9] > 0) {  // (a few blocks happened to fit: not taken -- back to "generic")
-            hipLaunchKernelGGL(k_sell_clear_flag2, dim3(g3), dim3(MFEM_BLOCK), 0, ctx->stream, nblk, A->sell_flags);
-          }
-        }
-      }
-    }
-    A->sell_rowid = rowid;
-    A->sell_ptr = ptr;
-    A->sell_total = total;
-    A->sell_nblk = nblk;
-    // the rows that read ghost columns are the last n_ghost sorted rows: the blocks in front of the first of them form the interior part
-    // of a split SpMV (the block that holds both kinds belongs to the boundary part)
-    A->sell_nb_int = has_ghosts ? (n - (int64_t)n_ghost) / SELL_B : nblk;
-    A->sell_state = 1;
-    rowid = nullptr;
-    ptr = nullptr;
-  }
-done:
-  if (keys) hipFree(keys);
-  if (ids) hipFree(ids);
-  if (keys2) hipFree(keys2);
-  if (rowid) hipFree(rowid);
-  if (sizes) hipFree(sizes);
-  if (ptr) hipFree(ptr);
-  if (tmp) hipFree(tmp);
-  return rc;
+  SellLayout L{};
+  int rc = mfem_bsell_plan(ctx, A, S, &L);
+  if (!rc && L.form == SELL_NONE) rc = sell_plan_rows(ctx, A, S, &L);
+  if (rc) return rc;
+  L.state = L.form != SELL_NONE ? 1 : -1;
+  A->sell = L;
+  return MFEM_OK;
 }
 
 size_t mfem_sell_vals_bytes(const mfem_csr_s* A) {
-  return (A->sell_state == 1 && g_sell_enable && A->n >= g_layout_min_rows_cols) ? sizeof(double) * (size_t)A->sell_total : 0;
+  return sell_serves(A->sell.state, mfem_sell_knobs(), mfem_sell_shape(A)) ? sizeof(double) * (size_t)A->sell.total : 0;
 }
 
 int mfem_sell_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc) {
-  A->sell_vals = nullptr;
-  A->sell_src = nullptr;
-  if (A->sell_state != 1 || !g_sell_enable || !buf) return MFEM_OK;
-  if (A->bsell_F > 0) {
-    const int maxL = A->max_row_nnz / A->bsell_F;
-    if (maxL <= BSELL_T_MAXL && !g_bsell_fill_quads) {  // through an LDS transpose (k_bsell_fill_t)
-      const int ldl = maxL | 1;  // (odd row stride: phase 2's lanes -- one node each -- spread over the banks)
-      const size_t ldsb = sizeof(double) * (size_t)64 * ldl + (size_t)A->bsell_F * 64 * sizeof(int64_t) + 64 * sizeof(int);
-      const int64_t jobs = A->sell_nblk * A->bsell_F;
-      const int gt = (int)(jobs < (int64_t)ctx->num_cus * 12 ? jobs : (int64_t)ctx->num_cus * 12);
-#define BSELL_FILL_T(RP, F)                                                                                                                     \
-  hipLaunchKernelGGL((k_bsell_fill_t<RP, F>), dim3(gt), dim3(MFEM_BLOCK), ldsb, ctx->stream, A->bsell_ncp, A->sell_nblk, (const RP*)A->rowptr, \
-                     A->sell_rowid, A->sell_ptr, vals, A->index_base, buf, A->colidx, dsc, ldl)
-#define BSELL_FILL_TF(RP)                           \
-  do {                                              \
-    if (A->bsell_F == 3) BSELL_FILL_T(RP, 3);       \
-    else if (A->bsell_F == 2) BSELL_FILL_T(RP, 2);  \
-    else BSELL_FILL_T(RP, 4);                       \
-  } while (0)
-      if (A->rowptr_bits == 64) BSELL_FILL_TF(int64_t); else BSELL_FILL_TF(int32_t);
-#undef BSELL_FILL_TF
-#undef BSELL_FILL_T
-      MFEM_CHECK_LAUNCH();
-      A->sell_vals = buf;
-      A->sell_src = vals;
-      return MFEM_OK;
-    }
-    const int gb = mfem_grid_for(A->sell_nblk * A->bsell_F * 4 * 64, MFEM_BLOCK, ctx->num_cus * 16);
-#define BSELL_FILL(RP, F)                                                                                                                      \
-  hipLaunchKernelGGL((k_bsell_fill<RP, F>), dim3(gb), dim3(MFEM_BLOCK), 0, ctx->stream, A->bsell_ncp, A->sell_nblk, (const RP*)A->rowptr,    \
-                     A->sell_rowid, A->sell_ptr, vals, A->index_base, buf, A->colidx, dsc)
-#define BSELL_FILL_F(RP)                          \
-  do {                                            \
-    if (A->bsell_F == 3) BSELL_FILL(RP, 3);       \
-    else if (A->bsell_F == 2) BSELL_FILL(RP, 2);  \
-    else BSELL_FILL(RP, 4);                       \
-  } while (0)
-    if (A->rowptr_bits == 64) BSELL_FILL_F(int64_t); else BSELL_FILL_F(int32_t);
-#undef BSELL_FILL_F
-#undef BSELL_FILL
+  SellLayout& L = A->sell;
+  mfem_sell_unbind(A);
+  if (L.state != 1 || !mfem_sell_knobs().enable || !buf) return MFEM_OK;
+  if (L.form == SELL_NODE_BLOCKED) {
+    const int rc = mfem_bsell_fill(ctx, A, vals, buf, dsc);
+    if (rc) return rc;
+  } else {
+    const int g2 = mfem_grid_for(8 * L.nblk * 64, MFEM_BLOCK, ctx->num_cus * 16);
+    mfem_by_rowptr(A, [&](auto rp) {
+      using RP = decltype(rp);
+      hipLaunchKernelGGL((k_sell_fill<RP, double, false>), dim3(g2), dim3(MFEM_BLOCK), 0, ctx->stream, A->n, L.nblk, (const RP*)A->rowptr, L.rows.rowid,
+                         L.rows.ptr, vals, A->index_base, buf, A->colidx, dsc);
+    });
     MFEM_CHECK_LAUNCH();
-    A->sell_vals = buf;
-    A->sell_src = vals;
-    return MFEM_OK;
   }
-  const int g2 = mfem_grid_for(8 * A->sell_nblk * 64, MFEM_BLOCK, ctx->num_cus * 16);
-  if (A->rowptr_bits == 64)
-    hipLaunchKernelGGL((k_sell_fill<int64_t, double, false>), dim3(g2), dim3(MFEM_BLOCK), 0, ctx->stream, A->n, A->sell_nblk,
-                       (const int64_t*)A->rowptr, A->sell_rowid, A->sell_ptr, vals, A->index_base, buf, A->colidx, dsc);
-  else
-    hipLaunchKernelGGL((k_sell_fill<int32_t, double, false>), dim3(g2), dim3(MFEM_BLOCK), 0, ctx->stream, A->n, A->sell_nblk,
-                       (const int32_t*)A->rowptr, A->sell_rowid, A->sell_ptr, vals, A->index_base, buf, A->colidx, dsc);
-  MFEM_CHECK_LAUNCH();
-  A->sell_vals = buf;
-  A->sell_src = vals;
+  L.vals = buf;
+  L.src = vals;
   return MFEM_OK;
 }
 
-// accounting (mfem_csr_solver_layout_entries / _bytes): the padded slots; blocks whose 128 rows share one diagonal list read it instead of their column stream
-int64_t mfem_sell_entries(const mfem_csr_s* A) { return A->sell_total; }
-int64_t mfem_sell_design_bytes(const mfem_csr_s* A) {
-  if (A->bsell_F > 0) return A->sell_total * 8 + A->bsell_slots * 4 + A->n * 16 + A->bsell_ncp * 4;  // node-blocked: one column per F x F values
-  const double regf = A->sell_nblk > 0 ? (double)A->sell_regular_blocks / (double)A->sell_nblk : 0.0;
-  // field-periodic blocks (round 6) read one column slot per node and F values: 1 / F of their column stream
-  const double per = (A->sell_nblk > 0 && A->sell_fields > 1) ? (double)A->sell_periodic_blocks / (double)A->sell_nblk : 0.0;
-  const double colfrac = (1.0 - regf - per) + (A->sell_fields > 1 ? per / (double)A->sell_fields : 0.0);
-  return A->sell_total * 8 + (int64_t)(colfrac * (double)A->sell_total) * 4 + A->n * 16 + A->n * 4;  // + the row permutation
-}
+// accounting (mfem_csr_solver_layout_entries / _bytes): the padded slots, and sell_design_bytes
+int64_t mfem_sell_entries(const mfem_csr_s* A) { return A->sell.total; }
+int64_t mfem_sell_design_bytes(const mfem_csr_s* A) { return sell_design_bytes(A->sell, A->n); }
 
 void mfem_sell_unbind(mfem_csr_s* A) {
-  A->sell_vals = nullptr;
-  A->sell_src = nullptr;
+  A->sell.vals = nullptr;
+  A->sell.src = nullptr;
 }
 
 void mfem_sell_free(mfem_csr_s* A) {
-  if (A->sell_cols) hipFree(A->sell_cols);
-  if (A->sell_rowid) hipFree(A->sell_rowid);
-  if (A->sell_ptr) hipFree(A->sell_ptr);
-  if (A->sell_flags) hipFree(A->sell_flags);
-  if (A->sell_off) hipFree(A->sell_off);
-  A->sell_flags = nullptr;
-  A->sell_off = nullptr;
-  A->sell_cols = nullptr;
-  A->sell_rowid = nullptr;
-  A->sell_ptr = nullptr;
-  A->sell_state = 0;
-  A->bsell_F = 0;
+  SellLayout& L = A->sell;
+  void* const owned[] = {L.rows.cols, L.rows.rowid, L.rows.ptr, L.rows.flags, L.rows.off, L.nodes.nodeid, L.nodes.ptr, L.nodes.cols};
+  for (void* p : owned)
+    if (p) (void)hipFree(p);
+  L = SellLayout{};  // (state 0: not planned; mfem_layout_drop has unbound the copy)
 }
 
+static auto sell_kernel(int U) -> decltype(&k_spmv_sell<5>) {
+  switch (U) {
+    case 4: return k_spmv_sell<4>;
+    case 8: return k_spmv_sell<8>;
+    case 9: return k_spmv_sell<9>;
+    case 10: return k_spmv_sell<10>;
+    case 15: return k_spmv_sell<15>;
+    default: return k_spmv_sell<5>;
+  }
+}
 // returns 1 if launched, 0 if another kernel should be used, <0 on error
 int mfem_spmv_sell_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, const double* x, double* y, double alpha,
                           double beta, const double* dotw, double* partials, int* n_partials, const int32_t* done_flag, int part) {
-  if (!A->sell_vals || vals != A->sell_src) return 0;
-  // part 1: the leading blocks, whose rows read no ghost column; part 2: the rest (mfem_spmv_halo)
-  const int64_t b_lo = part == 2 ? A->sell_nb_int : 0, b_hi = part == 1 ? A->sell_nb_int : A->sell_nblk;
+  const SellLayout& L = A->sell;
+  if (!L.vals || vals != L.src) return 0;
   if (n_partials) *n_partials = 0;
-  if (A->bsell_F > 0) {  // node-blocked form (no ghost columns: never split)
-    if (part == 2) return 1;
-    int capb = ctx->num_cus * g_sell_wg_per_cu;
-    if (capb > MFEM_MAX_PARTIALS) capb = MFEM_MAX_PARTIALS;
-    const int gridb = mfem_grid_for(A->sell_nblk * 64, MFEM_BLOCK, capb);
-#define BSELL_LAUNCH(F, U)                                                                                                                    \
-  hipLaunchKernelGGL((k_spmv_bsell<F, U>), dim3(gridb), dim3(MFEM_BLOCK), 0, ctx->stream, A->bsell_ncp, A->sell_nblk, A->sell_ptr, A->sell_rowid, \
-                     A->sell_cols, A->sell_vals, x, y, alpha, beta, dotw, partials, done_flag)
-    const int bu = g_sell_per_u;  // (A/B: node slots in flight)
-    if (A->bsell_F == 3) {  // (hex-20 elasticity 96^3, one box: 1 node slot in flight 2.98 ms, 2: 2.89, 3: 2.80)
-      if (bu == 1) BSELL_LAUNCH(3, 2);
-      else if (bu == 2) BSELL_LAUNCH(3, 4);
-      else if (bu == 3) BSELL_LAUNCH(3, 1);
-      else BSELL_LAUNCH(3, 3);
-    } else if (A->bsell_F == 2) BSELL_LAUNCH(2, 4);
-    else BSELL_LAUNCH(4, 2);
-#undef BSELL_LAUNCH
-    MFEM_CHECK_LAUNCH();
-    ++g_bsell_spmv_count;
-    if (n_partials && partials) *n_partials = gridb;
-    return 1;
-  }
-  if (b_hi <= b_lo) return 1;
-  int cap = ctx->num_cus * g_sell_wg_per_cu;
-  if (cap > MFEM_MAX_PARTIALS) cap = MFEM_MAX_PARTIALS;
-  if (part != 0) cap /= 2;  // the two parts of a split SpMV share one partial-sum array
-  const int grid = mfem_grid_for((b_hi - b_lo) * 64, MFEM_BLOCK, cap);
-#define SELL_LAUNCH(U)                                                                                                            \
-  hipLaunchKernelGGL(k_spmv_sell<U>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, A->n, A->sell_nblk, A->sell_ptr, A->sell_rowid, \
-                     g_sell_offsets ? A->sell_flags : nullptr, A->sell_off, A->sell_cols, A->sell_vals, x, y, alpha, beta, dotw,   \
-                     partials, done_flag, b_lo, b_hi, (g_sell_xcd && (grid & 7) == 0) ? 1 : 0, g_sell_periodic ? (A->sell_fields | (g_sell_per_u << 4)) : 0, A->sell_shift)
-  switch (g_sell_unroll) {
-    case 4: SELL_LAUNCH(4); break;
-    case 8: SELL_LAUNCH(8); break;
-    case 9: SELL_LAUNCH(9); break;
-    case 10: SELL_LAUNCH(10); break;
-    case 15: SELL_LAUNCH(15); break;
-    default: SELL_LAUNCH(5); break;
-  }
-#undef SELL_LAUNCH
+  if (L.form == SELL_NODE_BLOCKED) return mfem_bsell_launch(ctx, A, x, y, alpha, beta, dotw, partials, n_partials, done_flag, part);
+  const SellKnobs K = mfem_sell_knobs();
+  const SellRange b = sell_part_range(part, L.rows.nb_int, L.nblk);
+  if (b.hi <= b.lo) return 1;
+  const int grid = mfem_grid_for((b.hi - b.lo) * 64, MFEM_BLOCK, sell_grid_cap(ctx->num_cus, K, MFEM_MAX_PARTIALS, part));
+  hipLaunchKernelGGL(sell_kernel(sell_unroll_resolved(K)), dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, A->n, L.nblk, L.rows.ptr, L.rows.rowid,
+                     K.offsets ? L.rows.flags : nullptr, L.rows.off, L.rows.cols, L.vals, x, y, alpha, beta, dotw, partials, done_flag, b.lo, b.hi,
+                     sell_xcd_flag(K, grid), sell_periodic_word(K, L.rows.fields), L.rows.shift);
   MFEM_CHECK_LAUNCH();
   if (n_partials && partials) *n_partials = grid;
   return 1;
