@@ -15,10 +15,12 @@
 #include "../../include/metafem_mi355x_debug.h"
 #include "csr_decide.h"
 #include "sell_decide.h"
+#include "lat_decide.h"
 
 #define MFEM_WAVE 64
 #define MFEM_BLOCK 256
 #define MFEM_MAX_PARTIALS 4096
+static_assert(LAT_MAX_GATHER_GRID == MFEM_MAX_PARTIALS, "a workgroup of the tiles' gather pass writes one partial sum");
 #define MFEM_NSCALARS 4096       // device-resident Krylov scalars (doubles)  // upper bound on per-launch partial sums of a fused reduction
 
 void mfem_set_error(const char* fmt, ...);
@@ -159,7 +161,7 @@ struct mfem_csr_s {
   uint8_t* cw_elide;        // owned: one flag per tile of plan.w_elide_Rw rows of the fixed-row-count wave-tile kernel (k_spmv_csr_w): columns derivable from the tile's first row
   int32_t lat_m1, lat_m2, lat_fields;  // lattice hint of a structured pattern (0 = none): points per lattice plane = lat_m1 * lat_m2 (brick.hip)
   int32_t lat_m0, lat_plo, lat_gw;     // ... planes of the whole lattice, first owned plane of a slab, ghost planes per side (0 = not given)
-  int32_t lat_inferred;                // the hint was read off row 0 of a caller-supplied pattern (mfem_lattice_from_first_row), not given by mfem_brick_pattern
+  int32_t lat_inferred;                // the hint was read off row 0 of a caller-supplied pattern (mfem_lattice_hint_from_row0), not given by mfem_brick_pattern
   uint16_t* diag_off;       // owned, [n], built on first use: offset of the diagonal entry inside its row (0xFFFF = none stored): |diag| is then an
                             // n-sized gather instead of a scan of all nonzeros (Jacobi_By_Diagonal of every solve)
   // owned storage (mfem_brick_pattern) -- freed in destroy
@@ -198,24 +200,10 @@ struct mfem_csr_s {
   // solver layout mode 3 for rows of uneven length: the row-sorted sliced layout (spmv_sell.hip) or its node-blocked form (spmv_bsell.hip) -- sell.form
   // tells which, and each form has its own members; sell.state 0 = not planned, -1 = no, 1 = ready.  The record and the decisions: sell_decide.h
   SellLayout sell;
-  // symmetric lattice-tile layout of the hex-27 lattice matrix (spmv_lat27.hip): lat27_state 0 = not inspected, -1 = no, 1 = the pattern is the stencil
-  int lat27_state;
-  int32_t lat27_det;        // the bound copy of the hex-27 tiles is in the deterministic (lane = row, phase-major) form
-  const double* lat27_src;
-  const double* lat27_dsc;  // not owned: right Jacobi scaling applied to x while it is staged (nullptr: none)
-  double* lat27_vals;       // not owned (solver workspace): the stored (diagonal + upper) entries, unit by unit
-  double* lat27_dump;       // not owned (behind lat27_vals): one y block per tile
-  double lat27_asym;        // max |A[r][c] - A[c][r]| / max |A[r][c]| seen by the last bind
-  int lat27_scaled;         // the last bind carried a right Jacobi scaling (accounting)
+  // symmetric lattice tiles of the hex-27 lattice matrix (spmv_lat27.hip) and of the F-field 27-point lattice matrix (hex-8; spmv_lat8.hip): what the
+  // plan found and what is bound.  The record and the decisions: lat_decide.h
+  LatTiles lat27, lat8;
   int lat_refused;          // a lattice-tile bind has refused values of this pattern once (not symmetric): solves plan the other layouts too from then on
-  // the same for the 3-field 27-point lattice matrix (hex-8 elasticity; spmv_lat8.hip)
-  int lat8_state;
-  const double* lat8_src;
-  const double* lat8_dsc;
-  double* lat8_vals;
-  double* lat8_dump;
-  double lat8_asym;
-  int lat8_scaled;
   // A = S + N (spmv_rem.hip): the sparse skew remainder a lattice-tile bind carries when the values are nonsymmetric in a few rows only (Nitsche / SUPG
   // faces): owned device storage, grown on demand and kept between solves; rem_active: the CURRENT bind applies it after the tiles' gather pass
   int rem_active;
@@ -263,19 +251,20 @@ int mfem_spmv_lat8_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* vals
                           const double* dotw, double* partials, int* n_partials, const int32_t* done_flag, int part);
 int64_t mfem_lat8_design_bytes(const mfem_csr_s* A);
 int64_t mfem_lat8_entries(const mfem_csr_s* A);
-int mfem_lattice_from_first_row(mfem_context_s* ctx, mfem_csr_s* A);  // proposes lat_* for a pattern without a hint (spmv_lat27.hip)
-// First i-layer of lattice tiles (8 planes each, `gw` planes of upward reach) that stages a ghost plane of the upper neighbour: the layers below it
-// are the interior part of a slab's split SpMV.  m0 = owned planes; without an upper neighbour every layer is interior.
-static inline int mfem_lat_first_ghost_layer(int m0, int gw, int nti, bool has_upper) {
-  if (!has_upper) return nti;
-  int t = m0 - 7 - gw;  // a layer's staged planes end at 8 ti + 7 + gw
-  t = t <= 0 ? 0 : (t + 7) / 8;
-  return t < nti ? t : nti;
+int mfem_lattice_hint_from_row0(mfem_context_s* ctx, mfem_csr_s* A);  // proposes lat_* for a pattern without a hint (layout.hip; lat_decide.h: lattice_from_row0)
+static inline LatShape mfem_lat_shape(const mfem_csr_s* A, int64_t min_rows) {
+  return {A->n, A->ncols, A->max_row_nnz, A->lat_m0, A->lat_m1, A->lat_m2, A->lat_fields, A->lat_plo, A->lat_gw, min_rows};
 }
-// rem_fields > 0: rows above the gate may be repaired by a remainder built for that many fields (then *asym is the measure of tiles + remainder and
-// A->rem_active is set); 0: symmetric values only
-int mfem_sym_probe(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* scratch, double amax, void (*unbind)(mfem_csr_s*),
-                   void (*rebind)(mfem_csr_s*, void*), void* cookie, double* asym, int rem_fields = 0);
+// releases the tiles `T` of A (A->lat27 or A->lat8); the remainder belongs to the bind
+static inline void mfem_lat_unbind(mfem_csr_s* A, LatTiles& T) {
+  if (T.vals) A->rem_active = 0;
+  T.vals = T.dump = nullptr;
+  T.src = T.dsc = nullptr;
+}
+// The symmetry probe of a tile bind (sym_probe.hip): T = the tiles just filled from `vals` and bound without a column scaling.  rem_fields > 0: rows above
+// the gate may be repaired by a remainder built for that many fields (then *asym is the measure of tiles + remainder and A->rem_active is set); 0:
+// symmetric values only
+int mfem_sym_probe(mfem_context_s* ctx, mfem_csr_s* A, LatTiles* T, const double* vals, double* scratch, double amax, double* asym, int rem_fields);
 int mfem_spmv_lat27_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, const double* x, double* y, double alpha,
                            double beta, const double* dotw, double* partials, int* n_partials, const int32_t* done_flag, int part);
 int64_t mfem_lat27_design_bytes(const mfem_csr_s* A);
@@ -299,7 +288,7 @@ __attribute__((visibility("hidden"))) CsrKnobs mfem_csr_knobs();  // what mfem_d
 
 // The solver layouts of a pattern (layout.hip): which copy of the values a solve runs on, and its binding and release.  The values are the
 // mode numbers of mfem_csr_solver_layout: the CSR tile kernel on the caller's values (no copy), slot-major copy with explicit columns / with
-// diagonal-slotted regular blocks (spmv_ell.hip, spmv_dia.hip and the sweeps of spmv_sym.hip), row-sorted sliced ELL or its node-blocked form (spmv_sell.hip, spmv_bsell.hip), symmetric lattice tiles (spmv_lat27.hip, spmv_lat8.hip)
+// diagonal-slotted regular blocks (spmv_ell.hip, spmv_dia.hip and the sweeps of spmv_sym.hip), row-sorted sliced ELL or its node-blocked form (spmv_sell.hip, spmv_bsell.hip), symmetric lattice tiles (spmv_lat27.hip with spmv_lat27_gather.hip, spmv_lat8.hip)
 enum mfem_layout : int32_t { MFEM_LAYOUT_CSR = 0, MFEM_LAYOUT_ELL = 1, MFEM_LAYOUT_DIA = 2, MFEM_LAYOUT_SELL = 3, MFEM_LAYOUT_LAT27 = 4, MFEM_LAYOUT_LAT8 = 5 };
 // What a pattern offers a solve: a tile layout (taken if the values pass its symmetry probe) and a row layout, each with the workspace bytes of
 // its copy (MFEM_LAYOUT_CSR, 0: none)
@@ -339,6 +328,15 @@ __device__ __forceinline__ double wave_reduce_sum(double v) {
 // the LDS counter is drained; global loads into registers are waited for where the registers are used (the compiler's own s_waitcnt), stores never.
 // NOT for barriers that order global-memory accesses between the waves of a workgroup.
 __device__ __forceinline__ void mfem_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// Pass 1 of the lattice tiles: a launch of 8 * ceil(tcount / 8) workgroups covers tcount tiles.  Workgroups with equal blockIdx % 8 share an XCD
+// (round-robin dispatch): each XCD walks a contiguous eighth of the tiles, so the neighbourhoods that overlap are staged through one L2.  tsub = this
+// workgroup's tile; false: it has none (the whole workgroup leaves: no barrier is left waiting).
+__device__ __forceinline__ bool mfem_xcd_tile(int tcount, int& tsub) {
+  const int chunk = (tcount + 7) >> 3;
+  tsub = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);
+  return !((int)(blockIdx.x >> 3) >= chunk || tsub >= tcount);
+}
 
 __device__ __forceinline__ double block_reduce_sum(double v, double* smem /* >= 4 doubles */) {
   v = wave_reduce_sum(v);

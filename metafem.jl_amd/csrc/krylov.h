@@ -23,7 +23,7 @@ __device__ __forceinline__ double mfem_recip_nr(double d) {
   return fma(y, e, y);
 }
 
-// what the fused pass 2 + residual update of the lattice tiles (spmv_lat27.hip: k_lat27_gather_cg) needs of a CG iteration: the fields of CgArgs that k_cg_update reads,
+// what the fused pass 2 + residual update of the lattice tiles (spmv_lat27_gather.hip: k_lat27_gather_cg) needs of a CG iteration: the fields of CgArgs that k_cg_update reads,
 // the iteration's scalar bank, the vectors, and p . A p as the partials pass 1 left (mfem_lat27_dot_partials).
 struct LatCgUpdate {
   int32_t zrec, cur;
@@ -97,10 +97,10 @@ inline uint64_t mfem_csr_graph_key(uint64_t key, const mfem_csr_s* A) {
   key = mfem_hash(key, A->serial); key = mfem_hash(key, A->rowptr); key = mfem_hash(key, A->colidx);
   key = mfem_hash(key, A->n); key = mfem_hash(key, A->nnz); key = mfem_hash(key, A->max_row_nnz);
   key = mfem_hash(key, A->index_base); key = mfem_hash(key, A->ell_vals);
-  key = mfem_hash(key, A->ell_bound_mode + 16 * A->dia_kernel); key = mfem_hash(key, A->sell.vals); key = mfem_hash(key, A->lat27_vals); key = mfem_hash(key, A->lat8_vals); key = mfem_hash(key, A->symp_vals);
+  key = mfem_hash(key, A->ell_bound_mode + 16 * A->dia_kernel); key = mfem_hash(key, A->sell.vals); key = mfem_hash(key, A->lat27.vals); key = mfem_hash(key, A->lat8.vals); key = mfem_hash(key, A->symp_vals);
   // the column scaling the lattice-tile kernels apply to x is a kernel argument too: a solve with right Jacobi (dsc = the solve's d) and one without
   // (dsc = null) on the same pattern, values and workspace must not share a captured cycle
-  key = mfem_hash(key, A->lat27_dsc); key = mfem_hash(key, A->lat8_dsc);
+  key = mfem_hash(key, A->lat27.dsc); key = mfem_hash(key, A->lat8.dsc);
   // ... and so are the arrays of the skew remainder a tile bind may carry (spmv_rem.hip)
   key = mfem_hash(key, A->rem_active);
   if (A->rem_active) { key = mfem_hash(key, A->rem_nrows); key = mfem_hash(key, A->rem_rows); key = mfem_hash(key, A->rem_col); key = mfem_hash(key, A->rem_val); }

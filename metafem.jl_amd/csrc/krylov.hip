@@ -706,7 +706,7 @@ static int unscale_to_x_out(SolveRun& R) {
   return MFEM_OK;
 }
 
-// The symmetric lattice tiles store one triangle of a matrix that passed a symmetry GATE (4e-13 of the row's diagonal; a remainder, where one is
+// The symmetric lattice tiles store one triangle of a matrix that passed a symmetry GATE (LAT_SYM_GATE of the row's diagonal; a remainder, where one is
 // carried, repairs the rows above it): a residual the caller is told -- and a residual that ENDS the passes -- must not come from that copy.  One
 // product with the CSR kernel on the caller's own values: ||b - A x_out|| / sqrt(n), x_out = Pr(x) (one rank: x_out carries no ghost
 // entries; not in benchmark mode, where bench.py does the same recomputation outside its timed region).  V.w[0] is free between passes.

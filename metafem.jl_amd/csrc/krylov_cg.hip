@@ -1,7 +1,7 @@
 // cg!: the two Jacobi-preconditioned CG passes behind mfem_solve (not in the reference, F5) with their kernels -- mfem_cg_pass, the classic recurrence
 // (its z-carrying and scaled variants included), and mfem_cg_single_pass, one reduction group per iteration.  Which of the two a solve runs, and the
 // scaled system of cg_variant 4, are decided and set up by the driver (krylov.hip); the lattice tiles' fused residual update restates k_cg_update's
-// arithmetic in its own file (spmv_lat27.hip: k_lat27_gather_cg).
+// arithmetic in its own file (spmv_lat27_gather.hip: k_lat27_gather_cg).
 #include "krylov.h"
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
@@ -254,7 +254,7 @@ int mfem_cg_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovV
       // reduction group is one fold kernel + one all-reduce
       if (lat_fused) {
         // lattice tiles, one rank: pass 1 (its blocks stay in the dump, p . A p comes as one partial per tile), the fold of the partials, then pass 2 and
-        // the residual update in one kernel (spmv_lat27.hip: k_lat27_gather_cg) -- A p itself is never stored
+        // the residual update in one kernel (spmv_lat27_gather.hip: k_lat27_gather_cg) -- A p itself is never stored
         int rc = mfem_spmv_halo(ctx, A, vals, p, nullptr, 1.0, 0.0, p, part1, &np1, F);
         if (rc) return rc;
         int npt = 0;

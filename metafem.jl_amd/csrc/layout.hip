@@ -1,6 +1,6 @@
 // The solver layouts of a CSR handle, planned, bound, released and accounted for here only: mfem_solve (the stages of its driver, krylov.hip), the layout query and the diagnostic product
 // below take the same rules.  At most one layout is bound at a time; which one serves a product is read off the per-layout pointers, never cached
-// beside them: the tile binds' symmetry probe (mfem_sym_probe) unbinds and rebinds the tiles through callbacks of its own.  Nothing here issues a
+// beside them: the tile binds' symmetry probe (sym_probe.hip) puts the tiles' pointers aside for its CSR product.  Nothing here issues a
 // collective: a refusal of the tiles is a rank-local verdict (krylov.hip: bind_tiles, solve_inner).
 #include "blas1.h"
 #include "layouts.h"
@@ -54,9 +54,9 @@ int mfem_layout_bind(mfem_context_s* ctx, mfem_csr_s* A, mfem_layout mode, const
 }
 
 mfem_layout mfem_layout_bound(const mfem_csr_s* A, const double* vals) {
-  if (A->lat8_vals && vals == A->lat8_src) return MFEM_LAYOUT_LAT8;
+  if (A->lat8.vals && vals == A->lat8.src) return MFEM_LAYOUT_LAT8;
   if (A->ell_vals && vals == A->ell_src) return A->ell_bound_mode == 2 ? MFEM_LAYOUT_DIA : MFEM_LAYOUT_ELL;
-  if (A->lat27_vals && vals == A->lat27_src) return MFEM_LAYOUT_LAT27;
+  if (A->lat27.vals && vals == A->lat27.src) return MFEM_LAYOUT_LAT27;
   if (A->sell.vals && vals == A->sell.src) return MFEM_LAYOUT_SELL;
   return MFEM_LAYOUT_CSR;
 }
@@ -64,8 +64,8 @@ mfem_layout mfem_layout_bound(const mfem_csr_s* A, const double* vals) {
 void mfem_layout_unbind(mfem_csr_s* A) {
   mfem_ell_unbind(A);
   mfem_sell_unbind(A);
-  mfem_lat27_unbind(A);
-  mfem_lat8_unbind(A);
+  mfem_lat_unbind(A, A->lat27);
+  mfem_lat_unbind(A, A->lat8);
 }
 
 void mfem_layout_drop(mfem_csr_s* A) {
@@ -73,11 +73,46 @@ void mfem_layout_drop(mfem_csr_s* A) {
   mfem_ell_free(A);
   mfem_sell_free(A);
   mfem_rem_free(A);
-  A->lat27_state = A->lat8_state = A->lat_refused = A->sym_state = A->symp_state = 0;
+  A->lat27.state = A->lat8.state = A->lat_refused = A->sym_state = A->symp_state = 0;
   if (A->lat_inferred) {  // (a hint read off the arrays goes with them)
     A->lat_fields = A->lat_m0 = A->lat_m1 = A->lat_m2 = A->lat_plo = A->lat_gw = 0;
     A->lat_inferred = 0;
   }
+}
+
+// A pattern without a lattice hint (lat_fields == 0, no ghost columns: a caller-supplied pattern, mfem_csr_create with the reference's own K_J_ptr /
+// K_J) gets the one its row 0 proposes (lat_decide.h: lattice_from_row0); lat_fields = -1 afterwards if there is none, so that the question is asked
+// once per pattern.  Both tile plans call this; mfem_layout_drop forgets the answer with the arrays.
+int mfem_lattice_hint_from_row0(mfem_context_s* ctx, mfem_csr_s* A) {
+  if (A->lat_fields != 0) return MFEM_OK;
+  A->lat_fields = -1;
+  A->lat_inferred = 1;
+  if (A->n < 8 || (A->ncols > A->n)) return MFEM_OK;
+  int64_t rp[2] = {0, 0};
+  const int rc = mfem_by_rowptr(A, [&](auto w) -> int {
+    decltype(w) r[2];
+    MFEM_CHECK_HIP(hipMemcpyAsync(r, A->rowptr, sizeof(r), hipMemcpyDeviceToHost, ctx->stream));
+    MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+    rp[0] = r[0];
+    rp[1] = r[1];
+    return MFEM_OK;
+  });
+  if (rc) return rc;
+  const int64_t len = rp[1] - rp[0];
+  if (!lattice_row0_len(len)) return MFEM_OK;
+  int32_t c[27];
+  MFEM_CHECK_HIP(hipMemcpyAsync(c, A->colidx + (rp[0] - A->index_base), (size_t)len * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < len; ++i) c[i] -= A->index_base;
+  const LatHint H = lattice_from_row0(len, c, A->n);
+  if (!H.fields) return MFEM_OK;
+  A->lat_fields = H.fields;
+  A->lat_m0 = H.m0;
+  A->lat_m1 = H.m1;
+  A->lat_m2 = H.m2;
+  A->lat_plo = H.plo;
+  A->lat_gw = H.gw;
+  return MFEM_OK;
 }
 
 // What the Krylov loop of the next mfem_solve will run on this pattern: 0 = CSR tile kernel, 1 = slot-major copy with explicit

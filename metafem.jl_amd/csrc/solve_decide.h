@@ -29,7 +29,7 @@ static inline WsTrialStep ws_trial_decide(int tried, float ms, float best_ms) {
 // summation order, the repaired rows): the next pass, which iterates on the tiles' copy, would find itself converged at once and the passes would run
 // out with the caller's residual a hair above the tolerance (seen once in the 3-rank test's single-rank reference solve, round 5).  It iterates to a
 // tighter tolerance instead: below the tiles' residual of this pass by the margin the caller's residual is above the tolerance, and at least a factor two.
-//  the caller's residual can have a FLOOR above the tolerance -- a tight tolerance against the 4e-13-per-row gate --: the tiles' residual
+//  the caller's residual can have a FLOOR above the tolerance -- a tight tolerance against the per-row symmetry gate of the tiles (LAT_SYM_GATE) --: the tiles' residual
 // then keeps falling, the tightened tolerance compounds towards zero and every remaining pass burns its full maxiter.  If the caller's residual did not
 // fall since the previous recheck that went on (prev_csr_res; <= 0: none yet), iterating on the tiles cannot help: the passes end, not converged.  The
 // tightening is bounded.

@@ -16,66 +16,34 @@
 //     the same shape: for a stored entry a = A[r][c] the lane adds a x[c] to its register sum for row r and a x[r] to cell c
 //     (ds_add_f64) -- the mirrored entry A[c][r] is never read.  The whole y block -- own cells and neighbourhood -- leaves as one
 //     contiguous 34.6 KB run per tile.
-//   * pass 2 (k_lat27_gather): row r sums the up to 18 tiles whose block covers it, in a fixed order, applies alpha / beta and the fused
+//   * pass 2 (spmv_lat27_gather.hip): row r sums the up to 18 tiles whose block covers it, in a fixed order, applies alpha / beta and the fused
 //     dot product.  No global atomics; 2.1 cells per row written and read again (+ 12 % traffic).
 //   * eligibility is decided in two steps: the pattern must BE the lattice stencil (checked entry by entry once per pattern), and the values
-//     of this solve must be symmetric: measured per bind with a probe product (mfem_sym_probe below: the layout against the CSR kernel on one
-//     vector); the sliced layout serves the solve when a row of the two products differs by more than 4e-13 of that row's diagonal entry.  A right Jacobi scaling (bicgstabl_GS!, idrs!, cgs2! work on A D^-1, which is not
+//     of this solve must be symmetric: measured per bind with a probe product (sym_probe.hip: the layout against the CSR kernel on one
+//     vector); the sliced layout serves the solve when a row of the two products differs by more than LAT_SYM_GATE (lat_decide.h) of that row's diagonal entry.  A right Jacobi scaling (bicgstabl_GS!, idrs!, cgs2! work on A D^-1, which is not
 //     symmetric) is applied to x while it is staged: (A D^-1) x = A (x / d), so the stored matrix stays the symmetric A.
 //   * y differs from the CSR kernel's by round-off (other summation order), and the order in which the waves of a workgroup add into
 //     an LDS cell is not fixed: results are reproducible to ~1e-16 relative, not bitwise (mfem_debug_set_lat27(0) selects the sliced layout).
+// The host decisions (knobs, eligibility, geometry, sizes, the split of a slab's launch): lat_decide.h.
 #include "blas1.h"
 #include "layouts.h"
-#include "spmv_lat_tables.h"
-#include "krylov.h"  // scalar / flag slots of the Krylov loop (the fused CG update below)
-
-#define L27_TI 8
-#define L27_TJ 8
-#define L27_TK 32
-#define L27_SJ (L27_TJ + 4)
-#define L27_SK (L27_TK + 4)
-#define L27_CELLS ((L27_TI + 2) * L27_SJ * L27_SK)  // 4320
-#define L27_PI (L27_SJ * L27_SK + 8)                 // plane stride of the LDS blocks: 440 = 8 mod 16, so the 16 rows of a step (2 a PI + 2 b SK + 2 c) fall on 16 different bank pairs
-#define L27_LDS_CELLS ((L27_TI + 2) * L27_PI)
-#define L27_UNIT_D 4352                             // doubles per unit: 64 lanes x 68 steps
+#include "spmv_lat27.h"
 
 typedef double l_d2 __attribute__((ext_vector_type(2)));
 
 extern std::atomic<int64_t> g_layout_min_rows_lat27;  // spmv_ell.hip
-static std::atomic<int> g_lat27_enable{1};
-static std::atomic<int> g_lat27_det{1};  // bit 3 of mfem_debug_set_lat27: 0 = pass 1 by the four-lanes-per-row kernel (not bitwise reproducible), 1 (default) = lane = row, phase-major
-static std::atomic<int> g_lat27_cg_fused{1};  // bit 2 of mfem_debug_set_lat27: 0 = CG iterations as SpMV (pass 1 + pass 2) + k_cg_update instead of pass 1 + k_lat27_gather_cg
-static std::atomic<int> g_lat27_gather_staged{1};  // bit 1 of mfem_debug_set_lat27: 0 = pass 2 by k_lat27_gather (masked blocks, a round trip per covering block)
+static std::atomic<int> g_lat27_word{LAT27_WORD_DEFAULT};  // mfem_debug_set_lat27 (Lat27Knobs)
+static Lat27Knobs lat27_knobs() { return lat27_knobs_decode(g_lat27_word); }
+static LatShape lat27_shape(const mfem_csr_s* A) { return mfem_lat_shape(A, g_layout_min_rows_lat27); }
 static std::atomic<long long> g_lat27_count{0};
 extern "C" long long mfem_debug_lat27_spmv_count(void) { return g_lat27_count; }  // SpMVs the layout has served (bench.py: which kernel ran)
-// max |A[r][c] - A[c][r]| / max |A[r][c]| the layout pass of the last bind on this pattern measured (-1: no bind yet)
-extern "C" double mfem_debug_lat27_asymmetry(mfem_csr A) { return A ? A->lat27_asym : -1.0; }
+// what the symmetry probe of the last bind on this pattern measured (0: no bind yet)
+extern "C" double mfem_debug_lat27_asymmetry(mfem_csr A) { return A ? A->lat27.asym : -1.0; }
 extern "C" int mfem_debug_set_lat27(int enable) try {
   ++mfem_debug_epoch;
-  g_lat27_enable = enable & 1;
-  g_lat27_gather_staged = ((enable >> 1) & 1) ? 0 : 1;
-  g_lat27_cg_fused = ((enable >> 2) & 1) ? 0 : 1;
-  g_lat27_det = ((enable >> 3) & 1) ? 0 : 1;
+  g_lat27_word = enable & 15;
   return MFEM_OK;
 } MFEM_API_CATCH("mfem_debug_set_lat27")
-
-struct Lat27Geom {
-  int m0, m1, m2;     // OWNED lattice points per direction (m0 = owned planes of a slab; m1, m2 odd)
-  int nui, nuj, nuk;  // units of 4 x 4 x 8 points
-  int nti, ntj, ntk;  // tiles of 8 x 8 x 32 points
-  int64_t n;          // m0 * m1 * m2 owned rows
-  // slab: the owned planes are [plo, plo + m0) (plo even: slabs are cut on element boundaries) of a lattice of mg planes; x carries, behind the n
-  // owned entries, a low and a high block of gw = 2 ghost planes (brick_xindex); plo = 0, mg = m0 for a whole brick
-  int plo, mg, gw;
-};
-// local x index at GLOBAL plane gi (owned or ghost), in-plane position ip
-__device__ __forceinline__ int64_t l27_xindex(const Lat27Geom& G, int gi, int64_t ip) {
-  const int64_t PL = (int64_t)G.m1 * G.m2;
-  if (gi >= G.plo && gi < G.plo + G.m0) return (int64_t)(gi - G.plo) * PL + ip;
-  const int side = gi < G.plo ? 0 : 1;
-  const int off = side ? gi - (G.plo + G.m0) : gi - (G.plo - G.gw);
-  return G.n + ((int64_t)side * G.gw + off) * PL + ip;
-}
 
 // type t = 4 (i odd) + 2 (j odd) + (k odd); steps per lane K4, stored slots Kup, group base inside a unit (doubles), table base (entries)
 __constant__ int c_l27_Kup[8];
@@ -106,18 +74,6 @@ static int lat27_upload_tables() {
   }
   g_l27_tables = true;
   return MFEM_OK;
-}
-
-// offsets a row at lattice coordinate g (of m points) has along one direction: [lo, lo + cnt)
-__device__ __forceinline__ void l27_range(int g, int m, int& lo, int& cnt) {
-  if (g & 1) {
-    lo = -1;
-    cnt = 3;
-  } else {
-    lo = g >= 2 ? -2 : -g;
-    const int hi = (m - 1 - g) >= 2 ? 2 : (m - 1 - g);
-    cnt = hi - lo + 1;
-  }
 }
 
 // 1 in *bad if some row is not the lattice stencil row: length = product of the per-direction ranges, columns in lexicographic order
@@ -208,110 +164,6 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_l27_fill(Lat27Geom G, const RP* 
   if (lane == 0) atomicMax(stats + 1, (unsigned long long)__double_as_longlong(amax));
 }
 
-// ---- the symmetry measure shared by the lattice-tile layouts (modes 4 and 5) ---------------------------------------------------------
-// The layout stores one triangle and mirrors it; whether that is the caller's matrix is measured with a probe product: x with entries of magnitude
-// in [0.75, 1.25) and a random SIGN each (zero mean: a skew part with zero row sums -- convection-like terms -- is not attenuated the way a
-// nearly constant probe would), y1 = (layout) x, y2 = (CSR kernel on the caller's values) x.  y1 - y2 = (L - U^T) x: an entry pair that differs by
-// delta shows up as >= 0.75 |delta| in its row (the other terms of that row are the other pairs' differences: no cancellation for a generic x).
-// The two products round differently (a few 1e-15 of the row's entries for rows of up to 125 entries), so the layout is taken when
-//     max over rows r of |y1 - y2|_r / |a_rr|  <=  4e-13
-// -- the difference is weighed PER ROW by that row's diagonal entry (badly scaled matrices: a penalty or Robin row of 1e5 no longer hides an
-// asymmetric pair in a row of 1e-3); rows without a stored non-zero diagonal are weighed by the global max |a|.
-__global__ __launch_bounds__(MFEM_BLOCK) void k_probe_vector(int64_t n, double* __restrict__ x) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    uint64_t z = (uint64_t)i + 0x9E3779B97F4A7C15ull;  // splitmix64
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    z ^= z >> 31;
-    const double mag = 0.75 + 0.5 * (double)(z >> 11) * (1.0 / 9007199254740992.0);
-    x[i] = (z & 1ull) ? mag : -mag;
-  }
-}
-__global__ __launch_bounds__(MFEM_BLOCK) void k_probe_diff(int64_t n, const double* __restrict__ a, const double* __restrict__ b,
-                                                             const double* __restrict__ scale, unsigned long long* __restrict__ out) {
-  double d = 0.0;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    double e = fabs(a[i] - b[i]) / scale[i];  // (scale > 0: |diagonal| or the preset max |a|)
-    if (!(e == e)) e = __builtin_huge_val();
-    d = fmax(d, e);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) d = fmax(d, __shfl_down(d, o, MFEM_WAVE));
-  if ((threadIdx.x & 63) == 0) atomicMax(out, (unsigned long long)__double_as_longlong(d));
-}
-
-// scratch: ncols + 2 n doubles (x carries the ghost entries of a slab pattern).  The layout must be bound for `vals` with no column scaling; unbind() must leave the pattern without any bound layout
-// (the second product then runs the CSR kernel).  *asym = max over rows of |y1 - y2|_r / |a_rr| (rows without a non-zero diagonal: / amax).
-int mfem_sym_probe(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* scratch, double amax, void (*unbind)(mfem_csr_s*),
-                   void (*rebind)(mfem_csr_s*, void*), void* cookie, double* asym, int rem_fields) {
-  A->rem_active = 0;
-  A->rem_asym_before = 0.0;
-  A->rem_last_rows = A->rem_last_ent = 0;
-  const int64_t n = A->n, nc = A->ncols > n ? A->ncols : n;
-  double *x = scratch, *y1 = scratch + nc, *y2 = y1 + n;
-  unsigned long long* d_stat = (unsigned long long*)(ctx->d_flags + 12);
-  MFEM_CHECK_HIP(hipMemsetAsync(d_stat, 0, sizeof(unsigned long long), ctx->stream));
-  const int prof = ctx->prof_on;
-  ctx->prof_on = 0;  // (not SpMVs of the solve: bench.py's per-launch timing must not see them)
-  ctx->probe_active = 1;
-  hipLaunchKernelGGL(k_probe_vector, dim3(mfem_vec_grid(ctx, nc)), dim3(MFEM_BLOCK), 0, ctx->stream, nc, x);
-  int rc = mfem_spmv_launch(ctx, A, vals, x, y1, 1.0, 0.0, nullptr, nullptr, nullptr);
-  if (!rc) {
-    unbind(A);
-    rc = mfem_spmv_launch(ctx, A, vals, x, y2, 1.0, 0.0, nullptr, nullptr, nullptr);
-    rebind(A, cookie);
-  }
-  ctx->prof_on = prof;
-  ctx->probe_active = 0;
-  if (rc) return rc;
-  const bool finite = amax < __builtin_huge_val() && amax == amax;
-  if (!(amax > 0.0) || !finite) {  // an all-zero matrix is symmetric; a non-finite one is not taken
-    *asym = finite ? 0.0 : 1.0;
-    return MFEM_OK;
-  }
-  // the rows' weights into x (the probe vector has served): |a_rr|, preset max |a| where no non-zero diagonal is stored
-  int mfem_fill(mfem_context_s* ctx, int64_t n, double v, double* x);  // (krylov.hip)
-  rc = mfem_fill(ctx, n, amax, x);
-  if (!rc) rc = mfem_jacobi_diag_launch(ctx, A, vals, x, 0);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_probe_diff, dim3(mfem_vec_grid(ctx, n)), dim3(MFEM_BLOCK), 0, ctx->stream, n, y1, y2, x, d_stat);
-  MFEM_CHECK_LAUNCH();
-  MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 12, d_stat, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-  MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  double dmax;
-  memcpy(&dmax, ctx->h_flags + 12, sizeof(double));
-  *asym = dmax;  // already relative: max_r |y1 - y2|_r / |a_rr|
-  A->rem_asym_before = dmax;
-  if (dmax <= 4e-13 || rem_fields <= 0 || !(dmax < __builtin_huge_val())) return MFEM_OK;
-  // A = S + N (spmv_rem.hip): the rows above the gate get a remainder N[r][c] = A[r][c] - A[c][r] on their mirrored entries; accepted when the SAME
-  // probe passes on S + N.  (x holds the rows' weights now, y1 / y2 the two products.)
-  bool built = false;
-  rc = mfem_rem_build(ctx, A, vals, rem_fields, y1, y2, x, 4e-13, &built);
-  if (rc || !built) return rc;
-  hipLaunchKernelGGL(k_probe_vector, dim3(mfem_vec_grid(ctx, nc)), dim3(MFEM_BLOCK), 0, ctx->stream, nc, x);  // the probe vector again (the weights took its place)
-  MFEM_CHECK_LAUNCH();
-  ctx->probe_active = 1;
-  rc = mfem_rem_apply(ctx, A, x, nullptr, y1, 1.0, nullptr, nullptr, nullptr, nullptr);
-  ctx->probe_active = 0;
-  if (!rc) rc = mfem_fill(ctx, n, amax, x);
-  if (!rc) rc = mfem_jacobi_diag_launch(ctx, A, vals, x, 0);
-  if (rc) return rc;
-  MFEM_CHECK_HIP(hipMemsetAsync(d_stat, 0, sizeof(unsigned long long), ctx->stream));
-  hipLaunchKernelGGL(k_probe_diff, dim3(mfem_vec_grid(ctx, n)), dim3(MFEM_BLOCK), 0, ctx->stream, n, y1, y2, x, d_stat);
-  MFEM_CHECK_LAUNCH();
-  MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 12, d_stat, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-  MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  double dmax2;
-  memcpy(&dmax2, ctx->h_flags + 12, sizeof(double));
-  if (dmax2 <= 4e-13) {
-    *asym = dmax2;
-    A->rem_active = 1;
-    A->rem_last_rows = A->rem_nrows;
-    A->rem_last_ent = A->rem_nent;
-  }
-  return MFEM_OK;
-}
-
 // A unit's 68 steps run as 5 chunks of 16 / 10 / 10 / 16 / 16 steps (type 0; type 1; type 2; types 3 + 4; types 5 + 6 + 7: neighbours in the unit's
 // storage); the values of chunk k + 1 are in flight while chunk k is worked through LDS (two register buffers that swap roles; 9 smaller chunks left
 // 32 - 64 bytes per lane in flight, this keeps 80 - 128).
@@ -362,6 +214,38 @@ __device__ __forceinline__ void l27_unit(l_d2 (&A)[8], l_d2 (&B)[8], const doubl
   l27_proc<4, 6>(A, tabs + 128 + q * 2, p0 + PI + PJ + 1, q, xs, ys);  // type 7
 }
 
+// What both forms of pass 1 do around their products.  x of the tile's box -- own points and the (+2, +-2, +-2) neighbourhood -- into xs, divided by d
+// under a right Jacobi scaling; ys cleared.
+__device__ __forceinline__ void l27_stage_x(Lat27Geom G, const double* x, const double* dsc, int ti, int tj, int tk, int tid, double* xs, double* ys) {
+  const int i0 = ti * L27_TI, j0 = tj * L27_TJ - 2, k0 = tk * L27_TK - 2;
+  for (int e = tid; e < L27_LDS_CELLS; e += 512) {
+    const int li = e / L27_PI, r2 = e - li * L27_PI, lj = r2 / L27_SK, lk = r2 - lj * L27_SK;
+    const int gi = G.plo + i0 + li, gj = j0 + lj, gk = k0 + lk;  // global plane: the two planes behind the last owned one are ghost planes
+    double xv = 0.0;
+    if (lj < L27_SJ && gi < G.mg && gi < G.plo + G.m0 + G.gw && gj >= 0 && gj < G.m1 && gk >= 0 && gk < G.m2) {
+      const int64_t r = l27_xindex(G, gi, (int64_t)gj * G.m2 + gk);
+      xv = dsc ? x[r] / dsc[r] : x[r];
+    }
+    xs[e] = xv;
+    ys[e] = 0.0;
+  }
+}
+// the tile's y block leaves as one contiguous run; dotp: the tile's share of x . A x beside it
+__device__ __forceinline__ void l27_write_block(const double* xs, const double* ys, double* dump, int tile, int tid, double* dotp, double* dred) {
+  double* dt = dump + (int64_t)tile * L27_CELLS;
+  double dacc = 0.0;
+  for (int e = tid; e < L27_CELLS; e += 512) {
+    const int li = e / (L27_SJ * L27_SK);
+    const double yv = ys[e + 8 * li];
+    dt[e] = yv;
+    dacc += yv * xs[e + 8 * li];
+  }
+  if (dotp) {  // (kernel argument: every thread of the workgroup takes the same way)
+    const double d = block_reduce_sum(dacc, dred);
+    if (tid == 0) dotp[tile] = d;
+  }
+}
+
 // pass 1: one workgroup per tile.  dump[tile][cell] = what the tile's stored entries contribute to y on its own cells and on the
 // (+2, +-2, +-2) neighbourhood.
 // dsc != nullptr: the operator is A D^-1 (right Jacobi scaling, Mat_Div_Jacobi of 02_Preconditioner.jl:141-148): the stored matrix stays the
@@ -376,12 +260,9 @@ __global__ __launch_bounds__(512, 4) void k_spmv_lat27(Lat27Geom G, const double
   __shared__ uint32_t tabs[L27_TAB / 2];
   __shared__ double dred[8];
   if (done_flag && done_flag[0]) return;
-  // workgroups with equal blockIdx % 8 share an XCD (round-robin dispatch): each XCD walks a contiguous eighth of the tiles, so the
-  // neighbourhoods that overlap are staged through one L2
   // (this launch covers the tiles [tile0, tile0 + tcount) of the i-major tile list: all of them, or the interior / boundary part of a slab's SpMV)
-  const int chunk = (tcount + 7) >> 3;
-  const int tsub = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);
-  if ((int)(blockIdx.x >> 3) >= chunk || tsub >= tcount) return;
+  int tsub;
+  if (!mfem_xcd_tile(tcount, tsub)) return;
   const int tile = tile0 + tsub;
   const int tk = tile % G.ntk, t2 = tile / G.ntk, tj = t2 % G.ntj, ti = t2 / G.ntj;
   const int tid = threadIdx.x;
@@ -397,18 +278,7 @@ __global__ __launch_bounds__(512, 4) void k_spmv_lat27(Lat27Geom G, const double
   if (e0) l27_load<16>(A, uv0);  // in flight while x is staged
   for (int e = tid; e < L27_TAB / 2; e += 512)
     tabs[e] = (uint32_t)(uint16_t)c_l27_off[2 * e] | ((uint32_t)(uint16_t)c_l27_off[2 * e + 1] << 16);
-  const int i0 = ti * L27_TI, j0 = tj * L27_TJ - 2, k0 = tk * L27_TK - 2;
-  for (int e = tid; e < L27_LDS_CELLS; e += 512) {
-    const int li = e / L27_PI, r2 = e - li * L27_PI, lj = r2 / L27_SK, lk = r2 - lj * L27_SK;
-    const int gi = G.plo + i0 + li, gj = j0 + lj, gk = k0 + lk;  // global plane: the two planes behind the last owned one are ghost planes
-    double xv = 0.0;
-    if (lj < L27_SJ && gi < G.mg && gi < G.plo + G.m0 + G.gw && gj >= 0 && gj < G.m1 && gk >= 0 && gk < G.m2) {
-      const int64_t r = l27_xindex(G, gi, (int64_t)gj * G.m2 + gk);
-      xv = dsc ? x[r] / dsc[r] : x[r];
-    }
-    xs[e] = xv;
-    ys[e] = 0.0;
-  }
+  l27_stage_x(G, x, dsc, ti, tj, tk, tid, xs, ys);
   __syncthreads();
   if (e0) {
     // LDS cell of the lane's row of type (0, 0, 0) in the first unit; the other types are +1 in the odd directions, the second unit 4 planes on
@@ -417,18 +287,7 @@ __global__ __launch_bounds__(512, 4) void k_spmv_lat27(Lat27Geom G, const double
     if (e1) l27_unit(B, A, uv1, nullptr, p0 + 4 * L27_PI, q, tabs, xs, ys);
   }
   __syncthreads();
-  double* dt = dump + (int64_t)tile * L27_CELLS;
-  double dacc = 0.0;
-  for (int e = tid; e < L27_CELLS; e += 512) {
-    const int li = e / (L27_SJ * L27_SK);
-    const double yv = ys[e + 8 * li];
-    dt[e] = yv;
-    dacc += yv * xs[e + 8 * li];
-  }
-  if (dotp) {  // (kernel argument: every thread of the workgroup takes the same way)
-    const double d = block_reduce_sum(dacc, dred);
-    if (tid == 0) dotp[tile] = d;
-  }
+  l27_write_block(xs, ys, dump, tile, tid, dotp, dred);
 }
 
 
@@ -440,7 +299,6 @@ __global__ __launch_bounds__(512, 4) void k_spmv_lat27(Lat27Geom G, const double
 // per phase in program order: y is bitwise the same from run to run.  A cube's 260 steps are stored as its two waves' streams (138 + 122 steps of 64
 // lanes), a pair of steps per lane side by side: each wave reads its 70 / 62 KB front to back with 16-byte loads.  bit 3 of the "lat27" knob selects
 // the four-lanes-per-row kernel above (ds_add_f64 across waves: ~1e-16, not bitwise) for the A/B.
-#define L27D_CUBE_D (L27D_CUBE_STEPS * 64)  // doubles per cube
 __host__ __device__ constexpr int l27d_coff(int di, int dj, int dk) { return di * L27_PI + dj * L27_SK + dk; }
 __host__ __device__ constexpr int l27d_toff(int t) { return ((t >> 2) & 1) * L27_PI + ((t >> 1) & 1) * L27_SK + (t & 1); }
 
@@ -522,9 +380,8 @@ __global__ __launch_bounds__(512, 4) void k_spmv_lat27d(Lat27Geom G, const doubl
   __shared__ double ys[L27_LDS_CELLS];
   __shared__ double dred[8];
   if (done_flag && done_flag[0]) return;
-  const int chunk = (tcount + 7) >> 3;
-  const int tsub = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);
-  if ((int)(blockIdx.x >> 3) >= chunk || tsub >= tcount) return;  // (the whole workgroup leaves)
+  int tsub;
+  if (!mfem_xcd_tile(tcount, tsub)) return;
   const int tile = tile0 + tsub;
   const int tk = tile % G.ntk, t2 = tile / G.ntk, tj = t2 % G.ntj, ti = t2 / G.ntj;
   const int tid = threadIdx.x;
@@ -535,18 +392,7 @@ __global__ __launch_bounds__(512, 4) void k_spmv_lat27d(Lat27Geom G, const doubl
   const bool act = ck < nck;
   // a cube that does not exist (lattice edge in k) is read from a place that does and not worked on
   const double* sb = vals + (act ? (((int64_t)ti * ncj + tj) * nck + ck) * (int64_t)L27D_CUBE_D : 0) + (pg ? (int64_t)l27d_stream(0).n * 64 : 0) + lane * 2;
-  const int i0 = ti * L27_TI, j0 = tj * L27_TJ - 2, k0 = tk * L27_TK - 2;
-  for (int e = tid; e < L27_LDS_CELLS; e += 512) {
-    const int li = e / L27_PI, r2 = e - li * L27_PI, lj = r2 / L27_SK, lk = r2 - lj * L27_SK;
-    const int gi = G.plo + i0 + li, gj = j0 + lj, gk = k0 + lk;
-    double xv = 0.0;
-    if (lj < L27_SJ && gi < G.mg && gi < G.plo + G.m0 + G.gw && gj >= 0 && gj < G.m1 && gk >= 0 && gk < G.m2) {
-      const int64_t r = l27_xindex(G, gi, (int64_t)gj * G.m2 + gk);
-      xv = dsc ? x[r] / dsc[r] : x[r];
-    }
-    xs[e] = xv;
-    ys[e] = 0.0;
-  }
+  l27_stage_x(G, x, dsc, ti, tj, tk, tid, xs, ys);
   __syncthreads();
   {
     const int a = lane >> 4, b = (lane >> 2) & 3, c = lane & 3;
@@ -555,18 +401,7 @@ __global__ __launch_bounds__(512, 4) void k_spmv_lat27d(Lat27Geom G, const doubl
     else l27d_wave<1>(sb, p0, act, xs, ys);
   }
   __syncthreads();
-  double* dt = dump + (int64_t)tile * L27_CELLS;
-  double dacc = 0.0;
-  for (int e = tid; e < L27_CELLS; e += 512) {
-    const int li = e / (L27_SJ * L27_SK);
-    const double yv = ys[e + 8 * li];
-    dt[e] = yv;
-    dacc += yv * xs[e + 8 * li];
-  }
-  if (dotp) {
-    const double d = block_reduce_sum(dacc, dred);
-    if (tid == 0) dotp[tile] = d;
-  }
+  l27_write_block(xs, ys, dump, tile, tid, dotp, dred);
 }
 
 // the layout pass of the deterministic form: a wave per (cube, parity group), lane = row.  A lane walks the UPPER HALF of its CSR row front to back (the
@@ -673,584 +508,133 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_l27d_fill(Lat27Geom G, const RP*
   if (lane == 0) atomicMax(stats + 1, (unsigned long long)__double_as_longlong(amax));
 }
 
-// pass 2: y[r] = alpha * (sum over the tiles whose block covers r, fixed order) + beta * y[r]; fused dot with dotw.  A thread owns a
-// (j, k) position of the tile and its 8 lattice planes: 8 independent loads per covering tile.
-// Slab with a lower neighbour (G.plo > 0): the rows of the first owned plane (an even plane: reach 2) also have entries towards the two ghost planes
-// below.  No stored entry mirrors onto them (the rows that would belong to the neighbour rank), so they are taken from the caller's CSR values here.
-template <typename RP>
-__global__ __launch_bounds__(MFEM_BLOCK) void k_lat27_gather(Lat27Geom G, const double* __restrict__ dump, double* __restrict__ y,
-                                                               double alpha, double beta, const double* __restrict__ dotw,
-                                                               double* __restrict__ partials, const int32_t* __restrict__ done_flag,
-                                                               const RP* __restrict__ rowptr, int base, const double* __restrict__ csr_vals,
-                                                               const double* __restrict__ x, const double* __restrict__ dsc) {
-  __shared__ double red[4];
-  if (done_flag && done_flag[0]) return;
-  double dot_acc = 0.0;
-  const int ntiles = G.nti * G.ntj * G.ntk;
-  const int lk = threadIdx.x & (L27_TK - 1), lj = threadIdx.x >> 5;
-  const int PC = L27_SJ * L27_SK;
-  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int tk = tile % G.ntk, t2 = tile / G.ntk, tj = t2 % G.ntj, ti = t2 / G.ntj;
-    const int gj = tj * L27_TJ + lj, gk = tk * L27_TK + lk, gi0 = ti * L27_TI;
-    if (gj >= G.m1 || gk >= G.m2) continue;
-    double s[L27_TI];
-#pragma unroll
-    for (int u = 0; u < L27_TI; ++u) s[u] = 0.0;
-    // covering tiles (ti + a, tj + b, tk + c), a in {-1, 0}, b, c in {-1, 0, 1}, in this fixed order: the row's cell must exist in that tile's block
-    for (int b = -1; b <= 1; ++b) {
-      if ((b < 0 && (lj >= 2 || tj == 0)) || (b > 0 && (lj < L27_TJ - 2 || tj == G.ntj - 1))) continue;
-      for (int c = -1; c <= 1; ++c) {
-        if ((c < 0 && (lk >= 2 || tk == 0)) || (c > 0 && (lk < L27_TK - 2 || tk == G.ntk - 1))) continue;
-        const int cell = (lj - L27_TJ * b + 2) * L27_SK + (lk - L27_TK * c + 2);
-        if (ti > 0) {  // the tile below: its planes 8, 9 are this tile's 0, 1
-          const double* d = dump + (((int64_t)(ti - 1) * G.ntj + (tj + b)) * G.ntk + (tk + c)) * L27_CELLS + cell;
-          s[0] += d[8 * PC];
-          s[1] += d[9 * PC];
-        }
-        const double* d = dump + (((int64_t)ti * G.ntj + (tj + b)) * G.ntk + (tk + c)) * L27_CELLS + cell;
-#pragma unroll
-        for (int u = 0; u < L27_TI; ++u) s[u] += d[u * PC];
-      }
-    }
-    if (G.plo > 0 && ti == 0) {  // the lower ghost planes (see above): the first two of the row's five i-offsets
-      int l1, n1, l2, n2;
-      l27_range(gj, G.m1, l1, n1);
-      l27_range(gk, G.m2, l2, n2);
-      const int64_t rp = (int64_t)rowptr[(int64_t)gj * G.m2 + gk] - base;
-      double acc = 0.0;
-      for (int a = 0; a < 2; ++a)
-        for (int b = 0; b < n1; ++b)
-          for (int c = 0; c < n2; ++c) {
-            const int64_t xi = l27_xindex(G, G.plo - 2 + a, (int64_t)(gj + l1 + b) * G.m2 + gk + l2 + c);
-            acc += csr_vals[rp + ((int64_t)a * n1 + b) * n2 + c] * (dsc ? x[xi] / dsc[xi] : x[xi]);
-          }
-      s[0] += acc;
-    }
-#pragma unroll
-    for (int u = 0; u < L27_TI; ++u) {
-      if (gi0 + u < G.m0) {
-        const int64_t r = ((int64_t)(gi0 + u) * G.m1 + gj) * G.m2 + gk;
-        double yv = alpha * s[u];
-        if (beta != 0.0) yv += beta * y[r];
-        y[r] = yv;
-        if (dotw) dot_acc += yv * dotw[r];
-      }
-    }
-  }
-  if (partials) {
-    const double bsum = block_reduce_sum(dot_acc, red);
-    if (threadIdx.x == 0) partials[blockIdx.x] = bsum;
-  }
-}
-
-// pass 2, staged (round 4): the same sums in the same order, but every global load of a tile is in flight at once.  The kernel above walks the up to 18
-// covering blocks of a row in masked code blocks, one memory round trip each (every wave holds lanes on the tile's k rim, so every wave takes at least
-// three, the waves on the j rim nine: 3.1 TB/s).  Here the workgroup first copies the 4 320 (row, covering block) values of its tile -- the extended box
-// (8 + 2 planes) x (8 + 2 + 2 lines) x (32 + 2 + 2 columns): own cells, the cells the tile below / beside / diagonal to it holds for these rows -- into
-// LDS, 17 independent loads per thread, and the row owners then add them from LDS in the order of the kernel above (bitwise the same y).
-// Measured (tools/gather_ab.py, C4): 1 % off a 200-iteration solve -- the round trips were not what bounds pass 2 (a 0.18 ms kernel of 0.56 GB).
-#define L27_EJ (L27_TJ + 4)
-#define L27_EK (L27_TK + 4)
-#define L27_ECELLS ((L27_TI + 2) * L27_EJ * L27_EK)  // 4320
-#define L27_EU ((L27_ECELLS + MFEM_BLOCK - 1) / MFEM_BLOCK)
-template <typename RP>
-__global__ __launch_bounds__(MFEM_BLOCK) void k_lat27_gather_st(Lat27Geom G, const double* __restrict__ dump, double* __restrict__ y,
-                                                                  double alpha, double beta, const double* __restrict__ dotw,
-                                                                  double* __restrict__ partials, const int32_t* __restrict__ done_flag,
-                                                                  const RP* __restrict__ rowptr, int base, const double* __restrict__ csr_vals,
-                                                                  const double* __restrict__ x, const double* __restrict__ dsc) {
-  __shared__ double E[L27_ECELLS];
-  __shared__ double red[4];
-  if (done_flag && done_flag[0]) return;
-  double dot_acc = 0.0;
-  const int ntiles = G.nti * G.ntj * G.ntk;
-  const int lk = threadIdx.x & (L27_TK - 1), lj = threadIdx.x >> 5;
-  const int PC = L27_SJ * L27_SK;
-  // extended line / column e -> (neighbour offset, line or column of this tile): 0 .. T - 1 own; T, T + 1: the block below / before holds rows 0, 1;
-  // T + 2, T + 3: the block after holds rows T - 2, T - 1
-  auto ext = [](int e, int T, int& off, int& l) {
-    if (e < T) { off = 0; l = e; }
-    else if (e < T + 2) { off = -1; l = e - T; }
-    else { off = 1; l = e - 4; }
-  };
-  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {  // (the trip count is the workgroup's: every barrier below is reached by all threads)
-    const int tk = tile % G.ntk, t2 = tile / G.ntk, tj = t2 % G.ntj, ti = t2 / G.ntj;
-    double t[L27_EU];
-#pragma unroll
-    for (int u = 0; u < L27_EU; ++u) {
-      const int e = threadIdx.x + u * MFEM_BLOCK;
-      t[u] = 0.0;
-      if (e < L27_ECELLS) {
-        const int ei = e / (L27_EJ * L27_EK), r2 = e - ei * (L27_EJ * L27_EK), ej = r2 / L27_EK, ek = r2 - ej * L27_EK;
-        int b, c, sj, sk;
-        ext(ej, L27_TJ, b, sj);
-        ext(ek, L27_TK, c, sk);
-        const int a = ei < L27_TI ? 0 : -1;  // (planes 8, 9 of the block below are this tile's planes 0, 1: the block's plane index is ei either way)
-        const bool ok = (a == 0 || ti > 0) && (b == 0 || (b < 0 ? tj > 0 : tj < G.ntj - 1)) && (c == 0 || (c < 0 ? tk > 0 : tk < G.ntk - 1));
-        if (ok)
-          t[u] = __builtin_nontemporal_load(dump + (((int64_t)(ti + a) * G.ntj + (tj + b)) * G.ntk + (tk + c)) * L27_CELLS + ei * PC +
-                                            (sj - L27_TJ * b + 2) * L27_SK + (sk - L27_TK * c + 2));
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < L27_EU; ++u) {
-      const int e = threadIdx.x + u * MFEM_BLOCK;
-      if (e < L27_ECELLS) E[e] = t[u];
-    }
-    __syncthreads();
-    const int gj = tj * L27_TJ + lj, gk = tk * L27_TK + lk, gi0 = ti * L27_TI;
-    if (gj < G.m1 && gk < G.m2) {
-      double s[L27_TI];
-#pragma unroll
-      for (int u = 0; u < L27_TI; ++u) s[u] = 0.0;
-      for (int b = -1; b <= 1; ++b) {
-        if ((b < 0 && (lj >= 2 || tj == 0)) || (b > 0 && (lj < L27_TJ - 2 || tj == G.ntj - 1))) continue;
-        const int ej = b == 0 ? lj : b < 0 ? L27_TJ + lj : lj + 4;
-        for (int c = -1; c <= 1; ++c) {
-          if ((c < 0 && (lk >= 2 || tk == 0)) || (c > 0 && (lk < L27_TK - 2 || tk == G.ntk - 1))) continue;
-          const int ek = c == 0 ? lk : c < 0 ? L27_TK + lk : lk + 4;
-          const double* d = E + ej * L27_EK + ek;
-          if (ti > 0) {
-            s[0] += d[8 * (L27_EJ * L27_EK)];
-            s[1] += d[9 * (L27_EJ * L27_EK)];
-          }
-#pragma unroll
-          for (int u = 0; u < L27_TI; ++u) s[u] += d[u * (L27_EJ * L27_EK)];
-        }
-      }
-      if (G.plo > 0 && ti == 0) {  // the lower ghost planes (see k_lat27_gather): the first two of the row's five i-offsets
-        int l1, n1, l2, n2;
-        l27_range(gj, G.m1, l1, n1);
-        l27_range(gk, G.m2, l2, n2);
-        const int64_t rp = (int64_t)rowptr[(int64_t)gj * G.m2 + gk] - base;
-        double acc = 0.0;
-        for (int a = 0; a < 2; ++a)
-          for (int b = 0; b < n1; ++b)
-            for (int c = 0; c < n2; ++c) {
-              const int64_t xi = l27_xindex(G, G.plo - 2 + a, (int64_t)(gj + l1 + b) * G.m2 + gk + l2 + c);
-              acc += csr_vals[rp + ((int64_t)a * n1 + b) * n2 + c] * (dsc ? x[xi] / dsc[xi] : x[xi]);
-            }
-        s[0] += acc;
-      }
-#pragma unroll
-      for (int u = 0; u < L27_TI; ++u) {
-        if (gi0 + u < G.m0) {
-          const int64_t r = ((int64_t)(gi0 + u) * G.m1 + gj) * G.m2 + gk;
-          double yv = alpha * s[u];
-          if (beta != 0.0) yv += beta * y[r];
-          y[r] = yv;
-          if (dotw) dot_acc += yv * dotw[r];
-        }
-      }
-    }
-    __syncthreads();  // the staged values are consumed: the next tile's may land
-  }
-  if (partials) {
-    const double bsum = block_reduce_sum(dot_acc, red);
-    if (threadIdx.x == 0) partials[blockIdx.x] = bsum;
-  }
-}
-
-// The fused CG iteration on the lattice tiles (one rank): pass 2 and the residual update of Jacobi-CG in one kernel.  q = A p is needed twice in a CG iteration --
-// in p . q, which pass 1 now delivers (k_spmv_lat27: dotp), and in r -= alpha q -- so the sums over the covering blocks are formed here, used and never stored:
-// no y written and read back, no separate gather launch (3 of the iteration's vector streams and one launch less).  Staging and summation order are
-// k_lat27_gather_st's; the update arithmetic is k_cg_update's (krylov_cg.hip), operation for operation.
-__global__ __launch_bounds__(MFEM_BLOCK) void k_lat27_gather_cg(Lat27Geom G, const double* __restrict__ dump, LatCgUpdate U) {
-  __shared__ double E[L27_ECELLS];
-  __shared__ double red[4];
-  if (U.flags[F_DONE]) return;
-  const double pap = U.np > 0 ? reduce_partials_bcast(U.pap_partials, U.np, red) : U.S[S_PAP];  // (as k_cg_update / k_cg_pupdate: every workgroup folds the partials itself)
-  const double alpha = U.S[S_RZ0 + U.cur] / pap;
-  const bool exact = U.sw && U.S[S_RR] * U.n_inv <= U.gate2;
-  double rz = 0.0, rr = 0.0;
-  const int ntiles = G.nti * G.ntj * G.ntk;
-  const int lk = threadIdx.x & (L27_TK - 1), lj = threadIdx.x >> 5;
-  const int PC = L27_SJ * L27_SK;
-  auto ext = [](int e, int T, int& off, int& l) {
-    if (e < T) { off = 0; l = e; }
-    else if (e < T + 2) { off = -1; l = e - T; }
-    else { off = 1; l = e - 4; }
-  };
-  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {  // (the trip count is the workgroup's: every barrier below is reached by all threads)
-    const int tk = tile % G.ntk, t2 = tile / G.ntk, tj = t2 % G.ntj, ti = t2 / G.ntj;
-    double t[L27_EU];
-#pragma unroll
-    for (int u = 0; u < L27_EU; ++u) {
-      const int e = threadIdx.x + u * MFEM_BLOCK;
-      t[u] = 0.0;
-      if (e < L27_ECELLS) {
-        const int ei = e / (L27_EJ * L27_EK), r2 = e - ei * (L27_EJ * L27_EK), ej = r2 / L27_EK, ek = r2 - ej * L27_EK;
-        int b, c, sj, sk;
-        ext(ej, L27_TJ, b, sj);
-        ext(ek, L27_TK, c, sk);
-        const int a = ei < L27_TI ? 0 : -1;
-        const bool ok = (a == 0 || ti > 0) && (b == 0 || (b < 0 ? tj > 0 : tj < G.ntj - 1)) && (c == 0 || (c < 0 ? tk > 0 : tk < G.ntk - 1));
-        if (ok)
-          t[u] = __builtin_nontemporal_load(dump + (((int64_t)(ti + a) * G.ntj + (tj + b)) * G.ntk + (tk + c)) * L27_CELLS + ei * PC +
-                                            (sj - L27_TJ * b + 2) * L27_SK + (sk - L27_TK * c + 2));
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < L27_EU; ++u) {
-      const int e = threadIdx.x + u * MFEM_BLOCK;
-      if (e < L27_ECELLS) E[e] = t[u];
-    }
-    __syncthreads();
-    const int gj = tj * L27_TJ + lj, gk = tk * L27_TK + lk, gi0 = ti * L27_TI;
-    if (gj < G.m1 && gk < G.m2) {
-      double s[L27_TI];
-#pragma unroll
-      for (int u = 0; u < L27_TI; ++u) s[u] = 0.0;
-      for (int b = -1; b <= 1; ++b) {
-        if ((b < 0 && (lj >= 2 || tj == 0)) || (b > 0 && (lj < L27_TJ - 2 || tj == G.ntj - 1))) continue;
-        const int ej = b == 0 ? lj : b < 0 ? L27_TJ + lj : lj + 4;
-        for (int c = -1; c <= 1; ++c) {
-          if ((c < 0 && (lk >= 2 || tk == 0)) || (c > 0 && (lk < L27_TK - 2 || tk == G.ntk - 1))) continue;
-          const int ek = c == 0 ? lk : c < 0 ? L27_TK + lk : lk + 4;
-          const double* d = E + ej * L27_EK + ek;
-          if (ti > 0) {
-            s[0] += d[8 * (L27_EJ * L27_EK)];
-            s[1] += d[9 * (L27_EJ * L27_EK)];
-          }
-#pragma unroll
-          for (int u = 0; u < L27_TI; ++u) s[u] += d[u * (L27_EJ * L27_EK)];
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < L27_TI; ++u) {
-        if (gi0 + u < G.m0) {
-          const int64_t i = ((int64_t)(gi0 + u) * G.m1 + gj) * G.m2 + gk;
-          const double av = s[u];  // (A p)[i]
-          double rv, z;
-          if (U.zrec && U.dinv) {  // the array holds z: z -= alpha dinv .* Ap ; r = z ./ dinv for the two dot products only
-            const double dv = U.dinv[i];
-            z = U.r[i] - alpha * (av * dv);
-            U.r[i] = z;
-            rv = dv != 0.0 ? z * mfem_recip_nr(dv) : 0.0;
-          } else {
-            rv = U.r[i] - alpha * av;
-            U.r[i] = rv;
-            z = U.dinv ? rv * U.dinv[i] : rv;
-          }
-          rz += rv * z;
-          if (exact) {
-            const double tt = U.sw[i] * rv;
-            rr += tt * tt;
-          } else {
-            rr += rv * rv;
-          }
-        }
-      }
-    }
-    __syncthreads();  // the staged values are consumed: the next tile's may land
-  }
-  const double s0 = block_reduce_sum(rz, red);
-  const double s1 = block_reduce_sum(rr, red);
-  if (threadIdx.x == 0) {
-    U.partials2[blockIdx.x] = s0;
-    U.partials2[gridDim.x + blockIdx.x] = (U.sw && !exact) ? s1 * U.smax2 : s1;
-  }
-}
-
-static Lat27Geom lat27_geom(const mfem_csr_s* A) {
-  Lat27Geom G{};
-  G.m1 = A->lat_m1;
-  G.m2 = A->lat_m2;
-  G.n = A->n;
-  G.m0 = (int)(A->n / ((int64_t)A->lat_m1 * A->lat_m2));
-  G.plo = A->lat_plo;
-  G.mg = A->lat_m0 > 0 ? A->lat_m0 : G.m0;
-  G.gw = 2;
-  G.nui = (G.m0 + 3) / 4;
-  G.nuj = (G.m1 + 3) / 4;
-  G.nuk = (G.m2 + 7) / 8;
-  G.nti = (G.m0 + L27_TI - 1) / L27_TI;
-  G.ntj = (G.m1 + L27_TJ - 1) / L27_TJ;
-  G.ntk = (G.m2 + L27_TK - 1) / L27_TK;
-  return G;
-}
-
-// A pattern without a lattice hint (lat_fields == 0, no ghost columns): propose one from the columns of row 0 -- the corner node of a lattice
-// numbered plane by plane, line by line -- for the two stencils the lattice-tile layouts know.  Only a proposal: the plans check every entry.
-//   hex-27, one field:      row 0 = 27 columns {a PL + b m2 + c : a, b, c in 0..2}  ->  m2 = col[3], PL = col[9]
-//   27-point, F = 1..3 fields: row 0 = F x 8 columns {g N + a PL + b m2 + c : a, b, c in 0..1}  ->  m2 = col[2], PL = col[4], N = col[8] (F > 1)
-// lat_fields = -1 afterwards if neither fits (so that the question is asked once per pattern).
-int mfem_lattice_from_first_row(mfem_context_s* ctx, mfem_csr_s* A) {
-  if (A->lat_fields != 0) return MFEM_OK;
-  A->lat_fields = -1;
-  A->lat_inferred = 1;
-  if (A->n < 8 || (A->ncols > A->n)) return MFEM_OK;
-  int64_t rp[2] = {0, 0};
-  if (A->rowptr_bits == 64) {
-    MFEM_CHECK_HIP(hipMemcpyAsync(rp, A->rowptr, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  } else {
-    int32_t r32[2];
-    MFEM_CHECK_HIP(hipMemcpyAsync(r32, A->rowptr, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-    rp[0] = r32[0];
-    rp[1] = r32[1];
-  }
-  const int64_t len = rp[1] - rp[0];
-  if (len != 27 && len != 24 && len != 16 && len != 8) return MFEM_OK;
-  int32_t c[27];
-  MFEM_CHECK_HIP(hipMemcpyAsync(c, A->colidx + (rp[0] - A->index_base), (size_t)len * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  for (int i = 0; i < len; ++i) c[i] -= A->index_base;
-  if (c[0] != 0) return MFEM_OK;
-  if (len == 27) {
-    const int64_t m2 = c[3], PL = c[9];
-    if (m2 < 3 || PL < 3 * m2 || PL % m2 != 0 || A->n % PL != 0) return MFEM_OK;
-    for (int a = 0; a < 3; ++a)
-      for (int b = 0; b < 3; ++b)
-        for (int k = 0; k < 3; ++k)
-          if (c[(a * 3 + b) * 3 + k] != a * PL + b * m2 + k) return MFEM_OK;
-    A->lat_fields = 1;
-    A->lat_m2 = (int32_t)m2;
-    A->lat_m1 = (int32_t)(PL / m2);
-    A->lat_m0 = (int32_t)(A->n / PL);
-    A->lat_plo = 0;
-    A->lat_gw = 2;
-  } else {
-    const int F = (int)(len / 8);
-    if (A->n % F != 0) return MFEM_OK;
-    const int64_t m2 = c[2], PL = c[4], N = F > 1 ? c[8] : A->n;
-    if (m2 < 2 || PL < 2 * m2 || PL % m2 != 0 || N < 2 * PL || N % PL != 0 || A->n != F * N) return MFEM_OK;
-    for (int g = 0; g < F; ++g)
-      for (int a = 0; a < 2; ++a)
-        for (int b = 0; b < 2; ++b)
-          for (int k = 0; k < 2; ++k)
-            if (c[g * 8 + (a * 2 + b) * 2 + k] != g * N + a * PL + b * m2 + k) return MFEM_OK;
-    A->lat_fields = F;
-    A->lat_m2 = (int32_t)m2;
-    A->lat_m1 = (int32_t)(PL / m2);
-    A->lat_m0 = (int32_t)(N / PL);
-    A->lat_plo = 0;
-    A->lat_gw = 1;
-  }
-  return MFEM_OK;
-}
-
-// lat27_state: 0 not inspected, -1 not the lattice stencil, 1 structure ok
+// A->lat27.state: 0 not inspected, -1 not the lattice stencil, 1 structure ok
 int mfem_lat27_plan(mfem_context_s* ctx, mfem_csr_s* A) {
-  if (A->lat27_state != 0) return MFEM_OK;
-  if (A->n < g_layout_min_rows_lat27) return MFEM_OK;  // launch-bound sizes stay on the CSR tile kernel
-  A->lat27_state = -1;
-  if (A->lat_fields == 0) {  // a caller-supplied pattern (mfem_csr_create: the reference's own K_J_ptr / K_J): read the lattice off row 0
-    int rc0 = mfem_lattice_from_first_row(ctx, A);
-    if (rc0) return rc0;
-  }
-  if (A->lat_fields != 1 || A->lat_m1 < 3 || A->lat_m2 < 3 || !(A->lat_m1 & 1) || !(A->lat_m2 & 1)) return MFEM_OK;
-  const int64_t PL = (int64_t)A->lat_m1 * A->lat_m2;
-  if (A->n % PL != 0) return MFEM_OK;
-  const int64_t m0 = A->n / PL;
-  if (m0 < 1 || m0 > (1 << 20) || A->max_row_nnz > 125) return MFEM_OK;
-  if (A->ncols > A->n) {  // slab pattern (ghost columns): the hint must place the owned planes in the lattice (on element boundaries) and describe the ghost blocks
-    if (A->lat_m0 < 3 || !(A->lat_m0 & 1) || A->lat_gw != 2 || A->lat_plo < 0 || (A->lat_plo & 1) || A->lat_plo + m0 > A->lat_m0 ||
-        A->ncols != A->n + 4 * PL)
-      return MFEM_OK;
-  } else {
-    if (m0 < 3 || !(m0 & 1)) return MFEM_OK;
-    if (A->lat_m0 > 0 && (A->lat_m0 != m0 || A->lat_plo != 0)) return MFEM_OK;
-  }
-  {  // cheap refusal before the entry-by-entry check: the longest row of the stencil is known from the lattice sizes (a hex-8 lattice with odd point
-     // counts carries the same hint: 27 against 125)
-    const int64_t mg = A->lat_m0 > 0 ? A->lat_m0 : m0;
-    auto w = [](int64_t m) { return m >= 5 ? 5 : 3; };
-    if (A->max_row_nnz != w(mg) * w(A->lat_m1) * w(A->lat_m2)) return MFEM_OK;
-  }
-  int rc = lat27_upload_tables();
+  if (A->lat27.state != 0) return MFEM_OK;
+  if (lat27_eligible(lat27_shape(A)) == 0) return MFEM_OK;  // launch-bound sizes stay on the CSR tile kernel
+  A->lat27.state = -1;
+  int rc = mfem_lattice_hint_from_row0(ctx, A);  // (a caller-supplied pattern: read the lattice off row 0)
   if (rc) return rc;
-  const Lat27Geom G = lat27_geom(A);
-  if ((int64_t)G.nti * G.ntj * G.ntk >= ((int64_t)1 << 28)) return MFEM_OK;
+  const LatShape S = lat27_shape(A);
+  if (lat27_eligible(S) != 1) return MFEM_OK;
+  rc = lat27_upload_tables();
+  if (rc) return rc;
+  const Lat27Geom G = lat27_geom(S);
   int32_t* d_bad = ctx->d_flags + 12;
   MFEM_CHECK_HIP(hipMemsetAsync(d_bad, 0, sizeof(int32_t), ctx->stream));
   const int grid = mfem_grid_for(A->n, MFEM_BLOCK, ctx->num_cus * 16);
-  if (A->rowptr_bits == 64)
-    hipLaunchKernelGGL(k_l27_verify<int64_t>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, (const int64_t*)A->rowptr, A->colidx,
-                       A->index_base, d_bad);
-  else
-    hipLaunchKernelGGL(k_l27_verify<int32_t>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, (const int32_t*)A->rowptr, A->colidx,
-                       A->index_base, d_bad);
+  mfem_by_rowptr(A, [&](auto w) {
+    using RP = decltype(w);
+    hipLaunchKernelGGL(k_l27_verify<RP>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, (const RP*)A->rowptr, A->colidx, A->index_base, d_bad);
+  });
   MFEM_CHECK_LAUNCH();
   MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 12, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  if (ctx->h_flags[12] == 0) A->lat27_state = 1;
+  if (ctx->h_flags[12] == 0) A->lat27.state = 1;
   return MFEM_OK;
 }
 
-static size_t lat27d_vals_doubles(const Lat27Geom& G) { return (size_t)G.nti * G.ntj * ((G.m2 + 7) / 8) * L27D_CUBE_D; }
-static size_t lat27q_vals_doubles(const Lat27Geom& G) { return (size_t)G.nui * G.nuj * G.nuk * L27_UNIT_D; }
-// (the workspace is sized for whichever form needs more: the knob may change between the plan and a bind)
-static size_t lat27_vals_doubles(const Lat27Geom& G) { const size_t a = lat27d_vals_doubles(G), b = lat27q_vals_doubles(G); return a > b ? a : b; }
-static size_t lat27_read_doubles(const Lat27Geom& G) { return g_lat27_det ? lat27d_vals_doubles(G) : lat27q_vals_doubles(G); }  // what pass 1 streams
-static size_t lat27_dump_doubles(const Lat27Geom& G) { return (size_t)G.nti * G.ntj * G.ntk * L27_CELLS; }
-
-// workspace of the layout: the stored entries, then the per-tile y blocks
 size_t mfem_lat27_bytes(const mfem_csr_s* A) {
-  if (A->lat27_state != 1 || !g_lat27_enable || A->n < g_layout_min_rows_lat27) return 0;
-  const Lat27Geom G = lat27_geom(A);
-  return sizeof(double) * (lat27_vals_doubles(G) + lat27_dump_doubles(G) + (size_t)G.nti * G.ntj * G.ntk);  // (+ one dot-product partial per tile: the fused CG iteration)
-}
-
-struct Lat27Bind { double *vals, *dump; const double* src; };
-static void lat27_probe_unbind(mfem_csr_s* A) { mfem_lat27_unbind(A); }
-static void lat27_probe_rebind(mfem_csr_s* A, void* c) {
-  const Lat27Bind* b = (const Lat27Bind*)c;
-  A->lat27_vals = b->vals;
-  A->lat27_dump = b->dump;
-  A->lat27_src = b->src;
+  const LatShape S = lat27_shape(A);
+  return lat_serves(A->lat27.state, lat27_knobs().enable, S) ? lat27_ws_bytes(lat27_geom(S)) : 0;
 }
 
 // Makes the layout copy of `vals` in buf and binds it if the values are symmetric (mfem_sym_probe; else leaves the pattern unbound: the caller
 // binds the sliced layout instead).  scratch: 3 n doubles, left dirty.  Two stream synchronisations (max |a|, the verdict).
 int mfem_lat27_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, double* scratch, bool allow_rem) {
-  mfem_lat27_unbind(A);
-  if (A->lat27_state != 1 || !g_lat27_enable || !buf || !scratch) return MFEM_OK;
-  const Lat27Geom G = lat27_geom(A);
+  LatTiles& T = A->lat27;
+  mfem_lat_unbind(A, T);
+  const Lat27Knobs K = lat27_knobs();
+  if (T.state != 1 || !K.enable || !buf || !scratch) return MFEM_OK;
+  const Lat27Geom G = lat27_geom(lat27_shape(A));
   unsigned long long* d_stats = (unsigned long long*)(ctx->d_flags + 12);
   MFEM_CHECK_HIP(hipMemsetAsync(d_stats, 0, 2 * sizeof(unsigned long long), ctx->stream));
-  A->lat27_det = g_lat27_det ? 1 : 0;  // (the form THIS copy is made in: the launches follow the copy, not the knob)
-  if (A->lat27_det) {
+  T.det = K.det ? 1 : 0;  // (the form THIS copy is made in: the launches follow the copy, not the knob)
+  if (T.det) {
     const int rt = lat27d_upload_tables();
     if (rt) return rt;
-    const int64_t nwork = 8 * (int64_t)G.nti * G.ntj * ((G.m2 + 7) / 8);  // a wave per (cube, node type)
-    const int grid = mfem_grid_for(nwork * 64, MFEM_BLOCK, ctx->num_cus * 16);
-    if (A->rowptr_bits == 64)
-      hipLaunchKernelGGL(k_l27d_fill<int64_t>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, (const int64_t*)A->rowptr, A->index_base, vals, buf, d_stats);
-    else
-      hipLaunchKernelGGL(k_l27d_fill<int32_t>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, (const int32_t*)A->rowptr, A->index_base, vals, buf, d_stats);
-  } else {
-  const int64_t nunits = (int64_t)G.nui * G.nuj * G.nuk;
-  const int grid = mfem_grid_for(nunits * 64, MFEM_BLOCK, ctx->num_cus * 16);
-  if (A->rowptr_bits == 64)
-    hipLaunchKernelGGL(k_l27_fill<int64_t>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, (const int64_t*)A->rowptr, A->index_base,
-                       vals, buf, d_stats);
-  else
-    hipLaunchKernelGGL(k_l27_fill<int32_t>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, (const int32_t*)A->rowptr, A->index_base,
-                       vals, buf, d_stats);
   }
+  // a wave per (cube, node type) / per unit
+  const int64_t nwaves = T.det ? 8 * (int64_t)G.nti * G.ntj * ((G.m2 + 7) / 8) : (int64_t)G.nui * G.nuj * G.nuk;
+  const int grid = mfem_grid_for(nwaves * 64, MFEM_BLOCK, ctx->num_cus * 16);
+  mfem_by_rowptr(A, [&](auto w) {
+    using RP = decltype(w);
+    hipLaunchKernelGGL(T.det ? &k_l27d_fill<RP> : &k_l27_fill<RP>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, (const RP*)A->rowptr, A->index_base,
+                       vals, buf, d_stats);
+  });
   MFEM_CHECK_LAUNCH();
   MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 12, d_stats, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
   MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
   double amax;
   memcpy(&amax, ctx->h_flags + 14, sizeof(double));
-  Lat27Bind B{buf, buf + lat27_vals_doubles(G), vals};
-  lat27_probe_rebind(A, &B);
+  T.vals = buf;
+  T.dump = buf + lat27_vals_doubles(G);
+  T.src = vals;
   double asym = 1.0;
-  int rc = mfem_sym_probe(ctx, A, vals, scratch, amax, lat27_probe_unbind, lat27_probe_rebind, &B, &asym, allow_rem ? 1 : 0);
-  A->lat27_asym = asym;
-  if (rc || !(asym <= 4e-13)) {  // not symmetric (or NaN): the sliced layout serves this solve
-    mfem_lat27_unbind(A);
+  const int rc = mfem_sym_probe(ctx, A, &T, vals, scratch, amax, &asym, allow_rem ? 1 : 0);
+  T.asym = asym;
+  if (rc || !lat_accepts(asym)) {  // not symmetric (or NaN): the sliced layout serves this solve
+    mfem_lat_unbind(A, T);
     return rc;
   }
-  A->lat27_dsc = dsc;
-  A->lat27_scaled = dsc ? 1 : 0;
+  T.dsc = dsc;
+  T.scaled = dsc ? 1 : 0;
   return MFEM_OK;
-}
-
-void mfem_lat27_unbind(mfem_csr_s* A) {
-  if (A->lat27_vals) A->rem_active = 0;  // (the remainder belongs to the bind)
-  A->lat27_vals = nullptr;
-  A->lat27_dump = nullptr;
-  A->lat27_src = nullptr;
-  A->lat27_dsc = nullptr;
 }
 
 // returns 1 if launched, 0 if another kernel should be used, <0 on error
 int mfem_spmv_lat27_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, const double* x, double* y, double alpha,
                            double beta, const double* dotw, double* partials, int* n_partials, const int32_t* done_flag, int part) {
-  if (!A->lat27_vals || vals != A->lat27_src) return 0;
+  const LatTiles& T = A->lat27;
+  if (!T.vals || vals != T.src) return 0;
   if (n_partials) *n_partials = 0;
-  const Lat27Geom G = lat27_geom(A);
-  const int ntiles = G.nti * G.ntj * G.ntk;
-  // Split SpMV of a slab (mfem_spmv_halo): part 1 = the tiles that stage no ghost plane of the upper neighbour (the i-layers below
-  // mfem_lat_first_ghost_layer: a contiguous prefix of the i-major tile list), launched beside the halo exchange; part 2 = the remaining layers and
-  // the gather pass (which reads the lower ghost planes for the first owned rows), launched after it.  part 0 = everything.
-  const int tb = mfem_lat_first_ghost_layer(G.m0, G.gw, G.nti, G.plo + G.m0 < G.mg) * G.ntj * G.ntk;
-  const int tile0 = part == 2 ? tb : 0;
-  const int tcount = part == 1 ? tb : ntiles - tile0;
-  const int chunk = (tcount + 7) / 8;
-  if (!y) {
-    // the fused CG iteration (mfem_lat27_cg_fused): pass 1 alone, the tiles' blocks stay in the dump for mfem_lat27_gather_cg_update, x . A x comes out
-    // as one partial per tile behind the dump
-    MFEM_REQUIRE(part == 0 && dotw == x && alpha == 1.0 && beta == 0.0 && !A->lat27_dsc, "lattice tiles: pass 1 alone serves only the fused CG iteration");
-    double* dotp = A->lat27_dump + lat27_dump_doubles(G);
-    if (A->lat27_det)
-      hipLaunchKernelGGL(k_spmv_lat27d, dim3(8 * chunk), dim3(512), 0, ctx->stream, G, A->lat27_vals, x, (const double*)nullptr, A->lat27_dump, done_flag, 0,
-                         ntiles, dotp);
-    else
-      hipLaunchKernelGGL(k_spmv_lat27, dim3(8 * chunk), dim3(512), 0, ctx->stream, G, A->lat27_vals, x, (const double*)nullptr, A->lat27_dump, done_flag, 0,
-                         ntiles, dotp);
+  const Lat27Geom G = lat27_geom(lat27_shape(A));
+  const LatPart P = lat_part_tiles(G.m0, G.gw, G.nti, G.ntj, G.ntk, G.plo + G.m0 < G.mg, part);
+  // y == nullptr: the fused CG iteration (mfem_lat27_cg_fused) -- pass 1 alone, the tiles' blocks stay in the dump for mfem_lat27_gather_cg_update,
+  // x . A x comes out as one partial per tile behind the dump (the caller reads them where mfem_lat27_dot_partials says)
+  if (!y) MFEM_REQUIRE(part == 0 && dotw == x && alpha == 1.0 && beta == 0.0 && !T.dsc, "lattice tiles: pass 1 alone serves only the fused CG iteration");
+  if (P.tcount > 0) {
+    hipLaunchKernelGGL(T.det ? k_spmv_lat27d : k_spmv_lat27, dim3(P.grid), dim3(512), 0, ctx->stream, G, (const double*)T.vals, x, T.dsc, T.dump, done_flag,
+                       P.tile0, P.tcount, y ? (double*)nullptr : T.dump + lat27_dot_offset(G));
     MFEM_CHECK_LAUNCH();
-    (void)partials;  // (the caller reads the partials where mfem_lat27_dot_partials says)
-    if (n_partials) *n_partials = ntiles;
+  }
+  if (!y) {
+    if (n_partials) *n_partials = lat27_dot_partials(G);
     if (!ctx->probe_active) ++g_lat27_count;
     return 1;
   }
-  if (tcount > 0) {
-    if (A->lat27_det)
-      hipLaunchKernelGGL(k_spmv_lat27d, dim3(8 * chunk), dim3(512), 0, ctx->stream, G, A->lat27_vals, x, A->lat27_dsc, A->lat27_dump, done_flag, tile0, tcount,
-                         (double*)nullptr);
-    else
-      hipLaunchKernelGGL(k_spmv_lat27, dim3(8 * chunk), dim3(512), 0, ctx->stream, G, A->lat27_vals, x, A->lat27_dsc, A->lat27_dump, done_flag, tile0, tcount,
-                         (double*)nullptr);
-    MFEM_CHECK_LAUNCH();
-  }
   if (part == 1) return 1;  // (the gather pass belongs to part 2)
-  // persistent grid = what is resident (mfem_resident_per_cu; the staged gather holds 3 workgroups per CU at 145 VGPRs, the plain one 6: both were launched with 8)
   int grid = 1;
-#define L27_GATHER(KERNEL, RP)                                                                                                              \
-  do {                                                                                                                                      \
-    int cap = ctx->num_cus * mfem_resident_per_cu(reinterpret_cast<const void*>(&KERNEL<RP>), MFEM_BLOCK, 0, 3);                            \
-    if (cap > MFEM_MAX_PARTIALS) cap = MFEM_MAX_PARTIALS;                                                                                   \
-    grid = ntiles < cap ? ntiles : cap;                                                                                                     \
-    hipLaunchKernelGGL(KERNEL<RP>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, A->lat27_dump, y, alpha, beta, dotw, partials, done_flag, \
-                       (const RP*)A->rowptr, A->index_base, A->lat27_src, x, A->lat27_dsc);                                                 \
-  } while (0)
-  if (g_lat27_gather_staged) {
-    if (A->rowptr_bits == 64) L27_GATHER(k_lat27_gather_st, int64_t); else L27_GATHER(k_lat27_gather_st, int32_t);
-  } else {
-    if (A->rowptr_bits == 64) L27_GATHER(k_lat27_gather, int64_t); else L27_GATHER(k_lat27_gather, int32_t);
-  }
-#undef L27_GATHER
-  MFEM_CHECK_LAUNCH();
+  int rc = mfem_lat27_gather_launch(ctx, A, G, lat27_knobs().gather_staged, x, y, alpha, beta, dotw, partials, done_flag, &grid);
+  if (rc) return rc;
   if (n_partials && partials) *n_partials = grid;
   if (A->rem_active) {  // A = S + N: the skew remainder of the few nonsymmetric rows (spmv_rem.hip)
-    const int rcr = mfem_rem_apply(ctx, A, x, A->lat27_dsc, y, alpha, dotw, partials, n_partials, done_flag);
-    if (rcr) return rcr;
+    rc = mfem_rem_apply(ctx, A, x, T.dsc, y, alpha, dotw, partials, n_partials, done_flag);
+    if (rc) return rc;
   }
   if (!ctx->probe_active) ++g_lat27_count;
   return 1;
 }
 
-// bytes one SpMV of the layout moves by design: the stored entries, x as the tiles stage it, the y blocks written and read again, y
+// Accounting.  What pass 1 streams is read off the KNOB, not off the bound copy's form (nothing need be bound when bench.py asks).
 int64_t mfem_lat27_design_bytes(const mfem_csr_s* A) {
-  const Lat27Geom G = lat27_geom(A);
-  const int64_t tiles = (int64_t)G.nti * G.ntj * G.ntk;
-  return (int64_t)lat27_read_doubles(G) * 8 + tiles * L27_CELLS * 8 * (A->lat27_scaled ? 4 : 3) + A->n * 8 + mfem_rem_design_bytes(A);
+  return lat27_design_bytes(lat27_geom(lat27_shape(A)), lat27_knobs().det, A->lat27.scaled != 0) + mfem_rem_design_bytes(A);
 }
-int64_t mfem_lat27_entries(const mfem_csr_s* A) { return (int64_t)lat27_read_doubles(lat27_geom(A)); }
+int64_t mfem_lat27_entries(const mfem_csr_s* A) { return lat27_entries(lat27_geom(lat27_shape(A)), lat27_knobs().det); }
 
-// ---- the fused CG iteration (krylov_cg.hip, mfem_cg_pass): pass 1 alone (mfem_spmv_halo with y = nullptr), the dot-product partials, pass 2 + residual update
+// ---- the fused CG iteration (krylov_cg.hip, mfem_cg_pass): pass 1 alone (mfem_spmv_halo with y = nullptr), the dot-product partials; pass 2 + residual
+// update: spmv_lat27_gather.hip
 bool mfem_lat27_cg_fused(const mfem_context_s* ctx, const mfem_csr_s* A, const double* vals) {
-  return g_lat27_cg_fused && A->lat27_vals && vals == A->lat27_src && !A->lat27_dsc && !ctx->comm && !A->rem_active;
+  return lat27_cg_fusable(lat27_knobs(), A->lat27.vals && vals == A->lat27.src, A->lat27.dsc != nullptr, ctx->comm != nullptr, A->rem_active != 0);
 }
 const double* mfem_lat27_dot_partials(const mfem_csr_s* A, int* np) {
-  const Lat27Geom G = lat27_geom(A);
-  *np = G.nti * G.ntj * G.ntk;
-  return A->lat27_dump + lat27_dump_doubles(G);
+  const Lat27Geom G = lat27_geom(lat27_shape(A));
+  *np = lat27_dot_partials(G);
+  return A->lat27.dump + lat27_dot_offset(G);
 }
-int mfem_lat27_gather_cg_update(mfem_context_s* ctx, mfem_csr_s* A, const LatCgUpdate& U, int grid) {
-  const Lat27Geom G = lat27_geom(A);
-  hipLaunchKernelGGL(k_lat27_gather_cg, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, (const double*)A->lat27_dump, U);
-  MFEM_CHECK_LAUNCH();
-  return MFEM_OK;
-}
-// (accounting for bench.py) is the fused CG iteration on, and what pass 1 alone moves by design: the stored entries, x as the tiles stage it, the y blocks written
-extern "C" int mfem_debug_lat27_cg_fused(void) { return g_lat27_cg_fused; }
+// (accounting for bench.py) is the fused CG iteration on, and what pass 1 alone moves by design
+extern "C" int mfem_debug_lat27_cg_fused(void) { return lat27_knobs().cg_fused ? 1 : 0; }
 extern "C" int64_t mfem_debug_lat27_pass1_bytes(mfem_csr A) {
-  if (!A || A->lat27_state != 1) return -1;
-  const Lat27Geom G = lat27_geom(A);
-  return (int64_t)lat27_read_doubles(G) * 8 + (int64_t)G.nti * G.ntj * G.ntk * L27_CELLS * 8 * 2;
+  if (!A || A->lat27.state != 1) return -1;
+  return lat27_pass1_bytes(lat27_geom(lat27_shape(A)), lat27_knobs().det);
 }

@@ -15,49 +15,35 @@
 //     block leaves as one contiguous run per tile.
 //   * pass 2 (k_lat8_gather) sums the up to 18 tile blocks that cover a row in a fixed order, applies alpha / beta and the fused dot product.
 //   * the pattern must be the full stencil (checked entry by entry once), the values of a solve symmetric (a probe product of the layout against
-//     the CSR kernel, mfem_sym_probe in spmv_lat27.hip, within 4e-13 of the largest entry; the diagonal-slotted layout serves the solve otherwise).  Results equal the CSR kernel's to round-off, not
+//     the CSR kernel, sym_probe.hip, within LAT_SYM_GATE of the row's diagonal entry; the diagonal-slotted layout serves the solve otherwise).  Results equal the CSR kernel's to round-off, not
 //     bitwise, and not bitwise from run to run (order of the LDS adds of different waves).  mfem_debug_set_lat8(0) switches the layout off.
+// The host decisions (knobs, eligibility, geometry, sizes, the split of a slab's launch): lat_decide.h, where the tile sizes L8_* are too.
+#include <type_traits>
 #include "blas1.h"
 #include "layouts.h"
-#include "spmv_lat_tables.h"
-
-#define L8_TI 8
-#define L8_TJ 8
-#define L8_TK 16
-#define L8_SJ (L8_TJ + 2)
-#define L8_SK (L8_TK + 2)
-#define L8_PI (L8_SJ * L8_SK)            // 180
-#define L8_FC ((L8_TI + 1) * L8_PI)      // cells per field: 1620
 
 typedef double m_d2 __attribute__((ext_vector_type(2)));
 
 extern std::atomic<int64_t> g_layout_min_rows_dia;  // spmv_ell.hip
-static std::atomic<int> g_lat8_enable{1};
-static std::atomic<int> g_lat8_gather_staged{0};  // bit 2 of mfem_debug_set_lat8: 1 = pass 2 by k_lat8_gather_st (measured on C3, tools/gather_ab.py: 1.6 % SLOWER per solve than k_lat8_gather -- its two barriers and the LDS round trip cost more than the round trips it saves on these small tiles; the hex-27 tiles gain 1 %)
-static std::atomic<int> g_lat8_one_field_everywhere{0};  // bit 1 of mfem_debug_set_lat8: the query / diagnostic SpMV entry also report and take mode 5 for ONE field
+static std::atomic<int> g_lat8_word{LAT8_WORD_DEFAULT};  // mfem_debug_set_lat8 (Lat8Knobs)
+static Lat8Knobs lat8_knobs() { return lat8_knobs_decode(g_lat8_word); }
+static LatShape lat8_shape(const mfem_csr_s* A) { return mfem_lat_shape(A, g_layout_min_rows_dia); }
 static std::atomic<long long> g_lat8_count{0};
 extern "C" long long mfem_debug_lat8_spmv_count(void) { return g_lat8_count; }
-extern "C" double mfem_debug_lat8_asymmetry(mfem_csr A) { return A ? A->lat8_asym : -1.0; }
+extern "C" double mfem_debug_lat8_asymmetry(mfem_csr A) { return A ? A->lat8.asym : -1.0; }
 extern "C" int mfem_debug_set_lat8(int enable) try {
   ++mfem_debug_epoch;
-  g_lat8_enable = enable & 1;
-  g_lat8_one_field_everywhere = (enable >> 1) & 1;
-  g_lat8_gather_staged = (enable >> 2) & 1;
+  g_lat8_word = enable & 7;
   return MFEM_OK;
 } MFEM_API_CATCH("mfem_debug_set_lat8")
-// One field: cg! keeps the bitwise patch sweep of mode 2 (it moves the same bytes); the solvers that work on A D^-1 (idrs!, bicgstabl_GS!, cgs2!) cannot
-// use that sweep -- the scaled copy is not symmetric -- and take the tiles.  The layout query and the diagnostic SpMV entry answer for cg!.
-bool mfem_lat8_for_method(const mfem_csr_s* A, bool is_cg) { return A->lat_fields != 1 || !is_cg || g_lat8_one_field_everywhere; }
+bool mfem_lat8_for_method(const mfem_csr_s* A, bool is_cg) { return lat8_for_method(A->lat_fields, is_cg, lat8_knobs()); }
+// f(std::integral_constant<int, F>{}) for the F = 1..3 fields the kernels are instantiated for
+template <typename Fn> static inline void lat8_by_fields(int F, Fn&& f) {
+  if (F == 1) f(std::integral_constant<int, 1>{});
+  else if (F == 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 3>{});
+}
 
-struct Lat8Geom {
-  int m0, m1, m2;     // OWNED nodes per direction (m0 = owned lattice planes of a slab)
-  int nui, nuj, nuk;  // units of 4 x 4 x 4 nodes
-  int nti, ntj, ntk;  // tiles of 8 x 8 x 16 nodes
-  int64_t N;          // m0 * m1 * m2 owned nodes
-  // slab: the owned planes are [plo, plo + m0) of a lattice of mg planes; x carries, behind the F N owned entries, per field a low and a high
-  // block of gw ghost planes (brick_xindex); plo = 0, mg = m0 for a whole brick
-  int plo, mg, gw, F;
-};
 // local x index of field f at GLOBAL plane gi (owned or ghost), in-plane position ip
 __device__ __forceinline__ int64_t l8_xindex(const Lat8Geom& G, int f, int gi, int64_t ip) {
   const int64_t PL = (int64_t)G.m1 * G.m2;
@@ -331,9 +317,8 @@ __global__ __launch_bounds__(512, 4) void k_spmv_lat8(Lat8Geom G, const double* 
   __shared__ double ys[F * L8_FC];
   if (done_flag && done_flag[0]) return;
   // (this launch covers the tiles [tile0, tile0 + tcount) of the i-major tile list: all of them, or the interior / boundary part of a slab's SpMV)
-  const int chunk = (tcount + 7) >> 3;
-  const int tsub = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);  // every XCD walks a contiguous eighth of the tiles
-  if ((int)(blockIdx.x >> 3) >= chunk || tsub >= tcount) return;           // (the whole workgroup leaves: no barrier is left waiting)
+  int tsub;
+  if (!mfem_xcd_tile(tcount, tsub)) return;
   const int tile = tile0 + tsub;
   const int tk = tile % G.ntk, t2 = tile / G.ntk, tj = t2 % G.ntj, ti = t2 / G.ntj;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -389,6 +374,7 @@ __global__ __launch_bounds__(512, 4) void k_spmv_lat8(Lat8Geom G, const double* 
 // pass 2: a thread owns a (j, k) position of the tile and four of its planes, for the F fields
 // Slab with a lower neighbour (G.plo > 0): the rows of the first owned plane also have entries towards the ghost plane below.  No stored entry mirrors
 // onto them (the rows that would belong to the neighbour rank), so they are taken from the caller's CSR values here: 9 F products per row of that plane.
+// (This block and the epilogue are written out in both gathers: as inlined helpers they changed the instructions of k_lat8_gather.)
 template <typename RP, int F>
 __global__ __launch_bounds__(MFEM_BLOCK) void k_lat8_gather(Lat8Geom G, const double* __restrict__ dump, double* __restrict__ y, double alpha,
                                                               double beta, const double* __restrict__ dotw, double* __restrict__ partials,
@@ -576,197 +562,116 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_lat8_gather_st(Lat8Geom G, const
   }
 }
 
-static Lat8Geom lat8_geom(const mfem_csr_s* A) {
-  Lat8Geom G{};
-  G.F = A->lat_fields;
-  G.m1 = A->lat_m1;
-  G.m2 = A->lat_m2;
-  G.N = A->n / G.F;
-  G.m0 = (int)(G.N / ((int64_t)A->lat_m1 * A->lat_m2));
-  G.plo = A->lat_plo;
-  G.mg = A->lat_m0 > 0 ? A->lat_m0 : G.m0;
-  G.gw = A->lat_gw > 0 ? A->lat_gw : 1;
-  G.nui = (G.m0 + 3) / 4;
-  G.nuj = (G.m1 + 3) / 4;
-  G.nuk = (G.m2 + 3) / 4;
-  G.nti = (G.m0 + L8_TI - 1) / L8_TI;
-  G.ntj = (G.m1 + L8_TJ - 1) / L8_TJ;
-  G.ntk = (G.m2 + L8_TK - 1) / L8_TK;
-  return G;
-}
-// doubles of one stored pair of i-stacked units (the stream of a wave of pass 1: 2 x nsteps steps of 64 lanes)
-static int lat8_pair_doubles(int F) { return 2 * (F == 1 ? l8_nsteps(1) : F == 2 ? l8_nsteps(2) : l8_nsteps(3)) * 64; }
-
-// lat8_state: 0 not inspected, -1 not the F-field stencil, 1 structure ok
+// A->lat8.state: 0 not inspected, -1 not the F-field stencil, 1 structure ok
 int mfem_lat8_plan(mfem_context_s* ctx, mfem_csr_s* A) {
-  if (A->lat8_state != 0) return MFEM_OK;
-  if (A->n < g_layout_min_rows_dia) return MFEM_OK;  // launch-bound sizes stay on the CSR tile kernel
-  A->lat8_state = -1;
-  if (A->lat_fields == 0) {  // a caller-supplied pattern: read the lattice off row 0 (spmv_lat27.hip)
-    int rc0 = mfem_lattice_from_first_row(ctx, A);
-    if (rc0) return rc0;
-  }
-  const int F = A->lat_fields;
-  if (F < 1 || F > 3 || A->lat_m1 < 2 || A->lat_m2 < 2 || A->n % F != 0) return MFEM_OK;
-  const int64_t PL = (int64_t)A->lat_m1 * A->lat_m2, N = A->n / F;
-  if (N % PL != 0) return MFEM_OK;
-  const int64_t m0 = N / PL;
-  if (m0 < 1 || m0 > (1 << 20) || A->max_row_nnz > 27 * F) return MFEM_OK;
-  if (A->ncols > A->n) {  // slab pattern (ghost columns): the hint must say where the owned planes sit in the lattice and how the ghost blocks are laid out
-    if (A->lat_m0 < m0 || A->lat_gw != 1 || A->lat_plo < 0 || A->lat_plo + m0 > A->lat_m0 || A->ncols != A->n + 2 * F * PL) return MFEM_OK;
-  } else if (A->lat_m0 > 0 && (A->lat_m0 != m0 || A->lat_plo != 0)) {
-    return MFEM_OK;
-  }
-  {  // cheap refusal before the entry-by-entry check: the longest row of the stencil is known from the lattice sizes
-    const int64_t mg = A->lat_m0 > 0 ? A->lat_m0 : m0;
-    auto w = [](int64_t m) { return m >= 3 ? 3 : (int)m; };
-    if (A->max_row_nnz != F * w(mg) * w(A->lat_m1) * w(A->lat_m2)) return MFEM_OK;
-  }
-  const Lat8Geom G = lat8_geom(A);
-  if ((int64_t)G.nti * G.ntj * G.ntk >= ((int64_t)1 << 28)) return MFEM_OK;
+  if (A->lat8.state != 0) return MFEM_OK;
+  if (lat8_eligible(lat8_shape(A)) == 0) return MFEM_OK;  // launch-bound sizes stay on the CSR tile kernel
+  A->lat8.state = -1;
+  const int rc = mfem_lattice_hint_from_row0(ctx, A);  // (a caller-supplied pattern: read the lattice off row 0)
+  if (rc) return rc;
+  const LatShape S = lat8_shape(A);
+  if (lat8_eligible(S) != 1) return MFEM_OK;
+  const Lat8Geom G = lat8_geom(S);
   int32_t* d_bad = ctx->d_flags + 12;
   MFEM_CHECK_HIP(hipMemsetAsync(d_bad, 0, sizeof(int32_t), ctx->stream));
   const int grid = mfem_grid_for(A->n, MFEM_BLOCK, ctx->num_cus * 16);
-  if (A->rowptr_bits == 64)
-    hipLaunchKernelGGL(k_l8_verify<int64_t>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, (const int64_t*)A->rowptr, A->colidx, A->index_base,
-                       d_bad);
-  else
-    hipLaunchKernelGGL(k_l8_verify<int32_t>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, (const int32_t*)A->rowptr, A->colidx, A->index_base,
-                       d_bad);
+  mfem_by_rowptr(A, [&](auto w) {
+    using RP = decltype(w);
+    hipLaunchKernelGGL(k_l8_verify<RP>, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, (const RP*)A->rowptr, A->colidx, A->index_base, d_bad);
+  });
   MFEM_CHECK_LAUNCH();
   MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 12, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  if (ctx->h_flags[12] == 0) A->lat8_state = 1;
+  if (ctx->h_flags[12] == 0) A->lat8.state = 1;
   return MFEM_OK;
 }
 
-static size_t lat8_vals_doubles(const Lat8Geom& G) { return (size_t)((G.nui + 1) / 2) * G.nuj * G.nuk * lat8_pair_doubles(G.F); }
-static size_t lat8_dump_doubles(const Lat8Geom& G) { return (size_t)G.nti * G.ntj * G.ntk * G.F * L8_FC; }
-
 size_t mfem_lat8_bytes(const mfem_csr_s* A) {
-  if (A->lat8_state != 1 || !g_lat8_enable || A->n < g_layout_min_rows_dia) return 0;
-  const Lat8Geom G = lat8_geom(A);
-  return sizeof(double) * (lat8_vals_doubles(G) + lat8_dump_doubles(G));
+  const LatShape S = lat8_shape(A);
+  return lat_serves(A->lat8.state, lat8_knobs().enable, S) ? lat8_ws_bytes(lat8_geom(S)) : 0;
 }
 
-struct Lat8Bind { double *vals, *dump; const double* src; };
-static void lat8_probe_unbind(mfem_csr_s* A) { mfem_lat8_unbind(A); }
-static void lat8_probe_rebind(mfem_csr_s* A, void* c) {
-  const Lat8Bind* b = (const Lat8Bind*)c;
-  A->lat8_vals = b->vals;
-  A->lat8_dump = b->dump;
-  A->lat8_src = b->src;
-}
-
-#define L8_DISPATCH_F(F_, CALL) \
-  do {                          \
-    if ((F_) == 1) { CALL(1); } \
-    else if ((F_) == 2) { CALL(2); } \
-    else { CALL(3); }           \
-  } while (0)
-
-// Makes the layout copy of `vals` in buf and binds it if the values are symmetric (mfem_sym_probe, spmv_lat27.hip).  dsc: right Jacobi scaling the
+// Makes the layout copy of `vals` in buf and binds it if the values are symmetric (mfem_sym_probe).  dsc: right Jacobi scaling the
 // SpMV applies to x (nullptr: none); only the pointer is kept, it may be filled after the bind.  scratch: ncols + 2 n doubles, left dirty.
 int mfem_lat8_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, double* scratch, bool allow_rem) {
-  mfem_lat8_unbind(A);
-  if (A->lat8_state != 1 || !g_lat8_enable || !buf || !scratch) return MFEM_OK;
-  const Lat8Geom G = lat8_geom(A);
+  LatTiles& T = A->lat8;
+  mfem_lat_unbind(A, T);
+  if (T.state != 1 || !lat8_knobs().enable || !buf || !scratch) return MFEM_OK;
+  const Lat8Geom G = lat8_geom(lat8_shape(A));
   unsigned long long* d_stats = (unsigned long long*)(ctx->d_flags + 12);
   MFEM_CHECK_HIP(hipMemsetAsync(d_stats, 0, 2 * sizeof(unsigned long long), ctx->stream));
   const int64_t nunits = (int64_t)G.nui * G.nuj * G.nuk;
   const int grid = mfem_grid_for(nunits * 64, MFEM_BLOCK, ctx->num_cus * 16);
-#define L8_FILL(FF)                                                                                                                             \
-  if (A->rowptr_bits == 64)                                                                                                                     \
-    hipLaunchKernelGGL((k_l8_fill<int64_t, FF>), dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, (const int64_t*)A->rowptr, A->index_base, vals, \
-                       buf, d_stats);                                                                                                           \
-  else                                                                                                                                          \
-    hipLaunchKernelGGL((k_l8_fill<int32_t, FF>), dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, (const int32_t*)A->rowptr, A->index_base, vals, \
-                       buf, d_stats)
-  L8_DISPATCH_F(G.F, L8_FILL);
-#undef L8_FILL
+  lat8_by_fields(G.F, [&](auto f) {
+    mfem_by_rowptr(A, [&](auto w) {
+      using RP = decltype(w);
+      hipLaunchKernelGGL((k_l8_fill<RP, decltype(f)::value>), dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, (const RP*)A->rowptr, A->index_base, vals,
+                         buf, d_stats);
+    });
+  });
   MFEM_CHECK_LAUNCH();
   MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 12, d_stats, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
   MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
   double amax;
   memcpy(&amax, ctx->h_flags + 14, sizeof(double));
-  Lat8Bind B{buf, buf + lat8_vals_doubles(G), vals};
-  lat8_probe_rebind(A, &B);
+  T.vals = buf;
+  T.dump = buf + lat8_vals_doubles(G);
+  T.src = vals;
   double asym = 1.0;
-  int rc = mfem_sym_probe(ctx, A, vals, scratch, amax, lat8_probe_unbind, lat8_probe_rebind, &B, &asym, allow_rem ? G.F : 0);
-  A->lat8_asym = asym;
-  if (rc || !(asym <= 4e-13)) {  // not symmetric (or NaN): the other layouts serve this solve
-    mfem_lat8_unbind(A);
+  const int rc = mfem_sym_probe(ctx, A, &T, vals, scratch, amax, &asym, allow_rem ? G.F : 0);
+  T.asym = asym;
+  if (rc || !lat_accepts(asym)) {  // not symmetric (or NaN): the other layouts serve this solve
+    mfem_lat_unbind(A, T);
     return rc;
   }
-  A->lat8_dsc = dsc;
-  A->lat8_scaled = dsc ? 1 : 0;
+  T.dsc = dsc;
+  T.scaled = dsc ? 1 : 0;
   return MFEM_OK;
-}
-
-void mfem_lat8_unbind(mfem_csr_s* A) {
-  if (A->lat8_vals) A->rem_active = 0;  // (the remainder belongs to the bind)
-  A->lat8_vals = nullptr;
-  A->lat8_dump = nullptr;
-  A->lat8_src = nullptr;
-  A->lat8_dsc = nullptr;
 }
 
 // returns 1 if launched, 0 if another kernel should be used, <0 on error
 int mfem_spmv_lat8_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, const double* x, double* y, double alpha, double beta,
                           const double* dotw, double* partials, int* n_partials, const int32_t* done_flag, int part) {
-  if (!A->lat8_vals || vals != A->lat8_src) return 0;
+  const LatTiles& T = A->lat8;
+  if (!T.vals || vals != T.src) return 0;
   if (n_partials) *n_partials = 0;
-  const Lat8Geom G = lat8_geom(A);
-  const int ntiles = G.nti * G.ntj * G.ntk;
-  // split SpMV of a slab: see mfem_spmv_lat27_launch -- part 1 = the i-layers of tiles that stage no ghost plane, part 2 = the rest + the gather pass
-  const int tb = mfem_lat_first_ghost_layer(G.m0, G.gw, G.nti, G.plo + G.m0 < G.mg) * G.ntj * G.ntk;
-  const int tile0 = part == 2 ? tb : 0;
-  const int tcount = part == 1 ? tb : ntiles - tile0;
-  const int chunk = (tcount + 7) / 8;
-#define L8_PASS1_CH(FF, CH_)                                                                                                                         \
-  hipLaunchKernelGGL((k_spmv_lat8<FF, CH_>), dim3(8 * chunk), dim3(512), 0, ctx->stream, G, A->lat8_vals, x, A->lat8_dsc, A->lat8_dump, done_flag, tile0, \
-                     tcount)
-#define L8_PASS1(FF) L8_PASS1_CH(FF, 8)  // (12 and 16 steps per buffer were measured: the same time to 0.3 %)
-  if (tcount > 0) {
-    L8_DISPATCH_F(G.F, L8_PASS1);
+  const Lat8Geom G = lat8_geom(lat8_shape(A));
+  // split SpMV of a slab (lat_part_tiles): part 1 = the i-layers of tiles that stage no ghost plane, part 2 = the rest + the gather pass
+  const LatPart P = lat_part_tiles(G.m0, G.gw, G.nti, G.ntj, G.ntk, G.plo + G.m0 < G.mg, part);
+  if (P.tcount > 0) {
+    lat8_by_fields(G.F, [&](auto f) {  // (8 steps per register buffer; 12 and 16 were measured: the same time to 0.3 %)
+      hipLaunchKernelGGL((k_spmv_lat8<decltype(f)::value, 8>), dim3(P.grid), dim3(512), 0, ctx->stream, G, (const double*)T.vals, x, T.dsc, T.dump, done_flag,
+                         P.tile0, P.tcount);
+    });
     MFEM_CHECK_LAUNCH();
   }
-#undef L8_PASS1
   if (part == 1) return 1;  // (the gather pass belongs to part 2)
-  // persistent grid = what is resident (mfem_resident_per_cu): the F = 1 kernel holds 6 workgroups per CU, F = 2 five, F = 3 four -- launched with 8 per CU
+  // persistent grid = what is resident (lat_gather_grid): the F = 1 kernel holds 6 workgroups per CU, F = 2 five, F = 3 four -- launched with 8 per CU
   // (until round 5) the one- and two-field gathers ran two rounds for the work of 1.33 / 1.6
   int grid = 1;
-#define L8_GATHER(KERNEL, RP, FF)                                                                                                             \
-  do {                                                                                                                                        \
-    int cap = ctx->num_cus * mfem_resident_per_cu(reinterpret_cast<const void*>(&KERNEL<RP, FF>), MFEM_BLOCK, 0, 4);                          \
-    if (cap > MFEM_MAX_PARTIALS) cap = MFEM_MAX_PARTIALS;                                                                                     \
-    grid = ntiles < cap ? ntiles : cap;                                                                                                       \
-    hipLaunchKernelGGL((KERNEL<RP, FF>), dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, A->lat8_dump, y, alpha, beta, dotw, partials, done_flag, \
-                       (const RP*)A->rowptr, A->index_base, A->lat8_src, x, A->lat8_dsc);                                                     \
-  } while (0)
-#define L8_PASS2(FF)                                                                                                             \
-  if (g_lat8_gather_staged) {                                                                                                   \
-    if (A->rowptr_bits == 64) L8_GATHER(k_lat8_gather_st, int64_t, FF); else L8_GATHER(k_lat8_gather_st, int32_t, FF);          \
-  } else {                                                                                                                      \
-    if (A->rowptr_bits == 64) L8_GATHER(k_lat8_gather, int64_t, FF); else L8_GATHER(k_lat8_gather, int32_t, FF);                \
-  }
-  L8_DISPATCH_F(G.F, L8_PASS2);
-#undef L8_PASS2
-#undef L8_GATHER
+  const bool staged = lat8_knobs().gather_staged;
+  lat8_by_fields(G.F, [&](auto f) {
+    mfem_by_rowptr(A, [&](auto w) {
+      using RP = decltype(w);
+      constexpr int F = decltype(f)::value;
+      auto kernel = staged ? &k_lat8_gather_st<RP, F> : &k_lat8_gather<RP, F>;
+      grid = lat_gather_grid(ctx->num_cus, mfem_resident_per_cu(reinterpret_cast<const void*>(kernel), MFEM_BLOCK, 0, 4), G.nti * G.ntj * G.ntk);
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(MFEM_BLOCK), 0, ctx->stream, G, (const double*)T.dump, y, alpha, beta, dotw, partials, done_flag,
+                         (const RP*)A->rowptr, A->index_base, T.src, x, T.dsc);
+    });
+  });
   MFEM_CHECK_LAUNCH();
   if (n_partials && partials) *n_partials = grid;
   if (A->rem_active) {  // A = S + N: the skew remainder of the few nonsymmetric rows (spmv_rem.hip)
-    const int rcr = mfem_rem_apply(ctx, A, x, A->lat8_dsc, y, alpha, dotw, partials, n_partials, done_flag);
+    const int rcr = mfem_rem_apply(ctx, A, x, T.dsc, y, alpha, dotw, partials, n_partials, done_flag);
     if (rcr) return rcr;
   }
   if (!ctx->probe_active) ++g_lat8_count;
   return 1;
 }
 
-// bytes one SpMV of the layout moves by design: the stored entries, x (and d) as the tiles stage it, the y blocks written and read again, y
+// bytes one SpMV of the layout moves by design, and the entries it reads (lat_decide.h)
 int64_t mfem_lat8_design_bytes(const mfem_csr_s* A) {
-  const Lat8Geom G = lat8_geom(A);
-  const int64_t tiles = (int64_t)G.nti * G.ntj * G.ntk;
-  return (int64_t)lat8_vals_doubles(G) * 8 + tiles * G.F * L8_FC * 8 * (A->lat8_scaled ? 4 : 3) + A->n * 8 + mfem_rem_design_bytes(A);
+  return lat8_design_bytes(lat8_geom(lat8_shape(A)), A->lat8.scaled != 0) + mfem_rem_design_bytes(A);
 }
-int64_t mfem_lat8_entries(const mfem_csr_s* A) { return (int64_t)lat8_vals_doubles(lat8_geom(A)); }
+int64_t mfem_lat8_entries(const mfem_csr_s* A) { return lat8_entries(lat8_geom(lat8_shape(A))); }

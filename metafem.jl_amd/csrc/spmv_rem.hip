@@ -1,4 +1,4 @@
-// A = S + N: the sparse skew remainder of the symmetric lattice-tile layouts (solver layout modes 4 and 5, spmv_lat27.hip / spmv_lat8.hip).
+// A = S + N: the sparse skew remainder of the symmetric lattice-tile layouts (solver layout modes 4 and 5, spmv_lat27.hip / spmv_lat8.hip; their probe: sym_probe.hip).
 //
 // The tiles store one triangle of the matrix (per node the diagonal block's upper entries and the entries towards the "upper" lattice neighbours)
 // and mirror it, i.e. they apply S = U + U^T - D.  That is the caller's matrix only if its values are symmetric -- and the reference's OWN way of
@@ -10,7 +10,7 @@
 // as a small CSR of its own, applied after the tiles' gather pass:  y = S x + N x = A x  to round-off (one rounding in the difference).
 //
 // Which rows: the symmetry probe (mfem_sym_probe) already measures, per row, |(S x - A x)_r| / |a_rr| for a random-sign probe vector; the rows above
-// the gate (4e-13) are the rows of N.  The bind accepts when they are at most n / 8 AND the probe repeated with N applied passes the same gate
+// the gate (LAT_SYM_GATE) are the rows of N.  The bind accepts when they are at most n / 8 AND the probe repeated with N applied passes the same gate
 // on every row -- the acceptance test is the same as for symmetric values, only the operator it is applied to is S + N.
 // Everything here is generic in the pattern: the mirrored entry of (r, c) is found by searching row c of the caller's CSR for column r.
 #include "blas1.h"
