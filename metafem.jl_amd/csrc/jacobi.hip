@@ -205,8 +205,11 @@ extern "C" int mfem_jacobi2_by_column(mfem_context ctx, mfem_csr A, const double
     int rc = mfem_comm_halo_reduce(ctx, d);
     if (rc) return rc;
   }
-  hipLaunchKernelGGL(k_sqrt_inplace, dim3(mfem_grid_for(A->n, MFEM_BLOCK, ctx->num_cus * 8)), dim3(MFEM_BLOCK), 0,
-                     ctx->stream, A->n, d);
+  // without an exchange (one rank, or no communicator on a slab pattern) every entry is this matrix's own column sum: the root of all ncols
+  // of them; with one the owners take the root and the ghost entries are overwritten by the halo
+  const int64_t nroot = slab ? A->n : ncols;
+  hipLaunchKernelGGL(k_sqrt_inplace, dim3(mfem_grid_for(nroot, MFEM_BLOCK, ctx->num_cus * 8)), dim3(MFEM_BLOCK), 0,
+                     ctx->stream, nroot, d);
   MFEM_CHECK_LAUNCH();
   if (slab) return mfem_comm_halo(ctx, d);  // ghost entries = the owners' d
   return MFEM_OK;

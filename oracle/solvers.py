@@ -93,33 +93,36 @@ class JacobiP:
         return b
 
 
-def jacobi_by_diagonal(A: sp.csr_matrix) -> np.ndarray:
-    """Jacobi_By_Diagonal (:122-130): d_i = |K_ii|, rows without a stored diagonal keep 1."""
+def jacobi_by_diagonal(A: sp.csr_matrix, guard_zero: bool = False) -> np.ndarray:
+    """Jacobi_By_Diagonal (:122-130): d_i = |K_ii|, rows without a stored diagonal keep 1.  guard_zero: a stored diagonal equal to +-0.0 keeps 1
+    as well -- the product's rule (csrc/jacobi.hip); the reference takes |0| there and divides by it."""
     d = np.ones(A.shape[0])
     rows = np.repeat(np.arange(A.shape[0]), np.diff(A.indptr))
     on = rows == A.indices
+    if guard_zero:
+        on &= A.data != 0.0
     d[rows[on]] = np.abs(A.data[on])
     return d
 
 
-def pr_jacobi(A: sp.csr_matrix, normalized_by_column: bool = False) -> JacobiP:
+def pr_jacobi(A: sp.csr_matrix, normalized_by_column: bool = False, guard_zero: bool = False) -> JacobiP:
     """Pr_Jacobi! (:103-120): scales the COLUMNS of A in place, returns x -> x ./ d."""
     if normalized_by_column:
         d = np.zeros(A.shape[1])
         np.add.at(d, A.indices, A.data ** 2)  # Jacobi2_By_Colomn :132-139
         d **= 0.5
     else:
-        d = jacobi_by_diagonal(A)
+        d = jacobi_by_diagonal(A, guard_zero)
     A.data /= d[A.indices]  # Mat_Div_Jacobi :141-148
     return JacobiP(d)
 
 
-def pl_jacobi(A: sp.csr_matrix, normalized_by_row: bool = False) -> JacobiP:
+def pl_jacobi(A: sp.csr_matrix, normalized_by_row: bool = False, guard_zero: bool = False) -> JacobiP:
     """Pl_Jacobi (:155-168)."""
     if normalized_by_row:
         d = np.sqrt(np.asarray(A.multiply(A).sum(axis=1)).ravel())  # Jacobi_By_Row :170-177
     else:
-        d = jacobi_by_diagonal(A)
+        d = jacobi_by_diagonal(A, guard_zero)
     return JacobiP(d)
 
 
@@ -327,12 +330,12 @@ def solver_lu_cpu(rowptr, colidx, K_vals, residue) -> np.ndarray:
 
 
 def solve_cg_jacobi(rowptr, colidx, K_vals, residue, converge_tol, maxiter, max_pass=1,
-                    info: Optional[SolveInfo] = None) -> np.ndarray:
+                    info: Optional[SolveInfo] = None, guard_zero: bool = False) -> np.ndarray:
     """The added CG path: standard PCG with M = |diag K| on the UNSCALED matrix, wrapped in
     the reference's restart/true-residual loop (02_Preconditioner.jl:50-73)."""
     n = residue.size
     A = csr(rowptr, colidx, np.asarray(K_vals, dtype=np.float64), n)
-    d = jacobi_by_diagonal(A)
+    d = jacobi_by_diagonal(A, guard_zero)
     b = residue
     r = b.copy()
     x = np.zeros(n)

@@ -284,16 +284,26 @@ def test_jacobi_kernels(mf):
     M = solvers.csr(rowptr, cols, vals, n) + sp.diags(rng.standard_normal(n) + 3.0)
     M = M.tocsr()
     M.sort_indices()
-    # knock the diagonal out of a few rows: those keep d = 1 (02_Preconditioner.jl:110,122-130)
+    # knock the diagonal out of a few rows: those keep d = 1 (02_Preconditioner.jl:110,122-130); store an exact zero on a few others: those keep
+    # d = 1 as well (the guarded rule of csrc/jacobi.hip, oracle: guard_zero=True)
+    rows = np.repeat(np.arange(n), np.diff(M.indptr))
+    dslot = np.flatnonzero(rows == M.indices)
+    assert dslot.size == n and np.all(M.data[dslot] != 0.0)
+    gone, zeroed = dslot[[5, 130, 1777, 2999]], dslot[[0, 64, 2500]]
+    M.data[zeroed] = 0.0
+    keep = np.ones(M.nnz, dtype=bool)
+    keep[gone] = False
+    M = sp.csr_matrix((M.data[keep], M.indices[keep], np.concatenate([[0], np.cumsum(np.bincount(rows[keep], minlength=n))])), shape=(n, n))
+    d = solvers.jacobi_by_diagonal(M, guard_zero=True)
+    assert np.count_nonzero(d == 1.0) == 7 and np.all(d[[5, 130, 1777, 2999, 0, 64, 2500]] == 1.0)
     A = mf.FEM_SpMat_CSR(torch.tensor(M.indptr.astype(np.int32), device="cuda"),
                          torch.tensor(M.indices.astype(np.int32), device="cuda"), n)
     v = torch.tensor(M.data, device="cuda")
-    assert np.array_equal(mf.jacobi_by_diagonal(A, v).cpu().numpy(), solvers.jacobi_by_diagonal(M))
+    assert np.array_equal(mf.jacobi_by_diagonal(A, v).cpu().numpy(), d)
     col = np.sqrt(np.asarray(M.multiply(M).sum(axis=0)).ravel())
     row = np.sqrt(np.asarray(M.multiply(M).sum(axis=1)).ravel())
     assert np.allclose(mf.jacobi2_by_column(A, v).cpu().numpy(), col, rtol=1e-13)
     assert np.allclose(mf.jacobi_by_row(A, v).cpu().numpy(), row, rtol=1e-13)
-    d = solvers.jacobi_by_diagonal(M)
     mf.mat_div_jacobi_(A, v, torch.tensor(d, device="cuda"))
     assert np.array_equal(v.cpu().numpy(), M.data / d[M.indices])
 
