@@ -151,6 +151,9 @@ int mfem_csr_spmv_bytes(mfem_context ctx, mfem_csr A, int64_t* bytes, int64_t* c
 /* y = alpha A x + beta y through that layout, conversion of `vals` included (diagnostic: what the Krylov loop computes). */
 int mfem_spmv_solver_layout(mfem_context ctx, mfem_csr A, const double* vals, const double* x, double* y, double alpha,
                             double beta);
+/* ... with the dot product x . y the kernel accumulates beside the product (cg!'s p . Ap), its per-workgroup partial sums added on the host. */
+int mfem_spmv_solver_layout_dot(mfem_context ctx, mfem_csr A, const double* vals, const double* x, double* y, double alpha,
+                                double beta, double* xdoty);
 
 /* ---- S1: the linear solver seam  fem_domain.linear_solver(globalfield) -------------------- */
 typedef enum {

@@ -40,9 +40,9 @@ int mfem_debug_set(const char* key, int64_t a, int64_t b);
  * symmetric sweep kernels off; bit 23 the workgroup-tile sweep (k_spmv_sym27) instead of the wave-private patch sweep (k_spmv_symp); bit 26 rows
  * outside the swept planes in a launch of their own; bit 27 the patch-major copy made from the slot-major copy in a second pass; bit 28 the layout
  * copy without its software pipeline; bit 29 the swept rows by the copy's row tiles instead of k_symp_fill; bit 30 the symmetry of the swept rows
- * by the check pass instead of the fill's fingerprint.
- * RETIRED, accepted and ignored: bits 4-7 (variants of k_spmv_ell), every value of bits 16-19 other than 8 (variants of k_spmv_dia) and bits 24-25
- * (workgroup size of k_spmv_dia) -- the sweeps of round 1 (profiles/r01_spmv_sweep.txt) chose the kernels that remain.
+ * by the check pass instead of the fill's fingerprint; bits 24 / 25 force one / two bands of four lattice lines per patch of the patch sweep
+ * (neither: the bind decides by size, mfem_symp_bands_wanted).
+ * RETIRED, accepted and ignored: bits 4-7 (variants of k_spmv_ell), every value of bits 16-19 other than 8 (variants of k_spmv_dia) -- the sweeps of round 1 (profiles/r01_spmv_sweep.txt) chose the kernels that remain.
  * These knobs are read when a layout is BOUND (every mfem_solve and mfem_spmv_solver_layout binds its own): a product runs the kernel its bind
  * recorded; only the launch geometry (bits 8-15, 20, 26) is read per product.  Set them before the solve. */
 /* ^ key "ell": mfem_debug_set("ell", a, b) with (int enable) = (a[, b]) */

@@ -193,6 +193,7 @@ SIGNATURES = {
     "mfem_debug_lat8_spmv_count": (c_int64, []),
     "mfem_debug_lat8_asymmetry": (C.c_double, [c_void_p]),
     "mfem_spmv_solver_layout": (c_int, [P, P, P, P, P, c_double, c_double]),
+    "mfem_spmv_solver_layout_dot": (c_int, [P, P, P, P, P, c_double, c_double, C.POINTER(c_double)]),
     "mfem_csr_solver_layout": (c_int, [P, P, C.POINTER(c_int32), C.POINTER(c_int32), C.POINTER(c_int64), C.POINTER(c_int64)]),
     "mfem_csr_solver_layout_entries": (c_int, [P, P, C.POINTER(c_int64), C.POINTER(c_int32)]),
     "mfem_csr_solver_layout_bytes": (c_int, [P, P, C.POINTER(c_int64)]),

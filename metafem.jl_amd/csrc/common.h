@@ -196,6 +196,7 @@ struct mfem_csr_s {
   int64_t symp_PL;          // rows per lattice plane (m1 * m2)
   int symp_p0, symp_p1;     // regular lattice planes [p0, p1) (plane = row / PL): the rows the sweep computes
   int symp_NS, symp_NPk;    // strips of 4 lines, patches of 32 points per line
+  int symp_B;               // bands (strips) per patch of the bound patch-major copy: decided once per bind (dia_bind), 0 while none is bound
   double* symp_vals;        // not owned (solver workspace, behind ell_vals): [plane - p0][patch][27 x 128 + edge block]; set while dia_kernel is the patch sweep
   // solver layout mode 3 for rows of uneven length: the row-sorted sliced layout (spmv_sell.hip) or its node-blocked form (spmv_bsell.hip) -- sell.form
   // tells which, and each form has its own members; sell.state 0 = not planned, -1 = no, 1 = ready.  The record and the decisions: sell_decide.h

@@ -167,10 +167,10 @@ extern "C" int mfem_csr_solver_layout_bytes(mfem_context ctx, mfem_csr A, int64_
 // y = alpha A x + beta y through the layout mfem_solve would use for this pattern with cg! (the one-off conversion of `vals` included): the tiles if
 // these values pass their probe, the row layout otherwise.  A test / diagnostic entry point -- production SpMVs of caller-supplied values go
 // through mfem_spmv_csr.
-extern "C" int mfem_spmv_solver_layout(mfem_context ctx, mfem_csr A, const double* vals, const double* x, double* y, double alpha,
-                                       double beta) try {
+static int spmv_solver_layout(mfem_context ctx, mfem_csr A, const double* vals, const double* x, double* y, double alpha, double beta, double* xdoty) {
   MFEM_REQUIRE(ctx && A, "null handle");
   MFEM_REQUIRE(A->n == 0 || (x && y && (A->nnz == 0 || vals)), "null vector");
+  if (xdoty) *xdoty = 0.0;
   if (A->n == 0) return MFEM_OK;
   struct Release { mfem_csr_s* A; ~Release() { mfem_layout_unbind(A); } } release{A};  // nothing stays bound on any way out
   mfem_layout_plan_s P;
@@ -188,5 +188,26 @@ extern "C" int mfem_spmv_solver_layout(mfem_context ctx, mfem_csr A, const doubl
     if (!rc && P.rows != MFEM_LAYOUT_CSR) rc = mfem_layout_bind(ctx, A, P.rows, vals, (double*)ctx->ws, nullptr, nullptr, nullptr, false);
     if (rc) return rc;
   }
-  return mfem_spmv_launch(ctx, A, vals, x, y, alpha, beta, nullptr, nullptr, nullptr, nullptr);
+  if (!xdoty) return mfem_spmv_launch(ctx, A, vals, x, y, alpha, beta, nullptr, nullptr, nullptr, nullptr);
+  // with the product's fused x . y, as cg! takes p . Ap: one partial sum per workgroup, added on the host in workgroup order
+  int np = 0;
+  rc = mfem_spmv_launch(ctx, A, vals, x, y, alpha, beta, x, ctx->d_partials, &np, nullptr);
+  if (rc) return rc;
+  MFEM_REQUIRE(np > 0 && np <= MFEM_MAX_PARTIALS, "the product left no partial sums");
+  std::vector<double> h((size_t)np);
+  MFEM_CHECK_HIP(hipMemcpyAsync(h.data(), ctx->d_partials, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, ctx->stream));
+  MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  double s = 0.0;
+  for (double v : h) s += v;
+  *xdoty = s;
+  return MFEM_OK;
+}
+extern "C" int mfem_spmv_solver_layout(mfem_context ctx, mfem_csr A, const double* vals, const double* x, double* y, double alpha,
+                                       double beta) try {
+  return spmv_solver_layout(ctx, A, vals, x, y, alpha, beta, nullptr);
 } MFEM_API_CATCH("mfem_spmv_solver_layout")
+extern "C" int mfem_spmv_solver_layout_dot(mfem_context ctx, mfem_csr A, const double* vals, const double* x, double* y, double alpha,
+                                           double beta, double* xdoty) try {
+  MFEM_REQUIRE(xdoty, "null argument");
+  return spmv_solver_layout(ctx, A, vals, x, y, alpha, beta, xdoty);
+} MFEM_API_CATCH("mfem_spmv_solver_layout_dot")

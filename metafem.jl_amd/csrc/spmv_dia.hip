@@ -77,7 +77,7 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_dia_vals(int64_t n, int64_t npad
   const DiaOffsets& O = *Op;
   extern __shared__ double lds[];
   const int64_t slo = pv ? (int64_t)Gm.p0 * Gm.PL : 0, shi = pv ? (int64_t)Gm.p1 * Gm.PL : 0;  // swept rows
-  const int spNP = Gm.NS * Gm.NPk;
+  const int spNP = Gm.NR * Gm.NPk, spB = Gm.B > 0 ? Gm.B : 1, spMAIN = sp_main(spB), spLOW = sp_low(spB);
   const int64_t spT = (int64_t)spNP * (Gm.p1 - Gm.p0);
   // LPR = 2: a wave takes 32 rows at a time, two lanes per row -- lanes 0..31 walk their row's entries forward through the first half of
   // the diagonal list, lanes 32..63 walk them backward through the second half.  A lane per row (64 rows per tile) needs 12 x 64 x K
@@ -223,12 +223,13 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_dia_vals(int64_t n, int64_t npad
       int64_t mainoff = 0, lowoff = 0, edgeoff = 0;
       if (sw) {
         const int p = (int)(r / Gm.PL), rem = (int)(r - (int64_t)p * Gm.PL), jj = rem / Gm.m2, kk = rem - jj * Gm.m2;
-        line = jj % SP_L;
+        const int L = SP_L * spB, band = (jj % L) / SP_L;  // the row's patch row, band and line of the band
+        line = jj % L;
         pcol = kk % SP_W;
-        const int64_t step = (int64_t)(p - Gm.p0) * spNP + (jj / SP_L) * Gm.NPk + kk / SP_W;
-        mainoff = step * SP_MAIN + line * SP_W + pcol;
-        lowoff = spT * SP_MAIN + step * SP_LOW + line * SP_W + pcol;
-        edgeoff = step * SP_MAIN + 14 * SP_ROWS;
+        const int64_t step = (int64_t)(p - Gm.p0) * spNP + (jj / L) * Gm.NPk + kk / SP_W;
+        mainoff = step * spMAIN + band * 14 * SP_ROWS + (line - band * SP_L) * SP_W + pcol;
+        lowoff = spT * spMAIN + step * spLOW + band * 13 * SP_ROWS + (line - band * SP_L) * SP_W + pcol;
+        edgeoff = step * spMAIN + spB * 14 * SP_ROWS;
       }
       int j = half ? len - 1 : 0;
 #pragma unroll
@@ -247,7 +248,7 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_dia_vals(int64_t n, int64_t npad
           DIA_ST(pv + (sl < 13 ? lowoff + sl * SP_ROWS : mainoff + (sl - 13) * SP_ROWS), v);
           if (sl == 13) out[ell_base(r, K) + 13 * ELL_B] = v;  // the diagonal (offset 0 is the 14th of the 27 lattice offsets)
           if (half == 0 && t < 13) {                           // the edge block entry the row owns for this lower slot, if any
-            const int e = sp_edge_of(t, line, pcol);
+            const int e = sp_edge_of(t, line, pcol, spB);  // (line: counted over the patch's bands)
             if (e >= 0) pv[edgeoff + e] = v;
           }
         }
@@ -310,7 +311,7 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (launched with two waves per workgroup)
   double* T = lds + (size_t)w * (2 * RUN);
   double* E = lds + 2 * (2 * RUN);  // the step's edge block (SP_EPAD entries; zero between steps: entries of rows outside the lattice and the padding stay 0)
-  const int spNP = Gm.NS * Gm.NPk;
+  const int spNP = Gm.NR * Gm.NPk, spB = Gm.B, spMAIN = sp_main(spB), spLOW = sp_low(spB), spEPAD = sp_epad(spB);
   const int64_t spT = (int64_t)spNP * (Gm.p1 - Gm.p0);
   const int h = lane >> 5, c = lane & (SP_W - 1);
   const int32_t PL = (int32_t)Gm.PL, m2 = Gm.m2;
@@ -318,12 +319,15 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
     const uint32_t xl = __builtin_amdgcn_readfirstlane((uint32_t)(uint64_t)x), xh = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
     return (int64_t)(((uint64_t)xh << 32) | xl);
   };
-  for (int i = threadIdx.x; i < SP_EPAD; i += 128) E[i] = 0.0;
+  for (int i = threadIdx.x; i < spEPAD; i += 128) E[i] = 0.0;
   __syncthreads();
   for (int64_t step = blockIdx.x; step < spT; step += gridDim.x) {  // (every barrier below is reached by both waves: the trip count is the workgroup's)
     const int kp = (int)(step % Gm.NPk);
     const int64_t q = step / Gm.NPk;
-    const int strip = (int)(q % Gm.NS), pl = (int)(q / Gm.NS);
+    const int prow = (int)(q % Gm.NR), pl = (int)(q / Gm.NR);
+    double* const pe = pv + step * spMAIN + spB * 14 * SP_ROWS;
+    for (int band = 0; band < spB; ++band) {  // the strips of the patch one after the other: their edge entries meet in E (a strip past the lattice: nlines = 0)
+    const int strip = prow * spB + band;
     const int jj0 = strip * SP_L + 2 * w, kk0 = kp * SP_W;
     const int ncol = m2 - kk0 < SP_W ? m2 - kk0 : SP_W, nlines = Gm.m1 - jj0 < 2 ? (Gm.m1 - jj0 < 1 ? 0 : 1) : 2;  // (the last strip may end before this wave's lines)
     const int64_t rb = (int64_t)(Gm.p0 + pl) * Gm.PL + (int64_t)jj0 * m2 + kk0;  // lane 0's row
@@ -337,9 +341,8 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
     const bool valid = c < ncol && h < nlines;
     const int64_t r = rb + (int64_t)h * m2 + c;
     const int line = 2 * w + h;
-    double* const pm = pv + step * SP_MAIN + line * SP_W + c;
-    double* const plo = pv + spT * SP_MAIN + step * SP_LOW + line * SP_W + c;
-    double* const pe = pv + step * SP_MAIN + 14 * SP_ROWS;
+    double* const pm = pv + step * spMAIN + band * 14 * SP_ROWS + line * SP_W + c;
+    double* const plo = pv + spT * spMAIN + step * spLOW + band * 13 * SP_ROWS + line * SP_W + c;
     const double* Tr = T + lane * 27;
     double sc[27];
     double srow = 1.0;
@@ -442,7 +445,7 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
         }
         if (sl < 13) {
           DIA_ST(plo + sl * SP_ROWS, v);
-          const int e = sp_edge_of(sl, line, c);
+          const int e = sp_edge_of(sl, band * SP_L + line, c, spB);
           if (e >= 0) E[e] = v;
         } else {
           DIA_ST(pm + (sl - 13) * SP_ROWS, v);
@@ -450,8 +453,10 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
         }
       }
     }
+    __builtin_amdgcn_wave_barrier();  // (the wave's staging area is overwritten by its next strip)
+    }
     __syncthreads();
-    for (int i = threadIdx.x; i < SP_EPAD; i += 128) {
+    for (int i = threadIdx.x; i < spEPAD; i += 128) {
       DIA_ST(pe + i, E[i]);
       E[i] = 0.0;
     }
@@ -528,17 +533,18 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_spmv_dia_outside(int64_t n, int6
 // lattice lines of odd length: the lane pair at the line's end holds the last point and a cell outside the lattice, which no row writes
 // and the sweep reads as a structurally absent entry -- an explicit zero in all 27 slots of every step of the last patch column
 __global__ __launch_bounds__(MFEM_BLOCK) void k_symp_zero_odd(SympGeom Gm, double* __restrict__ pv) {
-  const int NP = Gm.NS * Gm.NPk, nplanes = Gm.p1 - Gm.p0;
+  const int NP = Gm.NR * Gm.NPk, nplanes = Gm.p1 - Gm.p0, B = Gm.B, MAINB = sp_main(B), LOWB = sp_low(B);
   const int64_t T = (int64_t)NP * nplanes, cells = (int64_t)nplanes * Gm.NS * SP_L * 27;
   const int col = Gm.m2 - (Gm.NPk - 1) * SP_W;  // first column past the line in the last patch column (odd, < SP_W)
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < cells; t += (int64_t)gridDim.x * blockDim.x) {
     const int s = (int)(t % 27), line = (int)((t / 27) % SP_L);
     const int64_t q = t / (27 * SP_L);
     const int strip = (int)(q % Gm.NS), pl = (int)(q / Gm.NS);
-    const int64_t step = (int64_t)pl * NP + (int64_t)strip * Gm.NPk + (Gm.NPk - 1);
+    const int band = strip % B;
+    const int64_t step = (int64_t)pl * NP + (int64_t)(strip / B) * Gm.NPk + (Gm.NPk - 1);
     const int idx = line * SP_W + col;
-    if (s < 13) pv[T * SP_MAIN + step * SP_LOW + s * SP_ROWS + idx] = 0.0;
-    else pv[step * SP_MAIN + (s - 13) * SP_ROWS + idx] = 0.0;
+    if (s < 13) pv[T * MAINB + step * LOWB + band * 13 * SP_ROWS + s * SP_ROWS + idx] = 0.0;
+    else pv[step * MAINB + band * 14 * SP_ROWS + (s - 13) * SP_ROWS + idx] = 0.0;
   }
 }
 
@@ -701,7 +707,7 @@ int mfem_dia_copy(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double
   const bool fast = lpr == 1 && !dsc && pvals && A->n < ((int64_t)1 << 31) && G.PL < ((int64_t)1 << 30) && G.m1 >= 3 && G.m2 >= 3 && g_ell.dia_fast;
   // the software-pipelined staging: a lane per row, rows of at most 28 entries, no scaling pass (bit 28 turns it off)
   const bool pipe = lpr == 1 && !dsc && A->ell_K <= 28 && g_ell.dia_pipe && !fast;
-  const int64_t ft = (int64_t)(G.p1 - G.p0) * G.NS * G.NPk;  // the fill: patch steps, one workgroup of two waves each
+  const int64_t ft = (int64_t)(G.p1 - G.p0) * G.NR * G.NPk;  // the fill: patch steps, one workgroup of two waves each
   int gf = (int)(ft < (int64_t)ctx->num_cus * 20 ? ft : (int64_t)ctx->num_cus * 20);  // (5 workgroups are resident per CU: four rounds)
   if (gf < 1) gf = 1;
   unsigned long long* fpr = fast && want_fp ? (unsigned long long*)(ctx->d_flags + 16) : nullptr;
@@ -717,7 +723,7 @@ int mfem_dia_copy(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double
     if (!fast) return MFEM_OK;
     if (fpr) MFEM_CHECK_HIP(hipMemsetAsync(fpr, 0, sizeof(unsigned long long), ctx->stream));
     const auto kf = ssym ? k_symp_fill<RP, true> : k_symp_fill<RP, false>;
-    hipLaunchKernelGGL(kf, dim3(gf), dim3(128), sizeof(double) * (2 * (2 * SP_W * 27) + SP_EPAD), ctx->stream, A->n, A->ell_K, (const RP*)A->rowptr,
+    hipLaunchKernelGGL(kf, dim3(gf), dim3(128), sizeof(double) * (2 * (2 * SP_W * 27) + sp_epad(G.B > 0 ? G.B : 1)), ctx->stream, A->n, A->ell_K, (const RP*)A->rowptr,
                        A->colidx, vals, A->index_base, O, A->sym_cls, buf, G, pvals, ssym, fpr);
     MFEM_CHECK_LAUNCH();
     return MFEM_OK;

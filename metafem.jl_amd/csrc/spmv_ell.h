@@ -35,6 +35,7 @@ struct SympGeom {
   int64_t PL, nx;
   int m1, m2, p0, p1, NS, NPk;
   int nseg;  // runs per patch: a run = one patch swept through nplanes / nseg consecutive planes
+  int B, NR; // bands of SP_L lines per patch (1 or 2); patch rows = ceil(NS / B): NR * NPk patches per plane (NS: strips of SP_L lines)
 };
 // the rows outside the swept planes, taken by the sweep's waves after their runs (unsplit SpMV): per-row code on the slot-major copy
 struct SympTail {
@@ -176,6 +177,7 @@ struct EllKnobs {
   std::atomic<int> xcd{0};               // bit 20: each XCD walks a contiguous eighth of the rows (k_spmv_dia; needs a grid that is a multiple of 8)
   std::atomic<int> sym{1};               // bit 22 clears it: no symmetric sweep kernel
   std::atomic<int> symp{1};              // bit 23 clears it: the workgroup-tile sweep (k_spmv_sym27) instead of the wave-private patch sweep (k_spmv_symp)
+  std::atomic<int> symp_bands{0};        // bits 24 / 25 force one / two bands of four lines per patch (0: mfem_symp_bands_wanted decides by size)
   std::atomic<int> symp_tail{1};         // bit 26 clears it: the rows outside the swept planes in a launch of their own (as in a split SpMV)
   std::atomic<int> symp_direct{1};       // bit 27 clears it: the patch-major copy made from the slot-major copy in a second pass (k_symp_bind)
   std::atomic<int> dia_pipe{1};          // bit 28 clears it: the layout copy (k_dia_vals) without its software pipeline
@@ -201,7 +203,9 @@ int mfem_dia_launch_outside(mfem_context_s* ctx, mfem_csr_s* A, const SpmvArgs& 
 void mfem_sym_plan(mfem_csr_s* A, const int32_t* off, int lc, int64_t m2, int64_t PL, int64_t run_lo, int64_t run_hi);
 bool mfem_sym_wanted(const mfem_csr_s* A, DiaKernel k);
 SympGeom mfem_symp_geom(const mfem_context_s* ctx, const mfem_csr_s* A);
-int64_t mfem_symp_steps(const mfem_csr_s* A);
+int64_t mfem_symp_steps(const mfem_csr_s* A, int B = 0);  // patch steps of the swept planes with B bands per patch (0: mfem_symp_bands)
+int mfem_symp_bands_wanted(const mfem_csr_s* A);  // the band count a bind of the patch sweep would take now
+int mfem_symp_bands(const mfem_csr_s* A);         // the bound copy's band count; unbound: what a bind would take
 int64_t mfem_sym_entries(const mfem_context_s* ctx, const mfem_csr_s* A, DiaKernel k);
 int mfem_sym_verdict(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const double* buf, double* pvals, const SympGeom& G, bool direct, bool fp_made, bool* ok);
 int mfem_sym_launch(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const SpmvArgs& a);

@@ -46,6 +46,7 @@ extern "C" int mfem_debug_set_ell(int enable) try {
   g_ell.xcd = (enable >> 20) & 1;
   g_ell.sym = ((enable >> 22) & 1) ? 0 : 1;
   g_ell.symp = ((enable >> 23) & 1) ? 0 : 1;
+  g_ell.symp_bands = ((enable >> 24) & 1) ? 1 : ((enable >> 25) & 1) ? 2 : 0;
   g_ell.symp_tail = ((enable >> 26) & 1) ? 0 : 1;
   g_ell.symp_direct = ((enable >> 27) & 1) ? 0 : 1;
   g_ell.dia_pipe = ((enable >> 28) & 1) ? 0 : 1;
@@ -274,12 +275,26 @@ DiaKernel mfem_dia_kernel_wanted(const mfem_csr_s* A, DiaKernel refused, bool* d
   if (direct) *direct = k == DIA_SYMP && g_ell.symp_direct;
   return k;
 }
+// Bands per patch of the patch sweep, decided here once per bind (dia_bind stores it with the copy): two 4-line bands move 6 % fewer matrix bytes
+// and a sixth less x, but leave three resident waves per CU instead of seven.  Measured at 512^3 (1.3e8 swept rows), parent and change alternated on
+// one box: 1073-1083 against 1128-1153 ms per benchmark step (profiles/r07_symp_bands_ab_512.txt).  Smaller lattices were not measured with two
+// bands and keep one: the limit lies between the two benchmark sizes (256^3: 1.7e7 swept rows).
+#define SYMP_BANDS2_MIN_ROWS 100000000
+int mfem_symp_bands_wanted(const mfem_csr_s* A) {
+  if (g_ell.symp_bands) return g_ell.symp_bands;
+  return A->symp_state == 1 && (int64_t)(A->symp_p1 - A->symp_p0) * A->symp_PL >= SYMP_BANDS2_MIN_ROWS ? 2 : 1;
+}
+int mfem_symp_bands(const mfem_csr_s* A) { return A->symp_B ? A->symp_B : mfem_symp_bands_wanted(A); }
 size_t mfem_ell_vals_bytes(const mfem_csr_s* A) {
   if (A->ell_state != 1 || !g_ell.enable) return 0;
   const bool dia = mfem_dia_layout_planned(A);
   if (A->n < (dia ? g_layout_min_rows_dia : g_layout_min_rows_cols)) return 0;
   size_t bytes = sizeof(double) * (size_t)A->ell_K * (size_t)A->ell_npad;
-  if (dia && mfem_dia_kernel_wanted(A) == DIA_SYMP) bytes += sizeof(double) * SP_STEP * (size_t)mfem_symp_steps(A);  // patch-major copy of the swept planes
+  if (dia && mfem_dia_kernel_wanted(A) == DIA_SYMP) {  // patch-major copy of the swept planes: room for either band count (the count is decided per bind)
+    size_t pm = 0;
+    for (int B = 1; B <= SP_BMAX; ++B) pm = std::max(pm, sizeof(double) * sp_step(B) * (size_t)mfem_symp_steps(A, B));
+    bytes += pm;
+  }
   return bytes;
 }
 // Bind of mode 2, once per solve: choose the kernel, make its copies, obtain the symmetry verdict of these values, fall back to the next kernel if
@@ -287,6 +302,7 @@ size_t mfem_ell_vals_bytes(const mfem_csr_s* A) {
 static int dia_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, const double* ssym) {
   bool direct = false, fp_made = false;
   DiaKernel k = mfem_dia_kernel_wanted(A, DIA_NONE, &direct);
+  A->symp_B = mfem_symp_bands_wanted(A);  // (A is unbound here: the geometry below is this count's)
   double* pvals = buf + (size_t)A->ell_K * (size_t)A->ell_npad;
   const SympGeom G = k == DIA_SYMP ? mfem_symp_geom(ctx, A) : SympGeom{};
   int rc = mfem_dia_copy(ctx, A, vals, buf, dsc, ssym, G, direct ? pvals : nullptr, g_ell.symp_fingerprint != 0, &fp_made);
@@ -304,6 +320,7 @@ static int dia_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, doub
   A->ell_bound_mode = 2;
   A->dia_kernel = k;
   A->symp_vals = k == DIA_SYMP ? pvals : nullptr;
+  if (k != DIA_SYMP) A->symp_B = 0;
   return MFEM_OK;
 }
 
@@ -334,6 +351,7 @@ void mfem_ell_unbind(mfem_csr_s* A) {
   A->ell_bound_mode = A->dia_kernel = DIA_NONE;
   A->ell_vals = A->symp_vals = nullptr;
   A->ell_src = nullptr;
+  A->symp_B = 0;
 }
 void mfem_ell_free(mfem_csr_s* A) {
   if (A->ell_cols) hipFree(A->ell_cols);
@@ -404,7 +422,7 @@ int64_t mfem_ell_design_bytes(const mfem_context_s* ctx, const mfem_csr_s* A) {
   if (!mfem_dia_layout_planned(A)) return ent * 12 + A->n * 16;
   const int64_t reg = (int64_t)A->dia_regular_blocks * 128;
   int64_t b = ent * 8 + A->n * 16 + (A->n > reg ? A->n - reg : 0) * (int64_t)A->ell_K * 4;  // (rows in generic blocks read their columns)
-  // the patch sweep stages a (4 + 2) x (32 + 2) neighbourhood of x per step instead of reading each swept entry once
-  if (sym == 2) b += mfem_symp_steps(A) * (int64_t)SP_XN * 8 - (int64_t)(A->symp_p1 - A->symp_p0) * A->symp_PL * 8;
+  // the patch sweep stages a (4 B + 2) x (32 + 2) neighbourhood of x per step instead of reading each swept entry once
+  if (sym == 2) b += mfem_symp_steps(A) * (int64_t)sp_xn(mfem_symp_bands(A)) * 8 - (int64_t)(A->symp_p1 - A->symp_p0) * A->symp_PL * 8;
   return b;
 }

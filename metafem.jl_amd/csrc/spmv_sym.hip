@@ -203,6 +203,10 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_sym27_check(int K, const DiaOffs
 //     each); a run's first step has no history and fills the previous-plane tables from the rows' own slots.  XCD c (workgroups
 //     with blockIdx % 8 == c) sweeps a contiguous eighth of the patches, segment by segment, so neighbouring patches advance
 //     through the planes together on one L2 (512^3: CG iteration 7.29 -> 6.66 ms against arbitrary equal cuts of the step list).
+//   * Bands (k_spmv_symp<MODE, B>; the count is decided per bind, mfem_symp_bands_wanted): with B = 2 a wave owns 8 lines x 32 points and runs them per
+//     plane as two sub-steps of the same step body.  The nine halo lines of 32 cells dominate the edge block (9 W + 6 (L - 1) + 3 L entries), so per 256
+//     rows it falls from 2 x 318 to 354 entries and the x neighbourhood from 2 x 6 x 34 to 10 x 34: 3968 instead of 4224 matrix doubles, at 41.2 KB of
+//     LDS per wave (three resident one-wave workgroups per CU instead of seven).  Same lane <-> row mapping, products and slot order: y is the same bit for bit.
 //   * Rows outside the swept planes (first / last lattice plane, the planes next to the ghost planes of a slab) come from the slot-major
 //     copy through the per-row code: the sweep's waves take them in 128-row units after their runs (unsplit SpMV: one launch, no tail);
 //     in a split (multi-rank) SpMV they are the boundary part, a launch of their own (k_spmv_dia_outside) after the halo has arrived.
@@ -212,47 +216,58 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_sym27_check(int K, const DiaOffs
 // (profiles/r02_symp_experiments.txt).
 // ---------------------------------------------------------------------------------------------------------------
 
-__constant__ int32_t c_sp_ecell[SP_EPAD];  // edge block entry -> LDS cell of its mirror table (the two padding entries: a spare cell)
+__constant__ int32_t c_sp_ecell[SP_BMAX][sp_epad(SP_BMAX)];  // per band count: edge block entry -> LDS cell of its mirror table (padding entries: a spare cell)
 static int symp_upload_tables(int device) {  // __constant__ data is per device
   static bool done[64] = {};
   if (device >= 0 && device < 64 && done[device]) return MFEM_OK;
-  int32_t h[SP_EPAD];
-  for (int e = 0; e < SP_EPAD; ++e) {
-    int s_, l_, c_, cell = 0;
-    h[e] = sp_edge(e, s_, l_, c_, cell) ? cell : SP_TAB;
-  }
+  int32_t h[SP_BMAX][sp_epad(SP_BMAX)];
+  for (int B = 1; B <= SP_BMAX; ++B)
+    for (int e = 0; e < sp_epad(SP_BMAX); ++e) {
+      int s_, l_, c_, cell = 0;
+      h[B - 1][e] = sp_edge(e, s_, l_, c_, cell, B) ? cell : sp_tab(B);
+    }
   MFEM_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_sp_ecell), h, sizeof(h)));
   if (device >= 0 && device < 64) done[device] = true;
   return MFEM_OK;
 }
 
-template <int MODE>
+// B bands of SP_L lines per patch.  Per plane the wave runs its bands top to bottom as sub-steps of one step body (lane <-> two points of line lj of the
+// band): the tables, the x ring and the edge block cover all SP_L * B lines, so band 1 finds band 0's +y entries of this plane (slots 9..11) and
+// its next-plane entries of the previous plane (slots 0..2) in the tables -- the latter because band 0 holds its writes to the tables of slots 0..2 back
+// until the last band of the plane has read them.  A band with no valid line (the last patch row) is skipped wave-uniformly.
+template <int MODE, int B>
 __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __restrict__ pv, const double* __restrict__ x,
                                                    double* __restrict__ y, double alpha, double beta,
                                                    const double* __restrict__ dotw, double* __restrict__ partials,
                                                    const int32_t* __restrict__ done_flag, int32_t* __restrict__ bad, SympTail tail) {
-  __shared__ __attribute__((aligned(16))) double xs[3][SP_XL][SP_XW];
-  __shared__ __attribute__((aligned(16))) double tab[SP_TAB + 2];
+  constexpr int XL = sp_xl(B), XN = sp_xn(B), XU = sp_xu(B), NE = sp_ne(B), EU = sp_eu(B), MAINB = sp_main(B), LOWB = sp_low(B);
+  constexpr int BM = 14 * SP_ROWS, BL = 13 * SP_ROWS, BT = SP_L * SP_LS;  // a band's share of the main part, of the low part, of a table
+  __shared__ __attribute__((aligned(16))) double xs[3][XL][SP_XW];
+  __shared__ __attribute__((aligned(16))) double tab[sp_tab(B) + 2];
   if (done_flag && done_flag[0]) return;
-  const int lane = threadIdx.x, lj = lane / SP_PW, pk = lane % SP_PW, lb = lj * SP_LS + 2 * pk;
-  const int NP = Gm.NS * Gm.NPk, nplanes = Gm.p1 - Gm.p0;
+  const int lane = threadIdx.x, lj = lane / SP_PW, pk = lane % SP_PW, lb0 = lj * SP_LS + 2 * pk;
+  const int NP = Gm.NR * Gm.NPk, nplanes = Gm.p1 - Gm.p0;
   // Runs and XCDs: workgroups with equal blockIdx % 8 share an XCD (round-robin dispatch; gridDim.x is a multiple of 8).  XCD c sweeps
   // a contiguous eighth of the patches, segment by segment, so that the runs resident on it at any time are neighbouring patches at
   // about the same plane: their overlapping x neighbourhoods meet in that XCD's L2.
   const int xcd = blockIdx.x & 7, pc = NP / 8, prem = NP % 8, pcnt = pc + (xcd < prem ? 1 : 0), pfirst = xcd * pc + (xcd < prem ? xcd : prem);
-  // the LDS cells this lane fills from the edge block (5 entries per lane; table made on the host once: decoding 320 entries with
+  // the LDS cells this lane fills from the edge block (5 or 6 entries per lane; table made on the host once: decoding the entries with
   // sp_edge() at the top of every launch cost every wave a few thousand instructions)
-  int ecell[SP_EU];
+  int ecell[EU];
 #pragma unroll
-  for (int u = 0; u < SP_EU; ++u) ecell[u] = c_sp_ecell[lane + 64 * u];
+  for (int u = 0; u < EU; ++u) ecell[u] = c_sp_ecell[B - 1][lane + 64 * u];
   int cur_patch = -1, bp = 0, bc = 1, bn = 2;  // x ring: previous / current / next plane
-  bool have_hist = false, vx = false, vy = false;
-  int64_t rin = 0;       // in-plane row offset j * m2 + k of the lane's first row
-  int xo[SP_XU], xa[SP_XU];  // x staging: in-plane offset (may be negative) and LDS slot of the lane's neighbourhood points
+  int nb = 1;            // bands of the patch with a valid line
+  bool have_hist = false;
+  bool vxb[B], vyb[B];   // per band: the lane's first / second point lies in the lattice
+  int64_t rin = 0;       // in-plane row offset j * m2 + k of the lane's first row in band 0
+  int xo[XU], xa[XU];  // x staging: in-plane offset (may be negative) and LDS slot of the lane's neighbourhood points
   double dot_acc = 0.0;
   int fail = 0;
-  e_d2 cur[14];          // slots 13..26 of the step, requested one step ahead
-  double ed[SP_EU], xr[SP_XU];  // its edge block entries and the x neighbourhood of the plane after it
+  e_d2 cur[B][14];       // per band: slots 13..26 of its sub-step, requested a full step (one plane) ahead -- with three resident waves per CU one
+                         // sub-step in flight left the stream short (512^3, B = 2: 1142 against 1131 ms per step with the four-line form)
+  e_d2 keep[3];          // band 0's slots 24..26, held back from the tables of slots 2..0 while a later band of the plane still reads the previous plane's
+  double ed[EU], xr[XU];  // the step's edge block entries and the x neighbourhood of the plane after it, requested with band 0
   // x neighbourhood entry of plane `plane`: positions outside the vector's owned entries (beyond the last lattice line of the last
   // plane) are only ever multiplied by structurally absent entries -- any finite value serves: clamp
   auto xidx = [&](int plane, int u) -> int64_t {
@@ -260,27 +275,32 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
     idx = idx < 0 ? 0 : idx;
     return idx < Gm.nx ? idx : Gm.nx - 1;
   };
-  auto request = [&](const double* v, int pnext) {
-    if (vx) {
+  // the main part of band b of the step at v
+  auto request = [&](const double* v, int b) {
+    if (vxb[b]) {
 #pragma unroll
-      for (int u = 0; u < 14; ++u) cur[u] = SYM_LD(reinterpret_cast<const e_d2*>(v + 2 * lane + u * SP_ROWS));
+      for (int u = 0; u < 14; ++u) cur[b][u] = SYM_LD(reinterpret_cast<const e_d2*>(v + b * BM + 2 * lane + u * SP_ROWS));
     } else {
 #pragma unroll
-      for (int u = 0; u < 14; ++u) cur[u] = (e_d2){0.0, 0.0};
+      for (int u = 0; u < 14; ++u) cur[b][u] = (e_d2){0.0, 0.0};
     }
+  };
+  // the edge block of the step at v and the x neighbourhood of plane pnext
+  auto request_step = [&](const double* v, int pnext) {
     if (MODE == 0) {
 #pragma unroll
-      for (int u = 0; u < SP_EU; ++u) ed[u] = SYM_LD(v + 14 * SP_ROWS + lane + 64 * u);  // the block is padded to SP_EPAD entries
+      for (int u = 0; u < EU - 1; ++u) ed[u] = SYM_LD(v + B * BM + lane + 64 * u);
+      ed[EU - 1] = lane < NE - 64 * (EU - 1) ? SYM_LD(v + B * BM + lane + 64 * (EU - 1)) : 0.0;
 #pragma unroll
-      for (int u = 0; u < SP_XU - 1; ++u) xr[u] = x[xidx(pnext, u)];
-      xr[SP_XU - 1] = lane < SP_XN - 64 * (SP_XU - 1) ? x[xidx(pnext, SP_XU - 1)] : 0.0;
+      for (int u = 0; u < XU - 1; ++u) xr[u] = x[xidx(pnext, u)];
+      xr[XU - 1] = lane < XN - 64 * (XU - 1) ? x[xidx(pnext, XU - 1)] : 0.0;
     }
   };
   auto stage_x = [&](int buf, int plane) {
     double* dst = &xs[buf][0][0];
 #pragma unroll
-    for (int u = 0; u < SP_XU - 1; ++u) dst[xa[u]] = x[xidx(plane, u)];
-    if (lane < SP_XN - 64 * (SP_XU - 1)) dst[xa[SP_XU - 1]] = x[xidx(plane, SP_XU - 1)];
+    for (int u = 0; u < XU - 1; ++u) dst[xa[u]] = x[xidx(plane, u)];
+    if (lane < XN - 64 * (XU - 1)) dst[xa[XU - 1]] = x[xidx(plane, XU - 1)];
   };
   for (int run = blockIdx.x >> 3; run < pcnt * Gm.nseg; run += gridDim.x >> 3) {
   const int patch = pfirst + run % pcnt, seg = run / pcnt;
@@ -289,61 +309,85 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
   for (int64_t t = t0; t < t1; ++t) {
     const int p = Gm.p0 + (int)(t - (int64_t)patch * nplanes);
     const int64_t step = (int64_t)(p - Gm.p0) * NP + patch;  // [plane][patch]: the runs of a segment advance plane by plane together
-    const double* v = pv + step * SP_MAIN;                                         // slots 13..26 + edge block of the step
-    const double* vlow = pv + (int64_t)NP * nplanes * SP_MAIN + step * SP_LOW;    // its slots 0..12
+    const double* v = pv + step * MAINB;                                         // per band slots 13..26, then the edge block of the step
+    const double* vlow = pv + (int64_t)NP * nplanes * MAINB + step * LOWB;      // per band its slots 0..12
     if (patch != cur_patch) {  // wave-uniform: a run or a patch starts -- nothing was requested ahead, no history
       cur_patch = patch;
-      const int j0 = (patch / Gm.NPk) * SP_L, k0 = (patch % Gm.NPk) * SP_W;
-      const int j = j0 + lj, k = k0 + 2 * pk;
-      vx = j < Gm.m1 && k < Gm.m2;
-      vy = j < Gm.m1 && k + 1 < Gm.m2;
-      rin = (int64_t)j * Gm.m2 + k;
+      const int j0 = (patch / Gm.NPk) * (SP_L * B), k0 = (patch % Gm.NPk) * SP_W;
+      const int k = k0 + 2 * pk;
+      nb = 1;
 #pragma unroll
-      for (int u = 0; u < SP_XU; ++u) {
+      for (int b = 0; b < B; ++b) {
+        const int j = j0 + SP_L * b + lj;
+        vxb[b] = j < Gm.m1 && k < Gm.m2;
+        vyb[b] = j < Gm.m1 && k + 1 < Gm.m2;
+        if (b > 0 && j0 + SP_L * b < Gm.m1) nb = b + 1;
+      }
+      rin = (int64_t)(j0 + lj) * Gm.m2 + k;
+#pragma unroll
+      for (int u = 0; u < XU; ++u) {
         const int tt = lane + 64 * u, xl = tt / SP_XC, xc = tt - SP_XC * xl;
         xo[u] = (j0 - 1 + xl) * Gm.m2 + (k0 - 1 + xc);
-        xa[u] = xl * SP_XW + xc;  // (u = 3: only lanes < 12 belong to the neighbourhood)
+        xa[u] = xl * SP_XW + xc;  // (the last u: only the first lanes belong to the neighbourhood)
       }
       have_hist = false;
       __syncthreads();  // the previous patch's last products may still be reading the x ring
-      request(v, p + 1);
+#pragma unroll
+      for (int b = 0; b < B; ++b)
+        if (b < nb) request(v, b);
+      request_step(v, p + 1);
       if (MODE == 0) {
         stage_x(bp, p - 1);
         stage_x(bc, p);
         // no history: the row's own previous-plane slots go where the mirror reads would look for them
 #pragma unroll
-        for (int s = 0; s < 9; ++s) {
-          const e_d2 w = vx ? SYM_LD(reinterpret_cast<const e_d2*>(vlow + 2 * lane + s * SP_ROWS)) : (e_d2){0.0, 0.0};
-          double* c = tab + sp_tbase(s) + (sp_dj(s) + sp_adj(s)) * SP_LS + sp_dk(s) + 2 + lb;
-          c[0] = w.x;
-          c[1] = w.y;
+        for (int b = 0; b < B; ++b) {
+          if (b < nb) {
+#pragma unroll
+            for (int s = 0; s < 9; ++s) {
+              const e_d2 w = vxb[b] ? SYM_LD(reinterpret_cast<const e_d2*>(vlow + b * BL + 2 * lane + s * SP_ROWS)) : (e_d2){0.0, 0.0};
+              double* c = tab + sp_tbase(s, B) + (sp_dj(s) + sp_adj(s)) * SP_LS + sp_dk(s) + 2 + b * BT + lb0;
+              c[0] = w.x;
+              c[1] = w.y;
+            }
+          }
         }
       }
     }
-    // ---- phase B: this step's +z / +y slots, its edge entries and the next plane's x go to LDS
+    const bool more = t + 1 < t1 && p + 1 < Gm.p1;  // the next step continues this sweep
 #pragma unroll
-    for (int s = 9; s < 13; ++s) *reinterpret_cast<e_d2*>(tab + sp_tbase(s) + sp_adj(s) * SP_LS + 2 + lb) = cur[26 - s - 13];
+    for (int b = 0; b < B; ++b) {   // (unrolled: the bands' registers are indexed at compile time)
+    if (b < nb) {                   // wave-uniform
+    const int lb = lb0 + b * BT;    // the lane's place in a table line block: line SP_L * b + lj of the patch
+    const bool vx = vxb[b], vy = vyb[b], lastb = b + 1 >= nb;
+    // ---- phase B: this sub-step's +z / +y slots go to LDS; with band 0 the step's edge entries and the next plane's x
+#pragma unroll
+    for (int s = 9; s < 13; ++s) *reinterpret_cast<e_d2*>(tab + sp_tbase(s, B) + sp_adj(s) * SP_LS + 2 + lb) = cur[b][26 - s - 13];
     e_d2 low[13];
     if (MODE == 0) {
+      if (b == 0) {
 #pragma unroll
-      for (int u = 0; u < SP_EU; ++u) tab[ecell[u]] = ed[u];
-      double* dst = &xs[bn][0][0];
+        for (int u = 0; u < EU; ++u) tab[ecell[u]] = ed[u];
+        double* dst = &xs[bn][0][0];
 #pragma unroll
-      for (int u = 0; u < SP_XU - 1; ++u) dst[xa[u]] = xr[u];
-      if (lane < SP_XN - 64 * (SP_XU - 1)) dst[xa[SP_XU - 1]] = xr[SP_XU - 1];
+        for (int u = 0; u < XU - 1; ++u) dst[xa[u]] = xr[u];
+        if (lane < XN - 64 * (XU - 1)) dst[xa[XU - 1]] = xr[XU - 1];
+      }
     } else {
 #pragma unroll
-      for (int s = 0; s < 13; ++s) low[s] = vx ? SYM_LD(reinterpret_cast<const e_d2*>(vlow + 2 * lane + s * SP_ROWS)) : (e_d2){0.0, 0.0};
+      for (int s = 0; s < 13; ++s) low[s] = vx ? SYM_LD(reinterpret_cast<const e_d2*>(vlow + b * BL + 2 * lane + s * SP_ROWS)) : (e_d2){0.0, 0.0};
     }
-    // the step's own upper slots stay in `mine`; the next step of the same sweep is requested now and arrives during the products
+    // the sub-step's own upper slots stay in `mine`; the next sub-step of the same sweep is requested now and arrives during the products
     e_d2 mine[14];
 #pragma unroll
-    for (int u = 0; u < 14; ++u) mine[u] = cur[u];
-    const bool more = t + 1 < t1 && p + 1 < Gm.p1;  // the next step continues this sweep
+    for (int u = 0; u < 14; ++u) mine[u] = cur[b][u];
     __syncthreads();  // one wave: orders its LDS writes before the reads of other lanes
-    if (more) request(v + (int64_t)NP * SP_MAIN, p + 2);
+    if (more) {  // this band of the next plane; with the plane's last band the next step's edge block and the x of the plane behind it
+      request(v + (int64_t)NP * MAINB, b);
+      if (lastb) request_step(v + (int64_t)NP * MAINB, p + 2);
+    }
     auto mirrored = [&](int s) -> e_d2 {
-      const double* c = tab + sp_tbase(s) + (sp_dj(s) + sp_adj(s)) * SP_LS + sp_dk(s) + 2 + lb;
+      const double* c = tab + sp_tbase(s, B) + (sp_dj(s) + sp_adj(s)) * SP_LS + sp_dk(s) + 2 + lb;
       e_d2 w;
       w.x = c[0];
       w.y = c[1];
@@ -356,7 +400,7 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
     // unchanged -- no select needed here.
     auto run = [&](const e_d2& va, const e_d2& vb, const e_d2& vc, int buf, int dj, bool self) {
 #pragma clang fp contract(off)  // v_mul_f64 + v_add_f64 like the plain kernel, not v_fma_f64
-      const double* xp = &xs[buf][lj + 1 + dj][2 * pk];
+      const double* xp = &xs[buf][SP_L * b + lj + 1 + dj][2 * pk];
       const e_d2 xa2 = *reinterpret_cast<const e_d2*>(xp), xb2 = *reinterpret_cast<const e_d2*>(xp + 2);
       acc.x = acc.x + va.x * xa2.x;
       acc.y = acc.y + va.y * xa2.y;
@@ -370,11 +414,12 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
       }
     };
     if (MODE == 1) {
-      // exactly the pairs the sweep mirrors: source rows inside the patch, previous-plane slots only where a history exists
+      // exactly the pairs the sweep mirrors: source rows inside the patch's valid bands (the seam between two bands included), previous-plane
+      // slots only where a history exists
 #pragma unroll
       for (int s = 0; s < 13; ++s) {
-        const int dj = sp_dj(s), dk = sp_dk(s);
-        const bool in = lj + dj >= 0 && lj + dj < SP_L && (dk < 0 ? pk > 0 : dk > 0 ? pk < SP_PW - 1 : true);
+        const int dj = sp_dj(s), dk = sp_dk(s), gl = SP_L * b + lj;
+        const bool in = gl + dj >= 0 && gl + dj < SP_L * nb && (dk < 0 ? pk > 0 : dk > 0 ? pk < SP_PW - 1 : true);
         if (in && vx && (s >= 9 || have_hist)) {
           const e_d2 m = mirrored(s);
           if (__double_as_longlong(m.x) != __double_as_longlong(low[s].x) && !(m.x == 0.0 && low[s].x == 0.0)) fail = 1;
@@ -390,14 +435,25 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
       run(mine[2], mine[3], mine[4], bc, 1, false);
     }
     __syncthreads();  // every lane is done with the tables
+    // the next-plane slots become the history of the next plane; slots 24..26 of a band that is not the plane's last wait in `keep`: the band below
+    // still reads the previous plane's from the table line this band would overwrite
 #pragma unroll
-    for (int s = 0; s < 9; ++s) *reinterpret_cast<e_d2*>(tab + sp_tbase(s) + sp_adj(s) * SP_LS + 2 + lb) = mine[26 - s - 13];
-    have_hist = true;
+    for (int s = 3; s < 9; ++s) *reinterpret_cast<e_d2*>(tab + sp_tbase(s, B) + sp_adj(s) * SP_LS + 2 + lb) = mine[26 - s - 13];
+    if (B > 1 && !lastb) {
+#pragma unroll
+      for (int s = 0; s < 3; ++s) keep[s] = mine[26 - s - 13];
+    } else {
+#pragma unroll
+      for (int s = 0; s < 3; ++s) {
+        *reinterpret_cast<e_d2*>(tab + sp_tbase(s, B) + sp_adj(s) * SP_LS + 2 + lb) = mine[26 - s - 13];
+        if (B > 1 && b > 0) *reinterpret_cast<e_d2*>(tab + sp_tbase(s, B) + sp_adj(s) * SP_LS + 2 + lb - BT) = keep[s];
+      }
+    }
     if (MODE == 0) {
       run(mine[5], mine[6], mine[7], bn, -1, false);
       run(mine[8], mine[9], mine[10], bn, 0, false);
       run(mine[11], mine[12], mine[13], bn, 1, false);
-      const int64_t r = (int64_t)p * Gm.PL + rin;
+      const int64_t r = (int64_t)p * Gm.PL + rin + (int64_t)(SP_L * b) * Gm.m2;
       double y0 = alpha * acc.x, y1 = alpha * acc.y;
       if (beta != 0.0) {
         if (vx) y0 += beta * y[r];
@@ -417,10 +473,15 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
           if (vy) dot_acc += y1 * dotw[r + 1];
         }
       }
-      const int b = bp;
+    }
+    }
+    }
+    have_hist = true;
+    if (MODE == 0) {
+      const int b_ = bp;
       bp = bc;
       bc = bn;
-      bn = b;
+      bn = b_;
     }
     if (!more) cur_patch = -1;  // nothing requested: the next step (if any) starts like a run
   }
@@ -443,43 +504,46 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
   }
 }
 
-// patch-major copy of the swept planes from the slot-major copy: per step [plane - p0][patch] the slots 13..26 + the edge block (main
-// part) and, behind all main parts, the slots 0..12 (low part), zero
+// patch-major copy of the swept planes from the slot-major copy: per step [plane - p0][patch] and band the slots 13..26, then the edge block (main
+// part) and, behind all main parts, per band the slots 0..12 (low part), zero
 // where the patch sticks out of the lattice; one wave per (plane, patch)
 __global__ __launch_bounds__(MFEM_BLOCK) void k_symp_bind(SympGeom Gm, int K, const double* __restrict__ ell, double* __restrict__ pv) {
   const int lane = threadIdx.x & 63, lj = lane / SP_PW, pk = lane % SP_PW;
-  const int NP = Gm.NS * Gm.NPk;
+  const int NP = Gm.NR * Gm.NPk, B = Gm.B;
+  const int MAINB = sp_main(B), LOWB = sp_low(B), NEB = sp_ne(B), EPADB = sp_epad(B);
   const int64_t T = (int64_t)NP * (Gm.p1 - Gm.p0);
   for (int64_t t = (int64_t)blockIdx.x * (MFEM_BLOCK / 64) + (threadIdx.x >> 6); t < T; t += (int64_t)gridDim.x * (MFEM_BLOCK / 64)) {
     const int nplanes = Gm.p1 - Gm.p0, patch = (int)(t / nplanes), p = Gm.p0 + (int)(t % nplanes);
-    const int j0 = (patch / Gm.NPk) * SP_L, k0 = (patch % Gm.NPk) * SP_W;
-    const int j = j0 + lj, k = k0 + 2 * pk;
-    const bool vx = j < Gm.m1 && k < Gm.m2, vy = j < Gm.m1 && k + 1 < Gm.m2;
-    const int64_t r = (int64_t)p * Gm.PL + (int64_t)j * Gm.m2 + k;
-    const int64_t b0 = ell_base(r, K), b1 = ell_base(r + 1, K);
+    const int j0 = (patch / Gm.NPk) * (SP_L * B), k0 = (patch % Gm.NPk) * SP_W;
     const int64_t step = (int64_t)(p - Gm.p0) * NP + patch;
-    double* out = pv + step * SP_MAIN;
-    double* outlow = pv + T * SP_MAIN + step * SP_LOW;
-    for (int s0 = 0; s0 < 27; s0 += 9) {
-      e_d2 w[9];
+    double* out = pv + step * MAINB;
+    double* outlow = pv + T * MAINB + step * LOWB;
+    for (int b = 0; b < B; ++b) {
+      const int j = j0 + SP_L * b + lj, k = k0 + 2 * pk;
+      const bool vx = j < Gm.m1 && k < Gm.m2, vy = j < Gm.m1 && k + 1 < Gm.m2;
+      const int64_t r = (int64_t)p * Gm.PL + (int64_t)j * Gm.m2 + k;
+      const int64_t b0 = ell_base(r, K), b1 = ell_base(r + 1, K);
+      for (int s0 = 0; s0 < 27; s0 += 9) {
+        e_d2 w[9];
 #pragma unroll
-      for (int u = 0; u < 9; ++u) {
-        w[u].x = vx ? ell[b0 + (s0 + u) * ELL_B] : 0.0;
-        w[u].y = vy ? ell[b1 + (s0 + u) * ELL_B] : 0.0;
-      }
+        for (int u = 0; u < 9; ++u) {
+          w[u].x = vx ? ell[b0 + (s0 + u) * ELL_B] : 0.0;
+          w[u].y = vy ? ell[b1 + (s0 + u) * ELL_B] : 0.0;
+        }
 #pragma unroll
-      for (int u = 0; u < 9; ++u) {
-        const int sl = s0 + u;  // slots 0..12 to the low part, 13..26 to the main part
-        double* dst = sl < 13 ? outlow + sl * SP_ROWS : out + (sl - 13) * SP_ROWS;
-        *reinterpret_cast<e_d2*>(dst + 2 * lane) = w[u];
+        for (int u = 0; u < 9; ++u) {
+          const int sl = s0 + u;  // slots 0..12 to the low part, 13..26 to the main part
+          double* dst = sl < 13 ? outlow + b * 13 * SP_ROWS + sl * SP_ROWS : out + b * 14 * SP_ROWS + (sl - 13) * SP_ROWS;
+          *reinterpret_cast<e_d2*>(dst + 2 * lane) = w[u];
+        }
       }
     }
-    for (int e = lane; e < SP_EPAD; e += 64) {
+    for (int e = lane; e < EPADB; e += 64) {
       int s = 0, line = 0, col = 0, cell = 0;
       double val = 0.0;
-      if (sp_edge(e, s, line, col, cell) && j0 + line < Gm.m1 && k0 + col < Gm.m2)
+      if (e < NEB && sp_edge(e, s, line, col, cell, B) && j0 + line < Gm.m1 && k0 + col < Gm.m2)
         val = ell[ell_base((int64_t)p * Gm.PL + (int64_t)(j0 + line) * Gm.m2 + k0 + col, K) + s * ELL_B];
-      out[14 * SP_ROWS + e] = val;
+      out[B * 14 * SP_ROWS + e] = val;
     }
   }
 }
@@ -569,7 +633,8 @@ static int sym27_grid(const mfem_context_s* ctx, const mfem_csr_s* A, int64_t* n
 // runs per patch: the smallest count that fills >= 90 % of the resident one-wave workgroups in whole rounds (a run's first step has no
 // history: runs stay >= 16 planes long)
 static int symp_nseg(const mfem_context_s* ctx, const mfem_csr_s* A) {
-  const int64_t NP = (int64_t)A->symp_NS * A->symp_NPk, slots = (int64_t)SP_WG_PER_CU * ctx->num_cus;
+  const int B = mfem_symp_bands(A);
+  const int64_t NP = (int64_t)((A->symp_NS + B - 1) / B) * A->symp_NPk, slots = (int64_t)sp_wg_per_cu(B) * ctx->num_cus;  // the form's own resident slots
   const int nplanes = A->symp_p1 - A->symp_p0;
   int best = 1;
   double best_eff = 0.0;
@@ -582,13 +647,18 @@ static int symp_nseg(const mfem_context_s* ctx, const mfem_csr_s* A) {
   return best;
 }
 SympGeom mfem_symp_geom(const mfem_context_s* ctx, const mfem_csr_s* A) {  // (nx = n: the sweep stages owned entries of x only -- swept rows reference no ghost column)
-  return SympGeom{A->symp_PL, A->n, A->symp_m1, A->symp_m2, A->symp_p0, A->symp_p1, A->symp_NS, A->symp_NPk, symp_nseg(ctx, A)};
+  const int B = mfem_symp_bands(A);
+  return SympGeom{A->symp_PL, A->n, A->symp_m1, A->symp_m2, A->symp_p0, A->symp_p1, A->symp_NS, A->symp_NPk, symp_nseg(ctx, A), B, (A->symp_NS + B - 1) / B};
 }
-int64_t mfem_symp_steps(const mfem_csr_s* A) { return (int64_t)A->symp_NS * A->symp_NPk * (A->symp_p1 - A->symp_p0); }
+int64_t mfem_symp_steps(const mfem_csr_s* A, int B) {
+  if (B < 1) B = mfem_symp_bands(A);
+  return (int64_t)((A->symp_NS + B - 1) / B) * A->symp_NPk * (A->symp_p1 - A->symp_p0);
+}
 static int symp_grid(const mfem_context_s* ctx, const mfem_csr_s* A) {
-  const int64_t NP = (int64_t)A->symp_NS * A->symp_NPk;
+  const int B = mfem_symp_bands(A);
+  const int64_t NP = (int64_t)((A->symp_NS + B - 1) / B) * A->symp_NPk;
   int64_t g = 8 * ((NP + 7) / 8) * symp_nseg(ctx, A);  // every XCD's share of the runs, padded to the largest share
-  int64_t cap = (int64_t)SP_WG_PER_CU * ctx->num_cus;
+  int64_t cap = (int64_t)sp_wg_per_cu(B) * ctx->num_cus;
   if (cap > MFEM_MAX_PARTIALS - 1024) cap = MFEM_MAX_PARTIALS - 1024;
   cap &= ~(int64_t)7;
   if (g > cap) g = cap;
@@ -603,15 +673,16 @@ int64_t mfem_sym_entries(const mfem_context_s* ctx, const mfem_csr_s* A, DiaKern
     const int64_t nch = A->sym_c1 - A->sym_c0;
     return (int64_t)A->ell_K * A->ell_npad - ((nch - sym27_grid(ctx, A, nullptr)) * A->sym_mx + nch * A->sym_myz);
   }
-  const int NP = A->symp_NS * A->symp_NPk, nplanes = A->symp_p1 - A->symp_p0, nseg = symp_nseg(ctx, A);
+  const int B = mfem_symp_bands(A);
+  const int NP = (A->symp_NS + B - 1) / B * A->symp_NPk, nplanes = A->symp_p1 - A->symp_p0, nseg = symp_nseg(ctx, A);
   int64_t e = (int64_t)A->ell_K * (A->ell_npad - (int64_t)nplanes * A->symp_PL);
   for (int patch = 0; patch < NP; ++patch) {
-    int64_t nv = 0;
-    for (int lane = 0; lane < 64; ++lane) {
-      const int j = (patch / A->symp_NPk) * SP_L + lane / SP_PW, kk = (patch % A->symp_NPk) * SP_W + 2 * (lane % SP_PW);
+    int64_t nv = 0;  // valid lane pairs of all bands (a band without a valid line is skipped: none of its lanes is valid)
+    for (int lp = 0; lp < 64 * B; ++lp) {
+      const int j = (patch / A->symp_NPk) * (SP_L * B) + lp / SP_PW, kk = (patch % A->symp_NPk) * SP_W + 2 * (lp % SP_PW);
       if (j < A->symp_m1 && kk < A->symp_m2) ++nv;
     }
-    e += (28 * nv + SP_NE) * nplanes + 18 * nv * nseg;
+    e += (28 * nv + sp_ne(B)) * nplanes + 18 * nv * nseg;
   }
   return e;
 }
@@ -644,8 +715,9 @@ int mfem_sym_verdict(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const doub
   }
   MFEM_CHECK_HIP(hipMemsetAsync(d_bad, 0, sizeof(int32_t), ctx->stream));
   if (k == DIA_SYMP)
-    hipLaunchKernelGGL(k_spmv_symp<1>, dim3(symp_grid(ctx, A)), dim3(64), 0, ctx->stream, G, (const double*)pvals, (const double*)nullptr,
-                       (double*)nullptr, 0.0, 0.0, (const double*)nullptr, (double*)nullptr, (const int32_t*)nullptr, d_bad, SympTail{});
+    hipLaunchKernelGGL((G.B == 2 ? k_spmv_symp<1, 2> : k_spmv_symp<1, 1>), dim3(symp_grid(ctx, A)), dim3(64), 0, ctx->stream, G, (const double*)pvals,
+                       (const double*)nullptr, (double*)nullptr, 0.0, 0.0, (const double*)nullptr, (double*)nullptr, (const int32_t*)nullptr, d_bad,
+                       SympTail{});
   else
     hipLaunchKernelGGL(k_sym27_check, dim3(ctx->num_cus * 8), dim3(MFEM_BLOCK), 0, ctx->stream, A->ell_K, (const DiaOffsets*)A->dia_dev, buf,
                        A->sym_c0 * SYM_ROWS, A->sym_c1 * SYM_ROWS, A->sym_cls, d_bad);
@@ -678,7 +750,7 @@ int mfem_sym_launch(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const SpmvA
     if (a.part.part == 0 && g_ell.symp_tail) tl = SympTail{1, A->ell_K, A->n, A->ell_npad, lo, hi, O, A->dia_flags, A->ell_cols, A->ell_vals};
     if (a.part.part != 2) {
       np = symp_grid(ctx, A);
-      hipLaunchKernelGGL(k_spmv_symp<0>, dim3(np), dim3(64), 0, ctx->stream, G, (const double*)A->symp_vals, a.x, a.y, a.alpha, a.beta, a.dotw,
+      hipLaunchKernelGGL((G.B == 2 ? k_spmv_symp<0, 2> : k_spmv_symp<0, 1>), dim3(np), dim3(64), 0, ctx->stream, G, (const double*)A->symp_vals, a.x, a.y, a.alpha, a.beta, a.dotw,
                          a.partials, a.done_flag, (int32_t*)nullptr, tl);
       MFEM_CHECK_LAUNCH();
     }

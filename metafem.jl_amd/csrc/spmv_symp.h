@@ -21,32 +21,62 @@
 // receives the referencing row's OWN slot-s entry from the step's edge block, so that the reads are the same two LDS loads for
 // every lane and slot.
 #define SP_LS (SP_W + 4)
+// Bands: a wave's patch is B bands of SP_L lines each (B = 1: the patch above; B = 2: 8 x 32 points, swept per plane as two sub-steps of the same
+// step body, band 0 first).  Tables, x ring and edge block cover all SP_L * B lines: the rows on the seam between two bands find their neighbours'
+// entries in the tables like any interior row and own no edge entry.  Every function below takes the band count; B = 1 gives the macros' values.
+#define SP_BMAX 2
 __host__ __device__ constexpr int sp_dj(int s) { return (s / 3) % 3 - 1; }
 __host__ __device__ constexpr int sp_dk(int s) { return s % 3 - 1; }
-__host__ __device__ constexpr int sp_tsize(int s) { return (sp_dj(s) == 0 ? SP_L : SP_L + 1) * SP_LS; }
-__host__ __device__ constexpr int sp_tbase(int s) { return s == 0 ? 0 : sp_tbase(s - 1) + sp_tsize(s - 1); }
+__host__ __device__ constexpr int sp_tsize(int s, int B = 1) { return (sp_dj(s) == 0 ? SP_L * B : SP_L * B + 1) * SP_LS; }
+__host__ __device__ constexpr int sp_tbase(int s, int B = 1) {
+  int b = 0;
+  for (int t = 0; t < s; ++t) b += sp_tsize(t, B);
+  return b;
+}
 __host__ __device__ constexpr int sp_adj(int s) { return sp_dj(s) == -1 ? 1 : 0; }  // table line of source line 0
-#define SP_TAB (sp_tbase(12) + sp_tsize(12))
+__host__ __device__ constexpr int sp_tab(int B) { return sp_tbase(13, B); }  // 2196 doubles for B = 1, 4068 for B = 2
+#define SP_TAB sp_tab(1)
 // edge block of a step: for s = 0..12 the halo cells of table s -- the halo line (SP_W cells) if dj != 0, then the halo column
 // (lines in ascending order) if dk != 0
-__host__ __device__ constexpr int sp_ecnt(int s) { return (sp_dj(s) != 0 ? SP_W : 0) + (sp_dk(s) != 0 ? (sp_dj(s) != 0 ? SP_L - 1 : SP_L) : 0); }
-__host__ __device__ constexpr int sp_ebase(int s) { return s == 0 ? 0 : sp_ebase(s - 1) + sp_ecnt(s - 1); }
-#define SP_NE (sp_ebase(12) + sp_ecnt(12))  // 318 for 4 x 32 patches (210 for 8 x 16)
-#define SP_EU ((SP_NE + 63) / 64)            // edge entries per lane
-#define SP_EPAD (64 * SP_EU)
-#define SP_STEP (27 * SP_ROWS + SP_EPAD)    // doubles per (plane, patch) in the patch-major copy, in two parts:
-#define SP_MAIN (14 * SP_ROWS + SP_EPAD)    //   what every step reads -- slots 13..26 and the edge block -- contiguous per step, steps [plane][patch]
-#define SP_LOW (13 * SP_ROWS)               //   the lower slots 0..12 (read where a run starts and by the symmetry check), behind all main parts
+__host__ __device__ constexpr int sp_ecnt(int s, int B = 1) {
+  return (sp_dj(s) != 0 ? SP_W : 0) + (sp_dk(s) != 0 ? (sp_dj(s) != 0 ? SP_L * B - 1 : SP_L * B) : 0);
+}
+__host__ __device__ constexpr int sp_ebase(int s, int B = 1) {
+  int b = 0;
+  for (int t = 0; t < s; ++t) b += sp_ecnt(t, B);
+  return b;
+}
+__host__ __device__ constexpr int sp_ne(int B) { return sp_ebase(13, B); }  // 318 for one band (210 for 8 x 16), 354 for two
+__host__ __device__ constexpr int sp_eu(int B) { return (sp_ne(B) + 63) / 64; }  // edge entries per lane
+__host__ __device__ constexpr int sp_epad(int B) { return 64 * sp_eu(B); }
+#define SP_NE sp_ne(1)
+#define SP_EU sp_eu(1)
+#define SP_EPAD sp_epad(1)
+// doubles per (plane, patch) in the patch-major copy, in two parts:
+//   main: what every step reads -- per band the slots 13..26 (14 x SP_ROWS, band after band), then the edge block -- contiguous per step, steps [plane][patch]
+//   low: per band the lower slots 0..12 (read where a run starts and by the symmetry check), behind all main parts
+__host__ __device__ constexpr int sp_main(int B) { return 14 * SP_ROWS * B + sp_epad(B); }
+__host__ __device__ constexpr int sp_low(int B) { return 13 * SP_ROWS * B; }
+__host__ __device__ constexpr int sp_step(int B) { return sp_main(B) + sp_low(B); }
+#define SP_STEP sp_step(1)
+#define SP_MAIN sp_main(1)
+#define SP_LOW sp_low(1)
+// staged x neighbourhood of a patch
+__host__ __device__ constexpr int sp_xl(int B) { return SP_L * B + 2; }
+__host__ __device__ constexpr int sp_xn(int B) { return sp_xl(B) * SP_XC; }
+__host__ __device__ constexpr int sp_xu(int B) { return (sp_xn(B) + 63) / 64; }
+// resident one-wave workgroups per CU: 22.8 KB of LDS each for one band, 41.2 KB for two
+__host__ __device__ constexpr int sp_wg_per_cu(int B) { return B == 1 ? SP_WG_PER_CU : 3; }
 // entry e of the edge block: lower slot s, the referencing row's (line, column) in the patch, the LDS cell of table s it fills
-__host__ __device__ inline bool sp_edge(int e, int& s, int& line, int& col, int& cell) {
-  if (e >= SP_NE) return false;
+__host__ __device__ inline bool sp_edge(int e, int& s, int& line, int& col, int& cell, int B = 1) {
+  if (e >= sp_ne(B)) return false;
   s = 0;
-  while (e >= sp_ebase(s) + sp_ecnt(s)) ++s;
-  int q = e - sp_ebase(s);
+  while (e >= sp_ebase(s, B) + sp_ecnt(s, B)) ++s;
+  int q = e - sp_ebase(s, B);
   const int dj = sp_dj(s), dk = sp_dk(s);
   int sl, sc;
   if (dj != 0 && q < SP_W) {
-    sl = dj < 0 ? -1 : SP_L;
+    sl = dj < 0 ? -1 : SP_L * B;
     sc = dk + q;
   } else {
     if (dj != 0) q -= SP_W;
@@ -55,17 +85,17 @@ __host__ __device__ inline bool sp_edge(int e, int& s, int& line, int& col, int&
   }
   line = sl - dj;
   col = sc - dk;
-  cell = sp_tbase(s) + (sl + sp_adj(s)) * SP_LS + sc + 2;
+  cell = sp_tbase(s, B) + (sl + sp_adj(s)) * SP_LS + sc + 2;
   return true;
 }
-// inverse of sp_edge for the row at (line, col) of its patch: the edge block entry that holds the row's own slot-s entry (s = 0..12), or
-// -1 when the row's slot-s neighbour lies inside the patch.  A row owns at most one entry per slot: the halo line takes the corner cells.
-__host__ __device__ constexpr int sp_edge_of(int s, int line, int col) {
+// inverse of sp_edge for the row at (line, col) of its patch (line counted over all bands): the edge block entry that holds the row's own slot-s
+// entry (s = 0..12), or -1 when the row's slot-s neighbour lies inside the patch.  A row owns at most one entry per slot: the halo line takes the corner cells.
+__host__ __device__ constexpr int sp_edge_of(int s, int line, int col, int B = 1) {
   const int dj = sp_dj(s), dk = sp_dk(s);
-  if (dj != 0 && line == (dj < 0 ? 0 : SP_L - 1)) return sp_ebase(s) + col;
+  if (dj != 0 && line == (dj < 0 ? 0 : SP_L * B - 1)) return sp_ebase(s, B) + col;
   if (dk != 0 && col == (dk < 0 ? 0 : SP_W - 1)) {
-    const int q = dj < 0 ? line - 1 : line;  // dj < 0: lines 1 .. SP_L - 1; dj > 0: lines 0 .. SP_L - 2; dj = 0: all lines
-    return sp_ebase(s) + (dj != 0 ? SP_W : 0) + q;
+    const int q = dj < 0 ? line - 1 : line;  // dj < 0: lines 1 .. L - 1; dj > 0: lines 0 .. L - 2; dj = 0: all lines
+    return sp_ebase(s, B) + (dj != 0 ? SP_W : 0) + q;
   }
   return -1;
 }
