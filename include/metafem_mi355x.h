@@ -573,6 +573,66 @@ int mfem_mesh_residual_facets(mfem_context ctx, int32_t dim, int32_t itg_b, int3
                               const mfem_res_symbol* symbols, int32_t n_terms, const mfem_affine_term* terms,
                               const int64_t* adj_ptr, const int32_t* adj, double* residue);
 
+/* ---- the S3 operators on unstructured meshes without stored tables (new) ----------------------------------------------
+ * mfem_op_var_batch / mfem_op_res_batch / mfem_op_kval_batch with geometry on the fly: the same sums, to round-off, computed from
+ * coordinates, connectivity and the reference tables instead of integral_vals[itg, itp, 1 + dim, nel] (17 KB per hex-20 element).
+ * Mesh inputs as mfem_mesh_assemble_elements / _facets; term arrays as the batch operators ([host], at most MFEM_MAX_BATCH_TERMS,
+ * sd 0 = value, 1 + j = d/dx_j); `vals` / `targets` term-major, term t at + t * itg * n_items, entry [q, u] of work unit u at
+ * q + itg * u.  elIDs / facetIDs (optional, ids per index_base): the item work unit u processes (e.g. the colour order).
+ * ONE DIFFERENCE to mfem_op_*: `vals` holds the COEFFICIENT only -- the kernels multiply by w_q det_q (facets: w_q * surface det),
+ * where the reference writes vals = @. expr * K_params * w (05_CodeGenerator.jl:75,110,136).  No weight array exists on this path.
+ * All of them return MFEM_ERR_UNSUPPORTED, before anything is launched or written, when itg * itp * (1 + dim) doubles or one wave's
+ * LDS block exceed 64 KB (or a cap named below): use mfem_op_* on the stored tables then. */
+/* targets[t][q, u] = sum_a D^{sd_t} N_a(q) x_t[cpID_shift_t + cp(a, el)]   (OVERWRITES, as mfem_op_var_batch) */
+int mfem_mesh_var_elements(mfem_context ctx, int32_t dim, int32_t itg, int32_t itp, int64_t nel, int64_t ncp,
+                           const double* ref_itp_vals, const double* itg_weight, const double* coords,
+                           const int32_t* controlpoint_IDs, int32_t index_base, int32_t n_terms, const mfem_var_term* terms,
+                           double* targets, const int32_t* elIDs, int64_t n_items);
+/* Facets: the basis of all host-element nodes evaluated on the face.  normal_directions (optional) [itg_b, dim, n_facets]: the outward
+ * unit normal of every processed facet in the layout of mfem_update_basic_boundary (indexed by FACET, not by work unit; 24 B per Gauss
+ * point); with it n_terms may be 0. */
+int mfem_mesh_var_facets(mfem_context ctx, int32_t dim, int32_t itg_b, int32_t itp, int32_t n_face_ids, int64_t n_facets, int64_t ncp,
+                         const double* bdy_ref_itp_vals, const double* bdy_itg_weights, const double* bdy_tangent_directions,
+                         const double* coords, const int32_t* controlpoint_IDs, const int32_t* element_ID,
+                         const int32_t* element_eindex, int32_t index_base, int32_t n_terms, const mfem_var_term* terms,
+                         double* targets, double* normal_directions, const int32_t* facetIDs, int64_t n_items);
+/* residue[cpID_shift_t + cp(a, el)] += sum_q D^{dual_sd_t} N_a(q) vals_t[q, u] w_q det_q, terms sorted by cpID_shift.  Two passes as
+ * mfem_mesh_residual_*: element vectors per dual field -> library-owned scratch, then one lane per (field, control point) sums its
+ * adjacency list (adj_ptr, adj as there: item * itp + local node, ascending) -- accumulating, no atomics, bitwise reproducible,
+ * collapsed elements handled.  Every item is processed: the work units are all nel elements / n_facets facets (elIDs / facetIDs:
+ * a permutation of them, or NULL).  MFEM_ERR_UNSUPPORTED for more than 8 distinct cpID_shift per call. */
+int mfem_mesh_res_elements(mfem_context ctx, int32_t dim, int32_t itg, int32_t itp, int64_t nel, int64_t ncp,
+                           const double* ref_itp_vals, const double* itg_weight, const double* coords,
+                           const int32_t* controlpoint_IDs, int32_t index_base, int32_t n_terms, const mfem_res_term* terms,
+                           const double* vals, const int32_t* elIDs, const int64_t* adj_ptr, const int32_t* adj, double* residue);
+int mfem_mesh_res_facets(mfem_context ctx, int32_t dim, int32_t itg_b, int32_t itp, int32_t n_face_ids, int64_t n_facets, int64_t ncp,
+                         const double* bdy_ref_itp_vals, const double* bdy_itg_weights, const double* bdy_tangent_directions,
+                         const double* coords, const int32_t* controlpoint_IDs, const int32_t* element_ID,
+                         const int32_t* element_eindex, int32_t index_base, int32_t n_terms, const mfem_res_term* terms,
+                         const double* vals, const int32_t* facetIDs, const int64_t* adj_ptr, const int32_t* adj, double* residue);
+/* K[slot(a, b, el; block_t)] += sum_q D^{dual_sd_t} N_a(q) D^{base_sd_t} N_b(q) vals_t[q, u] w_q det_q, the terms of a block summed
+ * before the single accumulate; slot(a, b, el; u) = sparse_IDs_by_el[u * slot_block_stride + a + itp * (b + itp * el)].
+ * n_colours = 0 -> FP64 atomics, else colour_offsets[n_colours + 1] [host] partitions the n_items work units. */
+int mfem_mesh_kval_elements(mfem_context ctx, int32_t dim, int32_t itg, int32_t itp, int64_t nel, int64_t ncp,
+                            const double* ref_itp_vals, const double* itg_weight, const double* coords,
+                            const int32_t* controlpoint_IDs, int32_t index_base, int32_t n_terms, const mfem_kval_term* terms,
+                            const double* vals, const int32_t* sparse_IDs_by_el, int64_t slot_block_stride, double* K_val,
+                            const int32_t* elIDs, int64_t n_items, int32_t n_colours, const int64_t* colour_offsets);
+/* Row-owner form (arguments and refusals of mfem_mesh_assemble_elements_rows; block = dual_pos * n_fields + base_pos): element
+ * matrices -> element-major scratch -> the row-owner gather.  K_val is ACCUMULATED into; no atomics, bitwise reproducible.  The
+ * work units are all nel elements (elIDs: a permutation, or NULL). */
+int mfem_mesh_kval_elements_rows(mfem_context ctx, int32_t dim, int32_t itg, int32_t itp, int64_t nel, int64_t ncp,
+                                 const double* ref_itp_vals, const double* itg_weight, const double* coords,
+                                 const int32_t* controlpoint_IDs, int32_t index_base, int32_t n_terms, const mfem_kval_term* terms,
+                                 const double* vals, const int32_t* elIDs, int32_t n_fields, mfem_csr A, const int64_t* adj_ptr,
+                                 const int32_t* adj, const uint16_t* ranks, double* K_val);
+int mfem_mesh_kval_facets(mfem_context ctx, int32_t dim, int32_t itg_b, int32_t itp, int32_t n_face_ids, int64_t n_facets, int64_t ncp,
+                          const double* bdy_ref_itp_vals, const double* bdy_itg_weights, const double* bdy_tangent_directions,
+                          const double* coords, const int32_t* controlpoint_IDs, const int32_t* element_ID,
+                          const int32_t* element_eindex, int32_t index_base, int32_t n_terms, const mfem_kval_term* terms,
+                          const double* vals, const int32_t* sparse_IDs_by_el, int64_t slot_block_stride, double* K_val,
+                          const int32_t* facetIDs, int64_t n_items, int32_t n_colours, const int64_t* colour_offsets);
+
 /* ---- multi-GPU (new; the reference is single-GPU, F6) ------------------------------------ */
 /* 128-byte RCCL unique id, created on rank 0 and shipped to the other ranks by the host
  * (torch.distributed / MPI / a file).  */

@@ -116,6 +116,8 @@ long long mfem_debug_graph_launch_count(void);
 int64_t mfem_debug_mesh_rows_count(void);
 /* number of mfem_mesh_residual_elements / _facets calls that launched the fused residual (process-wide) */
 int64_t mfem_debug_mesh_residual_count(void);
+/* number of mfem_mesh_var_* / mfem_mesh_res_* / mfem_mesh_kval_* calls that took a table-free launch (process-wide) */
+int64_t mfem_debug_mesh_ops_count(void);
 /* variants of the fused mesh assembly launched so far (process-wide), one bit per (dim, mode, kind): bit ((dim - 2) * 3 + mode) * 9 + kind, mode 0
  * values + gradients, 1 gradients only, 2 values only; kind 0/1 colour batches with the dense coefficient rows / the term list, 2/3 the same with FP64
  * atomics, 4/5 the same in the row-owner scratch form (elements of fewer than 16 nodes), 6 row-owner with 16+ nodes, 7 staged row-owner, 8 staged with

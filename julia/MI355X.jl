@@ -433,6 +433,88 @@ function row_ranks!(ranks::ROCArray{UInt16}, itp, nel, ncp, n_fields, A::CSRPatt
     return ranks
 end
 
+# ---- S3 on unstructured meshes without update_BasicElements tables (mfem_mesh_var_* / _res_* / _kval_*) ---------------------------
+# The batch operators with geometry on the fly.  ONE difference to var_batch! / res_batch! / kval_batch!: `vals` is the coefficient alone
+# (`@. expr * K_params`, WITHOUT `* w`): the kernels multiply by w_q det_q.  `ids`: the item of every work unit (1-based) or nothing.
+# Each returns false (nothing written) on MFEM_ERR_UNSUPPORTED: build the tables and take the operator path for that integration domain then.
+mesh_unsupported(rc) = rc == -3 ? false : (check(rc); true)
+
+function mesh_var_elements!(targets, dim, itg, itp, nel, ncp, ref_itp_vals, itg_weight, coords, controlpoint_IDs, terms::Vector{VarTerm}, ids, n_items)
+    mesh_unsupported(ccall((:mfem_mesh_var_elements, lib), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{VarTerm}, Ptr{Cvoid},
+         Ptr{Cvoid}, Int64),
+        ctx(), dim, itg, itp, nel, ncp, dptr(ref_itp_vals), dptr(itg_weight), dptr(coords), dptr(controlpoint_IDs), 1, length(terms), terms,
+        dptr(targets), dptr(ids), n_items))
+end
+
+"`normals` (or nothing): normal_directions[itg_b, dim, n_facets] to fill, the layout of update_BasicBoundary."
+function mesh_var_facets!(targets, normals, dim, itg_b, itp, n_face_ids, nf, ncp, bdy_ref_itp_vals, bdy_itg_weights, bdy_tangent_directions, coords,
+                          controlpoint_IDs, element_ID, element_eindex, terms::Vector{VarTerm}, ids, n_items)
+    mesh_unsupported(ccall((:mfem_mesh_var_facets, lib), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+         Int32, Int32, Ptr{VarTerm}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int64),
+        ctx(), dim, itg_b, itp, n_face_ids, nf, ncp, dptr(bdy_ref_itp_vals), dptr(bdy_itg_weights), dptr(bdy_tangent_directions), dptr(coords),
+        dptr(controlpoint_IDs), dptr(element_ID), dptr(element_eindex), 1, length(terms), terms, dptr(targets), dptr(normals), dptr(ids), n_items))
+end
+
+"residue is ACCUMULATED into; `terms` sorted by cpID_shift; `adj_ptr`, `adj`: the adjacency of `residual_affine_terms!`."
+function mesh_res_elements!(residue, dim, itg, itp, nel, ncp, ref_itp_vals, itg_weight, coords, controlpoint_IDs, terms::Vector{ResTerm}, vals, ids,
+                            adj_ptr, adj)
+    mesh_unsupported(ccall((:mfem_mesh_res_elements, lib), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{ResTerm}, Ptr{Cvoid},
+         Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        ctx(), dim, itg, itp, nel, ncp, dptr(ref_itp_vals), dptr(itg_weight), dptr(coords), dptr(controlpoint_IDs), 1, length(terms), terms,
+        dptr(vals), dptr(ids), dptr(adj_ptr), dptr(adj), dptr(residue)))
+end
+
+function mesh_res_facets!(residue, dim, itg_b, itp, n_face_ids, nf, ncp, bdy_ref_itp_vals, bdy_itg_weights, bdy_tangent_directions, coords,
+                          controlpoint_IDs, element_ID, element_eindex, terms::Vector{ResTerm}, vals, ids, adj_ptr, adj)
+    mesh_unsupported(ccall((:mfem_mesh_res_facets, lib), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+         Int32, Int32, Ptr{ResTerm}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        ctx(), dim, itg_b, itp, n_face_ids, nf, ncp, dptr(bdy_ref_itp_vals), dptr(bdy_itg_weights), dptr(bdy_tangent_directions), dptr(coords),
+        dptr(controlpoint_IDs), dptr(element_ID), dptr(element_eindex), 1, length(terms), terms, dptr(vals), dptr(ids), dptr(adj_ptr), dptr(adj),
+        dptr(residue)))
+end
+
+"K_val is ACCUMULATED into through the slot table; `terms` sorted by block; `colour_offsets` (host Vector{Int64}) or nothing -> FP64 atomics."
+function mesh_kval_elements!(K_val, dim, itg, itp, nel, ncp, ref_itp_vals, itg_weight, coords, controlpoint_IDs, terms::Vector{KvalTerm}, vals,
+                             sparse_IDs_by_el, slot_block_stride, ids, n_items, colour_offsets = nothing)
+    nc = colour_offsets === nothing ? 0 : length(colour_offsets) - 1
+    co = colour_offsets === nothing ? Ptr{Int64}(C_NULL) : pointer(colour_offsets)
+    GC.@preserve colour_offsets mesh_unsupported(ccall((:mfem_mesh_kval_elements, lib), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{KvalTerm}, Ptr{Cvoid},
+         Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Int64}),
+        ctx(), dim, itg, itp, nel, ncp, dptr(ref_itp_vals), dptr(itg_weight), dptr(coords), dptr(controlpoint_IDs), 1, length(terms), terms,
+        dptr(vals), dptr(sparse_IDs_by_el), slot_block_stride, dptr(K_val), dptr(ids), n_items, nc, co))
+end
+
+"Row-owner form (`adj_ptr`, `adj`, `ranks` of `row_ranks!`; block = dual_pos * n_fields + base_pos): no atomics, bitwise reproducible."
+function mesh_kval_elements_rows!(K_val, dim, itg, itp, nel, ncp, ref_itp_vals, itg_weight, coords, controlpoint_IDs, terms::Vector{KvalTerm}, vals,
+                                  ids, n_fields, A::CSRPattern, adj_ptr, adj, ranks)
+    mesh_unsupported(ccall((:mfem_mesh_kval_elements_rows, lib), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32, Ptr{KvalTerm}, Ptr{Cvoid},
+         Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        ctx(), dim, itg, itp, nel, ncp, dptr(ref_itp_vals), dptr(itg_weight), dptr(coords), dptr(controlpoint_IDs), 1, length(terms), terms,
+        dptr(vals), dptr(ids), n_fields, A.h, dptr(adj_ptr), dptr(adj), dptr(ranks), dptr(K_val)))
+end
+
+function mesh_kval_facets!(K_val, dim, itg_b, itp, n_face_ids, nf, ncp, bdy_ref_itp_vals, bdy_itg_weights, bdy_tangent_directions, coords,
+                           controlpoint_IDs, element_ID, element_eindex, terms::Vector{KvalTerm}, vals, sparse_IDs_by_el, slot_block_stride, ids,
+                           n_items, colour_offsets = nothing)
+    nc = colour_offsets === nothing ? 0 : length(colour_offsets) - 1
+    co = colour_offsets === nothing ? Ptr{Int64}(C_NULL) : pointer(colour_offsets)
+    GC.@preserve colour_offsets mesh_unsupported(ccall((:mfem_mesh_kval_facets, lib), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Int32, Int32, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid},
+         Int32, Int32, Ptr{KvalTerm}, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Int64, Int32, Ptr{Int64}),
+        ctx(), dim, itg_b, itp, n_face_ids, nf, ncp, dptr(bdy_ref_itp_vals), dptr(bdy_itg_weights), dptr(bdy_tangent_directions), dptr(coords),
+        dptr(controlpoint_IDs), dptr(element_ID), dptr(element_eindex), 1, length(terms), terms, dptr(vals), dptr(sparse_IDs_by_el),
+        slot_block_stride, dptr(K_val), dptr(ids), n_items, nc, co))
+end
+
+"Calls that took a table-free launch so far (process-wide)."
+mesh_ops_count() = ccall((:mfem_debug_mesh_ops_count, lib), Int64, ())
+
 # ---- several GPUs: one Julia process per GPU (MPI.jl), slab decomposition along the first dimension ---------------------------
 "Rank 0 creates the 128-byte RCCL id; the host broadcasts it (MPI.Bcast!)."
 function comm_unique_id()

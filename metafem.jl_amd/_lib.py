@@ -215,6 +215,21 @@ SIGNATURES = {
     "mfem_mesh_residual_facets": (c_int, [P, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, P, P, P, c_int32,
                                           c_int32, C.POINTER(ResSymbol), c_int32, C.POINTER(AffineTerm), P, P, P]),
     "mfem_debug_mesh_residual_count": (c_int64, []),
+    "mfem_mesh_var_elements": (c_int, [P, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, c_int32, c_int32,
+                                       C.POINTER(VarBatchTerm), P, P, c_int64]),
+    "mfem_mesh_var_facets": (c_int, [P, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, P, P, P, c_int32,
+                                     c_int32, C.POINTER(VarBatchTerm), P, P, P, c_int64]),
+    "mfem_mesh_res_elements": (c_int, [P, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, c_int32, c_int32,
+                                       C.POINTER(ResBatchTerm), P, P, P, P, P]),
+    "mfem_mesh_res_facets": (c_int, [P, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, P, P, P, c_int32,
+                                     c_int32, C.POINTER(ResBatchTerm), P, P, P, P, P]),
+    "mfem_mesh_kval_elements": (c_int, [P, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, c_int32, c_int32,
+                                        C.POINTER(KvalTerm), P, P, c_int64, P, P, c_int64, c_int32, C.POINTER(c_int64)]),
+    "mfem_mesh_kval_elements_rows": (c_int, [P, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, c_int32, c_int32,
+                                             C.POINTER(KvalTerm), P, P, c_int32, P, P, P, P, P]),
+    "mfem_mesh_kval_facets": (c_int, [P, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, P, P, P, c_int32,
+                                      c_int32, C.POINTER(KvalTerm), P, P, c_int64, P, P, c_int64, c_int32, C.POINTER(c_int64)]),
+    "mfem_debug_mesh_ops_count": (c_int64, []),
     "mfem_comm_unique_id": (c_int, [P]),
     "mfem_comm_create": (c_int, [P, c_int32, c_int32, P, C.POINTER(P)]),
     "mfem_comm_destroy": (c_int, [P]),

@@ -485,19 +485,9 @@ extern "C" int mfem_mesh_assemble_elements(mfem_context ctx, int32_t dim, int32_
 // (fd, fb), adds the itp contiguous scratch entries  S[el][a][k][0 .. itp)  at the positions of the columns
 // fb * ncp + node(el, b) (binary search in the staged list) -- distinct positions within a step, steps in sequence: no
 // atomics, a fixed summation order (bitwise reproducible), every K entry read and written once, contiguously.
-#define MG_MAXROW 2048
 static std::atomic<long long> g_mesh_rows_count{0};
 int g_mesh_gather_rows = 0;  // mfem_debug_set("mesh_gather_rows"): 1 = the gather by row of round 5 (A/B, tests)  // assemblies that took the row-owner form (tests, bench.py)
 extern "C" int64_t mfem_debug_mesh_rows_count(void) { return g_mesh_rows_count; }
-// element-matrix scratch the row-owner form may take from the context workspace (288 GB of HBM: hex-20 elasticity at 128^3 needs 60 GB)
-static const size_t MG_SCRATCH_BUDGET = (size_t)96 << 30;
-struct GatherBlocks {
-  int nf;          // fields
-  int nb;          // blocks in the scratch (runs of the term list)
-  int cnt[4];      // blocks with dual field fd
-  int k[4][4];     // their scratch index
-  int fb[4][4];    // their base field
-};
 
 // ranks[(j * itp) + b] = position of node(el, b) among the control points coupled to node i (ascending ids = the order of
 // the columns inside every field segment of a row of node i), for adjacency entry j = (i <- el, a).  Once per pattern.
@@ -726,6 +716,50 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_mesh_gather_nodes(int itp, int64
   }
 }
 
+// Pass 2 of the row-owner forms (here and mesh_ops.hip): adds the element-major scratch S, row by row, into K_val (overwrite: sets the rows).
+int mfem_mesh_gather_launch(mfem_context_s* ctx, int itp, int64_t ncp, const GatherBlocks& B, mfem_csr_s* A, const int64_t* adj_ptr,
+                            const int32_t* adj, const uint16_t* ranks, const double* S, double* K_val, int overwrite) {
+  const int n_fields = B.nf;
+  const int64_t nrows = (int64_t)n_fields * ncp;
+  const int maxrow = (A->max_row_nnz + 15) & ~15;
+  const int waves = 4;
+  int work = 0;
+  for (int fd = 0; fd < n_fields; ++fd) work = B.cnt[fd] * itp > work ? B.cnt[fd] * itp : work;
+  int G = work > 0 && work <= 64 ? 64 / work : 0;
+  auto lds_nodes = [&](int g) { return sizeof(double) * (size_t)maxrow * waves * g * n_fields; };
+  while (G > 1 && lds_nodes(G) > 32 * 1024) --G;  // (long rows: fewer nodes side by side)
+  if (G > 0 && lds_nodes(G) <= 64 * 1024 && !g_mesh_gather_rows) {  // by node (k_mesh_gather_nodes)
+    const size_t ldsn = lds_nodes(G);
+    const int gridn = mfem_grid_for((ncp + G - 1) / G, waves, ctx->num_cus * 16);
+#define MG_NODES(RP, NF)                                                                                                                    \
+  hipLaunchKernelGGL((k_mesh_gather_nodes<RP, NF>), dim3(gridn), dim3(64 * waves), ldsn, ctx->stream, itp, ncp, B, (const RP*)A->rowptr, \
+                     A->index_base, adj_ptr, adj, ranks, S, K_val, maxrow, work, G, overwrite)
+#define MG_FIELDS(RP)                                \
+  do {                                               \
+    if (n_fields == 1) MG_NODES(RP, 1);              \
+    else if (n_fields == 2) MG_NODES(RP, 2);         \
+    else if (n_fields == 3) MG_NODES(RP, 3);         \
+    else MG_NODES(RP, 4);                            \
+  } while (0)
+    if (A->rowptr_bits == 64) MG_FIELDS(int64_t); else MG_FIELDS(int32_t);
+#undef MG_FIELDS
+#undef MG_NODES
+    MFEM_CHECK_LAUNCH();
+    return MFEM_OK;
+  }
+  const size_t ldsb = sizeof(double) * (size_t)maxrow * waves;
+  const int grid = mfem_grid_for(nrows, waves, ctx->num_cus * 32);
+  if (A->rowptr_bits == 64)
+    hipLaunchKernelGGL(k_mesh_gather<int64_t>, dim3(grid), dim3(64 * waves), ldsb, ctx->stream, itp, ncp, B, (const int64_t*)A->rowptr,
+                       A->index_base, adj_ptr, adj, ranks, S, K_val, maxrow, overwrite);
+  else
+    hipLaunchKernelGGL(k_mesh_gather<int32_t>, dim3(grid), dim3(64 * waves), ldsb, ctx->stream, itp, ncp, B, (const int32_t*)A->rowptr,
+                       A->index_base, adj_ptr, adj, ranks, S, K_val, maxrow, overwrite);
+  MFEM_CHECK_LAUNCH();
+  return MFEM_OK;
+}
+
+
 static int mesh_rows(mfem_context_s* ctx, int32_t dim, int32_t itg, int32_t itp, int64_t nel, int64_t ncp, const double* ref_itp_vals,
                      const double* itg_weight, const double* coords, const int32_t* controlpoint_IDs, int32_t index_base, int32_t n_terms,
                      const mfem_const_term* terms, int32_t n_fields, mfem_csr_s* A, const int64_t* adj_ptr, const int32_t* adj,
@@ -772,43 +806,8 @@ static int mesh_rows(mfem_context_s* ctx, int32_t dim, int32_t itg, int32_t itp,
   MeshItems V{itg, itp, ncp, ref_itp_vals, 0, itg_weight, 0, nullptr, 0, coords, controlpoint_IDs, nullptr, nullptr, nullptr, index_base};
   rc = ma_launch(ctx, dim, V, T, nullptr, 0, S, nel, 0, nullptr, B.nb);
   if (rc) return rc;
-  const int64_t nrows = (int64_t)n_fields * ncp;
-  const int maxrow = (A->max_row_nnz + 15) & ~15;
-  const int waves = 4;
-  int work = 0;
-  for (int fd = 0; fd < n_fields; ++fd) work = B.cnt[fd] * itp > work ? B.cnt[fd] * itp : work;
-  int G = work > 0 && work <= 64 ? 64 / work : 0;
-  auto lds_nodes = [&](int g) { return sizeof(double) * (size_t)maxrow * waves * g * n_fields; };
-  while (G > 1 && lds_nodes(G) > 32 * 1024) --G;  // (long rows: fewer nodes side by side)
-  if (G > 0 && lds_nodes(G) <= 64 * 1024 && !g_mesh_gather_rows) {  // by node (k_mesh_gather_nodes)
-    const size_t ldsn = lds_nodes(G);
-    const int gridn = mfem_grid_for((ncp + G - 1) / G, waves, ctx->num_cus * 16);
-#define MG_NODES(RP, NF)                                                                                                                    \
-  hipLaunchKernelGGL((k_mesh_gather_nodes<RP, NF>), dim3(gridn), dim3(64 * waves), ldsn, ctx->stream, itp, ncp, B, (const RP*)A->rowptr, \
-                     A->index_base, adj_ptr, adj, ranks, S, K_val, maxrow, work, G, overwrite)
-#define MG_FIELDS(RP)                                \
-  do {                                               \
-    if (n_fields == 1) MG_NODES(RP, 1);              \
-    else if (n_fields == 2) MG_NODES(RP, 2);         \
-    else if (n_fields == 3) MG_NODES(RP, 3);         \
-    else MG_NODES(RP, 4);                            \
-  } while (0)
-    if (A->rowptr_bits == 64) MG_FIELDS(int64_t); else MG_FIELDS(int32_t);
-#undef MG_FIELDS
-#undef MG_NODES
-    MFEM_CHECK_LAUNCH();
-    ++g_mesh_rows_count;
-    return MFEM_OK;
-  }
-  const size_t ldsb = sizeof(double) * (size_t)maxrow * waves;
-  const int grid = mfem_grid_for(nrows, waves, ctx->num_cus * 32);
-  if (A->rowptr_bits == 64)
-    hipLaunchKernelGGL(k_mesh_gather<int64_t>, dim3(grid), dim3(64 * waves), ldsb, ctx->stream, itp, ncp, B, (const int64_t*)A->rowptr,
-                       A->index_base, adj_ptr, adj, ranks, S, K_val, maxrow, overwrite);
-  else
-    hipLaunchKernelGGL(k_mesh_gather<int32_t>, dim3(grid), dim3(64 * waves), ldsb, ctx->stream, itp, ncp, B, (const int32_t*)A->rowptr,
-                       A->index_base, adj_ptr, adj, ranks, S, K_val, maxrow, overwrite);
-  MFEM_CHECK_LAUNCH();
+  rc = mfem_mesh_gather_launch(ctx, itp, ncp, B, A, adj_ptr, adj, ranks, S, K_val, overwrite);
+  if (rc) return rc;
   ++g_mesh_rows_count;
   return MFEM_OK;
 }

@@ -139,3 +139,18 @@ __device__ __forceinline__ void mg_table(const double* R, const double* Ji, doub
     }
   }
 }
+
+// ---- pass 2 of the row-owner forms (assemble_mesh.hip: k_mesh_gather / k_mesh_gather_nodes), shared with mesh_ops.hip ------------------------
+#define MG_MAXROW 2048  // longest CSR row the gather stages in LDS
+// element-matrix scratch the row-owner form may take from the context workspace (288 GB of HBM: hex-20 elasticity at 128^3 needs 60 GB)
+static const size_t MG_SCRATCH_BUDGET = (size_t)96 << 30;
+struct GatherBlocks {
+  int nf;          // fields
+  int nb;          // blocks in the scratch (runs of the term list)
+  int cnt[4];      // blocks with dual field fd
+  int k[4][4];     // their scratch index
+  int fb[4][4];    // their base field
+};
+// adds (overwrite: sets) the element-major scratch S[((el * itp + a) * nb + k) * itp + b] into the rows of K_val; the launch lives with the kernels
+int mfem_mesh_gather_launch(mfem_context_s* ctx, int itp, int64_t ncp, const GatherBlocks& B, mfem_csr_s* A, const int64_t* adj_ptr,
+                            const int32_t* adj, const uint16_t* ranks, const double* S, double* K_val, int overwrite);

@@ -97,6 +97,7 @@ class _Group:
     def __init__(self, build, host_ids, el_ids, itg, colour_offsets=None, facet_el=None, facet_eidx=None):
         self._build, self._tables = build, None
         self.host_ids, self.el_ids, self.itg = host_ids, el_ids, itg
+        self.table_free = False  # set by GenericDomain(table_free=True); cleared for good when an entry point refuses this group
         self.colour_offsets = colour_offsets
         self.facet_el, self.facet_eidx = facet_el, facet_eidx  # boundary groups: element / local face id of every facet
         self.n = el_ids.numel()
@@ -122,7 +123,8 @@ class GenericDomain:
     def __init__(self, ctx, space, coords: np.ndarray, cp_ids: np.ndarray, n_fields: int, domain_wf: WeakForm,
                  boundaries: Sequence[Tuple[np.ndarray, np.ndarray, WeakForm]],
                  element_colours: Optional[np.ndarray] = None, max_time_level: int = 0, dissipative: bool = True,
-                 batched: bool = True, fused: bool = True, row_owner: bool = True, fused_residual: bool = False):
+                 batched: bool = True, fused: bool = True, row_owner: bool = True, fused_residual: bool = False,
+                 table_free: bool = False):
         """coords [ncp, dim]; cp_ids [itp, nel] 0-based (controlpoint_IDs in basis order); boundaries =
         [(element_ID[nf], element_eindex[nf] 0-based local face ids, WeakForm)].  element_colours (optional):
         a colour per element such that same-colour elements share no control point -> atomics-free scatter with a fixed
@@ -142,6 +144,15 @@ class GenericDomain:
         # mfem_mesh_residual_elements / _facets (geometry on the fly, one launch per integration domain); the other terms keep the
         # operator path, and the geometry tables it reads are built only if some group still needs them (table_bytes)
         self.fused_residual = fused_residual
+        # table_free = True (implies fused and fused_residual): every other term -- the words of inner_vars and nodal externals, facet normals,
+        # non-affine residual terms, variable-coefficient and nonlinear gradient terms -- goes through mfem_mesh_var_* / _res_* / _kval_*
+        # (csrc/mesh_ops.hip: the S3 operators with geometry on the fly); no group builds its tables (table_bytes stays 0) unless an entry
+        # point answers MFEM_ERR_UNSUPPORTED, after which that group alone takes the operator path
+        self.table_free = table_free
+        if table_free:
+            if not batched:
+                raise ValueError("table_free=True needs batched=True: the single-term seam (mfem_op_var / _res / _kval) reads the stored tables")
+            self.fused = self.fused_residual = fused = fused_residual = True
         self._affine_cache: Dict[Tuple[int, int], Tuple[Tuple[float, float], list]] = {}
         dev = f"cuda:{ctx.device}"
         self.dev = dev
@@ -216,6 +227,8 @@ class GenericDomain:
         if not fused_residual:  # (the operator path reads the tables at every residual: built here, as they always were)
             for g in self.groups:
                 g.tables()
+        for g in self.groups:
+            g.table_free = table_free
         # ---- assemble_Global_Variables!
         from . import assemble_SparseID  # late import: package root defines it
 
@@ -295,6 +308,10 @@ class GenericDomain:
     def _var_many(self, g: _Group, words) -> List[torch.Tensor]:
         """words: [(sd, shift, x tensor)] -> list of [n_items, itg] tensors."""
         out: List[torch.Tensor] = []
+        if g.table_free and words:
+            got = self._var_free(g, words, None)
+            if got is not None:
+                return got
         L, _k = self._layout(g, False)
         for c0 in range(0, len(words), _lib.MAX_BATCH_TERMS):
             chunk = words[c0:c0 + _lib.MAX_BATCH_TERMS]
@@ -310,6 +327,12 @@ class GenericDomain:
         if not terms:
             return
         order = sorted(range(len(terms)), key=lambda i: terms[i].dual_pos * self.n_fields + terms[i].base_pos)
+        if g.table_free:
+            order = self._kval_free(g, terms, order, env, K)
+            if not order:
+                return
+        if w is None:
+            w = self._w(g)
         L, _k = self._layout(g, True)
         stride = self.nel * self.itp * self.itp
         for c0 in range(0, len(order), _lib.MAX_BATCH_TERMS):
@@ -325,6 +348,12 @@ class GenericDomain:
         if not terms:
             return
         order = sorted(range(len(terms)), key=lambda i: terms[i].dual_pos)
+        if g.table_free:
+            order = self._res_free(g, terms, order, env)
+            if not order:
+                return
+        if w is None:
+            w = self._w(g)
         L, _k = self._layout(g, True)
         for c0 in range(0, len(order), _lib.MAX_BATCH_TERMS):
             ids = order[c0:c0 + _lib.MAX_BATCH_TERMS]
@@ -334,6 +363,16 @@ class GenericDomain:
                                         self.cp.data_ptr(), self.residue.data_ptr(), g.host_ids.data_ptr(), g.el_ids.data_ptr(), g.n))
 
     def _externals(self, wf: WeakForm, g: _Group, env: dict):
+        if g.table_free and (wf.cp_ext_vars or wf.normals):
+            nrm = torch.empty((g.facet_el.numel(), self.dim, g.itg), dtype=torch.float64, device=self.dev) if wf.normals else None
+            tg = self._var_free(g, [(s, 0, self.controlpoints[sym]) for _, sym, s in wf.cp_ext_vars], nrm)
+            if tg is not None:
+                for (name, _, _), t in zip(wf.cp_ext_vars, tg):
+                    env[name] = t
+                for name, comp in wf.normals:
+                    env[name] = nrm[:, comp, :][(g.host_ids - 1).long()]
+                env["t"], env["dt"] = self.t, self.dt
+                return
         if self.batched and wf.cp_ext_vars:
             tg = self._var_many(g, [(s, 0, self.controlpoints[sym]) for _, sym, s in wf.cp_ext_vars])
             for (name, _, _), t in zip(wf.cp_ext_vars, tg):
@@ -350,6 +389,90 @@ class GenericDomain:
         if not torch.is_tensor(v):
             v = torch.full_like(w, float(v))
         return (v * scale * w).contiguous()
+
+    # -- table-free operator wrappers (mfem_mesh_var_* / _res_* / _kval_*): the coefficient WITHOUT the weight, geometry on the fly ------
+    def _refused(self, g: _Group, rc: int) -> bool:
+        """MFEM_ERR_UNSUPPORTED from a table-free entry point: this group takes the operator path (and builds its tables) from now on."""
+        if rc == -3:
+            g.table_free = False
+            return True
+        check(rc)
+        return False
+
+    def _mesh_args(self, g: _Group):
+        """The leading mesh arguments of the table-free entry points for this group."""
+        h = self.ctx._h
+        if g.facet_el is None:
+            return (h, self.dim, self.space.itg, self.itp, self.nel, self.ncp, self._ref.data_ptr(), self._itgw.data_ptr(),
+                    self.coords.data_ptr(), self.cp.data_ptr(), 1)
+        return (h, self.dim, self.space.itg_b, self.itp, self._nface, g.facet_el.numel(), self.ncp, self._bref.data_ptr(), self._bw.data_ptr(),
+                self._btan.data_ptr(), self.coords.data_ptr(), self.cp.data_ptr(), g.facet_el.data_ptr(), g.facet_eidx.data_ptr(), 1)
+
+    def _coef(self, g: _Group, fn, env, scale=1.0) -> torch.Tensor:
+        """The coefficient of a term as [n_items, itg], without the weight (a scalar is broadcast)."""
+        v = fn(env)
+        if not torch.is_tensor(v):
+            return torch.full((g.n, g.itg), float(v) * scale, dtype=torch.float64, device=self.dev)
+        v = (v * scale).to(torch.float64)
+        return v.expand(g.n, g.itg).contiguous()
+
+    def _var_free(self, g: _Group, words, normals) -> Optional[List[torch.Tensor]]:
+        """_var_many without tables; normals (facets): the tensor [n_facets, dim, itg_b] to fill.  None: refused, nothing usable written."""
+        out: List[torch.Tensor] = []
+        chunks = [words[c0:c0 + _lib.MAX_BATCH_TERMS] for c0 in range(0, len(words), _lib.MAX_BATCH_TERMS)] or [[]]
+        for k, chunk in enumerate(chunks):
+            tgt = torch.empty((len(chunk), g.n, g.itg), dtype=torch.float64, device=self.dev)
+            terms = (_lib.VarBatchTerm * max(len(chunk), 1))(*[_lib.VarBatchTerm(sd, 0, shift, x.data_ptr()) for sd, shift, x in chunk])
+            if g.facet_el is None:
+                rc = lib.mfem_mesh_var_elements(*self._mesh_args(g), len(chunk), terms, tgt.data_ptr(), g.host_ids.data_ptr(), g.n)
+            else:
+                nptr = normals.data_ptr() if normals is not None and k == 0 else None
+                rc = lib.mfem_mesh_var_facets(*self._mesh_args(g), len(chunk), terms, tgt.data_ptr() if chunk else None, nptr,
+                                              g.host_ids.data_ptr(), g.n)
+            if self._refused(g, rc):
+                return None
+            out += [tgt[i] for i in range(len(chunk))]
+        return out
+
+    def _res_free(self, g: _Group, terms, order, env) -> list:
+        """_res_many without tables; returns the term ids the operator path still has to add (empty unless refused)."""
+        ptr, adj = self._residual_adj(g)
+        fn = lib.mfem_mesh_res_elements if g.facet_el is None else lib.mfem_mesh_res_facets
+        for c0 in range(0, len(order), _lib.MAX_BATCH_TERMS):
+            ids = order[c0:c0 + _lib.MAX_BATCH_TERMS]
+            vals = torch.stack([self._coef(g, terms[i].fn, env) for i in ids])
+            arr = (_lib.ResBatchTerm * len(ids))(*[_lib.ResBatchTerm(terms[i].dual_s, 0, terms[i].dual_pos * self.ncp) for i in ids])
+            rc = fn(*self._mesh_args(g), len(ids), arr, vals.data_ptr(), g.host_ids.data_ptr(), ptr.data_ptr(), adj.data_ptr(),
+                    self.residue.data_ptr())
+            if self._refused(g, rc):
+                return order[c0:]
+        return []
+
+    def _kval_free(self, g: _Group, terms, order, env, K: torch.Tensor) -> list:
+        """_kval_many without tables: the row-owner form on elements when the ranks exist, else the scatter form; returns the term ids left."""
+        offs = g.colour_offsets
+        ncol = 0 if offs is None else len(offs) - 1
+        carr = None if offs is None else (C.c_int64 * len(offs))(*[int(v) for v in offs])
+        stride = self.nel * self.itp * self.itp
+        for c0 in range(0, len(order), _lib.MAX_BATCH_TERMS):
+            ids = order[c0:c0 + _lib.MAX_BATCH_TERMS]
+            vals = torch.stack([self._coef(g, terms[i].fn, env, self.K_params[terms[i].td_order]) for i in ids])
+            arr = (_lib.KvalTerm * len(ids))(*[_lib.KvalTerm(terms[i].dual_s, terms[i].base_s,
+                                                             terms[i].dual_pos * self.n_fields + terms[i].base_pos, 0) for i in ids])
+            if g.facet_el is None and self.row_owner and self._row_ranks() is not None:
+                rc = lib.mfem_mesh_kval_elements_rows(*self._mesh_args(g), len(ids), arr, vals.data_ptr(), g.host_ids.data_ptr(), self.n_fields,
+                                                      self.A._h, self._adj_ptr.data_ptr(), self._adj.data_ptr(), self._ranks.data_ptr(),
+                                                      K.data_ptr())
+                if rc == 0:
+                    continue
+                if rc != -3:  # (MFEM_ERR_UNSUPPORTED: row too long / scratch too large -> the scatter form decides)
+                    check(rc)
+            fn = lib.mfem_mesh_kval_elements if g.facet_el is None else lib.mfem_mesh_kval_facets
+            rc = fn(*self._mesh_args(g), len(ids), arr, vals.data_ptr(), self.slots.data_ptr(), stride, K.data_ptr(), g.host_ids.data_ptr(), g.n,
+                    ncol, carr)
+            if self._refused(g, rc):
+                return order[c0:]
+        return []
 
     def _parts(self):
         yield self.domain_wf, self.groups[0]
@@ -428,10 +551,10 @@ class GenericDomain:
             self._K_started(self.K_linear)
             env: dict = {}
             self._externals(wf, g, env)
-            w = self._w(g)
             if self.batched:
-                self._kval_many(g, terms, env, w, self.K_linear)
+                self._kval_many(g, terms, env, None if g.table_free else self._w(g), self.K_linear)
                 continue
+            w = self._w(g)
             for t in terms:
                 self._kval(g, t, self._vals(t.fn, env, w, self.K_params[t.td_order]), self.K_linear)
         self._K_started(self.K_linear)
@@ -524,7 +647,7 @@ class GenericDomain:
                 for (name, _, _, _), t in zip(wf.inner_vars, tg):
                     env[name] = t
                 self._externals(wf, g, env)
-                w = self._w(g)
+                w = None if g.table_free else self._w(g)  # (table-free: the kernels multiply the weight in)
                 self._res_many(g, residues, env, w)
                 self._kval_many(g, wf.nonlinear_gradients, env, w, self.K_total)
                 continue
