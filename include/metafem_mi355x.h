@@ -515,6 +515,44 @@ int mfem_mesh_assemble_elements_rows_set(mfem_context ctx, int32_t dim, int32_t 
 int mfem_mesh_row_ranks(mfem_context ctx, int32_t itp, int64_t nel, int64_t ncp, int32_t n_fields, mfem_csr A,
                         const int64_t* adj_ptr, const int32_t* adj, const int32_t* controlpoint_IDs, int32_t index_base,
                         uint16_t* ranks);
+/* Direct form of the row-owner element assembly: the same rows, the same fixed summation order (the adjacency order of a row's control point), and NO
+ * element-matrix scratch.  A wave owns a batch of control points that share elements; for every element adjacent to the batch it builds the geometry
+ * and the physical table in LDS (as the fused assembly does), forms only the element-matrix rows of the batch's control points, adds them into the
+ * batch's rows staged in LDS and stores every row once.  Geometry is recomputed once per (batch, adjacent element); nothing per element goes to
+ * global memory.  Bitwise reproducible, and bit for bit the same under every batch cut.
+ * mfem_mesh_direct_plan_create: the one-off inspector per pattern, kept behind an opaque 64-bit handle (runs on the host: adj_ptr, adj and the row pointer of A are copied back once).
+ * Control points go in stable order of their owner -- the element of their first adjacency entry -- into batches of at most `budget` staged doubles
+ * (sum of n_fields^2 * L_i, L_i = coupled control points of i; the budget is chosen by the library, see mfem_debug_set("mesh_direct_budget")); the
+ * tasks of a batch are its adjacency entries sorted by element (16 bytes each on the device).  adj_ptr, adj, controlpoint_IDs, ranks: [device], as
+ * mfem_mesh_row_ranks takes / fills them; ranks must stay alive as long as the plan, and so must A.
+ * MFEM_ERR_UNSUPPORTED, nothing launched (use mfem_mesh_assemble_elements_rows): n_fields > 4; an element that lists a control point twice; one
+ * control point whose rows exceed the budget; and, from mfem_mesh_assemble_elements_direct, element tables that leave no room for the rows of the
+ * largest control point inside the 96 KB of LDS of a workgroup (a plan whose budget is merely larger than the room is cut again, once). */
+typedef struct {
+  int64_t batches, tasks;              /* tasks = nel * itp */
+  int64_t max_batch_doubles;           /* largest batch, in staged doubles */
+  int64_t max_batch_elements;          /* most geometry evaluations (adjacent elements) of one batch */
+  int64_t geometry_evaluations;        /* in total, per assembly call */
+  int64_t device_bytes;                /* held by the plan */
+  int64_t waves_per_trip;              /* waves of the last launch (0 before the first): more batches than this = the waves loop */
+  int64_t max_control_point_doubles;   /* n_fields^2 * L of the largest control point: the smallest budget */
+  int64_t budget_doubles;              /* the budget the batches were cut for */
+  int64_t waves_per_workgroup, lds_bytes; /* of the last launch */
+  int64_t split_owners;                /* owner elements whose control points went to two or more batches */
+  int64_t max_batch_owners;            /* most owner elements with a control point in one batch */
+} mfem_mesh_direct_stats;
+int mfem_mesh_direct_plan_create(mfem_context ctx, int32_t itp, int64_t nel, int64_t ncp, int32_t n_fields, mfem_csr A,
+                                 const int64_t* adj_ptr, const int32_t* adj, const int32_t* controlpoint_IDs, int32_t index_base,
+                                 const uint16_t* ranks, uint64_t* plan /* [host] out: the opaque handle, 0 = none */);
+int mfem_mesh_direct_plan_destroy(uint64_t plan);
+int mfem_mesh_direct_plan_stats(uint64_t plan, mfem_mesh_direct_stats* out /* [host] */);
+/* Arguments of mfem_mesh_assemble_elements_rows with the plan in place of (adj_ptr, adj, ranks).  overwrite != 0: every row of the pattern is SET
+ * (zero where no term of this call contributes), K_val need not be initialised; 0: the rows are added to K_val. */
+int mfem_mesh_assemble_elements_direct(mfem_context ctx, int32_t dim, int32_t itg, int32_t itp, int64_t nel, int64_t ncp,
+                                       const double* ref_itp_vals, const double* itg_weight, const double* coords,
+                                       const int32_t* controlpoint_IDs, int32_t index_base, int32_t n_terms,
+                                       const mfem_const_term* terms, int32_t n_fields, mfem_csr A, uint64_t plan,
+                                       double* K_val, int32_t overwrite);
 /* The same on boundary facets (element_ID, element_eindex as in mfem_update_basic_boundary): the basis of ALL nodes of the
  * host element evaluated on the face (05_CodeGenerator.jl:175-189), weight = w_q * surface det. */
 int mfem_mesh_assemble_facets(mfem_context ctx, int32_t dim, int32_t itg_b, int32_t itp, int32_t n_face_ids, int64_t n_facets,

@@ -114,6 +114,13 @@ long long mfem_debug_graph_launch_count(void);
 /* ^ key "hex27": mfem_debug_set("hex27", a, b) with (int two_pass) = (a[, b]) */
 /* number of mfem_mesh_assemble_elements_rows calls that ran the row-owner form (process-wide) */
 int64_t mfem_debug_mesh_rows_count(void);
+/* number of mfem_mesh_assemble_elements_direct calls that launched the direct row assembly (process-wide) */
+int64_t mfem_debug_mesh_direct_count(void);
+/* bytes of the context's workspace (grown on demand, never shrunk): what the scratch-taking entry points have reserved so far */
+int64_t mfem_debug_ws_bytes(mfem_context ctx);
+/* Staged rows per wave of the direct row assembly, in BYTES (0 = the default, 16 KB; capped at the 96 KB of a workgroup): read when a plan is created
+ * (mfem_mesh_direct_plan_create).  Tests and A/B runs: the result is the same bit for bit under every budget. */
+/* ^ key "mesh_direct_budget": mfem_debug_set("mesh_direct_budget", a, b) with (int64_t bytes) = (a[, b]) */
 /* number of mfem_mesh_residual_elements / _facets calls that launched the fused residual (process-wide) */
 int64_t mfem_debug_mesh_residual_count(void);
 /* number of mfem_mesh_var_* / mfem_mesh_res_* / mfem_mesh_kval_* calls that took a table-free launch (process-wide) */

@@ -433,6 +433,62 @@ function row_ranks!(ranks::ROCArray{UInt16}, itp, nel, ncp, n_fields, A::CSRPatt
     return ranks
 end
 
+# ---- the direct form of assemble_const_terms!: the same rows in the same summation order, no element-matrix scratch ----------------
+struct MeshDirectStats                    # == mfem_mesh_direct_stats
+    batches::Int64
+    tasks::Int64
+    max_batch_doubles::Int64
+    max_batch_elements::Int64
+    geometry_evaluations::Int64
+    device_bytes::Int64
+    waves_per_trip::Int64
+    max_control_point_doubles::Int64
+    budget_doubles::Int64
+    waves_per_workgroup::Int64
+    lds_bytes::Int64
+    split_owners::Int64
+    max_batch_owners::Int64
+end
+
+mutable struct MeshDirectPlan
+    h::UInt64
+end
+
+"The one-off inspector per pattern (`ranks` from `row_ranks!`; keep `ranks` and `A` alive with the plan).  `nothing` on MFEM_ERR_UNSUPPORTED."
+function mesh_direct_plan(itp, nel, ncp, n_fields, A::CSRPattern, adj_ptr, adj, controlpoint_IDs, ranks)
+    h = Ref{UInt64}(0)
+    rc = ccall((:mfem_mesh_direct_plan_create, lib), Cint,
+               (Ptr{Cvoid}, Int32, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{Cvoid}, Ref{UInt64}),
+               ctx(), itp, nel, ncp, n_fields, A.h, dptr(adj_ptr), dptr(adj), dptr(controlpoint_IDs), 1, dptr(ranks), h)
+    rc == -3 && return nothing
+    check(rc)
+    plan = MeshDirectPlan(h[])
+    finalizer(p -> (ccall((:mfem_mesh_direct_plan_destroy, lib), Cint, (UInt64,), p.h); p.h = 0), plan)
+    return plan
+end
+
+function mesh_direct_stats(plan::MeshDirectPlan)
+    st = Ref{MeshDirectStats}()
+    check(ccall((:mfem_mesh_direct_plan_stats, lib), Cint, (UInt64, Ref{MeshDirectStats}), plan.h, st))
+    return st[]
+end
+
+"Returns false (nothing written) on MFEM_ERR_UNSUPPORTED: call `assemble_const_terms!` then."
+function assemble_const_terms_direct!(K_linear, dim, itg, itp, nel, ncp, ref_itp_vals, itg_weight, coords, controlpoint_IDs,
+                                      terms::Vector{ConstTerm}, n_fields, A::CSRPattern, plan::MeshDirectPlan; overwrite::Bool = false)
+    sort!(terms, by = t -> t.block)
+    rc = ccall((:mfem_mesh_assemble_elements_direct, lib), Cint,
+               (Ptr{Cvoid}, Int32, Int32, Int32, Int64, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Int32,
+                Ptr{ConstTerm}, Int32, Ptr{Cvoid}, UInt64, Ptr{Cvoid}, Int32),
+               ctx(), dim, itg, itp, nel, ncp, dptr(ref_itp_vals), dptr(itg_weight), dptr(coords), dptr(controlpoint_IDs), 1,
+               length(terms), terms, n_fields, A.h, plan.h, dptr(K_linear), overwrite ? 1 : 0)
+    rc == -3 && return false
+    check(rc)
+    return true
+end
+mesh_direct_count() = ccall((:mfem_debug_mesh_direct_count, lib), Int64, ())
+ws_bytes() = ccall((:mfem_debug_ws_bytes, lib), Int64, (Ptr{Cvoid},), ctx())
+
 # ---- S3 on unstructured meshes without update_BasicElements tables (mfem_mesh_var_* / _res_* / _kval_*) ---------------------------
 # The batch operators with geometry on the fly.  ONE difference to var_batch! / res_batch! / kval_batch!: `vals` is the coefficient alone
 # (`@. expr * K_params`, WITHOUT `* w`): the kernels multiply by w_q det_q.  `ids`: the item of every work unit (1-based) or nothing.

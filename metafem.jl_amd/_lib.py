@@ -94,6 +94,12 @@ class ConstTerm(C.Structure):
 MAX_BATCH_TERMS = 48
 
 
+class MeshDirectStats(C.Structure):
+    _fields_ = [(n, c_int64) for n in ("batches", "tasks", "max_batch_doubles", "max_batch_elements", "geometry_evaluations", "device_bytes",
+                                       "waves_per_trip", "max_control_point_doubles", "budget_doubles", "waves_per_workgroup", "lds_bytes",
+                                       "split_owners", "max_batch_owners")]
+
+
 class ResSymbol(C.Structure):
     _fields_ = [("word", c_int32), ("reserved", c_int32), ("shift", c_int64), ("x", C.c_void_p)]
 
@@ -207,6 +213,13 @@ SIGNATURES = {
                                                  C.POINTER(ConstTerm), c_int32, P, P, P, P, P]),
     "mfem_mesh_assemble_elements_rows_set": (c_int, [P, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, c_int32, c_int32,
                                                  C.POINTER(ConstTerm), c_int32, P, P, P, P, P]),
+    "mfem_mesh_direct_plan_create": (c_int, [P, c_int32, c_int64, c_int64, c_int32, P, P, P, P, c_int32, P, C.POINTER(c_uint64)]),
+    "mfem_mesh_direct_plan_destroy": (c_int, [c_uint64]),
+    "mfem_mesh_direct_plan_stats": (c_int, [c_uint64, C.POINTER(MeshDirectStats)]),
+    "mfem_mesh_assemble_elements_direct": (c_int, [P, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, c_int32, c_int32,
+                                                   C.POINTER(ConstTerm), c_int32, P, c_uint64, P, c_int32]),
+    "mfem_debug_mesh_direct_count": (c_int64, []),
+    "mfem_debug_ws_bytes": (c_int64, [P]),
     "mfem_mesh_row_ranks": (c_int, [P, c_int32, c_int64, c_int64, c_int32, P, P, P, P, c_int32, P]),
     "mfem_mesh_assemble_facets": (c_int, [P, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, P, P, P, c_int32,
                                           c_int32, C.POINTER(ConstTerm), P, c_int64, P, P, c_int64, c_int32, C.POINTER(c_int64)]),

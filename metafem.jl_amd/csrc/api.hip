@@ -227,6 +227,7 @@ static int ws_free(void* raw) {
   return MFEM_OK;
 }
 int mfem_ws_release(void* raw) { return ws_free(raw); }
+extern "C" int64_t mfem_debug_ws_bytes(mfem_context ctx) { return ctx ? (int64_t)ctx->ws_bytes : 0; }
 extern "C" unsigned long long mfem_debug_ws_address(mfem_context ctx) { return ctx ? (unsigned long long)(uintptr_t)ctx->ws : 0ull; }
 // Next candidate for the workspace (same size, same placement rule).  First call (no alternative held): the current one moves to ws_alt*.  Later
 // calls: the current one is freed (the alternative stays) -- at most two are alive.  ws_try counts the candidates allocated after the first; it is
@@ -339,6 +340,7 @@ int mfem_debug_set_bsell(int);
 }
 extern int g_mesh_gather_rows, g_mesh_abl, g_mesh_stage_min_itp, g_mesh_term_matrix;  // assemble_mesh.hip
 extern int g_op_wave_forms, g_op_wave_min_itp;  // ops.hip
+extern int64_t g_mesh_direct_budget;  // mesh_direct.hip
 extern "C" int mfem_debug_set(const char* key, int64_t a, int64_t b) try {
   MFEM_REQUIRE(key, "null key");
   const std::string k(key);
@@ -368,6 +370,7 @@ extern "C" int mfem_debug_set(const char* key, int64_t a, int64_t b) try {
   if (k == "op_wave_forms") { g_op_wave_forms = (int)a; g_op_wave_min_itp = b > 0 ? (int)b : 10; return MFEM_OK; }
   if (k == "mesh_stage_min_itp") { g_mesh_stage_min_itp = a > 0 ? (int)a : 16; return MFEM_OK; }
   if (k == "mesh_term_matrix") { g_mesh_term_matrix = (int)a; return MFEM_OK; }
+  if (k == "mesh_direct_budget") { g_mesh_direct_budget = a > 0 ? a : 0; return MFEM_OK; }
   if (k == "mesh_abl") { g_mesh_abl = (int)a; return MFEM_OK; }
   if (k == "recheck_scale_ppm") return mfem_debug_set_recheck_scale((double)a * 1e-6);
   mfem_set_error("mfem_debug_set: unknown key '%s'", key);

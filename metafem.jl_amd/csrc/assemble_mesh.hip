@@ -16,13 +16,6 @@
 //      plain read-modify-write inside a colour (no two elements of a colour share a control point), FP64 atomics otherwise.
 #include "mesh_geometry.h"
 
-#define MA_MAX_TERMS 48
-struct ConstTerms {
-  int n;
-  int32_t ds[MA_MAX_TERMS], bs[MA_MAX_TERMS], block[MA_MAX_TERMS];
-  double coef[MA_MAX_TERMS];
-};
-
 // The terms as one dense coefficient row per sparse block (run of the term list): block value = sum_c c[k][c] * M[c], M = the NS x NS products of a node
 // pair.  Built on the host per launch; read with uniform indices (scalar loads from the kernel arguments, no branch per term).
 #define MA_MAX_RUNS 16
@@ -441,7 +434,7 @@ static int ma_launch(mfem_context_s* ctx, int dim, const MeshItems& V, const Con
   return MFEM_OK;
 }
 
-static int ma_terms(int32_t n_terms, const mfem_const_term* terms, int dim, ConstTerms* out) {
+int ma_terms(int32_t n_terms, const mfem_const_term* terms, int dim, ConstTerms* out) {
   MFEM_REQUIRE(n_terms > 0 && n_terms <= MA_MAX_TERMS && terms, "n_terms must be 1..48");
   out->n = n_terms;
   for (int i = 0; i < n_terms; ++i) {

@@ -25,6 +25,15 @@ struct MeshItems {
   int base;
 };
 
+// The constant-coefficient terms of one launch (assemble_mesh.hip, mesh_direct.hip), sorted by sparse block; ma_terms checks and copies the caller's list.
+#define MA_MAX_TERMS 48
+struct ConstTerms {
+  int n;
+  int32_t ds[MA_MAX_TERMS], bs[MA_MAX_TERMS], block[MA_MAX_TERMS];
+  double coef[MA_MAX_TERMS];
+};
+int ma_terms(int32_t n_terms, const mfem_const_term* terms, int dim, ConstTerms* out);
+
 template <int DIM>
 __device__ __forceinline__ double ma_inv(const double (&J)[3][3], double (&I)[3][3]) {
   if (DIM == 2) {

@@ -117,6 +117,25 @@ class _Group:
         return 0 if self._tables is None else sum(t.numel() * t.element_size() for t in self._tables if t is not None)
 
 
+class _DirectPlan:
+    """Handle of mfem_mesh_direct_plan_create; closed before its context (Context._children)."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self._h = ctx, handle
+        ctx._children.add(self)
+
+    def close(self):
+        if self._h:
+            lib.mfem_mesh_direct_plan_destroy(self._h)
+            self._h = C.c_uint64()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class GenericDomain:
     """FEM_Domain with one workpiece + GlobalField; static (max_time_level = 0) or generalised-alpha transient."""
 
@@ -124,7 +143,7 @@ class GenericDomain:
                  boundaries: Sequence[Tuple[np.ndarray, np.ndarray, WeakForm]],
                  element_colours: Optional[np.ndarray] = None, max_time_level: int = 0, dissipative: bool = True,
                  batched: bool = True, fused: bool = True, row_owner: bool = True, fused_residual: bool = False,
-                 table_free: bool = False):
+                 table_free: bool = False, direct_rows: bool = False):
         """coords [ncp, dim]; cp_ids [itp, nel] 0-based (controlpoint_IDs in basis order); boundaries =
         [(element_ID[nf], element_eindex[nf] 0-based local face ids, WeakForm)].  element_colours (optional):
         a colour per element such that same-colour elements share no control point -> atomics-free scatter with a fixed
@@ -149,6 +168,12 @@ class GenericDomain:
         # (csrc/mesh_ops.hip: the S3 operators with geometry on the fly); no group builds its tables (table_bytes stays 0) unless an entry
         # point answers MFEM_ERR_UNSUPPORTED, after which that group alone takes the operator path
         self.table_free = table_free
+        # direct_rows = True: where the fused element assembly would take its row-owner form, it takes the direct form instead
+        # (mfem_mesh_assemble_elements_direct, csrc/mesh_direct.hip: the same rows in the same summation order, computed batch by batch from the
+        # coordinates with NO element-matrix scratch); the plan is built on first use; on MFEM_ERR_UNSUPPORTED the two-pass form takes over for
+        # this domain.  Facet groups and variable-coefficient terms are unchanged.
+        self.direct_rows = direct_rows
+        self._direct_plan = None
         if table_free:
             if not batched:
                 raise ValueError("table_free=True needs batched=True: the single-term seam (mfem_op_var / _res / _kval) reads the stored tables")
@@ -486,11 +511,35 @@ class GenericDomain:
             rc = lib.mfem_mesh_row_ranks(self.ctx._h, self.itp, self.nel, self.ncp, self.n_fields, self.A._h, self._adj_ptr.data_ptr(),
                                          self._adj.data_ptr(), self.cp.data_ptr(), 1, ranks.data_ptr())
             if rc == -3:  # MFEM_ERR_UNSUPPORTED: an element lists a control point twice -> the scatter form from now on
-                self.row_owner = False
+                self.row_owner = self.direct_rows = False  # (the direct form adds through the same ranks)
                 return None
             check(rc)
             self._ranks = ranks
         return self._ranks
+
+    def _direct(self):
+        """The plan of the direct row assembly (mfem_mesh_direct_plan_create), built on first use; None once the form has been refused."""
+        if self._direct_plan is None and self.direct_rows:
+            if self.nel == 0 or self._row_ranks() is None:
+                self.direct_rows = False
+                return None
+            h = C.c_uint64()
+            rc = lib.mfem_mesh_direct_plan_create(self.ctx._h, self.itp, self.nel, self.ncp, self.n_fields, self.A._h, self._adj_ptr.data_ptr(),
+                                                  self._adj.data_ptr(), self.cp.data_ptr(), 1, self._ranks.data_ptr(), C.byref(h))
+            if rc == -3:  # MFEM_ERR_UNSUPPORTED: the two-pass form from now on
+                self.direct_rows = False
+                return None
+            check(rc)
+            self._direct_plan = _DirectPlan(self.ctx, h)
+        return self._direct_plan if self.direct_rows else None
+
+    def direct_stats(self) -> Optional[dict]:
+        """mfem_mesh_direct_plan_stats of the plan in use (None without one)."""
+        if self._direct_plan is None:
+            return None
+        st = _lib.MeshDirectStats()
+        check(lib.mfem_mesh_direct_plan_stats(self._direct_plan._h, C.byref(st)))
+        return {n: int(getattr(st, n)) for n, _ in st._fields_}
 
     def _assemble_const(self, g: _Group, cterms, K: torch.Tensor):
         """cterms: [(GradTerm, coefficient)] -> one fused launch per colour (mfem_mesh_assemble_elements / _facets)."""
@@ -505,6 +554,19 @@ class GenericDomain:
                                                                  c * self.K_params[t.td_order]) for t, c in chunk])
             if g.facet_el is None and self.row_owner and self._row_ranks() is not None:
                 fresh = getattr(self, "_K_fresh", False) and K is self.K_linear and self.nel > 0
+                plan = self._direct()
+                if plan is not None:
+                    rc = lib.mfem_mesh_assemble_elements_direct(self.ctx._h, self.dim, self.space.itg, self.itp, self.nel, self.ncp,
+                                                                self._ref.data_ptr(), self._itgw.data_ptr(), self.coords.data_ptr(),
+                                                                self.cp.data_ptr(), 1, len(chunk), arr, self.n_fields, self.A._h, plan._h,
+                                                                K.data_ptr(), 1 if fresh else 0)
+                    if rc == 0:
+                        if fresh:
+                            self._K_fresh = False
+                        continue
+                    if rc != -3:
+                        check(rc)
+                    self.direct_rows = False  # MFEM_ERR_UNSUPPORTED (the element's tables leave no LDS for the rows): the two-pass form for this domain
                 fn = lib.mfem_mesh_assemble_elements_rows_set if fresh else lib.mfem_mesh_assemble_elements_rows
                 rc = fn(self.ctx._h, self.dim, self.space.itg, self.itp, self.nel, self.ncp,
                                                           self._ref.data_ptr(), self._itgw.data_ptr(), self.coords.data_ptr(),
