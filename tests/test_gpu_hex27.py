@@ -242,6 +242,52 @@ def test_hex27_per_element_choice_on_mixed_meshes(mf, percent):
     assert float((Ka - Kb).abs().max()) == 0.0
 
 
+@pytest.mark.parametrize("n,slab", [((3, 3, 3), None), ((4, 3, 3), (4, 9))], ids=["brick", "upper_half_slab"])
+def test_hex27_mixed_path_on_a_fresh_workspace(mf, n, slab):
+    """The per-element choice on a context of its own, whose workspace is empty: the count of non-affine elements reserves G0 and the two maps, the stored
+    Ke of the ONE distorted element does not fit behind them, so the workspace grows -- and moves -- between the count and pass 1, and the tables are
+    made again in the new place (in the other tests an earlier, larger assembly on the shared context has usually left room).  The first matrix equals a
+    second assembly on the same context (no move) bitwise and the oracle's K_linear to 1e-12; also on the upper half of a brick as a slab."""
+    import torch
+    from metafem_jl_amd import _lib
+    from oracle import fem, mesh as om, problems, reference_element as re_
+
+    x = (1.0, 1.5, 0.75)
+    disc = re_.initialize_classical_element(3, "CUBE", 2, 1, 5)
+    msh = om.lattice_mesh(x, n, disc)
+    centre = _centre_nodes(n).reshape(n)[n[0] - 2, 1, 1]
+    msh.coords[centre] += 0.03 * np.array([1.0, -0.5, 0.7]) * np.array(x) / np.array(n)
+    od = fem.FEMDomain(msh, disc, 1, problems.thermal_domain(3, K_COND), [])
+    od.controlpoints["s"] = np.zeros(msh.ncp)
+    od.update_time()
+    od.K_linear_func()
+    m0, pl = 2 * n[0] + 1, (2 * n[1] + 1) * (2 * n[2] + 1)
+    lo, hi = slab or (0, m0)
+    lib = _lib.lib
+    ctx = mf.Context()
+    try:
+        brick = mf.make_Brick(x, n, 2, 5, ctx=ctx)
+        if slab:
+            brick.set_slab(lo, hi)
+        clo, chi = (max(lo - 2, 0), min(hi + 2, m0)) if slab else (0, m0)
+        for d in range(3):
+            brick.coords_view(d).copy_(torch.tensor(msh.coords[clo * pl:chi * pl, d], device="cuda"))
+        A = brick.pattern(1)
+        ws0, mixed0 = lib.mfem_debug_ws_bytes(ctx._h), lib.mfem_debug_hex27_mixed_count()
+        K = brick.assemble_thermal(A, K_COND, 0.0, TENV, 0)
+        ws1 = lib.mfem_debug_ws_bytes(ctx._h)
+        print(f"workspace of the fresh context: {ws0} -> {ws1} bytes")
+        assert ws1 > ws0
+        assert lib.mfem_debug_hex27_mixed_count() == mixed0 + 1
+        Kagain = brick.assemble_thermal(A, K_COND, 0.0, TENV, 0)
+        assert lib.mfem_debug_ws_bytes(ctx._h) == ws1 and lib.mfem_debug_hex27_mixed_count() == mixed0 + 2
+        assert torch.equal(K, Kagain)
+        rp = od.pattern.rowptr
+        assert np.abs(K.cpu().numpy() - od.K_linear[rp[lo * pl]:rp[hi * pl]]).max() <= 1e-12 * np.abs(od.K_linear).max()
+    finally:
+        ctx.close()
+
+
 def test_hex27_assembly_time_is_monotone_in_the_distorted_fraction(mf):
     """... and costs what its parts cost: at 48^3 elements the assembly with 0 / 1 / 25 / 50 % distorted elements takes increasing time, 1 % within 1.6x
     of the all-affine mesh allowing for timing noise (measured 1.11x; round 4: 2.6x -- the whole mesh took the two-pass path), and never more than the two-pass path forced on the same mesh."""

@@ -4,7 +4,9 @@ edge-block bookkeeping of the wave-private symmetric sweep, replayed on small la
 (every stencil pair listed exactly once: a product through the tables against the entry-by-entry product); the host decisions of the solve
 driver, of the CSR SpMV (which kernel, which tile, which inspections) of the sliced solver layout (csrc/sell_decide.h: which form, which
 keys, which padding, which instantiation) and of the symmetric lattice tiles (csrc/lat_decide.h: knob words, eligibility, the lattice of row 0,
-geometry and sizes, the split of a slab's launch, the gather grid, the symmetry gate), branch by branch."""
+geometry and sizes, the split of a slab's launch, the gather grid, the symmetry gate), branch by branch; the host decisions of the hex-27
+thermal assembly (csrc/hex27_decide.h: knob word, path choice, workspace, ring, grids, face schedule, LDS size) against the expressions of the
+driver they were cut out of, their own properties, and the macros the kernel lays its LDS block out with."""
 import os
 import subprocess
 
@@ -14,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("name", ["host_check_hex8", "host_check_symp", "host_check_lat", "host_check_solve", "host_check_csr", "host_check_sell",
-                                  "host_check_lat_decide"])
+                                  "host_check_lat_decide", "host_check_hex27"])
 def test_host_check(name, tmp_path):
     exe = str(tmp_path / name)
     subprocess.run(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "metafem.jl_amd", "csrc"),
