@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MFEM_ABI_VERSION 5
+#define MFEM_ABI_VERSION 6
 
 typedef enum {
   MFEM_OK = 0,
@@ -670,6 +670,52 @@ int mfem_mesh_kval_facets(mfem_context ctx, int32_t dim, int32_t itg_b, int32_t 
                           const int32_t* element_eindex, int32_t index_base, int32_t n_terms, const mfem_kval_term* terms,
                           const double* vals, const int32_t* sparse_IDs_by_el, int64_t slot_block_stride, double* K_val,
                           const int32_t* facetIDs, int64_t n_items, int32_t n_colours, const int64_t* colour_offsets);
+
+/* ---- matrix-free operator on unstructured meshes (constant-coefficient terms; new) --------------------------------------------------
+ * What caps the mesh on the assembled path is the matrix and what exists only to build or hold it (values, columns, the solver layout's copy,
+ * sparse_IDs_by_el, row ranks).  For weak forms whose linear gradients have constant coefficients -- on facets: constant plus linear in the
+ * components of the outward normal -- K x is the contraction the fused residual evaluates, so a solve needs the mesh, its vectors and one
+ * element-vector scratch.  The handle (an opaque 64-bit value, 0 = none) stores the mesh and up to 8 parts: part 0 the elements, then one
+ * per facet group in the order they were added.  All arrays are caller-owned device arrays and must outlive the handle; inputs have the
+ * meaning they have in mfem_mesh_residual_elements / _facets (adj_ptr / adj of a facet part list (facet * itp + local node of the host element)).
+ *   K = sum over parts, items, Gauss points and terms of (coef + sum_j normal_coef[j] n_j(q)) w_q det_q D^dual_sd N_a(q) D^base_sd N_b(q)
+ * at row (dual_pos, cp(a)), column (base_pos, cp(b)), block = dual_pos * n_fields + base_pos: to round-off the matrix
+ * mfem_mesh_assemble_elements / _facets (and the Nitsche terms through mfem_mesh_kval_facets) produce for the same terms.
+ * Caps, answered with MFEM_ERR_UNSUPPORTED at the set / add call, before any launch: 48 terms, 8 dual and 8 base fields and 128 distinct
+ * (field, word, normal) monomials per part, one wave's LDS block <= 64 KB, 8 parts, 32 fields.
+ * The product runs two passes (a wave per item -> element vectors in an element-major scratch; a lane per (field, control point) sums its
+ * adjacency entries, part by part in a fixed order): no atomics, bitwise reproducible. */
+typedef struct {
+  int32_t dual_sd, base_sd;   /* 0 = value, 1 + j = d/dx_j */
+  int32_t block;              /* dual_pos * n_fields + base_pos */
+  int32_t reserved;
+  double coef;                /* constant part of the coefficient, K_params factor included */
+  double normal_coef[3];      /* + normal_coef[j] * n_j(q): facets only; must be 0 on elements */
+} mfem_operator_term;
+int mfem_mesh_operator_create(mfem_context ctx, int32_t dim, int32_t itp, int64_t nel, int64_t ncp, int32_t n_fields, const double* coords,
+                              const int32_t* controlpoint_IDs, int32_t index_base, uint64_t* op /* [host] out */);
+int mfem_mesh_operator_set_elements(uint64_t op, int32_t itg, const double* ref_itp_vals, const double* itg_weight, const int64_t* adj_ptr,
+                                    const int32_t* adj, int32_t n_terms, const mfem_operator_term* terms);
+int mfem_mesh_operator_add_facets(uint64_t op, int32_t itg_b, int32_t n_face_ids, int64_t n_facets, const double* bdy_ref_itp_vals,
+                                  const double* bdy_itg_weights, const double* bdy_tangent_directions, const int32_t* element_ID,
+                                  const int32_t* element_eindex, const int64_t* adj_ptr, const int32_t* adj, int32_t n_terms,
+                                  const mfem_operator_term* terms, int32_t* part /* [host] out: the part's number, >= 1 */);
+/* Replaces the terms of a part (0 = the elements): host only, nothing is launched.  How the K_params of a new time step reach the operator. */
+int mfem_mesh_operator_set_terms(uint64_t op, int32_t part, int32_t n_terms, const mfem_operator_term* terms);
+int mfem_mesh_operator_destroy(uint64_t op);
+/* y = alpha K x + beta y (x, y: n_fields * ncp, field-major).  beta == 0 does not read y.  A control point in no adjacency list has an empty row.
+ * The scratch (sum over parts of n_items * itp * dual fields doubles) is taken from the context workspace. */
+int mfem_mesh_operator_apply(mfem_context ctx, uint64_t op, const double* x, double* y, double alpha, double beta);
+/* d[f * ncp + i] = K_(f,i),(f,i), signed (0 on an empty row): per item and local node sum_q w_q det_q sum_{terms on diagonal blocks} coef D^s N_a D^s' N_a,
+ * summed over the adjacency as the product is. */
+int mfem_mesh_operator_diagonal(mfem_context ctx, uint64_t op, double* d);
+/* mfem_solve on the operator: same options and statistics, every product an operator application (spmv_count: the per-method formulas above).  The
+ * workspace holds the vectors and the scratch only: no layout, no copy of a matrix.  Accepts every method but MFEM_SOLVER_LSQR, precond NONE or
+ * JACOBI_RIGHT_DIAG (the diagonal from the kernel above under the guarded rule of mfem_jacobi_by_diagonal: a row without adjacency or with an
+ * exactly zero diagonal keeps 1; the solvers on A D^-1 read x_j / d_j while the product gathers x), left_precond NONE; cg_variant 4 runs as 3.
+ * MFEM_ERR_UNSUPPORTED, nothing launched and x_out untouched: lsqr!, JACOBI_RIGHT_COLNORM, any left preconditioner (they need columns or rows of K
+ * or a product with A').  MFEM_ERR_INVALID: scale_in_place, an attached communicator (one rank only), null arguments. */
+int mfem_solve_operator(mfem_context ctx, uint64_t op, const double* b, double* x_out, const mfem_solve_options* opts, mfem_solve_stats* stats);
 
 /* ---- multi-GPU (new; the reference is single-GPU, F6) ------------------------------------ */
 /* 128-byte RCCL unique id, created on rank 0 and shipped to the other ranks by the host

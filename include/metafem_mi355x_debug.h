@@ -124,6 +124,9 @@ int64_t mfem_debug_ws_bytes(mfem_context ctx);
 /* ^ key "mesh_direct_budget": mfem_debug_set("mesh_direct_budget", a, b) with (int64_t bytes) = (a[, b]) */
 /* number of mfem_mesh_residual_elements / _facets calls that launched the fused residual (process-wide) */
 int64_t mfem_debug_mesh_residual_count(void);
+/* number of matrix-free operator applications the host launched (process-wide): mfem_mesh_operator_apply and every product of mfem_solve_operator
+ * (a product inside a captured solver cycle counts once, when the cycle is captured) */
+int64_t mfem_debug_mesh_operator_count(void);
 /* number of mfem_mesh_var_* / mfem_mesh_res_* / mfem_mesh_kval_* calls that took a table-free launch (process-wide) */
 int64_t mfem_debug_mesh_ops_count(void);
 /* variants of the fused mesh assembly launched so far (process-wide), one bit per (dim, mode, kind): bit ((dim - 2) * 3 + mode) * 9 + kind, mode 0

@@ -21,7 +21,7 @@ import LinearAlgebra
 
 # ---- library handle and error convention ---------------------------------------------------------------------------------
 const lib = get(ENV, "METAFEM_MI355X_LIB", joinpath(@__DIR__, "..", "metafem.jl_amd", "libmetafem_mi355x.so"))
-const ABI_VERSION = 5    # == MFEM_ABI_VERSION
+const ABI_VERSION = 6    # == MFEM_ABI_VERSION
 
 struct MFEMError <: Exception
     rc::Cint
@@ -570,6 +570,91 @@ end
 
 "Calls that took a table-free launch so far (process-wide)."
 mesh_ops_count() = ccall((:mfem_debug_mesh_ops_count, lib), Int64, ())
+
+# ---- matrix-free operator on unstructured meshes (mfem_mesh_operator_*, mfem_solve_operator) --------------------------------------
+# For weak forms whose linear gradients have constant coefficients (on facets: constant + linear in the normal components): no K_J_ptr / K_J /
+# K_total, no sparse_IDs_by_el -- the solve needs the mesh, its vectors and one element-vector scratch.  All arrays are borrowed: keep them alive.
+struct OperatorTerm                       # == mfem_operator_term
+    dual_sd::Int32
+    base_sd::Int32
+    block::Int32
+    reserved::Int32
+    coef::Float64
+    normal_coef::NTuple{3, Float64}
+end
+OperatorTerm(dual_sd, base_sd, block, coef; normal = (0.0, 0.0, 0.0)) = OperatorTerm(dual_sd, base_sd, block, 0, coef, normal)
+
+mutable struct MeshOperator
+    h::UInt64
+    n::Int64
+    keep::Vector{Any}
+end
+
+function mesh_operator(dim, itp, nel, ncp, n_fields, coords, controlpoint_IDs)
+    h = Ref{UInt64}(0)
+    check(ccall((:mfem_mesh_operator_create, lib), Cint,
+                (Ptr{Cvoid}, Int32, Int32, Int64, Int64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ref{UInt64}),
+                ctx(), dim, itp, nel, ncp, n_fields, dptr(coords), dptr(controlpoint_IDs), 1, h))
+    op = MeshOperator(h[], n_fields * ncp, Any[coords, controlpoint_IDs])
+    finalizer(o -> (ccall((:mfem_mesh_operator_destroy, lib), Cint, (UInt64,), o.h); o.h = 0), op)
+    return op
+end
+
+"The element part.  Returns false on MFEM_ERR_UNSUPPORTED (the caps): assemble K then."
+function operator_elements!(op::MeshOperator, itg, ref_itp_vals, itg_weight, adj_ptr, adj, terms::Vector{OperatorTerm})
+    rc = ccall((:mfem_mesh_operator_set_elements, lib), Cint,
+               (UInt64, Int32, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32, Ptr{OperatorTerm}),
+               op.h, itg, dptr(ref_itp_vals), dptr(itg_weight), dptr(adj_ptr), dptr(adj), length(terms), terms)
+    rc == -3 && return false
+    check(rc)
+    append!(op.keep, Any[ref_itp_vals, itg_weight, adj_ptr, adj])
+    return true
+end
+
+"A facet part (one per boundary group; `adj` lists (facet * itp + local node) per control point).  Returns the part's number, or nothing on MFEM_ERR_UNSUPPORTED."
+function operator_facets!(op::MeshOperator, itg_b, n_face_ids, nf, bdy_ref_itp_vals, bdy_itg_weights, bdy_tangent_directions, element_ID,
+                          element_eindex, adj_ptr, adj, terms::Vector{OperatorTerm})
+    part = Ref{Int32}(-1)
+    rc = ccall((:mfem_mesh_operator_add_facets, lib), Cint,
+               (UInt64, Int32, Int32, Int64, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Int32,
+                Ptr{OperatorTerm}, Ref{Int32}),
+               op.h, itg_b, n_face_ids, nf, dptr(bdy_ref_itp_vals), dptr(bdy_itg_weights), dptr(bdy_tangent_directions), dptr(element_ID),
+               dptr(element_eindex), dptr(adj_ptr), dptr(adj), length(terms), terms, part)
+    rc == -3 && return nothing
+    check(rc)
+    append!(op.keep, Any[bdy_ref_itp_vals, bdy_itg_weights, bdy_tangent_directions, element_ID, element_eindex, adj_ptr, adj])
+    return part[]
+end
+
+"Replaces the terms of a part (0 = the elements), host only: what K_linear_func does on this path (coefficient times the step's K_params)."
+operator_terms!(op::MeshOperator, part::Integer, terms::Vector{OperatorTerm}) =
+    check(ccall((:mfem_mesh_operator_set_terms, lib), Cint, (UInt64, Int32, Int32, Ptr{OperatorTerm}), op.h, part, length(terms), terms))
+
+"y = alpha K x + beta y"
+operator_mul!(y, op::MeshOperator, x, alpha = 1.0, beta = 0.0) =
+    check(ccall((:mfem_mesh_operator_apply, lib), Cint, (Ptr{Cvoid}, UInt64, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64),
+                ctx(), op.h, dptr(x), dptr(y), alpha, beta))
+
+function operator_diagonal(op::MeshOperator)
+    d = AMDGPU.zeros(Float64, op.n)
+    check(ccall((:mfem_mesh_operator_diagonal, lib), Cint, (Ptr{Cvoid}, UInt64, Ptr{Cvoid}), ctx(), op.h, dptr(d)))
+    return d
+end
+
+"iterative_Solve! on the operator: every solver but :lsqr!, Pr_func! :Identity or :Pr_Jacobi! (by the diagonal), no Pl_func."
+function iterative_Solve!(op::MeshOperator, residue, converge_tol; Sv_func!::Symbol = :idrs!, Pr_func!::Symbol = :Pr_Jacobi!, max_pass = 4,
+                          maxiter = 2000, s = 0, seed::UInt64 = 0x5EED, checkiter::Integer = 200)
+    x = AMDGPU.zeros(Float64, op.n)
+    l_or_s = Sv_func! == :tfqmr! ? checkiter : s
+    opts = Ref(SolveOptions(method = SOLVER_ID[Sv_func!], precond = PR_ID[Pr_func!], l_or_s = l_or_s, maxiter = maxiter, max_pass = max_pass,
+                            converge_tol = converge_tol, seed = seed))
+    stats = Ref{SolveStats}()
+    check(ccall((:mfem_solve_operator, lib), Cint, (Ptr{Cvoid}, UInt64, Ptr{Cvoid}, Ptr{Cvoid}, Ref{SolveOptions}, Ref{SolveStats}),
+                ctx(), op.h, dptr(residue), dptr(x), opts, stats))
+    println("pass $(stats[].passes) with res = $(stats[].final_res) iter = $(stats[].iterations).")
+    return x
+end
+mesh_operator_count() = ccall((:mfem_debug_mesh_operator_count, lib), Int64, ())
 
 # ---- several GPUs: one Julia process per GPU (MPI.jl), slab decomposition along the first dimension ---------------------------
 "Rank 0 creates the 128-byte RCCL id; the host broadcasts it (MPI.Bcast!)."

@@ -29,7 +29,7 @@ import torch
 from . import _lib
 from ._lib import (ElasticityParams, MetaFEMError, OpLayout, SolveOptions, SolveStats, ThermalParams, check, lib)
 
-__all__ = ["Context", "FEM_SpMat_CSR", "mul_", "tmul_", "dot", "nrm2", "axpby_", "FEM_rand", "normalized_norm",
+__all__ = ["Context", "FEM_SpMat_CSR", "MeshOperator", "mul_", "tmul_", "dot", "nrm2", "axpby_", "FEM_rand", "normalized_norm",
            "iterative_Solve", "Brick", "make_Brick", "ThermalDomain", "MetaFEMError", "SolveStats",
            "cg_", "bicgstabl_GS_", "idrs_", "cgs2_", "gmres_", "cgs_", "tfqmr_", "lsqr_", "FACE_BITS"]
 
@@ -159,8 +159,96 @@ class FEM_SpMat_CSR:
             pass
 
 
-def mul_(b: torch.Tensor, A: FEM_SpMat_CSR, vals: torch.Tensor, x: torch.Tensor, alpha: float = 1.0, beta: float = 0.0):
-    """mul!(b, A, x, alpha, beta): b = alpha*A*x + beta*b (04_GPU_Utils.jl:131)."""
+class MeshOperator:
+    """Matrix-free K of an unstructured mesh (mfem_mesh_operator_*, csrc/mesh_operator.hip): stands where a FEM_SpMat_CSR and its values stand --
+    `mul_(b, A, None, x)` and `iterative_Solve(A, None, residue, ...)` take it -- and holds no matrix: the mesh arrays (borrowed: coords SoA
+    [dim * ncp], controlpoint_IDs (nel, itp) C order), the reference tables and the adjacency of each part, and the terms
+    `(dual_sd, base_sd, block, coef[, (n0, n1, n2)])` of the elements and of every facet group."""
+
+    def __init__(self, ctx: "Context", dim: int, itp: int, nel: int, ncp: int, n_fields: int, coords: torch.Tensor, controlpoint_IDs: torch.Tensor,
+                 index_base: int = 1):
+        self.ctx = ctx
+        _need(coords, torch.float64, "coords", dim * ncp)
+        _need(controlpoint_IDs, torch.int32, "controlpoint_IDs", nel * itp)
+        self._keep = [coords, controlpoint_IDs]  # the library borrows every array
+        self.n_fields, self.ncp = n_fields, ncp
+        self.n = n_fields * ncp
+        self.nnz = 0
+        self.n_parts = 0
+        self._h = C.c_uint64()
+        check(lib.mfem_mesh_operator_create(ctx._h, dim, itp, nel, ncp, n_fields, _ptr(coords), _ptr(controlpoint_IDs), index_base, C.byref(self._h)))
+        ctx._children.add(self)
+
+    @staticmethod
+    def _terms(terms):
+        arr = (_lib.OperatorTerm * max(len(terms), 1))()
+        for i, t in enumerate(terms):
+            nrm = tuple(t[4]) if len(t) > 4 else (0.0, 0.0, 0.0)
+            arr[i] = _lib.OperatorTerm(int(t[0]), int(t[1]), int(t[2]), 0, float(t[3]), (C.c_double * 3)(*[float(v) for v in nrm]))
+        return arr
+
+    def set_elements(self, itg: int, ref_itp_vals: torch.Tensor, itg_weight: torch.Tensor, adj_ptr: torch.Tensor, adj: torch.Tensor, terms) -> int:
+        """rc of mfem_mesh_operator_set_elements (0, or -3 = MFEM_ERR_UNSUPPORTED: beyond the caps; anything else raises)."""
+        rc = lib.mfem_mesh_operator_set_elements(self._h, itg, _ptr(ref_itp_vals), _ptr(itg_weight), _ptr(adj_ptr), _ptr(adj), len(terms),
+                                                 self._terms(terms))
+        if rc != -3:
+            check(rc)
+            self._keep += [ref_itp_vals, itg_weight, adj_ptr, adj]
+            self.n_parts = max(self.n_parts, 1)
+        return rc
+
+    def add_facets(self, itg_b: int, n_face_ids: int, bdy_ref_itp_vals, bdy_itg_weights, bdy_tangent_directions, element_ID, element_eindex, adj_ptr,
+                   adj, terms) -> int:
+        """The part's number (>= 1), or -3 = MFEM_ERR_UNSUPPORTED."""
+        part = C.c_int32(-1)
+        rc = lib.mfem_mesh_operator_add_facets(self._h, itg_b, n_face_ids, element_ID.numel(), _ptr(bdy_ref_itp_vals), _ptr(bdy_itg_weights),
+                                               _ptr(bdy_tangent_directions), _ptr(element_ID), _ptr(element_eindex), _ptr(adj_ptr), _ptr(adj),
+                                               len(terms), self._terms(terms), C.byref(part))
+        if rc == -3:
+            return rc
+        check(rc)
+        self._keep += [bdy_ref_itp_vals, bdy_itg_weights, bdy_tangent_directions, element_ID, element_eindex, adj_ptr, adj]
+        self.n_parts = part.value + 1
+        return part.value
+
+    def set_terms(self, part: int, terms) -> int:
+        """Replaces the terms of a part (host only); rc as set_elements."""
+        rc = lib.mfem_mesh_operator_set_terms(self._h, part, len(terms), self._terms(terms))
+        if rc != -3:
+            check(rc)
+        return rc
+
+    def mul_(self, y: torch.Tensor, x: torch.Tensor, alpha: float = 1.0, beta: float = 0.0) -> torch.Tensor:
+        """y = alpha K x + beta y (beta == 0: y is not read)."""
+        _need(x, torch.float64, "x", self.n)
+        _need(y, torch.float64, "y", self.n)
+        check(lib.mfem_mesh_operator_apply(self.ctx._h, self._h, _ptr(x), _ptr(y), alpha, beta))
+        return y
+
+    def diagonal(self) -> torch.Tensor:
+        """diag K, signed (0 on a row without adjacency)."""
+        d = torch.empty(self.n, dtype=torch.float64, device=f"cuda:{self.ctx.device}")
+        check(lib.mfem_mesh_operator_diagonal(self.ctx._h, self._h, _ptr(d)))
+        return d
+
+    def close(self):
+        if self._h:
+            lib.mfem_mesh_operator_destroy(self._h)
+            self._h = C.c_uint64()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def mul_(b: torch.Tensor, A, vals: Optional[torch.Tensor], x: torch.Tensor, alpha: float = 1.0, beta: float = 0.0):
+    """mul!(b, A, x, alpha, beta): b = alpha*A*x + beta*b (04_GPU_Utils.jl:131).  A MeshOperator takes vals = None."""
+    if isinstance(A, MeshOperator):
+        if vals is not None:
+            raise MetaFEMError("a MeshOperator holds no values: pass vals = None")
+        return A.mul_(b, x, alpha, beta)
     _need(vals, torch.float64, "vals", A.nnz)
     _need(x, torch.float64, "x")
     _need(b, torch.float64, "b", A.n)
@@ -242,7 +330,7 @@ def mat_div_jacobi_(A: FEM_SpMat_CSR, vals: torch.Tensor, d: torch.Tensor) -> to
     return vals
 
 
-def iterative_Solve(A: FEM_SpMat_CSR, K_vals: torch.Tensor, residue: torch.Tensor, converge_tol: float, *,
+def iterative_Solve(A, K_vals: Optional[torch.Tensor], residue: torch.Tensor, converge_tol: float, *,
                     Sv_func: int = idrs_, Pr_func: int = Pr_Jacobi_, Pl_func: int = Identity, max_pass: int = 4,
                     maxiter: int = 2000,
                     s: int = 0, seed: int = 0x5EED, check_every: int = 32, fixed_iterations: bool = False,
@@ -258,9 +346,16 @@ def iterative_Solve(A: FEM_SpMat_CSR, K_vals: torch.Tensor, residue: torch.Tenso
     recurrence carrying the preconditioned residual (one vector stream less per iteration), 4 plain CG on the symmetrically Jacobi-scaled
     matrix (one stream less again; on the mirrored-sweep layout, one rank: the auto choice there, else 3).
 
+    A MeshOperator with K_vals = None solves matrix-free (mfem_solve_operator): every Sv_func but lsqr_, Pr_func Identity or Pr_Jacobi_, Pl_func
+    Identity, no scale_in_place.
+
     Returns (delta_x, stats); delta_x is a NEW device vector like the reference's return value.
     """
-    _need(K_vals, torch.float64, "K_vals", A.nnz)
+    matrix_free = isinstance(A, MeshOperator)
+    if matrix_free and K_vals is not None:
+        raise MetaFEMError("a MeshOperator holds no values: pass K_vals = None")
+    if not matrix_free:
+        _need(K_vals, torch.float64, "K_vals", A.nnz)
     _need(residue, torch.float64, "residue", A.n)
     x = torch.empty(A.n, dtype=torch.float64, device=residue.device)
     if Sv_func == tfqmr_:
@@ -276,7 +371,10 @@ def iterative_Solve(A: FEM_SpMat_CSR, K_vals: torch.Tensor, residue: torch.Tenso
         _need(shadow, torch.float64, "shadow")
         check(lib.mfem_solve_set_shadow(A.ctx._h, _ptr(shadow), shadow.numel() // A.n))
     try:
-        check(lib.mfem_solve(A.ctx._h, A._h, _ptr(K_vals), _ptr(residue), _ptr(x), C.byref(o), C.byref(st)))
+        if matrix_free:
+            check(lib.mfem_solve_operator(A.ctx._h, A._h, _ptr(residue), _ptr(x), C.byref(o), C.byref(st)))
+        else:
+            check(lib.mfem_solve(A.ctx._h, A._h, _ptr(K_vals), _ptr(residue), _ptr(x), C.byref(o), C.byref(st)))
     finally:
         if shadow is not None:
             lib.mfem_solve_set_shadow(A.ctx._h, None, 0)

@@ -112,6 +112,11 @@ class AffineTerm(C.Structure):
 MAX_RES_SYMBOLS, MAX_RES_TERMS, MAX_RES_PAIRS = 16, 48, 8  # MFEM_RES_MAX_*
 
 
+class OperatorTerm(C.Structure):
+    _fields_ = [("dual_sd", c_int32), ("base_sd", c_int32), ("block", c_int32), ("reserved", c_int32), ("coef", c_double),
+                ("normal_coef", c_double * 3)]
+
+
 ALLREDUCE_CB = C.CFUNCTYPE(c_int, c_void_p, C.POINTER(c_double), c_int32)
 EXCHANGE_CB = C.CFUNCTYPE(c_int, c_void_p, C.POINTER(c_double), C.POINTER(c_double), C.POINTER(c_double), C.POINTER(c_double), c_int64)
 
@@ -228,6 +233,16 @@ SIGNATURES = {
     "mfem_mesh_residual_facets": (c_int, [P, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, P, P, P, c_int32,
                                           c_int32, C.POINTER(ResSymbol), c_int32, C.POINTER(AffineTerm), P, P, P]),
     "mfem_debug_mesh_residual_count": (c_int64, []),
+    "mfem_mesh_operator_create": (c_int, [P, c_int32, c_int32, c_int64, c_int64, c_int32, P, P, c_int32, C.POINTER(c_uint64)]),
+    "mfem_mesh_operator_set_elements": (c_int, [c_uint64, c_int32, P, P, P, P, c_int32, C.POINTER(OperatorTerm)]),
+    "mfem_mesh_operator_add_facets": (c_int, [c_uint64, c_int32, c_int32, c_int64, P, P, P, P, P, P, P, c_int32, C.POINTER(OperatorTerm),
+                                              C.POINTER(c_int32)]),
+    "mfem_mesh_operator_set_terms": (c_int, [c_uint64, c_int32, c_int32, C.POINTER(OperatorTerm)]),
+    "mfem_mesh_operator_destroy": (c_int, [c_uint64]),
+    "mfem_mesh_operator_apply": (c_int, [P, c_uint64, P, P, c_double, c_double]),
+    "mfem_mesh_operator_diagonal": (c_int, [P, c_uint64, P]),
+    "mfem_solve_operator": (c_int, [P, c_uint64, P, P, C.POINTER(SolveOptions), C.POINTER(SolveStats)]),
+    "mfem_debug_mesh_operator_count": (c_int64, []),
     "mfem_mesh_var_elements": (c_int, [P, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, c_int32, c_int32,
                                        C.POINTER(VarBatchTerm), P, P, c_int64]),
     "mfem_mesh_var_facets": (c_int, [P, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, P, P, P, c_int32,

@@ -187,6 +187,59 @@ def _check(term, desc: AffineResidual, names, t, dt, shape=(5, 7)) -> bool:
     return bool(((got.to(torch.float64) - ref).abs() <= 1e-13 * (scale + 1e-300)).all())
 
 
+@dataclass
+class OperatorCoefficient:
+    """The coefficient of a linear gradient term the matrix-free operator takes: c0 + sum_j normal[j] n_j."""
+    c0: float
+    normal: Tuple[float, float, float]
+
+
+def operator_coefficient(term, wf, facet: bool, t: float = 0.0, dt: float = 1.0, check: bool = True) -> Optional[OperatorCoefficient]:
+    """The constant (on facets: constant plus normal-linear) description of the coefficient of `term` (a GradTerm of `wf`), or None if fn reads a
+    field or an external, is not linear in the normal components, or -- on elements -- reads a normal at all.  The probes are those of
+    `affine_residual`: only the normals, t and dt exist in the probe environment.  check: compare once with fn on random normals."""
+    comps = {name: comp for name, comp in wf.normals}
+    env = _ProbeEnv()
+    for name, comp in comps.items():
+        env[name] = _Aff({(None, comp): 1.0})
+    env["t"], env["dt"] = float(t), float(dt)
+    try:
+        v = _Aff._lift(term.fn(env))
+    except Exception:
+        return None
+    nrm = [0.0, 0.0, 0.0]
+    for (s, n), c in v.m.items():
+        if s is not None or (n is not None and not 0 <= n < 3):
+            return None
+        if n is not None:
+            nrm[n] += c
+    c0 = float(v.m.get((None, None), 0.0))
+    if not all(math.isfinite(c) for c in [c0] + nrm):
+        return None
+    if not facet and any(c != 0.0 for c in nrm):
+        return None
+    if check:
+        g = torch.Generator().manual_seed(0x0FE2)
+        shape = (5, 7)
+        vals = {name: torch.rand(shape, generator=g, dtype=torch.float64) * 2.0 - 1.0 for name in comps}
+        num: Dict[str, object] = dict(vals)
+        num["t"], num["dt"] = float(t), float(dt)
+        try:
+            got = term.fn(num)
+            if not torch.is_tensor(got):
+                got = torch.full(shape, float(got), dtype=torch.float64)
+        except Exception:
+            return None
+        ref = torch.full(shape, c0, dtype=torch.float64)
+        scale = torch.full(shape, abs(c0), dtype=torch.float64)
+        for name, comp in comps.items():
+            ref = ref + nrm[comp] * vals[name]
+            scale = scale + abs(nrm[comp]) * vals[name].abs()
+        if got.shape != ref.shape or not bool(((got.to(torch.float64) - ref).abs() <= 1e-13 * (scale + 1e-300)).all()):
+            return None
+    return OperatorCoefficient(c0, (nrm[0], nrm[1], nrm[2]))
+
+
 class CapsExceeded(ValueError):
     """The terms of one launch exceed MFEM_RES_MAX_SYMBOLS / _TERMS / _PAIRS: they take the operator path."""
 

@@ -221,6 +221,13 @@ struct mfem_csr_s {
   int64_t rem_last_rows, rem_last_ent;  // what the last ACCEPTED remainder of the last probe held (0: none) -- survives the unbind at the end of a solve (tests, bench.py)
   // transposed pattern for A' x (spmv_t.hip): built by the first mfem_spmv_csr_t or lsqr! solve, dropped by replan / destroy
   struct mfem_tplan_s* tplan;
+  // the internal pattern-less handle (n = n_fields * ncp, nnz = 0) of a matrix-free mesh operator (mesh_operator.hip): op is set while the operator is
+  // bound for a solve -- every product then goes to its launcher --, with the scratch and the column scaling of that solve; op_epoch counts the
+  // operator's term changes (a captured cycle bakes the compiled terms in)
+  struct mfem_mesh_operator_s* op;
+  double* op_scratch;
+  const double* op_dsc;
+  uint64_t op_epoch;
 };
 // The transpose plan of a pattern (spmv_t.hip): AT is an internal CSR handle over the owned transposed arrays (rows = the columns of A,
 // int64 row pointers, 0-based), perm maps its slots to A's slots (int32 below 2^31 entries, int64 above).
@@ -290,7 +297,8 @@ __attribute__((visibility("hidden"))) CsrKnobs mfem_csr_knobs();  // what mfem_d
 // The solver layouts of a pattern (layout.hip): which copy of the values a solve runs on, and its binding and release.  The values are the
 // mode numbers of mfem_csr_solver_layout: the CSR tile kernel on the caller's values (no copy), slot-major copy with explicit columns / with
 // diagonal-slotted regular blocks (spmv_ell.hip, spmv_dia.hip and the sweeps of spmv_sym.hip), row-sorted sliced ELL or its node-blocked form (spmv_sell.hip, spmv_bsell.hip), symmetric lattice tiles (spmv_lat27.hip with spmv_lat27_gather.hip, spmv_lat8.hip)
-enum mfem_layout : int32_t { MFEM_LAYOUT_CSR = 0, MFEM_LAYOUT_ELL = 1, MFEM_LAYOUT_DIA = 2, MFEM_LAYOUT_SELL = 3, MFEM_LAYOUT_LAT27 = 4, MFEM_LAYOUT_LAT8 = 5 };
+enum mfem_layout : int32_t { MFEM_LAYOUT_CSR = 0, MFEM_LAYOUT_ELL = 1, MFEM_LAYOUT_DIA = 2, MFEM_LAYOUT_SELL = 3, MFEM_LAYOUT_LAT27 = 4, MFEM_LAYOUT_LAT8 = 5,
+                             MFEM_LAYOUT_OPERATOR = 6 /* no copy of any values: a bound matrix-free mesh operator (mesh_operator.hip) */ };
 // What a pattern offers a solve: a tile layout (taken if the values pass its symmetry probe) and a row layout, each with the workspace bytes of
 // its copy (MFEM_LAYOUT_CSR, 0: none)
 struct mfem_layout_plan_s {

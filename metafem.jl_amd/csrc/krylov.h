@@ -103,6 +103,8 @@ inline uint64_t mfem_csr_graph_key(uint64_t key, const mfem_csr_s* A) {
   key = mfem_hash(key, A->lat27.dsc); key = mfem_hash(key, A->lat8.dsc);
   // ... and so are the arrays of the skew remainder a tile bind may carry (spmv_rem.hip)
   key = mfem_hash(key, A->rem_active);
+  // a bound matrix-free operator (mesh_operator.hip): its handle's serial is A->serial; the compiled terms, the scratch and the column scaling are kernel arguments
+  key = mfem_hash(key, A->op != nullptr); key = mfem_hash(key, A->op_epoch); key = mfem_hash(key, A->op_scratch); key = mfem_hash(key, A->op_dsc);
   if (A->rem_active) { key = mfem_hash(key, A->rem_nrows); key = mfem_hash(key, A->rem_rows); key = mfem_hash(key, A->rem_col); key = mfem_hash(key, A->rem_val); }
   key = mfem_hash(key, mfem_debug_epoch.load());
   return key;

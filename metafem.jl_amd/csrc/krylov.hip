@@ -15,6 +15,8 @@
 // no-ops; the host polls it every `check_every` iterations.
 #include "krylov.h"
 #include "solve_decide.h"
+#include "mesh_operator.h"
+#include "mesh_operator_decide.h"
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
 
@@ -291,6 +293,7 @@ struct SolveRun {
   const double* vals_src;  // what the right scaling is computed from
   double* lay;             // the layout copy
   bool tiles_bound, rows_bound, cg_scaled;
+  mfem_mesh_operator_s* op = nullptr;  // mfem_solve_operator: A is the operator's pattern-less handle, vals is null
 };
 
 // 1. the options; the method (with a communicator: the one all-reduce of n, every rank must take the same decisions)
@@ -300,7 +303,7 @@ static int choose_method(SolveRun& R) {
   const mfem_solve_options* o = R.o;
   double *vals = R.vals, *x_out = R.x_out;
   const double* b = R.b;
-  MFEM_REQUIRE(A->n == 0 || (vals && b && x_out), "null array");
+  MFEM_REQUIRE(A->n == 0 || ((vals || R.op) && b && x_out), "null array");
   MFEM_REQUIRE(o->maxiter >= 0 && o->max_pass >= 1, "maxiter >= 0 and max_pass >= 1 required");
   MFEM_REQUIRE(o->method >= MFEM_SOLVER_CG && o->method <= MFEM_SOLVER_LSQR, "unknown method");
   MFEM_REQUIRE(o->precond >= MFEM_PRECOND_NONE && o->precond <= MFEM_PRECOND_JACOBI_RIGHT_COLNORM, "unknown precond");
@@ -864,15 +867,14 @@ static int solve_inner(mfem_context ctx, mfem_csr A, double* vals, const double*
   return rc;
 }
 
-extern "C" int mfem_solve(mfem_context ctx, mfem_csr A, double* vals, const double* b, double* x_out,
-                          const mfem_solve_options* o, mfem_solve_stats* stats) try {
-  MFEM_REQUIRE(ctx && A && o, "null argument");
-  // Cycle graphs: not with a communicator (RCCL calls inside the cycle), not while per-launch SpMV timing is on (event
-  // records inside the cycle), not in benchmark mode on large systems.  The legacy null stream cannot be captured: the
-  // solve then runs on a private stream, ordered after / before the caller's stream work through events.
-  const bool graphs = g_graphs && (!ctx->comm || (graph_comm_wanted() && !mfem_graph_comm_broken && mfem_comm_capturable(ctx))) && !ctx->prof_on && A->n > 0 &&
-                      A->n <= g_graph_max_n;
-  if (!graphs) return solve_inner(ctx, A, vals, b, x_out, o, stats);
+// Cycle graphs around a solve of n rows: not with a communicator (RCCL calls inside the cycle), not while per-launch SpMV timing is on (event
+// records inside the cycle), not in benchmark mode on large systems.  The legacy null stream cannot be captured: the
+// solve then runs on a private stream, ordered after / before the caller's stream work through events.
+template <class Inner>
+static int solve_with_graphs(mfem_context_s* ctx, int64_t n, Inner inner) {
+  const bool graphs = g_graphs && (!ctx->comm || (graph_comm_wanted() && !mfem_graph_comm_broken && mfem_comm_capturable(ctx))) && !ctx->prof_on && n > 0 &&
+                      n <= g_graph_max_n;
+  if (!graphs) return inner();
   hipStream_t user = ctx->stream;
   if (user == nullptr) {
     if (!ctx->graph_stream) {
@@ -883,7 +885,7 @@ extern "C" int mfem_solve(mfem_context ctx, mfem_csr A, double* vals, const doub
     MFEM_CHECK_HIP(hipStreamWaitEvent(ctx->graph_stream, ctx->graph_ev, 0));
     ctx->stream = ctx->graph_stream;
   }
-  // whatever way solve_inner is left -- a status or a C++ exception on its way to the handler below (std::bad_alloc of a lazily made plan) -- the context
+  // whatever way the solve is left -- a status or a C++ exception on its way to the entry point's handler (std::bad_alloc of a lazily made plan) -- the context
   // goes back to the caller's stream and out of capture mode: the header promises that handles stay usable after a non-zero return
   struct Restore {
     mfem_context_s* ctx;
@@ -898,5 +900,96 @@ extern "C" int mfem_solve(mfem_context ctx, mfem_csr A, double* vals, const doub
     }
   } restore{ctx, user};
   ctx->graph_active = 1;
-  return solve_inner(ctx, A, vals, b, x_out, o, stats);
+  return inner();
+}
+
+extern "C" int mfem_solve(mfem_context ctx, mfem_csr A, double* vals, const double* b, double* x_out,
+                          const mfem_solve_options* o, mfem_solve_stats* stats) try {
+  MFEM_REQUIRE(ctx && A && o, "null argument");
+  return solve_with_graphs(ctx, A->n, [&]() { return solve_inner(ctx, A, vals, b, x_out, o, stats); });
 } MFEM_API_CATCH("mfem_solve")
+
+// ---- mfem_solve on a matrix-free mesh operator (mesh_operator.hip) ------------------------------------------------------------------------------
+// The same driver with an operator attempt in place of solve_attempt: the workspace holds the vectors and the operator's element-vector scratch
+// (mesh_operator_decide.h: mop_workspace) -- no layout, no copy of a matrix --, the Jacobi vector comes from the operator's diagonal kernel, and the
+// bound operator serves every product of the unchanged run_passes.  The stages that read CSR values (bind_tiles, try_scaled_cg, left_precond,
+// ws_trial, csr_true_residual) are never entered.  CG keeps K unscaled and takes 1 / d; the solvers on A D^-1 hand d to the product, which gathers
+// x_j / d_j (the role dsc plays for the lattice tiles).
+static int operator_attempt(SolveRun& R) {
+  mfem_context_s* ctx = R.ctx;
+  mfem_csr_s* A = R.A;
+  KrylovVecs& V = R.V;
+  const int64_t n = A->n;
+  R.next = GO_ON;
+  R.tiles_bound = R.rows_bound = R.cg_scaled = false;
+  R.fused_scale = R.jac && !R.is_cg;
+  R.need_copy = R.scaled_copy = R.gather_early = false;
+  R.tplan = nullptr;
+  R.lp = mfem_layout_plan_s{MFEM_LAYOUT_CSR, MFEM_LAYOUT_CSR, 0, 0};
+  V = KrylovVecs{};
+  V.n = n;
+  const int64_t nv = V.nv = (int64_t)align_up((size_t)n, 32);
+  const int nwork = V.nwork = R.method->nwork(R.s_param);
+  const OpWorkspace W = mop_workspace(nv, nwork, mfem_mesh_operator_scratch_doubles(R.op),
+                                      R.o->method == MFEM_SOLVER_GMRES ? mfem_gmres_workspace_bytes() : 0);
+  R.vec_bytes = W.vec_bytes;
+  R.csr_copy_bytes = R.layout_bytes = 0;
+  R.gm_offset = W.gm_offset;
+  R.total = W.total;
+  int rc = mfem_ws_reserve(ctx, R.total);
+  if (rc) return rc;
+  char* base = (char*)ctx->ws;
+  MFEM_CHECK_HIP(hipMemsetAsync(base, 0, R.vec_bytes * (4 + nwork), ctx->stream));
+  V.x = (double*)(base);
+  V.b = (double*)(base + R.vec_bytes);
+  V.d = (double*)(base + 2 * R.vec_bytes);
+  R.dinv_buf = (double*)(base + 3 * R.vec_bytes);
+  for (int i = 0; i < nwork; ++i) V.w[i] = (double*)(base + (4 + i) * R.vec_bytes);
+  if (R.o->method == MFEM_SOLVER_GMRES) V.gm = (double*)(base + R.gm_offset);
+  double* scratch = (double*)(base + W.scratch_offset);
+  R.vals_work = nullptr;
+  R.vals_src = nullptr;
+  R.lay = nullptr;
+  MFEM_CHECK_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  MFEM_CHECK_HIP(hipMemcpyAsync(V.b, R.b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  if (R.jac) {  // Pr_Jacobi!: d = |diag K| under the guarded rule (a row without adjacency or with a zero diagonal keeps the preset 1)
+    rc = mfem_fill(ctx, n, 1.0, V.d);
+    if (!rc) rc = mfem_mesh_operator_jacobi(ctx, R.op, scratch, V.d);
+    if (rc) return rc;
+    if (R.is_cg) {
+      hipLaunchKernelGGL(k_recip, dim3(mfem_vec_grid(ctx, n)), dim3(MFEM_BLOCK), 0, ctx->stream, n, V.d, R.dinv_buf);
+      MFEM_CHECK_LAUNCH();
+      V.dinv = R.dinv_buf;
+    }
+  }
+  struct Unbind { mfem_mesh_operator_s* op; ~Unbind() { mfem_mesh_operator_unbind(op); } } unbind{R.op};
+  mfem_mesh_operator_bind(R.op, scratch, R.fused_scale ? V.d : nullptr);
+  return run_passes(R);
+}
+
+extern "C" int mfem_solve_operator(mfem_context ctx, uint64_t handle, const double* b, double* x_out, const mfem_solve_options* o,
+                                   mfem_solve_stats* stats) try {
+  mfem_mesh_operator_s* op = mfem_mesh_operator_from_handle(handle);
+  MFEM_REQUIRE(ctx && op && o, "null argument");
+  MFEM_REQUIRE(mfem_mesh_operator_ctx(op) == ctx, "the operator was created on another context");
+  mfem_csr_s* A = mfem_mesh_operator_csr(op);
+  MFEM_REQUIRE(!A->op, "the operator is bound to a running solve");
+  MFEM_REQUIRE(A->n == 0 || (b && x_out), "null array");
+  MFEM_REQUIRE(o->method >= MFEM_SOLVER_CG && o->method <= MFEM_SOLVER_LSQR, "unknown method");
+  MFEM_REQUIRE(o->precond >= MFEM_PRECOND_NONE && o->precond <= MFEM_PRECOND_JACOBI_RIGHT_COLNORM, "unknown precond");
+  MFEM_REQUIRE(o->left_precond >= MFEM_LEFT_NONE && o->left_precond <= MFEM_LEFT_JACOBI_ROWNORM, "unknown left_precond");
+  const char* why = "";
+  const int gate = mop_solve_gate(o->method, o->precond, o->left_precond, o->scale_in_place, ctx->comm != nullptr, &why);
+  if (gate) {
+    mfem_set_error("mfem_solve_operator: %s", why);
+    return gate;
+  }
+  return solve_with_graphs(ctx, A->n, [&]() -> int {
+    SolveRun R{ctx, A, nullptr, b, x_out, o, stats};
+    R.op = op;
+    const int rc = choose_method(R);
+    if (rc || A->n == 0) return rc;
+    R.allow_lat = false;
+    return operator_attempt(R);
+  });
+} MFEM_API_CATCH("mfem_solve_operator")

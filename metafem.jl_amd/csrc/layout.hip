@@ -49,11 +49,13 @@ int mfem_layout_bind(mfem_context_s* ctx, mfem_csr_s* A, mfem_layout mode, const
     case MFEM_LAYOUT_SELL: return mfem_sell_bind(ctx, A, vals, buf, dsc);
     case MFEM_LAYOUT_LAT27: return mfem_lat27_bind(ctx, A, vals, buf, dsc, scratch, allow_rem);
     case MFEM_LAYOUT_LAT8: return mfem_lat8_bind(ctx, A, vals, buf, dsc, scratch, allow_rem);
+    case MFEM_LAYOUT_OPERATOR: break;  // (bound by mfem_mesh_operator_bind, never through a plan)
   }
   return MFEM_OK;
 }
 
 mfem_layout mfem_layout_bound(const mfem_csr_s* A, const double* vals) {
+  if (A->op) return MFEM_LAYOUT_OPERATOR;  // (the operator's own pattern-less handle: there are no values to tell apart)
   if (A->lat8.vals && vals == A->lat8.src) return MFEM_LAYOUT_LAT8;
   if (A->ell_vals && vals == A->ell_src) return A->ell_bound_mode == 2 ? MFEM_LAYOUT_DIA : MFEM_LAYOUT_ELL;
   if (A->lat27.vals && vals == A->lat27.src) return MFEM_LAYOUT_LAT27;
@@ -149,6 +151,7 @@ static int layout_account(mfem_context ctx, mfem_csr A, int64_t* entries, int32_
     case MFEM_LAYOUT_SELL: e = mfem_sell_entries(A); b = mfem_sell_design_bytes(A); break;
     case MFEM_LAYOUT_LAT27: e = mfem_lat27_entries(A); b = mfem_lat27_design_bytes(A); sym = 3; break;
     case MFEM_LAYOUT_LAT8: e = mfem_lat8_entries(A); b = mfem_lat8_design_bytes(A); sym = 3; break;
+    case MFEM_LAYOUT_OPERATOR: break;  // (never planned)
   }
   if (entries) *entries = e;
   if (sweep) *sweep = sym;

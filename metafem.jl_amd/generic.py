@@ -23,7 +23,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-from .affine import AffineResidual, affine_residual  # noqa: F401  (the residual-side generalisation of constant_coefficient)
+from .affine import AffineResidual, OperatorCoefficient, affine_residual, operator_coefficient  # noqa: F401  (the generalisations of constant_coefficient)
 
 
 @dataclass
@@ -90,6 +90,26 @@ def constant_coefficient(fn) -> Optional[float]:
         return None
 
 
+def matrix_free_terms(domain_wf: "WeakForm", boundary_wfs: Sequence["WeakForm"], t: float = 0.0, dt: float = 1.0):
+    """Eligibility of a problem for the matrix-free operator (GenericDomain(matrix_free=True)), decided on the host: no part has nonlinear
+    gradients, and every linear gradient's coefficient is a constant or, on facets, a constant plus a linear function of the normal components,
+    free of fields and externals (affine.operator_coefficient: probed, then checked numerically).
+    -> (per part [(GradTerm, OperatorCoefficient)], None) or (None, the reason)."""
+    parts = []
+    for i, wf in enumerate([domain_wf] + list(boundary_wfs)):
+        where = "the domain" if i == 0 else f"boundary group {i - 1}"
+        if wf.nonlinear_gradients:
+            return None, f"{where} has nonlinear gradient terms"
+        terms = []
+        for k, g in enumerate(wf.linear_gradients):
+            c = operator_coefficient(g, wf, facet=i > 0, t=t, dt=dt)
+            if c is None:
+                return None, f"linear gradient {k} of {where}: its coefficient is not a constant" + (" plus a normal-linear part" if i else "")
+            terms.append((g, c))
+        parts.append(terms)
+    return parts, None
+
+
 class _Group:
     """Integration hosts of one launch family (the elements, or the facets of one boundary group).  The geometry tables of the
     operator path (vals, weights, normals: update_BasicElements / update_BasicBoundary) are built by `build` on first access."""
@@ -143,7 +163,7 @@ class GenericDomain:
                  boundaries: Sequence[Tuple[np.ndarray, np.ndarray, WeakForm]],
                  element_colours: Optional[np.ndarray] = None, max_time_level: int = 0, dissipative: bool = True,
                  batched: bool = True, fused: bool = True, row_owner: bool = True, fused_residual: bool = False,
-                 table_free: bool = False, direct_rows: bool = False):
+                 table_free: bool = False, direct_rows: bool = False, matrix_free: bool = False):
         """coords [ncp, dim]; cp_ids [itp, nel] 0-based (controlpoint_IDs in basis order); boundaries =
         [(element_ID[nf], element_eindex[nf] 0-based local face ids, WeakForm)].  element_colours (optional):
         a colour per element such that same-colour elements share no control point -> atomics-free scatter with a fixed
@@ -174,6 +194,16 @@ class GenericDomain:
         # this domain.  Facet groups and variable-coefficient terms are unchanged.
         self.direct_rows = direct_rows
         self._direct_plan = None
+        # matrix_free = True (implies fused and fused_residual): no matrix at all.  self.A is a MeshOperator (mfem_mesh_operator_*: K x and diag K straight
+        # from the mesh), K_linear / K_total / slots are None, assemble_SparseID is never called and K_linear_func only re-sends the terms (coefficient
+        # times the current K_params); `linear_solver = lambda g: iterative_Solve(g.A, g.K_total, g.residue, ...)` works unchanged.  A problem that is
+        # not eligible (matrix_free_terms) or that the library refuses (MFEM_ERR_UNSUPPORTED: the caps) is built as the default domain is:
+        # matrix_free is False then and matrix_free_reason says why.
+        self.matrix_free, self.matrix_free_reason = bool(matrix_free), None
+        if matrix_free:
+            _, self.matrix_free_reason = matrix_free_terms(domain_wf, [b[2] for b in boundaries])
+            self.matrix_free = self.matrix_free_reason is None
+            self.fused = self.fused_residual = fused = fused_residual = True
         if table_free:
             if not batched:
                 raise ValueError("table_free=True needs batched=True: the single-term seam (mfem_op_var / _res / _kval) reads the stored tables")
@@ -259,19 +289,22 @@ class GenericDomain:
 
         self.variable_size = ncp
         self.basicfield_size = n_fields * ncp
-        self.A, self.slots = assemble_SparseID(self.cp, ncp, n_fields=n_fields, index_base=1, ctx=ctx)
+        if self.matrix_free:
+            self.A, self.slots = self._mesh_operator(), None
+        if not self.matrix_free:
+            self.A, self.slots = assemble_SparseID(self.cp, ncp, n_fields=n_fields, index_base=1, ctx=ctx)
         n = self.basicfield_size
         z = lambda m: torch.zeros(m, dtype=torch.float64, device=dev)
         # x, dx, x_star hold max_time_level + 1 blocks of basicfield_size (03_GlobalAssembly.jl:27-31)
         self.max_time_level = max_time_level
         nglob = (max_time_level + 1) * n
         self.x, self.dx, self.x_star, self.residue = z(nglob), z(nglob), z(nglob), z(n)
-        self.K_linear = z(self.A.nnz)
+        self.K_linear = None if self.matrix_free else z(self.A.nnz)
         # K_total = K_linear + the nonlinear gradient terms (05_CodeGenerator.jl:282-283).  A form without nonlinear gradient terms never adds anything: its
         # K_total IS K_linear (the same storage, unless K_total_private asks for a copy a solver may scale in place) -- no second nnz-sized array (15 GB for hex-20
         # elasticity at 96^3), no copy per Newton step
         self._K_total_aliases = not any(wf.nonlinear_gradients for wf in [domain_wf] + [b[-1] for b in boundaries])
-        self.K_total = self.K_linear if self._K_total_aliases else z(self.A.nnz)
+        self.K_total = self.K_linear if self._K_total_aliases or self.matrix_free else z(self.A.nnz)
         self.controlpoints: Dict[str, torch.Tensor] = {}
         self.converge_tol = 1e-6
         # GeneralAlpha (04_Time_Domain.jl:1-7); FEM_Domain builds it with dissipative = true (01_Types.jl:168)
@@ -287,6 +320,37 @@ class GenericDomain:
         # step would solve with the scaled matrix.  Off by default, so that solvers that only read K keep the memory of the alias.
         self.K_total_private = False
         self.history: List[float] = []
+
+    # -- the matrix-free operator (matrix_free=True) -------------------------------------------------------------
+    def _operator_terms(self, K_params):
+        """Per part the ABI terms (dual_sd, base_sd, block, coef, normal coefficients) at the current t / dt, times K_params; None: not eligible."""
+        parts, reason = matrix_free_terms(self.domain_wf, self.bwfs, t=getattr(self, "t", 0.0), dt=getattr(self, "dt", 1.0))
+        if parts is None:
+            self.matrix_free_reason = reason
+            return None
+        return [[(g.dual_s, g.base_s, g.dual_pos * self.n_fields + g.base_pos, c.c0 * K_params[g.td_order],
+                  tuple(v * K_params[g.td_order] for v in c.normal)) for g, c in terms] for terms in parts]
+
+    def _mesh_operator(self):
+        """The MeshOperator of this domain: the elements, then a part per boundary group that has linear gradients.  None (and matrix_free False,
+        the reason set) when the library answers MFEM_ERR_UNSUPPORTED."""
+        from . import MeshOperator
+
+        parts = self._operator_terms([1.0] * 8)
+        op = MeshOperator(self.ctx, self.dim, self.itp, self.nel, self.ncp, self.n_fields, self.coords, self.cp, 1)
+        self._op_part = [0] + [None] * len(self.bwfs)
+        rc = op.set_elements(self.space.itg, self._ref, self._itgw, self._adj_ptr, self._adj, parts[0])
+        for i, g in enumerate(self.groups[1:], start=1):
+            if rc == -3 or not parts[i] or g.facet_el.numel() == 0:
+                continue
+            ptr, adj = self._residual_adj(g)
+            rc = op.add_facets(self.space.itg_b, self._nface, self._bref, self._bw, self._btan, g.facet_el, g.facet_eidx, ptr, adj, parts[i])
+            self._op_part[i] = rc if rc >= 0 else None
+        if rc == -3:
+            op.close()
+            self.matrix_free, self.matrix_free_reason = False, "the library refused the operator: " + lib.mfem_last_error().decode()
+            return None
+        return op
 
     # -- assemble_X! / dessemble_X! (03_GlobalAssembly.jl:44-75)
     def assemble_X(self, infos):
@@ -597,6 +661,14 @@ class GenericDomain:
     def K_linear_func(self):
         # K_linear starts from zero (05_CodeGenerator.jl:282).  When the first thing it receives is the row-owner element assembly, that launch WRITES
         # every row instead (mfem_mesh_assemble_elements_rows_set): no memset, no read of the zeros.
+        if self.matrix_free:  # nothing is assembled: the terms, times this step's K_params, go to the operator
+            parts = self._operator_terms(self.K_params)
+            if parts is None:
+                raise _lib.MetaFEMError("matrix_free: " + self.matrix_free_reason)
+            for terms, part in zip(parts, self._op_part):
+                if part is not None and self.A.set_terms(part, terms) == -3:
+                    raise _lib.MetaFEMError("matrix_free: " + lib.mfem_last_error().decode())
+            return
         self._K_fresh = True
         for wf, g in self._parts():
             if not wf.linear_gradients:
@@ -688,10 +760,11 @@ class GenericDomain:
 
     def K_nonlinear_func(self):
         self.residue.zero_()
-        if self.K_total_private and self.K_total is self.K_linear:
-            self.K_total = torch.empty_like(self.K_linear)
-        if self.K_total is not self.K_linear:
-            self.K_total.copy_(self.K_linear)  # 05_CodeGenerator.jl:282-283
+        if not self.matrix_free:  # (matrix_free: no K_total, the operator is the matrix)
+            if self.K_total_private and self.K_total is self.K_linear:
+                self.K_total = torch.empty_like(self.K_linear)
+            if self.K_total is not self.K_linear:
+                self.K_total.copy_(self.K_linear)  # 05_CodeGenerator.jl:282-283
         for i, (wf, g) in enumerate(self._parts()):
             residues = wf.residues
             if self.fused_residual and not residues and not wf.nonlinear_gradients:
