@@ -58,30 +58,39 @@ def test_slab_rows_equal_global_rows(mf, n, lo, hi):
     assert np.allclose(y.cpu().numpy(), gy.cpu().numpy()[r0:r1], rtol=1e-14, atol=1e-10)
 
 
-@pytest.mark.parametrize("lo,hi", [(0, 2), (2, 5), (3, 6)])
-def test_elasticity_slab_rows_equal_global_rows(mf, lo, hi):
+# penalty faces, traction faces, sig (11, 22, 33, 23, 13, 12)
+ELASTICITY_SLAB_FACES = {"cantilever": ("x0", "y1", (0.0, 1.0, 0.0, 0.0, 0.0, 0.3)),
+                         # both terms on the slabs' own end planes (x0: first slab, x1: last slab, carrying both) and on faces every slab cuts
+                         "three_faces_each": ("x0|x1|z0", "x1|y0|z1", (0.7, 1.0, -0.3, 0.55, 0.25, -0.4))}
+
+
+@pytest.mark.parametrize("lo,hi,faces", [(lo, hi, f) for f in ELASTICITY_SLAB_FACES for lo, hi in ((0, 2), (2, 5), (3, 6))],
+                         ids=["0-2", "2-5", "3-6", "three_faces_each-0-2", "three_faces_each-2-5", "three_faces_each-3-6"])
+def test_elasticity_slab_rows_equal_global_rows(mf, lo, hi, faces):
     """3 fields, field-major: slab rows (f, owned node) and ghost columns behind all owned entries."""
     import torch
     from metafem_jl_amd import parallel as par
 
     x, n = (2.0, 1.0, 1.0), (5, 2, 3)
     lam, mu, tau = 0.5769, 0.3846, 1000.0
+    pen_names, tra_names, sig = ELASTICITY_SLAB_FACES[faces]
+    pen = sum(mf.FACE_BITS[s] for s in pen_names.split("|"))
+    tra = sum(mf.FACE_BITS[s] for s in tra_names.split("|"))
     m1, m2 = n[1] + 1, n[2] + 1
     pl = m1 * m2
     ncp = (n[0] + 1) * pl
     gb = mf.make_Brick(x, n)
     gA = gb.pattern(3)
-    gK = gb.assemble_elasticity(gA, lam, mu, tau, mf.FACE_BITS["x0"]).cpu().numpy()
+    gK = gb.assemble_elasticity(gA, lam, mu, tau, pen).cpu().numpy()
     grp, gcol = gA.rowptr.cpu().numpy(), gA.colidx.cpu().numpy()
     gx = 0.01 * np.random.default_rng(1).standard_normal(3 * ncp)
-    sig = (0.0, 1.0, 0.0, 0.0, 0.0, 0.3)
-    gR = gb.residual_elasticity(torch.tensor(gx, device="cuda"), lam, mu, tau, mf.FACE_BITS["x0"], mf.FACE_BITS["y1"], sig).cpu().numpy()
+    gR = gb.residual_elasticity(torch.tensor(gx, device="cuda"), lam, mu, tau, pen, tra, sig).cpu().numpy()
     sb = mf.make_Brick(x, n)
     sb.set_slab(lo, hi)
     sA = sb.pattern(3)
     n_owned = (hi - lo) * pl
     assert sA.n == 3 * n_owned
-    sK = sb.assemble_elasticity(sA, lam, mu, tau, mf.FACE_BITS["x0"]).cpu().numpy()
+    sK = sb.assemble_elasticity(sA, lam, mu, tau, pen).cpu().numpy()
     srp, scol = sA.rowptr.cpu().numpy(), sA.colidx.cpu().numpy()
     nloc = par.local_vector_length(lo, hi, m1, m2, 3)
     xl = np.zeros(nloc)
@@ -99,7 +108,7 @@ def test_elasticity_slab_rows_equal_global_rows(mf, lo, hi):
             jj, kk = np.meshgrid(np.arange(m1), np.arange(m2), indexing="ij")
             li = par.slab_local_index(np.full(jj.size, i), jj.ravel(), kk.ravel(), f, lo, hi, m1, m2, 3)
             xl[li] = gx[f * ncp + i * pl + jj.ravel() * m2 + kk.ravel()]
-    sR = sb.residual_elasticity(torch.tensor(xl, device="cuda"), lam, mu, tau, mf.FACE_BITS["x0"], mf.FACE_BITS["y1"], sig).cpu().numpy()
+    sR = sb.residual_elasticity(torch.tensor(xl, device="cuda"), lam, mu, tau, pen, tra, sig).cpu().numpy()
     for f in range(3):
         assert np.array_equal(sR[f * n_owned:(f + 1) * n_owned], gR[f * ncp + lo * pl:f * ncp + hi * pl])
 

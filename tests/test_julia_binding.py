@@ -271,6 +271,16 @@ def test_struct_mirrors_have_the_c_layout():
         assert need in seen, f"no Julia mirror of {need}"
 
 
+def test_traction_tensor_order_is_stated_alike_everywhere():
+    """mfem_elasticity_params.sig: the header, the Julia mirror, the Python wrapper and INTEGRATION.md name the order (11, 22, 33, 23, 13, 12)."""
+    order = re.compile(r"11,\s*22,\s*33,\s*23,\s*13,\s*12")
+    read = lambda *p: open(os.path.join(ROOT, *p)).read()
+    assert order.search(re.search(r"double sig\[6\];[^\n]*", read("include", "metafem_mi355x.h")).group(0))
+    assert order.search(re.search(r"sig::NTuple\{6, Float64\}[^\n]*", read("julia", "MI355X.jl")).group(0))
+    assert order.search(re.search(r"def residual_elasticity.*?\"\"\".*?\"\"\"", read("metafem.jl_amd", "__init__.py"), flags=re.S).group(0))
+    assert order.search(re.search(r"traction tensor `sig`[^\n]*", read("INTEGRATION.md")).group(0))
+
+
 def test_abi_version_constant():
     hdr = open(HEADERS[0]).read()
     ver = int(re.search(r"#define MFEM_ABI_VERSION (\d+)", hdr).group(1))
