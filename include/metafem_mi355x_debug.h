@@ -179,7 +179,7 @@ int mfem_debug_comm_selftest(mfem_context ctx, int64_t count, int32_t rounds);
 unsigned long long mfem_debug_ws_address(mfem_context ctx);
 /* Workspace placement trial, OFF by default (round 4: a drop-in mfem_solve must not hide seconds of allocation work).  1: the first solve on a
  * workspace of 8 GB or more times the solver SpMV, tries up to two more allocations of the workspace the same way (at most two alive: PEAK MEMORY
- * = TWICE THE WORKSPACE, 90 GB at 512^3) and keeps the fastest -- the speed follows the physical memory an allocation received (7 % of every later
+ * = TWICE THE WORKSPACE, 90 GB at 512^3 -- 105 GB with the ring of 8 CG directions) and keeps the fastest -- the speed follows the physical memory an allocation received (7 % of every later
  * iteration at 512^3, profiles/r04_placement_counters.txt).  Paid once per workspace: 5 - 7 s at 512^3 (a hipMalloc of 45 GB takes 2 s, a hipFree
  * about as long; MFEM_WS_TRIAL_VERBOSE=1 prints the steps' times to stderr).  Rank-local: with a communicator attached every rank runs its own
  * trial (the candidates' timing uses no collective).  bench.py opts in with --ws-trial 1 and says so in its line. */
@@ -187,6 +187,13 @@ unsigned long long mfem_debug_ws_address(mfem_context ctx);
 /* 1 (default): the two vector kernels of the classic CG recurrences use streaming (nontemporal) loads, and from 4e7 rows on streaming stores too
  * (csrc/krylov_cg.hip: cg_ld / cg_st); 0: plain accesses.  Same values either way. */
 /* ^ key "cg_streaming": mfem_debug_set("cg_streaming", a, b) with (int on) = (a[, b]) */
+/* Depth m of the ring of search directions of the classic CG recurrences (cg_variant 1, 3, 4; csrc/cg_decide.h, csrc/krylov_cg.hip): x is written
+ * once per m iterations from the last m directions -- per element, in iteration order, one fma per component each, so x and every statistic are the
+ * same BIT FOR BIT for every m.  0 (default): automatic -- 8 from 4e7 rows on (m - 1 more work vectors: 7.6 GB at 512^3), 1 below; 1 .. 16: that depth
+ * (1 = x += alpha p in every iteration); anything else: automatic.  tests/test_gpu_cg_ring.py. */
+/* ^ key "cg_ring": mfem_debug_set("cg_ring", a, b) with (int depth) = (a[, b]) */
+/* passes of the classic CG recurrences that ran with a ring deeper than 1 so far (process-wide) */
+long long mfem_debug_cg_ring_count(void);
 /* cg_variant 0 (auto) with a communicator of more than one rank: the single-reduction CG (one all-reduce, 9 vector streams per iteration) below this many
  * rows per rank (n_global / world; default 2e7), the classic recurrence (two all-reduces, 8 streams) from there on -- at 512^3 per rank a vector stream
  * costs 0.2 ms, an all-reduce ~0.03 ms.  Set 0 for always-classic, a huge value for always-single. */

@@ -168,6 +168,7 @@ SIGNATURES = {
     "mfem_debug_set": (c_int, [C.c_char_p, c_int64, c_int64]),
     "mfem_debug_graph_comm_count": (c_int, []),
     "mfem_debug_graph_launch_count": (C.c_longlong, []),
+    "mfem_debug_cg_ring_count": (C.c_longlong, []),
     "mfem_debug_lat27_cg_fused": (c_int, []),
     "mfem_debug_lat27_pass1_bytes": (c_int64, [P]),
     "mfem_prof_spmv_enable": (c_int, [P, c_int]),

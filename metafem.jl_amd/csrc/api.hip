@@ -332,6 +332,7 @@ int mfem_debug_set_hex8_thermal(int);
 int mfem_debug_set_ws_placement(long long, long long);
 int mfem_debug_set_ws_trial(int);
 int mfem_debug_set_cg_streaming(int);
+int mfem_debug_set_cg_ring(int);
 int mfem_debug_set_cg_single_max_rows(int64_t);
 int mfem_debug_set_csr_strips(int, int64_t);
 int mfem_debug_set_remainder(int);
@@ -362,6 +363,7 @@ extern "C" int mfem_debug_set(const char* key, int64_t a, int64_t b) try {
   if (k == "ws_placement") return mfem_debug_set_ws_placement((long long)a, (long long)b);
   if (k == "ws_trial") return mfem_debug_set_ws_trial((int)a);
   if (k == "cg_streaming") return mfem_debug_set_cg_streaming((int)a);
+  if (k == "cg_ring") return mfem_debug_set_cg_ring((int)a);
   if (k == "cg_single_max_rows") return mfem_debug_set_cg_single_max_rows(a);
   if (k == "csr_strips") return mfem_debug_set_csr_strips((int)a, b);
   if (k == "remainder") return mfem_debug_set_remainder((int)a);

@@ -51,6 +51,7 @@ struct KrylovVecs {
   double cg_smax = 1.0, cg_smin = 1.0;
   double* w[3 * MFEM_MAX_S + 8];
   int nwork;
+  int cg_ring = 1;  // mfem_cg_pass: depth m of its ring of search directions (cg_decide.h); w[3 .. m + 1] are slots 1 .. m - 1, one vector apart
   bool x_zero = false;  // x is still the zero vector a solve starts from (x0 = 0, 02_Preconditioner.jl:45): the first pass's r = b - A x is b itself
   double* gm = nullptr;  // gmres!: H, y and the block-dot partials (mfem_gmres_workspace_bytes)
   mfem_csr_s* AT = nullptr;  // lsqr!: the transposed pattern (spmv_t.hip) and its working values Pl(A_r)' (mfem_solve)
@@ -74,6 +75,7 @@ mfem_pass_fn mfem_cg_pass, mfem_cg_single_pass, mfem_bicgstabl_pass, mfem_cgs2_p
 // krylov_next.hip: cgs!, tfqmr! (checkiter = s, default 200), lsqr! (products with A' through V.AT / V.valsT)
 mfem_pass_fn mfem_cgs_pass, mfem_tfqmr_pass, mfem_lsqr_pass;
 size_t mfem_gmres_workspace_bytes();
+int mfem_cg_ring_depth(int64_t nv);  // krylov_cg.hip: cg_ring_depth (cg_decide.h) under the knob mfem_debug_set("cg_ring")
 
 // ---- hipGraph replay of one solver cycle -------------------------------------------------------------------------
 // The Krylov drivers keep every recurrence scalar on the device and guard their kernels with the DONE flag, so the kernel

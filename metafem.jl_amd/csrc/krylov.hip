@@ -248,7 +248,7 @@ struct KrylovMethod {
   mfem_pass_fn* pass;
 };
 static const KrylovMethod k_methods[] = {
-    {"cg!", 2, MFEM_MAX_S, [](int) { return 3; }, false, mfem_cg_pass},  // r, p, Ap
+    {"cg!", 2, MFEM_MAX_S, [](int) { return 3; }, false, mfem_cg_pass},  // r, p, Ap (+ m - 1 further slots of the ring of directions: cg_work_vectors)
     {"bicgstabl_GS!", 2, MFEM_MAX_S, [](int l) { return 2 * (l + 1) + 1; }, false, mfem_bicgstabl_pass},  // R[0..l], U[0..l], r~
     {"idrs!", 4, MFEM_MAX_S, [](int s) { return 3 * s + 4; }, false, mfem_idrs_pass},
     {"cgs2!", 2, MFEM_MAX_S, [](int) { return 9; }, false, mfem_cgs2_pass},
@@ -262,6 +262,19 @@ static const KrylovMethod k_methods[] = {
 // cg! with one reduction group per iteration: r, p, s, u, w
 static const KrylovMethod k_cg_single = {"cg!", 2, MFEM_MAX_S, [](int) { return 5; }, false, mfem_cg_single_pass};
 static_assert(sizeof(k_methods) / sizeof(k_methods[0]) == MFEM_SOLVER_LSQR + 1, "one row per mfem_solver_kind");
+
+// The work vectors of this solve and how many of them (with the four in front) start cleared.  mfem_cg_pass keeps a ring of m search directions
+// (cg_decide.h): its slots beyond p follow the method's three vectors.  Every slot is written in full before it is read (k_cg_init, k_cg_pupdate), so
+// they are left out of the per-solve clear -- 1.3 ms per solve at 512^3 with m = 8.
+static void cg_work_vectors(const KrylovMethod* method, int s_param, KrylovVecs& V, int* nclear) {
+  V.nwork = method->nwork(s_param);
+  *nclear = 4 + V.nwork;
+  V.cg_ring = 1;
+  if (method->pass == mfem_cg_pass) {
+    V.cg_ring = mfem_cg_ring_depth(V.nv);
+    V.nwork += V.cg_ring - 1;
+  }
+}
 
 // What the stages of one mfem_solve share: the arguments, what choose_method derives from them once per solve, and what one attempt sets up.  A stage
 // that cannot go on with this attempt says so in `next`; solve_inner then runs the set-up again from plan_layouts.
@@ -287,6 +300,7 @@ struct SolveRun {
   mfem_layout_plan_s lp;
   mfem_tplan_s* tplan;  // lsqr!: the transposed pattern
   size_t vec_bytes, csr_copy_bytes, layout_bytes, gm_offset, total;
+  int nclear;  // vectors at the front of the workspace that start cleared (cg_work_vectors)
   KrylovVecs V;
   double* dinv_buf;        // CG: 1 / d (scaled CG: 1 / S); otherwise the left scaling dl
   double* vals_work;       // the values the passes run on: the caller's, or the working copy
@@ -358,7 +372,8 @@ static int plan_layouts(SolveRun& R) {
   // x may carry ghost entries behind the owned rows (slab decomposition)
   const int64_t ghosts = ctx->comm ? 2 * ctx->halo_plane_len * ctx->halo_fields : 0;
   const int64_t nv = R.V.nv = (int64_t)align_up((size_t)(A->n + ghosts), 32);  // padded vector length (even => d2 kernels)
-  const int nwork = R.V.nwork = R.method->nwork(R.s_param);
+  cg_work_vectors(R.method, R.s_param, R.V, &R.nclear);
+  const int nwork = R.V.nwork;
   // lsqr!: the transposed pattern, planned on the first lsqr! solve (or mfem_spmv_csr_t) and kept on the handle
   R.tplan = nullptr;
   if (R.is_lsqr) {
@@ -405,7 +420,7 @@ static int carve_workspace(SolveRun& R) {
   int rc = mfem_ws_reserve(ctx, R.total);
   if (rc) return rc;
   char* base = (char*)ctx->ws;
-  MFEM_CHECK_HIP(hipMemsetAsync(base, 0, R.vec_bytes * (4 + nwork), ctx->stream));
+  MFEM_CHECK_HIP(hipMemsetAsync(base, 0, R.vec_bytes * R.nclear, ctx->stream));
   V.x = (double*)(base);
   V.b = (double*)(base + R.vec_bytes);
   V.d = (double*)(base + 2 * R.vec_bytes);
@@ -929,7 +944,8 @@ static int operator_attempt(SolveRun& R) {
   V = KrylovVecs{};
   V.n = n;
   const int64_t nv = V.nv = (int64_t)align_up((size_t)n, 32);
-  const int nwork = V.nwork = R.method->nwork(R.s_param);
+  cg_work_vectors(R.method, R.s_param, V, &R.nclear);
+  const int nwork = V.nwork;
   const OpWorkspace W = mop_workspace(nv, nwork, mfem_mesh_operator_scratch_doubles(R.op),
                                       R.o->method == MFEM_SOLVER_GMRES ? mfem_gmres_workspace_bytes() : 0);
   R.vec_bytes = W.vec_bytes;
@@ -939,7 +955,7 @@ static int operator_attempt(SolveRun& R) {
   int rc = mfem_ws_reserve(ctx, R.total);
   if (rc) return rc;
   char* base = (char*)ctx->ws;
-  MFEM_CHECK_HIP(hipMemsetAsync(base, 0, R.vec_bytes * (4 + nwork), ctx->stream));
+  MFEM_CHECK_HIP(hipMemsetAsync(base, 0, R.vec_bytes * R.nclear, ctx->stream));
   V.x = (double*)(base);
   V.b = (double*)(base + R.vec_bytes);
   V.d = (double*)(base + 2 * R.vec_bytes);

@@ -2,7 +2,15 @@
 // (its z-carrying and scaled variants included), and mfem_cg_single_pass, one reduction group per iteration.  Which of the two a solve runs, and the
 // scaled system of cg_variant 4, are decided and set up by the driver (krylov.hip); the lattice tiles' fused residual update restates k_cg_update's
 // arithmetic in its own file (spmv_lat27_gather.hip: k_lat27_gather_cg).
+//
+// Vector streams of one iteration of mfem_cg_pass beside the SpMV (scaled CG, cg_variant 4; the other variants add the stream of 1 / d where they
+// read it): k_cg_update reads A p and r and writes r (3); k_cg_pupdate reads r and p_it and writes p_(it+1) (3) -- 6 at the iterations that leave x
+// alone.  x is written once per m iterations from the ring of the last m directions (cg_decide.h): a flush position adds the m - 1 earlier
+// directions and the read and the write of x, 6 + (m - 1) + 2.  On average 6 + (m + 1) / m: 8 with m = 1 (x += alpha p every iteration), 7.125 with
+// m = 8.  The pending updates are applied per element in iteration order, one fma per component each, as the per-iteration update applies them: x is
+// the same bit for bit for every m, and nothing else in the iteration reads x.
 #include "krylov.h"
+#include "cg_decide.h"
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
 
@@ -27,11 +35,21 @@ __device__ __forceinline__ void cg_st(d2_t* p, int64_t i, d2_t v) {
 #define CG_LD(p, i) cg_ld<NT>((p), (i))
 #define CG_ST(p, i, v) cg_st<NT>((p), (i), (v))
 static std::atomic<int> g_cg_streaming{1};
+static std::atomic<int> g_cg_ring{0};  // depth of the ring of search directions: 0 = cg_ring_depth's own choice, 1 .. CG_RING_MAX forced
+extern "C" int mfem_debug_set_cg_ring(int depth) try {
+  ++mfem_debug_epoch;
+  g_cg_ring = (depth >= 1 && depth <= CG_RING_MAX) ? depth : 0;
+  return MFEM_OK;
+} MFEM_API_CATCH("mfem_debug_set_cg_ring")
+static std::atomic<long long> g_cg_ring_passes{0};
+extern "C" long long mfem_debug_cg_ring_count(void) { return g_cg_ring_passes; }
+int mfem_cg_ring_depth(int64_t nv) { return cg_ring_depth(nv, g_cg_ring); }  // (krylov.hip: the work vectors of a cg! solve)
 extern "C" int mfem_debug_set_cg_streaming(int on) try {
   ++mfem_debug_epoch;
   g_cg_streaming = on ? 1 : 0;
   return MFEM_OK;
 } MFEM_API_CATCH("mfem_debug_set_cg_streaming")
+enum { S_CG_RING_ALPHA = S_SOLVER + 8 };  // [ , + CG_RING_MAX): the step lengths of the iterations whose directions the ring holds (mfem_cg_pass)
 struct CgArgs {
   int64_t n2;       // padded length / 2
   double n_inv;     // 1 / global n (for normalized_norm)
@@ -133,13 +151,37 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_cg_update(CgArgs a, int cur, con
   }
 }
 
-// x += alpha p (the alpha of k_cg_update, recomputed from the same partials) ; beta = rz_new / rz_old ; p = z + beta p ;
-// workgroup 0 also advances the scalar state.  x gets this iteration's update even when the iteration turns out to be the last.
-template <int NT>
+// The ring of search directions as k_cg_pupdate and k_cg_xflush see it (cg_decide.h).  Slot 0 is the pass's p vector, slots 1 .. m - 1 lie n2 apart
+// behind `ring`; alpha[k] is the step length of the iteration whose direction slot k holds.
+struct CgRing {
+  d2_t* p0;
+  d2_t* ring;
+  double* alpha;
+  int32_t m;      // depth (a kernel instantiated for one depth uses its own constant)
+  int32_t slot;   // of this iteration's p; the next one's goes to (slot + 1) % m
+};
+__device__ __forceinline__ d2_t* cg_ring_ptr(const CgRing& g, int64_t n2, int k) { return k == 0 ? g.p0 : g.ring + (int64_t)(k - 1) * n2; }
+// x + alpha p as the iterate has always been updated: the compiler contracted `x + alpha * p` to one fma per component; spelled out, so that the
+// deferred applications and the per-iteration one round alike whatever the contraction setting
+__device__ __forceinline__ d2_t cg_axpy(double alpha, d2_t pv, d2_t xv) {
+  d2_t o;
+  o.x = __builtin_fma(alpha, pv.x, xv.x);
+  o.y = __builtin_fma(alpha, pv.y, xv.y);
+  return o;
+}
+
+// alpha (that of k_cg_update, recomputed from the same partials) ; beta = rz_new / rz_old ; p_(it+1) = z + beta p_it, read from slot it % m of the
+// ring and written to slot (it + 1) % m ; workgroup 0 also advances the scalar state and stores alpha beside its direction.
+// x: at a flush position ((it + 1) % m == 0, every iteration with m = 1) x += alpha_j p_j for the m - 1 earlier iterations of the ring, in iteration
+// order, then this one's -- x[i] read once, written once.  The slot of the oldest of them is the slot p_(it+1) goes to: the same thread reads that
+// element before it writes it (no __restrict__ on the ring).  Elsewhere x is not touched.  An iteration that turns out to be the last writes no
+// direction; at a flush position x gets all m pending updates, elsewhere they are left to k_cg_xflush.
+// MU: 1 = no ring (m = 1), 8 / 16 = that depth with the flush unrolled (all loads of an element in flight), 0 = the depth g.m.
+template <int NT, int MU>
 __global__ __launch_bounds__(MFEM_BLOCK) void k_cg_pupdate(CgArgs a, int cur, const double* __restrict__ pap_partials, int np1,
                                                              const double* __restrict__ partials2, int np,
                                                              const d2_t* __restrict__ r, const d2_t* __restrict__ dinv,
-                                                             d2_t* __restrict__ p, d2_t* __restrict__ x, double* __restrict__ S,
+                                                             CgRing g, d2_t* __restrict__ x, double* __restrict__ S,
                                                              const int32_t* __restrict__ flags, int32_t* __restrict__ flags_next) {
   __shared__ double red[4];
   if (flags[F_DONE]) {  // the stop state moves on to the bank the next iteration reads
@@ -163,15 +205,47 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_cg_pupdate(CgArgs a, int cur, co
   const int iter = flags[F_ITER] + 1;
   const bool done = (!a.fixed && sqrt(rr * a.n_inv) <= a.tol) || iter >= a.maxiter;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (!done) {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < a.n2; i += stride) {
-      const d2_t rv = CG_LD(r, i), pv = CG_LD(p, i);
-      CG_ST(x, i, CG_LD(x, i) + alpha * pv);
-      const d2_t z = (dinv && !a.zrec) ? rv * dinv[i] : rv;
-      CG_ST(p, i, z + beta * pv);
+  const int m = MU ? MU : g.m;
+  const bool flush = MU == 1 || g.slot == m - 1;
+  const d2_t* pc = cg_ring_ptr(g, a.n2, MU == 1 ? 0 : g.slot);
+  d2_t* pn = cg_ring_ptr(g, a.n2, (MU == 1 || flush) ? 0 : g.slot + 1);
+  constexpr int NE = MU > 1 ? MU - 1 : 1;  // earlier iterations of an unrolled flush
+  double al[NE];
+  if (MU > 1 && flush) {
+#pragma unroll
+    for (int k = 0; k < NE; ++k) al[k] = g.alpha[k];
+  }
+  // the pending updates of element i on top of xv, oldest first
+  auto pending = [&](d2_t xv, int64_t i, d2_t pv) -> d2_t {
+    if constexpr (MU > 1) {
+      d2_t e[NE];
+#pragma unroll
+      for (int k = 0; k < NE; ++k) e[k] = CG_LD(cg_ring_ptr(g, a.n2, k), i);
+#pragma unroll
+      for (int k = 0; k < NE; ++k) xv = cg_axpy(al[k], e[k], xv);
+    } else if constexpr (MU == 0) {
+      for (int k = 0; k < m - 1; ++k) xv = cg_axpy(g.alpha[k], CG_LD(cg_ring_ptr(g, a.n2, k), i), xv);
     }
-  } else {
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < a.n2; i += stride) x[i] = x[i] + alpha * p[i];
+    return cg_axpy(alpha, pv, xv);
+  };
+  if (!done) {
+    if (flush) {
+      for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < a.n2; i += stride) {
+        const d2_t rv = CG_LD(r, i), pv = CG_LD(pc, i);
+        const d2_t xv = pending(CG_LD(x, i), i, pv);
+        CG_ST(x, i, xv);
+        const d2_t z = (dinv && !a.zrec) ? rv * dinv[i] : rv;
+        CG_ST(pn, i, cg_axpy(beta, pv, z));
+      }
+    } else {
+      for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < a.n2; i += stride) {
+        const d2_t rv = CG_LD(r, i), pv = CG_LD(pc, i);
+        const d2_t z = (dinv && !a.zrec) ? rv * dinv[i] : rv;
+        CG_ST(pn, i, cg_axpy(beta, pv, z));
+      }
+    }
+  } else if (flush) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < a.n2; i += stride) x[i] = pending(x[i], i, pc[i]);
   }
   // bookkeeping last: every workgroup has read flags/S before workgroup 0 can change them only if it
   // reads first -- workgroup 0 reads above, writes here; other workgroups read slots this write does
@@ -179,22 +253,40 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_cg_pupdate(CgArgs a, int cur, co
   // F_ITER / F_DONE of the NEXT iteration live in the other flag bank (iterations alternate between two banks, like the scalar
   // slots): no workgroup of this kernel reads what is written here, so a late workgroup still sees the flags its siblings saw --
   // and no separate 1-thread kernel per iteration is needed for it.
+  // alpha[slot]: the flush of this ring reads the EARLIER slots only (this iteration's alpha it computes itself), k_cg_xflush runs after this kernel.
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     S[S_RZ0 + (cur ^ 1)] = rz_new;
     S[S_RR] = rr;
+    if (MU != 1) g.alpha[g.slot] = alpha;
     flags_next[F_ITER] = iter;
     flags_next[F_DONE] = done ? 1 : 0;
   }
 }
 
+// End of a pass: the updates of x that the ring still holds -- F_ITER % m of them, slots 0 .. pending - 1 in order -- whichever way the pass ended
+// (a tolerance stop inside a ring, maxiter, the end of a pass before a restart).  Nothing pending: returns at once.
+__global__ __launch_bounds__(MFEM_BLOCK) void k_cg_xflush(int64_t n2, CgRing g, d2_t* __restrict__ x, const int32_t* __restrict__ flags) {
+  const int pending = cg_ring_pending(flags[F_ITER], g.m);
+  if (pending == 0) return;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n2; i += stride) {
+    d2_t xv = x[i];
+    for (int k = 0; k < pending; ++k) xv = cg_axpy(g.alpha[k], cg_ring_ptr(g, n2, k)[i], xv);
+    x[i] = xv;
+  }
+}
+
 int mfem_cg_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovVecs& V, const mfem_solve_options* o, int, double tol, int64_t n_global,
                  int* iters_out, int* spmv_out) {
-  // V.x (current iterate), V.b ; work: r, p, Ap, dinv
+  // V.x (current iterate), V.b ; work: r, p (slot 0 of the ring of directions), Ap, slots 1 .. m - 1 of the ring ; dinv
   double* S = ctx->d_scalars;
   int32_t* F = ctx->d_flags;
   double* r = V.w[0];
   double* p = V.w[1];
   double* Ap = V.w[2];
+  const int m = V.cg_ring > 1 ? V.cg_ring : 1;  // (cg_decide.h; the driver has carved w[3 .. m + 1] one vector apart)
+  CgRing ring{(d2_t*)p, m > 1 ? (d2_t*)V.w[3] : nullptr, S + S_CG_RING_ALPHA, m, 0};
+  auto slot_ptr = [&](int k) -> double* { return k == 0 ? p : V.w[3] + (int64_t)(k - 1) * V.nv; };
   const double* dinv = V.dinv;
   const int64_t nv = V.nv;
   CgArgs a;
@@ -234,7 +326,9 @@ int mfem_cg_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovV
   uint64_t key = mfem_pass_key(MFEM_SOLVER_CG, A, vals, V, tol, n_global, o);
   key = mfem_hash(key, dinv); key = mfem_hash(key, a.zrec); key = mfem_hash(key, V.cg_s); key = mfem_hash(key, a.smax2); key = mfem_hash(key, a.gate2);
   const bool lat_fused = mfem_lat27_cg_fused(ctx, A, vals);  // (lattice tiles of the hex-27 matrix, one rank: pass 2 inside the residual update)
-  key = mfem_hash(key, (int)lat_fused);
+  key = mfem_hash(key, (int)lat_fused); key = mfem_hash(key, m);
+  const int unit = cg_ring_unit(m);
+  if (m > 1) ++g_cg_ring_passes;
   int it = 0;
   // flag banks: iteration `it` reads bank it & 1 (k_cg_init_fin fills bank 0) and leaves the next state in the other one
   for (;;) {
@@ -245,10 +339,29 @@ int mfem_cg_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovV
     }
     const int burst = (o->maxiter - it) < check ? (o->maxiter - it) : check;
     if (burst <= 0) break;
+    // k_cg_pupdate by streaming mode and ring depth (MU: 1 no ring, 8 / 16 unrolled, 0 any other depth)
+#define CG_PUPDATE_NM(NT_, MU_, PAP_, NP1_, NP2_) hipLaunchKernelGGL((k_cg_pupdate<NT_, MU_>), dim3(G), dim3(MFEM_BLOCK), 0, ctx->stream, a, cur, PAP_, NP1_, part2, \
+                                                                     NP2_, (const d2_t*)r, (const d2_t*)dinv, g, (d2_t*)V.x, S, F, Fn)
+#define CG_PUPDATE_N(NT_, PAP_, NP1_, NP2_)                                      \
+  do {                                                                           \
+    if (m == 1) CG_PUPDATE_NM(NT_, 1, PAP_, NP1_, NP2_);                         \
+    else if (m == 8) CG_PUPDATE_NM(NT_, 8, PAP_, NP1_, NP2_);                    \
+    else if (m == 16) CG_PUPDATE_NM(NT_, 16, PAP_, NP1_, NP2_);                  \
+    else CG_PUPDATE_NM(NT_, 0, PAP_, NP1_, NP2_);                                \
+  } while (0)
+#define CG_PUPDATE(PAP_, NP1_, NP2_)                                             \
+  do {                                                                           \
+    if (nt == 1) CG_PUPDATE_N(1, PAP_, NP1_, NP2_);                              \
+    else if (nt == 2) CG_PUPDATE_N(2, PAP_, NP1_, NP2_);                         \
+    else CG_PUPDATE_N(0, PAP_, NP1_, NP2_);                                      \
+  } while (0)
     auto iteration = [&](int it_) -> int {
       const int cur = it_ & 1;
       int32_t* F = ctx->d_flags + 4 * cur;          // this iteration's bank
       int32_t* Fn = ctx->d_flags + 4 * (cur ^ 1);   // the next one's
+      CgRing g = ring;
+      g.slot = cg_ring_slot(it_, m);
+      double* p = slot_ptr(g.slot);  // this iteration's direction
       int np1 = 0;
       // with a communicator: the exchange of p's boundary planes runs beside the rows that need no ghost entry, and every
       // reduction group is one fold kernel + one all-reduce
@@ -262,10 +375,7 @@ int mfem_cg_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovV
         const LatCgUpdate U{a.zrec, cur, (const double*)a.sw, a.smax2, a.gate2, a.n_inv, dinv, r, S, F, part2, tp, npt};
         rc = mfem_lat27_gather_cg_update(ctx, A, U, G);
         if (rc) return rc;
-#define CG_PUPDATE_F(NT_) hipLaunchKernelGGL(k_cg_pupdate<NT_>, dim3(G), dim3(MFEM_BLOCK), 0, ctx->stream, a, cur, tp, npt, part2, G, (const d2_t*)r, \
-                                             (const d2_t*)dinv, (d2_t*)p, (d2_t*)V.x, S, F, Fn)
-        if (nt == 1) CG_PUPDATE_F(1); else if (nt == 2) CG_PUPDATE_F(2); else CG_PUPDATE_F(0);
-#undef CG_PUPDATE_F
+        CG_PUPDATE(tp, npt, G);
         MFEM_CHECK_LAUNCH();
         return MFEM_OK;
       }
@@ -291,20 +401,27 @@ int mfem_cg_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovV
         if (rc) return rc;
         np2 = 0;
       }
-#define CG_PUPDATE(NT_) hipLaunchKernelGGL(k_cg_pupdate<NT_>, dim3(G), dim3(MFEM_BLOCK), 0, ctx->stream, a, cur, part1, np1, part2, np2, (const d2_t*)r, \
-                                           (const d2_t*)dinv, (d2_t*)p, (d2_t*)V.x, S, F, Fn)
-      if (nt == 1) CG_PUPDATE(1); else if (nt == 2) CG_PUPDATE(2); else CG_PUPDATE(0);
-#undef CG_PUPDATE
+      CG_PUPDATE(part1, np1, np2);
       MFEM_CHECK_LAUNCH();
       return MFEM_OK;
     };
-    // iterations alternate between two scalar slots (cur = it & 1): an even/odd PAIR has constant arguments and is the
-    // unit that is captured and replayed (mfem_cycle_run); a trailing odd iteration is launched directly
+#undef CG_PUPDATE
+#undef CG_PUPDATE_N
+#undef CG_PUPDATE_NM
+    // iterations alternate between two scalar slots (cur = it & 1) and walk the m slots of the ring: `unit` of them (cg_ring_unit; the even/odd PAIR
+    // with m = 1) have constant arguments and are what is captured and replayed (mfem_cycle_run), starting at it % unit == 0; iterations after whole
+    // units -- and, with a ring, those of a burst in front of them -- are launched directly with their own bank, slot and position
     int k = 0;
-    for (; k + 2 <= burst && (it & 1) == 0; k += 2, it += 2) {
+    if (m > 1)
+      for (; k < burst && it % unit != 0; ++k, ++it) {
+        rc = iteration(it);
+        if (rc) return rc;
+      }
+    for (; k + unit <= burst && it % unit == 0; k += unit, it += unit) {
       rc = mfem_cycle_run(ctx, key, [&]() -> int {
-        int r2 = iteration(0);
-        return r2 ? r2 : iteration(1);
+        int r2 = MFEM_OK;
+        for (int j = 0; j < unit && !r2; ++j) r2 = iteration(j);
+        return r2;
       });
       if (rc) return rc;
     }
@@ -312,6 +429,10 @@ int mfem_cg_pass(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, KrylovV
       rc = iteration(it);
       if (rc) return rc;
     }
+  }
+  if (m > 1) {  // (m = 1: nothing is ever pending)
+    hipLaunchKernelGGL(k_cg_xflush, dim3(G), dim3(MFEM_BLOCK), 0, ctx->stream, a.n2, ring, (d2_t*)V.x, (const int32_t*)(ctx->d_flags + 4 * (it & 1)));
+    MFEM_CHECK_LAUNCH();
   }
   rc = mfem_read_flags(ctx);
   if (rc) return rc;
