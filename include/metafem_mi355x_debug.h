@@ -24,6 +24,14 @@ extern "C" {
 int64_t mfem_debug_sym_spmv_count(void);
 /* binds of the patch sweep whose symmetry verdict came from the fingerprint the fill pass sums (round 6) instead of the separate check pass (process-wide) */
 long long mfem_debug_symp_fingerprint_count(void);
+/* binds that ended on the patch sweep with the coded-diagonal form of its copy (csrc/spmv_symp.h; process-wide): the scaled CG's binds unless bit 21 of
+ * the "ell" knob forces the stored form or the fill's gate met a diagonal without a code */
+long long mfem_debug_symp_coded_count(void);
+/* One product y = alpha (S^-1 A S^-1) x + beta y on the row layout bound as the scaled CG (cg_variant 4) binds it, ssym = 1 / S [device, n (+ ghosts)] folded
+ * into the copy, with the fused dotw . y (dotw null: none): the per-workgroup partial sums go to partials_out [host, cap], their count to *n_partials.
+ * *form: -1 the bind did not end on the patch sweep, 0 / 1 the copy's diagonal is stored / coded.  Nothing stays bound.  tests/test_gpu_symp_diag_code.py */
+int mfem_debug_spmv_scaled_layout(mfem_context ctx, mfem_csr A, const double* vals, const double* ssym, const double* x, double* y, double alpha, double beta,
+                                  const double* dotw, double* partials_out /* [host] */, int32_t cap, int32_t* n_partials /* [host] */, int32_t* form /* [host] */);
 /* THE tuning knobs: one entry point (round 6; until round 5 one function per knob).  Process-wide state read at launch time: set only while no call is
  * in flight on any context; every call bumps the epoch that is part of the cycle-graph cache key.  No knob changes results beyond round-off.  Keys and
  * the meaning of (a, b) are documented where the knobs are described below (lines marked `^ key "..."`); an unknown key returns MFEM_ERR_INVALID. */
@@ -36,7 +44,8 @@ int mfem_debug_set(const char* key, int64_t a, int64_t b);
  * created), persistent workgroups per CU. */
 /* ^ key "spmv": mfem_debug_set("spmv", a, b) with (int xcd_aware, int grid_mult) = (a[, b]) */
 /* modes 1/2: bit 0 on/off; bit 1 never use diagonal slots; bits 8-15 workgroups per CU of the per-row kernels; bits 16-19: the value 8 = the
- * diagonal-slotted per-row kernel without the shared x loads of consecutive diagonals (and no sweep); bit 20 XCD-contiguous row chunks; bit 22
+ * diagonal-slotted per-row kernel without the shared x loads of consecutive diagonals (and no sweep); bit 20 XCD-contiguous row chunks; bit 21
+ * the patch-major copy of the scaled CG keeps its diagonal as stored doubles instead of one-byte ulp codes (mfem_symp_coded_wanted; same results bit for bit); bit 22
  * symmetric sweep kernels off; bit 23 the workgroup-tile sweep (k_spmv_sym27) instead of the wave-private patch sweep (k_spmv_symp); bit 26 rows
  * outside the swept planes in a launch of their own; bit 27 the patch-major copy made from the slot-major copy in a second pass; bit 28 the layout
  * copy without its software pipeline; bit 29 the swept rows by the copy's row tiles instead of k_symp_fill; bit 30 the symmetry of the swept rows

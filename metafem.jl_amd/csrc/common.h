@@ -96,7 +96,7 @@ struct mfem_context_s {
   double* d_partials;   // [MFEM_MAX_PARTIALS * 8]
   double* d_scalars;    // [256] device-resident Krylov scalars
   double* h_scalars;    // pinned, [256]
-  int32_t* d_flags;     // [24] device flags (16-17: the symmetry fingerprint of k_symp_fill, 64 bits): 0-7 the Krylov loop's two banks (done, iteration count, ...); 9 mirrored-sweep check; 10 ring self-test; 11 mesh
+  int32_t* d_flags;     // [24] device flags (16-17: the symmetry fingerprint of k_symp_fill, 64 bits; 18: its coded-diagonal gate, 19: the codes' unit is -1.0): 0-7 the Krylov loop's two banks (done, iteration count, ...); 9 mirrored-sweep check; 10 ring self-test; 11 mesh
                         // assembly; 12-15 one-shot statistics, each user clears the slots it reads before its launch and synchronises after it (layout binds:
                         // 12-13 max |a| / symmetry measure, krylov.hip (try_scaled_cg): 12-15 extremes of S, assemble_hex27.hip: 14 count of non-affine elements)
   int32_t* h_flags;     // pinned
@@ -197,6 +197,9 @@ struct mfem_csr_s {
   int symp_p0, symp_p1;     // regular lattice planes [p0, p1) (plane = row / PL): the rows the sweep computes
   int symp_NS, symp_NPk;    // strips of 4 lines, patches of 32 points per line
   int symp_B;               // bands (strips) per patch of the bound patch-major copy: decided once per bind (dia_bind), 0 while none is bound
+  int symp_DC;              // form of the bound patch-major copy's main part (spmv_symp.h): 1 = the diagonal as one-byte codes (mfem_symp_coded_wanted), 0 stored / none bound
+  int symp_dneg;            // symp_DC = 1: the codes count from -1.0 (the first swept row's diagonal is negative), not from +1.0
+  int symp_dc_last;         // symp_DC of the last bind that ended on the patch sweep (the byte accounting of an unbound pattern answers for that bind)
   double* symp_vals;        // not owned (solver workspace, behind ell_vals): [plane - p0][patch][27 x 128 + edge block]; set while dia_kernel is the patch sweep
   // solver layout mode 3 for rows of uneven length: the row-sorted sliced layout (spmv_sell.hip) or its node-blocked form (spmv_bsell.hip) -- sell.form
   // tells which, and each form has its own members; sell.state 0 = not planned, -1 = no, 1 = ready.  The record and the decisions: sell_decide.h

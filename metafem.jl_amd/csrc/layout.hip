@@ -214,3 +214,34 @@ extern "C" int mfem_spmv_solver_layout_dot(mfem_context ctx, mfem_csr A, const d
   MFEM_REQUIRE(xdoty, "null argument");
   return spmv_solver_layout(ctx, A, vals, x, y, alpha, beta, xdoty);
 } MFEM_API_CATCH("mfem_spmv_solver_layout_dot")
+
+// TEST / DIAGNOSTIC entry point: one product y = alpha (S^-1 A S^-1) x + beta y on the row layout bound the way the scaled CG (cg_variant 4) binds it --
+// the symmetric scaling ssym = 1 / S folded into the copy -- with the fused dotw . y: its per-workgroup partial sums (at most `cap`) go to
+// partials_out, their count to *n_partials.  *form: -1 the bind did not end on the patch sweep, 0 / 1 its copy carries the diagonal stored / as one-byte
+// codes (spmv_symp.h; bit 21 of the "ell" knob forces the stored form).  Nothing stays bound.
+extern "C" int mfem_debug_spmv_scaled_layout(mfem_context ctx, mfem_csr A, const double* vals, const double* ssym, const double* x, double* y, double alpha,
+                                             double beta, const double* dotw, double* partials_out, int32_t cap, int32_t* n_partials, int32_t* form) try {
+  MFEM_REQUIRE(ctx && A && vals && ssym && x && y && form, "null argument");
+  *form = -1;
+  if (n_partials) *n_partials = 0;
+  struct Release { mfem_csr_s* A; ~Release() { mfem_layout_unbind(A); } } release{A};
+  mfem_layout_plan_s P;
+  int rc = mfem_layout_plan(ctx, A, true, false, &P);
+  if (rc) return rc;
+  MFEM_REQUIRE(P.rows == MFEM_LAYOUT_DIA, "the pattern has no diagonal-slotted layout");
+  rc = mfem_ws_reserve(ctx, P.rows_bytes);
+  if (!rc) rc = mfem_layout_bind(ctx, A, P.rows, vals, (double*)ctx->ws, nullptr, ssym, nullptr, false);
+  if (rc) return rc;
+  MFEM_REQUIRE(mfem_layout_bound(A, vals) == MFEM_LAYOUT_DIA, "the layout was not bound");
+  if (A->symp_vals) *form = A->symp_DC;
+  int np = 0;
+  rc = mfem_spmv_launch(ctx, A, vals, x, y, alpha, beta, dotw, dotw ? ctx->d_partials : nullptr, &np, nullptr);
+  if (rc) return rc;
+  if (dotw && partials_out) {
+    MFEM_REQUIRE(np > 0 && np <= MFEM_MAX_PARTIALS && np <= cap, "partial sums: none, or more than the caller's buffer holds");
+    MFEM_CHECK_HIP(hipMemcpyAsync(partials_out, ctx->d_partials, sizeof(double) * (size_t)np, hipMemcpyDeviceToHost, ctx->stream));
+    if (n_partials) *n_partials = np;
+  }
+  MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  return MFEM_OK;
+} MFEM_API_CATCH("mfem_debug_spmv_scaled_layout")

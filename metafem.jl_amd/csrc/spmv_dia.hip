@@ -292,14 +292,22 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_dia_vals(int64_t n, int64_t npad
 // runs (scalar loads), then the 27 values + the 27 factors of the symmetric scaling per lane, all issued before the first wait; tiles with short rows (lattice edge)
 // or missing lines / columns take the general path: per-lane row pointers, masked staging, the short rows' columns decoded into slots (offset = di PL + dj m2 + dk,
 // guaranteed by dia_lattice_class below) and every row expanded to its 27 slots in LDS.
-template <typename RP, bool SYM>
+// DC (with SYM; Gm.DC): the coded-diagonal form of the main part (spmv_symp.h) -- slots 14..26 per band, and the scaled diagonal a_ii * (t_i * t_i) as the signed
+// byte bits(v) - bits(1.0) in the step's code block, gathered in LDS like the edge block and written as one aligned piece (cells outside the lattice: code 0).  A
+// swept row whose diagonal is further than 127 ulps from the unit (the other sign, zero, absent, non-finite) raises dcbad[0]: the bind then refills in the stored
+// form.  The unit is +1.0 or, with dcbad[1] set (k_symp_diag_sign: the first swept row's diagonal is negative -- the thermal K is negative definite), -1.0.  The
+// slot-major copy gets the diagonal as a double either way (k_ell_diag, the rows outside the swept planes).
+template <typename RP, bool SYM, bool DC = false>
 __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                     const double* __restrict__ vals, int base, const DiaOffsets* __restrict__ Op, int cls,
                                                     double* __restrict__ out, SympGeom Gm, double* __restrict__ pv, const double* __restrict__ ssym,
-                                                    unsigned long long* __restrict__ fp) {
+                                                    unsigned long long* __restrict__ fp, int32_t* __restrict__ dcbad) {
   const DiaOffsets& O = *Op;
   extern __shared__ double lds[];
   constexpr int RUN = SP_W * 27;  // entries of a full 32-row run
+  constexpr int NSL = sp_nslots(DC), S0 = 27 - NSL;  // the main part holds slots S0..26 of every band
+  int nocode = 0;
+  const long long unit = sp_unit_bits(DC ? dcbad[1] : 0);
   // Symmetry fingerprint (round 6; fp != nullptr): are the values this pass WRITES bitwise symmetric among the swept rows?  Every stored entry (r, c), c != r,
   // both rows swept, adds  sign(c - r) * m(min, max) * bits(v)  to a 64-bit sum in wrap-around arithmetic, m a 64-bit hash of the unordered pair.  A
   // symmetric copy cancels pair by pair -- exactly, in any order (integer sums commute: no atomics on doubles, no second pass); a copy with v_rc != v_cr
@@ -311,7 +319,8 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (launched with two waves per workgroup)
   double* T = lds + (size_t)w * (2 * RUN);
   double* E = lds + 2 * (2 * RUN);  // the step's edge block (SP_EPAD entries; zero between steps: entries of rows outside the lattice and the padding stay 0)
-  const int spNP = Gm.NR * Gm.NPk, spB = Gm.B, spMAIN = sp_main(spB), spLOW = sp_low(spB), spEPAD = sp_epad(spB);
+  const int spNP = Gm.NR * Gm.NPk, spB = Gm.B, spMAIN = sp_main(spB, DC), spLOW = sp_low(spB), spEPAD = sp_epad(spB);
+  signed char* const Cb = reinterpret_cast<signed char*>(E + spEPAD);  // DC: the step's code block (spB * SP_ROWS bytes; zero between steps)
   const int64_t spT = (int64_t)spNP * (Gm.p1 - Gm.p0);
   const int h = lane >> 5, c = lane & (SP_W - 1);
   const int32_t PL = (int32_t)Gm.PL, m2 = Gm.m2;
@@ -319,13 +328,13 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
     const uint32_t xl = __builtin_amdgcn_readfirstlane((uint32_t)(uint64_t)x), xh = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
     return (int64_t)(((uint64_t)xh << 32) | xl);
   };
-  for (int i = threadIdx.x; i < spEPAD; i += 128) E[i] = 0.0;
+  for (int i = threadIdx.x; i < spEPAD + sp_cpad(spB, DC); i += 128) E[i] = 0.0;  // (the code block lies behind E: all-zero bytes)
   __syncthreads();
   for (int64_t step = blockIdx.x; step < spT; step += gridDim.x) {  // (every barrier below is reached by both waves: the trip count is the workgroup's)
     const int kp = (int)(step % Gm.NPk);
     const int64_t q = step / Gm.NPk;
     const int prow = (int)(q % Gm.NR), pl = (int)(q / Gm.NR);
-    double* const pe = pv + step * spMAIN + spB * 14 * SP_ROWS;
+    double* const pe = pv + step * spMAIN + spB * NSL * SP_ROWS;
     for (int band = 0; band < spB; ++band) {  // the strips of the patch one after the other: their edge entries meet in E (a strip past the lattice: nlines = 0)
     const int strip = prow * spB + band;
     const int jj0 = strip * SP_L + 2 * w, kk0 = kp * SP_W;
@@ -341,7 +350,7 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
     const bool valid = c < ncol && h < nlines;
     const int64_t r = rb + (int64_t)h * m2 + c;
     const int line = 2 * w + h;
-    double* const pm = pv + step * spMAIN + band * 14 * SP_ROWS + line * SP_W + c;
+    double* const pm = pv + step * spMAIN + band * NSL * SP_ROWS + line * SP_W + c;
     double* const plo = pv + spT * spMAIN + step * spLOW + band * 13 * SP_ROWS + line * SP_W + c;
     const double* Tr = T + lane * 27;
     double sc[27];
@@ -448,20 +457,28 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
           const int e = sp_edge_of(sl, band * SP_L + line, c, spB);
           if (e >= 0) E[e] = v;
         } else {
-          DIA_ST(pm + (sl - 13) * SP_ROWS, v);
-          if (sl == 13) DIA_ST(out + ell_base(r, K) + 13 * ELL_B, v);  // the diagonal also to the slot-major copy (k_ell_diag reads it there)
+          if (sl >= S0) DIA_ST(pm + (sl - S0) * SP_ROWS, v);
+          if (sl == 13) {
+            DIA_ST(out + ell_base(r, K) + 13 * ELL_B, v);  // the diagonal also to the slot-major copy (k_ell_diag reads it there)
+            if constexpr (DC) {
+              int code = 0;
+              if (!sp_diag_code(v, code, unit)) nocode = 1;
+              else Cb[band * SP_ROWS + line * SP_W + c] = (signed char)code;
+            }
+          }
         }
       }
     }
     __builtin_amdgcn_wave_barrier();  // (the wave's staging area is overwritten by its next strip)
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < spEPAD; i += 128) {
+    for (int i = threadIdx.x; i < spEPAD + sp_cpad(spB, DC); i += 128) {  // (DC: the code block follows the edge block in the copy as in LDS)
       DIA_ST(pe + i, E[i]);
       E[i] = 0.0;
     }
     __syncthreads();
   }
+  if (DC && nocode) atomicOr(dcbad, 1);
   if (fp) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) fsum += __shfl_down(fsum, o, MFEM_WAVE);
@@ -530,10 +547,19 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_spmv_dia_outside(int64_t n, int6
   }
 }
 
+// neg[0] = 1 if the stored diagonal of row r is negative (the symmetric scaling multiplies it by a square: the sign of the scaled diagonal)
+template <typename RP>
+__global__ __launch_bounds__(64) void k_symp_diag_sign(int64_t r, const RP* __restrict__ rowptr, const int32_t* __restrict__ col, const double* __restrict__ vals,
+                                                        int base, int32_t* __restrict__ neg) {
+  const int64_t lo = (int64_t)rowptr[r] - base, hi = (int64_t)rowptr[r + 1] - base;
+  for (int64_t j = lo + threadIdx.x; j < hi; j += 64)
+    if ((int64_t)col[j] - base == r && __double_as_longlong(vals[j]) < 0) neg[0] = 1;
+}
+
 // lattice lines of odd length: the lane pair at the line's end holds the last point and a cell outside the lattice, which no row writes
 // and the sweep reads as a structurally absent entry -- an explicit zero in all 27 slots of every step of the last patch column
 __global__ __launch_bounds__(MFEM_BLOCK) void k_symp_zero_odd(SympGeom Gm, double* __restrict__ pv) {
-  const int NP = Gm.NR * Gm.NPk, nplanes = Gm.p1 - Gm.p0, B = Gm.B, MAINB = sp_main(B), LOWB = sp_low(B);
+  const int NP = Gm.NR * Gm.NPk, nplanes = Gm.p1 - Gm.p0, B = Gm.B, MAINB = sp_main(B, Gm.DC), LOWB = sp_low(B), NSL = sp_nslots(Gm.DC);
   const int64_t T = (int64_t)NP * nplanes, cells = (int64_t)nplanes * Gm.NS * SP_L * 27;
   const int col = Gm.m2 - (Gm.NPk - 1) * SP_W;  // first column past the line in the last patch column (odd, < SP_W)
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < cells; t += (int64_t)gridDim.x * blockDim.x) {
@@ -544,7 +570,7 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_symp_zero_odd(SympGeom Gm, doubl
     const int64_t step = (int64_t)pl * NP + (int64_t)(strip / B) * Gm.NPk + (Gm.NPk - 1);
     const int idx = line * SP_W + col;
     if (s < 13) pv[T * MAINB + step * LOWB + band * 13 * SP_ROWS + s * SP_ROWS + idx] = 0.0;
-    else pv[step * MAINB + band * 14 * SP_ROWS + (s - 13) * SP_ROWS + idx] = 0.0;
+    else if (s >= 27 - NSL) pv[step * MAINB + band * NSL * SP_ROWS + (s - (27 - NSL)) * SP_ROWS + idx] = 0.0;  // (coded form: the fill writes every code byte)
   }
 }
 
@@ -683,6 +709,12 @@ int mfem_dia_plan(mfem_context_s* ctx, mfem_csr_s* A) {
 // The copies of a bind: the slot-major copy of `vals` into buf; with pvals the rows of the swept planes G go straight to the patch-major copy there
 // instead -- by k_symp_fill (patch-aligned tiles) where its conditions hold, after k_dia_vals has done the other rows, else by k_dia_vals.
 // *fp_made: the fill left the symmetry fingerprint of the swept rows, asked for with want_fp, in d_flags[16..17].
+// k_symp_fill fills the swept rows of a direct bind: a lane per row (K <= 64), no column scaling pass, 32-bit row arithmetic, lattice lines and planes long
+// enough for its column decoding (bit 29 of the "ell" knob turns it off)
+bool mfem_dia_fill_fast(const mfem_csr_s* A, const double* dsc, bool direct) {
+  return direct && A->symp_state == 1 && 8 * 64 * (size_t)A->ell_K * 2 <= 64 * 1024 && !dsc && A->n < ((int64_t)1 << 31) && A->symp_PL < ((int64_t)1 << 30) &&
+         A->symp_m1 >= 3 && A->symp_m2 >= 3 && g_ell.dia_fast;
+}
 int mfem_dia_copy(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, const double* ssym, const SympGeom& G,
                   double* pvals, bool want_fp, bool* fp_made) {
   const DiaOffsets* O = (const DiaOffsets*)A->dia_dev;
@@ -704,7 +736,7 @@ int mfem_dia_copy(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double
   if (g > ctx->num_cus * 16) g = ctx->num_cus * 16;
   // k_symp_fill: a patch-major copy to fill, no column scaling pass, 32-bit row arithmetic, lattice lines and planes long enough for its column
   // decoding (bit 29 of the "ell" knob turns it off)
-  const bool fast = lpr == 1 && !dsc && pvals && A->n < ((int64_t)1 << 31) && G.PL < ((int64_t)1 << 30) && G.m1 >= 3 && G.m2 >= 3 && g_ell.dia_fast;
+  const bool fast = pvals && mfem_dia_fill_fast(A, dsc, true);
   // the software-pipelined staging: a lane per row, rows of at most 28 entries, no scaling pass (bit 28 turns it off)
   const bool pipe = lpr == 1 && !dsc && A->ell_K <= 28 && g_ell.dia_pipe && !fast;
   const int64_t ft = (int64_t)(G.p1 - G.p0) * G.NR * G.NPk;  // the fill: patch steps, one workgroup of two waves each
@@ -712,6 +744,9 @@ int mfem_dia_copy(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double
   if (gf < 1) gf = 1;
   unsigned long long* fpr = fast && want_fp ? (unsigned long long*)(ctx->d_flags + 16) : nullptr;
   *fp_made = fpr != nullptr;
+  const bool coded = G.DC != 0;  // (decided by the bind, mfem_symp_coded_wanted: only with the fill and the symmetric scaling)
+  if (coded && !(fast && ssym)) return MFEM_ERR_INVALID;
+  int32_t* dcbad = ctx->d_flags + 18;  // beside the fingerprint; [19]: the unit is -1.0
   return mfem_by_rowptr(A, [&](auto t) -> int {
     using RP = decltype(t);
     auto kv = ssym ? k_dia_vals<RP, 1, true, false> : k_dia_vals<RP, 1, false, false>;
@@ -722,9 +757,15 @@ int mfem_dia_copy(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double
     MFEM_CHECK_LAUNCH();
     if (!fast) return MFEM_OK;
     if (fpr) MFEM_CHECK_HIP(hipMemsetAsync(fpr, 0, sizeof(unsigned long long), ctx->stream));
-    const auto kf = ssym ? k_symp_fill<RP, true> : k_symp_fill<RP, false>;
-    hipLaunchKernelGGL(kf, dim3(gf), dim3(128), sizeof(double) * (2 * (2 * SP_W * 27) + sp_epad(G.B > 0 ? G.B : 1)), ctx->stream, A->n, A->ell_K, (const RP*)A->rowptr,
-                       A->colidx, vals, A->index_base, O, A->sym_cls, buf, G, pvals, ssym, fpr);
+    if (coded) {  // the gate's flag, and the sign of the unit the codes count from
+      MFEM_CHECK_HIP(hipMemsetAsync(dcbad, 0, 2 * sizeof(int32_t), ctx->stream));
+      hipLaunchKernelGGL(k_symp_diag_sign<RP>, dim3(1), dim3(64), 0, ctx->stream, (int64_t)G.p0 * G.PL, (const RP*)A->rowptr, A->colidx, vals, A->index_base, dcbad + 1);
+      MFEM_CHECK_LAUNCH();
+    }
+    const auto kf = coded ? k_symp_fill<RP, true, true> : ssym ? k_symp_fill<RP, true> : k_symp_fill<RP, false>;
+    const int fB = G.B > 0 ? G.B : 1;
+    hipLaunchKernelGGL(kf, dim3(gf), dim3(128), sizeof(double) * (2 * (2 * SP_W * 27) + sp_epad(fB) + sp_cpad(fB, G.DC)), ctx->stream, A->n, A->ell_K, (const RP*)A->rowptr,
+                       A->colidx, vals, A->index_base, O, A->sym_cls, buf, G, pvals, ssym, fpr, dcbad);
     MFEM_CHECK_LAUNCH();
     return MFEM_OK;
   });

@@ -36,6 +36,8 @@ struct SympGeom {
   int m1, m2, p0, p1, NS, NPk;
   int nseg;  // runs per patch: a run = one patch swept through nplanes / nseg consecutive planes
   int B, NR; // bands of SP_L lines per patch (1 or 2); patch rows = ceil(NS / B): NR * NPk patches per plane (NS: strips of SP_L lines)
+  int DC;    // form of the copy's main part (spmv_symp.h): 0 the diagonal stored as slot 13, 1 carried as one-byte ulp codes
+  long long unit;  // DC = 1: bits of the unit the codes count from, +1.0 or -1.0 (known once the fill has run: the sweep's launches carry it)
 };
 // the rows outside the swept planes, taken by the sweep's waves after their runs (unsplit SpMV): per-row code on the slot-major copy
 struct SympTail {
@@ -175,6 +177,7 @@ struct EllKnobs {
   std::atomic<int> grid_mult{6};         // bits 8-15 (0 keeps the value): persistent workgroups per CU of the per-row kernels (profiles/r01_spmv_sweep.txt: 6 or 8)
   std::atomic<int> shared_x{1};          // bits 16-19 = 8 clears it: the plain per-row kernel without the shared x loads of three consecutive diagonals, no sweep
   std::atomic<int> xcd{0};               // bit 20: each XCD walks a contiguous eighth of the rows (k_spmv_dia; needs a grid that is a multiple of 8)
+  std::atomic<int> symp_coded{1};        // bit 21 clears it: the scaled CG's patch-major copy keeps its diagonal as stored doubles (mfem_symp_coded_wanted)
   std::atomic<int> sym{1};               // bit 22 clears it: no symmetric sweep kernel
   std::atomic<int> symp{1};              // bit 23 clears it: the workgroup-tile sweep (k_spmv_sym27) instead of the wave-private patch sweep (k_spmv_symp)
   std::atomic<int> symp_bands{0};        // bits 24 / 25 force one / two bands of four lines per patch (0: mfem_symp_bands_wanted decides by size)
@@ -206,6 +209,12 @@ SympGeom mfem_symp_geom(const mfem_context_s* ctx, const mfem_csr_s* A);
 int64_t mfem_symp_steps(const mfem_csr_s* A, int B = 0);  // patch steps of the swept planes with B bands per patch (0: mfem_symp_bands)
 int mfem_symp_bands_wanted(const mfem_csr_s* A);  // the band count a bind of the patch sweep would take now
 int mfem_symp_bands(const mfem_csr_s* A);         // the bound copy's band count; unbound: what a bind would take
+// THE decision which form the main part of a patch-major copy gets (spmv_symp.h): 1 = the diagonal as one-byte ulp codes -- only where the copy is
+// filled by k_symp_fill (`fast`: mfem_dia_fill_fast) with the symmetric scaling, whose diagonal is a_ii * (t_i * t_i) = 1.0 up to a few roundings
+int mfem_symp_coded_wanted(DiaKernel k, bool fast, const double* ssym);
+int mfem_symp_coded(const mfem_csr_s* A);         // the bound copy's form; unbound: the last patch-sweep bind's (0 before any)
+bool mfem_dia_fill_fast(const mfem_csr_s* A, const double* dsc, bool direct);  // spmv_dia.hip: would k_symp_fill fill the swept rows of a bind?
 int64_t mfem_sym_entries(const mfem_context_s* ctx, const mfem_csr_s* A, DiaKernel k);
-int mfem_sym_verdict(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const double* buf, double* pvals, const SympGeom& G, bool direct, bool fp_made, bool* ok);
+int mfem_sym_verdict(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const double* buf, double* pvals, const SympGeom& G, bool direct, bool fp_made, bool* ok,
+                     bool* dc_refused, int* dneg);
 int mfem_sym_launch(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const SpmvArgs& a);

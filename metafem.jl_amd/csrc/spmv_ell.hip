@@ -44,6 +44,7 @@ extern "C" int mfem_debug_set_ell(int enable) try {
   if ((enable >> 8) & 255) g_ell.grid_mult = (enable >> 8) & 255;
   g_ell.shared_x = ((enable >> 16) & 15) == 8 ? 0 : 1;
   g_ell.xcd = (enable >> 20) & 1;
+  g_ell.symp_coded = ((enable >> 21) & 1) ? 0 : 1;
   g_ell.sym = ((enable >> 22) & 1) ? 0 : 1;
   g_ell.symp = ((enable >> 23) & 1) ? 0 : 1;
   g_ell.symp_bands = ((enable >> 24) & 1) ? 1 : ((enable >> 25) & 1) ? 2 : 0;
@@ -285,6 +286,13 @@ int mfem_symp_bands_wanted(const mfem_csr_s* A) {
   return A->symp_state == 1 && (int64_t)(A->symp_p1 - A->symp_p0) * A->symp_PL >= SYMP_BANDS2_MIN_ROWS ? 2 : 1;
 }
 int mfem_symp_bands(const mfem_csr_s* A) { return A->symp_B ? A->symp_B : mfem_symp_bands_wanted(A); }
+// Form of the diagonal in the patch-major copy, decided here once per bind.  Coded (one signed byte per row instead of a double: 0.95 of the 19.7 GB a 512^3
+// product streams) where the fill writes S^-1 A S^-1 itself -- the values of every other bind have an arbitrary diagonal.  Measured:
+// profiles/r09_symp_diag_code_ab_512.txt.  The fill's gate (a diagonal without a code) sends a bind back to the stored form: dia_bind.
+int mfem_symp_coded_wanted(DiaKernel k, bool fast, const double* ssym) { return k == DIA_SYMP && fast && ssym && g_ell.symp_coded ? 1 : 0; }
+int mfem_symp_coded(const mfem_csr_s* A) { return A->symp_vals ? A->symp_DC : A->symp_dc_last; }
+static std::atomic<long long> g_symp_coded_binds{0};  // binds that ended on the patch sweep with the coded form (tests, the A/B)
+extern "C" long long mfem_debug_symp_coded_count(void) { return g_symp_coded_binds; }
 size_t mfem_ell_vals_bytes(const mfem_csr_s* A) {
   if (A->ell_state != 1 || !g_ell.enable) return 0;
   const bool dia = mfem_dia_layout_planned(A);
@@ -303,13 +311,22 @@ static int dia_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, doub
   bool direct = false, fp_made = false;
   DiaKernel k = mfem_dia_kernel_wanted(A, DIA_NONE, &direct);
   A->symp_B = mfem_symp_bands_wanted(A);  // (A is unbound here: the geometry below is this count's)
+  A->symp_DC = mfem_symp_coded_wanted(k, mfem_dia_fill_fast(A, dsc, direct), ssym);
+  A->symp_dneg = 0;
   double* pvals = buf + (size_t)A->ell_K * (size_t)A->ell_npad;
-  const SympGeom G = k == DIA_SYMP ? mfem_symp_geom(ctx, A) : SympGeom{};
+  SympGeom G = k == DIA_SYMP ? mfem_symp_geom(ctx, A) : SympGeom{};
   int rc = mfem_dia_copy(ctx, A, vals, buf, dsc, ssym, G, direct ? pvals : nullptr, g_ell.symp_fingerprint != 0, &fp_made);
   while (!rc && (k == DIA_SYMP || k == DIA_SYM27)) {  // a sweep: are the pairs it mirrors bitwise equal?
-    bool ok = false;
-    rc = mfem_sym_verdict(ctx, A, k, buf, pvals, G, direct, fp_made, &ok);
-    if (rc || ok) break;
+    bool ok = false, dc_refused = false;
+    rc = mfem_sym_verdict(ctx, A, k, buf, pvals, G, direct, fp_made, &ok, &dc_refused, &A->symp_dneg);
+    if (rc) break;
+    if (dc_refused) {  // a swept row's scaled diagonal has no code: the same copy in the stored form, and its verdict
+      A->symp_DC = 0;
+      G = mfem_symp_geom(ctx, A);
+      rc = mfem_dia_copy(ctx, A, vals, buf, dsc, ssym, G, pvals, g_ell.symp_fingerprint != 0, &fp_made);
+      continue;
+    }
+    if (ok) break;
     // the other kernels read all rows from the slot-major copy: after a direct fill the swept rows go there now
     if (k == DIA_SYMP && direct) rc = mfem_dia_copy(ctx, A, vals, buf, dsc, ssym, SympGeom{}, nullptr, false, &fp_made);
     k = mfem_dia_kernel_wanted(A, k);
@@ -320,7 +337,12 @@ static int dia_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, doub
   A->ell_bound_mode = 2;
   A->dia_kernel = k;
   A->symp_vals = k == DIA_SYMP ? pvals : nullptr;
-  if (k != DIA_SYMP) A->symp_B = 0;
+  if (k != DIA_SYMP) A->symp_B = A->symp_DC = 0;
+  if (!A->symp_DC) A->symp_dneg = 0;
+  if (k == DIA_SYMP) {  // (the byte accounting of the unbound pattern answers for this bind)
+    A->symp_dc_last = A->symp_DC;
+    if (A->symp_DC) ++g_symp_coded_binds;
+  }
   return MFEM_OK;
 }
 
@@ -351,7 +373,7 @@ void mfem_ell_unbind(mfem_csr_s* A) {
   A->ell_bound_mode = A->dia_kernel = DIA_NONE;
   A->ell_vals = A->symp_vals = nullptr;
   A->ell_src = nullptr;
-  A->symp_B = 0;
+  A->symp_B = A->symp_DC = A->symp_dneg = 0;
 }
 void mfem_ell_free(mfem_csr_s* A) {
   if (A->ell_cols) hipFree(A->ell_cols);

@@ -185,7 +185,7 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_sym27_check(int K, const DiaOffs
 // in flight.  Here a WAVE owns a (j, k) patch of 4 lattice lines x 32 points (lane <-> two neighbouring points of one line) and
 // sweeps it through consecutive lattice planes with no workgroup barrier at all:
 //   * the matrix values of the swept planes live in a patch-major copy, made when the solve binds its values (k_symp_fill, spmv_dia.hip; k_symp_bind): what every
-//     step reads -- slots 13..26 and the edge block, 16.9 KB -- contiguous per step [plane][patch], the lower slots (read where a run
+//     step reads -- slots 13..26 and the edge block, 16.9 KB (coded diagonal, below: slots 14..26, the edge block and a byte per row) -- contiguous per step [plane][patch], the lower slots (read where a run
 //     starts and by the symmetry check) behind;
 //   * the upper diagonals of a step go to the wave's LDS block when they are loaded: +z / +y (slots 14..17) for the rows behind
 //     them in this plane, the nine next-plane diagonals (18..26) for the same patch one plane on -- 10.5 of the 13 lower
@@ -207,6 +207,17 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_sym27_check(int K, const DiaOffs
 //     plane as two sub-steps of the same step body.  The nine halo lines of 32 cells dominate the edge block (9 W + 6 (L - 1) + 3 L entries), so per 256
 //     rows it falls from 2 x 318 to 354 entries and the x neighbourhood from 2 x 6 x 34 to 10 x 34: 3968 instead of 4224 matrix doubles, at 41.2 KB of
 //     LDS per wave (three resident one-wave workgroups per CU instead of seven).  Same lane <-> row mapping, products and slot order: y is the same bit for bit.
+//   * Coded diagonal (k_spmv_symp<MODE, B, DC>, DC = 1; the form is decided per bind, mfem_symp_coded_wanted): the copy k_symp_fill makes for the scaled CG holds
+//     S^-1 A S^-1, whose diagonal a_ii * (t_i * t_i), t_i = 1 / sqrt|a_ii|, is +-1.0 up to a few roundings (codes -4 .. +2 on the thermal matrices; the sign is
+//     the matrix's: the thermal K is negative definite).  Slot 13 then costs 8 of the 15.5 matrix doubles-equivalents a row streams for almost no information, so
+//     the main part carries 13 slots per band and, behind the edge block, one signed byte per row: bits(v) - bits(unit), unit = +-1.0 with the sign of the first
+//     swept row's diagonal (spmv_symp.h; 3744 instead of 3968 doubles per step for B = 2).  A lane's two codes are one 2-byte load requested with its band's main
+//     part a plane ahead and kept in one VGPR; the sweep rebuilds v = bits^-1(unit + code) and multiplies and adds it where the stored slot stood: y, the partial
+//     sums and every iterate are the stored form's bit for bit (tests/test_gpu_symp_diag_code.py).  The fill raises a flag beside its fingerprint when a swept
+//     row's diagonal has no code (the other sign, zero, non-finite: more than 127 ulps from the unit) and the bind refills in the stored form (dia_bind): only
+//     the speed depends on the gate.  MODE 1 does not use the diagonal and only follows the layout; the tail rows, k_symp_bind and k_dia_vals keep the stored
+//     form.  512^3: 3.62 -> 3.45 ms per launch, 256^3 (B = 1): 0.543 -> 0.518 ms (profiles/r09_symp_diag_code_ab_512.txt); 256 VGPRs + 138 AGPRs, no scratch,
+//     41.2 KB of LDS as before.
 //   * Rows outside the swept planes (first / last lattice plane, the planes next to the ghost planes of a slab) come from the slot-major
 //     copy through the per-row code: the sweep's waves take them in 128-row units after their runs (unsplit SpMV: one launch, no tail);
 //     in a split (multi-rank) SpMV they are the boundary part, a launch of their own (k_spmv_dia_outside) after the halo has arrived.
@@ -235,13 +246,15 @@ static int symp_upload_tables(int device) {  // __constant__ data is per device
 // band): the tables, the x ring and the edge block cover all SP_L * B lines, so band 1 finds band 0's +y entries of this plane (slots 9..11) and
 // its next-plane entries of the previous plane (slots 0..2) in the tables -- the latter because band 0 holds its writes to the tables of slots 0..2 back
 // until the last band of the plane has read them.  A band with no valid line (the last patch row) is skipped wave-uniformly.
-template <int MODE, int B>
+// DC: form of the copy's main part (spmv_symp.h) -- 0 the diagonal stored as slot 13, 1 carried as one-byte codes counted from Gm.unit.
+template <int MODE, int B, int DC>
 __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __restrict__ pv, const double* __restrict__ x,
                                                    double* __restrict__ y, double alpha, double beta,
                                                    const double* __restrict__ dotw, double* __restrict__ partials,
                                                    const int32_t* __restrict__ done_flag, int32_t* __restrict__ bad, SympTail tail) {
-  constexpr int XL = sp_xl(B), XN = sp_xn(B), XU = sp_xu(B), NE = sp_ne(B), EU = sp_eu(B), MAINB = sp_main(B), LOWB = sp_low(B);
-  constexpr int BM = 14 * SP_ROWS, BL = 13 * SP_ROWS, BT = SP_L * SP_LS;  // a band's share of the main part, of the low part, of a table
+  constexpr int XL = sp_xl(B), XN = sp_xn(B), XU = sp_xu(B), NE = sp_ne(B), EU = sp_eu(B), MAINB = sp_main(B, DC), LOWB = sp_low(B);
+  constexpr int NSL = sp_nslots(DC), S0 = 27 - NSL;  // slots S0..26 of a band are stored in its main part (DC = 1: the diagonal comes as a code)
+  constexpr int BM = NSL * SP_ROWS, BL = 13 * SP_ROWS, BT = SP_L * SP_LS;  // a band's share of the main part, of the low part, of a table
   __shared__ __attribute__((aligned(16))) double xs[3][XL][SP_XW];
   __shared__ __attribute__((aligned(16))) double tab[sp_tab(B) + 2];
   if (done_flag && done_flag[0]) return;
@@ -264,8 +277,9 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
   int xo[XU], xa[XU];  // x staging: in-plane offset (may be negative) and LDS slot of the lane's neighbourhood points
   double dot_acc = 0.0;
   int fail = 0;
-  e_d2 cur[B][14];       // per band: slots 13..26 of its sub-step, requested a full step (one plane) ahead -- with three resident waves per CU one
+  e_d2 cur[B][NSL];      // per band: slots S0..26 of its sub-step, requested a full step (one plane) ahead -- with three resident waves per CU one
                          // sub-step in flight left the stream short (512^3, B = 2: 1142 against 1131 ms per step with the four-line form)
+  int cdc[B];            // DC = 1: per band the codes of the lane's two diagonals (two signed bytes), requested with the band's main part
   e_d2 keep[3];          // band 0's slots 24..26, held back from the tables of slots 2..0 while a later band of the plane still reads the previous plane's
   double ed[EU], xr[XU];  // the step's edge block entries and the x neighbourhood of the plane after it, requested with band 0
   // x neighbourhood entry of plane `plane`: positions outside the vector's owned entries (beyond the last lattice line of the last
@@ -279,10 +293,12 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
   auto request = [&](const double* v, int b) {
     if (vxb[b]) {
 #pragma unroll
-      for (int u = 0; u < 14; ++u) cur[b][u] = SYM_LD(reinterpret_cast<const e_d2*>(v + b * BM + 2 * lane + u * SP_ROWS));
+      for (int u = 0; u < NSL; ++u) cur[b][u] = SYM_LD(reinterpret_cast<const e_d2*>(v + b * BM + 2 * lane + u * SP_ROWS));
+      if (DC && MODE == 0) cdc[b] = SYM_LD(reinterpret_cast<const unsigned short*>(v + sp_coff(B, DC)) + b * (SP_ROWS / 2) + lane);
     } else {
 #pragma unroll
-      for (int u = 0; u < 14; ++u) cur[b][u] = (e_d2){0.0, 0.0};
+      for (int u = 0; u < NSL; ++u) cur[b][u] = (e_d2){0.0, 0.0};
+      if (DC) cdc[b] = 0;  // (a lane outside the lattice: its sums are never stored)
     }
   };
   // the edge block of the step at v and the x neighbourhood of plane pnext
@@ -362,7 +378,7 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
     const bool vx = vxb[b], vy = vyb[b], lastb = b + 1 >= nb;
     // ---- phase B: this sub-step's +z / +y slots go to LDS; with band 0 the step's edge entries and the next plane's x
 #pragma unroll
-    for (int s = 9; s < 13; ++s) *reinterpret_cast<e_d2*>(tab + sp_tbase(s, B) + sp_adj(s) * SP_LS + 2 + lb) = cur[b][26 - s - 13];
+    for (int s = 9; s < 13; ++s) *reinterpret_cast<e_d2*>(tab + sp_tbase(s, B) + sp_adj(s) * SP_LS + 2 + lb) = cur[b][26 - s - S0];
     e_d2 low[13];
     if (MODE == 0) {
       if (b == 0) {
@@ -378,9 +394,10 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
       for (int s = 0; s < 13; ++s) low[s] = vx ? SYM_LD(reinterpret_cast<const e_d2*>(vlow + b * BL + 2 * lane + s * SP_ROWS)) : (e_d2){0.0, 0.0};
     }
     // the sub-step's own upper slots stay in `mine`; the next sub-step of the same sweep is requested now and arrives during the products
-    e_d2 mine[14];
+    e_d2 mine[NSL];
 #pragma unroll
-    for (int u = 0; u < 14; ++u) mine[u] = cur[b][u];
+    for (int u = 0; u < NSL; ++u) mine[u] = cur[b][u];
+    const int mcd = DC && MODE == 0 ? cdc[b] : 0;
     __syncthreads();  // one wave: orders its LDS writes before the reads of other lanes
     if (more) {  // this band of the next plane; with the plane's last band the next step's edge block and the x of the plane behind it
       request(v + (int64_t)NP * MAINB, b);
@@ -431,28 +448,35 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
       run(mirrored(3), mirrored(4), mirrored(5), bp, 0, false);
       run(mirrored(6), mirrored(7), mirrored(8), bp, 1, false);
       run(mirrored(9), mirrored(10), mirrored(11), bc, -1, false);
-      run(mirrored(12), mine[0], mine[1], bc, 0, true);
-      run(mine[2], mine[3], mine[4], bc, 1, false);
+      e_d2 dg;  // the diagonal: stored, or the bind's unit (+-1.0) moved by the row's code -- the same double bit for bit
+      if (DC) {
+        dg.x = __longlong_as_double(Gm.unit + (long long)(signed char)(mcd & 255));
+        dg.y = __longlong_as_double(Gm.unit + (long long)(signed char)((mcd >> 8) & 255));
+      } else {
+        dg = mine[0];
+      }
+      run(mirrored(12), dg, mine[14 - S0], bc, 0, true);
+      run(mine[15 - S0], mine[16 - S0], mine[17 - S0], bc, 1, false);
     }
     __syncthreads();  // every lane is done with the tables
     // the next-plane slots become the history of the next plane; slots 24..26 of a band that is not the plane's last wait in `keep`: the band below
     // still reads the previous plane's from the table line this band would overwrite
 #pragma unroll
-    for (int s = 3; s < 9; ++s) *reinterpret_cast<e_d2*>(tab + sp_tbase(s, B) + sp_adj(s) * SP_LS + 2 + lb) = mine[26 - s - 13];
+    for (int s = 3; s < 9; ++s) *reinterpret_cast<e_d2*>(tab + sp_tbase(s, B) + sp_adj(s) * SP_LS + 2 + lb) = mine[26 - s - S0];
     if (B > 1 && !lastb) {
 #pragma unroll
-      for (int s = 0; s < 3; ++s) keep[s] = mine[26 - s - 13];
+      for (int s = 0; s < 3; ++s) keep[s] = mine[26 - s - S0];
     } else {
 #pragma unroll
       for (int s = 0; s < 3; ++s) {
-        *reinterpret_cast<e_d2*>(tab + sp_tbase(s, B) + sp_adj(s) * SP_LS + 2 + lb) = mine[26 - s - 13];
+        *reinterpret_cast<e_d2*>(tab + sp_tbase(s, B) + sp_adj(s) * SP_LS + 2 + lb) = mine[26 - s - S0];
         if (B > 1 && b > 0) *reinterpret_cast<e_d2*>(tab + sp_tbase(s, B) + sp_adj(s) * SP_LS + 2 + lb - BT) = keep[s];
       }
     }
     if (MODE == 0) {
-      run(mine[5], mine[6], mine[7], bn, -1, false);
-      run(mine[8], mine[9], mine[10], bn, 0, false);
-      run(mine[11], mine[12], mine[13], bn, 1, false);
+      run(mine[18 - S0], mine[19 - S0], mine[20 - S0], bn, -1, false);
+      run(mine[21 - S0], mine[22 - S0], mine[23 - S0], bn, 0, false);
+      run(mine[24 - S0], mine[25 - S0], mine[26 - S0], bn, 1, false);
       const int64_t r = (int64_t)p * Gm.PL + rin + (int64_t)(SP_L * b) * Gm.m2;
       double y0 = alpha * acc.x, y1 = alpha * acc.y;
       if (beta != 0.0) {
@@ -648,7 +672,7 @@ static int symp_nseg(const mfem_context_s* ctx, const mfem_csr_s* A) {
 }
 SympGeom mfem_symp_geom(const mfem_context_s* ctx, const mfem_csr_s* A) {  // (nx = n: the sweep stages owned entries of x only -- swept rows reference no ghost column)
   const int B = mfem_symp_bands(A);
-  return SympGeom{A->symp_PL, A->n, A->symp_m1, A->symp_m2, A->symp_p0, A->symp_p1, A->symp_NS, A->symp_NPk, symp_nseg(ctx, A), B, (A->symp_NS + B - 1) / B};
+  return SympGeom{A->symp_PL, A->n, A->symp_m1, A->symp_m2, A->symp_p0, A->symp_p1, A->symp_NS, A->symp_NPk, symp_nseg(ctx, A), B, (A->symp_NS + B - 1) / B, A->symp_DC, sp_unit_bits(A->symp_dneg)};
 }
 int64_t mfem_symp_steps(const mfem_csr_s* A, int B) {
   if (B < 1) B = mfem_symp_bands(A);
@@ -667,7 +691,7 @@ static int symp_grid(const mfem_context_s* ctx, const mfem_csr_s* A) {
 
 // Matrix entries (8 B) one product by sweep k reads from memory.  Tile sweep: K per padded row less what it takes from LDS.  Patch sweep: the rows
 // outside the swept planes read their K slots; the sweep reads the 14 upper slots of every valid lane pair and the edge block per step + the nine
-// previous-plane slots wherever a run or a patch starts.
+// previous-plane slots wherever a run or a patch starts.  (The form of the diagonal: the bound copy's; unbound: the last patch-sweep bind's.)
 int64_t mfem_sym_entries(const mfem_context_s* ctx, const mfem_csr_s* A, DiaKernel k) {
   if (k == DIA_SYM27) {
     const int64_t nch = A->sym_c1 - A->sym_c0;
@@ -675,7 +699,7 @@ int64_t mfem_sym_entries(const mfem_context_s* ctx, const mfem_csr_s* A, DiaKern
   }
   const int B = mfem_symp_bands(A);
   const int NP = (A->symp_NS + B - 1) / B * A->symp_NPk, nplanes = A->symp_p1 - A->symp_p0, nseg = symp_nseg(ctx, A);
-  int64_t e = (int64_t)A->ell_K * (A->ell_npad - (int64_t)nplanes * A->symp_PL);
+  int64_t e = (int64_t)A->ell_K * (A->ell_npad - (int64_t)nplanes * A->symp_PL), codes = 0;
   for (int patch = 0; patch < NP; ++patch) {
     int64_t nv = 0;  // valid lane pairs of all bands (a band without a valid line is skipped: none of its lanes is valid)
     for (int lp = 0; lp < 64 * B; ++lp) {
@@ -683,8 +707,18 @@ int64_t mfem_sym_entries(const mfem_context_s* ctx, const mfem_csr_s* A, DiaKern
       if (j < A->symp_m1 && kk < A->symp_m2) ++nv;
     }
     e += (28 * nv + sp_ne(B)) * nplanes + 18 * nv * nseg;
+    codes += 2 * nv * nplanes;
   }
+  // the coded form reads two bytes instead of two doubles of diagonal per valid lane pair and step (whole entries: rounded up)
+  if (mfem_symp_coded(A)) e -= codes - (codes + 7) / 8;
   return e;
+}
+
+// the sweep's instantiation for a geometry: pass (MODE), bands, form of the diagonal
+template <int MODE>
+static auto symp_kernel(const SympGeom& G) {
+  if (G.DC) return G.B == 2 ? k_spmv_symp<MODE, 2, 1> : k_spmv_symp<MODE, 1, 1>;
+  return G.B == 2 ? k_spmv_symp<MODE, 2, 0> : k_spmv_symp<MODE, 1, 0>;
 }
 
 static std::atomic<long long> g_symp_fp_checks{0};  // binds whose symmetry verdict came from the fill's fingerprint (tests)
@@ -693,8 +727,13 @@ extern "C" long long mfem_debug_symp_fingerprint_count(void) { return g_symp_fp_
 // Are the pairs sweep k mirrors bitwise equal in the copies of this bind (buf: slot-major, pvals: patch-major)?  The patch sweep's copy is completed
 // first when it was not filled directly; its verdict is the fill's fingerprint when it made one (zero = symmetric among the swept rows), else a
 // check pass, as for the tile sweep.
-int mfem_sym_verdict(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const double* buf, double* pvals, const SympGeom& G, bool direct, bool fp_made, bool* ok) {
+// *dc_refused: the copy has the coded form (G.DC) and the fill met a swept row whose scaled diagonal has no code (d_flags[18], beside the fingerprint): the
+// bind refills in the stored form and asks again.  *dneg: the unit its codes count from is -1.0 (d_flags[19]).
+int mfem_sym_verdict(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const double* buf, double* pvals, const SympGeom& G, bool direct, bool fp_made, bool* ok,
+                     bool* dc_refused, int* dneg) {
   int32_t* d_bad = ctx->d_flags + 9;
+  *dc_refused = false;
+  *dneg = 0;
   if (k == DIA_SYMP) {
     { const int rt = symp_upload_tables(ctx->device); if (rt) return rt; }
     if (!direct) {
@@ -704,18 +743,20 @@ int mfem_sym_verdict(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const doub
       MFEM_CHECK_LAUNCH();
     }
     if (fp_made) {
-      MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 16, ctx->d_flags + 16, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+      MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 16, ctx->d_flags + 16, sizeof(unsigned long long) + 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
       MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
       unsigned long long fpv;
       memcpy(&fpv, ctx->h_flags + 16, sizeof(fpv));
       *ok = fpv == 0;
+      *dc_refused = G.DC && ctx->h_flags[18] != 0;
+      *dneg = G.DC && ctx->h_flags[19] != 0;
       ++g_symp_fp_checks;
       return MFEM_OK;
     }
   }
   MFEM_CHECK_HIP(hipMemsetAsync(d_bad, 0, sizeof(int32_t), ctx->stream));
   if (k == DIA_SYMP)
-    hipLaunchKernelGGL((G.B == 2 ? k_spmv_symp<1, 2> : k_spmv_symp<1, 1>), dim3(symp_grid(ctx, A)), dim3(64), 0, ctx->stream, G, (const double*)pvals,
+    hipLaunchKernelGGL(symp_kernel<1>(G), dim3(symp_grid(ctx, A)), dim3(64), 0, ctx->stream, G, (const double*)pvals,
                        (const double*)nullptr, (double*)nullptr, 0.0, 0.0, (const double*)nullptr, (double*)nullptr, (const int32_t*)nullptr, d_bad,
                        SympTail{});
   else
@@ -723,8 +764,11 @@ int mfem_sym_verdict(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const doub
                        A->sym_c0 * SYM_ROWS, A->sym_c1 * SYM_ROWS, A->sym_cls, d_bad);
   MFEM_CHECK_LAUNCH();
   MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 9, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (k == DIA_SYMP && G.DC) MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 18, ctx->d_flags + 18, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
   *ok = ctx->h_flags[9] == 0;
+  *dc_refused = k == DIA_SYMP && G.DC && ctx->h_flags[18] != 0;
+  *dneg = k == DIA_SYMP && G.DC && ctx->h_flags[19] != 0;
   return MFEM_OK;
 }
 
@@ -750,7 +794,7 @@ int mfem_sym_launch(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const SpmvA
     if (a.part.part == 0 && g_ell.symp_tail) tl = SympTail{1, A->ell_K, A->n, A->ell_npad, lo, hi, O, A->dia_flags, A->ell_cols, A->ell_vals};
     if (a.part.part != 2) {
       np = symp_grid(ctx, A);
-      hipLaunchKernelGGL((G.B == 2 ? k_spmv_symp<0, 2> : k_spmv_symp<0, 1>), dim3(np), dim3(64), 0, ctx->stream, G, (const double*)A->symp_vals, a.x, a.y, a.alpha, a.beta, a.dotw,
+      hipLaunchKernelGGL(symp_kernel<0>(G), dim3(np), dim3(64), 0, ctx->stream, G, (const double*)A->symp_vals, a.x, a.y, a.alpha, a.beta, a.dotw,
                          a.partials, a.done_flag, (int32_t*)nullptr, tl);
       MFEM_CHECK_LAUNCH();
     }

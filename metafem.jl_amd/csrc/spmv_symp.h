@@ -55,9 +55,36 @@ __host__ __device__ constexpr int sp_epad(int B) { return 64 * sp_eu(B); }
 // doubles per (plane, patch) in the patch-major copy, in two parts:
 //   main: what every step reads -- per band the slots 13..26 (14 x SP_ROWS, band after band), then the edge block -- contiguous per step, steps [plane][patch]
 //   low: per band the lower slots 0..12 (read where a run starts and by the symmetry check), behind all main parts
-__host__ __device__ constexpr int sp_main(int B) { return 14 * SP_ROWS * B + sp_epad(B); }
+// The main part has a second form, DC = 1 (coded diagonal; k_symp_fill with the symmetric scaling of the scaled CG): slot 13 of the scaled matrix is
+// a_ii * (t_i * t_i), t_i = 1 / sqrt|a_ii| -- 1.0 up to a few roundings, or -1.0 (the thermal K is negative definite) -- and is carried as one signed byte per
+// row, bits(v) - bits(+-1.0): the unit is the bind's, +-1.0 with the sign of the first swept row's diagonal (sp_unit_bits).  Per band the 13
+// slots 14..26, then the edge block, then the code block: SP_ROWS bytes per band (byte = row of the band, band after band; 128 B bytes keep the next
+// step 16-byte aligned).  B = 2: 3744 instead of 3968 doubles per step.  DC = 0, the default, is the stored form.
+#define SP_ONE_BITS 0x3FF0000000000000ll  // bits(1.0)
+#define SP_CODE_MAX 127                   // a diagonal further than this many ulps from the unit (the other sign, zero, non-finite) refuses the coded form
+__host__ __device__ constexpr long long sp_unit_bits(int negative) { return negative ? (long long)(0xBFF0000000000000ull) : SP_ONE_BITS; }  // bits(-1.0) / bits(1.0)
+__host__ __device__ constexpr int sp_nslots(int DC = 0) { return 14 - DC; }                // slots per band in the main part
+__host__ __device__ constexpr int sp_cpad(int B, int DC = 0) { return DC ? B * SP_ROWS / 8 : 0; }  // doubles of the code block
+__host__ __device__ constexpr int sp_eoff(int B, int DC = 0) { return sp_nslots(DC) * SP_ROWS * B; }  // the edge block's place in the main part
+__host__ __device__ constexpr int sp_coff(int B, int DC = 0) { return sp_eoff(B, DC) + sp_epad(B); }  // the code block's (DC = 1)
+__host__ __device__ constexpr int sp_main(int B, int DC = 0) { return sp_coff(B, DC) + sp_cpad(B, DC); }
 __host__ __device__ constexpr int sp_low(int B) { return 13 * SP_ROWS * B; }
-__host__ __device__ constexpr int sp_step(int B) { return sp_main(B) + sp_low(B); }
+__host__ __device__ constexpr int sp_step(int B, int DC = 0) { return sp_main(B, DC) + sp_low(B); }
+// code <-> double: IEEE ordering (of the magnitudes) is monotonic in the bits, so the code crosses the binade boundary at the unit like any other step; a
+// value of the other sign lies 2^63 away
+__host__ __device__ inline bool sp_diag_code(double v, int& code, long long unit = SP_ONE_BITS) {
+  long long b = 0;
+  __builtin_memcpy(&b, &v, 8);
+  const long long d = (long long)((unsigned long long)b - (unsigned long long)unit);
+  code = (int)(d < -SP_CODE_MAX ? -SP_CODE_MAX - 1 : d > SP_CODE_MAX ? SP_CODE_MAX + 1 : d);
+  return d >= -SP_CODE_MAX && d <= SP_CODE_MAX;
+}
+__host__ __device__ inline double sp_diag_value(int code, long long unit = SP_ONE_BITS) {
+  const long long b = unit + (long long)code;
+  double v = 0.0;
+  __builtin_memcpy(&v, &b, 8);
+  return v;
+}
 #define SP_STEP sp_step(1)
 #define SP_MAIN sp_main(1)
 #define SP_LOW sp_low(1)
