@@ -671,7 +671,7 @@ int mfem_mesh_kval_facets(mfem_context ctx, int32_t dim, int32_t itg_b, int32_t 
                           const double* vals, const int32_t* sparse_IDs_by_el, int64_t slot_block_stride, double* K_val,
                           const int32_t* facetIDs, int64_t n_items, int32_t n_colours, const int64_t* colour_offsets);
 
-/* ---- matrix-free operator on unstructured meshes (constant-coefficient terms; new) --------------------------------------------------
+/* ---- matrix-free operator on unstructured meshes (constant-coefficient terms, and variable terms read from coefficient arrays; new) ---
  * What caps the mesh on the assembled path is the matrix and what exists only to build or hold it (values, columns, the solver layout's copy,
  * sparse_IDs_by_el, row ranks).  For weak forms whose linear gradients have constant coefficients -- on facets: constant plus linear in the
  * components of the outward normal -- K x is the contraction the fused residual evaluates, so a solve needs the mesh, its vectors and one
@@ -702,12 +702,26 @@ int mfem_mesh_operator_add_facets(uint64_t op, int32_t itg_b, int32_t n_face_ids
                                   const mfem_operator_term* terms, int32_t* part /* [host] out: the part's number, >= 1 */);
 /* Replaces the terms of a part (0 = the elements): host only, nothing is launched.  How the K_params of a new time step reach the operator. */
 int mfem_mesh_operator_set_terms(uint64_t op, int32_t part, int32_t n_terms, const mfem_operator_term* terms);
+/* Variable terms of a part -- nonlinear gradients, linear gradients whose coefficient depends on fields or externals --, besides its constant ones:
+ *   K += sum over items u, Gauss points q and terms t of vals_t[q, u] w_q det_q D^dual_sd_t N_a(q) D^base_sd_t N_b(q)   at block_t.
+ * vals is a caller-owned device array with the layout and meaning of mfem_mesh_kval_elements: term t at + t * itg * n_items, entry [q, u] at
+ * q + itg * u, the coefficient only (K_params folded in by the caller; the kernel multiplies the weight, on facets w_q times the surface det).  Work
+ * unit u is item u of the part in its natural order -- element u, or facet u as passed to mfem_mesh_operator_add_facets --: no elIDs indirection.
+ * Host only, nothing is launched.  Replaces the part's variable terms (n_terms = 0 removes them: the part is then exactly what it was before);
+ * mfem_mesh_operator_set_terms replaces the constant ones and leaves these, mfem_mesh_operator_set_elements starts the element part afresh.  terms
+ * (block = dual_pos * n_fields + base_pos, as above) need not be sorted and are never merged.  vals is read at every later product, diagonal and
+ * solve until replaced; the caller may rewrite its CONTENTS between products -- how a Newton iteration updates the tangent -- without calling again.
+ * Within a dual word the constant entries are summed first, then the variable ones in the order given: bitwise reproducible.
+ * MFEM_ERR_INVALID: null vals or terms with n_terms > 0, words or blocks out of range, a part that does not exist or has no items.
+ * MFEM_ERR_UNSUPPORTED: more than 128 variable terms, more than 128 entries (distinct constant monomials plus variable terms), more than 8 dual or
+ * 8 base fields in the part, one wave's LDS block > 64 KB. */
+int mfem_mesh_operator_set_variable_terms(uint64_t op, int32_t part, int32_t n_terms, const mfem_kval_term* terms, const double* vals);
 int mfem_mesh_operator_destroy(uint64_t op);
 /* y = alpha K x + beta y (x, y: n_fields * ncp, field-major).  beta == 0 does not read y.  A control point in no adjacency list has an empty row.
  * The scratch (sum over parts of n_items * itp * dual fields doubles) is taken from the context workspace. */
 int mfem_mesh_operator_apply(mfem_context ctx, uint64_t op, const double* x, double* y, double alpha, double beta);
 /* d[f * ncp + i] = K_(f,i),(f,i), signed (0 on an empty row): per item and local node sum_q w_q det_q sum_{terms on diagonal blocks} coef D^s N_a D^s' N_a,
- * summed over the adjacency as the product is. */
+ * summed over the adjacency as the product is; variable terms on diagonal blocks add sum_q w_q det_q vals_t[q, u] D^s N_a D^s' N_a. */
 int mfem_mesh_operator_diagonal(mfem_context ctx, uint64_t op, double* d);
 /* mfem_solve on the operator: same options and statistics, every product an operator application (spmv_count: the per-method formulas above).  The
  * workspace holds the vectors and the scratch only: no layout, no copy of a matrix.  Accepts every method but MFEM_SOLVER_LSQR, precond NONE or

@@ -572,8 +572,9 @@ end
 mesh_ops_count() = ccall((:mfem_debug_mesh_ops_count, lib), Int64, ())
 
 # ---- matrix-free operator on unstructured meshes (mfem_mesh_operator_*, mfem_solve_operator) --------------------------------------
-# For weak forms whose linear gradients have constant coefficients (on facets: constant + linear in the normal components): no K_J_ptr / K_J /
-# K_total, no sparse_IDs_by_el -- the solve needs the mesh, its vectors and one element-vector scratch.  All arrays are borrowed: keep them alive.
+# Constant-coefficient linear gradients (on facets: constant + linear in the normal components) go in as terms; every other gradient term
+# (nonlinear, or with a field- or external-dependent coefficient) as a variable term whose coefficient array the caller fills: no K_J_ptr / K_J /
+# K_total, no sparse_IDs_by_el -- the solve needs the mesh, its vectors, one element-vector scratch and those arrays.  All arrays are borrowed.
 struct OperatorTerm                       # == mfem_operator_term
     dual_sd::Int32
     base_sd::Int32
@@ -629,6 +630,20 @@ end
 "Replaces the terms of a part (0 = the elements), host only: what K_linear_func does on this path (coefficient times the step's K_params)."
 operator_terms!(op::MeshOperator, part::Integer, terms::Vector{OperatorTerm}) =
     check(ccall((:mfem_mesh_operator_set_terms, lib), Cint, (UInt64, Int32, Int32, Ptr{OperatorTerm}), op.h, part, length(terms), terms))
+
+"""
+Replaces the variable terms of a part: `vals` (`itg * n_items * length(terms)` Float64, term-major, `[q, item]` within a term) holds their
+coefficients WITHOUT the weight and is borrowed -- rewrite its contents between products (a Newton iteration), do not free it.  No terms removes them.
+Returns false on MFEM_ERR_UNSUPPORTED (the caps).
+"""
+function operator_variable_terms!(op::MeshOperator, part::Integer, terms::Vector{KvalTerm}, vals)
+    rc = ccall((:mfem_mesh_operator_set_variable_terms, lib), Cint, (UInt64, Int32, Int32, Ptr{KvalTerm}, Ptr{Cvoid}),
+               op.h, part, length(terms), terms, isempty(terms) ? C_NULL : dptr(vals))
+    rc == -3 && return false
+    check(rc)
+    isempty(terms) || push!(op.keep, vals)
+    return true
+end
 
 "y = alpha K x + beta y"
 operator_mul!(y, op::MeshOperator, x, alpha = 1.0, beta = 0.0) =

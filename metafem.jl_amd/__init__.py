@@ -171,6 +171,7 @@ class MeshOperator:
         _need(coords, torch.float64, "coords", dim * ncp)
         _need(controlpoint_IDs, torch.int32, "controlpoint_IDs", nel * itp)
         self._keep = [coords, controlpoint_IDs]  # the library borrows every array
+        self._var_keep = {}  # part -> the coefficient array of its variable terms
         self.n_fields, self.ncp = n_fields, ncp
         self.n = n_fields * ncp
         self.nnz = 0
@@ -216,6 +217,17 @@ class MeshOperator:
         rc = lib.mfem_mesh_operator_set_terms(self._h, part, len(terms), self._terms(terms))
         if rc != -3:
             check(rc)
+        return rc
+
+    def set_variable_terms(self, part: int, terms, vals: Optional[torch.Tensor]) -> int:
+        """Replaces the variable terms `(dual_sd, base_sd, block)` of a part (host only); vals: the float64 device array [n_terms, n_items, itg] of
+        their coefficients (borrowed: read at every later product, diagonal and solve; rewrite its contents freely).  No terms: they are removed.
+        rc as set_elements."""
+        arr = (_lib.KvalTerm * max(len(terms), 1))(*[_lib.KvalTerm(int(t[0]), int(t[1]), int(t[2]), 0) for t in terms])
+        rc = lib.mfem_mesh_operator_set_variable_terms(self._h, part, len(terms), arr, _ptr(vals) if len(terms) else None)
+        if rc != -3:
+            check(rc)
+            self._var_keep[part] = vals if len(terms) else None
         return rc
 
     def mul_(self, y: torch.Tensor, x: torch.Tensor, alpha: float = 1.0, beta: float = 0.0) -> torch.Tensor:

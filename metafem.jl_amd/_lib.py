@@ -241,6 +241,7 @@ SIGNATURES = {
     "mfem_mesh_operator_add_facets": (c_int, [c_uint64, c_int32, c_int32, c_int64, P, P, P, P, P, P, P, c_int32, C.POINTER(OperatorTerm),
                                               C.POINTER(c_int32)]),
     "mfem_mesh_operator_set_terms": (c_int, [c_uint64, c_int32, c_int32, C.POINTER(OperatorTerm)]),
+    "mfem_mesh_operator_set_variable_terms": (c_int, [c_uint64, c_int32, c_int32, C.POINTER(KvalTerm), P]),
     "mfem_mesh_operator_destroy": (c_int, [c_uint64]),
     "mfem_mesh_operator_apply": (c_int, [P, c_uint64, P, P, c_double, c_double]),
     "mfem_mesh_operator_diagonal": (c_int, [P, c_uint64, P]),

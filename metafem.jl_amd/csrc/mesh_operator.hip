@@ -15,6 +15,11 @@
 // leaves the partial sums of dotw . y the Krylov kernels fold; both passes leave at once when the solve's stop flag is set.
 // Diagonal (k_mesh_operator_diag): the same wave per item computes, per dual field and local node, sum_q w_q det_q sum_{terms on the diagonal block}
 // coef [n_j] D^s N_a(q) D^s' N_a(q) into the same scratch; the same gather sums it.
+// Variable terms (mfem_mesh_operator_set_variable_terms): a part may carry, behind the constant entries of a dual word, entries whose coefficient is
+// read at every product from the caller's array vals[slot][item][q] (the layout of mfem_mesh_kval_elements: the coefficient alone, the kernel
+// multiplies w_q det_q in).  Such a part launches the VAR instantiation of pass 1 and of the diagonal: phase 4 maps lanes to (dual word, q) pairs and
+// adds, after the constant entries, vals[slot_e][q + itg * item] * u_e(q) in the order the terms were given; every load is unit-stride along q and
+// nothing of it is staged in LDS.  A part without variable terms launches the instantiation it always did.
 #include <memory>
 #include <vector>
 #include "mesh_geometry.h"
@@ -31,6 +36,10 @@ struct OpPart {
   const int64_t* adj_ptr;
   const int32_t* adj;
   OpProgram P;
+  int32_t n_terms, n_var;                      // the caller's lists, kept so that either can be replaced without the other
+  mfem_operator_term terms[MOP_MAX_TERMS];
+  mfem_kval_term vterms[MOP_MAX_VAR_TERMS];
+  const double* var_vals;                      // [n_var][n_items][itg], caller-owned; read at every product and diagonal
   int waves;          // of a pass-1 workgroup
   size_t lds_doubles; // of one wave
   size_t offset;      // of the part's element vectors in the scratch, in doubles
@@ -64,9 +73,10 @@ void mfem_mesh_operator_unbind(mfem_mesh_operator_s* op) {
 }
 
 // ---- pass 1 ------------------------------------------------------------------------------------------------------------------------------------
-template <int DIM>
+template <int DIM, bool VAR>
 __global__ __launch_bounds__(MFEM_BLOCK) void k_mesh_operator(MeshItems V, OpProgram P, const double* __restrict__ x, const double* __restrict__ dsc,
-                                                              double* __restrict__ S, int64_t n_items, const int32_t* __restrict__ done_flag) {
+                                                              double* __restrict__ S, int64_t n_items, const int32_t* __restrict__ done_flag,
+                                                              const double* __restrict__ vals) {
   extern __shared__ double lds[];
   if (done_flag && done_flag[0]) return;
   constexpr int NC = 1 + DIM;  // value, d/dx_1 .. d/dx_DIM
@@ -130,17 +140,36 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_mesh_operator(MeshItems V, OpPro
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_s_waitcnt(0xC07F);
   __builtin_amdgcn_wave_barrier();
-  // ---- the terms of every dual word, times the weight (lane <-> q; groups in sequence: uniform entry lists)
-  for (int g = 0; g < P.ngroups; ++g) {
-    const int e0 = g ? P.grp_end[g - 1] : 0, e1 = P.grp_end[g];
-    for (int q = lane; q < itg; q += 64) {
+  // ---- the terms of every dual word, times the weight
+  if constexpr (VAR) {
+    // lane <-> (dual word, q): the constant entries, then the variable ones, whose coefficients come from vals[slot][item][q] (unit stride along q)
+    const double* vq = vals + (size_t)itg * (size_t)t;
+    const size_t term_stride = (size_t)itg * (size_t)n_items;
+    for (int i = lane; i < P.ngroups * itg; i += 64) {
+      const int g = i / itg, q = i - g * itg;
+      const int e0 = g ? P.grp_end[g - 1] : 0, ev = P.grp_var[g], e1 = P.grp_end[g];
       double sum = 0.0;
-      for (int e = e0; e < e1; ++e) {
+      for (int e = e0; e < ev; ++e) {
         double c = P.ent_coef[e];
         if (P.ent_nrm[e] >= 0) c *= Nq[q * DIM + P.ent_nrm[e]];
         sum += c * Vs[((size_t)P.ent_src[e] * itg + q) * NC + P.ent_word[e]];
       }
-      D[g * itg + q] = sum * wd[q];
+      for (int e = ev; e < e1; ++e)
+        sum += vq[(size_t)P.ent_nrm[e] * term_stride + q] * Vs[((size_t)P.ent_src[e] * itg + q) * NC + P.ent_word[e]];
+      D[i] = sum * wd[q];
+    }
+  } else {  // (lane <-> q; groups in sequence: uniform entry lists)
+    for (int g = 0; g < P.ngroups; ++g) {
+      const int e0 = g ? P.grp_end[g - 1] : 0, e1 = P.grp_end[g];
+      for (int q = lane; q < itg; q += 64) {
+        double sum = 0.0;
+        for (int e = e0; e < e1; ++e) {
+          double c = P.ent_coef[e];
+          if (P.ent_nrm[e] >= 0) c *= Nq[q * DIM + P.ent_nrm[e]];
+          sum += c * Vs[((size_t)P.ent_src[e] * itg + q) * NC + P.ent_word[e]];
+        }
+        D[g * itg + q] = sum * wd[q];
+      }
     }
   }
   __builtin_amdgcn_wave_barrier();
@@ -185,8 +214,9 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_mesh_operator(MeshItems V, OpPro
 }
 
 // ---- the diagonal of one part: S[item][fo][a] = sum_q w_q det_q sum_{g of fo} sum_{e of g on the diagonal block} coef [n_j] D^{s_g} N_a(q) D^{word_e} N_a(q)
-template <int DIM>
-__global__ __launch_bounds__(MFEM_BLOCK) void k_mesh_operator_diag(MeshItems V, OpProgram P, double* __restrict__ S, int64_t n_items) {
+template <int DIM, bool VAR>
+__global__ __launch_bounds__(MFEM_BLOCK) void k_mesh_operator_diag(MeshItems V, OpProgram P, double* __restrict__ S, int64_t n_items,
+                                                                   const double* __restrict__ vals) {
   extern __shared__ double lds[];
   constexpr int NC = 1 + DIM;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
@@ -229,7 +259,7 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_mesh_operator_diag(MeshItems V, 
       }
       double sum = 0.0;
       for (int g = P.fo_g0[fo]; g < P.fo_g0[fo + 1]; ++g) {
-        const int e0 = g ? P.grp_end[g - 1] : 0, e1 = P.grp_end[g];
+        const int e0 = g ? P.grp_end[g - 1] : 0, e1 = VAR ? P.grp_var[g] : P.grp_end[g];
         double ng = 0.0, gs = 0.0;
 #pragma unroll
         for (int c = 0; c < NC; ++c)
@@ -243,6 +273,16 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_mesh_operator_diag(MeshItems V, 
           for (int k = 0; k < NC; ++k)
             if (P.ent_word[e] == k) nb = n[k];
           gs += c * nb;
+        }
+        if constexpr (VAR) {
+          for (int e = e1; e < P.grp_end[g]; ++e) {
+            if (P.src_pos[P.ent_src[e]] != P.fo_pos[fo]) continue;
+            double nb = 0.0;
+#pragma unroll
+            for (int k = 0; k < NC; ++k)
+              if (P.ent_word[e] == k) nb = n[k];
+            gs += vals[((size_t)P.ent_nrm[e] * (size_t)n_items + (size_t)t) * itg + q] * nb;
+          }
         }
         sum += ng * gs;
       }
@@ -316,12 +356,14 @@ static int op_refuse(int rc, const char* why) {
   return rc;
 }
 
-// compiles `terms` for part `k` (its MeshItems already set) and decides its LDS block; the part is changed only if everything is accepted
-static int op_set_program(mfem_mesh_operator_s* op, OpPart& part, int32_t n_terms, const mfem_operator_term* terms) {
+// compiles `terms` and the variable `vterms` for a part (its MeshItems already set) and decides its LDS block; the part is changed only if
+// everything is accepted.  Either list may be the part's own stored copy.
+static int op_set_program(mfem_mesh_operator_s* op, OpPart& part, int32_t n_terms, const mfem_operator_term* terms, int32_t n_var,
+                          const mfem_kval_term* vterms, const double* vals) {
   const bool facet = part.V.eindex != nullptr;
   OpProgram P;
   const char* why = "";
-  const int rc = mop_compile(op->dim, facet, op->n_fields, n_terms, terms, &P, &why);
+  const int rc = mop_compile_mixed(op->dim, facet, op->n_fields, n_terms, terms, n_var, vterms, &P, &why);
   if (rc) return op_refuse(rc, why);
   const size_t doubles = mop_wave_doubles(op->dim, part.V.itg, part.V.itp, facet, P.nsrc, P.nfo, P.ngroups);
   const int waves = mop_waves(doubles);
@@ -330,6 +372,11 @@ static int op_set_program(mfem_mesh_operator_s* op, OpPart& part, int32_t n_term
     return MFEM_ERR_UNSUPPORTED;
   }
   part.P = P;
+  if (n_terms > 0 && terms != part.terms) memcpy(part.terms, terms, sizeof(mfem_operator_term) * (size_t)n_terms);
+  if (n_var > 0 && vterms != part.vterms) memcpy(part.vterms, vterms, sizeof(mfem_kval_term) * (size_t)n_var);
+  part.n_terms = n_terms;
+  part.n_var = n_var;
+  part.var_vals = n_var ? vals : nullptr;
   part.waves = waves;
   part.lds_doubles = doubles;
   return MFEM_OK;
@@ -346,7 +393,7 @@ static void op_layout(mfem_mesh_operator_s* op) {
   }
   op->scratch_doubles = mop_scratch_layout(np, n_items, nfo, op->itp, off);
   for (int p = 0; p < np; ++p) op->parts[p].offset = off[p];
-  ++op->csr.op_epoch;  // (compiled terms and offsets are kernel arguments of a captured cycle)
+  ++op->csr.op_epoch;  // (compiled terms, offsets, the instantiation and the coefficient array of a part are baked into a captured cycle)
 }
 
 extern "C" int mfem_mesh_operator_create(mfem_context ctx, int32_t dim, int32_t itp, int64_t nel, int64_t ncp, int32_t n_fields, const double* coords,
@@ -398,7 +445,7 @@ extern "C" int mfem_mesh_operator_set_elements(uint64_t handle, int32_t itg, con
   part.n_items = op->nel;
   part.adj_ptr = adj_ptr;
   part.adj = adj;
-  const int rc = op_set_program(op, part, n_terms, terms);
+  const int rc = op_set_program(op, part, n_terms, terms, 0, nullptr, nullptr);
   if (rc) return rc;
   op->parts[0] = part;
   op_layout(op);
@@ -428,7 +475,7 @@ extern "C" int mfem_mesh_operator_add_facets(uint64_t handle, int32_t itg_b, int
   part.n_items = n_facets;
   part.adj_ptr = adj_ptr;
   part.adj = adj;
-  const int rc = op_set_program(op, part, n_terms, terms);
+  const int rc = op_set_program(op, part, n_terms, terms, 0, nullptr, nullptr);
   if (rc) return rc;
   mfem_host_alloc_probe();
   op->parts.push_back(part);
@@ -442,11 +489,26 @@ extern "C" int mfem_mesh_operator_set_terms(uint64_t handle, int32_t part, int32
   MFEM_REQUIRE(op, "null handle");
   MFEM_REQUIRE(part >= 0 && part < (int)op->parts.size() && op->parts[part].n_items >= 0, "no such part");
   MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
-  const int rc = op_set_program(op, op->parts[part], n_terms, terms);
+  OpPart& pt = op->parts[part];
+  const int rc = op_set_program(op, pt, n_terms, terms, pt.n_var, pt.vterms, pt.var_vals);  // (the variable terms stay)
   if (rc) return rc;
   op_layout(op);
   return MFEM_OK;
 } MFEM_API_CATCH("mfem_mesh_operator_set_terms")
+
+extern "C" int mfem_mesh_operator_set_variable_terms(uint64_t handle, int32_t part, int32_t n_terms, const mfem_kval_term* terms,
+                                                     const double* vals) try {
+  mfem_mesh_operator_s* op = mfem_mesh_operator_from_handle(handle);
+  MFEM_REQUIRE(op, "null handle");
+  MFEM_REQUIRE(part >= 0 && part < (int)op->parts.size() && op->parts[part].n_items > 0, "no such part, or a part without items");
+  MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
+  MFEM_REQUIRE(n_terms >= 0 && (n_terms == 0 || (terms && vals)), "null terms or vals");
+  OpPart& pt = op->parts[part];
+  const int rc = op_set_program(op, pt, pt.n_terms, pt.terms, n_terms, terms, vals);  // (the constant terms stay)
+  if (rc) return rc;
+  op_layout(op);  // (a new epoch: no captured cycle replays the old array or the other instantiation)
+  return MFEM_OK;
+} MFEM_API_CATCH("mfem_mesh_operator_set_variable_terms")
 
 extern "C" int mfem_mesh_operator_destroy(uint64_t handle) try {
   mfem_mesh_operator_s* op = mfem_mesh_operator_from_handle(handle);
@@ -500,18 +562,17 @@ static int op_items_launch(mfem_context_s* ctx, const mfem_mesh_operator_s* op, 
     MFEM_REQUIRE(grid < (1ll << 31), "too many items for one launch");
     const size_t ldsb = doubles * sizeof(double) * waves;
     double* Sp = S + part.offset;
+    const dim3 gr((unsigned)grid), bl(64 * waves);
+    const bool var = part.P.nvar > 0;  // (a part without variable terms launches the instantiation it always did)
+    const double* vals = part.var_vals;
     if (diag) {
-      if (op->dim == 2)
-        hipLaunchKernelGGL(k_mesh_operator_diag<2>, dim3((unsigned)grid), dim3(64 * waves), ldsb, ctx->stream, part.V, part.P, Sp, part.n_items);
-      else
-        hipLaunchKernelGGL(k_mesh_operator_diag<3>, dim3((unsigned)grid), dim3(64 * waves), ldsb, ctx->stream, part.V, part.P, Sp, part.n_items);
+      auto k = op->dim == 2 ? (var ? k_mesh_operator_diag<2, true> : k_mesh_operator_diag<2, false>)
+                            : (var ? k_mesh_operator_diag<3, true> : k_mesh_operator_diag<3, false>);
+      hipLaunchKernelGGL(k, gr, bl, ldsb, ctx->stream, part.V, part.P, Sp, part.n_items, vals);
     } else {
-      if (op->dim == 2)
-        hipLaunchKernelGGL(k_mesh_operator<2>, dim3((unsigned)grid), dim3(64 * waves), ldsb, ctx->stream, part.V, part.P, x, dsc, Sp, part.n_items,
-                           done_flag);
-      else
-        hipLaunchKernelGGL(k_mesh_operator<3>, dim3((unsigned)grid), dim3(64 * waves), ldsb, ctx->stream, part.V, part.P, x, dsc, Sp, part.n_items,
-                           done_flag);
+      auto k = op->dim == 2 ? (var ? k_mesh_operator<2, true> : k_mesh_operator<2, false>)
+                            : (var ? k_mesh_operator<3, true> : k_mesh_operator<3, false>);
+      hipLaunchKernelGGL(k, gr, bl, ldsb, ctx->stream, part.V, part.P, x, dsc, Sp, part.n_items, done_flag, vals);
     }
     MFEM_CHECK_LAUNCH();
   }

@@ -1,22 +1,25 @@
 // The host decisions of the matrix-free mesh operator (mesh_operator.hip, mfem_solve_operator in krylov.hip) that are arithmetic alone: the terms of a
 // part compiled, grouped and merged into the program the kernels read, the caps, the doubles of one wave's LDS block and the waves of a workgroup,
 // where every part's element vectors lie in the scratch and where the scratch lies in the solve's workspace, and which solve options the operator
-// accepts.  No HIP, no context: tools/host_check_mesh_operator.cpp walks them on the CPU.
+// accepts.  No HIP, no context: tools/host_check_mesh_operator.cpp and tools/host_check_mesh_operator_var.cpp walk them on the CPU.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 #include <string.h>
 #include "../../include/metafem_mi355x.h"
 
-#define MOP_MAX_TERMS 48     // terms of one part
+#define MOP_MAX_TERMS 48     // constant terms of one part
+#define MOP_MAX_VAR_TERMS 128  // variable terms of one part (coefficient arrays at the Gauss points)
 #define MOP_MAX_FIELDS 8     // dual fields of one part, and base fields (sources) of one part
-#define MOP_MAX_ENTRIES 128  // distinct (base field, base word, normal) monomials of one part, after merging per dual word
+#define MOP_MAX_ENTRIES 128  // distinct (base field, base word, normal) monomials of one part, after merging per dual word, plus its variable terms
 #define MOP_MAX_PARTS 8      // the elements + facet groups
 #define MOP_MAX_NFIELDS 32   // fields of the system
 static const size_t MOP_LDS_CAP = 64 * 1024;  // bytes of LDS one wave's block may take
 
 // The terms of one part, compiled for the kernels (passed by value; read with wave-uniform or small indices).  y[f][a] of an item is
 //   sum_q sum_{g of f} D^{grp_sd[g]} N_a(q) * w_q det_q * sum_{e of g} ent_coef[e] [n_{ent_nrm[e]}(q)] D^{ent_word[e]} x_{src_pos[ent_src[e]]}(q)
+// The entries of group g are its constant ones, [grp_end[g - 1], grp_var[g]), then its variable ones, [grp_var[g], grp_end[g]), in the order the
+// caller gave them and never merged: entry e of those takes its coefficient from the caller's array, term ent_nrm[e] (the slot), at [q, item].
 struct OpProgram {
   int nsrc, ngroups, nfo, nent;
   int32_t src_pos[MOP_MAX_FIELDS];      // base field of source k
@@ -28,16 +31,27 @@ struct OpProgram {
   double ent_coef[MOP_MAX_ENTRIES];
   int32_t fo_pos[MOP_MAX_FIELDS];       // dual field of output fo
   int8_t fo_g0[MOP_MAX_FIELDS + 1];     // groups of output fo: [fo_g0[fo], fo_g0[fo + 1])
+  int16_t grp_var[MOP_MAX_TERMS];       // first variable entry of group g (== grp_end[g]: none); behind the fields of the constant program
+  int32_t nvar;                         // variable entries of the part
 };
 static_assert(sizeof(OpProgram) < 2048, "OpProgram travels in the kernel arguments");
 
-// Checks the caller's terms and compiles them.  MFEM_OK, MFEM_ERR_INVALID or MFEM_ERR_UNSUPPORTED; *why names the reason of a refusal.
-static inline int mop_compile(int dim, bool facet, int n_fields, int32_t n_terms, const mfem_operator_term* terms, OpProgram* P, const char** why) {
+// Checks the caller's constant terms and variable terms (vterms: n_var of them, slot = position in the list) and compiles them into one program.
+// MFEM_OK, MFEM_ERR_INVALID or MFEM_ERR_UNSUPPORTED; *why names the reason of a refusal.  With n_var == 0 the program is the constant one.
+static inline int mop_compile_mixed(int dim, bool facet, int n_fields, int32_t n_terms, const mfem_operator_term* terms, int32_t n_var,
+                                    const mfem_kval_term* vterms, OpProgram* P, const char** why) {
   static const char* none = "";
   *why = none;
   if (n_terms < 0 || (n_terms > 0 && !terms)) { *why = "terms missing"; return MFEM_ERR_INVALID; }
+  if (n_var < 0 || (n_var > 0 && !vterms)) { *why = "variable terms missing"; return MFEM_ERR_INVALID; }
   if (n_terms > MOP_MAX_TERMS) { *why = "more than 48 terms in one part"; return MFEM_ERR_UNSUPPORTED; }
   memset(P, 0, sizeof(*P));
+  for (int i = 0; i < n_var; ++i) {  // (checked before the cap: a list with a bad word is invalid however long it is)
+    const mfem_kval_term& T = vterms[i];
+    if (T.dual_sd < 0 || T.dual_sd > dim || T.base_sd < 0 || T.base_sd > dim) { *why = "term words: 0 = value, 1 + j = d/dx_j"; return MFEM_ERR_INVALID; }
+    if (T.block < 0 || T.block >= n_fields * n_fields) { *why = "term block out of range"; return MFEM_ERR_INVALID; }
+  }
+  if (n_var > MOP_MAX_VAR_TERMS) { *why = "more than 128 variable terms in one part"; return MFEM_ERR_UNSUPPORTED; }
   for (int i = 0; i < n_terms; ++i) {
     const mfem_operator_term& T = terms[i];
     if (T.dual_sd < 0 || T.dual_sd > dim || T.base_sd < 0 || T.base_sd > dim) { *why = "term words: 0 = value, 1 + j = d/dx_j"; return MFEM_ERR_INVALID; }
@@ -48,30 +62,35 @@ static inline int mop_compile(int dim, bool facet, int n_fields, int32_t n_terms
       if (T.normal_coef[j] != 0.0 && (!facet || j >= dim)) { *why = "normal_coef must be 0 on elements and beyond the dimension"; return MFEM_ERR_INVALID; }
     }
   }
-  // groups = distinct (dual field, dual word), sorted by field then word (stable: the terms of a group keep their order)
-  int order[MOP_MAX_TERMS];
-  for (int i = 0; i < n_terms; ++i) order[i] = i;
-  auto dpos = [&](int i) { return terms[i].block / n_fields; };
-  for (int i = 1; i < n_terms; ++i)
+  // groups = distinct (dual field, dual word), sorted by field then word (stable: the terms of a group keep their order, the constant ones first)
+  const int n_all = n_terms + n_var;
+  int order[MOP_MAX_TERMS + MOP_MAX_VAR_TERMS];
+  for (int i = 0; i < n_all; ++i) order[i] = i;
+  auto blk = [&](int i) { return i < n_terms ? terms[i].block : vterms[i - n_terms].block; };
+  auto dsd = [&](int i) { return i < n_terms ? terms[i].dual_sd : vterms[i - n_terms].dual_sd; };
+  auto bsd = [&](int i) { return i < n_terms ? terms[i].base_sd : vterms[i - n_terms].base_sd; };
+  auto dpos = [&](int i) { return blk(i) / n_fields; };
+  for (int i = 1; i < n_all; ++i)
     for (int j = i; j > 0; --j) {
       const int a = order[j - 1], b = order[j];
-      if (dpos(a) < dpos(b) || (dpos(a) == dpos(b) && terms[a].dual_sd <= terms[b].dual_sd)) break;
+      if (dpos(a) < dpos(b) || (dpos(a) == dpos(b) && dsd(a) <= dsd(b))) break;
       order[j - 1] = b;
       order[j] = a;
     }
   int nent = 0;
-  for (int ii = 0; ii < n_terms; ++ii) {
-    const mfem_operator_term& T = terms[order[ii]];
-    const int dp = T.block / n_fields, bp = T.block % n_fields;
+  for (int ii = 0; ii < n_all; ++ii) {
+    const int it = order[ii];
+    const int dp = blk(it) / n_fields, bp = blk(it) % n_fields;
     const bool new_field = ii == 0 || dp != dpos(order[ii - 1]);
-    if (new_field || T.dual_sd != terms[order[ii - 1]].dual_sd) {
+    if (new_field || dsd(it) != dsd(order[ii - 1])) {
       if (new_field) {
         if (P->nfo == MOP_MAX_FIELDS) { *why = "more than 8 dual fields in one part"; return MFEM_ERR_UNSUPPORTED; }
         P->fo_pos[P->nfo] = dp;
         P->fo_g0[P->nfo] = (int8_t)P->ngroups;
         ++P->nfo;
       }
-      P->grp_sd[P->ngroups] = (int8_t)T.dual_sd;
+      P->grp_sd[P->ngroups] = (int8_t)dsd(it);
+      P->grp_var[P->ngroups] = (int16_t)nent;
       ++P->ngroups;
     }
     const int g = P->ngroups - 1;
@@ -82,6 +101,18 @@ static inline int mop_compile(int dim, bool facet, int n_fields, int32_t n_terms
       P->src_pos[P->nsrc++] = bp;
     }
     const int g_begin = g ? P->grp_end[g - 1] : 0;
+    if (it >= n_terms) {  // a variable term: an entry of its own behind the constant ones of its dual word
+      if (nent == MOP_MAX_ENTRIES) { *why = "more than 128 entries (distinct constant monomials plus variable terms) in one part"; return MFEM_ERR_UNSUPPORTED; }
+      P->ent_src[nent] = (int8_t)s;
+      P->ent_word[nent] = (int8_t)bsd(it);
+      P->ent_nrm[nent] = (int8_t)(it - n_terms);  // the slot
+      P->ent_coef[nent] = 0.0;
+      ++nent;
+      ++P->nvar;
+      P->grp_end[g] = (int16_t)nent;
+      continue;
+    }
+    const mfem_operator_term& T = terms[it];
     for (int j = -1; j < 3; ++j) {
       const double c = j < 0 ? T.coef : T.normal_coef[j];
       if (c == 0.0) continue;
@@ -98,10 +129,14 @@ static inline int mop_compile(int dim, bool facet, int n_fields, int32_t n_terms
       P->ent_coef[e] += c;
     }
     P->grp_end[g] = (int16_t)nent;
+    P->grp_var[g] = (int16_t)nent;
   }
   P->fo_g0[P->nfo] = (int8_t)P->ngroups;
   P->nent = nent;
   return MFEM_OK;
+}
+static inline int mop_compile(int dim, bool facet, int n_fields, int32_t n_terms, const mfem_operator_term* terms, OpProgram* P, const char** why) {
+  return mop_compile_mixed(dim, facet, n_fields, n_terms, terms, 0, nullptr, P, why);
 }
 
 // One wave's LDS block of the product kernel: w det, J^-1, node coordinates, (facets) normals, the nodal values of the sources, their words at the

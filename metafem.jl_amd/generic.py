@@ -110,6 +110,36 @@ def matrix_free_terms(domain_wf: "WeakForm", boundary_wfs: Sequence["WeakForm"],
     return parts, None
 
 
+@dataclass
+class OperatorPart:
+    """One part (the domain, or a boundary group) as GenericDomain(matrix_free="any") hands it to the operator."""
+    constant: List[Tuple[GradTerm, OperatorCoefficient]]  # -> mfem_mesh_operator_set_terms, as matrix_free_terms analyses them
+    variable_linear: List[GradTerm]  # linear gradients whose coefficient is not a constant (plus, on facets, a normal-linear part)
+    nonlinear: List[GradTerm]
+
+    @property
+    def variable(self) -> List[GradTerm]:
+        """The variable terms in slot order: the linear ones (filled by K_linear_func), then the nonlinear ones (K_nonlinear_func)."""
+        return self.variable_linear + self.nonlinear
+
+
+def matrix_free_parts(domain_wf: "WeakForm", boundary_wfs: Sequence["WeakForm"], t: float = 0.0, dt: float = 1.0) -> List[OperatorPart]:
+    """The classifier of GenericDomain(matrix_free="any"), decided on the host: per part the constant terms (operator_coefficient, exactly as
+    matrix_free_terms takes them) and the variable ones -- every nonlinear gradient and every linear gradient whose coefficient depends on fields,
+    externals or, beyond the linear part, the normal.  Nothing is refused here: what is left to refuse are the library's caps."""
+    parts = []
+    for i, wf in enumerate([domain_wf] + list(boundary_wfs)):
+        part = OperatorPart([], [], list(wf.nonlinear_gradients))
+        for g in wf.linear_gradients:
+            c = operator_coefficient(g, wf, facet=i > 0, t=t, dt=dt)
+            if c is None:
+                part.variable_linear.append(g)
+            else:
+                part.constant.append((g, c))
+        parts.append(part)
+    return parts
+
+
 class _Group:
     """Integration hosts of one launch family (the elements, or the facets of one boundary group).  The geometry tables of the
     operator path (vals, weights, normals: update_BasicElements / update_BasicBoundary) are built by `build` on first access."""
@@ -163,7 +193,7 @@ class GenericDomain:
                  boundaries: Sequence[Tuple[np.ndarray, np.ndarray, WeakForm]],
                  element_colours: Optional[np.ndarray] = None, max_time_level: int = 0, dissipative: bool = True,
                  batched: bool = True, fused: bool = True, row_owner: bool = True, fused_residual: bool = False,
-                 table_free: bool = False, direct_rows: bool = False, matrix_free: bool = False):
+                 table_free: bool = False, direct_rows: bool = False, matrix_free=False):
         """coords [ncp, dim]; cp_ids [itp, nel] 0-based (controlpoint_IDs in basis order); boundaries =
         [(element_ID[nf], element_eindex[nf] 0-based local face ids, WeakForm)].  element_colours (optional):
         a colour per element such that same-colour elements share no control point -> atomics-free scatter with a fixed
@@ -199,10 +229,26 @@ class GenericDomain:
         # times the current K_params); `linear_solver = lambda g: iterative_Solve(g.A, g.K_total, g.residue, ...)` works unchanged.  A problem that is
         # not eligible (matrix_free_terms) or that the library refuses (MFEM_ERR_UNSUPPORTED: the caps) is built as the default domain is:
         # matrix_free is False then and matrix_free_reason says why.
+        # matrix_free = "any" (implies table_free): the same, for ANY weak form.  The constant terms go to the operator as above; every other gradient
+        # term -- nonlinear, or linear with a field- or external-dependent coefficient (matrix_free_parts) -- is a VARIABLE term
+        # (mfem_mesh_operator_set_variable_terms): per part one persistent buffer [n_var_terms, n_items, itg] of coefficients at the Gauss points,
+        # registered once; K_linear_func fills the slices of the linear ones, K_nonlinear_func those of the nonlinear ones (_coef: the words of the
+        # fields and externals evaluated without tables, in item order), and the operator reads them at every product.  No K_total, no _kval_*.
+        # Falls back as above only when the library refuses (the caps) or the mesh is empty.
+        if isinstance(matrix_free, str) and matrix_free != "any":
+            raise ValueError("matrix_free: False, True or 'any'")
+        self.matrix_free_any = matrix_free == "any"
         self.matrix_free, self.matrix_free_reason = bool(matrix_free), None
-        if matrix_free:
+        self._var_buf: List[Optional[torch.Tensor]] = []
+        if self.matrix_free_any:
+            if cp_ids.shape[1] == 0:
+                self.matrix_free, self.matrix_free_reason = False, "the mesh has no elements"
+            self.table_free = table_free = True
+            element_colours = None  # (no scatter anywhere on this path: the items keep their natural order, which is how the operator indexes vals)
+        elif matrix_free:
             _, self.matrix_free_reason = matrix_free_terms(domain_wf, [b[2] for b in boundaries])
             self.matrix_free = self.matrix_free_reason is None
+        if matrix_free:
             self.fused = self.fused_residual = fused = fused_residual = True
         if table_free:
             if not batched:
@@ -324,7 +370,14 @@ class GenericDomain:
     # -- the matrix-free operator (matrix_free=True) -------------------------------------------------------------
     def _operator_terms(self, K_params):
         """Per part the ABI terms (dual_sd, base_sd, block, coef, normal coefficients) at the current t / dt, times K_params; None: not eligible."""
-        parts, reason = matrix_free_terms(self.domain_wf, self.bwfs, t=getattr(self, "t", 0.0), dt=getattr(self, "dt", 1.0))
+        if self.matrix_free_any:
+            found = matrix_free_parts(self.domain_wf, self.bwfs, t=getattr(self, "t", 0.0), dt=getattr(self, "dt", 1.0))
+            if getattr(self, "_op_parts", None) is not None and [len(p.constant) for p in found] != [len(p.constant) for p in self._op_parts]:
+                self.matrix_free_reason = "a coefficient that was constant when the operator was built is not at this t / dt"
+                return None
+            parts, reason = [p.constant for p in found], None
+        else:
+            parts, reason = matrix_free_terms(self.domain_wf, self.bwfs, t=getattr(self, "t", 0.0), dt=getattr(self, "dt", 1.0))
         if parts is None:
             self.matrix_free_reason = reason
             return None
@@ -337,20 +390,38 @@ class GenericDomain:
         from . import MeshOperator
 
         parts = self._operator_terms([1.0] * 8)
+        self._op_parts = matrix_free_parts(self.domain_wf, self.bwfs) if self.matrix_free_any else None
+        nvar = [len(p.variable) for p in self._op_parts] if self.matrix_free_any else [0] * len(parts)
         op = MeshOperator(self.ctx, self.dim, self.itp, self.nel, self.ncp, self.n_fields, self.coords, self.cp, 1)
         self._op_part = [0] + [None] * len(self.bwfs)
+        self._var_buf = [None] * len(parts)
         rc = op.set_elements(self.space.itg, self._ref, self._itgw, self._adj_ptr, self._adj, parts[0])
         for i, g in enumerate(self.groups[1:], start=1):
-            if rc == -3 or not parts[i] or g.facet_el.numel() == 0:
+            if rc == -3 or not (parts[i] or nvar[i]) or g.facet_el.numel() == 0:
                 continue
             ptr, adj = self._residual_adj(g)
             rc = op.add_facets(self.space.itg_b, self._nface, self._bref, self._bw, self._btan, g.facet_el, g.facet_eidx, ptr, adj, parts[i])
             self._op_part[i] = rc if rc >= 0 else None
+        for i, g in enumerate(self.groups):  # the variable terms: one persistent buffer per part, registered once
+            if rc == -3 or not nvar[i] or self._op_part[i] is None:
+                continue
+            buf = torch.zeros((nvar[i], g.n, g.itg), dtype=torch.float64, device=self.dev)
+            rc = op.set_variable_terms(self._op_part[i], [(t.dual_s, t.base_s, t.dual_pos * self.n_fields + t.base_pos)
+                                                          for t in self._op_parts[i].variable], buf)
+            self._var_buf[i] = buf if rc == 0 else None
         if rc == -3:
             op.close()
             self.matrix_free, self.matrix_free_reason = False, "the library refused the operator: " + lib.mfem_last_error().decode()
+            self._var_buf = []
             return None
         return op
+
+    def _fill_variable(self, i: int, g: _Group, env: dict, nonlinear: bool):
+        """Evaluates the coefficients of part i's variable linear (K_linear_func) or nonlinear (K_nonlinear_func) terms into their slices."""
+        part = self._op_parts[i]
+        terms, s0 = (part.nonlinear, len(part.variable_linear)) if nonlinear else (part.variable_linear, 0)
+        for k, t in enumerate(terms):
+            self._var_buf[i][s0 + k].copy_(self._coef(g, t.fn, env, self.K_params[t.td_order]))
 
     # -- assemble_X! / dessemble_X! (03_GlobalAssembly.jl:44-75)
     def assemble_X(self, infos):
@@ -668,6 +739,11 @@ class GenericDomain:
             for terms, part in zip(parts, self._op_part):
                 if part is not None and self.A.set_terms(part, terms) == -3:
                     raise _lib.MetaFEMError("matrix_free: " + lib.mfem_last_error().decode())
+            for i, (wf, g) in enumerate(self._parts()):  # (matrix_free="any": the variable linear gradients -> their slices of the part's buffer)
+                if i < len(self._var_buf) and self._var_buf[i] is not None and self._op_parts[i].variable_linear:
+                    env = {}
+                    self._externals(wf, g, env)
+                    self._fill_variable(i, g, env, nonlinear=False)
             return
         self._K_fresh = True
         for wf, g in self._parts():
@@ -784,6 +860,10 @@ class GenericDomain:
                 self._externals(wf, g, env)
                 w = None if g.table_free else self._w(g)  # (table-free: the kernels multiply the weight in)
                 self._res_many(g, residues, env, w)
+                if self.matrix_free_any and self.matrix_free:  # (the tangent is the operator: the coefficients go straight to its buffer)
+                    if self._var_buf[i] is not None:
+                        self._fill_variable(i, g, env, nonlinear=True)
+                    continue
                 self._kval_many(g, wf.nonlinear_gradients, env, w, self.K_total)
                 continue
             for name, pos, s, td in wf.inner_vars:  # declare_Innervar_GPU (:1-13)
