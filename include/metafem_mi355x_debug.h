@@ -27,6 +27,8 @@ long long mfem_debug_symp_fingerprint_count(void);
 /* binds that ended on the patch sweep with the coded-diagonal form of its copy (csrc/spmv_symp.h; process-wide): the scaled CG's binds unless bit 21 of
  * the "ell" knob forces the stored form or the fill's gate met a diagonal without a code */
 long long mfem_debug_symp_coded_count(void);
+/* binds that ended on the patch sweep in its trimmed form, with rim rows outside its patches (csrc/symp_trim_decide.h; process-wide) */
+long long mfem_debug_symp_trim_count(void);
 /* One product y = alpha (S^-1 A S^-1) x + beta y on the row layout bound as the scaled CG (cg_variant 4) binds it, ssym = 1 / S [device, n (+ ghosts)] folded
  * into the copy, with the fused dotw . y (dotw null: none): the per-workgroup partial sums go to partials_out [host, cap], their count to *n_partials.
  * *form: -1 the bind did not end on the patch sweep, 0 / 1 the copy's diagonal is stored / coded.  Nothing stays bound.  tests/test_gpu_symp_diag_code.py */
@@ -50,7 +52,9 @@ int mfem_debug_set(const char* key, int64_t a, int64_t b);
  * outside the swept planes in a launch of their own; bit 27 the patch-major copy made from the slot-major copy in a second pass; bit 28 the layout
  * copy without its software pipeline; bit 29 the swept rows by the copy's row tiles instead of k_symp_fill; bit 30 the symmetry of the swept rows
  * by the check pass instead of the fill's fingerprint; bits 24 / 25 force one / two bands of four lattice lines per patch of the patch sweep
- * (neither: the bind decides by size, mfem_symp_bands_wanted).
+ * (neither: the bind decides by size, mfem_symp_bands_wanted); bit 2 forces the untrimmed patch sweep (every row of a swept plane in a patch, the
+ * ragged last patch column and row included), bit 3 the trimmed one -- whole patches only, the rim rows computed row by row -- at any size (neither: the bind
+ * decides by size, mfem_symp_trim_wanted; csrc/symp_trim_decide.h).
  * RETIRED, accepted and ignored: bits 4-7 (variants of k_spmv_ell), every value of bits 16-19 other than 8 (variants of k_spmv_dia) -- the sweeps of round 1 (profiles/r01_spmv_sweep.txt) chose the kernels that remain.
  * These knobs are read when a layout is BOUND (every mfem_solve and mfem_spmv_solver_layout binds its own): a product runs the kernel its bind
  * recorded; only the launch geometry (bits 8-15, 20, 26) is read per product.  Set them before the solve. */

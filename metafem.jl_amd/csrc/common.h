@@ -197,6 +197,7 @@ struct mfem_csr_s {
   int symp_p0, symp_p1;     // regular lattice planes [p0, p1) (plane = row / PL): the rows the sweep computes
   int symp_NS, symp_NPk;    // strips of 4 lines, patches of 32 points per line
   int symp_B;               // bands (strips) per patch of the bound patch-major copy: decided once per bind (dia_bind), 0 while none is bound
+  int symp_trim;            // the bound patch-major copy covers whole patches only, the rim rows have a compact copy behind it (symp_trim_decide.h; mfem_symp_trim_wanted)
   int symp_DC;              // form of the bound patch-major copy's main part (spmv_symp.h): 1 = the diagonal as one-byte codes (mfem_symp_coded_wanted), 0 stored / none bound
   int symp_dneg;            // symp_DC = 1: the codes count from -1.0 (the first swept row's diagonal is negative), not from +1.0
   int symp_dc_last;         // symp_DC of the last bind that ended on the patch sweep (the byte accounting of an unbound pattern answers for that bind)

@@ -100,7 +100,7 @@ inline uint64_t mfem_csr_graph_key(uint64_t key, const mfem_csr_s* A) {
   key = mfem_hash(key, A->n); key = mfem_hash(key, A->nnz); key = mfem_hash(key, A->max_row_nnz);
   key = mfem_hash(key, A->index_base); key = mfem_hash(key, A->ell_vals);
   key = mfem_hash(key, A->ell_bound_mode + 16 * A->dia_kernel); key = mfem_hash(key, A->sell.vals); key = mfem_hash(key, A->lat27.vals); key = mfem_hash(key, A->lat8.vals); key = mfem_hash(key, A->symp_vals);
-  key = mfem_hash(key, A->symp_B + 16 * A->symp_DC + 32 * A->symp_dneg);  // (the sweep's instantiation: the coded form's gate decides per bind, on the same buffers)
+  key = mfem_hash(key, A->symp_B + 16 * A->symp_DC + 32 * A->symp_dneg + 64 * A->symp_trim);  // (the sweep's instantiation: the coded form's gate decides per bind, on the same buffers)
   // the column scaling the lattice-tile kernels apply to x is a kernel argument too: a solve with right Jacobi (dsc = the solve's d) and one without
   // (dsc = null) on the same pattern, values and workspace must not share a captured cycle
   key = mfem_hash(key, A->lat27.dsc); key = mfem_hash(key, A->lat8.dsc);

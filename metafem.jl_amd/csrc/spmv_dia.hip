@@ -217,12 +217,19 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_dia_vals(int64_t n, int64_t npad
     };
     auto colat = [&](int j) -> int64_t { return stage_cols ? (int64_t)Tc[off0 + j] : (int64_t)col[lo + j] - base; };
     if (cls >= 0 && r0 < shi && r0 + RT > slo) {  // a tile with swept rows (all of them in regular blocks of the 27-diagonal lattice class)
-      const bool sw = r >= slo && r < shi;
+      bool sw = r >= slo && r < shi;
+      int p = 0, jj = 0, kk = 0;
+      if (sw) {
+        p = (int)(r / Gm.PL);
+        const int rem = (int)(r - (int64_t)p * Gm.PL);
+        jj = rem / Gm.m2;
+        kk = rem - jj * Gm.m2;
+        sw = jj < Gm.ms1 && kk < Gm.ms2;  // (a rim row of a trimmed sweep goes to the slot-major copy like a row outside the swept planes; the product reads k_symp_rim_fill's copy)
+      }
       if (fast && sw) len = 0;  // (k_symp_fill's row: nothing is stored for it below)
       int line = 0, pcol = 0;
       int64_t mainoff = 0, lowoff = 0, edgeoff = 0;
       if (sw) {
-        const int p = (int)(r / Gm.PL), rem = (int)(r - (int64_t)p * Gm.PL), jj = rem / Gm.m2, kk = rem - jj * Gm.m2;
         const int L = SP_L * spB, band = (jj % L) / SP_L;  // the row's patch row, band and line of the band
         line = jj % L;
         pcol = kk % SP_W;
@@ -313,7 +320,8 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
   // symmetric copy cancels pair by pair -- exactly, in any order (integer sums commute: no atomics on doubles, no second pass); a copy with v_rc != v_cr
   // anywhere leaves a non-zero sum unless the pairs' hashed multipliers conspire (2^-63 for a given matrix).  It replaces the separate check pass over the
   // copy (k_spmv_symp<1>: 4.6 ms of the 21 ms a 512^3 solve spends outside its iterations); the pass is still there (bit 30 of the "ell" knob) and the
-  // test-suite compares the two verdicts.  Stricter than the pass (which looks at the pairs the sweep mirrors): never the other way round.
+  // test-suite compares the two verdicts.  Stricter than the pass (which looks at the pairs the sweep mirrors): never the other way round.  Swept: in a patch --
+  // an entry towards a rim row of a trimmed sweep has no partner in this pass and is not counted.
   unsigned long long fsum = 0;
   const int64_t sw_lo = (int64_t)Gm.p0 * Gm.PL, sw_hi = (int64_t)Gm.p1 * Gm.PL;
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (launched with two waves per workgroup)
@@ -330,7 +338,14 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
   };
   for (int i = threadIdx.x; i < spEPAD + sp_cpad(spB, DC); i += 128) E[i] = 0.0;  // (the code block lies behind E: all-zero bytes)
   __syncthreads();
-  for (int64_t step = blockIdx.x; step < spT; step += gridDim.x) {  // (every barrier below is reached by both waves: the trip count is the workgroup's)
+  // Work item wi = (plane, q) takes patch (q + plane * rot) % NP of its plane.  Workgroups with equal blockIdx % 8 share an XCD and the grid is a multiple of 8: with
+  // a patch count per plane that is a multiple of 8 too (whole patches of the usual meshes: 1024 at 512^3) a workgroup would meet the same patch, and an XCD
+  // the same patch columns, in every plane -- measured at 512^3: 22.0 ms per fill that way (the 512-point lattice of --n 511, untrimmed: 21.7 ms), 13.9 ms with
+  // the planes' patch orders shifted against each other (rot = 1, 3, 7, 13, NP - 1 alike), as the 1105 patches of the untrimmed plane shift by themselves
+  // (profiles/r10_symp_trim_ab_512.txt).
+  const int rot = spNP % 8 == 0 ? 1 : 0;
+  for (int64_t wi = blockIdx.x; wi < spT; wi += gridDim.x) {  // (every barrier below is reached by both waves: the trip count is the workgroup's)
+    const int64_t wpl = wi / spNP, step = wpl * spNP + (wi - wpl * spNP + wpl * rot) % spNP;
     const int kp = (int)(step % Gm.NPk);
     const int64_t q = step / Gm.NPk;
     const int prow = (int)(q % Gm.NR), pl = (int)(q / Gm.NR);
@@ -441,7 +456,7 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
           if constexpr (SYM) v = v * (srow * sc[sl]);  // (the product of the two factors first: a mirrored pair is multiplied by the same number)
           if (fp && sl != 13) {
             const int64_t cc = r + O.off[cls][sl];
-            if (cc >= sw_lo && cc < sw_hi) {
+            if (cc >= sw_lo && cc < sw_hi && jj0 + h + sp_dj(sl) < Gm.ms1 && kk0 + c + sp_dk(sl) < Gm.ms2) {
               const uint64_t lo_ = (uint64_t)(sl < 13 ? cc : r), hi_ = (uint64_t)(sl < 13 ? r : cc);
               uint64_t z = lo_ * 0x9E3779B97F4A7C15ull + hi_ * 0xD1B54A32D192ED03ull + 0x2545F4914F6CDD1Dull;
               z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -483,6 +498,77 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) fsum += __shfl_down(fsum, o, MFEM_WAVE);
     if (lane == 0 && fsum) atomicAdd(fp, fsum);
+  }
+}
+
+// The compact copy of the rim rows of a trimmed sweep (symp_trim_decide.h): units of SPT_UNIT rows in the rim's enumeration, slot-major inside a unit, a lane per
+// row.  The row's CSR entries are merged into the 27 lattice slots (columns and offsets both ascend; an absent entry is a stored zero) with the arithmetic of
+// the other copies: entry / dsc[column], then entry * (ssym[row] * ssym[column]).  The diagonal also goes to the slot-major copy (k_ell_diag reads it there):
+// k_dia_vals steps over the tiles inside the swept planes when k_symp_fill fills them.
+template <typename RP>
+__global__ __launch_bounds__(64) void k_symp_rim_fill(int K, const RP* __restrict__ rowptr, const int32_t* __restrict__ col, const double* __restrict__ vals,
+                                                       int base, double* __restrict__ out, SympGeom Gm, double* __restrict__ rim, const double* __restrict__ dsc,
+                                                       const double* __restrict__ ssym) {
+  const int lane = threadIdx.x;
+  for (int64_t u = blockIdx.x; u < Gm.rim_units; u += gridDim.x) {
+    const int64_t g = u * SPT_UNIT + lane;
+    const bool valid = g < Gm.rim_rows;
+    int64_t r = 0, lo = 0;
+    int len = 0;
+    double sr = 1.0;
+    if (valid) {
+      const int pl = (int)(g / Gm.rim_pp);
+      int j = 0, k = 0;
+      spt_rim_row((int)(g - (int64_t)pl * Gm.rim_pp), Gm.m2, Gm.ms1, Gm.ms2, j, k);
+      r = (int64_t)(Gm.p0 + pl) * Gm.PL + (int64_t)j * Gm.m2 + k;
+      lo = (int64_t)rowptr[r] - base;
+      len = (int)((int64_t)rowptr[r + 1] - base - lo);
+      if (ssym) sr = ssym[r];
+    }
+    double* const dst = rim + u * SPT_UNIT_DOUBLES + lane;
+    // all loads of a row are issued before the first use (a row of 27 entries, nearly all of them, has entry s in slot s: one memory round trip)
+    double ev[27];
+    int32_t ec[27];
+#pragma unroll
+    for (int e = 0; e < 27; ++e) {
+      ev[e] = e < len ? vals[lo + e] : 0.0;
+      ec[e] = e < len ? col[lo + e] : 0;
+    }
+    uint32_t slot_of = 0;  // bit sl: the row has an entry on lattice offset sl (columns and offsets both ascend)
+    if (len == 27) {
+      slot_of = 0x7FFFFFFu;
+    } else {
+      int sl = 0;
+#pragma unroll
+      for (int e = 0; e < 27; ++e) {
+        if (e < len) {
+          const int64_t d = (int64_t)ec[e] - base - r;
+          while (sl < 27 && (int64_t)(sl / 9 - 1) * Gm.PL + (int64_t)(sp_dj(sl) * Gm.m2 + sp_dk(sl)) < d) ++sl;
+          if (sl < 27) slot_of |= 1u << sl;
+          ++sl;
+        }
+      }
+    }
+    // the e-th set bit of slot_of is entry e's slot: walk slots and entries together with compile-time register indices
+    int cnt = 0;  // entries placed so far
+#pragma unroll
+    for (int sl = 0; sl < 27; ++sl) {
+      double v = 0.0;
+      if (slot_of >> sl & 1u) {
+        int64_t c = 0;
+#pragma unroll
+        for (int e = 0; e <= sl; ++e)
+          if (e == cnt) {
+            v = ev[e];
+            c = (int64_t)ec[e] - base;
+          }
+        if (dsc) v /= dsc[c];
+        if (ssym) v = v * (sr * ssym[c]);
+        ++cnt;
+      }
+      DIA_ST(dst + sl * SPT_UNIT, v);
+      if (sl == 13 && valid) out[ell_base(r, K) + 13 * ELL_B] = v;
+    }
   }
 }
 
@@ -561,7 +647,7 @@ __global__ __launch_bounds__(64) void k_symp_diag_sign(int64_t r, const RP* __re
 __global__ __launch_bounds__(MFEM_BLOCK) void k_symp_zero_odd(SympGeom Gm, double* __restrict__ pv) {
   const int NP = Gm.NR * Gm.NPk, nplanes = Gm.p1 - Gm.p0, B = Gm.B, MAINB = sp_main(B, Gm.DC), LOWB = sp_low(B), NSL = sp_nslots(Gm.DC);
   const int64_t T = (int64_t)NP * nplanes, cells = (int64_t)nplanes * Gm.NS * SP_L * 27;
-  const int col = Gm.m2 - (Gm.NPk - 1) * SP_W;  // first column past the line in the last patch column (odd, < SP_W)
+  const int col = Gm.ms2 - (Gm.NPk - 1) * SP_W;  // first column past the line in the last patch column (odd, < SP_W)
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < cells; t += (int64_t)gridDim.x * blockDim.x) {
     const int s = (int)(t % 27), line = (int)((t / 27) % SP_L);
     const int64_t q = t / (27 * SP_L);
@@ -716,9 +802,9 @@ bool mfem_dia_fill_fast(const mfem_csr_s* A, const double* dsc, bool direct) {
          A->symp_m1 >= 3 && A->symp_m2 >= 3 && g_ell.dia_fast;
 }
 int mfem_dia_copy(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, const double* ssym, const SympGeom& G,
-                  double* pvals, bool want_fp, bool* fp_made) {
+                  double* pvals, double* rim, bool want_fp, bool* fp_made) {
   const DiaOffsets* O = (const DiaOffsets*)A->dia_dev;
-  if (pvals && (G.m2 & 1)) {  // lattice lines of odd length leave cells of the patch-major copy that no row writes
+  if (pvals && (G.ms2 & 1)) {  // lattice lines of odd length leave cells of the patch-major copy that no row writes
     const int64_t cells = (int64_t)(G.p1 - G.p0) * G.NS * SP_L * 27;
     hipLaunchKernelGGL(k_symp_zero_odd, dim3(mfem_grid_for(cells, MFEM_BLOCK, ctx->num_cus * 8)), dim3(MFEM_BLOCK), 0, ctx->stream, G, pvals);
     MFEM_CHECK_LAUNCH();
@@ -755,6 +841,11 @@ int mfem_dia_copy(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double
     hipLaunchKernelGGL(kv, dim3(g), dim3(64 * wv), ldsb, ctx->stream, A->n, A->ell_npad, A->ell_K, (const RP*)A->rowptr, A->colidx, vals, A->index_base,
                        O, A->dia_flags, buf, G, pvals, dsc, ssym, fast ? 1 : 0);
     MFEM_CHECK_LAUNCH();
+    if (rim && G.rim_units > 0) {  // after k_dia_vals: the rim rows' diagonals of the slot-major copy are this kernel's where both write them (the same value)
+      const int gr = (int)(G.rim_units < (int64_t)ctx->num_cus * 32 ? G.rim_units : (int64_t)ctx->num_cus * 32);
+      hipLaunchKernelGGL(k_symp_rim_fill<RP>, dim3(gr), dim3(64), 0, ctx->stream, A->ell_K, (const RP*)A->rowptr, A->colidx, vals, A->index_base, buf, G, rim, dsc, ssym);
+      MFEM_CHECK_LAUNCH();
+    }
     if (!fast) return MFEM_OK;
     if (fpr) MFEM_CHECK_HIP(hipMemsetAsync(fpr, 0, sizeof(unsigned long long), ctx->stream));
     if (coded) {  // the gate's flag, and the sign of the unit the codes count from

@@ -8,6 +8,7 @@
 
 #include "layouts.h"
 #include "spmv_symp.h"
+#include "symp_trim_decide.h"
 
 // Blocked slot-major layout ("sliced ELL"): rows are grouped in blocks of ELL_B = 128 (the rows of one wave at two rows per
 // lane); block b stores its K slots one after the other, element (row r, slot s) at  b * K * 128 + s * 128 + (r & 127).
@@ -38,10 +39,16 @@ struct SympGeom {
   int B, NR; // bands of SP_L lines per patch (1 or 2); patch rows = ceil(NS / B): NR * NPk patches per plane (NS: strips of SP_L lines)
   int DC;    // form of the copy's main part (spmv_symp.h): 0 the diagonal stored as slot 13, 1 carried as one-byte ulp codes
   long long unit;  // DC = 1: bits of the unit the codes count from, +1.0 or -1.0 (known once the fill has run: the sweep's launches carry it)
+  // swept extents (symp_trim_decide.h): the patches cover lines [0, ms1) x points [0, ms2) of a plane -- NS, NPk, NR count those -- and the other rows of
+  // the swept planes, the rim, are computed row by row from a compact copy behind the patch-major one.  Lane validity, rows and x offsets use m1, m2.
+  int ms1, ms2;
+  int rim_pp;              // rim rows per plane
+  int64_t rim_rows, rim_units;  // rim rows of all swept planes; units of SPT_UNIT rows of their copy
 };
 // the rows outside the swept planes, taken by the sweep's waves after their runs (unsplit SpMV): per-row code on the slot-major copy
 struct SympTail {
   int on, K;
+  int rim;                  // the sweep's waves also take the units of rim rows (symp_trim_decide.h) after their runs; else a launch of their own (k_symp_rim)
   int64_t n, npad, lo, hi;  // rows [lo, hi) are the sweep's
   const DiaOffsets* Op;
   const int32_t* flags;
@@ -174,6 +181,7 @@ __device__ __forceinline__ void dia_rows(int64_t r, int64_t n, int64_t npad, int
 struct EllKnobs {
   std::atomic<int> enable{1};            // bit 0: modes 1 and 2 on
   std::atomic<int> dia{1};               // bit 1 clears it: explicit columns even when the matrix is diagonal-structured
+  std::atomic<int> symp_trim{0};         // bit 2 forces the untrimmed patch sweep (every row of a swept plane in a patch), bit 3 the trimmed one at any size (0: mfem_symp_trim_wanted decides by size)
   std::atomic<int> grid_mult{6};         // bits 8-15 (0 keeps the value): persistent workgroups per CU of the per-row kernels (profiles/r01_spmv_sweep.txt: 6 or 8)
   std::atomic<int> shared_x{1};          // bits 16-19 = 8 clears it: the plain per-row kernel without the shared x loads of three consecutive diagonals, no sweep
   std::atomic<int> xcd{0};               // bit 20: each XCD walks a contiguous eighth of the rows (k_spmv_dia; needs a grid that is a multiple of 8)
@@ -199,16 +207,21 @@ DiaKernel mfem_dia_kernel_wanted(const mfem_csr_s* A, DiaKernel refused = DIA_NO
 // spmv_dia.hip: inspection; the copies of a bind (pvals: the swept planes G straight to the patch-major copy); all rows / the rows outside [lo, hi)
 int mfem_dia_plan(mfem_context_s* ctx, mfem_csr_s* A);
 int mfem_dia_copy(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, const double* ssym, const SympGeom& G,
-                  double* pvals, bool want_fp, bool* fp_made);
+                  double* pvals, double* rim, bool want_fp, bool* fp_made);  // rim: the compact copy of G's rim rows (nullptr: none wanted)
 int mfem_dia_launch(mfem_context_s* ctx, mfem_csr_s* A, bool triples, int cap, const SpmvArgs& a);
 int mfem_dia_launch_outside(mfem_context_s* ctx, mfem_csr_s* A, const SpmvArgs& a, double* partials, int64_t lo, int64_t hi, int* ngrid);
 // spmv_sym.hip: the two sweeps k = DIA_SYM27, DIA_SYMP -- structure, size rule, geometry, accounting, the symmetry verdict of a bind, the product
 void mfem_sym_plan(mfem_csr_s* A, const int32_t* off, int lc, int64_t m2, int64_t PL, int64_t run_lo, int64_t run_hi);
 bool mfem_sym_wanted(const mfem_csr_s* A, DiaKernel k);
 SympGeom mfem_symp_geom(const mfem_context_s* ctx, const mfem_csr_s* A);
-int64_t mfem_symp_steps(const mfem_csr_s* A, int B = 0);  // patch steps of the swept planes with B bands per patch (0: mfem_symp_bands)
+int64_t mfem_symp_steps(const mfem_csr_s* A, int B = 0, int trim = -1);  // patch steps of the swept planes with B bands per patch (0: mfem_symp_bands), trimmed or not (-1: mfem_symp_trim)
 int mfem_symp_bands_wanted(const mfem_csr_s* A);  // the band count a bind of the patch sweep would take now
 int mfem_symp_bands(const mfem_csr_s* A);         // the bound copy's band count; unbound: what a bind would take
+// THE decision whether the patch sweep of a bind covers whole patches only (symp_trim_decide.h), and the bound copy's answer (unbound: what a bind would take)
+int mfem_symp_trim_wanted(const mfem_csr_s* A);
+int mfem_symp_trim(const mfem_csr_s* A);
+int64_t mfem_symp_copy_doubles(const mfem_csr_s* A, int B, int trim);  // doubles of the patch-major copy and the rim copy behind it (stored form: the larger one)
+int64_t mfem_symp_swept_rows(const mfem_csr_s* A);                     // rows the patches cover (bound copy's geometry; unbound: what a bind would take)
 // THE decision which form the main part of a patch-major copy gets (spmv_symp.h): 1 = the diagonal as one-byte ulp codes -- only where the copy is
 // filled by k_symp_fill (`fast`: mfem_dia_fill_fast) with the symmetric scaling, whose diagonal is a_ii * (t_i * t_i) = 1.0 up to a few roundings
 int mfem_symp_coded_wanted(DiaKernel k, bool fast, const double* ssym);

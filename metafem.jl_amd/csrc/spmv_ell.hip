@@ -41,6 +41,7 @@ extern "C" int mfem_debug_set_ell(int enable) try {
   ++mfem_debug_epoch;
   g_ell.enable = enable & 1;
   g_ell.dia = (enable & 2) ? 0 : 1;
+  g_ell.symp_trim = (enable & 4) ? 2 : (enable & 8) ? 1 : 0;
   if ((enable >> 8) & 255) g_ell.grid_mult = (enable >> 8) & 255;
   g_ell.shared_x = ((enable >> 16) & 15) == 8 ? 0 : 1;
   g_ell.xcd = (enable >> 20) & 1;
@@ -286,6 +287,18 @@ int mfem_symp_bands_wanted(const mfem_csr_s* A) {
   return A->symp_state == 1 && (int64_t)(A->symp_p1 - A->symp_p0) * A->symp_PL >= SYMP_BANDS2_MIN_ROWS ? 2 : 1;
 }
 int mfem_symp_bands(const mfem_csr_s* A) { return A->symp_B ? A->symp_B : mfem_symp_bands_wanted(A); }
+// Whole patches only (symp_trim_decide.h: a remainder of <= 2 points per line or of one line per plane leaves the sweep and is computed row by row), decided
+// here once per bind.  Measured at 512^3 (B = 2: 1105 -> 1024 patches per plane, 2 -> 3 runs per patch) and 256^3 (B = 1: 585 -> 512 patches), parent and
+// change alternated on one box: profiles/r10_symp_trim_ab_512.txt.  Smaller lattices were not measured and keep every row in a patch: the limit is the
+// smaller measured size (256^3: 1.67e7 swept rows).  Bit 2 of the "ell" knob forces the untrimmed form, bit 3 the trimmed one at any size (the tests).
+#define SYMP_TRIM_MIN_ROWS 16000000
+int mfem_symp_trim_wanted(const mfem_csr_s* A) {
+  if (g_ell.symp_trim) return g_ell.symp_trim == 1 ? 1 : 0;
+  return A->symp_state == 1 && (int64_t)(A->symp_p1 - A->symp_p0) * A->symp_PL >= SYMP_TRIM_MIN_ROWS ? 1 : 0;
+}
+int mfem_symp_trim(const mfem_csr_s* A) { return A->symp_B ? A->symp_trim : mfem_symp_trim_wanted(A); }
+static std::atomic<long long> g_symp_trim_binds{0};  // binds that ended on the patch sweep with rim rows outside its patches (tests, the A/B)
+extern "C" long long mfem_debug_symp_trim_count(void) { return g_symp_trim_binds; }
 // Form of the diagonal in the patch-major copy, decided here once per bind.  Coded (one signed byte per row instead of a double: 0.95 of the 19.7 GB a 512^3
 // product streams) where the fill writes S^-1 A S^-1 itself -- the values of every other bind have an arbitrary diagonal.  Measured:
 // profiles/r09_symp_diag_code_ab_512.txt.  The fill's gate (a diagonal without a code) sends a bind back to the stored form: dia_bind.
@@ -300,7 +313,8 @@ size_t mfem_ell_vals_bytes(const mfem_csr_s* A) {
   size_t bytes = sizeof(double) * (size_t)A->ell_K * (size_t)A->ell_npad;
   if (dia && mfem_dia_kernel_wanted(A) == DIA_SYMP) {  // patch-major copy of the swept planes: room for either band count (the count is decided per bind)
     size_t pm = 0;
-    for (int B = 1; B <= SP_BMAX; ++B) pm = std::max(pm, sizeof(double) * sp_step(B) * (size_t)mfem_symp_steps(A, B));
+    for (int B = 1; B <= SP_BMAX; ++B)
+      for (int trim = 0; trim <= 1; ++trim) pm = std::max(pm, sizeof(double) * (size_t)mfem_symp_copy_doubles(A, B, trim));  // (and either extent: the knob is read by the bind)
     bytes += pm;
   }
   return bytes;
@@ -310,12 +324,15 @@ size_t mfem_ell_vals_bytes(const mfem_csr_s* A) {
 static int dia_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, const double* ssym) {
   bool direct = false, fp_made = false;
   DiaKernel k = mfem_dia_kernel_wanted(A, DIA_NONE, &direct);
+  A->symp_trim = mfem_symp_trim_wanted(A);
   A->symp_B = mfem_symp_bands_wanted(A);  // (A is unbound here: the geometry below is this count's)
   A->symp_DC = mfem_symp_coded_wanted(k, mfem_dia_fill_fast(A, dsc, direct), ssym);
   A->symp_dneg = 0;
   double* pvals = buf + (size_t)A->ell_K * (size_t)A->ell_npad;
   SympGeom G = k == DIA_SYMP ? mfem_symp_geom(ctx, A) : SympGeom{};
-  int rc = mfem_dia_copy(ctx, A, vals, buf, dsc, ssym, G, direct ? pvals : nullptr, g_ell.symp_fingerprint != 0, &fp_made);
+  // the rim rows' compact copy lies behind the patch-major one (whose length depends on the form of the diagonal: placed per copy)
+  auto rim_of = [&](const SympGeom& g) -> double* { return k == DIA_SYMP && g.rim_units > 0 ? pvals + (int64_t)g.NR * g.NPk * (g.p1 - g.p0) * sp_step(g.B, g.DC) : nullptr; };
+  int rc = mfem_dia_copy(ctx, A, vals, buf, dsc, ssym, G, direct ? pvals : nullptr, rim_of(G), g_ell.symp_fingerprint != 0, &fp_made);
   while (!rc && (k == DIA_SYMP || k == DIA_SYM27)) {  // a sweep: are the pairs it mirrors bitwise equal?
     bool ok = false, dc_refused = false;
     rc = mfem_sym_verdict(ctx, A, k, buf, pvals, G, direct, fp_made, &ok, &dc_refused, &A->symp_dneg);
@@ -323,12 +340,12 @@ static int dia_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, doub
     if (dc_refused) {  // a swept row's scaled diagonal has no code: the same copy in the stored form, and its verdict
       A->symp_DC = 0;
       G = mfem_symp_geom(ctx, A);
-      rc = mfem_dia_copy(ctx, A, vals, buf, dsc, ssym, G, pvals, g_ell.symp_fingerprint != 0, &fp_made);
+      rc = mfem_dia_copy(ctx, A, vals, buf, dsc, ssym, G, pvals, rim_of(G), g_ell.symp_fingerprint != 0, &fp_made);
       continue;
     }
     if (ok) break;
     // the other kernels read all rows from the slot-major copy: after a direct fill the swept rows go there now
-    if (k == DIA_SYMP && direct) rc = mfem_dia_copy(ctx, A, vals, buf, dsc, ssym, SympGeom{}, nullptr, false, &fp_made);
+    if (k == DIA_SYMP && direct) rc = mfem_dia_copy(ctx, A, vals, buf, dsc, ssym, SympGeom{}, nullptr, nullptr, false, &fp_made);
     k = mfem_dia_kernel_wanted(A, k);
   }
   if (rc) return rc;
@@ -337,11 +354,12 @@ static int dia_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, doub
   A->ell_bound_mode = 2;
   A->dia_kernel = k;
   A->symp_vals = k == DIA_SYMP ? pvals : nullptr;
-  if (k != DIA_SYMP) A->symp_B = A->symp_DC = 0;
+  if (k != DIA_SYMP) A->symp_B = A->symp_DC = A->symp_trim = 0;
   if (!A->symp_DC) A->symp_dneg = 0;
   if (k == DIA_SYMP) {  // (the byte accounting of the unbound pattern answers for this bind)
     A->symp_dc_last = A->symp_DC;
     if (A->symp_DC) ++g_symp_coded_binds;
+    if (G.rim_units > 0) ++g_symp_trim_binds;
   }
   return MFEM_OK;
 }
@@ -373,7 +391,7 @@ void mfem_ell_unbind(mfem_csr_s* A) {
   A->ell_bound_mode = A->dia_kernel = DIA_NONE;
   A->ell_vals = A->symp_vals = nullptr;
   A->ell_src = nullptr;
-  A->symp_B = A->symp_DC = A->symp_dneg = 0;
+  A->symp_B = A->symp_DC = A->symp_dneg = A->symp_trim = 0;
 }
 void mfem_ell_free(mfem_csr_s* A) {
   if (A->ell_cols) hipFree(A->ell_cols);
@@ -445,6 +463,7 @@ int64_t mfem_ell_design_bytes(const mfem_context_s* ctx, const mfem_csr_s* A) {
   const int64_t reg = (int64_t)A->dia_regular_blocks * 128;
   int64_t b = ent * 8 + A->n * 16 + (A->n > reg ? A->n - reg : 0) * (int64_t)A->ell_K * 4;  // (rows in generic blocks read their columns)
   // the patch sweep stages a (4 B + 2) x (32 + 2) neighbourhood of x per step instead of reading each swept entry once
-  if (sym == 2) b += mfem_symp_steps(A) * (int64_t)sp_xn(mfem_symp_bands(A)) * 8 - (int64_t)(A->symp_p1 - A->symp_p0) * A->symp_PL * 8;
+  // (a rim row of a trimmed sweep reads x like a row outside the swept planes)
+  if (sym == 2) b += mfem_symp_steps(A) * (int64_t)sp_xn(mfem_symp_bands(A)) * 8 - mfem_symp_swept_rows(A) * 8;
   return b;
 }

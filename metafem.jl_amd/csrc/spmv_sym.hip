@@ -218,6 +218,12 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_sym27_check(int K, const DiaOffs
 //     the speed depends on the gate.  MODE 1 does not use the diagonal and only follows the layout; the tail rows, k_symp_bind and k_dia_vals keep the stored
 //     form.  512^3: 3.62 -> 3.45 ms per launch, 256^3 (B = 1): 0.543 -> 0.518 ms (profiles/r09_symp_diag_code_ab_512.txt); 256 VGPRs + 138 AGPRs, no scratch,
 //     41.2 KB of LDS as before.
+//   * Whole patches only (the form is decided per bind, mfem_symp_trim_wanted; symp_trim_decide.h): a 513-point line leaves a 17th patch column with ONE valid column,
+//     a 513-line plane a 65th patch row with one line -- 81 of 1105 patches per plane whose steps read a whole edge block and x neighbourhood, pass both barriers
+//     and hold a wave slot.  Trimmed, Gm.NR x Gm.NPk patches cover lines [0, ms1) x points [0, ms2) and the rim rows are computed a lane per row from a compact
+//     copy behind the patch-major one (symp_rim_unit: the sweep's waves take its 64-row units after their runs).  Nothing changes in the step body: lane
+//     validity and the x offsets keep using m1, m2, and a halo cell next to the rim is filled from the edge block as before.  512^3: 1024 patches, 3 runs per
+//     patch = 4 x 768 slots exactly; 3.46 -> 3.30 ms per launch, 256^3 0.518 -> 0.482 ms (profiles/r10_symp_trim_ab_512.txt).
 //   * Rows outside the swept planes (first / last lattice plane, the planes next to the ghost planes of a slab) come from the slot-major
 //     copy through the per-row code: the sweep's waves take them in 128-row units after their runs (unsplit SpMV: one launch, no tail);
 //     in a split (multi-rank) SpMV they are the boundary part, a launch of their own (k_spmv_dia_outside) after the halo has arrived.
@@ -240,6 +246,47 @@ static int symp_upload_tables(int device) {  // __constant__ data is per device
   MFEM_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(c_sp_ecell), h, sizeof(h)));
   if (device >= 0 && device < 64) done[device] = true;
   return MFEM_OK;
+}
+
+// One unit of SPT_UNIT rim rows of a trimmed sweep (symp_trim_decide.h), a lane per row: the row's 27 slots from the compact copy (slot-major inside the
+// unit: every slot one 512-byte piece), x at r + off[s] -- clamped as xidx clamps: a position outside the vector is only ever met by an absent entry, a
+// stored zero --, 27 products rounded, then added, in slot order with a zero slot skipped: what dia_rows computes for the row, bit for bit.
+__device__ __forceinline__ void symp_rim_unit(const SympGeom& Gm, const double* __restrict__ rimv, int64_t u, int lane, const double* __restrict__ x,
+                                              double* __restrict__ y, double alpha, double beta, const double* __restrict__ dotw, double& dot_acc) {
+  const int64_t g = u * SPT_UNIT + lane;
+  if (g >= Gm.rim_rows) return;
+  const int pl = (int)(g / Gm.rim_pp);
+  int j = 0, k = 0;
+  spt_rim_row((int)(g - (int64_t)pl * Gm.rim_pp), Gm.m2, Gm.ms1, Gm.ms2, j, k);
+  const int64_t r = (int64_t)(Gm.p0 + pl) * Gm.PL + (int64_t)j * Gm.m2 + k;
+  const double* v = rimv + u * SPT_UNIT_DOUBLES + lane;
+  double vv[27], xv[27];
+#pragma unroll
+  for (int s = 0; s < 27; ++s) {
+    vv[s] = SYM_LD(v + s * SPT_UNIT);
+    int64_t idx = r + (int64_t)(s / 9 - 1) * Gm.PL + (int64_t)(sp_dj(s) * Gm.m2 + sp_dk(s));
+    idx = idx < 0 ? 0 : idx;
+    xv[s] = x[idx < Gm.nx ? idx : Gm.nx - 1];
+  }
+  double acc = 0.0;
+#pragma unroll
+  for (int s = 0; s < 27; ++s) acc += vv[s] != 0.0 ? vv[s] * xv[s] : 0.0;  // (the select keeps the product and the sum apart, as in dia_rows)
+  double y0 = alpha * acc;
+  if (beta != 0.0) y0 += beta * y[r];
+  y[r] = y0;
+  if (dotw) dot_acc += y0 * dotw[r];
+}
+// the rim rows in a launch of their own: beside the boundary part of a split SpMV, or with bit 26 of the "ell" knob
+__global__ __launch_bounds__(64) void k_symp_rim(SympGeom Gm, const double* __restrict__ rimv, const double* __restrict__ x, double* __restrict__ y,
+                                                  double alpha, double beta, const double* __restrict__ dotw, double* __restrict__ partials,
+                                                  const int32_t* __restrict__ done_flag) {
+  if (done_flag && done_flag[0]) return;
+  double dot_acc = 0.0;
+  for (int64_t u = blockIdx.x; u < Gm.rim_units; u += gridDim.x) symp_rim_unit(Gm, rimv, u, threadIdx.x, x, y, alpha, beta, dotw, dot_acc);
+  if (partials) {
+    const double w = wave_reduce_sum(dot_acc);
+    if (threadIdx.x == 0) partials[blockIdx.x] = w;
+  }
 }
 
 // B bands of SP_L lines per patch.  Per plane the wave runs its bands top to bottom as sub-steps of one step body (lane <-> two points of line lj of the
@@ -520,6 +567,10 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
                              tail.lo, tail.hi);
     }
   }
+  if (MODE == 0 && tail.rim) {  // the rim rows of a trimmed sweep: their compact copy lies behind the patch-major one
+    const double* rimv = pv + (int64_t)NP * nplanes * (MAINB + LOWB);
+    for (int64_t u = blockIdx.x; u < Gm.rim_units; u += gridDim.x) symp_rim_unit(Gm, rimv, u, lane, x, y, alpha, beta, dotw, dot_acc);
+  }
   if (MODE == 1) {
     if (fail) atomicOr(bad, 1);
   } else if (partials) {
@@ -656,34 +707,53 @@ static int sym27_grid(const mfem_context_s* ctx, const mfem_csr_s* A, int64_t* n
 }
 // runs per patch: the smallest count that fills >= 90 % of the resident one-wave workgroups in whole rounds (a run's first step has no
 // history: runs stay >= 16 planes long)
-static int symp_nseg(const mfem_context_s* ctx, const mfem_csr_s* A) {
-  const int B = mfem_symp_bands(A);
-  const int64_t NP = (int64_t)((A->symp_NS + B - 1) / B) * A->symp_NPk, slots = (int64_t)sp_wg_per_cu(B) * ctx->num_cus;  // the form's own resident slots
-  const int nplanes = A->symp_p1 - A->symp_p0;
-  int best = 1;
-  double best_eff = 0.0;
-  for (int ns = 1; ns <= (nplanes / 16 > 1 ? nplanes / 16 : 1) && ns <= 64; ++ns) {
-    const int64_t R = NP * ns, rounds = (R + slots - 1) / slots;
-    const double eff = (double)R / (double)(rounds * slots);
-    if (eff > best_eff + 1e-9) { best_eff = eff; best = ns; }
-    if (eff >= 0.9) { best = ns; break; }
-  }
-  return best;
+struct SympExt { int ms1, ms2, NS, NPk, NR; };  // swept extents of a plane and the strips, patch columns and patch rows that cover them
+static SympExt symp_ext(const mfem_csr_s* A, int B, int trim) {
+  SympExt e;
+  e.ms1 = spt_ms1(A->symp_m1, B, trim != 0);
+  e.ms2 = spt_ms2(A->symp_m2, trim != 0);
+  e.NS = (e.ms1 + SP_L - 1) / SP_L;
+  e.NPk = spt_cols(e.ms2);
+  e.NR = spt_rows(e.ms1, B);
+  return e;
+}
+static SympExt symp_ext(const mfem_csr_s* A) { return symp_ext(A, mfem_symp_bands(A), mfem_symp_trim(A)); }
+static int symp_nseg(const mfem_context_s* ctx, const mfem_csr_s* A) {  // (the rule: spt_nseg, symp_trim_decide.h)
+  const SympExt e = symp_ext(A);
+  return spt_nseg((int64_t)e.NR * e.NPk, (int64_t)sp_wg_per_cu(mfem_symp_bands(A)) * ctx->num_cus, A->symp_p1 - A->symp_p0);  // the form's own resident slots
 }
 SympGeom mfem_symp_geom(const mfem_context_s* ctx, const mfem_csr_s* A) {  // (nx = n: the sweep stages owned entries of x only -- swept rows reference no ghost column)
   const int B = mfem_symp_bands(A);
-  return SympGeom{A->symp_PL, A->n, A->symp_m1, A->symp_m2, A->symp_p0, A->symp_p1, A->symp_NS, A->symp_NPk, symp_nseg(ctx, A), B, (A->symp_NS + B - 1) / B, A->symp_DC, sp_unit_bits(A->symp_dneg)};
+  const SympExt e = symp_ext(A);
+  SympGeom G{A->symp_PL, A->n, A->symp_m1, A->symp_m2, A->symp_p0, A->symp_p1, e.NS, e.NPk, symp_nseg(ctx, A), B, e.NR, A->symp_DC, sp_unit_bits(A->symp_dneg)};
+  G.ms1 = e.ms1;
+  G.ms2 = e.ms2;
+  G.rim_pp = spt_rim(G.m1, G.m2, G.ms1, G.ms2);
+  G.rim_rows = (int64_t)G.rim_pp * (G.p1 - G.p0);
+  G.rim_units = spt_units(G.rim_rows);
+  return G;
 }
-int64_t mfem_symp_steps(const mfem_csr_s* A, int B) {
+int64_t mfem_symp_steps(const mfem_csr_s* A, int B, int trim) {
   if (B < 1) B = mfem_symp_bands(A);
-  return (int64_t)((A->symp_NS + B - 1) / B) * A->symp_NPk * (A->symp_p1 - A->symp_p0);
+  const SympExt e = symp_ext(A, B, trim < 0 ? mfem_symp_trim(A) : trim);
+  return (int64_t)e.NR * e.NPk * (A->symp_p1 - A->symp_p0);
 }
+int64_t mfem_symp_copy_doubles(const mfem_csr_s* A, int B, int trim) {
+  const SympExt e = symp_ext(A, B, trim);
+  return mfem_symp_steps(A, B, trim) * sp_step(B) + spt_units((int64_t)spt_rim(A->symp_m1, A->symp_m2, e.ms1, e.ms2) * (A->symp_p1 - A->symp_p0)) * SPT_UNIT_DOUBLES;
+}
+int64_t mfem_symp_swept_rows(const mfem_csr_s* A) {
+  const SympExt e = symp_ext(A);
+  return (int64_t)(A->symp_p1 - A->symp_p0) * e.ms1 * e.ms2;
+}
+#define SYMP_RIM_GRID 256  // workgroups of k_symp_rim at the most (one partial sum each)
 static int symp_grid(const mfem_context_s* ctx, const mfem_csr_s* A) {
   const int B = mfem_symp_bands(A);
-  const int64_t NP = (int64_t)((A->symp_NS + B - 1) / B) * A->symp_NPk;
+  const SympExt e = symp_ext(A);
+  const int64_t NP = (int64_t)e.NR * e.NPk;
   int64_t g = 8 * ((NP + 7) / 8) * symp_nseg(ctx, A);  // every XCD's share of the runs, padded to the largest share
   int64_t cap = (int64_t)sp_wg_per_cu(B) * ctx->num_cus;
-  if (cap > MFEM_MAX_PARTIALS - 1024) cap = MFEM_MAX_PARTIALS - 1024;
+  if (cap > MFEM_MAX_PARTIALS - 1024 - SYMP_RIM_GRID) cap = MFEM_MAX_PARTIALS - 1024 - SYMP_RIM_GRID;  // (the boundary part's and the rim launch's partial sums follow)
   cap &= ~(int64_t)7;
   if (g > cap) g = cap;
   return g < 8 ? 8 : (int)g;
@@ -691,19 +761,22 @@ static int symp_grid(const mfem_context_s* ctx, const mfem_csr_s* A) {
 
 // Matrix entries (8 B) one product by sweep k reads from memory.  Tile sweep: K per padded row less what it takes from LDS.  Patch sweep: the rows
 // outside the swept planes read their K slots; the sweep reads the 14 upper slots of every valid lane pair and the edge block per step + the nine
-// previous-plane slots wherever a run or a patch starts.  (The form of the diagonal: the bound copy's; unbound: the last patch-sweep bind's.)
+// previous-plane slots wherever a run or a patch starts; a trimmed sweep has whole patches only and its rim rows read their 27 slots.  (The form of the
+// diagonal: the bound copy's; unbound: the last patch-sweep bind's.)
 int64_t mfem_sym_entries(const mfem_context_s* ctx, const mfem_csr_s* A, DiaKernel k) {
   if (k == DIA_SYM27) {
     const int64_t nch = A->sym_c1 - A->sym_c0;
     return (int64_t)A->ell_K * A->ell_npad - ((nch - sym27_grid(ctx, A, nullptr)) * A->sym_mx + nch * A->sym_myz);
   }
   const int B = mfem_symp_bands(A);
-  const int NP = (A->symp_NS + B - 1) / B * A->symp_NPk, nplanes = A->symp_p1 - A->symp_p0, nseg = symp_nseg(ctx, A);
+  const SympExt x = symp_ext(A);
+  const int NP = x.NR * x.NPk, nplanes = A->symp_p1 - A->symp_p0, nseg = symp_nseg(ctx, A);
   int64_t e = (int64_t)A->ell_K * (A->ell_npad - (int64_t)nplanes * A->symp_PL), codes = 0;
+  e += 27 * (int64_t)spt_rim(A->symp_m1, A->symp_m2, x.ms1, x.ms2) * nplanes;
   for (int patch = 0; patch < NP; ++patch) {
     int64_t nv = 0;  // valid lane pairs of all bands (a band without a valid line is skipped: none of its lanes is valid)
     for (int lp = 0; lp < 64 * B; ++lp) {
-      const int j = (patch / A->symp_NPk) * (SP_L * B) + lp / SP_PW, kk = (patch % A->symp_NPk) * SP_W + 2 * (lp % SP_PW);
+      const int j = (patch / x.NPk) * (SP_L * B) + lp / SP_PW, kk = (patch % x.NPk) * SP_W + 2 * (lp % SP_PW);
       if (j < A->symp_m1 && kk < A->symp_m2) ++nv;
     }
     e += (28 * nv + sp_ne(B)) * nplanes + 18 * nv * nseg;
@@ -791,7 +864,7 @@ int mfem_sym_launch(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const SpmvA
     const SympGeom G = mfem_symp_geom(ctx, A);
     const int64_t lo = (int64_t)G.p0 * G.PL, hi = (int64_t)G.p1 * G.PL;
     SympTail tl{};
-    if (a.part.part == 0 && g_ell.symp_tail) tl = SympTail{1, A->ell_K, A->n, A->ell_npad, lo, hi, O, A->dia_flags, A->ell_cols, A->ell_vals};
+    if (a.part.part == 0 && g_ell.symp_tail) tl = SympTail{1, A->ell_K, G.rim_units > 0, A->n, A->ell_npad, lo, hi, O, A->dia_flags, A->ell_cols, A->ell_vals};
     if (a.part.part != 2) {
       np = symp_grid(ctx, A);
       hipLaunchKernelGGL(symp_kernel<0>(G), dim3(np), dim3(64), 0, ctx->stream, G, (const double*)A->symp_vals, a.x, a.y, a.alpha, a.beta, a.dotw,
@@ -803,6 +876,13 @@ int mfem_sym_launch(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const SpmvA
       const int rc = mfem_dia_launch_outside(ctx, A, a, a.partials ? a.partials + np : nullptr, lo, hi, &go);
       if (rc) return rc;
       np += go;
+      if (G.rim_units > 0) {  // the rim rows of the swept planes: no ghost column, but one launch with the other rows the sweep leaves out
+        const int gr = (int)(G.rim_units < SYMP_RIM_GRID ? G.rim_units : SYMP_RIM_GRID);
+        hipLaunchKernelGGL(k_symp_rim, dim3(gr), dim3(64), 0, ctx->stream, G, (const double*)A->symp_vals + (int64_t)G.NR * G.NPk * (G.p1 - G.p0) * sp_step(G.B, G.DC),
+                           a.x, a.y, a.alpha, a.beta, a.dotw, a.partials ? a.partials + np : nullptr, a.done_flag);
+        MFEM_CHECK_LAUNCH();
+        np += gr;
+      }
     }
   }
   if (a.n_partials && a.partials) *a.n_partials = np;
