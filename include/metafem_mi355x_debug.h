@@ -158,14 +158,20 @@ int64_t mfem_debug_hex27_rows_count(void);
 int64_t mfem_debug_hex27_mixed_count(void);
 /* number of hex-27 matrix assemblies that took the scratch-free path so far (process-wide) */
 int64_t mfem_debug_hex27_direct_count(void);
-/* hex-8 elasticity kernels.  Bit 0: matrix -- 0 (default) thread per (control point, element) with the rows accumulated in LDS and
- * written once; 1 the earlier row-owner kernel accumulating in global memory (equal to round-off: other summation order, table form of
- * the Jacobian).  Bit 1: residual -- 0 (default) the plane-sweep kernel with one sum-factorised integration per element (2-point Gauss
- * rule); 1 the kernel that integrates an element once per adjacent control point (table form; equal to round-off).  Bits 2-4: TIMING-ONLY
- * ablations of the default matrix kernel (wrong values): no accumulation steps / no write-out / no integration (tools/el_time.py). */
+/* hex-8 elasticity kernels; bits 0-5 of the word are read (the decode: H8ElasticityKnobs, csrc/hex8_decide.h).  Bit 0: matrix -- 0 (default)
+ * thread per (control point, element) with the rows accumulated in LDS and written once; 1 the earlier row-owner kernel accumulating in
+ * global memory (equal to round-off: other summation order, table form of the Jacobian).  Bit 1: residual -- 0 (default) the plane-sweep
+ * kernel with one sum-factorised integration per element (2-point Gauss rule; every other rule takes the kernel of bit 1); 1 the kernel that
+ * integrates an element once per adjacent control point (table form; equal to round-off).  Bits 2-4: TIMING-ONLY ablations of the default
+ * matrix kernel (wrong values): bit 2 no accumulation steps, bit 3 no write-out, bit 4 no integration (tools/el_time.py).  Bit 5: the default
+ * matrix kernel integrates affine elements like any other, without the reference-integral shortcut (equal to round-off). */
 /* ^ key "elasticity": mfem_debug_set("elasticity", a, b) with (int variant) = (a[, b]) */
-/* hex-8 thermal matrix / residual kernels: 0 (default) the plane-sweep kernels with sum-factorised element integration
- * (2- and 3-point Gauss rules; other rules always use the tile kernels); 1 the 4 x 4 x 8 tile kernels with the table form. */
+/* hex-8 thermal matrix / residual kernels; bits 0-5 of the word are read (the decode: H8ThermalKnobs, csrc/hex8_decide.h).  Bit 0: 0 (default)
+ * the plane-sweep kernels with sum-factorised element integration (2- and 3-point Gauss rules; other rules always use the tile kernels); 1 the
+ * 4 x 4 x 8 tile kernels with the table form.  Bit 1: the matrix sweep writes every row per thread instead of staging full rows through LDS
+ * (the same bits).  Bit 2: both sweeps integrate affine elements like any other, without the one-adjugate shortcut (equal to round-off).
+ * Bits 3-5: TIMING-ONLY ablations of the matrix sweep (wrong values): bit 3 no integration, bit 4 no gather from LDS, bit 5 no staged
+ * write-out (tools/thermal_sweep_ablate.py). */
 /* ^ key "hex8_thermal": mfem_debug_set("hex8_thermal", a, b) with (int variant) = (a[, b]) */
 /* Per-launch timing of the solver's SpMV kernel with hip events on the context stream (bench.py's roofline).
  * read: total device ms and launch count since the last reset. */

@@ -371,7 +371,7 @@ SF_HD bool sf_is_affine(const double (&X)[3][2][4]) {
 }
 
 // ---- thermal element matrix, the 36 unique entries of the symmetric 8 x 8 Ke = sum_q w det (-k) grad N_a . grad N_b.
-// Node a = ax + 2 ay + 4 az (tensor order, x fastest = c_dN's order); packing ke36[sym36(a, b)] of assemble_hex8.hip.
+// Node a = ax + 2 ay + 4 az (tensor order, x fastest = c_dN's order); packing ke36[sym36(a, b)] of hex8_thermal.hip.
 SF_HD constexpr int sf_sym36(int a, int b) {
   return a <= b ? a * 8 - (a * (a - 1)) / 2 + (b - a) : b * 8 - (b * (b - 1)) / 2 + (a - b);
 }

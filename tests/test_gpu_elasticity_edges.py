@@ -257,7 +257,7 @@ def test_quadrature_orders_share_their_rule(mf):
 
 # ---- C. lattice edges ------------------------------------------------------------------------------------------------------------
 PEN_C, TRA_C = "x0|y1", "z1|y0"
-# The residual sweep cuts the planes into segments of L = 4 at every size here (sweep_planes: L halves from 32 while the grid stays below
+# The residual sweep cuts the planes into segments of L = 4 at every size here (h8_residual_sweep: L halves from 32 while the grid stays below
 # 2048 workgroups, down to 4), so 10 planes are segments of 4, 4, 2 and 5 planes are segments of 4 and 1.
 CASES_C = [(1, 1, 1), (2, 1, 1), (1, 1, 40), (1, 40, 1), (40, 1, 1),  # one element thick: a block of 32 control points spans many lines and planes
            (2, 1, 30), (2, 1, 31), (2, 1, 32),                        # lines of 31, 32, 33 control points: a block is a line, one short, one over

@@ -6,7 +6,9 @@ driver, of the CSR SpMV (which kernel, which tile, which inspections) of the sli
 keys, which padding, which instantiation) and of the symmetric lattice tiles (csrc/lat_decide.h: knob words, eligibility, the lattice of row 0,
 geometry and sizes, the split of a slab's launch, the gather grid, the symmetry gate), branch by branch; the host decisions of the hex-27
 thermal assembly (csrc/hex27_decide.h: knob word, path choice, workspace, ring, grids, face schedule, LDS size) against the expressions of the
-driver they were cut out of, their own properties, and the macros the kernel lays its LDS block out with."""
+driver they were cut out of, their own properties, and the macros the kernel lays its LDS block out with; the host decisions of the fused
+hex-8 assembly (csrc/hex8_decide.h: both knob words, kernel choice and flag words, sweep segments and grids, face predicates, block-to-tile
+maps, boundary enumeration, reference tables) in the same three parts."""
 import os
 import subprocess
 
@@ -16,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.mark.parametrize("name", ["host_check_hex8", "host_check_symp", "host_check_lat", "host_check_solve", "host_check_csr", "host_check_sell",
-                                  "host_check_lat_decide", "host_check_hex27"])
+                                  "host_check_lat_decide", "host_check_hex27", "host_check_hex8_decide"])
 def test_host_check(name, tmp_path):
     exe = str(tmp_path / name)
     subprocess.run(["g++", "-O2", "-std=c++17", "-I", os.path.join(ROOT, "metafem.jl_amd", "csrc"),
