@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MFEM_ABI_VERSION 6
+#define MFEM_ABI_VERSION 7
 
 typedef enum {
   MFEM_OK = 0,
@@ -730,6 +730,27 @@ int mfem_mesh_operator_diagonal(mfem_context ctx, uint64_t op, double* d);
  * MFEM_ERR_UNSUPPORTED, nothing launched and x_out untouched: lsqr!, JACOBI_RIGHT_COLNORM, any left preconditioner (they need columns or rows of K
  * or a product with A').  MFEM_ERR_INVALID: scale_in_place, an attached communicator (one rank only), null arguments. */
 int mfem_solve_operator(mfem_context ctx, uint64_t op, const double* b, double* x_out, const mfem_solve_options* opts, mfem_solve_stats* stats);
+
+/* ---- matrix-free operator on hex-8 thermal bricks (new) ---------------------------------------------------------------------------------
+ * K of mfem_brick_assemble_thermal for the same mfem_thermal_params -- the volume term, the Robin faces and the Nitsche fixed_faces (K is
+ * nonsymmetric then) -- without a pattern, values or any scratch: K x is the fused residual with s = 0, Tenv = 0, Tw = 0, evaluated from the brick's
+ * coordinates, which are read LIVE at every product (a caller may move them between solves).  The brick must outlive the handle (an opaque
+ * 64-bit value, 0 = none).  A product is one launch (volume: the plane sweep for itg_order 2-5, 4 x 4 x 8 tiles for 1 and 7; every control point
+ * written once by its owner) plus one over the boundary control points when there are face terms; no atomics, bitwise reproducible.
+ * MFEM_ERR_UNSUPPORTED with a message, nothing created: an order-2 (hex-27) brick, a brick with a slab set (also answered by apply / diagonal /
+ * a solve if the slab is set later). */
+int mfem_brick_operator_create(mfem_context ctx, mfem_brick m, const mfem_thermal_params* p, uint64_t* op /* [host] out */);
+/* Replaces the parameters (how K_linear_func re-sends them): host only, nothing is launched.  MFEM_ERR_INVALID while a solve runs on the operator. */
+int mfem_brick_operator_set_params(uint64_t op, const mfem_thermal_params* p);
+int mfem_brick_operator_destroy(uint64_t op);  /* MFEM_ERR_INVALID while a solve runs on the operator, like set_params, apply and diagonal */
+/* y = alpha K x + beta y (x, y: one entry per control point).  beta == 0 does not read y.  No workspace is taken. */
+int mfem_brick_operator_apply(mfem_context ctx, uint64_t op, const double* x, double* y, double alpha, double beta);
+/* d_i <- |K_ii| where K_ii != 0; a row with an exactly zero diagonal keeps the value the CALLER preset (the guarded rule of
+ * mfem_jacobi_by_diagonal).  K_ii: the diagonal entries of the <= 8 adjacent element matrices plus the point's own face terms -h N_a N_a and
+ * -h_penalty N_a N_a + k N_a n . grad N_a; no row and no element matrix is stored. */
+int mfem_brick_operator_diagonal(mfem_context ctx, uint64_t op, double* d);
+/* mfem_solve_operator takes a brick operator's handle as it takes a mesh operator's (every handle starts with a kind tag): same options, same
+ * refusals, same spmv_count formulas; the workspace is the solver's vectors only. */
 
 /* ---- multi-GPU (new; the reference is single-GPU, F6) ------------------------------------ */
 /* 128-byte RCCL unique id, created on rank 0 and shipped to the other ranks by the host

@@ -140,6 +140,8 @@ int64_t mfem_debug_mesh_residual_count(void);
 /* number of matrix-free operator applications the host launched (process-wide): mfem_mesh_operator_apply and every product of mfem_solve_operator
  * (a product inside a captured solver cycle counts once, when the cycle is captured) */
 int64_t mfem_debug_mesh_operator_count(void);
+/* the same for the hex-8 brick operator: mfem_brick_operator_apply and every product of mfem_solve_operator on a brick operator's handle */
+int64_t mfem_debug_brick_operator_count(void);
 /* number of mfem_mesh_var_* / mfem_mesh_res_* / mfem_mesh_kval_* calls that took a table-free launch (process-wide) */
 int64_t mfem_debug_mesh_ops_count(void);
 /* variants of the fused mesh assembly launched so far (process-wide), one bit per (dim, mode, kind): bit ((dim - 2) * 3 + mode) * 9 + kind, mode 0

@@ -21,7 +21,7 @@ import LinearAlgebra
 
 # ---- library handle and error convention ---------------------------------------------------------------------------------
 const lib = get(ENV, "METAFEM_MI355X_LIB", joinpath(@__DIR__, "..", "metafem.jl_amd", "libmetafem_mi355x.so"))
-const ABI_VERSION = 6    # == MFEM_ABI_VERSION
+const ABI_VERSION = 7    # == MFEM_ABI_VERSION
 
 struct MFEMError <: Exception
     rc::Cint
@@ -670,6 +670,57 @@ function iterative_Solve!(op::MeshOperator, residue, converge_tol; Sv_func!::Sym
     return x
 end
 mesh_operator_count() = ccall((:mfem_debug_mesh_operator_count, lib), Int64, ())
+
+# ---- matrix-free operator on hex-8 thermal bricks (mfem_brick_operator_*, mfem_solve_operator) -------------------------------------
+# K of mfem_brick_assemble_thermal without K_J_ptr / K_J / K_total: K x is evaluated from the brick's coordinates (read live at every product).
+# The brick is kept alive by the operator; hex-27 bricks and bricks with a slab are refused (`nothing`; mfem_last_error says why).
+mutable struct BrickOperator
+    h::UInt64
+    n::Int64
+    brick::Brick
+end
+
+function brick_operator(brick::Brick, p::ThermalParams)
+    h = Ref{UInt64}(0)
+    rc = ccall((:mfem_brick_operator_create, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{ThermalParams}, Ref{UInt64}), ctx(), brick.h, Ref(p), h)
+    rc == -3 && return nothing
+    check(rc)
+    n = ccall((:mfem_brick_num_controlpoints, lib), Int64, (Ptr{Cvoid},), brick.h)
+    op = BrickOperator(h[], n, brick)
+    finalizer(o -> (ccall((:mfem_brick_operator_destroy, lib), Cint, (UInt64,), o.h); o.h = 0), op)
+    return op
+end
+
+"Re-sends the parameters (K_linear_func of a matrix-free domain): host only."
+brick_operator_set_params!(op::BrickOperator, p::ThermalParams) =
+    check(ccall((:mfem_brick_operator_set_params, lib), Cint, (UInt64, Ref{ThermalParams}), op.h, Ref(p)))
+
+"y = alpha K x + beta y"
+operator_mul!(y, op::BrickOperator, x, alpha = 1.0, beta = 0.0) =
+    check(ccall((:mfem_brick_operator_apply, lib), Cint, (Ptr{Cvoid}, UInt64, Ptr{Cvoid}, Ptr{Cvoid}, Float64, Float64),
+                ctx(), op.h, dptr(x), dptr(y), alpha, beta))
+
+"|diag K| under the guarded rule: a row with a zero diagonal keeps 1."
+function operator_diagonal(op::BrickOperator)
+    d = AMDGPU.ones(Float64, op.n)
+    check(ccall((:mfem_brick_operator_diagonal, lib), Cint, (Ptr{Cvoid}, UInt64, Ptr{Cvoid}), ctx(), op.h, dptr(d)))
+    return d
+end
+
+"iterative_Solve! on the brick operator: the options and refusals of the mesh operator's."
+function iterative_Solve!(op::BrickOperator, residue, converge_tol; Sv_func!::Symbol = :idrs!, Pr_func!::Symbol = :Pr_Jacobi!, max_pass = 4,
+                          maxiter = 2000, s = 0, seed::UInt64 = 0x5EED, checkiter::Integer = 200)
+    x = AMDGPU.zeros(Float64, op.n)
+    l_or_s = Sv_func! == :tfqmr! ? checkiter : s
+    opts = Ref(SolveOptions(method = SOLVER_ID[Sv_func!], precond = PR_ID[Pr_func!], l_or_s = l_or_s, maxiter = maxiter, max_pass = max_pass,
+                            converge_tol = converge_tol, seed = seed))
+    stats = Ref{SolveStats}()
+    check(ccall((:mfem_solve_operator, lib), Cint, (Ptr{Cvoid}, UInt64, Ptr{Cvoid}, Ptr{Cvoid}, Ref{SolveOptions}, Ref{SolveStats}),
+                ctx(), op.h, dptr(residue), dptr(x), opts, stats))
+    println("pass $(stats[].passes) with res = $(stats[].final_res) iter = $(stats[].iterations).")
+    return x
+end
+brick_operator_count() = ccall((:mfem_debug_brick_operator_count, lib), Int64, ())
 
 # ---- several GPUs: one Julia process per GPU (MPI.jl), slab decomposition along the first dimension ---------------------------
 "Rank 0 creates the 128-byte RCCL id; the host broadcasts it (MPI.Bcast!)."

@@ -29,7 +29,7 @@ import torch
 from . import _lib
 from ._lib import (ElasticityParams, MetaFEMError, OpLayout, SolveOptions, SolveStats, ThermalParams, check, lib)
 
-__all__ = ["Context", "FEM_SpMat_CSR", "MeshOperator", "mul_", "tmul_", "dot", "nrm2", "axpby_", "FEM_rand", "normalized_norm",
+__all__ = ["Context", "FEM_SpMat_CSR", "MeshOperator", "BrickOperator", "BrickOperatorRefused", "brick_operator_refusal", "mul_", "tmul_", "dot", "nrm2", "axpby_", "FEM_rand", "normalized_norm",
            "iterative_Solve", "Brick", "make_Brick", "ThermalDomain", "MetaFEMError", "SolveStats",
            "cg_", "bicgstabl_GS_", "idrs_", "cgs2_", "gmres_", "cgs_", "tfqmr_", "lsqr_", "FACE_BITS"]
 
@@ -255,11 +255,68 @@ class MeshOperator:
             pass
 
 
+class BrickOperatorRefused(MetaFEMError):
+    """mfem_brick_operator_create answered MFEM_ERR_UNSUPPORTED; the message is the library's."""
+
+
+class BrickOperator:
+    """Matrix-free K of a hex-8 thermal brick (mfem_brick_operator_*, csrc/brick_operator.hip): the matrix of Brick.assemble_thermal for the same
+    parameters, evaluated from the brick's coordinates (read live: they may move between solves) -- no pattern, no values, no scratch.  Stands where
+    a FEM_SpMat_CSR and its values stand: `mul_(b, op, None, x)` and `iterative_Solve(op, None, residue, ...)` take it.  Made by
+    Brick.thermal_operator; raises BrickOperatorRefused (a MetaFEMError) with the library's message for a brick it refuses (hex-27, a slab)."""
+
+    def __init__(self, brick: "Brick", params: "ThermalParams"):
+        self.ctx, self.brick = brick.ctx, brick  # (the library borrows the brick: kept alive here)
+        self.n = brick.ncp
+        self.nnz = 0
+        self._h = C.c_uint64()
+        rc = lib.mfem_brick_operator_create(self.ctx._h, brick._h, C.byref(params), C.byref(self._h))
+        if rc == -3:  # MFEM_ERR_UNSUPPORTED: a brick the operator does not cover
+            raise BrickOperatorRefused(lib.mfem_last_error().decode())
+        check(rc)
+        self.params = params
+        self.ctx._children.add(self)
+
+    def set_params(self, k: float, h: float = 0.0, Tenv: float = 0.0, robin_faces: int = 0, fixed_faces: int = 0, h_penalty: float = 0.0,
+                   Tw: float = 0.0):
+        """Re-sends the parameters (host only, nothing is launched)."""
+        p = ThermalParams(k, h, Tenv, robin_faces, fixed_faces, h_penalty, Tw)
+        check(lib.mfem_brick_operator_set_params(self._h, C.byref(p)))
+        self.params = p
+
+    def mul_(self, y: torch.Tensor, x: torch.Tensor, alpha: float = 1.0, beta: float = 0.0) -> torch.Tensor:
+        """y = alpha K x + beta y (beta == 0: y is not read)."""
+        _need(x, torch.float64, "x", self.n)
+        _need(y, torch.float64, "y", self.n)
+        check(lib.mfem_brick_operator_apply(self.ctx._h, self._h, _ptr(x), _ptr(y), alpha, beta))
+        return y
+
+    def diagonal(self, preset: float = 1.0) -> torch.Tensor:
+        """|diag K| under the guarded rule of jacobi_by_diagonal: a row with an exactly zero diagonal keeps `preset`."""
+        d = torch.full((self.n,), float(preset), dtype=torch.float64, device=f"cuda:{self.ctx.device}")
+        check(lib.mfem_brick_operator_diagonal(self.ctx._h, self._h, _ptr(d)))
+        return d
+
+    def close(self):
+        if self._h:
+            lib.mfem_brick_operator_destroy(self._h)
+            self._h = C.c_uint64()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+_OPERATORS = (MeshOperator, BrickOperator)  # what stands in for (A, vals) with vals = None
+
+
 def mul_(b: torch.Tensor, A, vals: Optional[torch.Tensor], x: torch.Tensor, alpha: float = 1.0, beta: float = 0.0):
-    """mul!(b, A, x, alpha, beta): b = alpha*A*x + beta*b (04_GPU_Utils.jl:131).  A MeshOperator takes vals = None."""
-    if isinstance(A, MeshOperator):
+    """mul!(b, A, x, alpha, beta): b = alpha*A*x + beta*b (04_GPU_Utils.jl:131).  A MeshOperator or BrickOperator takes vals = None."""
+    if isinstance(A, _OPERATORS):
         if vals is not None:
-            raise MetaFEMError("a MeshOperator holds no values: pass vals = None")
+            raise MetaFEMError(f"a {type(A).__name__} holds no values: pass vals = None")
         return A.mul_(b, x, alpha, beta)
     _need(vals, torch.float64, "vals", A.nnz)
     _need(x, torch.float64, "x")
@@ -358,14 +415,14 @@ def iterative_Solve(A, K_vals: Optional[torch.Tensor], residue: torch.Tensor, co
     recurrence carrying the preconditioned residual (one vector stream less per iteration), 4 plain CG on the symmetrically Jacobi-scaled
     matrix (one stream less again; on the mirrored-sweep layout, one rank: the auto choice there, else 3).
 
-    A MeshOperator with K_vals = None solves matrix-free (mfem_solve_operator): every Sv_func but lsqr_, Pr_func Identity or Pr_Jacobi_, Pl_func
+    A MeshOperator or a BrickOperator with K_vals = None solves matrix-free (mfem_solve_operator): every Sv_func but lsqr_, Pr_func Identity or Pr_Jacobi_, Pl_func
     Identity, no scale_in_place.
 
     Returns (delta_x, stats); delta_x is a NEW device vector like the reference's return value.
     """
-    matrix_free = isinstance(A, MeshOperator)
+    matrix_free = isinstance(A, _OPERATORS)
     if matrix_free and K_vals is not None:
-        raise MetaFEMError("a MeshOperator holds no values: pass K_vals = None")
+        raise MetaFEMError(f"a {type(A).__name__} holds no values: pass K_vals = None")
     if not matrix_free:
         _need(K_vals, torch.float64, "K_vals", A.nnz)
     _need(residue, torch.float64, "residue", A.n)
@@ -507,6 +564,12 @@ class Brick:
         check(lib.mfem_brick_assemble_thermal(self.ctx._h, self._h, A._h, C.byref(p), _ptr(vals)))
         return vals
 
+    def thermal_operator(self, k: float, h: float = 0.0, Tenv: float = 0.0, robin_faces: int = 0, fixed_faces: int = 0, h_penalty: float = 0.0,
+                         Tw: float = 0.0) -> "BrickOperator":
+        """The matrix-free K of assemble_thermal for the same parameters (BrickOperator).  A hex-27 brick or a brick with a slab raises
+        BrickOperatorRefused."""
+        return BrickOperator(self, ThermalParams(k, h, Tenv, robin_faces, fixed_faces, h_penalty, Tw))
+
     def residual_thermal(self, x_star: torch.Tensor, k: float, h: float = 0.0, Tenv: float = 0.0, robin_faces: int = 0,
                          s: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, *, fixed_faces: int = 0,
                          h_penalty: float = 0.0, Tw: float = 0.0) -> torch.Tensor:
@@ -546,6 +609,16 @@ class Brick:
             pass
 
 
+def brick_operator_refusal(brick: Brick) -> Optional[str]:
+    """The host's forecast of mfem_brick_operator_create's refusals (csrc/brick_operator_decide.h: bop_refusal), or None: lets ThermalDomain decide
+    without a device call.  The library has the last word: ThermalDomain also falls back on BrickOperatorRefused."""
+    if brick.itp_order != 1:
+        return "an order-2 (hex-27) brick: the matrix-free brick operator covers hex-8 bricks"
+    if tuple(brick.slab) != (0, brick.m[0]):
+        return "a brick with a slab set: the matrix-free brick operator runs on the whole lattice, one rank"
+    return None
+
+
 def make_Brick(x, n, itp_order: int = 1, itg_order: int = 3, ctx: Optional[Context] = None) -> Brick:
     return Brick(x, n, itp_order, itg_order, ctx)
 
@@ -578,19 +651,31 @@ class ThermalDomain:
     reference's Newton driver (04_Time_Domain.jl:59-80)."""
 
     def __init__(self, brick: Brick, k: float, h: float, Tenv: float, robin_faces: int = ALL_FACES, *, fixed_faces: int = 0,
-                 h_penalty: float = 0.0, Tw: float = 0.0):
+                 h_penalty: float = 0.0, Tw: float = 0.0, matrix_free: bool = False):
         self.brick, self.k, self.h, self.Tenv, self.robin_faces = brick, k, h, Tenv, robin_faces
         # weakly imposed Dirichlet faces (fix_boundary of examples/thermal_conduction/2D_Script.jl:58)
         self.fixed = dict(fixed_faces=fixed_faces, h_penalty=h_penalty, Tw=Tw)
         dev = f"cuda:{brick.ctx.device}"
-        self.A = brick.pattern(1)  # assemble_Global_Variables! -> assemble_SparseID!
+        # matrix_free = True: no matrix at all.  self.A is a BrickOperator (K x and diag K straight from the coordinates), K_linear = K_total = None,
+        # brick.pattern is never called and K_linear_func only re-sends the parameters; the default linear_solver hands (A, None) to iterative_Solve.
+        # A brick the operator does not cover (brick_operator_refusal) is built as the default domain is: matrix_free is False then and
+        # matrix_free_reason says why (GenericDomain's rule).
+        self.matrix_free_reason = brick_operator_refusal(brick) if matrix_free else None
+        self.matrix_free = bool(matrix_free) and self.matrix_free_reason is None
+        if self.matrix_free:
+            try:
+                self.A = brick.thermal_operator(k, h, Tenv, robin_faces, **self.fixed)
+            except BrickOperatorRefused as e:  # (whatever rule the library applies beyond the host's forecast reaches the fallback too)
+                self.matrix_free, self.matrix_free_reason = False, str(e)
+        if not self.matrix_free:
+            self.A = brick.pattern(1)  # assemble_Global_Variables! -> assemble_SparseID!
         n = self.A.n
         self.basicfield_size = n
         self.x = torch.zeros(n, dtype=torch.float64, device=dev)
         self.dx = torch.zeros(n, dtype=torch.float64, device=dev)
         self.x_star = torch.zeros(n, dtype=torch.float64, device=dev)
         self.residue = torch.zeros(n, dtype=torch.float64, device=dev)
-        self.K_linear = torch.zeros(self.A.nnz, dtype=torch.float64, device=dev)
+        self.K_linear = None if self.matrix_free else torch.zeros(self.A.nnz, dtype=torch.float64, device=dev)
         self.K_total = self.K_linear  # no nonlinear gradients in this form: K_total .= K_linear is an alias
         self.s = torch.zeros(n, dtype=torch.float64, device=dev)  # controlpoints.s
         self.converge_tol = 1e-6
@@ -599,6 +684,9 @@ class ThermalDomain:
         self.history = []
 
     def K_linear_func(self):
+        if self.matrix_free:  # nothing is assembled: the parameters go to the operator
+            self.A.set_params(self.k, self.h, self.Tenv, self.robin_faces, **self.fixed)
+            return
         self.brick.assemble_thermal(self.A, self.k, self.h, self.Tenv, self.robin_faces, out=self.K_linear, **self.fixed)
 
     def K_nonlinear_func(self):

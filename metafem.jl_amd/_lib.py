@@ -248,6 +248,12 @@ SIGNATURES = {
     "mfem_mesh_operator_diagonal": (c_int, [P, c_uint64, P]),
     "mfem_solve_operator": (c_int, [P, c_uint64, P, P, C.POINTER(SolveOptions), C.POINTER(SolveStats)]),
     "mfem_debug_mesh_operator_count": (c_int64, []),
+    "mfem_brick_operator_create": (c_int, [P, P, C.POINTER(ThermalParams), C.POINTER(c_uint64)]),
+    "mfem_brick_operator_set_params": (c_int, [c_uint64, C.POINTER(ThermalParams)]),
+    "mfem_brick_operator_destroy": (c_int, [c_uint64]),
+    "mfem_brick_operator_apply": (c_int, [P, c_uint64, P, P, c_double, c_double]),
+    "mfem_brick_operator_diagonal": (c_int, [P, c_uint64, P]),
+    "mfem_debug_brick_operator_count": (c_int64, []),
     "mfem_mesh_var_elements": (c_int, [P, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, c_int32, c_int32,
                                        C.POINTER(VarBatchTerm), P, P, c_int64]),
     "mfem_mesh_var_facets": (c_int, [P, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, P, P, P, c_int32,

@@ -141,6 +141,7 @@ struct mfem_context_s {
 #define MFEM_PROF_PAIRS 1024
 int mfem_prof_flush(mfem_context_s* ctx);
 
+struct mfem_operator_head;  // operator.h: the kind tag every matrix-free operator handle starts with
 struct mfem_csr_s {
   mfem_context_s* ctx;
   uint64_t serial;          // unique per created pattern (cycle-graph cache key)
@@ -225,10 +226,10 @@ struct mfem_csr_s {
   int64_t rem_last_rows, rem_last_ent;  // what the last ACCEPTED remainder of the last probe held (0: none) -- survives the unbind at the end of a solve (tests, bench.py)
   // transposed pattern for A' x (spmv_t.hip): built by the first mfem_spmv_csr_t or lsqr! solve, dropped by replan / destroy
   struct mfem_tplan_s* tplan;
-  // the internal pattern-less handle (n = n_fields * ncp, nnz = 0) of a matrix-free mesh operator (mesh_operator.hip): op is set while the operator is
-  // bound for a solve -- every product then goes to its launcher --, with the scratch and the column scaling of that solve; op_epoch counts the
-  // operator's term changes (a captured cycle bakes the compiled terms in)
-  struct mfem_mesh_operator_s* op;
+  // the internal pattern-less handle (n rows, nnz = 0) of a matrix-free operator (operator.h: mesh_operator.hip, brick_operator.hip): op is set while
+  // the operator is bound for a solve -- every product then goes to its kind's launcher --, with the scratch and the column scaling of that solve;
+  // op_epoch counts the operator's term / parameter changes (a captured cycle bakes them in)
+  struct mfem_operator_head* op;
   double* op_scratch;
   const double* op_dsc;
   uint64_t op_epoch;
@@ -302,7 +303,7 @@ __attribute__((visibility("hidden"))) CsrKnobs mfem_csr_knobs();  // what mfem_d
 // mode numbers of mfem_csr_solver_layout: the CSR tile kernel on the caller's values (no copy), slot-major copy with explicit columns / with
 // diagonal-slotted regular blocks (spmv_ell.hip, spmv_dia.hip and the sweeps of spmv_sym.hip), row-sorted sliced ELL or its node-blocked form (spmv_sell.hip, spmv_bsell.hip), symmetric lattice tiles (spmv_lat27.hip with spmv_lat27_gather.hip, spmv_lat8.hip)
 enum mfem_layout : int32_t { MFEM_LAYOUT_CSR = 0, MFEM_LAYOUT_ELL = 1, MFEM_LAYOUT_DIA = 2, MFEM_LAYOUT_SELL = 3, MFEM_LAYOUT_LAT27 = 4, MFEM_LAYOUT_LAT8 = 5,
-                             MFEM_LAYOUT_OPERATOR = 6 /* no copy of any values: a bound matrix-free mesh operator (mesh_operator.hip) */ };
+                             MFEM_LAYOUT_OPERATOR = 6 /* no copy of any values: a bound matrix-free operator (operator.h) */ };
 // What a pattern offers a solve: a tile layout (taken if the values pass its symmetry probe) and a row layout, each with the workspace bytes of
 // its copy (MFEM_LAYOUT_CSR, 0: none)
 struct mfem_layout_plan_s {

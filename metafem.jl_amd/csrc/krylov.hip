@@ -15,7 +15,7 @@
 // no-ops; the host polls it every `check_every` iterations.
 #include "krylov.h"
 #include "solve_decide.h"
-#include "mesh_operator.h"
+#include "operator.h"
 #include "mesh_operator_decide.h"
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
@@ -307,7 +307,8 @@ struct SolveRun {
   const double* vals_src;  // what the right scaling is computed from
   double* lay;             // the layout copy
   bool tiles_bound, rows_bound, cg_scaled;
-  mfem_mesh_operator_s* op = nullptr;  // mfem_solve_operator: A is the operator's pattern-less handle, vals is null
+  mfem_operator_head* op = nullptr;  // mfem_solve_operator: A is the operator's pattern-less handle, vals is null
+  const mfem_operator_interface* opi = nullptr;  // ... and its kind's table (operator.h)
 };
 
 // 1. the options; the method (with a communicator: the one all-reduce of n, every rank must take the same decisions)
@@ -924,9 +925,9 @@ extern "C" int mfem_solve(mfem_context ctx, mfem_csr A, double* vals, const doub
   return solve_with_graphs(ctx, A->n, [&]() { return solve_inner(ctx, A, vals, b, x_out, o, stats); });
 } MFEM_API_CATCH("mfem_solve")
 
-// ---- mfem_solve on a matrix-free mesh operator (mesh_operator.hip) ------------------------------------------------------------------------------
-// The same driver with an operator attempt in place of solve_attempt: the workspace holds the vectors and the operator's element-vector scratch
-// (mesh_operator_decide.h: mop_workspace) -- no layout, no copy of a matrix --, the Jacobi vector comes from the operator's diagonal kernel, and the
+// ---- mfem_solve on a matrix-free operator (operator.h: mesh_operator.hip or brick_operator.hip) -------------------------------------------------
+// The same driver with an operator attempt in place of solve_attempt: the workspace holds the vectors and the operator's scratch (the mesh operator's
+// element vectors; the brick operator has none: mesh_operator_decide.h: mop_workspace) -- no layout, no copy of a matrix --, the Jacobi vector comes from the operator's diagonal kernel, and the
 // bound operator serves every product of the unchanged run_passes.  The stages that read CSR values (bind_tiles, try_scaled_cg, left_precond,
 // ws_trial, csr_true_residual) are never entered.  CG keeps K unscaled and takes 1 / d; the solvers on A D^-1 hand d to the product, which gathers
 // x_j / d_j (the role dsc plays for the lattice tiles).
@@ -946,7 +947,7 @@ static int operator_attempt(SolveRun& R) {
   const int64_t nv = V.nv = (int64_t)align_up((size_t)n, 32);
   cg_work_vectors(R.method, R.s_param, V, &R.nclear);
   const int nwork = V.nwork;
-  const OpWorkspace W = mop_workspace(nv, nwork, mfem_mesh_operator_scratch_doubles(R.op),
+  const OpWorkspace W = mop_workspace(nv, nwork, R.opi->scratch_doubles(R.op),
                                       R.o->method == MFEM_SOLVER_GMRES ? mfem_gmres_workspace_bytes() : 0);
   R.vec_bytes = W.vec_bytes;
   R.csr_copy_bytes = R.layout_bytes = 0;
@@ -970,7 +971,7 @@ static int operator_attempt(SolveRun& R) {
   MFEM_CHECK_HIP(hipMemcpyAsync(V.b, R.b, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
   if (R.jac) {  // Pr_Jacobi!: d = |diag K| under the guarded rule (a row without adjacency or with a zero diagonal keeps the preset 1)
     rc = mfem_fill(ctx, n, 1.0, V.d);
-    if (!rc) rc = mfem_mesh_operator_jacobi(ctx, R.op, scratch, V.d);
+    if (!rc) rc = R.opi->jacobi(ctx, R.op, scratch, V.d);
     if (rc) return rc;
     if (R.is_cg) {
       hipLaunchKernelGGL(k_recip, dim3(mfem_vec_grid(ctx, n)), dim3(MFEM_BLOCK), 0, ctx->stream, n, V.d, R.dinv_buf);
@@ -978,17 +979,20 @@ static int operator_attempt(SolveRun& R) {
       V.dinv = R.dinv_buf;
     }
   }
-  struct Unbind { mfem_mesh_operator_s* op; ~Unbind() { mfem_mesh_operator_unbind(op); } } unbind{R.op};
-  mfem_mesh_operator_bind(R.op, scratch, R.fused_scale ? V.d : nullptr);
+  rc = R.opi->bind(R.op, scratch, R.fused_scale ? V.d : nullptr);
+  if (rc) return rc;
+  struct Unbind { SolveRun& R; ~Unbind() { R.opi->unbind(R.op); } } unbind{R};
   return run_passes(R);
 }
 
 extern "C" int mfem_solve_operator(mfem_context ctx, uint64_t handle, const double* b, double* x_out, const mfem_solve_options* o,
                                    mfem_solve_stats* stats) try {
-  mfem_mesh_operator_s* op = mfem_mesh_operator_from_handle(handle);
+  mfem_operator_head* op = (mfem_operator_head*)(uintptr_t)handle;
   MFEM_REQUIRE(ctx && op && o, "null argument");
-  MFEM_REQUIRE(mfem_mesh_operator_ctx(op) == ctx, "the operator was created on another context");
-  mfem_csr_s* A = mfem_mesh_operator_csr(op);
+  const mfem_operator_interface* opi = mfem_operator_interface_of(op);
+  MFEM_REQUIRE(opi, "the handle is neither a mesh operator's nor a brick operator's");
+  MFEM_REQUIRE(opi->ctx(op) == ctx, "the operator was created on another context");
+  mfem_csr_s* A = opi->csr(op);
   MFEM_REQUIRE(!A->op, "the operator is bound to a running solve");
   MFEM_REQUIRE(A->n == 0 || (b && x_out), "null array");
   MFEM_REQUIRE(o->method >= MFEM_SOLVER_CG && o->method <= MFEM_SOLVER_LSQR, "unknown method");
@@ -1003,6 +1007,7 @@ extern "C" int mfem_solve_operator(mfem_context ctx, uint64_t handle, const doub
   return solve_with_graphs(ctx, A->n, [&]() -> int {
     SolveRun R{ctx, A, nullptr, b, x_out, o, stats};
     R.op = op;
+    R.opi = opi;
     const int rc = choose_method(R);
     if (rc || A->n == 0) return rc;
     R.allow_lat = false;

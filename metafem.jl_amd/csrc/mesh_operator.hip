@@ -46,6 +46,7 @@ struct OpPart {
 };
 
 struct mfem_mesh_operator_s {
+  mfem_operator_head head;    // MFEM_OPERATOR_MESH (operator.h)
   mfem_context_s* ctx;
   int dim, itp, n_fields, base;
   int64_t nel, ncp;
@@ -56,17 +57,18 @@ struct mfem_mesh_operator_s {
   mfem_csr_s csr;             // pattern-less: what the Krylov loop holds in place of a matrix
 };
 
-mfem_mesh_operator_s* mfem_mesh_operator_from_handle(uint64_t handle) { return (mfem_mesh_operator_s*)(uintptr_t)handle; }
-mfem_context_s* mfem_mesh_operator_ctx(mfem_mesh_operator_s* op) { return op->ctx; }
-mfem_csr_s* mfem_mesh_operator_csr(mfem_mesh_operator_s* op) { return &op->csr; }
-size_t mfem_mesh_operator_scratch_doubles(const mfem_mesh_operator_s* op) { return op->scratch_doubles; }
+// the handle of an entry point of this file; nullptr: none, or another kind's
+static mfem_mesh_operator_s* mfem_mesh_operator_from_handle(uint64_t handle) {
+  mfem_operator_head* h = (mfem_operator_head*)(uintptr_t)handle;
+  return h && h->kind == MFEM_OPERATOR_MESH ? (mfem_mesh_operator_s*)h : nullptr;
+}
 
-void mfem_mesh_operator_bind(mfem_mesh_operator_s* op, double* scratch, const double* dsc) {
-  op->csr.op = op;
+static void mfem_mesh_operator_bind(mfem_mesh_operator_s* op, double* scratch, const double* dsc) {
+  op->csr.op = &op->head;
   op->csr.op_scratch = scratch;
   op->csr.op_dsc = dsc;
 }
-void mfem_mesh_operator_unbind(mfem_mesh_operator_s* op) {
+static void mfem_mesh_operator_unbind(mfem_mesh_operator_s* op) {
   op->csr.op = nullptr;
   op->csr.op_scratch = nullptr;
   op->csr.op_dsc = nullptr;
@@ -411,6 +413,7 @@ extern "C" int mfem_mesh_operator_create(mfem_context ctx, int32_t dim, int32_t 
   }
   mfem_host_alloc_probe();
   std::unique_ptr<mfem_mesh_operator_s> op(new mfem_mesh_operator_s());
+  op->head.kind = MFEM_OPERATOR_MESH;
   op->ctx = ctx;
   op->dim = dim;
   op->itp = itp;
@@ -579,9 +582,9 @@ static int op_items_launch(mfem_context_s* ctx, const mfem_mesh_operator_s* op, 
   return MFEM_OK;
 }
 
-int mfem_mesh_operator_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* x, double* y, double alpha, double beta, const double* dotw,
-                              double* partials, int* n_partials, const int32_t* done_flag) {
-  mfem_mesh_operator_s* op = A->op;
+static int mfem_mesh_operator_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* x, double* y, double alpha, double beta, const double* dotw,
+                                     double* partials, int* n_partials, const int32_t* done_flag) {
+  mfem_mesh_operator_s* op = A->op && A->op->kind == MFEM_OPERATOR_MESH ? (mfem_mesh_operator_s*)A->op : nullptr;
   MFEM_REQUIRE(op && (A->op_scratch || op->scratch_doubles == 0), "the operator is not bound");
   int rc = op_items_launch(ctx, op, false, x, A->op_dsc, A->op_scratch, done_flag);
   if (!rc) rc = op_gather_launch(ctx, op, A->op_scratch, y, alpha, beta, OPG_PRODUCT, dotw, partials, n_partials, done_flag);
@@ -590,16 +593,29 @@ int mfem_mesh_operator_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* 
   return MFEM_OK;
 }
 
-int mfem_mesh_operator_jacobi(mfem_context_s* ctx, mfem_mesh_operator_s* op, double* scratch, double* d) {
+static int mfem_mesh_operator_jacobi(mfem_context_s* ctx, mfem_mesh_operator_s* op, double* scratch, double* d) {
   int rc = op_items_launch(ctx, op, true, nullptr, nullptr, scratch, nullptr);
   if (!rc) rc = op_gather_launch(ctx, op, scratch, d, 1.0, 0.0, OPG_JACOBI, nullptr, nullptr, nullptr, nullptr);
   return rc;
 }
 
+// what the solve driver and the product dispatch hold of this kind (operator.h)
+static mfem_mesh_operator_s* as_mesh(mfem_operator_head* h) { return (mfem_mesh_operator_s*)h; }
+static mfem_context_s* mop_if_ctx(mfem_operator_head* h) { return as_mesh(h)->ctx; }
+static mfem_csr_s* mop_if_csr(mfem_operator_head* h) { return &as_mesh(h)->csr; }
+static size_t mop_if_scratch(const mfem_operator_head* h) { return ((const mfem_mesh_operator_s*)h)->scratch_doubles; }
+static int mop_if_bind(mfem_operator_head* h, double* scratch, const double* dsc) { mfem_mesh_operator_bind(as_mesh(h), scratch, dsc); return MFEM_OK; }
+static void mop_if_unbind(mfem_operator_head* h) { mfem_mesh_operator_unbind(as_mesh(h)); }
+static int mop_if_jacobi(mfem_context_s* ctx, mfem_operator_head* h, double* scratch, double* d) { return mfem_mesh_operator_jacobi(ctx, as_mesh(h), scratch, d); }
+const mfem_operator_interface* mfem_mesh_operator_interface() {  // (a function-local table: a const global of a .hip file is emitted for the device too)
+  static const mfem_operator_interface I = {mop_if_ctx, mop_if_csr, mop_if_scratch, mop_if_bind, mop_if_unbind, mop_if_jacobi, mfem_mesh_operator_launch};
+  return &I;
+}
+
 // the stand-alone entry points take the scratch from the context workspace, as the fused residual does
 static int op_standalone(mfem_context ctx, uint64_t handle, mfem_mesh_operator_s** out) {
   mfem_mesh_operator_s* op = mfem_mesh_operator_from_handle(handle);
-  MFEM_REQUIRE(ctx && op, "null handle");
+  MFEM_REQUIRE(ctx && op, "null handle, or not a mesh operator's");
   MFEM_REQUIRE(op->ctx == ctx, "the operator was created on another context");
   MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
   const int rc = mfem_ws_reserve(ctx, op->scratch_doubles * sizeof(double));

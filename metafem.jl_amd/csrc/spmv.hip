@@ -2,7 +2,7 @@
 // the CSR kernels on the caller's arrays (spmv_csr.hip) --, its optional timing bracket, and the slab form that overlaps the halo exchange of x with
 // the rows that need no ghost entry.
 #include "blas1.h"
-#include "mesh_operator.h"
+#include "operator.h"
 
 // Internal launcher: y = alpha*A*x + beta*y, optionally partial sums of (dotw . y) into `partials`
 // (*n_partials receives the number written).
@@ -142,7 +142,11 @@ static int spmv_launch_inner(mfem_context_s* ctx, mfem_csr_s* A, const double* v
     case MFEM_LAYOUT_LAT27: launched = mfem_spmv_lat27_launch(ctx, A, vals, x, y, alpha, beta, dotw, partials, n_partials, done_flag, part.part); break;
     case MFEM_LAYOUT_LAT8: launched = mfem_spmv_lat8_launch(ctx, A, vals, x, y, alpha, beta, dotw, partials, n_partials, done_flag, part.part); break;
     // (a matrix-free operator has no CSR arrays to fall back to: its launcher launches or fails)
-    case MFEM_LAYOUT_OPERATOR: return mfem_mesh_operator_launch(ctx, A, x, y, alpha, beta, dotw, partials, n_partials, done_flag);
+    case MFEM_LAYOUT_OPERATOR: {
+      const mfem_operator_interface* I = mfem_operator_interface_of(A->op);
+      MFEM_REQUIRE(I, "the bound operator's handle carries no known kind tag");
+      return I->launch(ctx, A, x, y, alpha, beta, dotw, partials, n_partials, done_flag);
+    }
   }
   if (launched != 0) return launched < 0 ? launched : MFEM_OK;
   return mfem_spmv_csr_launch(ctx, A, vals, x, y, alpha, beta, dotw, partials, n_partials, done_flag, part);  // (also what a layout that did not launch falls back to)
