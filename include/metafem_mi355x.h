@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MFEM_ABI_VERSION 7
+#define MFEM_ABI_VERSION 8
 
 typedef enum {
   MFEM_OK = 0,
@@ -731,7 +731,7 @@ int mfem_mesh_operator_diagonal(mfem_context ctx, uint64_t op, double* d);
  * or a product with A').  MFEM_ERR_INVALID: scale_in_place, an attached communicator (one rank only), null arguments. */
 int mfem_solve_operator(mfem_context ctx, uint64_t op, const double* b, double* x_out, const mfem_solve_options* opts, mfem_solve_stats* stats);
 
-/* ---- matrix-free operator on hex-8 thermal bricks (new) ---------------------------------------------------------------------------------
+/* ---- matrix-free operator on hex-8 bricks: thermal, and three-field elasticity below (new) ---------------------------------------------------------------------------------
  * K of mfem_brick_assemble_thermal for the same mfem_thermal_params -- the volume term, the Robin faces and the Nitsche fixed_faces (K is
  * nonsymmetric then) -- without a pattern, values or any scratch: K x is the fused residual with s = 0, Tenv = 0, Tw = 0, evaluated from the brick's
  * coordinates, which are read LIVE at every product (a caller may move them between solves).  The brick must outlive the handle (an opaque
@@ -751,6 +751,18 @@ int mfem_brick_operator_apply(mfem_context ctx, uint64_t op, const double* x, do
 int mfem_brick_operator_diagonal(mfem_context ctx, uint64_t op, double* d);
 /* mfem_solve_operator takes a brick operator's handle as it takes a mesh operator's (every handle starts with a kind tag): same options, same
  * refusals, same spmv_count formulas; the workspace is the solver's vectors only. */
+/* The same operator on three-field linear elasticity (ABI 8): K of mfem_brick_assemble_elasticity for the same mfem_elasticity_params -- the volume
+ * term -int sigma_ij(u) d_jN_a and the penalty faces -tau N_a N_b delta_fg on penalty_faces; traction_faces and sig contribute nothing to K and are
+ * ignored.  Unknowns are field-major, n = 3 * control points; x, y and d of apply / diagonal hold 3 entries per control point.  K x is the fused
+ * residual with the traction dropped and x as the displacement: the plane sweep for itg_order 2-3, a thread per control point for every other
+ * rule, plus one launch over the boundary control points when tau != 0 and penalty_faces != 0.  The diagonal, for f = 0..2:
+ * K_(f,a),(f,a) = -sum_el sum_q w det [lambda g_f^2 + mu (|g|^2 + g_f^2)] - tau sum_faces sum_q w^s N_a^2 (g = grad N_a), under the same guarded rule.
+ * apply, diagonal, destroy and mfem_solve_operator take the handle unchanged; the refusals are those of mfem_brick_operator_create, with the same
+ * messages. */
+int mfem_brick_operator_create_elasticity(mfem_context ctx, mfem_brick m, const mfem_elasticity_params* p, uint64_t* op /* [host] out */);
+/* Replaces the parameters of an elasticity operator.  A set-params call of the other physics (this one on a thermal operator,
+ * mfem_brick_operator_set_params on an elasticity operator) answers MFEM_ERR_INVALID and changes nothing. */
+int mfem_brick_operator_set_elasticity_params(uint64_t op, const mfem_elasticity_params* p);
 
 /* ---- multi-GPU (new; the reference is single-GPU, F6) ------------------------------------ */
 /* 128-byte RCCL unique id, created on rank 0 and shipped to the other ranks by the host

@@ -142,6 +142,12 @@ int64_t mfem_debug_mesh_residual_count(void);
 int64_t mfem_debug_mesh_operator_count(void);
 /* the same for the hex-8 brick operator: mfem_brick_operator_apply and every product of mfem_solve_operator on a brick operator's handle */
 int64_t mfem_debug_brick_operator_count(void);
+/* One product of a brick operator (either physics) as a solver's cycle launches it when it wants a dot product with it: y = alpha K x + beta y and
+ * the partial sums of dotw . y -- the volume kernel's workgroup sums first, the face kernel's increments behind them -- into `partials` (device,
+ * MFEM_MAX_PARTIALS = 4096 doubles), their number into *n_partials (host).  With partial sums the work items are folded onto the capped grid;
+ * mfem_brick_operator_apply launches one workgroup per item.  Tests: y is the same bit for bit both ways, the sums add up to dotw . y. */
+int mfem_debug_brick_operator_apply_dot(mfem_context ctx, uint64_t op, const double* x, double* y, double alpha, double beta, const double* dotw,
+                                        double* partials, int32_t* n_partials /* [host] out */);
 /* number of mfem_mesh_var_* / mfem_mesh_res_* / mfem_mesh_kval_* calls that took a table-free launch (process-wide) */
 int64_t mfem_debug_mesh_ops_count(void);
 /* variants of the fused mesh assembly launched so far (process-wide), one bit per (dim, mode, kind): bit ((dim - 2) * 3 + mode) * 9 + kind, mode 0

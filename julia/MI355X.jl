@@ -21,7 +21,7 @@ import LinearAlgebra
 
 # ---- library handle and error convention ---------------------------------------------------------------------------------
 const lib = get(ENV, "METAFEM_MI355X_LIB", joinpath(@__DIR__, "..", "metafem.jl_amd", "libmetafem_mi355x.so"))
-const ABI_VERSION = 7    # == MFEM_ABI_VERSION
+const ABI_VERSION = 8    # == MFEM_ABI_VERSION
 
 struct MFEMError <: Exception
     rc::Cint
@@ -671,7 +671,7 @@ function iterative_Solve!(op::MeshOperator, residue, converge_tol; Sv_func!::Sym
 end
 mesh_operator_count() = ccall((:mfem_debug_mesh_operator_count, lib), Int64, ())
 
-# ---- matrix-free operator on hex-8 thermal bricks (mfem_brick_operator_*, mfem_solve_operator) -------------------------------------
+# ---- matrix-free operator on hex-8 bricks, thermal and elasticity (mfem_brick_operator_*, mfem_solve_operator) -------------------------------------
 # K of mfem_brick_assemble_thermal without K_J_ptr / K_J / K_total: K x is evaluated from the brick's coordinates (read live at every product).
 # The brick is kept alive by the operator; hex-27 bricks and bricks with a slab are refused (`nothing`; mfem_last_error says why).
 mutable struct BrickOperator
@@ -694,6 +694,24 @@ end
 "Re-sends the parameters (K_linear_func of a matrix-free domain): host only."
 brick_operator_set_params!(op::BrickOperator, p::ThermalParams) =
     check(ccall((:mfem_brick_operator_set_params, lib), Cint, (UInt64, Ref{ThermalParams}), op.h, Ref(p)))
+
+# The same operator on three-field linear elasticity (ABI 8): K of mfem_brick_assemble_elasticity for the same ElasticityParams (volume term and
+# penalty faces; traction_faces and sig are the residual's load and are ignored).  n = 3 control points, field-major.  operator_mul!,
+# operator_diagonal and iterative_Solve! take the operator unchanged.
+function brick_operator(brick::Brick, p::ElasticityParams)
+    h = Ref{UInt64}(0)
+    rc = ccall((:mfem_brick_operator_create_elasticity, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{ElasticityParams}, Ref{UInt64}), ctx(), brick.h, Ref(p), h)
+    rc == -3 && return nothing
+    check(rc)
+    n = 3 * ccall((:mfem_brick_num_controlpoints, lib), Int64, (Ptr{Cvoid},), brick.h)
+    op = BrickOperator(h[], n, brick)
+    finalizer(o -> (ccall((:mfem_brick_operator_destroy, lib), Cint, (UInt64,), o.h); o.h = 0), op)
+    return op
+end
+
+"Re-sends the parameters of an elasticity operator; a thermal operator answers MFEM_ERR_INVALID (and the other way round)."
+brick_operator_set_params!(op::BrickOperator, p::ElasticityParams) =
+    check(ccall((:mfem_brick_operator_set_elasticity_params, lib), Cint, (UInt64, Ref{ElasticityParams}), op.h, Ref(p)))
 
 "y = alpha K x + beta y"
 operator_mul!(y, op::BrickOperator, x, alpha = 1.0, beta = 0.0) =

@@ -29,8 +29,8 @@ import torch
 from . import _lib
 from ._lib import (ElasticityParams, MetaFEMError, OpLayout, SolveOptions, SolveStats, ThermalParams, check, lib)
 
-__all__ = ["Context", "FEM_SpMat_CSR", "MeshOperator", "BrickOperator", "BrickOperatorRefused", "brick_operator_refusal", "mul_", "tmul_", "dot", "nrm2", "axpby_", "FEM_rand", "normalized_norm",
-           "iterative_Solve", "Brick", "make_Brick", "ThermalDomain", "MetaFEMError", "SolveStats",
+__all__ = ["Context", "FEM_SpMat_CSR", "MeshOperator", "BrickOperator", "ElasticityBrickOperator", "BrickOperatorRefused", "brick_operator_refusal", "mul_", "tmul_", "dot", "nrm2", "axpby_", "FEM_rand", "normalized_norm",
+           "iterative_Solve", "Brick", "make_Brick", "ThermalDomain", "ElasticityDomain", "MetaFEMError", "SolveStats",
            "cg_", "bicgstabl_GS_", "idrs_", "cgs2_", "gmres_", "cgs_", "tfqmr_", "lsqr_", "FACE_BITS"]
 
 # solver / preconditioner selectors (the reference passes Julia functions: Sv_func! = idrs! ...)
@@ -307,6 +307,31 @@ class BrickOperator:
             self.close()
         except Exception:
             pass
+
+
+class ElasticityBrickOperator(BrickOperator):
+    """Matrix-free K of a hex-8 brick under three-field linear elasticity (mfem_brick_operator_create_elasticity, csrc/brick_operator_elasticity.hip):
+    the matrix of Brick.assemble_elasticity for the same parameters -- the volume term and the penalty faces; traction faces and sig are the
+    residual's load and do not enter K.  n = 3 * ncp, field-major.  Made by Brick.elasticity_operator; mul_, diagonal and iterative_Solve take it
+    as they take a BrickOperator."""
+
+    def __init__(self, brick: "Brick", params: "ElasticityParams"):
+        self.ctx, self.brick = brick.ctx, brick  # (the library borrows the brick: kept alive here)
+        self.n = 3 * brick.ncp
+        self.nnz = 0
+        self._h = C.c_uint64()
+        rc = lib.mfem_brick_operator_create_elasticity(self.ctx._h, brick._h, C.byref(params), C.byref(self._h))
+        if rc == -3:  # MFEM_ERR_UNSUPPORTED: a brick the operator does not cover
+            raise BrickOperatorRefused(lib.mfem_last_error().decode())
+        check(rc)
+        self.params = params
+        self.ctx._children.add(self)
+
+    def set_params(self, lam: float, mu: float, tau: float = 0.0, penalty_faces: int = 0):
+        """Re-sends the parameters (host only, nothing is launched)."""
+        p = ElasticityParams(lam, mu, tau, penalty_faces, 0, (C.c_double * 6)(*([0.0] * 6)))
+        check(lib.mfem_brick_operator_set_elasticity_params(self._h, C.byref(p)))
+        self.params = p
 
 
 _OPERATORS = (MeshOperator, BrickOperator)  # what stands in for (A, vals) with vals = None
@@ -588,6 +613,11 @@ class Brick:
         check(lib.mfem_brick_assemble_elasticity(self.ctx._h, self._h, A._h, C.byref(p), _ptr(vals)))
         return vals
 
+    def elasticity_operator(self, lam: float, mu: float, tau: float = 0.0, penalty_faces: int = 0) -> "ElasticityBrickOperator":
+        """The matrix-free K of assemble_elasticity for the same parameters (a BrickOperator with n == 3 * ncp).  A hex-27 brick or a brick with a
+        slab raises BrickOperatorRefused."""
+        return ElasticityBrickOperator(self, ElasticityParams(lam, mu, tau, penalty_faces, 0, (C.c_double * 6)(*([0.0] * 6))))
+
     def residual_elasticity(self, x_star: torch.Tensor, lam: float, mu: float, tau: float = 0.0, penalty_faces: int = 0,
                             traction_faces: int = 0, sig=(0.0,) * 6, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """sig = constant symmetric tensor (11, 22, 33, 23, 13, 12) of Bilinear(d{i}, sig{i,j}*n{j}) (:61)."""
@@ -636,6 +666,69 @@ def _tensor_from_ptr(ptr, n: int, dtype, device: int, owner=None) -> torch.Tenso
         return torch.empty(0, dtype=dtype, device=f"cuda:{device}")
     typestr = {torch.float64: "<f8", torch.int64: "<i8", torch.int32: "<i4"}[dtype]
     return torch.as_tensor(_PtrHolder(int(ptr), n, typestr, owner), device=f"cuda:{device}")
+
+
+class ElasticityDomain:
+    """FEM_Domain + GlobalField for the linear-elasticity weak form of examples/linear_elasticity/cantilever/3D_Script.jl:52-61 on a structured
+    brick (three fields, field-major): displacement held by the penalty tau on penalty_faces, the constant traction sig on traction_faces.  The two
+    generated closures are the fused HIP kernels; update_OneStep is the reference's Newton driver, as in ThermalDomain."""
+
+    def __init__(self, brick: Brick, lam: float, mu: float, tau: float, penalty_faces: int, traction_faces: int = 0, sig=(0.0,) * 6, *,
+                 matrix_free: bool = False):
+        self.brick, self.lam, self.mu, self.tau, self.penalty_faces = brick, lam, mu, tau, penalty_faces
+        self.traction_faces, self.sig = traction_faces, tuple(sig)
+        dev = f"cuda:{brick.ctx.device}"
+        # matrix_free = True: no matrix at all.  self.A is the elasticity BrickOperator, K_linear = K_total = None, brick.pattern is never called and
+        # K_linear_func only re-sends the parameters.  A brick the operator does not cover is built as the default domain is, and
+        # matrix_free_reason says why (ThermalDomain's rule).
+        self.matrix_free_reason = brick_operator_refusal(brick) if matrix_free else None
+        self.matrix_free = bool(matrix_free) and self.matrix_free_reason is None
+        if self.matrix_free:
+            try:
+                self.A = brick.elasticity_operator(lam, mu, tau, penalty_faces)
+            except BrickOperatorRefused as e:
+                self.matrix_free, self.matrix_free_reason = False, str(e)
+        if not self.matrix_free:
+            self.A = brick.pattern(3)
+        n = self.A.n
+        self.basicfield_size = n
+        self.x = torch.zeros(n, dtype=torch.float64, device=dev)
+        self.dx = torch.zeros(n, dtype=torch.float64, device=dev)
+        self.x_star = torch.zeros(n, dtype=torch.float64, device=dev)
+        self.residue = torch.zeros(n, dtype=torch.float64, device=dev)
+        self.K_linear = None if self.matrix_free else torch.zeros(self.A.nnz, dtype=torch.float64, device=dev)
+        self.K_total = self.K_linear  # a linear form: K_total .= K_linear is an alias
+        self.converge_tol = 1e-6
+        self.linear_solver: Callable = lambda gf: iterative_Solve(gf.A, gf.K_total, gf.residue, gf.converge_tol,
+                                                                   Sv_func=idrs_, maxiter=2000, max_pass=10, s=8)[0]
+        self.history = []
+
+    def K_linear_func(self):
+        if self.matrix_free:  # nothing is assembled: the parameters go to the operator
+            self.A.set_params(self.lam, self.mu, self.tau, self.penalty_faces)
+            return
+        self.brick.assemble_elasticity(self.A, self.lam, self.mu, self.tau, self.penalty_faces, out=self.K_linear)
+
+    def K_nonlinear_func(self):
+        self.brick.residual_elasticity(self.x_star, self.lam, self.mu, self.tau, self.penalty_faces, self.traction_faces, self.sig, out=self.residue)
+
+    def update_OneStep(self, max_iter: int = 4):
+        self.dx.zero_()
+        self.K_linear_func()
+        counter = -1
+        self.history = []
+        while True:
+            torch.add(self.x, self.dx, out=self.x_star)
+            self.K_nonlinear_func()
+            res = normalized_norm(self.residue, self.brick.ctx)
+            counter += 1
+            self.history.append(res)
+            if res < self.converge_tol or counter > max_iter:
+                break
+            delta_x = self.linear_solver(self)
+            self.dx -= delta_x
+        self.x += self.dx
+        return self.history
 
 
 @dataclass

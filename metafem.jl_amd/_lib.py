@@ -250,10 +250,13 @@ SIGNATURES = {
     "mfem_debug_mesh_operator_count": (c_int64, []),
     "mfem_brick_operator_create": (c_int, [P, P, C.POINTER(ThermalParams), C.POINTER(c_uint64)]),
     "mfem_brick_operator_set_params": (c_int, [c_uint64, C.POINTER(ThermalParams)]),
+    "mfem_brick_operator_create_elasticity": (c_int, [P, P, C.POINTER(ElasticityParams), C.POINTER(c_uint64)]),
+    "mfem_brick_operator_set_elasticity_params": (c_int, [c_uint64, C.POINTER(ElasticityParams)]),
     "mfem_brick_operator_destroy": (c_int, [c_uint64]),
     "mfem_brick_operator_apply": (c_int, [P, c_uint64, P, P, c_double, c_double]),
     "mfem_brick_operator_diagonal": (c_int, [P, c_uint64, P]),
     "mfem_debug_brick_operator_count": (c_int64, []),
+    "mfem_debug_brick_operator_apply_dot": (c_int, [P, c_uint64, P, P, c_double, c_double, P, P, C.POINTER(c_int32)]),
     "mfem_mesh_var_elements": (c_int, [P, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, c_int32, c_int32,
                                        C.POINTER(VarBatchTerm), P, P, c_int64]),
     "mfem_mesh_var_facets": (c_int, [P, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, P, P, P, c_int32,

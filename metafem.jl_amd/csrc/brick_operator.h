@@ -1,0 +1,89 @@
+// What the two files of the matrix-free hex-8 brick operator share: brick_operator.hip (the handle, the entry points, the thermal kernels) and
+// brick_operator_elasticity.hip (the elasticity kernels and their launchers).  The library is one code object per .hip file and a kernel is launched
+// from the file that defines it, so the device functions here are inline copies per file; the reference tables have ONE owner (bop_tables,
+// brick_operator.hip), and the handle's launch and diagonal hand an elasticity operator over to bop_elasticity_launch / bop_elasticity_jacobi.
+#pragma once
+#include "hex8_device.h"
+#include "brick_operator_decide.h"
+#include "operator.h"
+
+// Reference-cell tables in device memory, one IMMUTABLE copy per (device, rule), made when the first operator with that rule is created and kept for the
+// life of the process.  The constant-memory tables of hex8_device.h are one mutable copy per file, re-uploaded whenever the rule changes: a solver cycle
+// captured with one rule and replayed from the graph cache after a brick with another rule had been served would read the wrong tables, and an
+// upload at launch is a synchronous copy inside a stream capture.  These kernels therefore take a pointer that never changes its contents, and nothing
+// is uploaded at launch.
+int bop_tables(int device, int ng, const H8Tables** out);  // brick_operator.hip
+
+// hex8_geom and face_geom of hex8_device.h on those tables
+__device__ __forceinline__ double bop_geom(const H8Tables* __restrict__ T, const double (&X)[8][3], int q, double (&g)[8][3]) {
+  double J[3][3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+      double s = 0.0;
+#pragma unroll
+      for (int b = 0; b < 8; ++b) s += T->dN[q][b][m] * X[b][i];
+      J[i][m] = s;
+    }
+  const double det = J[0][0] * J[1][1] * J[2][2] - J[0][0] * J[1][2] * J[2][1] - J[0][1] * J[1][0] * J[2][2] +
+                     J[0][1] * J[1][2] * J[2][0] + J[0][2] * J[1][0] * J[2][1] - J[0][2] * J[1][1] * J[2][0];
+  const double id = 1.0 / det;
+  double I[3][3];
+  I[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id;
+  I[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
+  I[0][2] = (J[0][1] * J[1][2] - J[1][1] * J[0][2]) * id;
+  I[1][0] = (J[1][2] * J[2][0] - J[2][2] * J[1][0]) * id;
+  I[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
+  I[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
+  I[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id;
+  I[2][1] = (J[0][1] * J[2][0] - J[2][1] * J[0][0]) * id;
+  I[2][2] = (J[0][0] * J[1][1] - J[1][0] * J[0][1]) * id;
+#pragma unroll
+  for (int b = 0; b < 8; ++b)
+#pragma unroll
+    for (int s = 0; s < 3; ++s) g[b][s] = T->dN[q][b][0] * I[0][s] + T->dN[q][b][1] * I[1][s] + T->dN[q][b][2] * I[2][s];
+  return T->w[q] * det;
+}
+__device__ __forceinline__ double bop_face_weight(const H8Tables* __restrict__ T, const double (&Xf)[4][3], int q, bool low_face) {
+  double t1[3], t2[3];
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    double a = 0.0, b = 0.0;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      a += T->fdN[q][c][0] * Xf[c][i];
+      b += T->fdN[q][c][1] * Xf[c][i];
+    }
+    t1[i] = low_face ? -a : a;
+    t2[i] = b;
+  }
+  const double r0 = t1[1] * t2[2] - t1[2] * t2[1];
+  const double r1 = -t1[0] * t2[2] + t1[2] * t2[0];
+  const double r2 = t1[0] * t2[1] - t1[1] * t2[0];
+  return T->fw[q] * sqrt(r0 * r0 + r1 * r1 + r2 * r2);
+}
+
+enum { BOP_PHYSICS_THERMAL = 1, BOP_PHYSICS_ELASTICITY = 2 };
+struct mfem_brick_operator_s {
+  mfem_operator_head head;  // MFEM_OPERATOR_BRICK (operator.h)
+  mfem_context_s* ctx;
+  mfem_brick_s* brick;      // borrowed: coordinates are read live at every product
+  int physics;              // BOP_PHYSICS_*: which parameter block is set
+  mfem_thermal_params thermal;
+  mfem_elasticity_params elasticity;  // (traction_faces and sig are kept as sent and never read: they contribute nothing to K)
+  const H8Tables* tables;   // bop_tables(ctx->device, brick->ng): immutable
+  int ng;                   // the brick's rule when the operator was created
+  const double* seen_x0;    // the brick's first coordinate array at the last bind (a change starts a new epoch of the cycle-graph key)
+  mfem_csr_s csr;           // pattern-less: what the Krylov loop holds in place of a matrix (n = fields x control points)
+};
+
+__device__ __forceinline__ double bop_scaled(const double* __restrict__ x, const double* __restrict__ dsc, int64_t i) {
+  return dsc ? x[i] / dsc[i] : x[i];
+}
+
+// brick_operator_elasticity.hip: the product and the diagonal of an operator with physics == BOP_PHYSICS_ELASTICITY, on the view its caller verified
+// (bop_view).  The launch contract is bop_launch's.
+int bop_elasticity_launch(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, const double* x, const double* dsc, double* y, double alpha,
+                          double beta, const double* dotw, double* partials, int* n_partials, const int32_t* done_flag);
+int bop_elasticity_jacobi(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, double* d);

@@ -17,18 +17,20 @@
 // the solve's cycle graphs), and leave the partial sums of dotw . y of the final y: the volume kernel's workgroup sums first, the face kernel's increments
 // behind them.  Then the grids are capped (brick_operator_decide.h): a workgroup FOLDS the work items b, b + grid, ... in that order; a product without
 // partial sums launches one workgroup per item, as the residual does.  No atomics.
+// This file owns the handle of BOTH physics (a physics tag selects the parameter block), every entry point, the tables and the bind; the kernels of
+// the three-field elasticity operator and their two launchers are in brick_operator_elasticity.hip (bop_launch and bop_jacobi hand over to them),
+// what the two files share is in brick_operator.h.
 #include <memory>
 #include "hex8_device.h"
 #include "hex8_sumfac.h"
 #include "blas1.h"
-#include "brick_operator_decide.h"
-#include "operator.h"
+#include "brick_operator.h"
 static_assert(BOP_MAX_PARTIALS == MFEM_MAX_PARTIALS, "brick_operator_decide.h spells the cap out");
 
 static std::atomic<long long> g_brick_operator_count{0};
 extern "C" int64_t mfem_debug_brick_operator_count(void) { return g_brick_operator_count; }
 
-// what the kernels take of the weak form (thermal; an elasticity block would stand beside it)
+// what the kernels take of the weak form (thermal; the elasticity block and its kernels: brick_operator_elasticity.hip)
 struct BopThermal {
   double k, h, hp;
   uint32_t robin, fixed;
@@ -37,13 +39,9 @@ struct BopThermal {
   const H8Tables* T;    // the reference-cell tables of the brick's rule: bop_tables
 };
 
-// Reference-cell tables in device memory, one IMMUTABLE copy per (device, rule), made when the first operator with that rule is created and kept for the
-// life of the process.  The constant-memory tables of hex8_device.h are one mutable copy per file, re-uploaded whenever the rule changes: a solver cycle
-// captured with one rule and replayed from the graph cache after a brick with another rule had been served would read the wrong tables, and an
-// upload at launch is a synchronous copy inside a stream capture.  These kernels therefore take a pointer that never changes its contents, and nothing
-// is uploaded at launch.
+// the one owner of the immutable per-rule tables (brick_operator.h says why they exist)
 #define BOP_MAX_DEVICES 64
-static int bop_tables(int device, int ng, const H8Tables** out) {
+int bop_tables(int device, int ng, const H8Tables** out) {
   static std::mutex mu;
   static H8Tables* tables[BOP_MAX_DEVICES][H8_MAX_NG];
   MFEM_REQUIRE(device >= 0 && device < BOP_MAX_DEVICES && ng >= 1 && ng <= H8_MAX_NG, "device or Gauss rule out of range");
@@ -59,76 +57,10 @@ static int bop_tables(int device, int ng, const H8Tables** out) {
   *out = tables[device][ng - 1];
   return MFEM_OK;
 }
-// hex8_geom and face_geom of hex8_device.h on those tables
-__device__ __forceinline__ double bop_geom(const H8Tables* __restrict__ T, const double (&X)[8][3], int q, double (&g)[8][3]) {
-  double J[3][3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-      double s = 0.0;
-#pragma unroll
-      for (int b = 0; b < 8; ++b) s += T->dN[q][b][m] * X[b][i];
-      J[i][m] = s;
-    }
-  const double det = J[0][0] * J[1][1] * J[2][2] - J[0][0] * J[1][2] * J[2][1] - J[0][1] * J[1][0] * J[2][2] +
-                     J[0][1] * J[1][2] * J[2][0] + J[0][2] * J[1][0] * J[2][1] - J[0][2] * J[1][1] * J[2][0];
-  const double id = 1.0 / det;
-  double I[3][3];
-  I[0][0] = (J[1][1] * J[2][2] - J[1][2] * J[2][1]) * id;
-  I[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) * id;
-  I[0][2] = (J[0][1] * J[1][2] - J[1][1] * J[0][2]) * id;
-  I[1][0] = (J[1][2] * J[2][0] - J[2][2] * J[1][0]) * id;
-  I[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) * id;
-  I[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) * id;
-  I[2][0] = (J[1][0] * J[2][1] - J[1][1] * J[2][0]) * id;
-  I[2][1] = (J[0][1] * J[2][0] - J[2][1] * J[0][0]) * id;
-  I[2][2] = (J[0][0] * J[1][1] - J[1][0] * J[0][1]) * id;
-#pragma unroll
-  for (int b = 0; b < 8; ++b)
-#pragma unroll
-    for (int s = 0; s < 3; ++s) g[b][s] = T->dN[q][b][0] * I[0][s] + T->dN[q][b][1] * I[1][s] + T->dN[q][b][2] * I[2][s];
-  return T->w[q] * det;
-}
-__device__ __forceinline__ double bop_face_weight(const H8Tables* __restrict__ T, const double (&Xf)[4][3], int q, bool low_face) {
-  double t1[3], t2[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    double a = 0.0, b = 0.0;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      a += T->fdN[q][c][0] * Xf[c][i];
-      b += T->fdN[q][c][1] * Xf[c][i];
-    }
-    t1[i] = low_face ? -a : a;
-    t2[i] = b;
-  }
-  const double r0 = t1[1] * t2[2] - t1[2] * t2[1];
-  const double r1 = -t1[0] * t2[2] + t1[2] * t2[0];
-  const double r2 = t1[0] * t2[1] - t1[1] * t2[0];
-  return T->fw[q] * sqrt(r0 * r0 + r1 * r1 + r2 * r2);
-}
-
-enum { BOP_PHYSICS_THERMAL = 1 };
-struct mfem_brick_operator_s {
-  mfem_operator_head head;  // MFEM_OPERATOR_BRICK (operator.h)
-  mfem_context_s* ctx;
-  mfem_brick_s* brick;      // borrowed: coordinates are read live at every product
-  int physics;              // BOP_PHYSICS_*: which parameter block is set
-  mfem_thermal_params thermal;
-  const H8Tables* tables;   // bop_tables(ctx->device, brick->ng): immutable
-  int ng;                   // the brick's rule when the operator was created
-  const double* seen_x0;    // the brick's first coordinate array at the last bind (a change starts a new epoch of the cycle-graph key)
-  mfem_csr_s csr;           // pattern-less: what the Krylov loop holds in place of a matrix
-};
 
 static mfem_brick_operator_s* bop_from_handle(uint64_t handle) {
   mfem_operator_head* h = (mfem_operator_head*)(uintptr_t)handle;
   return h && h->kind == MFEM_OPERATOR_BRICK ? (mfem_brick_operator_s*)h : nullptr;
-}
-
-__device__ __forceinline__ double bop_scaled(const double* __restrict__ x, const double* __restrict__ dsc, int64_t i) {
-  return dsc ? x[i] / dsc[i] : x[i];
 }
 
 // =================================================================================================
@@ -527,9 +459,10 @@ static int bop_view(const mfem_brick_operator_s* op, BrickView* B) {
   const mfem_brick_s* m = op->brick;
   const char* why = bop_refusal(m->p, m->plo, m->phi, m->m[0]);
   if (why) return bop_refuse(MFEM_ERR_UNSUPPORTED, why);
-  MFEM_REQUIRE(m->n_owned == op->csr.n, "the brick changed size under the operator");
+  const int fields = op->physics == BOP_PHYSICS_ELASTICITY ? 3 : 1;
+  MFEM_REQUIRE(fields * m->n_owned == op->csr.n, "the brick changed size under the operator");
   MFEM_REQUIRE(m->ng == op->ng, "the brick's Gauss rule changed under the operator");
-  *B = mfem_brick_view(m, 1);
+  *B = mfem_brick_view(m, fields);
   return MFEM_OK;
 }
 
@@ -542,6 +475,12 @@ static int bop_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* x, doubl
   if (rc) return rc;
   const mfem_brick_s* m = op->brick;
   const double* dsc = A->op_dsc;
+  if (op->physics == BOP_PHYSICS_ELASTICITY) {  // (its kernels are launched from the file that defines them)
+    rc = bop_elasticity_launch(ctx, op, B, x, dsc, y, alpha, beta, dotw, partials, n_partials, done_flag);
+    if (rc) return rc;
+    if (!ctx->probe_active) ++g_brick_operator_count;
+    return MFEM_OK;
+  }
   const BopThermal P = bop_thermal(op);
   const BopVolume V = bop_volume(m->ng, m->m[0], m->m[1], m->m[2]);
   const int64_t vgrid = bop_volume_grid(V, partials != nullptr);  // (folded onto the partial sums only when some are asked for)
@@ -573,6 +512,7 @@ static int bop_jacobi(mfem_context_s* ctx, mfem_brick_operator_s* op, double* d)
   BrickView B;
   const int rc = bop_view(op, &B);
   if (rc) return rc;
+  if (op->physics == BOP_PHYSICS_ELASTICITY) return bop_elasticity_jacobi(ctx, op, B, d);
   const int64_t grid = bop_diagonal_grid(B.n_owned);
   MFEM_REQUIRE(grid < ((int64_t)1 << 31), "too many control points for one launch");
   hipLaunchKernelGGL(k_brick_diagonal, dim3((unsigned)grid), dim3(MFEM_BLOCK), 0, ctx->stream, B, bop_thermal(op), d);
@@ -612,7 +552,8 @@ const mfem_operator_interface* mfem_brick_operator_interface() {  // (a function
   return &I;
 }
 
-extern "C" int mfem_brick_operator_create(mfem_context ctx, mfem_brick m, const mfem_thermal_params* p, uint64_t* out) try {
+// what both physics do to create an operator: the refusals, the rule's tables (the one upload of a rule: here, never at a launch), the handle
+static int bop_create(mfem_context ctx, mfem_brick m, int physics, const void* p, uint64_t* out) {
   MFEM_REQUIRE(out, "null out");
   *out = 0;
   MFEM_REQUIRE(ctx && m && p, "null argument");
@@ -620,7 +561,7 @@ extern "C" int mfem_brick_operator_create(mfem_context ctx, mfem_brick m, const 
   const char* why = bop_refusal(m->p, m->plo, m->phi, m->m[0]);
   if (why) return bop_refuse(MFEM_ERR_UNSUPPORTED, why);
   const H8Tables* tables = nullptr;
-  const int rct = bop_tables(ctx->device, m->ng, &tables);  // (the one upload of a rule: here, never at a launch)
+  const int rct = bop_tables(ctx->device, m->ng, &tables);
   if (rct) return rct;
   mfem_host_alloc_probe();
   std::unique_ptr<mfem_brick_operator_s> op(new mfem_brick_operator_s());
@@ -630,25 +571,51 @@ extern "C" int mfem_brick_operator_create(mfem_context ctx, mfem_brick m, const 
   op->seen_x0 = nullptr;
   op->ctx = ctx;
   op->brick = m;
-  op->physics = BOP_PHYSICS_THERMAL;
-  op->thermal = *p;
+  op->physics = physics;
+  memset(&op->thermal, 0, sizeof(op->thermal));
+  memset(&op->elasticity, 0, sizeof(op->elasticity));
+  if (physics == BOP_PHYSICS_ELASTICITY) op->elasticity = *(const mfem_elasticity_params*)p;
+  else op->thermal = *(const mfem_thermal_params*)p;
   memset(&op->csr, 0, sizeof(op->csr));
   op->csr.ctx = ctx;
   op->csr.serial = mfem_next_csr_serial();
-  op->csr.n = m->n_owned;
+  op->csr.n = (physics == BOP_PHYSICS_ELASTICITY ? 3 : 1) * m->n_owned;  // field-major unknowns (brick_xindex)
   op->csr.rowptr_bits = 64;
   *out = (uint64_t)(uintptr_t)op.release();
   return MFEM_OK;
+}
+extern "C" int mfem_brick_operator_create(mfem_context ctx, mfem_brick m, const mfem_thermal_params* p, uint64_t* out) try {
+  return bop_create(ctx, m, BOP_PHYSICS_THERMAL, p, out);
 } MFEM_API_CATCH("mfem_brick_operator_create")
+extern "C" int mfem_brick_operator_create_elasticity(mfem_context ctx, mfem_brick m, const mfem_elasticity_params* p, uint64_t* out) try {
+  return bop_create(ctx, m, BOP_PHYSICS_ELASTICITY, p, out);
+} MFEM_API_CATCH("mfem_brick_operator_create_elasticity")
 
-extern "C" int mfem_brick_operator_set_params(uint64_t handle, const mfem_thermal_params* p) try {
+// a set-params call of the other physics answers MFEM_ERR_INVALID and changes nothing
+static int bop_params_target(uint64_t handle, const void* p, int physics, mfem_brick_operator_s** out) {
   mfem_brick_operator_s* op = bop_from_handle(handle);
   MFEM_REQUIRE(op && p, "null argument, or not a brick operator's handle");
+  MFEM_REQUIRE(op->physics == physics, "the operator was created for the other physics (thermal: mfem_brick_operator_set_params, elasticity: mfem_brick_operator_set_elasticity_params)");
   MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
+  *out = op;
+  return MFEM_OK;
+}
+extern "C" int mfem_brick_operator_set_params(uint64_t handle, const mfem_thermal_params* p) try {
+  mfem_brick_operator_s* op = nullptr;
+  const int rc = bop_params_target(handle, p, BOP_PHYSICS_THERMAL, &op);
+  if (rc) return rc;
   op->thermal = *p;
   ++op->csr.op_epoch;  // (a captured cycle bakes the parameters in)
   return MFEM_OK;
 } MFEM_API_CATCH("mfem_brick_operator_set_params")
+extern "C" int mfem_brick_operator_set_elasticity_params(uint64_t handle, const mfem_elasticity_params* p) try {
+  mfem_brick_operator_s* op = nullptr;
+  const int rc = bop_params_target(handle, p, BOP_PHYSICS_ELASTICITY, &op);
+  if (rc) return rc;
+  op->elasticity = *p;
+  ++op->csr.op_epoch;
+  return MFEM_OK;
+} MFEM_API_CATCH("mfem_brick_operator_set_elasticity_params")
 
 extern "C" int mfem_brick_operator_destroy(uint64_t handle) try {
   if (!handle) return MFEM_OK;
@@ -683,6 +650,21 @@ extern "C" int mfem_brick_operator_apply(mfem_context ctx, uint64_t handle, cons
   struct Release { mfem_brick_operator_s* op; ~Release() { bop_unbind(op); } } release{op};
   return mfem_spmv_launch(ctx, &op->csr, nullptr, x, y, alpha, beta, nullptr, nullptr, nullptr, nullptr);
 } MFEM_API_CATCH("mfem_brick_operator_apply")
+
+extern "C" int mfem_debug_brick_operator_apply_dot(mfem_context ctx, uint64_t handle, const double* x, double* y, double alpha, double beta, const double* dotw,
+                                                   double* partials, int32_t* n_partials) try {
+  mfem_brick_operator_s* op = nullptr;
+  const int rc = bop_standalone(ctx, handle, &op);
+  if (rc) return rc;
+  MFEM_REQUIRE(x && y && dotw && partials && n_partials, "null argument");
+  const int rcb = bop_bind(op, nullptr);
+  if (rcb) return rcb;
+  struct Release { mfem_brick_operator_s* op; ~Release() { bop_unbind(op); } } release{op};
+  int np = 0;
+  const int rcl = bop_launch(ctx, &op->csr, x, y, alpha, beta, dotw, partials, &np, nullptr);
+  *n_partials = np;
+  return rcl;
+} MFEM_API_CATCH("mfem_debug_brick_operator_apply_dot")
 
 extern "C" int mfem_brick_operator_diagonal(mfem_context ctx, uint64_t handle, double* d) try {
   mfem_brick_operator_s* op = nullptr;
