@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MFEM_ABI_VERSION 8
+#define MFEM_ABI_VERSION 9
 
 typedef enum {
   MFEM_OK = 0,
@@ -763,6 +763,20 @@ int mfem_brick_operator_create_elasticity(mfem_context ctx, mfem_brick m, const 
 /* Replaces the parameters of an elasticity operator.  A set-params call of the other physics (this one on a thermal operator,
  * mfem_brick_operator_set_params on an elasticity operator) answers MFEM_ERR_INVALID and changes nothing. */
 int mfem_brick_operator_set_elasticity_params(uint64_t op, const mfem_elasticity_params* p);
+/* The thermal operator on an ORDER-2 (hex-27) brick (ABI 9): K of mfem_brick_assemble_thermal for the same mfem_thermal_params on a Lagrange-2
+ * brick -- the volume term, the Robin faces and the Nitsche fixed_faces (K is nonsymmetric then) -- evaluated from the coordinates, read live; no
+ * pattern, no values, no scratch (scratch_doubles is 0), where the assembled matrix holds up to 125 entries per row.  A product is one launch of a
+ * row-owner sweep (a workgroup sweeps the element planes along dimension 0 over a tile of 8 x 8 element columns plus the one-element halo on the
+ * low sides, a wave per element with the sum-factorised stages of the hex-27 residual, its affine shortcut included; every control point is written
+ * once by its owner, the element vectors that meet in it added in a fixed order) plus one over the boundary control points when there are face
+ * terms: no atomics, no colours, bitwise reproducible, the same bits whether or not the work items are folded onto the partial sums.  The reference
+ * tables are immutable device copies per (device, rule): nothing is uploaded at a launch, and an assembly with another rule between two solves does
+ * not disturb a cached solver cycle.  The handle is a brick operator: mfem_brick_operator_set_params, _apply, _diagonal (K_ii from the <= 8 adjacent
+ * elements plus the point's own face terms, the guarded rule), _destroy and mfem_solve_operator take it unchanged (same options, same refusals, same
+ * spmv_count formulas); mfem_brick_operator_set_elasticity_params answers MFEM_ERR_INVALID.
+ * MFEM_ERR_UNSUPPORTED with a message, nothing created: an order-1 (hex-8) brick (it takes mfem_brick_operator_create), a brick with a slab set
+ * (also answered by apply / diagonal / a solve if the slab is set later). */
+int mfem_brick_operator_create_hex27(mfem_context ctx, mfem_brick m, const mfem_thermal_params* p, uint64_t* op /* [host] out */);
 
 /* ---- multi-GPU (new; the reference is single-GPU, F6) ------------------------------------ */
 /* 128-byte RCCL unique id, created on rank 0 and shipped to the other ranks by the host

@@ -21,7 +21,7 @@ import LinearAlgebra
 
 # ---- library handle and error convention ---------------------------------------------------------------------------------
 const lib = get(ENV, "METAFEM_MI355X_LIB", joinpath(@__DIR__, "..", "metafem.jl_amd", "libmetafem_mi355x.so"))
-const ABI_VERSION = 8    # == MFEM_ABI_VERSION
+const ABI_VERSION = 9    # == MFEM_ABI_VERSION
 
 struct MFEMError <: Exception
     rc::Cint
@@ -704,6 +704,20 @@ function brick_operator(brick::Brick, p::ElasticityParams)
     rc == -3 && return nothing
     check(rc)
     n = 3 * ccall((:mfem_brick_num_controlpoints, lib), Int64, (Ptr{Cvoid},), brick.h)
+    op = BrickOperator(h[], n, brick)
+    finalizer(o -> (ccall((:mfem_brick_operator_destroy, lib), Cint, (UInt64,), o.h); o.h = 0), op)
+    return op
+end
+
+# The thermal operator on an order-2 (hex-27) brick (ABI 9): K of mfem_brick_assemble_thermal for the same ThermalParams, evaluated from the
+# coordinates by a row-owner sweep -- no K_J_ptr / K_J / K_total where a row holds up to 125 entries.  A hex-8 brick and a brick with a slab are
+# refused (`nothing`).  brick_operator_set_params!(op, ::ThermalParams), operator_mul!, operator_diagonal and iterative_Solve! take the operator unchanged.
+function brick_operator_hex27(brick::Brick, p::ThermalParams)
+    h = Ref{UInt64}(0)
+    rc = ccall((:mfem_brick_operator_create_hex27, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{ThermalParams}, Ref{UInt64}), ctx(), brick.h, Ref(p), h)
+    rc == -3 && return nothing
+    check(rc)
+    n = ccall((:mfem_brick_num_controlpoints, lib), Int64, (Ptr{Cvoid},), brick.h)
     op = BrickOperator(h[], n, brick)
     finalizer(o -> (ccall((:mfem_brick_operator_destroy, lib), Cint, (UInt64,), o.h); o.h = 0), op)
     return op

@@ -29,7 +29,8 @@ import torch
 from . import _lib
 from ._lib import (ElasticityParams, MetaFEMError, OpLayout, SolveOptions, SolveStats, ThermalParams, check, lib)
 
-__all__ = ["Context", "FEM_SpMat_CSR", "MeshOperator", "BrickOperator", "ElasticityBrickOperator", "BrickOperatorRefused", "brick_operator_refusal", "mul_", "tmul_", "dot", "nrm2", "axpby_", "FEM_rand", "normalized_norm",
+__all__ = ["Context", "FEM_SpMat_CSR", "MeshOperator", "BrickOperator", "ElasticityBrickOperator", "Hex27BrickOperator", "BrickOperatorRefused", "brick_operator_refusal",
+           "brick_operator_hex27_refusal", "mul_", "tmul_", "dot", "nrm2", "axpby_", "FEM_rand", "normalized_norm",
            "iterative_Solve", "Brick", "make_Brick", "ThermalDomain", "ElasticityDomain", "MetaFEMError", "SolveStats",
            "cg_", "bicgstabl_GS_", "idrs_", "cgs2_", "gmres_", "cgs_", "tfqmr_", "lsqr_", "FACE_BITS"]
 
@@ -334,7 +335,26 @@ class ElasticityBrickOperator(BrickOperator):
         self.params = p
 
 
-_OPERATORS = (MeshOperator, BrickOperator)  # what stands in for (A, vals) with vals = None
+class Hex27BrickOperator(BrickOperator):
+    """Matrix-free K of a hex-27 (order-2) thermal brick (mfem_brick_operator_create_hex27, csrc/brick_operator_hex27.hip): the matrix of
+    Brick.assemble_thermal for the same parameters -- volume term, Robin faces, Nitsche fixed_faces -- evaluated from the coordinates by a row-owner
+    sweep; n = ncp.  Made by Brick.thermal_operator_hex27; set_params, mul_, diagonal and iterative_Solve take it as they take a BrickOperator.
+    Raises BrickOperatorRefused for a hex-8 brick (Brick.thermal_operator covers it) and for a brick with a slab."""
+
+    def __init__(self, brick: "Brick", params: "ThermalParams"):
+        self.ctx, self.brick = brick.ctx, brick  # (the library borrows the brick: kept alive here)
+        self.n = brick.ncp
+        self.nnz = 0
+        self._h = C.c_uint64()
+        rc = lib.mfem_brick_operator_create_hex27(self.ctx._h, brick._h, C.byref(params), C.byref(self._h))
+        if rc == -3:  # MFEM_ERR_UNSUPPORTED: a brick the operator does not cover
+            raise BrickOperatorRefused(lib.mfem_last_error().decode())
+        check(rc)
+        self.params = params
+        self.ctx._children.add(self)
+
+
+_OPERATORS = (MeshOperator, BrickOperator, Hex27BrickOperator)  # what stands in for (A, vals) with vals = None
 
 
 def mul_(b: torch.Tensor, A, vals: Optional[torch.Tensor], x: torch.Tensor, alpha: float = 1.0, beta: float = 0.0):
@@ -595,6 +615,12 @@ class Brick:
         BrickOperatorRefused."""
         return BrickOperator(self, ThermalParams(k, h, Tenv, robin_faces, fixed_faces, h_penalty, Tw))
 
+    def thermal_operator_hex27(self, k: float, h: float = 0.0, Tenv: float = 0.0, robin_faces: int = 0, fixed_faces: int = 0, h_penalty: float = 0.0,
+                               Tw: float = 0.0) -> "Hex27BrickOperator":
+        """The matrix-free K of assemble_thermal on an order-2 (hex-27) brick (Hex27BrickOperator).  A hex-8 brick or a brick with a slab raises
+        BrickOperatorRefused."""
+        return Hex27BrickOperator(self, ThermalParams(k, h, Tenv, robin_faces, fixed_faces, h_penalty, Tw))
+
     def residual_thermal(self, x_star: torch.Tensor, k: float, h: float = 0.0, Tenv: float = 0.0, robin_faces: int = 0,
                          s: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, *, fixed_faces: int = 0,
                          h_penalty: float = 0.0, Tw: float = 0.0) -> torch.Tensor:
@@ -644,6 +670,15 @@ def brick_operator_refusal(brick: Brick) -> Optional[str]:
     without a device call.  The library has the last word: ThermalDomain also falls back on BrickOperatorRefused."""
     if brick.itp_order != 1:
         return "an order-2 (hex-27) brick: the matrix-free brick operator covers hex-8 bricks"
+    if tuple(brick.slab) != (0, brick.m[0]):
+        return "a brick with a slab set: the matrix-free brick operator runs on the whole lattice, one rank"
+    return None
+
+
+def brick_operator_hex27_refusal(brick: Brick) -> Optional[str]:
+    """The host's forecast of mfem_brick_operator_create_hex27's refusals (csrc/brick_operator_hex27_decide.h: bop27_refusal), or None."""
+    if brick.itp_order != 2:
+        return "an order-1 (hex-8) brick: the hex-27 operator covers order-2 bricks; a hex-8 brick takes mfem_brick_operator_create"
     if tuple(brick.slab) != (0, brick.m[0]):
         return "a brick with a slab set: the matrix-free brick operator runs on the whole lattice, one rank"
     return None
@@ -744,7 +779,7 @@ class ThermalDomain:
     reference's Newton driver (04_Time_Domain.jl:59-80)."""
 
     def __init__(self, brick: Brick, k: float, h: float, Tenv: float, robin_faces: int = ALL_FACES, *, fixed_faces: int = 0,
-                 h_penalty: float = 0.0, Tw: float = 0.0, matrix_free: bool = False):
+                 h_penalty: float = 0.0, Tw: float = 0.0, matrix_free=False):
         self.brick, self.k, self.h, self.Tenv, self.robin_faces = brick, k, h, Tenv, robin_faces
         # weakly imposed Dirichlet faces (fix_boundary of examples/thermal_conduction/2D_Script.jl:58)
         self.fixed = dict(fixed_faces=fixed_faces, h_penalty=h_penalty, Tw=Tw)
@@ -753,11 +788,17 @@ class ThermalDomain:
         # brick.pattern is never called and K_linear_func only re-sends the parameters; the default linear_solver hands (A, None) to iterative_Solve.
         # A brick the operator does not cover (brick_operator_refusal) is built as the default domain is: matrix_free is False then and
         # matrix_free_reason says why (GenericDomain's rule).
-        self.matrix_free_reason = brick_operator_refusal(brick) if matrix_free else None
+        # matrix_free = "any" (GenericDomain's word for "whichever operator covers it"): a hex-8 brick as True; a hex-27 brick gets the
+        # Hex27BrickOperator (matrix_free = True keeps falling back on one); a slab falls back with the reason.
+        if isinstance(matrix_free, str) and matrix_free != "any":
+            raise ValueError("matrix_free: False, True or 'any'")
+        hex27 = matrix_free == "any" and brick.itp_order == 2
+        self.matrix_free_reason = (brick_operator_hex27_refusal(brick) if hex27 else brick_operator_refusal(brick)) if matrix_free else None
         self.matrix_free = bool(matrix_free) and self.matrix_free_reason is None
         if self.matrix_free:
             try:
-                self.A = brick.thermal_operator(k, h, Tenv, robin_faces, **self.fixed)
+                make = brick.thermal_operator_hex27 if hex27 else brick.thermal_operator
+                self.A = make(k, h, Tenv, robin_faces, **self.fixed)
             except BrickOperatorRefused as e:  # (whatever rule the library applies beyond the host's forecast reaches the fallback too)
                 self.matrix_free, self.matrix_free_reason = False, str(e)
         if not self.matrix_free:

@@ -44,8 +44,8 @@ static void lag2(double x, double* L, double* dL) {  // nodes 0, 1/2, 1 (102_Int
   dL[2] = 4.0 * x - 1.0;
 }
 
-// the reference tables of ng Gauss points per direction, on the host
-static void hex27_fill_tables(int ng, Hex27Tables* h) {
+// the reference tables of ng Gauss points per direction, on the host (hex27.h: the matrix-free operator makes its own immutable copies from it)
+void hex27_fill_tables(int ng, Hex27Tables* h) {
   memset(h, 0, sizeof(*h));
   double gp[4], gw[4];
   for (int i = 0; i < ng; ++i) {

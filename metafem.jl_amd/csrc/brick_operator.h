@@ -1,5 +1,5 @@
-// What the two files of the matrix-free hex-8 brick operator share: brick_operator.hip (the handle, the entry points, the thermal kernels) and
-// brick_operator_elasticity.hip (the elasticity kernels and their launchers).  The library is one code object per .hip file and a kernel is launched
+// What the files of the matrix-free brick operator share: brick_operator.hip (the handle, the entry points, the hex-8 thermal kernels),
+// brick_operator_elasticity.hip (the hex-8 elasticity kernels and their launchers) and brick_operator_hex27.hip (the hex-27 thermal kernels and theirs).  The library is one code object per .hip file and a kernel is launched
 // from the file that defines it, so the device functions here are inline copies per file; the reference tables have ONE owner (bop_tables,
 // brick_operator.hip), and the handle's launch and diagonal hand an elasticity operator over to bop_elasticity_launch / bop_elasticity_jacobi.
 #pragma once
@@ -64,7 +64,8 @@ __device__ __forceinline__ double bop_face_weight(const H8Tables* __restrict__ T
   return T->fw[q] * sqrt(r0 * r0 + r1 * r1 + r2 * r2);
 }
 
-enum { BOP_PHYSICS_THERMAL = 1, BOP_PHYSICS_ELASTICITY = 2 };
+enum { BOP_PHYSICS_THERMAL = 1, BOP_PHYSICS_ELASTICITY = 2, BOP_PHYSICS_HEX27 = 3 };  // (HEX27: thermal on an order-2 brick; its parameter block is `thermal`)
+struct Hex27Tables;  // hex27.h
 struct mfem_brick_operator_s {
   mfem_operator_head head;  // MFEM_OPERATOR_BRICK (operator.h)
   mfem_context_s* ctx;
@@ -72,7 +73,8 @@ struct mfem_brick_operator_s {
   int physics;              // BOP_PHYSICS_*: which parameter block is set
   mfem_thermal_params thermal;
   mfem_elasticity_params elasticity;  // (traction_faces and sig are kept as sent and never read: they contribute nothing to K)
-  const H8Tables* tables;   // bop_tables(ctx->device, brick->ng): immutable
+  const H8Tables* tables;   // bop_tables(ctx->device, brick->ng): immutable (hex-8 physics)
+  const Hex27Tables* tables27;  // bop27_tables(ctx->device, brick->ng): immutable (BOP_PHYSICS_HEX27)
   int ng;                   // the brick's rule when the operator was created
   const double* seen_x0;    // the brick's first coordinate array at the last bind (a change starts a new epoch of the cycle-graph key)
   mfem_csr_s csr;           // pattern-less: what the Krylov loop holds in place of a matrix (n = fields x control points)
@@ -87,3 +89,12 @@ __device__ __forceinline__ double bop_scaled(const double* __restrict__ x, const
 int bop_elasticity_launch(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, const double* x, const double* dsc, double* y, double alpha,
                           double beta, const double* dotw, double* partials, int* n_partials, const int32_t* done_flag);
 int bop_elasticity_jacobi(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, double* d);
+
+// brick_operator_hex27.hip: the product and the diagonal of an operator with physics == BOP_PHYSICS_HEX27 (thermal, order-2 brick) under the same
+// contract; its immutable per-(device, rule) tables; bop27_prepare raises the volume kernel's dynamic-LDS limit (when an operator is created: never at
+// a launch).
+int bop27_tables(int device, int ng, const Hex27Tables** out);
+int bop27_prepare(int ng);
+int bop27_launch(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, const double* x, const double* dsc, double* y, double alpha,
+                 double beta, const double* dotw, double* partials, int* n_partials, const int32_t* done_flag);
+int bop27_jacobi(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, double* d);

@@ -17,14 +17,16 @@
 // the solve's cycle graphs), and leave the partial sums of dotw . y of the final y: the volume kernel's workgroup sums first, the face kernel's increments
 // behind them.  Then the grids are capped (brick_operator_decide.h): a workgroup FOLDS the work items b, b + grid, ... in that order; a product without
 // partial sums launches one workgroup per item, as the residual does.  No atomics.
-// This file owns the handle of BOTH physics (a physics tag selects the parameter block), every entry point, the tables and the bind; the kernels of
-// the three-field elasticity operator and their two launchers are in brick_operator_elasticity.hip (bop_launch and bop_jacobi hand over to them),
-// what the two files share is in brick_operator.h.
+// This file owns the handle of EVERY physics (a physics tag selects the parameter block), every entry point, the hex-8 tables and the bind; the kernels
+// of the three-field elasticity operator and their two launchers are in brick_operator_elasticity.hip, those of the thermal operator on an order-2
+// (hex-27) brick -- mfem_brick_operator_create_hex27 -- in brick_operator_hex27.hip (bop_launch and bop_jacobi hand over to them); what the files
+// share is in brick_operator.h.
 #include <memory>
 #include "hex8_device.h"
 #include "hex8_sumfac.h"
 #include "blas1.h"
 #include "brick_operator.h"
+#include "brick_operator_hex27_decide.h"
 static_assert(BOP_MAX_PARTIALS == MFEM_MAX_PARTIALS, "brick_operator_decide.h spells the cap out");
 
 static std::atomic<long long> g_brick_operator_count{0};
@@ -457,7 +459,7 @@ static BopThermal bop_thermal(const mfem_brick_operator_s* op) {
 // nothing is uploaded.  Called when the operator is bound -- before the driver can replay a cached cycle -- and again at every launch.
 static int bop_view(const mfem_brick_operator_s* op, BrickView* B) {
   const mfem_brick_s* m = op->brick;
-  const char* why = bop_refusal(m->p, m->plo, m->phi, m->m[0]);
+  const char* why = op->physics == BOP_PHYSICS_HEX27 ? bop27_refusal(m->p, m->plo, m->phi, m->m[0]) : bop_refusal(m->p, m->plo, m->phi, m->m[0]);
   if (why) return bop_refuse(MFEM_ERR_UNSUPPORTED, why);
   const int fields = op->physics == BOP_PHYSICS_ELASTICITY ? 3 : 1;
   MFEM_REQUIRE(fields * m->n_owned == op->csr.n, "the brick changed size under the operator");
@@ -477,6 +479,12 @@ static int bop_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* x, doubl
   const double* dsc = A->op_dsc;
   if (op->physics == BOP_PHYSICS_ELASTICITY) {  // (its kernels are launched from the file that defines them)
     rc = bop_elasticity_launch(ctx, op, B, x, dsc, y, alpha, beta, dotw, partials, n_partials, done_flag);
+    if (rc) return rc;
+    if (!ctx->probe_active) ++g_brick_operator_count;
+    return MFEM_OK;
+  }
+  if (op->physics == BOP_PHYSICS_HEX27) {
+    rc = bop27_launch(ctx, op, B, x, dsc, y, alpha, beta, dotw, partials, n_partials, done_flag);
     if (rc) return rc;
     if (!ctx->probe_active) ++g_brick_operator_count;
     return MFEM_OK;
@@ -513,6 +521,7 @@ static int bop_jacobi(mfem_context_s* ctx, mfem_brick_operator_s* op, double* d)
   const int rc = bop_view(op, &B);
   if (rc) return rc;
   if (op->physics == BOP_PHYSICS_ELASTICITY) return bop_elasticity_jacobi(ctx, op, B, d);
+  if (op->physics == BOP_PHYSICS_HEX27) return bop27_jacobi(ctx, op, B, d);
   const int64_t grid = bop_diagonal_grid(B.n_owned);
   MFEM_REQUIRE(grid < ((int64_t)1 << 31), "too many control points for one launch");
   hipLaunchKernelGGL(k_brick_diagonal, dim3((unsigned)grid), dim3(MFEM_BLOCK), 0, ctx->stream, B, bop_thermal(op), d);
@@ -558,15 +567,18 @@ static int bop_create(mfem_context ctx, mfem_brick m, int physics, const void* p
   *out = 0;
   MFEM_REQUIRE(ctx && m && p, "null argument");
   MFEM_REQUIRE(m->ctx == ctx, "the brick was created on another context");
-  const char* why = bop_refusal(m->p, m->plo, m->phi, m->m[0]);
+  const char* why = physics == BOP_PHYSICS_HEX27 ? bop27_refusal(m->p, m->plo, m->phi, m->m[0]) : bop_refusal(m->p, m->plo, m->phi, m->m[0]);
   if (why) return bop_refuse(MFEM_ERR_UNSUPPORTED, why);
   const H8Tables* tables = nullptr;
-  const int rct = bop_tables(ctx->device, m->ng, &tables);
+  const Hex27Tables* tables27 = nullptr;
+  int rct = physics == BOP_PHYSICS_HEX27 ? bop27_tables(ctx->device, m->ng, &tables27) : bop_tables(ctx->device, m->ng, &tables);
+  if (!rct && physics == BOP_PHYSICS_HEX27) rct = bop27_prepare(m->ng);
   if (rct) return rct;
   mfem_host_alloc_probe();
   std::unique_ptr<mfem_brick_operator_s> op(new mfem_brick_operator_s());
   op->head.kind = MFEM_OPERATOR_BRICK;
   op->tables = tables;
+  op->tables27 = tables27;
   op->ng = m->ng;
   op->seen_x0 = nullptr;
   op->ctx = ctx;
@@ -590,12 +602,15 @@ extern "C" int mfem_brick_operator_create(mfem_context ctx, mfem_brick m, const 
 extern "C" int mfem_brick_operator_create_elasticity(mfem_context ctx, mfem_brick m, const mfem_elasticity_params* p, uint64_t* out) try {
   return bop_create(ctx, m, BOP_PHYSICS_ELASTICITY, p, out);
 } MFEM_API_CATCH("mfem_brick_operator_create_elasticity")
+extern "C" int mfem_brick_operator_create_hex27(mfem_context ctx, mfem_brick m, const mfem_thermal_params* p, uint64_t* out) try {
+  return bop_create(ctx, m, BOP_PHYSICS_HEX27, p, out);
+} MFEM_API_CATCH("mfem_brick_operator_create_hex27")
 
 // a set-params call of the other physics answers MFEM_ERR_INVALID and changes nothing
 static int bop_params_target(uint64_t handle, const void* p, int physics, mfem_brick_operator_s** out) {
   mfem_brick_operator_s* op = bop_from_handle(handle);
   MFEM_REQUIRE(op && p, "null argument, or not a brick operator's handle");
-  MFEM_REQUIRE(op->physics == physics, "the operator was created for the other physics (thermal: mfem_brick_operator_set_params, elasticity: mfem_brick_operator_set_elasticity_params)");
+  MFEM_REQUIRE(op->physics == physics || (physics == BOP_PHYSICS_THERMAL && op->physics == BOP_PHYSICS_HEX27), "the operator was created for the other physics (thermal: mfem_brick_operator_set_params, elasticity: mfem_brick_operator_set_elasticity_params)");
   MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
   *out = op;
   return MFEM_OK;

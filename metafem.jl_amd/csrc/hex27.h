@@ -24,6 +24,8 @@ struct Hex27Tables {        // device-global, filled once per ng
 };
 // the device copy, filled for the ng of the last hex27_upload_tables (assemble_hex27.hip owns it)
 const Hex27Tables* hex27_tables();
+// the tables of ng Gauss points per direction, filled on the host (assemble_hex27.hip)
+void hex27_fill_tables(int ng, Hex27Tables* h);
 
 struct Hex27Args {
   BrickView B;
