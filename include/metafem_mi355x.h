@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MFEM_ABI_VERSION 9
+#define MFEM_ABI_VERSION 10
 
 typedef enum {
   MFEM_OK = 0,
@@ -170,6 +170,11 @@ typedef enum {
  * from r = b: 0), +1 for the true residual the restart wrapper computes after every pass.  Every solver counts the products that ran, on the
  * device (cg!: from its iteration count), so a cycle replayed after the stop and the unrun rest of a cut-off IDR(s) cycle count nothing:
  *   cg!             x0 + it + 1                      (A p per iteration; cg_variant 1, 3, 4, and 0 unless it picks the next form)
+ *   cg! + multigrid x0 + it + 2 nu it + 1             (MFEM_PRECOND_MULTIGRID; level-0 products only: A p per iteration, one V-cycle of 2 nu level-0
+ *                                                    products per iteration -- the first before iteration 1, none after the last; a brick that does
+ *                                                    not coarsen has one level: nu_c - 1 in place of 2 nu; it = 0: x0 + 1.  This pass reads the stop
+ *                                                    flag after EVERY iteration, whatever check_every says: a cycle costs far more than the read, and
+ *                                                    an iteration that stops the pass launches no cycle)
  *   cg! (1 reduction) x0 + 1 + it + 1                (cg_variant 2, or 0 with a communicator: A u before the first iteration, then one per
  *                                                    iteration -- also when the start has converged, it = 0)
  *   bicgstabl_GS!(l) x0 + 2 (it - 1) + 1             (it = 1 + l per sweep; 2 l products per sweep)
@@ -189,7 +194,9 @@ typedef enum {
 typedef enum {
   MFEM_PRECOND_NONE = 0,            /* Identity, 02_Preconditioner.jl:78-86 */
   MFEM_PRECOND_JACOBI_RIGHT_DIAG = 1,   /* Pr_Jacobi!(normalized_by_column=false), :103-120 */
-  MFEM_PRECOND_JACOBI_RIGHT_COLNORM = 2 /* Pr_Jacobi!(normalized_by_column=true) */
+  MFEM_PRECOND_JACOBI_RIGHT_COLNORM = 2,/* Pr_Jacobi!(normalized_by_column=true) */
+  MFEM_PRECOND_MULTIGRID = 3        /* added (ABI 10): a geometric multigrid V-cycle, cg! on a hex-8 thermal brick operator only (mfem_solve_operator;
+                                       see mfem_brick_multigrid_create) */
 } mfem_precond_kind;
 
 typedef enum {
@@ -777,6 +784,65 @@ int mfem_brick_operator_set_elasticity_params(uint64_t op, const mfem_elasticity
  * MFEM_ERR_UNSUPPORTED with a message, nothing created: an order-1 (hex-8) brick (it takes mfem_brick_operator_create), a brick with a slab set
  * (also answered by apply / diagonal / a solve if the slab is set later). */
 int mfem_brick_operator_create_hex27(mfem_context ctx, mfem_brick m, const mfem_thermal_params* p, uint64_t* op /* [host] out */);
+
+/* ---- geometric multigrid preconditioner for cg! on the hex-8 thermal brick operator (ABI 10) ------------------------------------------------------
+ * Pr_Multigrid: one V-cycle as the preconditioner of cg!, for an operator of mfem_brick_operator_create (thermal, whole lattice, one rank) whose K is
+ * symmetric (no Nitsche term active).  Nothing needs a matrix, a pattern or an atomic: products and diagonals of the brick operator on every level.
+ *   sign     s = the sign of diag K (the thermal K is negative definite), detected at every setup; A = s K, dinv = 1 / |diag K|.  A diagonal of mixed
+ *            sign or with a zero: MFEM_ERR_UNSUPPORTED.  The cycle approximates A^-1: r . z > 0.
+ *   levels   level 0 is the caller's brick (nx, ny, nz); level l + 1 exists while all three element counts of level l are even and each half is >= 2,
+ *            at most MFEM_MG_MAX_LEVELS.  A coarse brick is the library's own (same lx, ly, lz, itg_order); its coordinates are INJECTED from the next
+ *            finer level at every setup (coarse point (i, j, k) takes fine point (2 i, 2 j, 2 k)); its operator is mfem_brick_operator_create on it
+ *            with the caller's parameters (rediscretisation).
+ *   transfers P = trilinear interpolation (weights (1/2)^(number of odd fine indices)), restriction = P' unscaled; gather kernels, fixed order.
+ *   smoother  Chebyshev polynomial of degree nu in D^-1 A on [hi / range, hi], hi = 1.1 x lambda_max; the residual is carried by recurrence.
+ *   lambda_max(D^-1 A) per level: eig_steps power steps from the start vector mfem_rand(0x4d47, level), then the Rayleigh quotient v . A v / v . D v
+ *            (never above the true value); the same bits at every setup.
+ *   cycle    below the coarsest level: nu steps from a zero start, restrict the carried residual, recurse, z += P e and r -= A (P e), nu steps; on the
+ *            coarsest: coarse_degree steps on [hi / coarse_range, hi].  Level-l products per cycle: 2 nu, on the coarsest coarse_degree - 1.
+ * A zero field of the options takes its default: smoother_degree 2, coarse_degree 32, smoothing_range 4, coarse_range 300, eig_steps 20 (at least
+ * 10), max_levels 12. */
+#define MFEM_MG_MAX_LEVELS 12
+typedef struct {
+  int32_t smoother_degree;  /* nu */
+  int32_t coarse_degree;    /* nu_c */
+  double smoothing_range;   /* rho_s: the smoother works on [hi / rho_s, hi] */
+  double coarse_range;      /* rho_c */
+  int32_t eig_steps;
+  int32_t max_levels;
+} mfem_multigrid_options;
+typedef struct {
+  int32_t levels;
+  int32_t sign;             /* of diag K at the last setup: -1 or +1; 0 before the first setup */
+  int32_t nx[12];           /* element counts per level (MFEM_MG_MAX_LEVELS entries) */
+  int32_t ny[12];
+  int32_t nz[12];
+  double lambda_max[12];    /* the estimate of lambda_max(D^-1 A) per level, without the 1.1 */
+  int64_t products[12];     /* products the CYCLES launched on each level since creation, counted on the host (a setup's eig_steps products per
+                               level are in setup_products) */
+  int64_t setup_products;   /* products the setups launched, all levels together */
+  int64_t bytes;            /* device bytes the hierarchy owns: vectors, coarse coordinates and lattice tables */
+  int64_t cycles;           /* cycles run since creation */
+  int64_t setups;
+} mfem_multigrid_info;
+/* Allocates the coarse bricks, operators and vectors and three level-0 scratch vectors and ATTACHES the hierarchy to the operator: one per operator,
+ * destroyed with it (or earlier, by mfem_brick_multigrid_destroy).  opts may be NULL.  The handle is an opaque 64-bit value, 0 = none.
+ * MFEM_ERR_UNSUPPORTED, nothing created: not a hex-8 thermal brick operator, a Nitsche term active.  MFEM_ERR_INVALID: null arguments, another
+ * context's operator, an operator that already has a hierarchy, options out of range. */
+int mfem_brick_multigrid_create(mfem_context ctx, uint64_t op, const mfem_multigrid_options* opts, uint64_t* mg /* [host] out */);
+/* Re-sends the fine operator's CURRENT parameters to every level, injects the coordinates, computes the diagonals, the sign and the estimates.
+ * Synchronises the context stream.  MFEM_ERR_UNSUPPORTED: a Nitsche term active, a diagonal of mixed sign or with a zero. */
+int mfem_brick_multigrid_setup(mfem_context ctx, uint64_t mg);
+/* z = one cycle applied to r (one entry per control point; r is not changed).  Needs a setup; uses the levels as that setup left them. */
+int mfem_brick_multigrid_apply(mfem_context ctx, uint64_t mg, const double* r, double* z);
+int mfem_brick_multigrid_info(uint64_t mg, mfem_multigrid_info* info /* [host] out */);
+int mfem_brick_multigrid_destroy(uint64_t mg);
+/* mfem_solve_operator with precond = MFEM_PRECOND_MULTIGRID: only for a hex-8 thermal brick operator, MFEM_SOLVER_CG, no left preconditioner, no
+ * communicator, no active Nitsche term -- every other combination, every other operator kind and mfem_solve answer MFEM_ERR_UNSUPPORTED with a reason
+ * naming what is missing; nothing is launched, nothing is written.  A solve creates a default hierarchy when none is attached and ALWAYS runs the
+ * setup first, inside solve_ms (where a Jacobi solve computes its diagonal): parameters re-sent and coordinates overwritten since the last solve can
+ * never leave a stale level.  Nothing is allocated once the iteration has started.  cg_variant and check_every are ignored (the classic recurrence;
+ * the flag is read after every iteration). */
 
 /* ---- multi-GPU (new; the reference is single-GPU, F6) ------------------------------------ */
 /* 128-byte RCCL unique id, created on rank 0 and shipped to the other ranks by the host

@@ -21,7 +21,7 @@ import LinearAlgebra
 
 # ---- library handle and error convention ---------------------------------------------------------------------------------
 const lib = get(ENV, "METAFEM_MI355X_LIB", joinpath(@__DIR__, "..", "metafem.jl_amd", "libmetafem_mi355x.so"))
-const ABI_VERSION = 9    # == MFEM_ABI_VERSION
+const ABI_VERSION = 10   # == MFEM_ABI_VERSION
 
 struct MFEMError <: Exception
     rc::Cint
@@ -58,7 +58,7 @@ ctx() = (isassigned(CTX) || (CTX[] = Context(0)); CTX[].h)
 # ---- struct mirrors of include/metafem_mi355x.h (isbits, C layout) ---------------------------------------------------------
 Base.@kwdef struct SolveOptions           # == mfem_solve_options
     method::Int32 = 2                     # 0 cg (new), 1 bicgstabl_GS!, 2 idrs!, 3 cgs2!, 4 gmres!, 5 cgs!, 6 tfqmr!, 7 lsqr!
-    precond::Int32 = 1                    # 0 Identity, 1 Pr_Jacobi!, 2 Pr_Jacobi!(normalized_by_column = true)
+    precond::Int32 = 1                    # 0 Identity, 1 Pr_Jacobi!, 2 Pr_Jacobi!(normalized_by_column = true), 3 Pr_Multigrid! (cg! on a hex-8 thermal BrickOperator)
     l_or_s::Int32 = 0                     # the `s` kwarg (tfqmr!: checkiter)
     maxiter::Int32 = 2000
     max_pass::Int32 = 4
@@ -222,7 +222,9 @@ end
 
 # ---- S1: the linear-solver seam --------------------------------------------------------------------------------------------
 const SOLVER_ID = Dict(:cg! => 0, :bicgstabl_GS! => 1, :idrs! => 2, :cgs2! => 3, :gmres! => 4, :cgs! => 5, :tfqmr! => 6, :lsqr! => 7)
-const PR_ID = Dict(:Identity => 0, :Pr_Jacobi! => 1)      # (install! passes nameof(Pr_func!))
+const PRECOND_MULTIGRID = Int32(3)                        # == MFEM_PRECOND_MULTIGRID
+const MG_MAX_LEVELS = 12                                  # == MFEM_MG_MAX_LEVELS
+const PR_ID = Dict(:Identity => 0, :Pr_Jacobi! => 1, :Pr_Multigrid! => Int(PRECOND_MULTIGRID))      # (install! passes nameof(Pr_func!))
 const PL_ID = Dict(:Identity => 0, :Pl_Jacobi => 1)      # cylinder_flow/3D_MetaFEM_Script.jl:90 passes Pl_func = Pl_Jacobi
 
 """
@@ -753,6 +755,59 @@ function iterative_Solve!(op::BrickOperator, residue, converge_tol; Sv_func!::Sy
     return x
 end
 brick_operator_count() = ccall((:mfem_debug_brick_operator_count, lib), Int64, ())
+
+# ---- geometric multigrid preconditioner for cg! on the hex-8 thermal brick operator (mfem_brick_multigrid_*, ABI 10) -------------------------------
+# iterative_Solve!(op, residue, tol; Sv_func! = :cg!, Pr_func! = :Pr_Multigrid!) applies one V-cycle per iteration; the solve creates a default
+# hierarchy when none is attached and always runs its setup first.  A zero field of the options takes the default (2, 32, 4, 300, 20, 12).
+Base.@kwdef struct MultigridOptions       # == mfem_multigrid_options
+    smoother_degree::Int32 = 0
+    coarse_degree::Int32 = 0
+    smoothing_range::Float64 = 0.0
+    coarse_range::Float64 = 0.0
+    eig_steps::Int32 = 0
+    max_levels::Int32 = 0
+end
+
+struct MultigridInfo                      # == mfem_multigrid_info
+    levels::Int32
+    sign::Int32
+    nx::NTuple{12, Int32}
+    ny::NTuple{12, Int32}
+    nz::NTuple{12, Int32}
+    lambda_max::NTuple{12, Float64}
+    products::NTuple{12, Int64}
+    setup_products::Int64
+    bytes::Int64
+    cycles::Int64
+    setups::Int64
+end
+
+mutable struct BrickMultigrid
+    h::UInt64
+    op::BrickOperator
+end
+
+"The hierarchy of a hex-8 thermal brick operator: one per operator, destroyed with it.  `nothing`: refused (mfem_last_error says why)."
+function brick_multigrid(op::BrickOperator, opts::MultigridOptions = MultigridOptions())
+    h = Ref{UInt64}(0)
+    rc = ccall((:mfem_brick_multigrid_create, lib), Cint, (Ptr{Cvoid}, UInt64, Ref{MultigridOptions}, Ref{UInt64}), ctx(), op.h, Ref(opts), h)
+    rc == -3 && return nothing
+    check(rc)
+    return BrickMultigrid(h[], op)
+end
+multigrid_setup!(mg::BrickMultigrid) = check(ccall((:mfem_brick_multigrid_setup, lib), Cint, (Ptr{Cvoid}, UInt64), ctx(), mg.h))
+"z = one cycle applied to r"
+multigrid_apply!(z, mg::BrickMultigrid, r) =
+    check(ccall((:mfem_brick_multigrid_apply, lib), Cint, (Ptr{Cvoid}, UInt64, Ptr{Cvoid}, Ptr{Cvoid}), ctx(), mg.h, dptr(r), dptr(z)))
+function multigrid_info(mg::BrickMultigrid)
+    info = Ref{MultigridInfo}()
+    check(ccall((:mfem_brick_multigrid_info, lib), Cint, (UInt64, Ref{MultigridInfo}), mg.h, info))
+    return info[]
+end
+function multigrid_destroy!(mg::BrickMultigrid)
+    check(ccall((:mfem_brick_multigrid_destroy, lib), Cint, (UInt64,), mg.h))
+    mg.h = 0
+end
 
 # ---- several GPUs: one Julia process per GPU (MPI.jl), slab decomposition along the first dimension ---------------------------
 "Rank 0 creates the 128-byte RCCL id; the host broadcasts it (MPI.Bcast!)."

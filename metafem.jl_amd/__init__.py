@@ -29,7 +29,7 @@ import torch
 from . import _lib
 from ._lib import (ElasticityParams, MetaFEMError, OpLayout, SolveOptions, SolveStats, ThermalParams, check, lib)
 
-__all__ = ["Context", "FEM_SpMat_CSR", "MeshOperator", "BrickOperator", "ElasticityBrickOperator", "Hex27BrickOperator", "BrickOperatorRefused", "brick_operator_refusal",
+__all__ = ["Context", "FEM_SpMat_CSR", "MeshOperator", "BrickOperator", "BrickMultigrid", "MultigridRefused", "Pr_Multigrid_", "multigrid_plan", "ElasticityBrickOperator", "Hex27BrickOperator", "BrickOperatorRefused", "brick_operator_refusal",
            "brick_operator_hex27_refusal", "mul_", "tmul_", "dot", "nrm2", "axpby_", "FEM_rand", "normalized_norm",
            "iterative_Solve", "Brick", "make_Brick", "ThermalDomain", "ElasticityDomain", "MetaFEMError", "SolveStats",
            "cg_", "bicgstabl_GS_", "idrs_", "cgs2_", "gmres_", "cgs_", "tfqmr_", "lsqr_", "FACE_BITS"]
@@ -37,6 +37,7 @@ __all__ = ["Context", "FEM_SpMat_CSR", "MeshOperator", "BrickOperator", "Elastic
 # solver / preconditioner selectors (the reference passes Julia functions: Sv_func! = idrs! ...)
 cg_, bicgstabl_GS_, idrs_, cgs2_, gmres_, cgs_, tfqmr_, lsqr_ = 0, 1, 2, 3, 4, 5, 6, 7
 Identity, Pr_Jacobi_, Pr_Jacobi_colnorm_ = 0, 1, 2
+Pr_Multigrid_ = 3  # a geometric multigrid V-cycle: cg_ on a hex-8 thermal BrickOperator only (BrickOperator.multigrid)
 Pl_Jacobi_, Pl_Jacobi_rownorm_ = 1, 2  # Pl_func selectors (02_Preconditioner.jl:155-168)
 
 # reference local face ids (ref_geometry/002_Initialization.jl:8): 1 z=0, 2 y=0, 3 x=L, 4 y=L, 5 x=0, 6 z=L
@@ -270,6 +271,7 @@ class BrickOperator:
         self.ctx, self.brick = brick.ctx, brick  # (the library borrows the brick: kept alive here)
         self.n = brick.ncp
         self.nnz = 0
+        self._mg = None  # the BrickMultigrid made by multigrid(), if any (a solve's default hierarchy lives in the library alone)
         self._h = C.c_uint64()
         rc = lib.mfem_brick_operator_create(self.ctx._h, brick._h, C.byref(params), C.byref(self._h))
         if rc == -3:  # MFEM_ERR_UNSUPPORTED: a brick the operator does not cover
@@ -298,10 +300,91 @@ class BrickOperator:
         check(lib.mfem_brick_operator_diagonal(self.ctx._h, self._h, _ptr(d)))
         return d
 
+    def multigrid(self, **opts) -> "BrickMultigrid":
+        """The geometric multigrid hierarchy of this operator (mfem_brick_multigrid_create): one per operator, destroyed with it.  opts:
+        smoother_degree, coarse_degree, smoothing_range, coarse_range, eig_steps, max_levels (0 or absent: the default).  Raises MultigridRefused for
+        an operator the hierarchy does not cover (elasticity, hex-27, an active Nitsche term)."""
+        return BrickMultigrid(self, **opts)
+
     def close(self):
         if self._h:
+            mg = getattr(self, "_mg", None)
+            if mg is not None:  # (the library destroys the hierarchy with its operator)
+                mg._h = C.c_uint64()
+                self._mg = None
             lib.mfem_brick_operator_destroy(self._h)
             self._h = C.c_uint64()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class MultigridRefused(MetaFEMError):
+    """mfem_brick_multigrid_create / _setup answered MFEM_ERR_UNSUPPORTED; the message is the library's."""
+
+
+def multigrid_plan(n, max_levels: int = 12):
+    """The level plan of an (nx, ny, nz) brick (csrc/brick_multigrid_decide.h: mg_plan): level l + 1 exists while all three element counts of level l
+    are even and each half is >= 2."""
+    levels = [tuple(int(v) for v in n)]
+    while len(levels) < max_levels and all(v % 2 == 0 and v // 2 >= 2 for v in levels[-1]):
+        levels.append(tuple(v // 2 for v in levels[-1]))
+    return levels
+
+
+class BrickMultigrid:
+    """Geometric multigrid V-cycle of a hex-8 thermal BrickOperator (mfem_brick_multigrid_*, csrc/brick_multigrid.hip): the preconditioner
+    `iterative_Solve(op, None, b, tol, Sv_func=cg_, Pr_func=Pr_Multigrid_)` applies.  A solve runs setup() itself, always; setup() and apply() are
+    for a caller that uses the cycle on its own."""
+
+    def __init__(self, op: "BrickOperator", **opts):
+        unknown = set(opts) - {"smoother_degree", "coarse_degree", "smoothing_range", "coarse_range", "eig_steps", "max_levels"}
+        if unknown:
+            raise TypeError(f"unknown multigrid options {sorted(unknown)}")
+        self.ctx, self.op = op.ctx, op
+        self._h = C.c_uint64()
+        o = _lib.MultigridOptions(int(opts.get("smoother_degree", 0)), int(opts.get("coarse_degree", 0)), float(opts.get("smoothing_range", 0.0)),
+                                  float(opts.get("coarse_range", 0.0)), int(opts.get("eig_steps", 0)), int(opts.get("max_levels", 0)))
+        rc = lib.mfem_brick_multigrid_create(self.ctx._h, op._h, C.byref(o), C.byref(self._h))
+        if rc == -3:
+            raise MultigridRefused(lib.mfem_last_error().decode())
+        check(rc)
+        op._mg = self
+
+    def setup(self):
+        rc = lib.mfem_brick_multigrid_setup(self.ctx._h, self._h)
+        if rc == -3:
+            raise MultigridRefused(lib.mfem_last_error().decode())
+        check(rc)
+        return self
+
+    def apply(self, r: torch.Tensor, z: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """z = one cycle applied to r (r is not changed)."""
+        _need(r, torch.float64, "r", self.op.n)
+        if z is None:
+            z = torch.empty_like(r)
+        _need(z, torch.float64, "z", self.op.n)
+        check(lib.mfem_brick_multigrid_apply(self.ctx._h, self._h, _ptr(r), _ptr(z)))
+        return z
+
+    def info(self) -> dict:
+        """levels, ne (element counts per level), lambda_max (per level, without the 1.1), sign, bytes, cycles, setups, products (per level, the
+        cycles' only), setup_products."""
+        i = _lib.MultigridInfo()
+        check(lib.mfem_brick_multigrid_info(self._h, C.byref(i)))
+        L = i.levels
+        return dict(levels=L, sign=i.sign, ne=[(i.nx[l], i.ny[l], i.nz[l]) for l in range(L)], lambda_max=[i.lambda_max[l] for l in range(L)],
+                    products=[i.products[l] for l in range(L)], setup_products=i.setup_products, bytes=i.bytes, cycles=i.cycles, setups=i.setups)
+
+    def close(self):
+        if self._h:
+            lib.mfem_brick_multigrid_destroy(self._h)
+            self._h = C.c_uint64()
+            if getattr(self.op, "_mg", None) is self:
+                self.op._mg = None
 
     def __del__(self):
         try:
@@ -461,7 +544,9 @@ def iterative_Solve(A, K_vals: Optional[torch.Tensor], residue: torch.Tensor, co
     matrix (one stream less again; on the mirrored-sweep layout, one rank: the auto choice there, else 3).
 
     A MeshOperator or a BrickOperator with K_vals = None solves matrix-free (mfem_solve_operator): every Sv_func but lsqr_, Pr_func Identity or Pr_Jacobi_, Pl_func
-    Identity, no scale_in_place.
+    Identity, no scale_in_place.  Pr_func = Pr_Multigrid_: a geometric multigrid V-cycle, for Sv_func = cg_ on a hex-8 thermal BrickOperator
+    without an active Nitsche term and without a communicator (anything else raises with the library's reason); the solve creates a default hierarchy
+    when BrickOperator.multigrid has not made one and always runs its setup first (inside solve_ms); check_every and cg_variant are ignored.
 
     Returns (delta_x, stats); delta_x is a NEW device vector like the reference's return value.
     """
@@ -779,7 +864,7 @@ class ThermalDomain:
     reference's Newton driver (04_Time_Domain.jl:59-80)."""
 
     def __init__(self, brick: Brick, k: float, h: float, Tenv: float, robin_faces: int = ALL_FACES, *, fixed_faces: int = 0,
-                 h_penalty: float = 0.0, Tw: float = 0.0, matrix_free=False):
+                 h_penalty: float = 0.0, Tw: float = 0.0, matrix_free=False, multigrid: bool = False):
         self.brick, self.k, self.h, self.Tenv, self.robin_faces = brick, k, h, Tenv, robin_faces
         # weakly imposed Dirichlet faces (fix_boundary of examples/thermal_conduction/2D_Script.jl:58)
         self.fixed = dict(fixed_faces=fixed_faces, h_penalty=h_penalty, Tw=Tw)
@@ -815,6 +900,23 @@ class ThermalDomain:
         self.converge_tol = 1e-6
         self.linear_solver: Callable = lambda gf: iterative_Solve(gf.A, gf.K_total, gf.residue, gf.converge_tol,
                                                                    Sv_func=idrs_, maxiter=2000, max_pass=10, s=8)[0]
+        # multigrid = True (with matrix_free on a hex-8 brick, K symmetric): linear_solver is cg_ with the V-cycle as its preconditioner.  With fixed
+        # faces (K is nonsymmetric), on a hex-27 operator or on a domain that fell back to the assembled path the default solver stays, and
+        # multigrid_reason says why.
+        self.multigrid, self.multigrid_reason = False, None
+        if multigrid:
+            if not self.matrix_free:
+                self.multigrid_reason = "the domain holds an assembled matrix (" + (self.matrix_free_reason or "matrix_free was not asked for") + \
+                                        "): the multigrid preconditioner needs the matrix-free hex-8 operator"
+            elif hex27:
+                self.multigrid_reason = "a hex-27 operator: the multigrid preconditioner covers the hex-8 thermal brick operator"
+            elif fixed_faces and (h_penalty != 0.0 or k != 0.0):
+                self.multigrid_reason = "fixed_faces make K nonsymmetric: the multigrid preconditioner needs cg_"
+            else:
+                self.multigrid = True
+                self.mg = self.A.multigrid()  # (the solves run its setup: K_linear_func's parameters can never leave a stale level)
+                self.linear_solver = lambda gf: iterative_Solve(gf.A, None, gf.residue, gf.converge_tol, Sv_func=cg_, Pr_func=Pr_Multigrid_,
+                                                                maxiter=200, max_pass=4)[0]
         self.history = []
 
     def K_linear_func(self):

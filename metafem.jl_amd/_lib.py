@@ -117,6 +117,20 @@ class OperatorTerm(C.Structure):
                 ("normal_coef", c_double * 3)]
 
 
+MG_MAX_LEVELS = 12  # MFEM_MG_MAX_LEVELS
+
+
+class MultigridOptions(C.Structure):
+    _fields_ = [("smoother_degree", c_int32), ("coarse_degree", c_int32), ("smoothing_range", c_double), ("coarse_range", c_double),
+                ("eig_steps", c_int32), ("max_levels", c_int32)]
+
+
+class MultigridInfo(C.Structure):
+    _fields_ = [("levels", c_int32), ("sign", c_int32), ("nx", c_int32 * 12), ("ny", c_int32 * 12), ("nz", c_int32 * 12),
+                ("lambda_max", c_double * 12), ("products", c_int64 * 12), ("setup_products", c_int64), ("bytes", c_int64), ("cycles", c_int64),
+                ("setups", c_int64)]
+
+
 ALLREDUCE_CB = C.CFUNCTYPE(c_int, c_void_p, C.POINTER(c_double), c_int32)
 EXCHANGE_CB = C.CFUNCTYPE(c_int, c_void_p, C.POINTER(c_double), C.POINTER(c_double), C.POINTER(c_double), C.POINTER(c_double), c_int64)
 
@@ -258,6 +272,13 @@ SIGNATURES = {
     "mfem_brick_operator_diagonal": (c_int, [P, c_uint64, P]),
     "mfem_debug_brick_operator_count": (c_int64, []),
     "mfem_debug_brick_operator_apply_dot": (c_int, [P, c_uint64, P, P, c_double, c_double, P, P, C.POINTER(c_int32)]),
+    "mfem_brick_multigrid_create": (c_int, [P, c_uint64, C.POINTER(MultigridOptions), C.POINTER(c_uint64)]),
+    "mfem_brick_multigrid_setup": (c_int, [P, c_uint64]),
+    "mfem_brick_multigrid_apply": (c_int, [P, c_uint64, P, P]),
+    "mfem_brick_multigrid_info": (c_int, [c_uint64, C.POINTER(MultigridInfo)]),
+    "mfem_brick_multigrid_destroy": (c_int, [c_uint64]),
+    "mfem_debug_brick_multigrid_transfer": (c_int, [P, c_uint64, c_int32, c_int32, P, P]),
+    "mfem_debug_brick_multigrid_coords": (P, [c_uint64, c_int32, c_int32]),
     "mfem_mesh_var_elements": (c_int, [P, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, c_int32, c_int32,
                                        C.POINTER(VarBatchTerm), P, P, c_int64]),
     "mfem_mesh_var_facets": (c_int, [P, c_int32, c_int32, c_int32, c_int32, c_int64, c_int64, P, P, P, P, P, P, P, c_int32,

@@ -1,0 +1,174 @@
+// The host decisions of the geometric multigrid preconditioner on hex-8 thermal bricks (brick_multigrid.hip, krylov_cg_mg.hip) that are arithmetic
+// alone: the level plan, the options' defaults and their refusals, the Chebyshev coefficients, the grids and tiles of the transfer kernels, how many
+// vectors a level owns, the device bytes of a hierarchy, the products of a cycle and of a pass, and which solves take the preconditioner.  Plain
+// integers in, plain structs out; no HIP, no context: tools/host_check_brick_multigrid.cpp walks them on the CPU.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include "../../include/metafem_mi355x.h"
+
+#define MG_MAX_LEVELS 12  // (= MFEM_MG_MAX_LEVELS)
+static_assert(MG_MAX_LEVELS == MFEM_MG_MAX_LEVELS, "the header spells the cap out");
+
+// ---- the options: a zero field takes the default -----------------------------------------------------------------------------------------------------
+#define MG_DEFAULT_SMOOTHER_DEGREE 2
+#define MG_DEFAULT_COARSE_DEGREE 32
+#define MG_DEFAULT_SMOOTHING_RANGE 4.0
+#define MG_DEFAULT_COARSE_RANGE 300.0
+#define MG_DEFAULT_EIG_STEPS 20
+#define MG_MIN_EIG_STEPS 10
+#define MG_MAX_DEGREE 4096
+#define MG_EIG_SAFETY 1.1  // hi = 1.1 x the estimate of lambda_max(D^-1 A)
+#define MG_EIG_SEED 0x4d47u  // the start vector of the estimate: mfem_rand(MG_EIG_SEED, level)
+
+struct MgOptions {
+  int nu, nu_c, eig_steps, max_levels;
+  double range_s, range_c;
+};
+// nullptr: taken (*out filled); otherwise what is wrong (MFEM_ERR_INVALID)
+static inline const char* mg_options(const mfem_multigrid_options* o, MgOptions* out) {
+  MgOptions r{MG_DEFAULT_SMOOTHER_DEGREE, MG_DEFAULT_COARSE_DEGREE, MG_DEFAULT_EIG_STEPS, MG_MAX_LEVELS, MG_DEFAULT_SMOOTHING_RANGE, MG_DEFAULT_COARSE_RANGE};
+  if (o) {
+    if (o->smoother_degree < 0 || o->smoother_degree > MG_MAX_DEGREE) return "smoother_degree must be in 1 .. 4096 (0: the default, 2)";
+    if (o->coarse_degree < 0 || o->coarse_degree > MG_MAX_DEGREE) return "coarse_degree must be in 1 .. 4096 (0: the default, 32)";
+    if (o->smoothing_range != 0.0 && !(o->smoothing_range > 1.0)) return "smoothing_range must be > 1 (0: the default, 4)";
+    if (o->coarse_range != 0.0 && !(o->coarse_range > 1.0)) return "coarse_range must be > 1 (0: the default, 300)";
+    if (o->eig_steps != 0 && (o->eig_steps < MG_MIN_EIG_STEPS || o->eig_steps > MG_MAX_DEGREE)) return "eig_steps must be in 10 .. 4096 (0: the default, 20)";
+    if (o->max_levels < 0 || o->max_levels > MG_MAX_LEVELS) return "max_levels must be in 1 .. 12 (0: the default, 12)";
+    if (o->smoother_degree) r.nu = o->smoother_degree;
+    if (o->coarse_degree) r.nu_c = o->coarse_degree;
+    if (o->smoothing_range != 0.0) r.range_s = o->smoothing_range;
+    if (o->coarse_range != 0.0) r.range_c = o->coarse_range;
+    if (o->eig_steps) r.eig_steps = o->eig_steps;
+    if (o->max_levels) r.max_levels = o->max_levels;
+  }
+  *out = r;
+  return nullptr;
+}
+
+// ---- the level plan: level 0 is the caller's brick; level l + 1 exists while all three element counts of level l are even and each half is >= 2 ----
+struct MgPlan {
+  int nlev;
+  int ne[MG_MAX_LEVELS][3];
+};
+static inline MgPlan mg_plan(int nx, int ny, int nz, int max_levels) {
+  MgPlan P;
+  P.nlev = 1;
+  P.ne[0][0] = nx; P.ne[0][1] = ny; P.ne[0][2] = nz;
+  if (max_levels < 1 || max_levels > MG_MAX_LEVELS) max_levels = MG_MAX_LEVELS;
+  while (P.nlev < max_levels) {
+    const int* e = P.ne[P.nlev - 1];
+    if ((e[0] | e[1] | e[2]) & 1) break;
+    if (e[0] / 2 < 2 || e[1] / 2 < 2 || e[2] / 2 < 2) break;
+    for (int d = 0; d < 3; ++d) P.ne[P.nlev][d] = e[d] / 2;
+    ++P.nlev;
+  }
+  return P;
+}
+static inline int64_t mg_points(const int* ne) { return (int64_t)(ne[0] + 1) * (ne[1] + 1) * (ne[2] + 1); }
+
+// ---- the transfer kernels: a thread per lattice point of the lattice the kernel WRITES (restriction: the coarse one; prolongation and the injection
+// of the coordinates: the fine resp. the coarse one), lanes along k, the fastest index: a workgroup owns MG_TILE_J lattice lines x MG_TILE_K points
+// of one lattice plane ------------------------------------------------------------------------------------------------------------------------------
+#define MG_TILE_K 64
+#define MG_TILE_J 4
+#define MG_TILE_THREADS (MG_TILE_K * MG_TILE_J)
+#define MG_RESTRICT_TILE_K MG_TILE_K   // (coarse points)
+#define MG_RESTRICT_TILE_J MG_TILE_J
+#define MG_PROLONG_TILE_K MG_TILE_K    // (fine points)
+#define MG_PROLONG_TILE_J MG_TILE_J
+struct MgGrid {
+  unsigned gx, gy, gz;  // tiles along k, tiles along j, planes
+};
+static inline MgGrid mg_transfer_grid(int m0, int m1, int m2) {
+  MgGrid g;
+  g.gx = (unsigned)((m2 + MG_TILE_K - 1) / MG_TILE_K);
+  g.gy = (unsigned)((m1 + MG_TILE_J - 1) / MG_TILE_J);
+  g.gz = (unsigned)m0;
+  return g;
+}
+// the point thread t of workgroup (bx, by, bz) owns; false: none (past the end of a line or of the plane)
+static inline bool mg_tile_point(unsigned bx, unsigned by, unsigned bz, int t, int m1, int m2, int* i, int* j, int* k) {
+  *i = (int)bz;
+  *j = (int)by * MG_TILE_J + t / MG_TILE_K;
+  *k = (int)bx * MG_TILE_K + t % MG_TILE_K;
+  return *j < m1 && *k < m2;
+}
+// a launch's grid dimensions y and z hold at most 65535 workgroups
+static inline bool mg_grid_ok(const MgGrid& g) { return g.gx >= 1 && g.gy >= 1 && g.gz >= 1 && g.gy <= 65535u && g.gz <= 65535u; }
+
+// ---- vectors and bytes ------------------------------------------------------------------------------------------------------------------------------
+// Level 0 works on the caller's r and z and owns three scratch vectors (1 / |diag|, the carried residual, the Chebyshev direction); a coarse level owns
+// five (its right-hand side and its iterate besides).  Every vector is padded to a multiple of 32 doubles.  A coarse level also owns its brick: three
+// coordinate arrays and the per-dimension lattice tables of mfem_brick_create (two int32 and one int64 entry per lattice index, one more int64).
+#define MG_FINE_VECTORS 3
+#define MG_COARSE_VECTORS 5
+#define MG_FLAG_BYTES 16
+static inline int64_t mg_padded(int64_t n) { return (n + 31) / 32 * 32; }
+static inline int mg_level_vectors(int level) { return level == 0 ? MG_FINE_VECTORS : MG_COARSE_VECTORS; }
+static inline int64_t mg_level_bytes(int level, const int* ne) {
+  const int64_t n = mg_points(ne);
+  int64_t b = (int64_t)mg_level_vectors(level) * mg_padded(n) * 8;
+  if (level > 0) {
+    b += 3 * (n > 0 ? n : 1) * 8;
+    for (int d = 0; d < 3; ++d) b += (int64_t)(ne[d] + 1) * 16 + 8;
+  }
+  return b;
+}
+static inline int64_t mg_bytes(const MgPlan& P) {
+  int64_t b = MG_FLAG_BYTES;
+  for (int l = 0; l < P.nlev; ++l) b += mg_level_bytes(l, P.ne[l]);
+  return b;
+}
+
+// ---- products: 2 nu per cycle on every level but the coarsest, nu_c - 1 there; a pass of cg! with the cycle runs one A p per iteration, one cycle per
+// iteration (the first before iteration 1, none after the last) and the restart wrapper's true residual ------------------------------------------------
+static inline int mg_cycle_products(int level, int nlev, int nu, int nu_c) { return level == nlev - 1 ? nu_c - 1 : 2 * nu; }
+static inline int64_t mg_pass_products(int x0, int it, int nlev, int nu, int nu_c) {
+  return it >= 1 ? (int64_t)x0 + it + (int64_t)mg_cycle_products(0, nlev, nu, nu_c) * it + 1 : (int64_t)x0 + 1;
+}
+// vector streams the library's own kernels move per cycle on a level, the products' own traffic apart:
+//   below the coarsest: first step from a zero start 5 (b, 1/d -> d, z, r), every further step 6 (r, 1/d, d, z -> d, z), the restriction's read of r 1,
+//   the prolongation 3 (z -> z, d; the coarse iterate counts on its own level), the first step after it 5 (r, 1/d, z -> d, z):
+//   2 * (5 + 6 (nu - 1)) + 1 + 3 = 12 nu + 2 (26 at nu = 2)
+//   on the coarsest: 5 + 6 (nu_c - 1), or 4 when nu_c == 1 (no copy of b is needed); a level that is restricted to also takes the write of its b, and
+//   one that is prolongated from the read of its z
+static inline int mg_cycle_streams(int level, int nlev, int nu, int nu_c) {
+  int s = 0;
+  if (level == nlev - 1) s = nu_c == 1 ? 4 : 5 + 6 * (nu_c - 1);
+  else s = 12 * nu + 2;
+  if (level > 0) s += 2;
+  return s;
+}
+
+// ---- Chebyshev polynomial smoother in D^-1 A on [lo, hi]: step k adds d_k = c1_k d_(k-1) + c2_k D^-1 r to z ------------------------------------------
+struct MgCheb {
+  double theta, delta, sigma, rho;  // rho: of the step last taken
+};
+static inline MgCheb mg_cheb_start(double lo, double hi, double* c1, double* c2) {
+  MgCheb C;
+  C.theta = (hi + lo) / 2.0;
+  C.delta = (hi - lo) / 2.0;
+  C.sigma = C.theta / C.delta;
+  C.rho = 1.0 / C.sigma;
+  *c1 = 0.0;
+  *c2 = 1.0 / C.theta;
+  return C;
+}
+static inline void mg_cheb_next(MgCheb* C, double* c1, double* c2) {
+  const double rho = 1.0 / (2.0 * C->sigma - C->rho);
+  *c1 = rho * C->rho;
+  *c2 = 2.0 * rho / C->delta;
+  C->rho = rho;
+}
+
+// ---- which solves take MFEM_PRECOND_MULTIGRID: nullptr, or what is missing (MFEM_ERR_UNSUPPORTED, nothing launched, nothing written) ---------------
+static inline const char* mg_solve_refusal(bool brick_operator, bool thermal_hex8, int method, int left_precond, bool has_comm, bool nitsche_on) {
+  if (!brick_operator) return "the multigrid preconditioner needs a hex-8 thermal brick operator (mfem_brick_operator_create): this handle is not one";
+  if (!thermal_hex8) return "the multigrid preconditioner covers the hex-8 thermal brick operator: elasticity and hex-27 operators are not covered";
+  if (method != MFEM_SOLVER_CG) return "the multigrid preconditioner needs MFEM_SOLVER_CG: the cycle is a symmetric operator, the other methods are not offered it";
+  if (left_precond != MFEM_LEFT_NONE) return "the multigrid preconditioner takes no left preconditioner";
+  if (has_comm) return "the multigrid preconditioner runs on one rank: no communicator may be attached";
+  if (nitsche_on) return "the multigrid preconditioner needs a symmetric K: a Nitsche (fixed_faces) term is active";
+  return nullptr;
+}

@@ -78,7 +78,13 @@ struct mfem_brick_operator_s {
   int ng;                   // the brick's rule when the operator was created
   const double* seen_x0;    // the brick's first coordinate array at the last bind (a change starts a new epoch of the cycle-graph key)
   mfem_csr_s csr;           // pattern-less: what the Krylov loop holds in place of a matrix (n = fields x control points)
+  struct mfem_brick_multigrid_s* mg;  // the multigrid hierarchy attached to a hex-8 thermal operator (brick_multigrid.hip), or nullptr; destroyed with the operator
 };
+mfem_brick_operator_s* bop_from_handle(uint64_t handle);  // brick_operator.hip: nullptr unless the handle is a brick operator's
+// diag K of a hex-8 thermal operator WITH its sign (d_i <- K_ii where K_ii != 0; a zero diagonal keeps the caller's preset): what the multigrid setup
+// reads the sign of K from
+int bop_signed_diagonal(mfem_context_s* ctx, mfem_brick_operator_s* op, double* d);
+void mfem_mg_release(struct mfem_brick_multigrid_s* mg);  // brick_multigrid.hip: frees a hierarchy (its operator is being destroyed, or it is destroyed on its own)
 
 __device__ __forceinline__ double bop_scaled(const double* __restrict__ x, const double* __restrict__ dsc, int64_t i) {
   return dsc ? x[i] / dsc[i] : x[i];

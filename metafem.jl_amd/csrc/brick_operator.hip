@@ -60,7 +60,7 @@ int bop_tables(int device, int ng, const H8Tables** out) {
   return MFEM_OK;
 }
 
-static mfem_brick_operator_s* bop_from_handle(uint64_t handle) {
+mfem_brick_operator_s* bop_from_handle(uint64_t handle) {
   mfem_operator_head* h = (mfem_operator_head*)(uintptr_t)handle;
   return h && h->kind == MFEM_OPERATOR_BRICK ? (mfem_brick_operator_s*)h : nullptr;
 }
@@ -405,6 +405,7 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_brick_product_faces(BrickView B,
 // Diagonal: d_i <- |K_ii| where K_ii != 0 (else d_i keeps its preset).  A thread per control point: the (a, a) entry of each adjacent element's
 // Ke = sum_q w det (-k) |grad N_a|^2 (table form, hex8_geom), then the point's own face terms.  Nothing is stored.  Runs once per solve.
 // =================================================================================================
+template <bool SIGNED>  // (SIGNED: K_ii itself, for the multigrid setup, which reads the sign of K from it)
 __global__ __launch_bounds__(MFEM_BLOCK) void k_brick_diagonal(BrickView B, BopThermal P, double* __restrict__ d) {
   const int64_t node = (int64_t)blockIdx.x * MFEM_BLOCK + threadIdx.x;
   if (node >= B.n_owned) return;
@@ -431,7 +432,7 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_brick_diagonal(BrickView B, BopT
     }
   }
   if (i == 0 || i == B.ne0 || j == 0 || j == B.ne1 || k == 0 || k == B.ne2) sum += bop_face_row<true>(B, P, i, j, k, nullptr, nullptr);
-  if (sum != 0.0) d[node] = fabs(sum);
+  if (sum != 0.0) d[node] = SIGNED ? sum : fabs(sum);
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------------------------
@@ -524,7 +525,18 @@ static int bop_jacobi(mfem_context_s* ctx, mfem_brick_operator_s* op, double* d)
   if (op->physics == BOP_PHYSICS_HEX27) return bop27_jacobi(ctx, op, B, d);
   const int64_t grid = bop_diagonal_grid(B.n_owned);
   MFEM_REQUIRE(grid < ((int64_t)1 << 31), "too many control points for one launch");
-  hipLaunchKernelGGL(k_brick_diagonal, dim3((unsigned)grid), dim3(MFEM_BLOCK), 0, ctx->stream, B, bop_thermal(op), d);
+  hipLaunchKernelGGL(k_brick_diagonal<false>, dim3((unsigned)grid), dim3(MFEM_BLOCK), 0, ctx->stream, B, bop_thermal(op), d);
+  MFEM_CHECK_LAUNCH();
+  return MFEM_OK;
+}
+int bop_signed_diagonal(mfem_context_s* ctx, mfem_brick_operator_s* op, double* d) {
+  MFEM_REQUIRE(op->physics == BOP_PHYSICS_THERMAL, "the signed diagonal exists for the hex-8 thermal operator");
+  BrickView B;
+  const int rc = bop_view(op, &B);
+  if (rc) return rc;
+  const int64_t grid = bop_diagonal_grid(B.n_owned);
+  MFEM_REQUIRE(grid < ((int64_t)1 << 31), "too many control points for one launch");
+  hipLaunchKernelGGL(k_brick_diagonal<true>, dim3((unsigned)grid), dim3(MFEM_BLOCK), 0, ctx->stream, B, bop_thermal(op), d);
   MFEM_CHECK_LAUNCH();
   return MFEM_OK;
 }
@@ -581,6 +593,7 @@ static int bop_create(mfem_context ctx, mfem_brick m, int physics, const void* p
   op->tables27 = tables27;
   op->ng = m->ng;
   op->seen_x0 = nullptr;
+  op->mg = nullptr;
   op->ctx = ctx;
   op->brick = m;
   op->physics = physics;
@@ -641,6 +654,7 @@ extern "C" int mfem_brick_operator_destroy(uint64_t handle) try {
     (void)hipStreamSynchronize(op->ctx->stream);
     mfem_graphs_invalidate(op->ctx);  // (a cached cycle holds the brick's arrays and the parameters)
   }
+  if (op->mg) mfem_mg_release(op->mg);  // (one hierarchy per operator, destroyed with it)
   op->head.kind = 0;
   delete op;
   return MFEM_OK;

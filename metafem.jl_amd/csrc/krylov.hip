@@ -17,6 +17,7 @@
 #include "solve_decide.h"
 #include "operator.h"
 #include "mesh_operator_decide.h"
+#include "brick_multigrid.h"
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
 
@@ -261,6 +262,8 @@ static const KrylovMethod k_methods[] = {
 };
 // cg! with one reduction group per iteration: r, p, s, u, w
 static const KrylovMethod k_cg_single = {"cg!", 2, MFEM_MAX_S, [](int) { return 5; }, false, mfem_cg_single_pass};
+// cg! with the multigrid V-cycle (MFEM_PRECOND_MULTIGRID, one rank, a hex-8 thermal brick operator): r, p, Ap, z
+static const KrylovMethod k_cg_mg = {"cg!", 2, MFEM_MAX_S, [](int) { return 4; }, true, mfem_cg_mg_pass};
 static_assert(sizeof(k_methods) / sizeof(k_methods[0]) == MFEM_SOLVER_LSQR + 1, "one row per mfem_solver_kind");
 
 // The work vectors of this solve and how many of them (with the four in front) start cleared.  mfem_cg_pass keeps a ring of m search directions
@@ -293,6 +296,7 @@ struct SolveRun {
   int64_t n_global;  // rows of the whole system
   double n_inv;      // 1 / n_global
   bool is_cg, jac, left, is_lsqr;
+  bool mg = false;  // MFEM_PRECOND_MULTIGRID (mfem_solve_operator on a hex-8 thermal brick operator: the gate has passed)
   bool allow_lat;  // false: the symmetric lattice tiles have refused this solve's values (they are not tried again in this call)
   // per attempt
   SolveNext next;
@@ -321,7 +325,7 @@ static int choose_method(SolveRun& R) {
   MFEM_REQUIRE(A->n == 0 || ((vals || R.op) && b && x_out), "null array");
   MFEM_REQUIRE(o->maxiter >= 0 && o->max_pass >= 1, "maxiter >= 0 and max_pass >= 1 required");
   MFEM_REQUIRE(o->method >= MFEM_SOLVER_CG && o->method <= MFEM_SOLVER_LSQR, "unknown method");
-  MFEM_REQUIRE(o->precond >= MFEM_PRECOND_NONE && o->precond <= MFEM_PRECOND_JACOBI_RIGHT_COLNORM, "unknown precond");
+  MFEM_REQUIRE((o->precond >= MFEM_PRECOND_NONE && o->precond <= MFEM_PRECOND_JACOBI_RIGHT_COLNORM) || R.mg, "unknown precond");
   MFEM_REQUIRE(o->left_precond >= MFEM_LEFT_NONE && o->left_precond <= MFEM_LEFT_JACOBI_ROWNORM, "unknown left_precond");
   MFEM_REQUIRE(!(o->left_precond && o->method == MFEM_SOLVER_CG), "left Jacobi would break the symmetry CG needs");
   if (R.stats) memset(R.stats, 0, sizeof(*R.stats));
@@ -349,13 +353,14 @@ static int choose_method(SolveRun& R) {
   if (o->method == MFEM_SOLVER_CG &&
       (o->cg_variant == 2 || (o->cg_variant == 0 && world_ranks > 1 && R.n_global / world_ranks < g_cg_single_max_rows)))
     method = &k_cg_single;
+  if (R.mg) method = &k_cg_mg;
   R.n_inv = 1.0 / (double)R.n_global;
   MFEM_REQUIRE(s_param <= method->max_s, "l_or_s too large");
   R.method = method;
   R.s_param = s_param;
   R.is_lsqr = o->method == MFEM_SOLVER_LSQR;
   R.is_cg = o->method == MFEM_SOLVER_CG;
-  R.jac = o->precond != MFEM_PRECOND_NONE;
+  R.jac = o->precond != MFEM_PRECOND_NONE && !R.mg;  // (the cycle is applied by the pass itself: no diagonal scaling)
   R.left = o->left_precond != MFEM_LEFT_NONE;
   return MFEM_OK;
 }
@@ -922,6 +927,10 @@ static int solve_with_graphs(mfem_context_s* ctx, int64_t n, Inner inner) {
 extern "C" int mfem_solve(mfem_context ctx, mfem_csr A, double* vals, const double* b, double* x_out,
                           const mfem_solve_options* o, mfem_solve_stats* stats) try {
   MFEM_REQUIRE(ctx && A && o, "null argument");
+  if (o->precond == MFEM_PRECOND_MULTIGRID) {  // (nothing is launched, nothing is written)
+    mfem_set_error("mfem_solve: the multigrid preconditioner needs a hex-8 thermal brick operator (mfem_brick_operator_create) and mfem_solve_operator: an assembled matrix has no lattice to coarsen");
+    return MFEM_ERR_UNSUPPORTED;
+  }
   return solve_with_graphs(ctx, A->n, [&]() { return solve_inner(ctx, A, vals, b, x_out, o, stats); });
 } MFEM_API_CATCH("mfem_solve")
 
@@ -979,6 +988,10 @@ static int operator_attempt(SolveRun& R) {
       V.dinv = R.dinv_buf;
     }
   }
+  if (R.mg) {  // Pr_Multigrid: the setup of the attached hierarchy, always, where the Jacobi diagonal is computed -- inside solve_ms
+    rc = mfem_mg_setup_attached(ctx, R.op);
+    if (rc) return rc;
+  }
   rc = R.opi->bind(R.op, scratch, R.fused_scale ? V.d : nullptr);
   if (rc) return rc;
   struct Unbind { SolveRun& R; ~Unbind() { R.opi->unbind(R.op); } } unbind{R};
@@ -996,21 +1009,34 @@ extern "C" int mfem_solve_operator(mfem_context ctx, uint64_t handle, const doub
   MFEM_REQUIRE(!A->op, "the operator is bound to a running solve");
   MFEM_REQUIRE(A->n == 0 || (b && x_out), "null array");
   MFEM_REQUIRE(o->method >= MFEM_SOLVER_CG && o->method <= MFEM_SOLVER_LSQR, "unknown method");
-  MFEM_REQUIRE(o->precond >= MFEM_PRECOND_NONE && o->precond <= MFEM_PRECOND_JACOBI_RIGHT_COLNORM, "unknown precond");
+  MFEM_REQUIRE(o->precond >= MFEM_PRECOND_NONE && o->precond <= MFEM_PRECOND_MULTIGRID, "unknown precond");
   MFEM_REQUIRE(o->left_precond >= MFEM_LEFT_NONE && o->left_precond <= MFEM_LEFT_JACOBI_ROWNORM, "unknown left_precond");
+  const bool mg = o->precond == MFEM_PRECOND_MULTIGRID;
+  if (mg) {  // the new value is gated in front of mop_solve_gate: what is missing is named, nothing is launched, nothing is written
+    const int rcg = mfem_mg_solve_check(ctx, op, o);
+    if (rcg) return rcg;
+  }
   const char* why = "";
   const int gate = mop_solve_gate(o->method, o->precond, o->left_precond, o->scale_in_place, ctx->comm != nullptr, &why);
   if (gate) {
     mfem_set_error("mfem_solve_operator: %s", why);
     return gate;
   }
-  return solve_with_graphs(ctx, A->n, [&]() -> int {
+  auto run = [&]() -> int {
     SolveRun R{ctx, A, nullptr, b, x_out, o, stats};
     R.op = op;
     R.opi = opi;
+    R.mg = mg;
     const int rc = choose_method(R);
     if (rc || A->n == 0) return rc;
     R.allow_lat = false;
     return operator_attempt(R);
-  });
+  };
+  if (mg) {  // a default hierarchy when none is attached: allocated here, before the workspace is taken; the pass captures no cycle graph
+    MFEM_REQUIRE(o->maxiter >= 0 && o->max_pass >= 1, "maxiter >= 0 and max_pass >= 1 required");
+    const int rca = mfem_mg_attach_default(ctx, op);
+    if (rca) return rca;
+    return run();
+  }
+  return solve_with_graphs(ctx, A->n, run);
 } MFEM_API_CATCH("mfem_solve_operator")
