@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MFEM_ABI_VERSION 10
+#define MFEM_ABI_VERSION 11
 
 typedef enum {
   MFEM_OK = 0,
@@ -195,8 +195,9 @@ typedef enum {
   MFEM_PRECOND_NONE = 0,            /* Identity, 02_Preconditioner.jl:78-86 */
   MFEM_PRECOND_JACOBI_RIGHT_DIAG = 1,   /* Pr_Jacobi!(normalized_by_column=false), :103-120 */
   MFEM_PRECOND_JACOBI_RIGHT_COLNORM = 2,/* Pr_Jacobi!(normalized_by_column=true) */
-  MFEM_PRECOND_MULTIGRID = 3        /* added (ABI 10): a geometric multigrid V-cycle, cg! on a hex-8 thermal brick operator only (mfem_solve_operator;
-                                       see mfem_brick_multigrid_create) */
+  MFEM_PRECOND_MULTIGRID = 3        /* added (ABI 10): a geometric multigrid V-cycle, cg! on a hex-8 thermal brick operator (mfem_solve_operator; see
+                                       mfem_brick_multigrid_create) or, ABI 11, on a hex-8 elasticity brick operator with a hierarchy of
+                                       mfem_brick_multigrid_create_elasticity attached */
 } mfem_precond_kind;
 
 typedef enum {
@@ -830,6 +831,16 @@ typedef struct {
  * MFEM_ERR_UNSUPPORTED, nothing created: not a hex-8 thermal brick operator, a Nitsche term active.  MFEM_ERR_INVALID: null arguments, another
  * context's operator, an operator that already has a hierarchy, options out of range. */
 int mfem_brick_multigrid_create(mfem_context ctx, uint64_t op, const mfem_multigrid_options* opts, uint64_t* mg /* [host] out */);
+/* Added (ABI 11).  The same hierarchy for an operator of mfem_brick_operator_create_elasticity: three field-major fields per lattice point.  The
+ * contract is mfem_brick_multigrid_create's (attached, one per operator, destroyed with it); the handle goes to the same _setup, _apply (r and z hold
+ * 3 entries per control point, field-major), _info and _destroy.  A level vector holds 3 x points entries; P = I_3 (x) the trilinear interpolation,
+ * one launch per transfer; a coarse operator is mfem_brick_operator_create_elasticity on the coarse brick with the caller's current parameters; the
+ * smoother's D is the scalar diagonal of K (no 3 x 3 point blocks).  The elasticity K is negative definite with a penalty face: sign = -1.
+ * MFEM_ERR_UNSUPPORTED with a message, nothing created, launched or written: a thermal or hex-27 operator (they keep mfem_brick_multigrid_create),
+ * a mesh operator; and here as at every setup: tau == 0 or penalty_faces == 0 (K keeps the rigid-body modes: the coarsest level's Chebyshev interval
+ * does not cover a singular operator), a diagonal of mixed sign or with a zero, a non-positive estimate.  MFEM_ERR_INVALID as for
+ * mfem_brick_multigrid_create. */
+int mfem_brick_multigrid_create_elasticity(mfem_context ctx, uint64_t op, const mfem_multigrid_options* opts, uint64_t* mg /* [host] out */);
 /* Re-sends the fine operator's CURRENT parameters to every level, injects the coordinates, computes the diagonals, the sign and the estimates.
  * Synchronises the context stream.  MFEM_ERR_UNSUPPORTED: a Nitsche term active, a diagonal of mixed sign or with a zero. */
 int mfem_brick_multigrid_setup(mfem_context ctx, uint64_t mg);
@@ -837,10 +848,12 @@ int mfem_brick_multigrid_setup(mfem_context ctx, uint64_t mg);
 int mfem_brick_multigrid_apply(mfem_context ctx, uint64_t mg, const double* r, double* z);
 int mfem_brick_multigrid_info(uint64_t mg, mfem_multigrid_info* info /* [host] out */);
 int mfem_brick_multigrid_destroy(uint64_t mg);
-/* mfem_solve_operator with precond = MFEM_PRECOND_MULTIGRID: only for a hex-8 thermal brick operator, MFEM_SOLVER_CG, no left preconditioner, no
+/* mfem_solve_operator with precond = MFEM_PRECOND_MULTIGRID: only for a hex-8 thermal brick operator, or (ABI 11) a hex-8 elasticity brick operator
+ * with a hierarchy of mfem_brick_multigrid_create_elasticity ATTACHED (that hierarchy is the opt-in: without one the solve is refused and the message
+ * names the entry point; tau == 0 or penalty_faces == 0 is refused too), MFEM_SOLVER_CG, no left preconditioner, no
  * communicator, no active Nitsche term -- every other combination, every other operator kind and mfem_solve answer MFEM_ERR_UNSUPPORTED with a reason
- * naming what is missing; nothing is launched, nothing is written.  A solve creates a default hierarchy when none is attached and ALWAYS runs the
- * setup first, inside solve_ms (where a Jacobi solve computes its diagonal): parameters re-sent and coordinates overwritten since the last solve can
+ * naming what is missing; nothing is launched, nothing is written.  On a thermal operator a solve creates a default hierarchy when none is attached;
+ * every solve ALWAYS runs the setup first, inside solve_ms (where a Jacobi solve computes its diagonal): parameters re-sent and coordinates overwritten since the last solve can
  * never leave a stale level.  Nothing is allocated once the iteration has started.  cg_variant and check_every are ignored (the classic recurrence;
  * the flag is read after every iteration). */
 

@@ -21,7 +21,7 @@ import LinearAlgebra
 
 # ---- library handle and error convention ---------------------------------------------------------------------------------
 const lib = get(ENV, "METAFEM_MI355X_LIB", joinpath(@__DIR__, "..", "metafem.jl_amd", "libmetafem_mi355x.so"))
-const ABI_VERSION = 10   # == MFEM_ABI_VERSION
+const ABI_VERSION = 11   # == MFEM_ABI_VERSION
 
 struct MFEMError <: Exception
     rc::Cint
@@ -58,7 +58,7 @@ ctx() = (isassigned(CTX) || (CTX[] = Context(0)); CTX[].h)
 # ---- struct mirrors of include/metafem_mi355x.h (isbits, C layout) ---------------------------------------------------------
 Base.@kwdef struct SolveOptions           # == mfem_solve_options
     method::Int32 = 2                     # 0 cg (new), 1 bicgstabl_GS!, 2 idrs!, 3 cgs2!, 4 gmres!, 5 cgs!, 6 tfqmr!, 7 lsqr!
-    precond::Int32 = 1                    # 0 Identity, 1 Pr_Jacobi!, 2 Pr_Jacobi!(normalized_by_column = true), 3 Pr_Multigrid! (cg! on a hex-8 thermal BrickOperator)
+    precond::Int32 = 1                    # 0 Identity, 1 Pr_Jacobi!, 2 Pr_Jacobi!(normalized_by_column = true), 3 Pr_Multigrid! (cg! on a hex-8 thermal BrickOperator, or an elasticity one with brick_multigrid_elasticity attached)
     l_or_s::Int32 = 0                     # the `s` kwarg (tfqmr!: checkiter)
     maxiter::Int32 = 2000
     max_pass::Int32 = 4
@@ -791,6 +791,16 @@ end
 function brick_multigrid(op::BrickOperator, opts::MultigridOptions = MultigridOptions())
     h = Ref{UInt64}(0)
     rc = ccall((:mfem_brick_multigrid_create, lib), Cint, (Ptr{Cvoid}, UInt64, Ref{MultigridOptions}, Ref{UInt64}), ctx(), op.h, Ref(opts), h)
+    rc == -3 && return nothing
+    check(rc)
+    return BrickMultigrid(h[], op)
+end
+"The hierarchy of a hex-8 elasticity brick operator (ABI 11): three field-major fields per lattice point; r and z of multigrid_apply! hold 3 entries
+per control point.  Attaching it is what admits Pr_Multigrid! on the operator (no default hierarchy is made for elasticity).  `nothing`: refused
+(a thermal, hex-27 or mesh operator; tau == 0 or no penalty face)."
+function brick_multigrid_elasticity(op::BrickOperator, opts::MultigridOptions = MultigridOptions())
+    h = Ref{UInt64}(0)
+    rc = ccall((:mfem_brick_multigrid_create_elasticity, lib), Cint, (Ptr{Cvoid}, UInt64, Ref{MultigridOptions}, Ref{UInt64}), ctx(), op.h, Ref(opts), h)
     rc == -3 && return nothing
     check(rc)
     return BrickMultigrid(h[], op)

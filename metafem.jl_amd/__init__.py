@@ -37,7 +37,8 @@ __all__ = ["Context", "FEM_SpMat_CSR", "MeshOperator", "BrickOperator", "BrickMu
 # solver / preconditioner selectors (the reference passes Julia functions: Sv_func! = idrs! ...)
 cg_, bicgstabl_GS_, idrs_, cgs2_, gmres_, cgs_, tfqmr_, lsqr_ = 0, 1, 2, 3, 4, 5, 6, 7
 Identity, Pr_Jacobi_, Pr_Jacobi_colnorm_ = 0, 1, 2
-Pr_Multigrid_ = 3  # a geometric multigrid V-cycle: cg_ on a hex-8 thermal BrickOperator only (BrickOperator.multigrid)
+Pr_Multigrid_ = 3  # a geometric multigrid V-cycle: cg_ on a hex-8 thermal BrickOperator (BrickOperator.multigrid), or on an ElasticityBrickOperator
+# to which ElasticityBrickOperator.multigrid() has attached a hierarchy (no default one is made for elasticity)
 Pl_Jacobi_, Pl_Jacobi_rownorm_ = 1, 2  # Pl_func selectors (02_Preconditioner.jl:155-168)
 
 # reference local face ids (ref_geometry/002_Initialization.jl:8): 1 z=0, 2 y=0, 3 x=L, 4 y=L, 5 x=0, 6 z=L
@@ -303,7 +304,8 @@ class BrickOperator:
     def multigrid(self, **opts) -> "BrickMultigrid":
         """The geometric multigrid hierarchy of this operator (mfem_brick_multigrid_create): one per operator, destroyed with it.  opts:
         smoother_degree, coarse_degree, smoothing_range, coarse_range, eig_steps, max_levels (0 or absent: the default).  Raises MultigridRefused for
-        an operator the hierarchy does not cover (elasticity, hex-27, an active Nitsche term)."""
+        an operator the hierarchy does not cover (hex-27, an active Nitsche term; an ElasticityBrickOperator builds its own three-field hierarchy and
+        refuses tau == 0 or no penalty face)."""
         return BrickMultigrid(self, **opts)
 
     def close(self):
@@ -336,9 +338,11 @@ def multigrid_plan(n, max_levels: int = 12):
 
 
 class BrickMultigrid:
-    """Geometric multigrid V-cycle of a hex-8 thermal BrickOperator (mfem_brick_multigrid_*, csrc/brick_multigrid.hip): the preconditioner
-    `iterative_Solve(op, None, b, tol, Sv_func=cg_, Pr_func=Pr_Multigrid_)` applies.  A solve runs setup() itself, always; setup() and apply() are
-    for a caller that uses the cycle on its own."""
+    """Geometric multigrid V-cycle of a hex-8 thermal BrickOperator or of an ElasticityBrickOperator (mfem_brick_multigrid_*,
+    csrc/brick_multigrid.hip): the preconditioner `iterative_Solve(op, None, b, tol, Sv_func=cg_, Pr_func=Pr_Multigrid_)` applies.  The operator
+    says which entry point creates it (ElasticityBrickOperator: mfem_brick_multigrid_create_elasticity, three field-major fields per lattice
+    point: apply() takes op.n = 3 * ncp entries).  A solve runs setup() itself, always; setup() and apply() are for a caller that uses the cycle
+    on its own."""
 
     def __init__(self, op: "BrickOperator", **opts):
         unknown = set(opts) - {"smoother_degree", "coarse_degree", "smoothing_range", "coarse_range", "eig_steps", "max_levels"}
@@ -348,7 +352,8 @@ class BrickMultigrid:
         self._h = C.c_uint64()
         o = _lib.MultigridOptions(int(opts.get("smoother_degree", 0)), int(opts.get("coarse_degree", 0)), float(opts.get("smoothing_range", 0.0)),
                                   float(opts.get("coarse_range", 0.0)), int(opts.get("eig_steps", 0)), int(opts.get("max_levels", 0)))
-        rc = lib.mfem_brick_multigrid_create(self.ctx._h, op._h, C.byref(o), C.byref(self._h))
+        create = getattr(lib, getattr(op, "_multigrid_create", "mfem_brick_multigrid_create"))
+        rc = create(self.ctx._h, op._h, C.byref(o), C.byref(self._h))
         if rc == -3:
             raise MultigridRefused(lib.mfem_last_error().decode())
         check(rc)
@@ -397,12 +402,17 @@ class ElasticityBrickOperator(BrickOperator):
     """Matrix-free K of a hex-8 brick under three-field linear elasticity (mfem_brick_operator_create_elasticity, csrc/brick_operator_elasticity.hip):
     the matrix of Brick.assemble_elasticity for the same parameters -- the volume term and the penalty faces; traction faces and sig are the
     residual's load and do not enter K.  n = 3 * ncp, field-major.  Made by Brick.elasticity_operator; mul_, diagonal and iterative_Solve take it
-    as they take a BrickOperator."""
+    as they take a BrickOperator.  multigrid(**opts) attaches a three-field hierarchy (mfem_brick_multigrid_create_elasticity): with one attached,
+    and only then, iterative_Solve takes Pr_func = Pr_Multigrid_ with cg_; it raises MultigridRefused for tau == 0 or no penalty face (K is
+    singular)."""
+
+    _multigrid_create = "mfem_brick_multigrid_create_elasticity"  # (BrickMultigrid asks the operator which entry point builds its hierarchy)
 
     def __init__(self, brick: "Brick", params: "ElasticityParams"):
         self.ctx, self.brick = brick.ctx, brick  # (the library borrows the brick: kept alive here)
         self.n = 3 * brick.ncp
         self.nnz = 0
+        self._mg = None
         self._h = C.c_uint64()
         rc = lib.mfem_brick_operator_create_elasticity(self.ctx._h, brick._h, C.byref(params), C.byref(self._h))
         if rc == -3:  # MFEM_ERR_UNSUPPORTED: a brick the operator does not cover
@@ -547,6 +557,8 @@ def iterative_Solve(A, K_vals: Optional[torch.Tensor], residue: torch.Tensor, co
     Identity, no scale_in_place.  Pr_func = Pr_Multigrid_: a geometric multigrid V-cycle, for Sv_func = cg_ on a hex-8 thermal BrickOperator
     without an active Nitsche term and without a communicator (anything else raises with the library's reason); the solve creates a default hierarchy
     when BrickOperator.multigrid has not made one and always runs its setup first (inside solve_ms); check_every and cg_variant are ignored.
+    An ElasticityBrickOperator takes it under the same conditions once ElasticityBrickOperator.multigrid() has attached a hierarchy (that call is
+    the opt-in: without it the solve raises and the message names the entry point) and while tau != 0 on at least one penalty face.
 
     Returns (delta_x, stats); delta_x is a NEW device vector like the reference's return value.
     """
@@ -794,7 +806,7 @@ class ElasticityDomain:
     generated closures are the fused HIP kernels; update_OneStep is the reference's Newton driver, as in ThermalDomain."""
 
     def __init__(self, brick: Brick, lam: float, mu: float, tau: float, penalty_faces: int, traction_faces: int = 0, sig=(0.0,) * 6, *,
-                 matrix_free: bool = False):
+                 matrix_free: bool = False, multigrid: bool = False):
         self.brick, self.lam, self.mu, self.tau, self.penalty_faces = brick, lam, mu, tau, penalty_faces
         self.traction_faces, self.sig = traction_faces, tuple(sig)
         dev = f"cuda:{brick.ctx.device}"
@@ -821,6 +833,22 @@ class ElasticityDomain:
         self.converge_tol = 1e-6
         self.linear_solver: Callable = lambda gf: iterative_Solve(gf.A, gf.K_total, gf.residue, gf.converge_tol,
                                                                    Sv_func=idrs_, maxiter=2000, max_pass=10, s=8)[0]
+        # multigrid = True (with matrix_free, tau != 0 on a penalty face): a hierarchy is attached to the operator and linear_solver is cg_ with the
+        # V-cycle as its preconditioner.  On a domain that fell back to the assembled path, or without a penalty face (K is singular), the default
+        # solver stays and multigrid_reason says why (ThermalDomain's rule).
+        self.multigrid, self.multigrid_reason = False, None
+        if multigrid:
+            if not self.matrix_free:
+                self.multigrid_reason = "the domain holds an assembled matrix (" + (self.matrix_free_reason or "matrix_free was not asked for") + \
+                                        "): the multigrid preconditioner needs the matrix-free hex-8 operator"
+            elif tau == 0.0 or (penalty_faces & ALL_FACES) == 0:
+                self.multigrid_reason = "no penalty face (tau == 0 or penalty_faces == 0): K keeps the rigid-body modes, the multigrid " \
+                                        "preconditioner needs a definite K"
+            else:
+                self.multigrid = True
+                self.mg = self.A.multigrid()  # (the solves run its setup: K_linear_func's parameters can never leave a stale level)
+                self.linear_solver = lambda gf: iterative_Solve(gf.A, None, gf.residue, gf.converge_tol, Sv_func=cg_, Pr_func=Pr_Multigrid_,
+                                                                maxiter=400, max_pass=4)[0]
         self.history = []
 
     def K_linear_func(self):

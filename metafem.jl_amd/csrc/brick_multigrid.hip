@@ -1,4 +1,4 @@
-// Geometric multigrid V-cycle on hex-8 thermal bricks: the preconditioner behind MFEM_PRECOND_MULTIGRID (cg! on the matrix-free brick operator;
+// Geometric multigrid V-cycle on hex-8 thermal and elasticity bricks: the preconditioner behind MFEM_PRECOND_MULTIGRID (cg! on the matrix-free brick operator;
 // the pass: krylov_cg_mg.hip).  The hierarchy of an (nx, ny, nz) brick is the bricks (nx/2, ny/2, nz/2), ...: library-owned mfem_bricks whose
 // coordinates are injected from the next finer level at every setup, with a brick operator each (rediscretisation: the caller's parameters on the
 // coarse brick).  Everything is made of that operator's product and diagonal and of the kernels below; no matrix, no pattern, no atomic.
@@ -12,6 +12,9 @@
 // recurrence (r -= A d through the operator's own launch with alpha = -s, beta = 1) and never recomputed.  All sums have a fixed order: a cycle, a
 // setup and a solve give the same bits on every run.
 // Vector streams per cycle beside the products: mg_cycle_streams (12 nu + 2 on a level below the coarsest).
+// An elasticity hierarchy (mfem_brick_multigrid_create_elasticity) carries three field-major fields per lattice point: a level vector holds
+// fields x points entries, the transfers are the <NF = 3> instantiations (one launch, a thread per lattice point looping over the fields: P is
+// I_3 (x) the scalar P), the coarse operators are mfem_brick_operator_create_elasticity's, and everything elementwise runs on n = fields x points.
 #include <memory>
 #include "brick_operator.h"
 #include "brick_multigrid.h"
@@ -27,7 +30,9 @@ static_assert(MG_TILE_THREADS == MFEM_BLOCK, "a transfer tile is one workgroup")
 
 struct MgLevel {
   int ne[3], m[3];
-  int64_t n, npad;
+  int fields;            // 1 (thermal) or 3 (elasticity), field-major: field f of a level vector starts at f * points
+  int64_t points;        // lattice points
+  int64_t n, npad;       // fields * points; mg_padded(n): the vector is padded, not each field
   mfem_brick_s* brick;        // level 0: the caller's (borrowed); coarse levels: owned
   mfem_brick_operator_s* op;  // likewise
   double* slab;               // the level's vectors, one allocation
@@ -56,6 +61,11 @@ static int mg_refuse(const char* why) {
   mfem_set_error("multigrid on the hex-8 thermal brick operator: %s", why);
   return MFEM_ERR_UNSUPPORTED;
 }
+static int mg_refuse_elasticity(const char* why) {
+  mfem_set_error("multigrid on the hex-8 elasticity brick operator: %s", why);
+  return MFEM_ERR_UNSUPPORTED;
+}
+static bool mg_is_elasticity(const mfem_brick_operator_s* op) { return op->physics == BOP_PHYSICS_ELASTICITY; }
 
 // ---- kernels -------------------------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool mg_point(int m1, int m2, int& i, int& j, int& k) {
@@ -77,11 +87,16 @@ __global__ __launch_bounds__(MG_TILE_THREADS) void k_mg_inject(int mc1, int mc2,
   C2[c] = F2[f];
 }
 
-__global__ __launch_bounds__(MG_TILE_THREADS) void k_mg_restrict(int mc1, int mc2, int mf0, int mf1, int mf2, const double* __restrict__ rf,
-                                                                   double* __restrict__ bc) {
+// NF fields, field-major: field f of rf starts at f * pf (fine points), of bc at f * pc (coarse points).  The neighbour's index and weight are
+// computed once and serve every field; within a field the sum runs in the order of the one-field kernel (<1> is that kernel).
+template <int NF>
+__global__ __launch_bounds__(MG_TILE_THREADS) void k_mg_restrict(int mc1, int mc2, int mf0, int mf1, int mf2, int64_t pf, int64_t pc,
+                                                                   const double* __restrict__ rf, double* __restrict__ bc) {
   int I, J, K;
   if (!mg_point(mc1, mc2, I, J, K)) return;
-  double acc = 0.0;
+  double acc[NF];
+#pragma unroll
+  for (int f = 0; f < NF; ++f) acc[f] = 0.0;
 #pragma unroll
   for (int di = -1; di <= 1; ++di) {
     const int fi = 2 * I + di;
@@ -96,30 +111,45 @@ __global__ __launch_bounds__(MG_TILE_THREADS) void k_mg_restrict(int mc1, int mc
       for (int dk = -1; dk <= 1; ++dk) {
         const int fk = 2 * K + dk;
         if (fk < 0 || fk >= mf2) continue;
-        acc += (dk ? 0.5 * wij : wij) * rf[((int64_t)fi * mf1 + fj) * mf2 + fk];
+        const double w = dk ? 0.5 * wij : wij;
+        const int64_t src = ((int64_t)fi * mf1 + fj) * mf2 + fk;
+#pragma unroll
+        for (int f = 0; f < NF; ++f) acc[f] += w * rf[f * pf + src];
       }
     }
   }
-  bc[((int64_t)I * mc1 + J) * mc2 + K] = acc;
+  const int64_t dst = ((int64_t)I * mc1 + J) * mc2 + K;
+#pragma unroll
+  for (int f = 0; f < NF; ++f) bc[f * pc + dst] = acc[f];
 }
 
-// z may be null (the transfer alone)
-__global__ __launch_bounds__(MG_TILE_THREADS) void k_mg_prolong(int mf1, int mf2, int mc1, int mc2, const double* __restrict__ ec, double* __restrict__ z,
-                                                                  double* __restrict__ d) {
+// z may be null (the transfer alone).  NF fields as in k_mg_restrict: the parents and the weight once, the correction fused for every field.
+template <int NF>
+__global__ __launch_bounds__(MG_TILE_THREADS) void k_mg_prolong(int mf1, int mf2, int mc1, int mc2, int64_t pf, int64_t pc, const double* __restrict__ ec,
+                                                                  double* __restrict__ z, double* __restrict__ d) {
   int i, j, k;
   if (!mg_point(mf1, mf2, i, j, k)) return;
   // an even index has the one parent i / 2 (weight 1), an odd one the parents (i - 1) / 2 and (i + 1) / 2 (1/2 each; the upper one exists: an odd
   // index is never the last of a lattice of 2 mc - 1 points)
   const int ni = 1 + (i & 1), nj = 1 + (j & 1), nk = 1 + (k & 1);
   const double w = ((i & 1) ? 0.5 : 1.0) * ((j & 1) ? 0.5 : 1.0) * ((k & 1) ? 0.5 : 1.0);
-  double acc = 0.0;
+  double acc[NF];
+#pragma unroll
+  for (int f = 0; f < NF; ++f) acc[f] = 0.0;
   for (int a = 0; a < ni; ++a)
     for (int b = 0; b < nj; ++b)
-      for (int c = 0; c < nk; ++c) acc += ec[((int64_t)((i >> 1) + a) * mc1 + (j >> 1) + b) * mc2 + (k >> 1) + c];
-  acc *= w;
-  const int64_t f = ((int64_t)i * mf1 + j) * mf2 + k;
-  if (z) z[f] += acc;
-  d[f] = acc;
+      for (int c = 0; c < nk; ++c) {
+        const int64_t src = ((int64_t)((i >> 1) + a) * mc1 + (j >> 1) + b) * mc2 + (k >> 1) + c;
+#pragma unroll
+        for (int f = 0; f < NF; ++f) acc[f] += ec[f * pc + src];
+      }
+  const int64_t dst = ((int64_t)i * mf1 + j) * mf2 + k;
+#pragma unroll
+  for (int f = 0; f < NF; ++f) {
+    const double e = acc[f] * w;
+    if (z) z[f * pf + dst] += e;
+    d[f * pf + dst] = e;
+  }
 }
 
 // d (holding the signed diagonal, preset 0) -> dinv = 1 / |d|; flags: every thread that sees a positive / negative / zero entry stores 1 to its flag
@@ -254,14 +284,17 @@ static int mg_cheb(mfem_brick_multigrid_s* mg, int l, const double* b, double* z
 static int mg_restrict(mfem_context_s* ctx, const MgLevel& F, const MgLevel& Cc, const double* rf, double* bc) {
   const MgGrid g = mg_transfer_grid(Cc.m[0], Cc.m[1], Cc.m[2]);
   MFEM_REQUIRE(mg_grid_ok(g), "a lattice too large for the transfer kernels' grid");
-  hipLaunchKernelGGL(k_mg_restrict, dim3(g.gx, g.gy, g.gz), dim3(MG_TILE_THREADS), 0, ctx->stream, Cc.m[1], Cc.m[2], F.m[0], F.m[1], F.m[2], rf, bc);
+  const auto kernel = F.fields == MG_ELASTICITY_FIELDS ? k_mg_restrict<MG_ELASTICITY_FIELDS> : k_mg_restrict<1>;
+  hipLaunchKernelGGL(kernel, dim3(g.gx, g.gy, g.gz), dim3(MG_TILE_THREADS), 0, ctx->stream, Cc.m[1], Cc.m[2], F.m[0], F.m[1], F.m[2], F.points, Cc.points, rf,
+                     bc);
   MFEM_CHECK_LAUNCH();
   return MFEM_OK;
 }
 static int mg_prolong(mfem_context_s* ctx, const MgLevel& F, const MgLevel& Cc, const double* ec, double* z, double* d) {
   const MgGrid g = mg_transfer_grid(F.m[0], F.m[1], F.m[2]);
   MFEM_REQUIRE(mg_grid_ok(g), "a lattice too large for the transfer kernels' grid");
-  hipLaunchKernelGGL(k_mg_prolong, dim3(g.gx, g.gy, g.gz), dim3(MG_TILE_THREADS), 0, ctx->stream, F.m[1], F.m[2], Cc.m[1], Cc.m[2], ec, z, d);
+  const auto kernel = F.fields == MG_ELASTICITY_FIELDS ? k_mg_prolong<MG_ELASTICITY_FIELDS> : k_mg_prolong<1>;
+  hipLaunchKernelGGL(kernel, dim3(g.gx, g.gy, g.gz), dim3(MG_TILE_THREADS), 0, ctx->stream, F.m[1], F.m[2], Cc.m[1], Cc.m[2], F.points, Cc.points, ec, z, d);
   MFEM_CHECK_LAUNCH();
   return MFEM_OK;
 }
@@ -319,6 +352,7 @@ void mfem_mg_release(mfem_brick_multigrid_s* mg) {
 static int mg_create(mfem_context_s* ctx, mfem_brick_operator_s* op, const MgOptions& opt, mfem_brick_multigrid_s** out) {
   const mfem_brick_s* fb = op->brick;
   const MgPlan P = mg_plan(fb->ne[0], fb->ne[1], fb->ne[2], opt.max_levels);
+  const int fields = mg_is_elasticity(op) ? MG_ELASTICITY_FIELDS : 1;
   mfem_host_alloc_probe();
   mfem_brick_multigrid_s* mg = new mfem_brick_multigrid_s();
   memset(mg, 0, sizeof(*mg));
@@ -334,7 +368,9 @@ static int mg_create(mfem_context_s* ctx, mfem_brick_operator_s* op, const MgOpt
         L.ne[d] = P.ne[l][d];
         L.m[d] = P.ne[l][d] + 1;
       }
-      L.n = mg_points(L.ne);
+      L.fields = fields;
+      L.points = mg_points(L.ne);
+      L.n = mg_level_entries(fields, L.ne);
       L.npad = mg_padded(L.n);
       if (l == 0) {
         L.brick = op->brick;
@@ -343,7 +379,7 @@ static int mg_create(mfem_context_s* ctx, mfem_brick_operator_s* op, const MgOpt
         int rc = mfem_brick_create(ctx, L.ne[0], L.ne[1], L.ne[2], fb->len[0], fb->len[1], fb->len[2], 1, fb->itg_order, &L.brick);
         if (rc) return rc;
         uint64_t h = 0;
-        rc = mfem_brick_operator_create(ctx, L.brick, &op->thermal, &h);
+        rc = fields == 1 ? mfem_brick_operator_create(ctx, L.brick, &op->thermal, &h) : mfem_brick_operator_create_elasticity(ctx, L.brick, &op->elasticity, &h);
         if (rc) return rc;
         L.op = bop_from_handle(h);
       }
@@ -369,7 +405,7 @@ static int mg_create(mfem_context_s* ctx, mfem_brick_operator_s* op, const MgOpt
     mfem_mg_release(mg);
     return rc;
   }
-  mg->bytes = mg_bytes(P);
+  mg->bytes = mg_bytes_fields(P, fields);
   mg->fine = op;
   op->mg = mg;
   *out = mg;
@@ -381,7 +417,14 @@ static bool mg_nitsche(const mfem_brick_operator_s* op) { return bop_nitsche_on(
 static int mg_setup(mfem_context_s* ctx, mfem_brick_multigrid_s* mg) {
   mfem_brick_operator_s* fine = mg->fine;
   mg->ready = false;
-  if (mg_nitsche(fine)) return mg_refuse("a Nitsche (fixed_faces) term is active: K is not symmetric");
+  const bool elasticity = mg_is_elasticity(fine);
+  if (elasticity) {
+    const char* why = mg_elasticity_refusal(fine->elasticity.tau, fine->elasticity.penalty_faces);
+    if (why) return mg_refuse_elasticity(why);
+  } else if (mg_nitsche(fine)) {
+    return mg_refuse("a Nitsche (fixed_faces) term is active: K is not symmetric");
+  }
+  const auto refuse = elasticity ? mg_refuse_elasticity : mg_refuse;
   for (int l = 0; l < mg->nlev; ++l) MFEM_REQUIRE(!mg->lev[l].op->csr.op, "a level's operator is bound to a running solve");
   const mfem_brick_s* fb = fine->brick;
   MFEM_REQUIRE(fb->ne[0] == mg->lev[0].ne[0] && fb->ne[1] == mg->lev[0].ne[1] && fb->ne[2] == mg->lev[0].ne[2] && fb->plo == 0 && fb->phi == fb->m[0],
@@ -390,6 +433,7 @@ static int mg_setup(mfem_context_s* ctx, mfem_brick_multigrid_s* mg) {
   for (int l = 1; l < mg->nlev; ++l) {
     MgLevel &F = mg->lev[l - 1], &L = mg->lev[l];
     L.op->thermal = fine->thermal;
+    L.op->elasticity = fine->elasticity;
     ++L.op->csr.op_epoch;
     const MgGrid g = mg_transfer_grid(L.m[0], L.m[1], L.m[2]);
     MFEM_REQUIRE(mg_grid_ok(g), "a lattice too large for the transfer kernels' grid");
@@ -410,8 +454,8 @@ static int mg_setup(mfem_context_s* ctx, mfem_brick_multigrid_s* mg) {
   int32_t flags[4] = {0, 0, 0, 0};
   MFEM_CHECK_HIP(hipMemcpyAsync(flags, mg->d_flags, sizeof(flags), hipMemcpyDeviceToHost, ctx->stream));
   MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-  if (flags[2]) return mg_refuse("diag K has a zero (or an entry that is not a number) on some level");
-  if (flags[0] && flags[1]) return mg_refuse("diag K has entries of both signs");
+  if (flags[2]) return refuse("diag K has a zero (or an entry that is not a number) on some level");
+  if (flags[0] && flags[1]) return refuse("diag K has entries of both signs");
   mg->sign = flags[0] ? 1 : -1;
   // 3. lambda_max(D^-1 A) per level: eig_steps power steps from a fixed seeded start, the Rayleigh quotient of the last iterate
   const double s = (double)mg->sign;
@@ -436,7 +480,7 @@ static int mg_setup(mfem_context_s* ctx, mfem_brick_multigrid_s* mg) {
   if (rc) return rc;
   for (int l = 0; l < mg->nlev; ++l) {
     const double lam = ctx->h_scalars[S_MG_LAMBDA + l];
-    if (!(lam > 0.0) || !(lam < __builtin_huge_val())) return mg_refuse("the estimate of lambda_max(D^-1 A) is not a positive number: K is not definite");
+    if (!(lam > 0.0) || !(lam < __builtin_huge_val())) return refuse("the estimate of lambda_max(D^-1 A) is not a positive number: K is not definite");
     mg->lev[l].lambda_max = lam;
   }
   ++mg->setups;
@@ -449,7 +493,13 @@ int mfem_mg_solve_check(mfem_context_s* ctx, mfem_operator_head* head, const mfe
   const bool brick = head->kind == MFEM_OPERATOR_BRICK;
   const mfem_brick_operator_s* op = brick ? (const mfem_brick_operator_s*)head : nullptr;
   const bool thermal = op && op->physics == BOP_PHYSICS_THERMAL;
-  const char* why = mg_solve_refusal(brick, thermal, o->method, o->left_precond, ctx->comm != nullptr, thermal && mg_nitsche(op));
+  const bool elasticity = op && mg_is_elasticity(op);
+  const char* why = mg_solve_refusal_fields(brick, thermal, elasticity, op && op->mg != nullptr, o->method, o->left_precond, ctx->comm != nullptr,
+                                            thermal && mg_nitsche(op));
+  if (!why && elasticity) {  // (the setup inside the solve would refuse it: answered here, before anything is launched)
+    why = mg_elasticity_refusal(op->elasticity.tau, op->elasticity.penalty_faces);
+    if (why) return mg_refuse_elasticity(why);
+  }
   if (!why) return MFEM_OK;
   mfem_set_error("mfem_solve_operator: %s", why);
   return MFEM_ERR_UNSUPPORTED;
@@ -485,7 +535,8 @@ extern "C" int mfem_brick_multigrid_create(mfem_context ctx, uint64_t handle, co
   if (head->kind == MFEM_OPERATOR_MESH) return mg_refuse("a mesh operator's handle: the hierarchy is built on the lattice of a brick");
   mfem_brick_operator_s* op = bop_from_handle(handle);
   MFEM_REQUIRE(op, "not an operator's handle");
-  if (op->physics != BOP_PHYSICS_THERMAL) return mg_refuse("elasticity and hex-27 operators are not covered");
+  if (op->physics != BOP_PHYSICS_THERMAL)
+    return mg_refuse("elasticity and hex-27 operators are not covered (a hex-8 elasticity operator takes mfem_brick_multigrid_create_elasticity)");
   MFEM_REQUIRE(op->ctx == ctx, "the operator was created on another context");
   MFEM_REQUIRE(!op->mg, "the operator already has a hierarchy (one per operator: destroy it first)");
   MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
@@ -502,6 +553,35 @@ extern "C" int mfem_brick_multigrid_create(mfem_context ctx, uint64_t handle, co
   *out = (uint64_t)(uintptr_t)mg;
   return MFEM_OK;
 } MFEM_API_CATCH("mfem_brick_multigrid_create")
+
+// The hierarchy of a hex-8 elasticity operator: three field-major fields per lattice point.  The contract is mfem_brick_multigrid_create's.
+extern "C" int mfem_brick_multigrid_create_elasticity(mfem_context ctx, uint64_t handle, const mfem_multigrid_options* opts, uint64_t* out) try {
+  MFEM_REQUIRE(out, "null out");
+  *out = 0;
+  mfem_operator_head* head = (mfem_operator_head*)(uintptr_t)handle;
+  MFEM_REQUIRE(ctx && head, "null argument");
+  if (head->kind == MFEM_OPERATOR_MESH) return mg_refuse_elasticity("a mesh operator's handle: the hierarchy is built on the lattice of a brick");
+  mfem_brick_operator_s* op = bop_from_handle(handle);
+  MFEM_REQUIRE(op, "not an operator's handle");
+  if (op->physics == BOP_PHYSICS_THERMAL) return mg_refuse_elasticity("a hex-8 thermal operator's handle: it takes mfem_brick_multigrid_create");
+  if (!mg_is_elasticity(op)) return mg_refuse_elasticity("a hex-27 operator's handle: hex-27 operators are not covered");
+  MFEM_REQUIRE(op->ctx == ctx, "the operator was created on another context");
+  MFEM_REQUIRE(!op->mg, "the operator already has a hierarchy (one per operator: destroy it first)");
+  MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
+  const char* why = mg_elasticity_refusal(op->elasticity.tau, op->elasticity.penalty_faces);
+  if (why) return mg_refuse_elasticity(why);
+  MgOptions opt;
+  const char* bad = mg_options(opts, &opt);
+  if (bad) {
+    mfem_set_error("mfem_brick_multigrid_create_elasticity: %s", bad);
+    return MFEM_ERR_INVALID;
+  }
+  mfem_brick_multigrid_s* mg = nullptr;
+  const int rc = mg_create(ctx, op, opt, &mg);
+  if (rc) return rc;
+  *out = (uint64_t)(uintptr_t)mg;
+  return MFEM_OK;
+} MFEM_API_CATCH("mfem_brick_multigrid_create_elasticity")
 
 static int mg_target(mfem_context ctx, uint64_t handle, mfem_brick_multigrid_s** out) {
   mfem_brick_multigrid_s* mg = mg_from_handle(handle);

@@ -1,7 +1,8 @@
-// The host decisions of the geometric multigrid preconditioner on hex-8 thermal bricks (brick_multigrid.hip, krylov_cg_mg.hip) that are arithmetic
+// The host decisions of the geometric multigrid preconditioner on hex-8 thermal and elasticity bricks (brick_multigrid.hip, krylov_cg_mg.hip) that are arithmetic
 // alone: the level plan, the options' defaults and their refusals, the Chebyshev coefficients, the grids and tiles of the transfer kernels, how many
 // vectors a level owns, the device bytes of a hierarchy, the products of a cycle and of a pass, and which solves take the preconditioner.  Plain
-// integers in, plain structs out; no HIP, no context: tools/host_check_brick_multigrid.cpp walks them on the CPU.
+// integers in, plain structs out; no HIP, no context: tools/host_check_brick_multigrid.cpp walks them on the CPU (the field-aware forms at the end:
+// tools/host_check_brick_multigrid_elasticity.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -171,4 +172,45 @@ static inline const char* mg_solve_refusal(bool brick_operator, bool thermal_hex
   if (has_comm) return "the multigrid preconditioner runs on one rank: no communicator may be attached";
   if (nitsche_on) return "the multigrid preconditioner needs a symmetric K: a Nitsche (fixed_faces) term is active";
   return nullptr;
+}
+
+// ---- the field-aware forms: a hierarchy of `fields` field-major fields per lattice point (1: thermal, 3: elasticity) ----------------------------------
+// A level vector holds fields x points entries, field f at [f * points, (f + 1) * points); the VECTOR is padded to 32 doubles, not each field.  The
+// transfer kernels keep their grids (a thread per lattice point, which loops over the fields); coordinates are three arrays whatever the fields.
+#define MG_ELASTICITY_FIELDS 3
+static inline int64_t mg_field_offset(int field, int64_t points) { return (int64_t)field * points; }
+static inline int64_t mg_level_entries(int fields, const int* ne) { return (int64_t)fields * mg_points(ne); }
+static inline int64_t mg_level_bytes_fields(int level, const int* ne, int fields) {
+  const int64_t n = mg_points(ne);
+  int64_t b = (int64_t)mg_level_vectors(level) * mg_padded((int64_t)fields * n) * 8;
+  if (level > 0) {
+    b += 3 * (n > 0 ? n : 1) * 8;
+    for (int d = 0; d < 3; ++d) b += (int64_t)(ne[d] + 1) * 16 + 8;
+  }
+  return b;
+}
+static inline int64_t mg_bytes_fields(const MgPlan& P, int fields) {
+  int64_t b = MG_FLAG_BYTES;
+  for (int l = 0; l < P.nlev; ++l) b += mg_level_bytes_fields(l, P.ne[l], fields);
+  return b;
+}
+// bytes the library's own kernels move per cycle on a level: mg_cycle_streams (unchanged) level vectors of fields x points doubles
+static inline int64_t mg_cycle_stream_bytes(int level, int nlev, int nu, int nu_c, int fields, const int* ne) {
+  return (int64_t)mg_cycle_streams(level, nlev, nu, nu_c) * 8 * mg_level_entries(fields, ne);
+}
+// an elasticity K without a penalty face keeps the rigid-body modes: the coarsest level's Chebyshev interval does not cover a singular operator
+static inline const char* mg_elasticity_refusal(double tau, uint32_t penalty_faces) {
+  if (tau == 0.0) return "tau == 0: without the penalty K keeps the rigid-body modes and is singular";
+  if ((penalty_faces & 0x3Fu) == 0u) return "penalty_faces == 0: without a penalty face K keeps the rigid-body modes and is singular";
+  return nullptr;
+}
+// mg_solve_refusal with the hex-8 elasticity operator admitted when a hierarchy of mfem_brick_multigrid_create_elasticity is attached to it (that
+// hierarchy is the opt-in: no default one is created); every other row answers as mg_solve_refusal does
+static inline const char* mg_solve_refusal_fields(bool brick_operator, bool thermal_hex8, bool elasticity_hex8, bool hierarchy_attached, int method,
+                                                  int left_precond, bool has_comm, bool nitsche_on) {
+  if (!brick_operator || !elasticity_hex8 || thermal_hex8) return mg_solve_refusal(brick_operator, thermal_hex8, method, left_precond, has_comm, nitsche_on);
+  if (!hierarchy_attached)
+    return "the multigrid preconditioner runs on a hex-8 elasticity brick operator only with a hierarchy attached: create one with "
+           "mfem_brick_multigrid_create_elasticity (no default hierarchy is made for elasticity)";
+  return mg_solve_refusal(true, true, method, left_precond, has_comm, false);
 }

@@ -78,11 +78,11 @@ struct mfem_brick_operator_s {
   int ng;                   // the brick's rule when the operator was created
   const double* seen_x0;    // the brick's first coordinate array at the last bind (a change starts a new epoch of the cycle-graph key)
   mfem_csr_s csr;           // pattern-less: what the Krylov loop holds in place of a matrix (n = fields x control points)
-  struct mfem_brick_multigrid_s* mg;  // the multigrid hierarchy attached to a hex-8 thermal operator (brick_multigrid.hip), or nullptr; destroyed with the operator
+  struct mfem_brick_multigrid_s* mg;  // the multigrid hierarchy attached to a hex-8 thermal or elasticity operator (brick_multigrid.hip), or nullptr; destroyed with the operator
 };
 mfem_brick_operator_s* bop_from_handle(uint64_t handle);  // brick_operator.hip: nullptr unless the handle is a brick operator's
-// diag K of a hex-8 thermal operator WITH its sign (d_i <- K_ii where K_ii != 0; a zero diagonal keeps the caller's preset): what the multigrid setup
-// reads the sign of K from
+// diag K of a hex-8 thermal or elasticity operator WITH its sign (d_i <- K_ii where K_ii != 0; a zero diagonal keeps the caller's preset; elasticity:
+// 3 x control points entries, field-major): what the multigrid setup reads the sign of K from
 int bop_signed_diagonal(mfem_context_s* ctx, mfem_brick_operator_s* op, double* d);
 void mfem_mg_release(struct mfem_brick_multigrid_s* mg);  // brick_multigrid.hip: frees a hierarchy (its operator is being destroyed, or it is destroyed on its own)
 
@@ -95,6 +95,7 @@ __device__ __forceinline__ double bop_scaled(const double* __restrict__ x, const
 int bop_elasticity_launch(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, const double* x, const double* dsc, double* y, double alpha,
                           double beta, const double* dotw, double* partials, int* n_partials, const int32_t* done_flag);
 int bop_elasticity_jacobi(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, double* d);
+int bop_elasticity_signed_diagonal(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, double* d);  // K_ii itself (bop_signed_diagonal)
 
 // brick_operator_hex27.hip: the product and the diagonal of an operator with physics == BOP_PHYSICS_HEX27 (thermal, order-2 brick) under the same
 // contract; its immutable per-(device, rule) tables; bop27_prepare raises the volume kernel's dynamic-LDS limit (when an operator is created: never at

@@ -530,10 +530,11 @@ static int bop_jacobi(mfem_context_s* ctx, mfem_brick_operator_s* op, double* d)
   return MFEM_OK;
 }
 int bop_signed_diagonal(mfem_context_s* ctx, mfem_brick_operator_s* op, double* d) {
-  MFEM_REQUIRE(op->physics == BOP_PHYSICS_THERMAL, "the signed diagonal exists for the hex-8 thermal operator");
+  MFEM_REQUIRE(op->physics == BOP_PHYSICS_THERMAL || op->physics == BOP_PHYSICS_ELASTICITY, "the signed diagonal exists for the hex-8 operators");
   BrickView B;
   const int rc = bop_view(op, &B);
   if (rc) return rc;
+  if (op->physics == BOP_PHYSICS_ELASTICITY) return bop_elasticity_signed_diagonal(ctx, op, B, d);  // (3 x control points entries, field-major)
   const int64_t grid = bop_diagonal_grid(B.n_owned);
   MFEM_REQUIRE(grid < ((int64_t)1 << 31), "too many control points for one launch");
   hipLaunchKernelGGL(k_brick_diagonal<true>, dim3((unsigned)grid), dim3(MFEM_BLOCK), 0, ctx->stream, B, bop_thermal(op), d);

@@ -274,6 +274,7 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_bop_elasticity_faces(BrickView B
 // over its <= 8 adjacent elements, -sum_q w det [lam g_f^2 + mu (|g|^2 + g_f^2)] with g = grad N_a (table form), then its own penalty term.
 // Nothing is stored per element.  Runs once per solve.
 // =================================================================================================
+template <bool SIGNED>  // (SIGNED: K_(f,a),(f,a) itself, for the multigrid setup, which reads the sign of K from it)
 __global__ __launch_bounds__(MFEM_BLOCK) void k_bop_elasticity_diagonal(BrickView B, const H8Tables* __restrict__ T8, double lam, double mu, double tau,
                                                                           uint32_t penalty, int face_terms, double* __restrict__ d) {
   const int64_t node = (int64_t)blockIdx.x * MFEM_BLOCK + threadIdx.x;
@@ -311,7 +312,7 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_bop_elasticity_diagonal(BrickVie
   }
 #pragma unroll
   for (int f = 0; f < 3; ++f)
-    if (sum[f] != 0.0) d[(int64_t)f * B.n_owned + node] = fabs(sum[f]);
+    if (sum[f] != 0.0) d[(int64_t)f * B.n_owned + node] = SIGNED ? sum[f] : fabs(sum[f]);
 }
 
 // ---- host side (called from brick_operator.hip: bop_launch, bop_jacobi) -----------------------------------------------------------------------------
@@ -345,12 +346,17 @@ int bop_elasticity_launch(mfem_context_s* ctx, const mfem_brick_operator_s* op, 
   return MFEM_OK;
 }
 
-int bop_elasticity_jacobi(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, double* d) {
+template <bool SIGNED>
+static int bop_elasticity_diagonal(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, double* d) {
   const mfem_elasticity_params& p = op->elasticity;
   const int64_t grid = bop_diagonal_grid(B.n_owned);
   MFEM_REQUIRE(grid < ((int64_t)1 << 31), "too many control points for one launch");
-  hipLaunchKernelGGL(k_bop_elasticity_diagonal, dim3((unsigned)grid), dim3(MFEM_BLOCK), 0, ctx->stream, B, op->tables, p.lambda, p.mu, p.tau, p.penalty_faces,
+  hipLaunchKernelGGL(k_bop_elasticity_diagonal<SIGNED>, dim3((unsigned)grid), dim3(MFEM_BLOCK), 0, ctx->stream, B, op->tables, p.lambda, p.mu, p.tau, p.penalty_faces,
                      bop_elasticity_face_launch(p.tau, p.penalty_faces) ? 1 : 0, d);
   MFEM_CHECK_LAUNCH();
   return MFEM_OK;
+}
+int bop_elasticity_jacobi(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, double* d) { return bop_elasticity_diagonal<false>(ctx, op, B, d); }
+int bop_elasticity_signed_diagonal(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, double* d) {
+  return bop_elasticity_diagonal<true>(ctx, op, B, d);
 }

@@ -296,7 +296,7 @@ struct SolveRun {
   int64_t n_global;  // rows of the whole system
   double n_inv;      // 1 / n_global
   bool is_cg, jac, left, is_lsqr;
-  bool mg = false;  // MFEM_PRECOND_MULTIGRID (mfem_solve_operator on a hex-8 thermal brick operator: the gate has passed)
+  bool mg = false;  // MFEM_PRECOND_MULTIGRID (mfem_solve_operator on a hex-8 thermal or elasticity brick operator: the gate has passed)
   bool allow_lat;  // false: the symmetric lattice tiles have refused this solve's values (they are not tried again in this call)
   // per attempt
   SolveNext next;
@@ -928,7 +928,7 @@ extern "C" int mfem_solve(mfem_context ctx, mfem_csr A, double* vals, const doub
                           const mfem_solve_options* o, mfem_solve_stats* stats) try {
   MFEM_REQUIRE(ctx && A && o, "null argument");
   if (o->precond == MFEM_PRECOND_MULTIGRID) {  // (nothing is launched, nothing is written)
-    mfem_set_error("mfem_solve: the multigrid preconditioner needs a hex-8 thermal brick operator (mfem_brick_operator_create) and mfem_solve_operator: an assembled matrix has no lattice to coarsen");
+    mfem_set_error("mfem_solve: the multigrid preconditioner needs a hex-8 thermal brick operator (mfem_brick_operator_create), or a hex-8 elasticity one with a hierarchy of mfem_brick_multigrid_create_elasticity attached, and mfem_solve_operator: an assembled matrix has no lattice to coarsen");
     return MFEM_ERR_UNSUPPORTED;
   }
   return solve_with_graphs(ctx, A->n, [&]() { return solve_inner(ctx, A, vals, b, x_out, o, stats); });
@@ -1032,7 +1032,7 @@ extern "C" int mfem_solve_operator(mfem_context ctx, uint64_t handle, const doub
     R.allow_lat = false;
     return operator_attempt(R);
   };
-  if (mg) {  // a default hierarchy when none is attached: allocated here, before the workspace is taken; the pass captures no cycle graph
+  if (mg) {  // a default hierarchy when none is attached (thermal; an elasticity operator passed the gate with its own attached): allocated here, before the workspace is taken; the pass captures no cycle graph
     MFEM_REQUIRE(o->maxiter >= 0 && o->max_pass >= 1, "maxiter >= 0 and max_pass >= 1 required");
     const int rca = mfem_mg_attach_default(ctx, op);
     if (rca) return rca;
