@@ -29,6 +29,11 @@ long long mfem_debug_symp_fingerprint_count(void);
 long long mfem_debug_symp_coded_count(void);
 /* binds that ended on the patch sweep in its trimmed form, with rim rows outside its patches (csrc/symp_trim_decide.h; process-wide) */
 long long mfem_debug_symp_trim_count(void);
+/* binds that ended on the patch sweep in its constant form (csrc/symp_const_decide.h; process-wide): the steps the fill flagged -- every matrix value equal,
+ * bit for bit, to the reference row's of the same slot -- take their values from the kernel's arguments instead of from memory */
+long long mfem_debug_symp_const_count(void);
+/* steps the fill flagged in the last bind that ended on the patch sweep, whichever form it took (0: no direct fill, or bit 4 of the "ell" knob) */
+long long mfem_debug_symp_const_steps(void);
 /* One product y = alpha (S^-1 A S^-1) x + beta y on the row layout bound as the scaled CG (cg_variant 4) binds it, ssym = 1 / S [device, n (+ ghosts)] folded
  * into the copy, with the fused dotw . y (dotw null: none): the per-workgroup partial sums go to partials_out [host, cap], their count to *n_partials.
  * *form: -1 the bind did not end on the patch sweep, 0 / 1 the copy's diagonal is stored / coded.  Nothing stays bound.  tests/test_gpu_symp_diag_code.py */
@@ -54,8 +59,9 @@ int mfem_debug_set(const char* key, int64_t a, int64_t b);
  * by the check pass instead of the fill's fingerprint; bits 24 / 25 force one / two bands of four lattice lines per patch of the patch sweep
  * (neither: the bind decides by size, mfem_symp_bands_wanted); bit 2 forces the untrimmed patch sweep (every row of a swept plane in a patch, the
  * ragged last patch column and row included), bit 3 the trimmed one -- whole patches only, the rim rows computed row by row -- at any size (neither: the bind
- * decides by size, mfem_symp_trim_wanted; csrc/symp_trim_decide.h).
- * RETIRED, accepted and ignored: bits 4-7 (variants of k_spmv_ell), every value of bits 16-19 other than 8 (variants of k_spmv_dia) -- the sweeps of round 1 (profiles/r01_spmv_sweep.txt) chose the kernels that remain.
+ * decides by size, mfem_symp_trim_wanted; csrc/symp_trim_decide.h); bit 4 forces the stored form of the patch sweep (the fill makes no step flags), bit 5 its
+ * constant form whatever the share of flagged steps (neither: the bind decides by that share, spc_gate; csrc/symp_const_decide.h; same results bit for bit).
+ * RETIRED, accepted and ignored: bits 6-7 (variants of k_spmv_ell; bits 4-5 were retired with them and have been given out again), every value of bits 16-19 other than 8 (variants of k_spmv_dia) -- the sweeps of round 1 (profiles/r01_spmv_sweep.txt) chose the kernels that remain.
  * These knobs are read when a layout is BOUND (every mfem_solve and mfem_spmv_solver_layout binds its own): a product runs the kernel its bind
  * recorded; only the launch geometry (bits 8-15, 20, 26) is read per product.  Set them before the solve. */
 /* ^ key "ell": mfem_debug_set("ell", a, b) with (int enable) = (a[, b]) */

@@ -68,10 +68,10 @@ static int context_allocate(mfem_context_s* c) {
   MFEM_CHECK_HIP(hipMalloc(&c->d_partials, sizeof(double) * MFEM_MAX_PARTIALS * 8));
   MFEM_CHECK_HIP(hipMalloc(&c->d_scalars, sizeof(double) * MFEM_NSCALARS));
   MFEM_CHECK_HIP(hipHostMalloc(&c->h_scalars, sizeof(double) * MFEM_NSCALARS));
-  MFEM_CHECK_HIP(hipMalloc(&c->d_flags, sizeof(int32_t) * 24));
-  MFEM_CHECK_HIP(hipHostMalloc(&c->h_flags, sizeof(int32_t) * 24));
+  MFEM_CHECK_HIP(hipMalloc(&c->d_flags, sizeof(int32_t) * MFEM_NFLAGS));
+  MFEM_CHECK_HIP(hipHostMalloc(&c->h_flags, sizeof(int32_t) * MFEM_NFLAGS));
   MFEM_CHECK_HIP(hipMemsetAsync(c->d_scalars, 0, sizeof(double) * MFEM_NSCALARS, c->stream));
-  MFEM_CHECK_HIP(hipMemsetAsync(c->d_flags, 0, sizeof(int32_t) * 24, c->stream));
+  MFEM_CHECK_HIP(hipMemsetAsync(c->d_flags, 0, sizeof(int32_t) * MFEM_NFLAGS, c->stream));
   MFEM_CHECK_HIP(hipEventCreate(&c->ev0));
   MFEM_CHECK_HIP(hipEventCreate(&c->ev1));
   return MFEM_OK;

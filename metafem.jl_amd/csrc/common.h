@@ -21,7 +21,8 @@
 #define MFEM_BLOCK 256
 #define MFEM_MAX_PARTIALS 4096
 static_assert(LAT_MAX_GATHER_GRID == MFEM_MAX_PARTIALS, "a workgroup of the tiles' gather pass writes one partial sum");
-#define MFEM_NSCALARS 4096       // device-resident Krylov scalars (doubles)  // upper bound on per-launch partial sums of a fused reduction
+#define MFEM_NFLAGS 80           // 32-bit device flags of a context (mfem_context_s::d_flags)
+#define MFEM_NSCALARS 4096      // device-resident Krylov scalars (doubles)  // upper bound on per-launch partial sums of a fused reduction
 
 void mfem_set_error(const char* fmt, ...);
 
@@ -96,7 +97,8 @@ struct mfem_context_s {
   double* d_partials;   // [MFEM_MAX_PARTIALS * 8]
   double* d_scalars;    // [256] device-resident Krylov scalars
   double* h_scalars;    // pinned, [256]
-  int32_t* d_flags;     // [24] device flags (16-17: the symmetry fingerprint of k_symp_fill, 64 bits; 18: its coded-diagonal gate, 19: the codes' unit is -1.0): 0-7 the Krylov loop's two banks (done, iteration count, ...); 9 mirrored-sweep check; 10 ring self-test; 11 mesh
+  int32_t* d_flags;     // [MFEM_NFLAGS] device flags (16-17: the symmetry fingerprint of k_symp_fill, 64 bits; 18: its coded-diagonal gate, 19: the codes' unit is -1.0; 20: its count of
+                        // constant steps, 22-77: the reference row of the constant form, a SympConst -- symp_const_decide.h): 0-7 the Krylov loop's two banks (done, iteration count, ...); 9 mirrored-sweep check; 10 ring self-test; 11 mesh
                         // assembly; 12-15 one-shot statistics, each user clears the slots it reads before its launch and synchronises after it (layout binds:
                         // 12-13 max |a| / symmetry measure, krylov.hip (try_scaled_cg): 12-15 extremes of S, assemble_hex27.hip: 14 count of non-affine elements)
   int32_t* h_flags;     // pinned
@@ -201,6 +203,11 @@ struct mfem_csr_s {
   int symp_trim;            // the bound patch-major copy covers whole patches only, the rim rows have a compact copy behind it (symp_trim_decide.h; mfem_symp_trim_wanted)
   int symp_DC;              // form of the bound patch-major copy's main part (spmv_symp.h): 1 = the diagonal as one-byte codes (mfem_symp_coded_wanted), 0 stored / none bound
   int symp_dneg;            // symp_DC = 1: the codes count from -1.0 (the first swept row's diagonal is negative), not from +1.0
+  int symp_CS;              // the bound patch sweep takes the values of its flagged steps from kernel arguments (symp_const_decide.h), 0 stored form / none bound
+  int symp_cs_last;         // symp_CS and the flagged steps of the last bind that ended on the patch sweep (accounting of an unbound pattern, as symp_dc_last)
+  int64_t symp_flagged, symp_flagged_last;  // flagged steps of the bound copy (counted by the fill whether or not the constant form is taken)
+  double symp_cst[27];      // symp_CS = 1: the reference row's 27 values as the fill forms them
+  int symp_ccode;           // ... and, coded diagonal, its diagonal's code
   int symp_dc_last;         // symp_DC of the last bind that ended on the patch sweep (the byte accounting of an unbound pattern answers for that bind)
   double* symp_vals;        // not owned (solver workspace, behind ell_vals): [plane - p0][patch][27 x 128 + edge block]; set while dia_kernel is the patch sweep
   // solver layout mode 3 for rows of uneven length: the row-sorted sliced layout (spmv_sell.hip) or its node-blocked form (spmv_bsell.hip) -- sell.form

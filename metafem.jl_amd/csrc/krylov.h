@@ -102,6 +102,9 @@ inline uint64_t mfem_csr_graph_key(uint64_t key, const mfem_csr_s* A) {
   key = mfem_hash(key, A->index_base); key = mfem_hash(key, A->ell_vals);
   key = mfem_hash(key, A->ell_bound_mode + 16 * A->dia_kernel); key = mfem_hash(key, A->sell.vals); key = mfem_hash(key, A->lat27.vals); key = mfem_hash(key, A->lat8.vals); key = mfem_hash(key, A->symp_vals);
   key = mfem_hash(key, A->symp_B + 16 * A->symp_DC + 32 * A->symp_dneg + 64 * A->symp_trim);  // (the sweep's instantiation: the coded form's gate decides per bind, on the same buffers)
+  // the constant form (symp_const_decide.h) passes the reference row's values and code in the sweep's arguments: another matrix, another cycle
+  key = mfem_hash(key, A->symp_CS);
+  if (A->symp_CS) { key = mfem_hash_bytes(key, A->symp_cst, sizeof(A->symp_cst)); key = mfem_hash(key, A->symp_ccode); }
   // the column scaling the lattice-tile kernels apply to x is a kernel argument too: a solve with right Jacobi (dsc = the solve's d) and one without
   // (dsc = null) on the same pattern, values and workspace must not share a captured cycle
   key = mfem_hash(key, A->lat27.dsc); key = mfem_hash(key, A->lat8.dsc);

@@ -290,6 +290,14 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_dia_vals(int64_t n, int64_t npad
   }
 }
 
+// A value of the patch-major copy as the fill forms it: with the symmetric scaling v * (srow * sc) -- the product of the two factors first: a mirrored pair is
+// multiplied by the same number --, else the plain value.  One function for k_symp_fill and k_symp_const_ref: the reference row's values are compared bit by bit.
+template <bool SYM>
+__device__ __forceinline__ double symp_formed(double v, double srow, double sc) {
+  if constexpr (SYM) return v * (srow * sc);
+  else return v;
+}
+
 // The swept rows of the patch-major copy: a workgroup of two waves per patch step (plane, strip of SP_L lines, patch column), a wave per pair of lattice lines,
 // lane = line * SP_W + column -- 64 rows whose CSR values are two contiguous runs (one per line: 6.9 KB when all 32 rows have their 27 entries).  Every slot store of
 // a wave is ONE aligned 512-byte piece of the copy and the two halves of each 1 KB slot are written by the same workgroup; the step's edge block (318 entries owned by
@@ -304,11 +312,17 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_dia_vals(int64_t n, int64_t npad
 // swept row whose diagonal is further than 127 ulps from the unit (the other sign, zero, absent, non-finite) raises dcbad[0]: the bind then refills in the stored
 // form.  The unit is +1.0 or, with dcbad[1] set (k_symp_diag_sign: the first swept row's diagonal is negative -- the thermal K is negative definite), -1.0.  The
 // slot-major copy gets the diagonal as a double either way (k_ell_diag, the rows outside the swept planes).
+// Constant steps (symp_const_decide.h; sflags != nullptr): every lane compares each value it forms, by bit pattern (-0.0, NaN and an absent entry's zero all
+// differ from a reference row of 27 finite entries), with the reference row's of the same slot (cref, written by k_symp_const_ref in front of this launch) and,
+// coded form, its diagonal's code.  A step is flagged when all its bands took the full-tile path in both waves (whole patch, 27 entries in every row) and no lane
+// met a difference: one LDS word gathers the waves' verdicts in front of the barrier that closes the step, thread 0 writes the step's byte behind it.  The
+// edge block needs no look of its own: its entries are copies of the rows' lower-slot values.  The workgroup's flagged steps are added once to *scount.
 template <typename RP, bool SYM, bool DC = false>
 __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* __restrict__ rowptr, const int32_t* __restrict__ col,
                                                     const double* __restrict__ vals, int base, const DiaOffsets* __restrict__ Op, int cls,
                                                     double* __restrict__ out, SympGeom Gm, double* __restrict__ pv, const double* __restrict__ ssym,
-                                                    unsigned long long* __restrict__ fp, int32_t* __restrict__ dcbad) {
+                                                    unsigned long long* __restrict__ fp, int32_t* __restrict__ dcbad, const SympConst* __restrict__ cref,
+                                                    unsigned char* __restrict__ sflags, int32_t* __restrict__ scount) {
   const DiaOffsets& O = *Op;
   extern __shared__ double lds[];
   constexpr int RUN = SP_W * 27;  // entries of a full 32-row run
@@ -336,7 +350,16 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
     const uint32_t xl = __builtin_amdgcn_readfirstlane((uint32_t)(uint64_t)x), xh = __builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)x >> 32));
     return (int64_t)(((uint64_t)xh << 32) | xl);
   };
+  int* const Fw = reinterpret_cast<int*>(E + spEPAD + sp_cpad(spB, DC));  // constant steps: non-zero once a wave of the step has met a difference (zero between steps)
+  const bool cs = sflags != nullptr && cref->valid != 0;  // (no reference row: every step's byte is 0)
+  const int ccode = DC && cs ? cref->code : 0;
+  // the reference row, copied to LDS once in front of the steps and read there as broadcasts.  Read from memory inside the step, the scalar loads share their
+  // counter with the LDS staging of the tile and every step waited for them (14.46 instead of 13.89 ms per fill at 512^3); held in 54 scalar registers they spill.
+  double* const Cv = reinterpret_cast<double*>(Fw) + 1;
+  if (threadIdx.x < 27) Cv[threadIdx.x] = cref->v[threadIdx.x];
+  int nflagged = 0;
   for (int i = threadIdx.x; i < spEPAD + sp_cpad(spB, DC); i += 128) E[i] = 0.0;  // (the code block lies behind E: all-zero bytes)
+  if (threadIdx.x == 0) *Fw = 0;
   __syncthreads();
   // Work item wi = (plane, q) takes patch (q + plane * rot) % NP of its plane.  Workgroups with equal blockIdx % 8 share an XCD and the grid is a multiple of 8: with
   // a patch count per plane that is a multiple of 8 too (whole patches of the usual meshes: 1024 at 512^3) a workgroup would meet the same patch, and an XCD
@@ -350,6 +373,7 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
     const int64_t q = step / Gm.NPk;
     const int prow = (int)(q % Gm.NR), pl = (int)(q / Gm.NR);
     double* const pe = pv + step * spMAIN + spB * NSL * SP_ROWS;
+    int differs = cs ? 0 : 1;
     for (int band = 0; band < spB; ++band) {  // the strips of the patch one after the other: their edge entries meet in E (a strip past the lattice: nlines = 0)
     const int strip = prow * spB + band;
     const int jj0 = strip * SP_L + 2 * w, kk0 = kp * SP_W;
@@ -363,6 +387,8 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
     }
     const bool full = ncol == SP_W && nlines == 2 && a1 - a0 == RUN && b1 - b0 == RUN;
     const bool valid = c < ncol && h < nlines;
+    const bool cmp = cs && full;  // (wave-uniform)
+    if (!full) differs = 1;
     const int64_t r = rb + (int64_t)h * m2 + c;
     const int line = 2 * w + h;
     double* const pm = pv + step * spMAIN + band * NSL * SP_ROWS + line * SP_W + c;
@@ -453,7 +479,8 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
         double v = 0.0;
         if (present >> sl & 1u) {
           v = Tr[sl];
-          if constexpr (SYM) v = v * (srow * sc[sl]);  // (the product of the two factors first: a mirrored pair is multiplied by the same number)
+          v = symp_formed<SYM>(v, srow, sc[sl]);
+          if (cmp) differs |= __double_as_longlong(v) != __double_as_longlong(Cv[sl]) ? 1 : 0;
           if (fp && sl != 13) {
             const int64_t cc = r + O.off[cls][sl];
             if (cc >= sw_lo && cc < sw_hi && jj0 + h + sp_dj(sl) < Gm.ms1 && kk0 + c + sp_dk(sl) < Gm.ms2) {
@@ -479,6 +506,7 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
               int code = 0;
               if (!sp_diag_code(v, code, unit)) nocode = 1;
               else Cb[band * SP_ROWS + line * SP_W + c] = (signed char)code;
+              if (cmp) differs |= code != ccode ? 1 : 0;
             }
           }
         }
@@ -486,13 +514,21 @@ __global__ __launch_bounds__(128) void k_symp_fill(int64_t n, int K, const RP* _
     }
     __builtin_amdgcn_wave_barrier();  // (the wave's staging area is overwritten by its next strip)
     }
+    if (sflags && __ballot(differs) != 0 && lane == 0) *Fw = 1;
     __syncthreads();
     for (int i = threadIdx.x; i < spEPAD + sp_cpad(spB, DC); i += 128) {  // (DC: the code block follows the edge block in the copy as in LDS)
       DIA_ST(pe + i, E[i]);
       E[i] = 0.0;
     }
+    if (sflags && threadIdx.x == 0) {  // (the barrier below orders the reset before the next step's verdicts)
+      const int f = *Fw == 0 ? 1 : 0;
+      sflags[step] = (unsigned char)f;
+      nflagged += f;
+      *Fw = 0;
+    }
     __syncthreads();
   }
+  if (sflags && threadIdx.x == 0 && nflagged) atomicAdd(scount, nflagged);
   if (DC && nocode) atomicOr(dcbad, 1);
   if (fp) {
 #pragma unroll
@@ -640,6 +676,35 @@ __global__ __launch_bounds__(64) void k_symp_diag_sign(int64_t r, const RP* __re
   const int64_t lo = (int64_t)rowptr[r] - base, hi = (int64_t)rowptr[r + 1] - base;
   for (int64_t j = lo + threadIdx.x; j < hi; j += 64)
     if ((int64_t)col[j] - base == r && __double_as_longlong(vals[j]) < 0) neg[0] = 1;
+}
+
+// The reference row of the constant form (symp_const_decide.h): row r -- the centre of the swept region -- formed as k_symp_fill forms it, lane s = slot s
+// (a row of 27 entries has entry s in slot s).  valid = 0 when the row is short or, coded form, its diagonal has no code counted from the unit of dcbad[1].
+// One wave, in front of the fill.
+template <typename RP, bool SYM, bool DC>
+__global__ __launch_bounds__(64) void k_symp_const_ref(int64_t r, const RP* __restrict__ rowptr, const double* __restrict__ vals, int base,
+                                                        const DiaOffsets* __restrict__ Op, int cls, const double* __restrict__ ssym,
+                                                        const int32_t* __restrict__ dcbad, SympConst* __restrict__ ref) {
+  const int lane = threadIdx.x;
+  const int64_t lo = (int64_t)rowptr[r] - base, hi = (int64_t)rowptr[r + 1] - base;
+  const bool full = hi - lo == 27;
+  int code = 0;
+  bool coded = true;
+  if (full && lane < 27) {
+    double srow = 1.0, sc = 1.0;
+    if constexpr (SYM) {
+      srow = ssym[r];
+      sc = ssym[r + Op->off[cls][lane]];
+    }
+    const double v = symp_formed<SYM>(vals[lo + lane], srow, sc);
+    ref->v[lane] = v;
+    if (DC && lane == 13) coded = sp_diag_code(v, code, sp_unit_bits(dcbad[1]));
+  }
+  const bool ok = full && __ballot(!coded) == 0;
+  if (lane == 13) {
+    ref->code = code;
+    ref->valid = ok ? 1 : 0;
+  }
 }
 
 // lattice lines of odd length: the lane pair at the line's end holds the last point and a cell outside the lattice, which no row writes
@@ -802,7 +867,8 @@ bool mfem_dia_fill_fast(const mfem_csr_s* A, const double* dsc, bool direct) {
          A->symp_m1 >= 3 && A->symp_m2 >= 3 && g_ell.dia_fast;
 }
 int mfem_dia_copy(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, const double* ssym, const SympGeom& G,
-                  double* pvals, double* rim, bool want_fp, bool* fp_made) {
+                  double* pvals, double* rim, bool want_fp, bool* fp_made, unsigned char* sflags, bool* flags_made) {
+  if (flags_made) *flags_made = false;
   const DiaOffsets* O = (const DiaOffsets*)A->dia_dev;
   if (pvals && (G.ms2 & 1)) {  // lattice lines of odd length leave cells of the patch-major copy that no row writes
     const int64_t cells = (int64_t)(G.p1 - G.p0) * G.NS * SP_L * 27;
@@ -853,10 +919,20 @@ int mfem_dia_copy(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double
       hipLaunchKernelGGL(k_symp_diag_sign<RP>, dim3(1), dim3(64), 0, ctx->stream, (int64_t)G.p0 * G.PL, (const RP*)A->rowptr, A->colidx, vals, A->index_base, dcbad + 1);
       MFEM_CHECK_LAUNCH();
     }
+    SympConst* cref = (SympConst*)(ctx->d_flags + SPC_REF_AT);
+    int32_t* scount = ctx->d_flags + SPC_COUNT_AT;
+    if (sflags) {  // the constant form's reference row: the centre of the swept region (middle swept plane, line ms1 / 2, point ms2 / 2), formed as the fill forms it
+      const int64_t rr = (int64_t)(G.p0 + (G.p1 - G.p0) / 2) * G.PL + (int64_t)(G.ms1 / 2) * G.m2 + G.ms2 / 2;
+      MFEM_CHECK_HIP(hipMemsetAsync(scount, 0, sizeof(int32_t), ctx->stream));
+      const auto kr = coded ? k_symp_const_ref<RP, true, true> : ssym ? k_symp_const_ref<RP, true, false> : k_symp_const_ref<RP, false, false>;
+      hipLaunchKernelGGL(kr, dim3(1), dim3(64), 0, ctx->stream, rr, (const RP*)A->rowptr, vals, A->index_base, O, A->sym_cls, ssym, (const int32_t*)dcbad, cref);
+      MFEM_CHECK_LAUNCH();
+      if (flags_made) *flags_made = true;
+    }
     const auto kf = coded ? k_symp_fill<RP, true, true> : ssym ? k_symp_fill<RP, true> : k_symp_fill<RP, false>;
     const int fB = G.B > 0 ? G.B : 1;
-    hipLaunchKernelGGL(kf, dim3(gf), dim3(128), sizeof(double) * (2 * (2 * SP_W * 27) + sp_epad(fB) + sp_cpad(fB, G.DC)), ctx->stream, A->n, A->ell_K, (const RP*)A->rowptr,
-                       A->colidx, vals, A->index_base, O, A->sym_cls, buf, G, pvals, ssym, fpr, dcbad);
+    hipLaunchKernelGGL(kf, dim3(gf), dim3(128), sizeof(double) * (2 * (2 * SP_W * 27) + sp_epad(fB) + sp_cpad(fB, G.DC) + 1 + 27), ctx->stream, A->n, A->ell_K, (const RP*)A->rowptr,
+                       A->colidx, vals, A->index_base, O, A->sym_cls, buf, G, pvals, ssym, fpr, dcbad, (const SympConst*)cref, sflags, scount);
     MFEM_CHECK_LAUNCH();
     return MFEM_OK;
   });

@@ -9,6 +9,7 @@
 #include "layouts.h"
 #include "spmv_symp.h"
 #include "symp_trim_decide.h"
+#include "symp_const_decide.h"
 
 // Blocked slot-major layout ("sliced ELL"): rows are grouped in blocks of ELL_B = 128 (the rows of one wave at two rows per
 // lane); block b stores its K slots one after the other, element (row r, slot s) at  b * K * 128 + s * 128 + (r & 127).
@@ -45,6 +46,16 @@ struct SympGeom {
   int rim_pp;              // rim rows per plane
   int64_t rim_rows, rim_units;  // rim rows of all swept planes; units of SPT_UNIT rows of their copy
 };
+// The constant form of the patch sweep (symp_const_decide.h).  On the device (ctx->d_flags + SPC_REF_AT, written by k_symp_const_ref before the fill): the
+// reference row's 27 values as the fill forms them, its diagonal's code (coded form) and whether the row had all 27 entries (and a code).  In the
+// sweep's arguments (CS = 1): the same values, passed by value -- wave-uniform, they live in scalar registers.
+struct SympConst {
+  double v[27];
+  int32_t code, valid;
+};
+#define SPC_COUNT_AT 20  // ctx->d_flags[20]: flagged steps of the last fill
+#define SPC_REF_AT 22    // ctx->d_flags[22..77]: the SympConst (8-byte aligned)
+static_assert(SPC_REF_AT % 2 == 0 && SPC_REF_AT * 4 + sizeof(SympConst) <= MFEM_NFLAGS * 4, "the reference row must fit the context's flags");
 // the rows outside the swept planes, taken by the sweep's waves after their runs (unsplit SpMV): per-row code on the slot-major copy
 struct SympTail {
   int on, K;
@@ -182,6 +193,7 @@ struct EllKnobs {
   std::atomic<int> enable{1};            // bit 0: modes 1 and 2 on
   std::atomic<int> dia{1};               // bit 1 clears it: explicit columns even when the matrix is diagonal-structured
   std::atomic<int> symp_trim{0};         // bit 2 forces the untrimmed patch sweep (every row of a swept plane in a patch), bit 3 the trimmed one at any size (0: mfem_symp_trim_wanted decides by size)
+  std::atomic<int> symp_const{0};        // bit 4 forces the stored form of the patch sweep, bit 5 the constant form whatever the share of flagged steps (0: spc_gate decides; symp_const_decide.h)
   std::atomic<int> grid_mult{6};         // bits 8-15 (0 keeps the value): persistent workgroups per CU of the per-row kernels (profiles/r01_spmv_sweep.txt: 6 or 8)
   std::atomic<int> shared_x{1};          // bits 16-19 = 8 clears it: the plain per-row kernel without the shared x loads of three consecutive diagonals, no sweep
   std::atomic<int> xcd{0};               // bit 20: each XCD walks a contiguous eighth of the rows (k_spmv_dia; needs a grid that is a multiple of 8)
@@ -207,7 +219,7 @@ DiaKernel mfem_dia_kernel_wanted(const mfem_csr_s* A, DiaKernel refused = DIA_NO
 // spmv_dia.hip: inspection; the copies of a bind (pvals: the swept planes G straight to the patch-major copy); all rows / the rows outside [lo, hi)
 int mfem_dia_plan(mfem_context_s* ctx, mfem_csr_s* A);
 int mfem_dia_copy(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, const double* ssym, const SympGeom& G,
-                  double* pvals, double* rim, bool want_fp, bool* fp_made);  // rim: the compact copy of G's rim rows (nullptr: none wanted)
+                  double* pvals, double* rim, bool want_fp, bool* fp_made, unsigned char* sflags = nullptr, bool* flags_made = nullptr);  // rim: the compact copy of G's rim rows (nullptr: none wanted); sflags: the step flags of the constant form (made by k_symp_fill alone)
 int mfem_dia_launch(mfem_context_s* ctx, mfem_csr_s* A, bool triples, int cap, const SpmvArgs& a);
 int mfem_dia_launch_outside(mfem_context_s* ctx, mfem_csr_s* A, const SpmvArgs& a, double* partials, int64_t lo, int64_t hi, int* ngrid);
 // spmv_sym.hip: the two sweeps k = DIA_SYM27, DIA_SYMP -- structure, size rule, geometry, accounting, the symmetry verdict of a bind, the product
@@ -220,7 +232,7 @@ int mfem_symp_bands(const mfem_csr_s* A);         // the bound copy's band count
 // THE decision whether the patch sweep of a bind covers whole patches only (symp_trim_decide.h), and the bound copy's answer (unbound: what a bind would take)
 int mfem_symp_trim_wanted(const mfem_csr_s* A);
 int mfem_symp_trim(const mfem_csr_s* A);
-int64_t mfem_symp_copy_doubles(const mfem_csr_s* A, int B, int trim);  // doubles of the patch-major copy and the rim copy behind it (stored form: the larger one)
+int64_t mfem_symp_copy_doubles(const mfem_csr_s* A, int B, int trim);  // doubles of the patch-major copy, the rim copy behind it (stored form: the larger one) and the step flags of the constant form behind that
 int64_t mfem_symp_swept_rows(const mfem_csr_s* A);                     // rows the patches cover (bound copy's geometry; unbound: what a bind would take)
 // THE decision which form the main part of a patch-major copy gets (spmv_symp.h): 1 = the diagonal as one-byte ulp codes -- only where the copy is
 // filled by k_symp_fill (`fast`: mfem_dia_fill_fast) with the symmetric scaling, whose diagonal is a_ii * (t_i * t_i) = 1.0 up to a few roundings
@@ -229,5 +241,7 @@ int mfem_symp_coded(const mfem_csr_s* A);         // the bound copy's form; unbo
 bool mfem_dia_fill_fast(const mfem_csr_s* A, const double* dsc, bool direct);  // spmv_dia.hip: would k_symp_fill fill the swept rows of a bind?
 int64_t mfem_sym_entries(const mfem_context_s* ctx, const mfem_csr_s* A, DiaKernel k);
 int mfem_sym_verdict(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const double* buf, double* pvals, const SympGeom& G, bool direct, bool fp_made, bool* ok,
-                     bool* dc_refused, int* dneg);
+                     bool* dc_refused, int* dneg, bool flags_made = false, SympConst* cst = nullptr, int64_t* flagged = nullptr);
+// the step flags' place in the layout's buffer: behind the patch-major copy and the rim copy of geometry G (spmv_sym.hip)
+unsigned char* mfem_symp_flags_of(double* pvals, const SympGeom& G);
 int mfem_sym_launch(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const SpmvArgs& a);

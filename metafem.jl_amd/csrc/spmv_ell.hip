@@ -34,7 +34,7 @@ extern "C" int mfem_debug_set_layout_min_rows(int64_t diagonal_slots, int64_t ex
   return MFEM_OK;
 } MFEM_API_CATCH("mfem_debug_set_layout_min_rows")
 
-// The "ell" knob word, decoded here and nowhere else (fields: spmv_ell.h; bits: include/metafem_mi355x_debug.h).  Bits 4-7, 16-19 (other than the value
+// The "ell" knob word, decoded here and nowhere else (fields: spmv_ell.h; bits: include/metafem_mi355x_debug.h).  Bits 6-7, 16-19 (other than the value
 // 8) and 24-25 selected kernel variants of the round-1 sweeps (profiles/r01_spmv_sweep.txt): the winners alone are left, the bits are ignored.
 EllKnobs g_ell;
 extern "C" int mfem_debug_set_ell(int enable) try {
@@ -42,6 +42,7 @@ extern "C" int mfem_debug_set_ell(int enable) try {
   g_ell.enable = enable & 1;
   g_ell.dia = (enable & 2) ? 0 : 1;
   g_ell.symp_trim = (enable & 4) ? 2 : (enable & 8) ? 1 : 0;
+  g_ell.symp_const = (enable & 16) ? 2 : (enable & 32) ? 1 : 0;
   if ((enable >> 8) & 255) g_ell.grid_mult = (enable >> 8) & 255;
   g_ell.shared_x = ((enable >> 16) & 15) == 8 ? 0 : 1;
   g_ell.xcd = (enable >> 20) & 1;
@@ -306,6 +307,10 @@ int mfem_symp_coded_wanted(DiaKernel k, bool fast, const double* ssym) { return 
 int mfem_symp_coded(const mfem_csr_s* A) { return A->symp_vals ? A->symp_DC : A->symp_dc_last; }
 static std::atomic<long long> g_symp_coded_binds{0};  // binds that ended on the patch sweep with the coded form (tests, the A/B)
 extern "C" long long mfem_debug_symp_coded_count(void) { return g_symp_coded_binds; }
+// The constant form of the patch sweep, decided here once per bind (spc_form, symp_const_decide.h) from the fill's count of flagged steps.
+static std::atomic<long long> g_symp_const_binds{0}, g_symp_const_steps{0};  // binds that ended in the constant form; flagged steps of the last patch-sweep bind (tests, the A/B)
+extern "C" long long mfem_debug_symp_const_count(void) { return g_symp_const_binds; }
+extern "C" long long mfem_debug_symp_const_steps(void) { return g_symp_const_steps; }
 size_t mfem_ell_vals_bytes(const mfem_csr_s* A) {
   if (A->ell_state != 1 || !g_ell.enable) return 0;
   const bool dia = mfem_dia_layout_planned(A);
@@ -322,7 +327,9 @@ size_t mfem_ell_vals_bytes(const mfem_csr_s* A) {
 // Bind of mode 2, once per solve: choose the kernel, make its copies, obtain the symmetry verdict of these values, fall back to the next kernel if
 // they are refused.  The copy is bound only once the kernel that serves it is known.
 static int dia_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, double* buf, const double* dsc, const double* ssym) {
-  bool direct = false, fp_made = false;
+  bool direct = false, fp_made = false, flags_made = false;
+  SympConst cst{};
+  int64_t flagged = 0;
   DiaKernel k = mfem_dia_kernel_wanted(A, DIA_NONE, &direct);
   A->symp_trim = mfem_symp_trim_wanted(A);
   A->symp_B = mfem_symp_bands_wanted(A);  // (A is unbound here: the geometry below is this count's)
@@ -332,15 +339,17 @@ static int dia_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, doub
   SympGeom G = k == DIA_SYMP ? mfem_symp_geom(ctx, A) : SympGeom{};
   // the rim rows' compact copy lies behind the patch-major one (whose length depends on the form of the diagonal: placed per copy)
   auto rim_of = [&](const SympGeom& g) -> double* { return k == DIA_SYMP && g.rim_units > 0 ? pvals + (int64_t)g.NR * g.NPk * (g.p1 - g.p0) * sp_step(g.B, g.DC) : nullptr; };
-  int rc = mfem_dia_copy(ctx, A, vals, buf, dsc, ssym, G, direct ? pvals : nullptr, rim_of(G), g_ell.symp_fingerprint != 0, &fp_made);
+  // the step flags of the constant form lie behind the rim copy; the fill makes them unless the knob forces the stored form
+  auto flags_of = [&](const SympGeom& g) -> unsigned char* { return k == DIA_SYMP && direct && g_ell.symp_const != 2 ? mfem_symp_flags_of(pvals, g) : nullptr; };
+  int rc = mfem_dia_copy(ctx, A, vals, buf, dsc, ssym, G, direct ? pvals : nullptr, rim_of(G), g_ell.symp_fingerprint != 0, &fp_made, flags_of(G), &flags_made);
   while (!rc && (k == DIA_SYMP || k == DIA_SYM27)) {  // a sweep: are the pairs it mirrors bitwise equal?
     bool ok = false, dc_refused = false;
-    rc = mfem_sym_verdict(ctx, A, k, buf, pvals, G, direct, fp_made, &ok, &dc_refused, &A->symp_dneg);
+    rc = mfem_sym_verdict(ctx, A, k, buf, pvals, G, direct, fp_made, &ok, &dc_refused, &A->symp_dneg, flags_made, &cst, &flagged);
     if (rc) break;
     if (dc_refused) {  // a swept row's scaled diagonal has no code: the same copy in the stored form, and its verdict
       A->symp_DC = 0;
       G = mfem_symp_geom(ctx, A);
-      rc = mfem_dia_copy(ctx, A, vals, buf, dsc, ssym, G, pvals, rim_of(G), g_ell.symp_fingerprint != 0, &fp_made);
+      rc = mfem_dia_copy(ctx, A, vals, buf, dsc, ssym, G, pvals, rim_of(G), g_ell.symp_fingerprint != 0, &fp_made, flags_of(G), &flags_made);
       continue;
     }
     if (ok) break;
@@ -356,7 +365,24 @@ static int dia_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, doub
   A->symp_vals = k == DIA_SYMP ? pvals : nullptr;
   if (k != DIA_SYMP) A->symp_B = A->symp_DC = A->symp_trim = 0;
   if (!A->symp_DC) A->symp_dneg = 0;
+  A->symp_CS = 0;
+  A->symp_flagged = 0;
   if (k == DIA_SYMP) {  // (the byte accounting of the unbound pattern answers for this bind)
+    const int64_t steps = mfem_symp_steps(A);
+    if (!flags_made) flagged = 0;
+    // the sweep's path for flagged steps multiplies by the reference row's values where the stored form reads the mirrored entry: only behind the fingerprint's
+    // verdict (every pair among the swept rows bitwise equal; the check pass lets +0.0 meet -0.0) and with a reference row that is its own mirror image
+    // (no flagged step: nothing to ask)
+    bool mirror = fp_made || flagged == 0;
+    for (int sl = 0; sl < 13 && mirror && flagged > 0; ++sl) mirror = memcmp(&cst.v[sl], &cst.v[26 - sl], sizeof(double)) == 0;
+    A->symp_CS = spc_form(flags_made && mirror, flags_made && cst.valid != 0, flagged, steps, g_ell.symp_const == 2, g_ell.symp_const == 1);
+    A->symp_flagged = flagged;
+    memcpy(A->symp_cst, cst.v, sizeof(A->symp_cst));
+    A->symp_ccode = cst.code;
+    A->symp_cs_last = A->symp_CS;
+    A->symp_flagged_last = flagged;
+    g_symp_const_steps = flagged;
+    if (A->symp_CS) ++g_symp_const_binds;
     A->symp_dc_last = A->symp_DC;
     if (A->symp_DC) ++g_symp_coded_binds;
     if (G.rim_units > 0) ++g_symp_trim_binds;
@@ -391,7 +417,8 @@ void mfem_ell_unbind(mfem_csr_s* A) {
   A->ell_bound_mode = A->dia_kernel = DIA_NONE;
   A->ell_vals = A->symp_vals = nullptr;
   A->ell_src = nullptr;
-  A->symp_B = A->symp_DC = A->symp_dneg = A->symp_trim = 0;
+  A->symp_B = A->symp_DC = A->symp_dneg = A->symp_trim = A->symp_CS = 0;
+  A->symp_flagged = 0;
 }
 void mfem_ell_free(mfem_csr_s* A) {
   if (A->ell_cols) hipFree(A->ell_cols);

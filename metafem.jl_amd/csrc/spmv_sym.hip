@@ -224,6 +224,21 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_sym27_check(int K, const DiaOffs
 //     copy behind the patch-major one (symp_rim_unit: the sweep's waves take its 64-row units after their runs).  Nothing changes in the step body: lane
 //     validity and the x offsets keep using m1, m2, and a halo cell next to the rim is filled from the edge block as before.  512^3: 1024 patches, 3 runs per
 //     patch = 4 x 768 slots exactly; 3.46 -> 3.30 ms per launch, 256^3 0.518 -> 0.482 ms (profiles/r10_symp_trim_ab_512.txt).
+//   * Constant steps (k_spmv_symp_const<B, DC>: the body below with CS = 1; the form is decided per bind, spc_form; symp_const_decide.h): on a uniform brick with dyadic spacing a
+//     constant-coefficient operator is assembled to bitwise identical rows, and every row of the benchmark's scaled matrix whose 27 neighbours are interior nodes
+//     holds the same 27 doubles.  k_symp_fill compares every value it forms with one reference row's (k_symp_const_ref), bit by bit, and flags the steps -- whole
+//     patches -- in which all of them match: a byte per step behind the rim copy (512^3: 62 x 14 of the 1024 patches in each of the 509 swept planes, 84.8 %).  A
+//     flagged step takes a path of its own: the next plane's x into the ring, then per band the 27 products with the reference row's values (27 doubles in the wave's LDS, read as broadcasts),
+//     rounded, then added, in slot order -- no matrix load, no mirror table, no edge block, two barriers per step instead of two per band.  Its own slots are the
+//     constants because the fill compared them, the mirrored ones because the bind's fingerprint found every pair among the swept rows bitwise equal and the
+//     reference row is its own mirror image (dia_bind asks both): y, the partial sums and every iterate are the stored form's bit for bit
+//     (tests/test_gpu_symp_const.py).  The tables are left stale, so an unflagged step behind a flagged one starts like a run; a run's flags come in one gathered
+//     load per 63 steps.  What it showed: with the constants merely put where the loads had put their values (the registers of the unchanged step body) the launch
+//     moved 5.3 instead of 18.45 GB and took as long as before, 3.33 against 3.35 ms -- a wave has its SIMD to itself and the step body's ~2500 instructions at
+//     4 cycles each ARE the 4.9 us of a step; the time follows the instructions of a step, not its bytes.  The path above is ~450 instructions.  Runs are rotated
+//     among an XCD's waves from round to round (spc_run) so that no wave keeps the first or last patch column, whose steps are never flagged.  512^3: 3.31 ->
+//     2.60 ms per launch (profiles/r12_symp_const_ab_512.txt).  At n = 511, on a 0.3 m box, or with variable conductivity, no step is flagged: the bind keeps the
+//     stored kernel and pays nothing.
 //   * Rows outside the swept planes (first / last lattice plane, the planes next to the ghost planes of a slab) come from the slot-major
 //     copy through the per-row code: the sweep's waves take them in 128-row units after their runs (unsplit SpMV: one launch, no tail);
 //     in a split (multi-rank) SpMV they are the boundary part, a launch of their own (k_spmv_dia_outside) after the halo has arrived.
@@ -294,16 +309,21 @@ __global__ __launch_bounds__(64) void k_symp_rim(SympGeom Gm, const double* __re
 // its next-plane entries of the previous plane (slots 0..2) in the tables -- the latter because band 0 holds its writes to the tables of slots 0..2 back
 // until the last band of the plane has read them.  A band with no valid line (the last patch row) is skipped wave-uniformly.
 // DC: form of the copy's main part (spmv_symp.h) -- 0 the diagonal stored as slot 13, 1 carried as one-byte codes counted from Gm.unit.
-template <int MODE, int B, int DC>
-__global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __restrict__ pv, const double* __restrict__ x,
-                                                   double* __restrict__ y, double alpha, double beta,
-                                                   const double* __restrict__ dotw, double* __restrict__ partials,
-                                                   const int32_t* __restrict__ done_flag, int32_t* __restrict__ bad, SympTail tail) {
+// CS: 1 = the constant form (symp_const_decide.h; MODE 0 only) -- a step whose byte in sflags is set is computed from the reference row cst alone.
+// The body of both kernels below: k_spmv_symp<MODE, B, DC> is CS = 0, k_spmv_symp_const<B, DC> is MODE 0 with CS = 1.
+template <int MODE, int B, int DC, int CS>
+__device__ __forceinline__ void symp_sweep(const SympGeom& Gm, const double* __restrict__ pv, const double* __restrict__ x,
+                                           double* __restrict__ y, double alpha, double beta,
+                                           const double* __restrict__ dotw, double* __restrict__ partials,
+                                           const int32_t* __restrict__ done_flag, int32_t* __restrict__ bad, const SympTail& tail, const SympConst& cst,
+                                           const uint32_t* __restrict__ sflags) {
+  static_assert(CS == 0 || MODE == 0, "the check pass reads the stored copy");
   constexpr int XL = sp_xl(B), XN = sp_xn(B), XU = sp_xu(B), NE = sp_ne(B), EU = sp_eu(B), MAINB = sp_main(B, DC), LOWB = sp_low(B);
   constexpr int NSL = sp_nslots(DC), S0 = 27 - NSL;  // slots S0..26 of a band are stored in its main part (DC = 1: the diagonal comes as a code)
   constexpr int BM = NSL * SP_ROWS, BL = 13 * SP_ROWS, BT = SP_L * SP_LS;  // a band's share of the main part, of the low part, of a table
   __shared__ __attribute__((aligned(16))) double xs[3][XL][SP_XW];
-  __shared__ __attribute__((aligned(16))) double tab[sp_tab(B) + 2];
+  __shared__ __attribute__((aligned(16))) double tab[sp_tab(B) + 2 + (CS ? 28 : 0)];  // CS: behind the tables and the spare cells the reference row's 27 values
+  double* const ctab = tab + sp_tab(B) + 2;
   if (done_flag && done_flag[0]) return;
   const int lane = threadIdx.x, lj = lane / SP_PW, pk = lane % SP_PW, lb0 = lj * SP_LS + 2 * pk;
   const int NP = Gm.NR * Gm.NPk, nplanes = Gm.p1 - Gm.p0;
@@ -316,6 +336,16 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
   int ecell[EU];
 #pragma unroll
   for (int u = 0; u < EU; ++u) ecell[u] = c_sp_ecell[B - 1][lane + 64 * u];
+  // the reference row goes to LDS once per launch (the barrier every run starts with orders it before the first read): 54 scalar registers held through the
+  // sweep spilled 117 of them into lanes and cost every UNFLAGGED step a quarter more (the 512-point lattice with the form forced: 4.01 against 3.17 ms)
+  if (CS && lane == 0) {
+#pragma unroll
+    for (int s = 0; s < 27; ++s) ctab[s] = cst.v[s];
+  }
+  // The flags of up to 64 consecutive steps of a run, lane i <-> step ft0 + i, in ONE gathered load per 63 steps: a scalar load per step showed its whole
+  // latency (the wave has its SIMD to itself, and a scalar load shares its counter with the LDS traffic of the step body).  A step's flag is read from its lane.
+  int fw = 0;
+  int64_t ft0 = 0;
   int cur_patch = -1, bp = 0, bc = 1, bn = 2;  // x ring: previous / current / next plane
   int nb = 1;            // bands of the patch with a valid line
   bool have_hist = false;
@@ -337,7 +367,8 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
     return idx < Gm.nx ? idx : Gm.nx - 1;
   };
   // the main part of band b of the step at v
-  auto request = [&](const double* v, int b) {
+  auto request = [&](const double* v, int b, bool fl) {
+    if (CS && fl) return;  // (wave-uniform) a flagged step reads no matrix value
     if (vxb[b]) {
 #pragma unroll
       for (int u = 0; u < NSL; ++u) cur[b][u] = SYM_LD(reinterpret_cast<const e_d2*>(v + b * BM + 2 * lane + u * SP_ROWS));
@@ -349,11 +380,13 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
     }
   };
   // the edge block of the step at v and the x neighbourhood of plane pnext
-  auto request_step = [&](const double* v, int pnext) {
+  auto request_step = [&](const double* v, int pnext, bool fl) {
     if (MODE == 0) {
+      if (!(CS && fl)) {
 #pragma unroll
-      for (int u = 0; u < EU - 1; ++u) ed[u] = SYM_LD(v + B * BM + lane + 64 * u);
-      ed[EU - 1] = lane < NE - 64 * (EU - 1) ? SYM_LD(v + B * BM + lane + 64 * (EU - 1)) : 0.0;
+        for (int u = 0; u < EU - 1; ++u) ed[u] = SYM_LD(v + B * BM + lane + 64 * u);
+        ed[EU - 1] = lane < NE - 64 * (EU - 1) ? SYM_LD(v + B * BM + lane + 64 * (EU - 1)) : 0.0;
+      }
 #pragma unroll
       for (int u = 0; u < XU - 1; ++u) xr[u] = x[xidx(pnext, u)];
       xr[XU - 1] = lane < XN - 64 * (XU - 1) ? x[xidx(pnext, XU - 1)] : 0.0;
@@ -365,7 +398,11 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
     for (int u = 0; u < XU - 1; ++u) dst[xa[u]] = x[xidx(plane, u)];
     if (lane < XN - 64 * (XU - 1)) dst[xa[XU - 1]] = x[xidx(plane, XU - 1)];
   };
-  for (int run = blockIdx.x >> 3; run < pcnt * Gm.nseg; run += gridDim.x >> 3) {
+  // round rk: the XCD's runs [W rk, W rk + W), rotated among its W waves from round to round (spc_run, symp_const_decide.h: a wave does not keep its patch column)
+  const int W = gridDim.x >> 3, jw = blockIdx.x >> 3, rot = spc_rot(Gm.NPk);
+  for (int rk = 0; W * rk < pcnt * Gm.nseg; ++rk) {
+  const int run = spc_run(W, jw, rk, rot);
+  if (run >= pcnt * Gm.nseg) continue;
   const int patch = pfirst + run % pcnt, seg = run / pcnt;
   const int64_t t0 = (int64_t)patch * nplanes + (int64_t)nplanes * seg / Gm.nseg, t1 = (int64_t)patch * nplanes + (int64_t)nplanes * (seg + 1) / Gm.nseg;
   cur_patch = -1;
@@ -374,6 +411,14 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
     const int64_t step = (int64_t)(p - Gm.p0) * NP + patch;  // [plane][patch]: the runs of a segment advance plane by plane together
     const double* v = pv + step * MAINB;                                         // per band slots 13..26, then the edge block of the step
     const double* vlow = pv + (int64_t)NP * nplanes * MAINB + step * LOWB;      // per band its slots 0..12
+    const bool more = t + 1 < t1 && p + 1 < Gm.p1;  // the next step continues this sweep
+    if (CS && (patch != cur_patch || t - ft0 >= 63)) {  // (wave-uniform)
+      ft0 = t;
+      const int64_t tl = t + lane, sl = (tl - (int64_t)patch * nplanes) * NP + patch;  // the step of the run's (t + lane)-th entry
+      fw = tl < t1 ? (int)((sflags[sl >> 2] >> (8 * (int)(sl & 3))) & 255u) : 0;
+    }
+    const bool fnow = CS && __builtin_amdgcn_readlane(fw, (int)(t - ft0)) != 0;
+    const bool fnext = CS && more && __builtin_amdgcn_readlane(fw, (int)(t + 1 - ft0)) != 0;
     if (patch != cur_patch) {  // wave-uniform: a run or a patch starts -- nothing was requested ahead, no history
       cur_patch = patch;
       const int j0 = (patch / Gm.NPk) * (SP_L * B), k0 = (patch % Gm.NPk) * SP_W;
@@ -397,15 +442,15 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
       __syncthreads();  // the previous patch's last products may still be reading the x ring
 #pragma unroll
       for (int b = 0; b < B; ++b)
-        if (b < nb) request(v, b);
-      request_step(v, p + 1);
+        if (b < nb) request(v, b, fnow);
+      request_step(v, p + 1, fnow);
       if (MODE == 0) {
         stage_x(bp, p - 1);
         stage_x(bc, p);
         // no history: the row's own previous-plane slots go where the mirror reads would look for them
 #pragma unroll
         for (int b = 0; b < B; ++b) {
-          if (b < nb) {
+          if (b < nb && !fnow) {
 #pragma unroll
             for (int s = 0; s < 9; ++s) {
               const e_d2 w = vxb[b] ? SYM_LD(reinterpret_cast<const e_d2*>(vlow + b * BL + 2 * lane + s * SP_ROWS)) : (e_d2){0.0, 0.0};
@@ -417,7 +462,73 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
         }
       }
     }
-    const bool more = t + 1 < t1 && p + 1 < Gm.p1;  // the next step continues this sweep
+    if (CS && fnow) {
+      // ---- a flagged step: whole patch, every row's 27 entries are the reference row's, bit for bit -- its own slots (compared by the fill) and therefore the
+      // mirrored ones (the bind's fingerprint: every pair among the swept rows is bitwise equal; dia_bind: cst.v[s] = cst.v[26 - s] bit for bit).
+      // No table, no edge block, no matrix load: the next plane's x into the ring, then per band the 27 products with the constants (a broadcast read of the wave's LDS copy) -- rounded,
+      // then added, in slot order, the sums the step body below forms.  The tables are left stale: an unflagged step behind a flagged one starts like a run.
+      {
+        double* dst = &xs[bn][0][0];
+#pragma unroll
+        for (int u = 0; u < XU - 1; ++u) dst[xa[u]] = xr[u];
+        if (lane < XN - 64 * (XU - 1)) dst[xa[XU - 1]] = xr[XU - 1];
+      }
+      __syncthreads();  // the ring's three planes are complete
+      if (more && fnext) request_step(v + (int64_t)NP * MAINB, p + 2, true);  // (x alone)
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        e_d2 acc = {0.0, 0.0};
+        double xself0 = 0.0, xself1 = 0.0;
+        auto crun = [&](int s, int buf, int dj, bool self) {
+#pragma clang fp contract(off)
+          const double* xp = &xs[buf][SP_L * b + lj + 1 + dj][2 * pk];
+          const e_d2 xa2 = *reinterpret_cast<const e_d2*>(xp), xb2 = *reinterpret_cast<const e_d2*>(xp + 2);
+          const double c0 = ctab[s], c1 = ctab[s + 1], c2 = ctab[s + 2];  // (every lane the same address: a broadcast read)
+          acc.x = acc.x + c0 * xa2.x;
+          acc.y = acc.y + c0 * xa2.y;
+          acc.x = acc.x + c1 * xa2.y;
+          acc.y = acc.y + c1 * xb2.x;
+          acc.x = acc.x + c2 * xb2.x;
+          acc.y = acc.y + c2 * xb2.y;
+          if (self) {
+            xself0 = xa2.y;
+            xself1 = xb2.x;
+          }
+        };
+        crun(0, bp, -1, false);
+        crun(3, bp, 0, false);
+        crun(6, bp, 1, false);
+        crun(9, bc, -1, false);
+        crun(12, bc, 0, true);
+        crun(15, bc, 1, false);
+        crun(18, bn, -1, false);
+        crun(21, bn, 0, false);
+        crun(24, bn, 1, false);
+        const int64_t r = (int64_t)p * Gm.PL + rin + (int64_t)(SP_L * b) * Gm.m2;
+        double y0 = alpha * acc.x, y1 = alpha * acc.y;
+        if (beta != 0.0) {
+          y0 += beta * y[r];
+          y1 += beta * y[r + 1];
+        }
+        __builtin_nontemporal_store((u_d2){y0, y1}, reinterpret_cast<u_d2*>(y + r));
+        if (dotw) {
+          if (dotw == x) {
+            dot_acc += y0 * xself0;
+            dot_acc += y1 * xself1;
+          } else {
+            dot_acc += y0 * dotw[r];
+            dot_acc += y1 * dotw[r + 1];
+          }
+        }
+      }
+      __syncthreads();  // every lane is done with the ring's oldest plane: the next step overwrites it
+      const int b_ = bp;
+      bp = bc;
+      bc = bn;
+      bn = b_;
+      if (!(more && fnext)) cur_patch = -1;  // the sweep ends, or an unflagged step follows: it starts like a run (requests, x ring, no history)
+      continue;
+    }
 #pragma unroll
     for (int b = 0; b < B; ++b) {   // (unrolled: the bands' registers are indexed at compile time)
     if (b < nb) {                   // wave-uniform
@@ -447,8 +558,8 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
     const int mcd = DC && MODE == 0 ? cdc[b] : 0;
     __syncthreads();  // one wave: orders its LDS writes before the reads of other lanes
     if (more) {  // this band of the next plane; with the plane's last band the next step's edge block and the x of the plane behind it
-      request(v + (int64_t)NP * MAINB, b);
-      if (lastb) request_step(v + (int64_t)NP * MAINB, p + 2);
+      request(v + (int64_t)NP * MAINB, b, fnext);
+      if (lastb) request_step(v + (int64_t)NP * MAINB, p + 2, fnext);
     }
     auto mirrored = [&](int s) -> e_d2 {
       const double* c = tab + sp_tbase(s, B) + (sp_dj(s) + sp_adj(s)) * SP_LS + sp_dk(s) + 2 + lb;
@@ -577,6 +688,22 @@ __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __r
     const double w = wave_reduce_sum(dot_acc);
     if (lane == 0) partials[blockIdx.x] = w;
   }
+}
+
+template <int MODE, int B, int DC>
+__global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __restrict__ pv, const double* __restrict__ x,
+                                                   double* __restrict__ y, double alpha, double beta,
+                                                   const double* __restrict__ dotw, double* __restrict__ partials,
+                                                   const int32_t* __restrict__ done_flag, int32_t* __restrict__ bad, SympTail tail) {
+  symp_sweep<MODE, B, DC, 0>(Gm, pv, x, y, alpha, beta, dotw, partials, done_flag, bad, tail, SympConst{}, nullptr);
+}
+template <int B, int DC>
+__global__ __launch_bounds__(64) void k_spmv_symp_const(SympGeom Gm, const double* __restrict__ pv, const double* __restrict__ x,
+                                                         double* __restrict__ y, double alpha, double beta,
+                                                         const double* __restrict__ dotw, double* __restrict__ partials,
+                                                         const int32_t* __restrict__ done_flag, SympTail tail, SympConst cst,
+                                                         const uint32_t* __restrict__ sflags) {
+  symp_sweep<0, B, DC, 1>(Gm, pv, x, y, alpha, beta, dotw, partials, done_flag, nullptr, tail, cst, sflags);
 }
 
 // patch-major copy of the swept planes from the slot-major copy: per step [plane - p0][patch] and band the slots 13..26, then the edge block (main
@@ -740,7 +867,11 @@ int64_t mfem_symp_steps(const mfem_csr_s* A, int B, int trim) {
 }
 int64_t mfem_symp_copy_doubles(const mfem_csr_s* A, int B, int trim) {
   const SympExt e = symp_ext(A, B, trim);
-  return mfem_symp_steps(A, B, trim) * sp_step(B) + spt_units((int64_t)spt_rim(A->symp_m1, A->symp_m2, e.ms1, e.ms2) * (A->symp_p1 - A->symp_p0)) * SPT_UNIT_DOUBLES;
+  return mfem_symp_steps(A, B, trim) * sp_step(B) + spt_units((int64_t)spt_rim(A->symp_m1, A->symp_m2, e.ms1, e.ms2) * (A->symp_p1 - A->symp_p0)) * SPT_UNIT_DOUBLES +
+         spc_flag_doubles(mfem_symp_steps(A, B, trim));
+}
+unsigned char* mfem_symp_flags_of(double* pvals, const SympGeom& G) {
+  return (unsigned char*)(pvals + (int64_t)G.NR * G.NPk * (G.p1 - G.p0) * sp_step(G.B, G.DC) + G.rim_units * SPT_UNIT_DOUBLES);
 }
 int64_t mfem_symp_swept_rows(const mfem_csr_s* A) {
   const SympExt e = symp_ext(A);
@@ -782,12 +913,22 @@ int64_t mfem_sym_entries(const mfem_context_s* ctx, const mfem_csr_s* A, DiaKern
     e += (28 * nv + sp_ne(B)) * nplanes + 18 * nv * nseg;
     codes += 2 * nv * nplanes;
   }
+  // the constant form reads neither the upper slots, the edge block nor the codes of a flagged step (a whole patch), and one flag byte per step
+  if (A->symp_vals ? A->symp_CS : A->symp_cs_last) {
+    const int64_t fl = A->symp_vals ? A->symp_flagged : A->symp_flagged_last;
+    e -= fl * spc_saved_entries(B) - spc_flag_doubles((int64_t)NP * nplanes);
+    codes -= fl * spc_saved_codes(B);
+  }
   // the coded form reads two bytes instead of two doubles of diagonal per valid lane pair and step (whole entries: rounded up)
   if (mfem_symp_coded(A)) e -= codes - (codes + 7) / 8;
   return e;
 }
 
-// the sweep's instantiation for a geometry: pass (MODE), bands, form of the diagonal
+// the sweep's instantiation for a geometry: pass (MODE), bands, form of the diagonal; the constant form (MODE 0 only)
+static auto symp_const_kernel(const SympGeom& G) {
+  if (G.DC) return G.B == 2 ? k_spmv_symp_const<2, 1> : k_spmv_symp_const<1, 1>;
+  return G.B == 2 ? k_spmv_symp_const<2, 0> : k_spmv_symp_const<1, 0>;
+}
 template <int MODE>
 static auto symp_kernel(const SympGeom& G) {
   if (G.DC) return G.B == 2 ? k_spmv_symp<MODE, 2, 1> : k_spmv_symp<MODE, 1, 1>;
@@ -802,9 +943,17 @@ extern "C" long long mfem_debug_symp_fingerprint_count(void) { return g_symp_fp_
 // check pass, as for the tile sweep.
 // *dc_refused: the copy has the coded form (G.DC) and the fill met a swept row whose scaled diagonal has no code (d_flags[18], beside the fingerprint): the
 // bind refills in the stored form and asks again.  *dneg: the unit its codes count from is -1.0 (d_flags[19]).
+// flags_made: the fill also left its count of constant steps (d_flags[SPC_COUNT_AT]) and their reference row (d_flags[SPC_REF_AT..]): *flagged, *cst come
+// back in the same copy as the fingerprint.
 int mfem_sym_verdict(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const double* buf, double* pvals, const SympGeom& G, bool direct, bool fp_made, bool* ok,
-                     bool* dc_refused, int* dneg) {
+                     bool* dc_refused, int* dneg, bool flags_made, SympConst* cst, int64_t* flagged) {
   int32_t* d_bad = ctx->d_flags + 9;
+  const size_t fp_ints = flags_made && k == DIA_SYMP ? MFEM_NFLAGS - 16 : 4;  // the fingerprint, the coded form's two flags (and the constant form's count and reference row)
+  auto read_const = [&]() {
+    if (!(flags_made && k == DIA_SYMP && cst && flagged)) return;
+    *flagged = ctx->h_flags[SPC_COUNT_AT];
+    memcpy(cst, ctx->h_flags + SPC_REF_AT, sizeof(SympConst));
+  };
   *dc_refused = false;
   *dneg = 0;
   if (k == DIA_SYMP) {
@@ -816,13 +965,14 @@ int mfem_sym_verdict(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const doub
       MFEM_CHECK_LAUNCH();
     }
     if (fp_made) {
-      MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 16, ctx->d_flags + 16, sizeof(unsigned long long) + 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+      MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 16, ctx->d_flags + 16, fp_ints * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
       MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
       unsigned long long fpv;
       memcpy(&fpv, ctx->h_flags + 16, sizeof(fpv));
       *ok = fpv == 0;
       *dc_refused = G.DC && ctx->h_flags[18] != 0;
       *dneg = G.DC && ctx->h_flags[19] != 0;
+      read_const();
       ++g_symp_fp_checks;
       return MFEM_OK;
     }
@@ -837,11 +987,12 @@ int mfem_sym_verdict(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const doub
                        A->sym_c0 * SYM_ROWS, A->sym_c1 * SYM_ROWS, A->sym_cls, d_bad);
   MFEM_CHECK_LAUNCH();
   MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 9, d_bad, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (k == DIA_SYMP && G.DC) MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 18, ctx->d_flags + 18, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (k == DIA_SYMP && (G.DC || flags_made)) MFEM_CHECK_HIP(hipMemcpyAsync(ctx->h_flags + 18, ctx->d_flags + 18, (fp_ints - 2) * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
   *ok = ctx->h_flags[9] == 0;
   *dc_refused = k == DIA_SYMP && G.DC && ctx->h_flags[18] != 0;
   *dneg = k == DIA_SYMP && G.DC && ctx->h_flags[19] != 0;
+  read_const();
   return MFEM_OK;
 }
 
@@ -867,8 +1018,17 @@ int mfem_sym_launch(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const SpmvA
     if (a.part.part == 0 && g_ell.symp_tail) tl = SympTail{1, A->ell_K, G.rim_units > 0, A->n, A->ell_npad, lo, hi, O, A->dia_flags, A->ell_cols, A->ell_vals};
     if (a.part.part != 2) {
       np = symp_grid(ctx, A);
-      hipLaunchKernelGGL(symp_kernel<0>(G), dim3(np), dim3(64), 0, ctx->stream, G, (const double*)A->symp_vals, a.x, a.y, a.alpha, a.beta, a.dotw,
-                         a.partials, a.done_flag, (int32_t*)nullptr, tl);
+      if (A->symp_CS) {
+        SympConst cst{};
+        memcpy(cst.v, A->symp_cst, sizeof(cst.v));
+        cst.code = A->symp_ccode;
+        cst.valid = 1;
+        hipLaunchKernelGGL(symp_const_kernel(G), dim3(np), dim3(64), 0, ctx->stream, G, (const double*)A->symp_vals, a.x, a.y, a.alpha, a.beta, a.dotw,
+                           a.partials, a.done_flag, tl, cst, (const uint32_t*)mfem_symp_flags_of(A->symp_vals, G));
+      } else {
+        hipLaunchKernelGGL(symp_kernel<0>(G), dim3(np), dim3(64), 0, ctx->stream, G, (const double*)A->symp_vals, a.x, a.y, a.alpha, a.beta, a.dotw,
+                           a.partials, a.done_flag, (int32_t*)nullptr, tl);
+      }
       MFEM_CHECK_LAUNCH();
     }
     if (a.part.part == 2 || (a.part.part == 0 && !tl.on)) {

@@ -60,6 +60,9 @@ __host__ __device__ constexpr int sp_epad(int B) { return 64 * sp_eu(B); }
 // row, bits(v) - bits(+-1.0): the unit is the bind's, +-1.0 with the sign of the first swept row's diagonal (sp_unit_bits).  Per band the 13
 // slots 14..26, then the edge block, then the code block: SP_ROWS bytes per band (byte = row of the band, band after band; 128 B bytes keep the next
 // step 16-byte aligned).  B = 2: 3744 instead of 3968 doubles per step.  DC = 0, the default, is the stored form.
+// Behind all main and low parts lies the rim copy of a trimmed sweep (symp_trim_decide.h) and behind that, where k_symp_fill made the copy, ONE BYTE PER STEP
+// [plane][patch], padded to whole doubles (symp_const_decide.h): 1 = every value of the step equals the bind's reference row's of the same slot, bit for bit.  The
+// copy itself is complete either way -- the constant form (CS = 1) of the sweep does not read the main part, the edge block or the codes of a flagged step.
 #define SP_ONE_BITS 0x3FF0000000000000ll  // bits(1.0)
 #define SP_CODE_MAX 127                   // a diagonal further than this many ulps from the unit (the other sign, zero, non-finite) refuses the coded form
 __host__ __device__ constexpr long long sp_unit_bits(int negative) { return negative ? (long long)(0xBFF0000000000000ull) : SP_ONE_BITS; }  // bits(-1.0) / bits(1.0)
