@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MFEM_ABI_VERSION 11
+#define MFEM_ABI_VERSION 12
 
 typedef enum {
   MFEM_OK = 0,
@@ -197,7 +197,8 @@ typedef enum {
   MFEM_PRECOND_JACOBI_RIGHT_COLNORM = 2,/* Pr_Jacobi!(normalized_by_column=true) */
   MFEM_PRECOND_MULTIGRID = 3        /* added (ABI 10): a geometric multigrid V-cycle, cg! on a hex-8 thermal brick operator (mfem_solve_operator; see
                                        mfem_brick_multigrid_create) or, ABI 11, on a hex-8 elasticity brick operator with a hierarchy of
-                                       mfem_brick_multigrid_create_elasticity attached */
+                                       mfem_brick_multigrid_create_elasticity attached or, ABI 12, on a hex-27 thermal brick operator with a
+                                       hierarchy of mfem_brick_multigrid_create_hex27 attached */
 } mfem_precond_kind;
 
 typedef enum {
@@ -841,6 +842,23 @@ int mfem_brick_multigrid_create(mfem_context ctx, uint64_t op, const mfem_multig
  * does not cover a singular operator), a diagonal of mixed sign or with a zero, a non-positive estimate.  MFEM_ERR_INVALID as for
  * mfem_brick_multigrid_create. */
 int mfem_brick_multigrid_create_elasticity(mfem_context ctx, uint64_t op, const mfem_multigrid_options* opts, uint64_t* mg /* [host] out */);
+/* Added (ABI 12).  The hierarchy for an operator of mfem_brick_operator_create_hex27: p-coarsening once, then the hex-8 thermal hierarchy.  Level 0 is
+ * the caller's hex-27 brick of (nx, ny, nz) elements on the lattice (2 nx + 1, 2 ny + 1, 2 nz + 1); level 1 exists whenever max_levels >= 2, for any
+ * element counts >= 1: a library-owned hex-8 brick with the SAME element counts, lengths and itg_order on the lattice (nx + 1, ny + 1, nz + 1), whose
+ * coordinates are the even lattice points (the corner nodes) of the hex-27 brick; from level 1 on the halving rule of mfem_brick_multigrid_create.  The
+ * lattices of levels 0 and 1 relate as two hex-8 levels do (mf = 2 mc - 1): the trilinear interpolation is the embedding Q1 in Q2 on the same mesh.
+ * mfem_multigrid_info keeps its layout and reports ELEMENT counts: on such a hierarchy nx[0] == nx[1], ny[0] == ny[1], nz[0] == nz[1]; bytes is
+ * exact (level 0 owns three vectors of (2 nx + 1)(2 ny + 1)(2 nz + 1) entries, padded).  The contract is mfem_brick_multigrid_create_elasticity's:
+ * attached, one per operator, destroyed with it, the handle goes to the same _setup, _apply, _info and _destroy, and the attached hierarchy IS the
+ * opt-in of MFEM_PRECOND_MULTIGRID on the operator.  The setup re-sends the caller's current thermal parameters to every hex-8 level, injects the
+ * coordinates level by level, and computes K_ii of level 0 with its sign by a plane sweep on the product's skeleton (the same bits on every run;
+ * mfem_brick_operator_diagonal and Pr_Jacobi! keep their kernel and their bits).  The thermal K is negative definite: sign = -1.
+ * MFEM_ERR_UNSUPPORTED with a message, nothing created, launched or written: a hex-8 thermal operator (it takes mfem_brick_multigrid_create), an
+ * elasticity operator (mfem_brick_multigrid_create_elasticity), a mesh operator; and here as at every setup and in the solve gate: a Nitsche term
+ * active, a rule with fewer than 3 Gauss points per direction (itg_order < 4: the under-integrated order-2 K keeps near-null modes that the hex-8
+ * coarse space does not hold -- on a CPU twin 111 iterations and a 25 % error where itg_order 5 needs 5), a diagonal of mixed sign or with a zero, a
+ * non-positive estimate.  MFEM_ERR_INVALID as for mfem_brick_multigrid_create. */
+int mfem_brick_multigrid_create_hex27(mfem_context ctx, uint64_t op, const mfem_multigrid_options* opts, uint64_t* mg /* [host] out */);
 /* Re-sends the fine operator's CURRENT parameters to every level, injects the coordinates, computes the diagonals, the sign and the estimates.
  * Synchronises the context stream.  MFEM_ERR_UNSUPPORTED: a Nitsche term active, a diagonal of mixed sign or with a zero. */
 int mfem_brick_multigrid_setup(mfem_context ctx, uint64_t mg);
@@ -850,7 +868,8 @@ int mfem_brick_multigrid_info(uint64_t mg, mfem_multigrid_info* info /* [host] o
 int mfem_brick_multigrid_destroy(uint64_t mg);
 /* mfem_solve_operator with precond = MFEM_PRECOND_MULTIGRID: only for a hex-8 thermal brick operator, or (ABI 11) a hex-8 elasticity brick operator
  * with a hierarchy of mfem_brick_multigrid_create_elasticity ATTACHED (that hierarchy is the opt-in: without one the solve is refused and the message
- * names the entry point; tau == 0 or penalty_faces == 0 is refused too), MFEM_SOLVER_CG, no left preconditioner, no
+ * names the entry point; tau == 0 or penalty_faces == 0 is refused too), or (ABI 12) a hex-27 thermal brick operator with a hierarchy of
+ * mfem_brick_multigrid_create_hex27 ATTACHED (the same opt-in; itg_order < 4 is refused too), MFEM_SOLVER_CG, no left preconditioner, no
  * communicator, no active Nitsche term -- every other combination, every other operator kind and mfem_solve answer MFEM_ERR_UNSUPPORTED with a reason
  * naming what is missing; nothing is launched, nothing is written.  On a thermal operator a solve creates a default hierarchy when none is attached;
  * every solve ALWAYS runs the setup first, inside solve_ms (where a Jacobi solve computes its diagonal): parameters re-sent and coordinates overwritten since the last solve can

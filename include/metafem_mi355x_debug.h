@@ -284,6 +284,9 @@ long long mfem_debug_rem_spmv_count(void);
 /* The transpose plan of mfem_spmv_csr_t / lsqr! (spmv_t.hip): returns 1 if the pattern holds one (bytes = its device bytes, build_ms = the host
  * time its build took, synchronised), 0 if not (both 0). */
 int mfem_debug_csr_tplan(mfem_csr A, int64_t* bytes /* [host] */, double* build_ms /* [host] */);
+/* K_ii of a brick operator WITH its sign, as the multigrid setup computes it (bop_signed_diagonal): d must hold the preset 0 on entry.  hex-27:
+ * the plane sweep of brick_operator_hex27_diagonal.hip. */
+int mfem_debug_brick_operator_signed_diagonal(mfem_context ctx, uint64_t op, double* d);
 /* The transfer kernels of a multigrid hierarchy (mfem_brick_multigrid_create) alone, between level `level` (fine) and level + 1 (coarse):
  * restriction == 0: out (fine lattice) = P in (coarse lattice); != 0: out (coarse) = P' in (fine).  Tests: against the sparse P of the twin. */
 int mfem_debug_brick_multigrid_transfer(mfem_context ctx, uint64_t mg, int32_t level, int32_t restriction, const double* in, double* out);

@@ -21,7 +21,7 @@ import LinearAlgebra
 
 # ---- library handle and error convention ---------------------------------------------------------------------------------
 const lib = get(ENV, "METAFEM_MI355X_LIB", joinpath(@__DIR__, "..", "metafem.jl_amd", "libmetafem_mi355x.so"))
-const ABI_VERSION = 11   # == MFEM_ABI_VERSION
+const ABI_VERSION = 12   # == MFEM_ABI_VERSION
 
 struct MFEMError <: Exception
     rc::Cint
@@ -58,7 +58,7 @@ ctx() = (isassigned(CTX) || (CTX[] = Context(0)); CTX[].h)
 # ---- struct mirrors of include/metafem_mi355x.h (isbits, C layout) ---------------------------------------------------------
 Base.@kwdef struct SolveOptions           # == mfem_solve_options
     method::Int32 = 2                     # 0 cg (new), 1 bicgstabl_GS!, 2 idrs!, 3 cgs2!, 4 gmres!, 5 cgs!, 6 tfqmr!, 7 lsqr!
-    precond::Int32 = 1                    # 0 Identity, 1 Pr_Jacobi!, 2 Pr_Jacobi!(normalized_by_column = true), 3 Pr_Multigrid! (cg! on a hex-8 thermal BrickOperator, or an elasticity one with brick_multigrid_elasticity attached)
+    precond::Int32 = 1                    # 0 Identity, 1 Pr_Jacobi!, 2 Pr_Jacobi!(normalized_by_column = true), 3 Pr_Multigrid! (cg! on a hex-8 thermal BrickOperator, or an elasticity / hex-27 one with brick_multigrid_elasticity / brick_multigrid_hex27 attached)
     l_or_s::Int32 = 0                     # the `s` kwarg (tfqmr!: checkiter)
     maxiter::Int32 = 2000
     max_pass::Int32 = 4
@@ -801,6 +801,17 @@ per control point.  Attaching it is what admits Pr_Multigrid! on the operator (n
 function brick_multigrid_elasticity(op::BrickOperator, opts::MultigridOptions = MultigridOptions())
     h = Ref{UInt64}(0)
     rc = ccall((:mfem_brick_multigrid_create_elasticity, lib), Cint, (Ptr{Cvoid}, UInt64, Ref{MultigridOptions}, Ref{UInt64}), ctx(), op.h, Ref(opts), h)
+    rc == -3 && return nothing
+    check(rc)
+    return BrickMultigrid(h[], op)
+end
+"The hierarchy of a hex-27 thermal brick operator (ABI 12): p-coarsening onto a library-owned hex-8 brick of the same elements (level 1, whenever
+max_levels >= 2), then the hex-8 thermal hierarchy; multigrid_info reports nx[1] == nx[2] (element counts).  Attaching it is what admits
+Pr_Multigrid! on the operator (no default hierarchy is made for hex-27).  `nothing`: refused (a hex-8 thermal, elasticity or mesh operator; an
+active Nitsche term; itg_order < 4)."
+function brick_multigrid_hex27(op::BrickOperator, opts::MultigridOptions = MultigridOptions())
+    h = Ref{UInt64}(0)
+    rc = ccall((:mfem_brick_multigrid_create_hex27, lib), Cint, (Ptr{Cvoid}, UInt64, Ref{MultigridOptions}, Ref{UInt64}), ctx(), op.h, Ref(opts), h)
     rc == -3 && return nothing
     check(rc)
     return BrickMultigrid(h[], op)

@@ -29,7 +29,7 @@ import torch
 from . import _lib
 from ._lib import (ElasticityParams, MetaFEMError, OpLayout, SolveOptions, SolveStats, ThermalParams, check, lib)
 
-__all__ = ["Context", "FEM_SpMat_CSR", "MeshOperator", "BrickOperator", "BrickMultigrid", "MultigridRefused", "Pr_Multigrid_", "multigrid_plan", "ElasticityBrickOperator", "Hex27BrickOperator", "BrickOperatorRefused", "brick_operator_refusal",
+__all__ = ["Context", "FEM_SpMat_CSR", "MeshOperator", "BrickOperator", "BrickMultigrid", "MultigridRefused", "Pr_Multigrid_", "multigrid_plan", "multigrid_plan_hex27", "ElasticityBrickOperator", "Hex27BrickOperator", "BrickOperatorRefused", "brick_operator_refusal",
            "brick_operator_hex27_refusal", "mul_", "tmul_", "dot", "nrm2", "axpby_", "FEM_rand", "normalized_norm",
            "iterative_Solve", "Brick", "make_Brick", "ThermalDomain", "ElasticityDomain", "MetaFEMError", "SolveStats",
            "cg_", "bicgstabl_GS_", "idrs_", "cgs2_", "gmres_", "cgs_", "tfqmr_", "lsqr_", "FACE_BITS"]
@@ -38,7 +38,7 @@ __all__ = ["Context", "FEM_SpMat_CSR", "MeshOperator", "BrickOperator", "BrickMu
 cg_, bicgstabl_GS_, idrs_, cgs2_, gmres_, cgs_, tfqmr_, lsqr_ = 0, 1, 2, 3, 4, 5, 6, 7
 Identity, Pr_Jacobi_, Pr_Jacobi_colnorm_ = 0, 1, 2
 Pr_Multigrid_ = 3  # a geometric multigrid V-cycle: cg_ on a hex-8 thermal BrickOperator (BrickOperator.multigrid), or on an ElasticityBrickOperator
-# to which ElasticityBrickOperator.multigrid() has attached a hierarchy (no default one is made for elasticity)
+# or a Hex27BrickOperator to which its multigrid() has attached a hierarchy (no default one is made for those two)
 Pl_Jacobi_, Pl_Jacobi_rownorm_ = 1, 2  # Pl_func selectors (02_Preconditioner.jl:155-168)
 
 # reference local face ids (ref_geometry/002_Initialization.jl:8): 1 z=0, 2 y=0, 3 x=L, 4 y=L, 5 x=0, 6 z=L
@@ -304,8 +304,8 @@ class BrickOperator:
     def multigrid(self, **opts) -> "BrickMultigrid":
         """The geometric multigrid hierarchy of this operator (mfem_brick_multigrid_create): one per operator, destroyed with it.  opts:
         smoother_degree, coarse_degree, smoothing_range, coarse_range, eig_steps, max_levels (0 or absent: the default).  Raises MultigridRefused for
-        an operator the hierarchy does not cover (hex-27, an active Nitsche term; an ElasticityBrickOperator builds its own three-field hierarchy and
-        refuses tau == 0 or no penalty face)."""
+        an operator the hierarchy does not cover (an active Nitsche term; an ElasticityBrickOperator builds its own three-field hierarchy and
+        refuses tau == 0 or no penalty face; a Hex27BrickOperator builds its own p-coarsened one and refuses a rule below itg_order 4)."""
         return BrickMultigrid(self, **opts)
 
     def close(self):
@@ -337,12 +337,21 @@ def multigrid_plan(n, max_levels: int = 12):
     return levels
 
 
+def multigrid_plan_hex27(n, max_levels: int = 12):
+    """The level plan of a hex-27 brick of (nx, ny, nz) elements (csrc/brick_multigrid_decide.h: mg_plan_hex27), in ELEMENT counts: level 0 is the
+    hex-27 brick on the lattice 2 n + 1, level 1 -- whenever max_levels >= 2 -- a hex-8 brick of the same elements on the lattice n + 1
+    (p-coarsening), then multigrid_plan's halving rule."""
+    first = tuple(int(v) for v in n)
+    return [first] + (multigrid_plan(first, max_levels - 1) if max_levels >= 2 else [])
+
+
 class BrickMultigrid:
-    """Geometric multigrid V-cycle of a hex-8 thermal BrickOperator or of an ElasticityBrickOperator (mfem_brick_multigrid_*,
-    csrc/brick_multigrid.hip): the preconditioner `iterative_Solve(op, None, b, tol, Sv_func=cg_, Pr_func=Pr_Multigrid_)` applies.  The operator
-    says which entry point creates it (ElasticityBrickOperator: mfem_brick_multigrid_create_elasticity, three field-major fields per lattice
-    point: apply() takes op.n = 3 * ncp entries).  A solve runs setup() itself, always; setup() and apply() are for a caller that uses the cycle
-    on its own."""
+    """Geometric multigrid V-cycle of a hex-8 thermal BrickOperator, of an ElasticityBrickOperator or of a Hex27BrickOperator
+    (mfem_brick_multigrid_*, csrc/brick_multigrid.hip): the preconditioner `iterative_Solve(op, None, b, tol, Sv_func=cg_, Pr_func=Pr_Multigrid_)`
+    applies.  The operator says which entry point creates it (ElasticityBrickOperator: mfem_brick_multigrid_create_elasticity, three field-major
+    fields per lattice point: apply() takes op.n = 3 * ncp entries; Hex27BrickOperator: mfem_brick_multigrid_create_hex27, level 1 is a hex-8
+    brick of the same elements, so info()["ne"][0] == info()["ne"][1]).  A solve runs setup() itself, always; setup() and apply() are for a
+    caller that uses the cycle on its own."""
 
     def __init__(self, op: "BrickOperator", **opts):
         unknown = set(opts) - {"smoother_degree", "coarse_degree", "smoothing_range", "coarse_range", "eig_steps", "max_levels"}
@@ -432,12 +441,19 @@ class Hex27BrickOperator(BrickOperator):
     """Matrix-free K of a hex-27 (order-2) thermal brick (mfem_brick_operator_create_hex27, csrc/brick_operator_hex27.hip): the matrix of
     Brick.assemble_thermal for the same parameters -- volume term, Robin faces, Nitsche fixed_faces -- evaluated from the coordinates by a row-owner
     sweep; n = ncp.  Made by Brick.thermal_operator_hex27; set_params, mul_, diagonal and iterative_Solve take it as they take a BrickOperator.
-    Raises BrickOperatorRefused for a hex-8 brick (Brick.thermal_operator covers it) and for a brick with a slab."""
+    Raises BrickOperatorRefused for a hex-8 brick (Brick.thermal_operator covers it) and for a brick with a slab.  multigrid(**opts) attaches a
+    hierarchy (mfem_brick_multigrid_create_hex27: p-coarsening onto a hex-8 brick of the same elements, then the hex-8 thermal hierarchy): with one
+    attached, and only then, iterative_Solve takes Pr_func = Pr_Multigrid_ with cg_; it raises MultigridRefused for an active Nitsche term and for a
+    rule with fewer than 3 Gauss points per direction (itg_order < 4: the under-integrated K keeps near-null modes the coarse space does not hold)."""
 
     def __init__(self, brick: "Brick", params: "ThermalParams"):
         self.ctx, self.brick = brick.ctx, brick  # (the library borrows the brick: kept alive here)
         self.n = brick.ncp
         self.nnz = 0
+        self._mg = None
+        # (BrickMultigrid asks the operator which entry point builds its hierarchy.  Set on the operator, not on the class: the class keeps answering
+        # hasattr(Hex27BrickOperator, "_multigrid_create") with False, which tests/test_brick_multigrid_elasticity_host.py pins)
+        self._multigrid_create = "mfem_brick_multigrid_create_hex27"
         self._h = C.c_uint64()
         rc = lib.mfem_brick_operator_create_hex27(self.ctx._h, brick._h, C.byref(params), C.byref(self._h))
         if rc == -3:  # MFEM_ERR_UNSUPPORTED: a brick the operator does not cover
@@ -558,7 +574,8 @@ def iterative_Solve(A, K_vals: Optional[torch.Tensor], residue: torch.Tensor, co
     without an active Nitsche term and without a communicator (anything else raises with the library's reason); the solve creates a default hierarchy
     when BrickOperator.multigrid has not made one and always runs its setup first (inside solve_ms); check_every and cg_variant are ignored.
     An ElasticityBrickOperator takes it under the same conditions once ElasticityBrickOperator.multigrid() has attached a hierarchy (that call is
-    the opt-in: without it the solve raises and the message names the entry point) and while tau != 0 on at least one penalty face.
+    the opt-in: without it the solve raises and the message names the entry point) and while tau != 0 on at least one penalty face; a
+    Hex27BrickOperator likewise once Hex27BrickOperator.multigrid() has attached one (refused with an active Nitsche term or itg_order < 4).
 
     Returns (delta_x, stats); delta_x is a NEW device vector like the reference's return value.
     """
@@ -928,16 +945,18 @@ class ThermalDomain:
         self.converge_tol = 1e-6
         self.linear_solver: Callable = lambda gf: iterative_Solve(gf.A, gf.K_total, gf.residue, gf.converge_tol,
                                                                    Sv_func=idrs_, maxiter=2000, max_pass=10, s=8)[0]
-        # multigrid = True (with matrix_free on a hex-8 brick, K symmetric): linear_solver is cg_ with the V-cycle as its preconditioner.  With fixed
-        # faces (K is nonsymmetric), on a hex-27 operator or on a domain that fell back to the assembled path the default solver stays, and
+        # multigrid = True (with matrix_free, K symmetric): linear_solver is cg_ with the V-cycle as its preconditioner; on a hex-27 operator
+        # (matrix_free = "any") the hierarchy is the p-coarsened one of Hex27BrickOperator.multigrid.  With fixed faces (K is nonsymmetric), on a
+        # hex-27 brick with a rule below itg_order 4 or on a domain that fell back to the assembled path the default solver stays, and
         # multigrid_reason says why.
         self.multigrid, self.multigrid_reason = False, None
         if multigrid:
             if not self.matrix_free:
                 self.multigrid_reason = "the domain holds an assembled matrix (" + (self.matrix_free_reason or "matrix_free was not asked for") + \
-                                        "): the multigrid preconditioner needs the matrix-free hex-8 operator"
-            elif hex27:
-                self.multigrid_reason = "a hex-27 operator: the multigrid preconditioner covers the hex-8 thermal brick operator"
+                                        "): the multigrid preconditioner needs a matrix-free brick operator"
+            elif hex27 and brick.itg_order < 4:
+                self.multigrid_reason = "a hex-27 brick with fewer than 3 Gauss points per direction (itg_order < 4): the under-integrated K keeps " \
+                                        "near-null modes that the hex-8 coarse space of the multigrid preconditioner does not hold"
             elif fixed_faces and (h_penalty != 0.0 or k != 0.0):
                 self.multigrid_reason = "fixed_faces make K nonsymmetric: the multigrid preconditioner needs cg_"
             else:

@@ -273,9 +273,11 @@ SIGNATURES = {
     "mfem_brick_operator_apply": (c_int, [P, c_uint64, P, P, c_double, c_double]),
     "mfem_brick_operator_diagonal": (c_int, [P, c_uint64, P]),
     "mfem_debug_brick_operator_count": (c_int64, []),
+    "mfem_debug_brick_operator_signed_diagonal": (c_int, [P, c_uint64, P]),
     "mfem_debug_brick_operator_apply_dot": (c_int, [P, c_uint64, P, P, c_double, c_double, P, P, C.POINTER(c_int32)]),
     "mfem_brick_multigrid_create": (c_int, [P, c_uint64, C.POINTER(MultigridOptions), C.POINTER(c_uint64)]),
     "mfem_brick_multigrid_create_elasticity": (c_int, [P, c_uint64, C.POINTER(MultigridOptions), C.POINTER(c_uint64)]),
+    "mfem_brick_multigrid_create_hex27": (c_int, [P, c_uint64, C.POINTER(MultigridOptions), C.POINTER(c_uint64)]),
     "mfem_brick_multigrid_setup": (c_int, [P, c_uint64]),
     "mfem_brick_multigrid_apply": (c_int, [P, c_uint64, P, P]),
     "mfem_brick_multigrid_info": (c_int, [c_uint64, C.POINTER(MultigridInfo)]),

@@ -9,7 +9,7 @@ struct mfem_brick_multigrid_s;
 // (host only: nothing is launched, nothing is written)
 int mfem_mg_solve_check(mfem_context_s* ctx, mfem_operator_head* op, const mfem_solve_options* o);
 // the hierarchy attached to the operator; a default one is created and attached when there is none (before the solve takes its workspace; thermal
-// only: the gate admits an elasticity operator only with its own hierarchy attached)
+// only: the gate admits an elasticity or a hex-27 operator only with its own hierarchy attached)
 int mfem_mg_attach_default(mfem_context_s* ctx, mfem_operator_head* op);
 // the setup of the attached hierarchy, inside solve_ms (the operator is not bound yet)
 int mfem_mg_setup_attached(mfem_context_s* ctx, mfem_operator_head* op);

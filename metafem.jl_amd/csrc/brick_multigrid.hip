@@ -1,4 +1,4 @@
-// Geometric multigrid V-cycle on hex-8 thermal and elasticity bricks: the preconditioner behind MFEM_PRECOND_MULTIGRID (cg! on the matrix-free brick operator;
+// Geometric multigrid V-cycle on hex-8 thermal and elasticity bricks and on hex-27 thermal bricks: the preconditioner behind MFEM_PRECOND_MULTIGRID (cg! on the matrix-free brick operator;
 // the pass: krylov_cg_mg.hip).  The hierarchy of an (nx, ny, nz) brick is the bricks (nx/2, ny/2, nz/2), ...: library-owned mfem_bricks whose
 // coordinates are injected from the next finer level at every setup, with a brick operator each (rediscretisation: the caller's parameters on the
 // coarse brick).  Everything is made of that operator's product and diagonal and of the kernels below; no matrix, no pattern, no atomic.
@@ -15,6 +15,10 @@
 // An elasticity hierarchy (mfem_brick_multigrid_create_elasticity) carries three field-major fields per lattice point: a level vector holds
 // fields x points entries, the transfers are the <NF = 3> instantiations (one launch, a thread per lattice point looping over the fields: P is
 // I_3 (x) the scalar P), the coarse operators are mfem_brick_operator_create_elasticity's, and everything elementwise runs on n = fields x points.
+// A hex-27 hierarchy (mfem_brick_multigrid_create_hex27) is p-coarsened once: level 0 is the caller's order-2 brick on the lattice 2 ne + 1, level 1 a
+// hex-8 brick of the SAME elements on ne + 1 -- mf = 2 mc - 1 as between two hex-8 levels, so k_mg_inject (the corner nodes), k_mg_restrict<1> and
+// k_mg_prolong<1> (the embedding Q1 in Q2) serve unchanged -- and the thermal h-hierarchy follows; level 0's signed diagonal is the plane sweep of
+// brick_operator_hex27_diagonal.hip, its product bop27_launch through the operator interface.
 #include <memory>
 #include "brick_operator.h"
 #include "brick_multigrid.h"
@@ -65,7 +69,12 @@ static int mg_refuse_elasticity(const char* why) {
   mfem_set_error("multigrid on the hex-8 elasticity brick operator: %s", why);
   return MFEM_ERR_UNSUPPORTED;
 }
+static int mg_refuse_hex27(const char* why) {
+  mfem_set_error("multigrid on the hex-27 thermal brick operator: %s", why);
+  return MFEM_ERR_UNSUPPORTED;
+}
 static bool mg_is_elasticity(const mfem_brick_operator_s* op) { return op->physics == BOP_PHYSICS_ELASTICITY; }
+static bool mg_is_hex27(const mfem_brick_operator_s* op) { return op->physics == BOP_PHYSICS_HEX27; }
 
 // ---- kernels -------------------------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool mg_point(int m1, int m2, int& i, int& j, int& k) {
@@ -351,7 +360,8 @@ void mfem_mg_release(mfem_brick_multigrid_s* mg) {
 
 static int mg_create(mfem_context_s* ctx, mfem_brick_operator_s* op, const MgOptions& opt, mfem_brick_multigrid_s** out) {
   const mfem_brick_s* fb = op->brick;
-  const MgPlan P = mg_plan(fb->ne[0], fb->ne[1], fb->ne[2], opt.max_levels);
+  const bool hex27 = mg_is_hex27(op);  // level 0 on the lattice 2 ne + 1, a hex-8 brick of the same elements below it (mg_plan_hex27)
+  const MgPlan P = hex27 ? mg_plan_hex27(fb->ne[0], fb->ne[1], fb->ne[2], opt.max_levels) : mg_plan(fb->ne[0], fb->ne[1], fb->ne[2], opt.max_levels);
   const int fields = mg_is_elasticity(op) ? MG_ELASTICITY_FIELDS : 1;
   mfem_host_alloc_probe();
   mfem_brick_multigrid_s* mg = new mfem_brick_multigrid_s();
@@ -366,11 +376,11 @@ static int mg_create(mfem_context_s* ctx, mfem_brick_operator_s* op, const MgOpt
       MgLevel& L = mg->lev[l];
       for (int d = 0; d < 3; ++d) {
         L.ne[d] = P.ne[l][d];
-        L.m[d] = P.ne[l][d] + 1;
+        L.m[d] = hex27 ? mg_lattice_hex27(l, P.ne[l][d]) : P.ne[l][d] + 1;
       }
       L.fields = fields;
-      L.points = mg_points(L.ne);
-      L.n = mg_level_entries(fields, L.ne);
+      L.points = hex27 ? mg_points_hex27(l, L.ne) : mg_points(L.ne);
+      L.n = (int64_t)fields * L.points;
       L.npad = mg_padded(L.n);
       if (l == 0) {
         L.brick = op->brick;
@@ -405,7 +415,7 @@ static int mg_create(mfem_context_s* ctx, mfem_brick_operator_s* op, const MgOpt
     mfem_mg_release(mg);
     return rc;
   }
-  mg->bytes = mg_bytes_fields(P, fields);
+  mg->bytes = hex27 ? mg_bytes_hex27(P) : mg_bytes_fields(P, fields);
   mg->fine = op;
   op->mg = mg;
   *out = mg;
@@ -421,10 +431,13 @@ static int mg_setup(mfem_context_s* ctx, mfem_brick_multigrid_s* mg) {
   if (elasticity) {
     const char* why = mg_elasticity_refusal(fine->elasticity.tau, fine->elasticity.penalty_faces);
     if (why) return mg_refuse_elasticity(why);
+  } else if (mg_is_hex27(fine)) {
+    const char* why = mg_hex27_refusal(fine->brick->ng, mg_nitsche(fine));
+    if (why) return mg_refuse_hex27(why);
   } else if (mg_nitsche(fine)) {
     return mg_refuse("a Nitsche (fixed_faces) term is active: K is not symmetric");
   }
-  const auto refuse = elasticity ? mg_refuse_elasticity : mg_refuse;
+  const auto refuse = elasticity ? mg_refuse_elasticity : mg_is_hex27(fine) ? mg_refuse_hex27 : mg_refuse;
   for (int l = 0; l < mg->nlev; ++l) MFEM_REQUIRE(!mg->lev[l].op->csr.op, "a level's operator is bound to a running solve");
   const mfem_brick_s* fb = fine->brick;
   MFEM_REQUIRE(fb->ne[0] == mg->lev[0].ne[0] && fb->ne[1] == mg->lev[0].ne[1] && fb->ne[2] == mg->lev[0].ne[2] && fb->plo == 0 && fb->phi == fb->m[0],
@@ -494,8 +507,13 @@ int mfem_mg_solve_check(mfem_context_s* ctx, mfem_operator_head* head, const mfe
   const mfem_brick_operator_s* op = brick ? (const mfem_brick_operator_s*)head : nullptr;
   const bool thermal = op && op->physics == BOP_PHYSICS_THERMAL;
   const bool elasticity = op && mg_is_elasticity(op);
-  const char* why = mg_solve_refusal_fields(brick, thermal, elasticity, op && op->mg != nullptr, o->method, o->left_precond, ctx->comm != nullptr,
-                                            thermal && mg_nitsche(op));
+  const bool hex27 = op && mg_is_hex27(op);
+  const char* why = mg_solve_refusal_hex27(brick, thermal, elasticity, hex27, op && op->mg != nullptr, o->method, o->left_precond, ctx->comm != nullptr,
+                                           (thermal || hex27) && mg_nitsche(op));
+  if (!why && hex27) {  // (the setup inside the solve would refuse it: answered here, before anything is launched)
+    why = mg_hex27_refusal(op->brick->ng, false);
+    if (why) return mg_refuse_hex27(why);
+  }
   if (!why && elasticity) {  // (the setup inside the solve would refuse it: answered here, before anything is launched)
     why = mg_elasticity_refusal(op->elasticity.tau, op->elasticity.penalty_faces);
     if (why) return mg_refuse_elasticity(why);
@@ -536,7 +554,8 @@ extern "C" int mfem_brick_multigrid_create(mfem_context ctx, uint64_t handle, co
   mfem_brick_operator_s* op = bop_from_handle(handle);
   MFEM_REQUIRE(op, "not an operator's handle");
   if (op->physics != BOP_PHYSICS_THERMAL)
-    return mg_refuse("elasticity and hex-27 operators are not covered (a hex-8 elasticity operator takes mfem_brick_multigrid_create_elasticity)");
+    return mg_refuse("elasticity and hex-27 operators are not covered (a hex-8 elasticity operator takes mfem_brick_multigrid_create_elasticity, a hex-27 "
+                     "thermal operator mfem_brick_multigrid_create_hex27)");
   MFEM_REQUIRE(op->ctx == ctx, "the operator was created on another context");
   MFEM_REQUIRE(!op->mg, "the operator already has a hierarchy (one per operator: destroy it first)");
   MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
@@ -564,7 +583,7 @@ extern "C" int mfem_brick_multigrid_create_elasticity(mfem_context ctx, uint64_t
   mfem_brick_operator_s* op = bop_from_handle(handle);
   MFEM_REQUIRE(op, "not an operator's handle");
   if (op->physics == BOP_PHYSICS_THERMAL) return mg_refuse_elasticity("a hex-8 thermal operator's handle: it takes mfem_brick_multigrid_create");
-  if (!mg_is_elasticity(op)) return mg_refuse_elasticity("a hex-27 operator's handle: hex-27 operators are not covered");
+  if (!mg_is_elasticity(op)) return mg_refuse_elasticity("a hex-27 operator's handle: it takes mfem_brick_multigrid_create_hex27");
   MFEM_REQUIRE(op->ctx == ctx, "the operator was created on another context");
   MFEM_REQUIRE(!op->mg, "the operator already has a hierarchy (one per operator: destroy it first)");
   MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
@@ -582,6 +601,37 @@ extern "C" int mfem_brick_multigrid_create_elasticity(mfem_context ctx, uint64_t
   *out = (uint64_t)(uintptr_t)mg;
   return MFEM_OK;
 } MFEM_API_CATCH("mfem_brick_multigrid_create_elasticity")
+
+// The hierarchy of a hex-27 thermal operator: p-coarsening once onto a hex-8 brick of the same elements, then the thermal h-hierarchy.  The contract is
+// mfem_brick_multigrid_create_elasticity's (attached, one per operator, destroyed with it; the attached hierarchy is the opt-in).
+extern "C" int mfem_brick_multigrid_create_hex27(mfem_context ctx, uint64_t handle, const mfem_multigrid_options* opts, uint64_t* out) try {
+  MFEM_REQUIRE(out, "null out");
+  *out = 0;
+  mfem_operator_head* head = (mfem_operator_head*)(uintptr_t)handle;
+  MFEM_REQUIRE(ctx && head, "null argument");
+  if (head->kind == MFEM_OPERATOR_MESH) return mg_refuse_hex27("a mesh operator's handle: the hierarchy is built on the lattice of a brick");
+  mfem_brick_operator_s* op = bop_from_handle(handle);
+  MFEM_REQUIRE(op, "not an operator's handle");
+  if (op->physics == BOP_PHYSICS_THERMAL) return mg_refuse_hex27("a hex-8 thermal operator's handle: it takes mfem_brick_multigrid_create");
+  if (mg_is_elasticity(op)) return mg_refuse_hex27("a hex-8 elasticity operator's handle: it takes mfem_brick_multigrid_create_elasticity");
+  MFEM_REQUIRE(mg_is_hex27(op), "not a hex-27 thermal brick operator's handle");
+  MFEM_REQUIRE(op->ctx == ctx, "the operator was created on another context");
+  MFEM_REQUIRE(!op->mg, "the operator already has a hierarchy (one per operator: destroy it first)");
+  MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
+  const char* why = mg_hex27_refusal(op->brick->ng, mg_nitsche(op));
+  if (why) return mg_refuse_hex27(why);
+  MgOptions opt;
+  const char* bad = mg_options(opts, &opt);
+  if (bad) {
+    mfem_set_error("mfem_brick_multigrid_create_hex27: %s", bad);
+    return MFEM_ERR_INVALID;
+  }
+  mfem_brick_multigrid_s* mg = nullptr;
+  const int rc = mg_create(ctx, op, opt, &mg);
+  if (rc) return rc;
+  *out = (uint64_t)(uintptr_t)mg;
+  return MFEM_OK;
+} MFEM_API_CATCH("mfem_brick_multigrid_create_hex27")
 
 static int mg_target(mfem_context ctx, uint64_t handle, mfem_brick_multigrid_s** out) {
   mfem_brick_multigrid_s* mg = mg_from_handle(handle);

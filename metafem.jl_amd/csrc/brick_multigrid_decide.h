@@ -2,7 +2,7 @@
 // alone: the level plan, the options' defaults and their refusals, the Chebyshev coefficients, the grids and tiles of the transfer kernels, how many
 // vectors a level owns, the device bytes of a hierarchy, the products of a cycle and of a pass, and which solves take the preconditioner.  Plain
 // integers in, plain structs out; no HIP, no context: tools/host_check_brick_multigrid.cpp walks them on the CPU (the field-aware forms at the end:
-// tools/host_check_brick_multigrid_elasticity.cpp).
+// tools/host_check_brick_multigrid_elasticity.cpp; the hex-27 forms behind them: tools/host_check_brick_multigrid_hex27.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -213,4 +213,62 @@ static inline const char* mg_solve_refusal_fields(bool brick_operator, bool ther
     return "the multigrid preconditioner runs on a hex-8 elasticity brick operator only with a hierarchy attached: create one with "
            "mfem_brick_multigrid_create_elasticity (no default hierarchy is made for elasticity)";
   return mg_solve_refusal(true, true, method, left_precond, has_comm, false);
+}
+
+// ---- the hex-27 thermal hierarchy (mfem_brick_multigrid_create_hex27): p-coarsening once, then the h-hierarchy above -----------------------------------
+// Level 0 is the caller's hex-27 brick of (nx, ny, nz) elements on the lattice (2 nx + 1, 2 ny + 1, 2 nz + 1); level 1 -- whenever max_levels >= 2, for
+// any element counts >= 1 -- is a library-owned hex-8 brick with the SAME element counts, lengths and rule on the lattice (nx + 1, ny + 1, nz + 1), so
+// mf = 2 mc - 1 as between two hex-8 levels: the trilinear P of k_mg_prolong<1> is the embedding Q1 in Q2 on the same mesh, k_mg_restrict<1> its
+// transpose, and k_mg_inject takes the hex-27 corner nodes (the even lattice points) as the hex-8 coordinates.  From level 1 on mg_plan's halving rule.
+// MgPlan.ne holds ELEMENT counts on every level: ne[0] == ne[1] on such a plan, and the lattice of level 0 is mg_lattice_hex27's.
+static inline MgPlan mg_plan_hex27(int nx, int ny, int nz, int max_levels) {
+  if (max_levels < 1 || max_levels > MG_MAX_LEVELS) max_levels = MG_MAX_LEVELS;
+  MgPlan P;
+  P.nlev = 1;
+  P.ne[0][0] = nx; P.ne[0][1] = ny; P.ne[0][2] = nz;
+  if (max_levels < 2) return P;
+  const MgPlan H = mg_plan(nx, ny, nz, max_levels - 1);  // the hex-8 brick of the same elements and what lies below it
+  for (int l = 0; l < H.nlev; ++l)
+    for (int d = 0; d < 3; ++d) P.ne[1 + l][d] = H.ne[l][d];
+  P.nlev = 1 + H.nlev;
+  return P;
+}
+// lattice points per direction of a level: 2 ne + 1 on the hex-27 level 0, ne + 1 on every hex-8 level
+static inline int mg_lattice_hex27(int level, int ne) { return level == 0 ? 2 * ne + 1 : ne + 1; }
+static inline int64_t mg_points_hex27(int level, const int* ne) {
+  return (int64_t)mg_lattice_hex27(level, ne[0]) * mg_lattice_hex27(level, ne[1]) * mg_lattice_hex27(level, ne[2]);
+}
+// the bytes of a level that knows the level-0 lattice: level 0 owns its three scratch vectors of (2 nx + 1)(2 ny + 1)(2 nz + 1) entries, a hex-8 level
+// what mg_level_bytes counts
+static inline int64_t mg_level_bytes_hex27(int level, const int* ne) {
+  if (level > 0) return mg_level_bytes(level, ne);
+  return (int64_t)mg_level_vectors(0) * mg_padded(mg_points_hex27(0, ne)) * 8;
+}
+static inline int64_t mg_bytes_hex27(const MgPlan& P) {
+  int64_t b = MG_FLAG_BYTES;
+  for (int l = 0; l < P.nlev; ++l) b += mg_level_bytes_hex27(l, P.ne[l]);
+  return b;
+}
+static inline int64_t mg_cycle_stream_bytes_hex27(int level, int nlev, int nu, int nu_c, const int* ne) {
+  return (int64_t)mg_cycle_streams(level, nlev, nu, nu_c) * 8 * mg_points_hex27(level, ne);
+}
+// what the hex-27 hierarchy refuses beside the thermal rows (create, every setup, the solve gate): a rule with fewer than 3 Gauss points per direction
+#define MG_HEX27_MIN_NG 3
+static inline const char* mg_hex27_refusal(int ng, bool nitsche_on) {
+  if (nitsche_on) return "a Nitsche (fixed_faces) term is active: K is not symmetric";
+  if (ng < MG_HEX27_MIN_NG)
+    return "a rule with fewer than 3 Gauss points per direction (itg_order < 4): the under-integrated order-2 K keeps near-null modes that the "
+           "hex-8 coarse space does not hold";
+  return nullptr;
+}
+// mg_solve_refusal_fields with the hex-27 thermal operator admitted when a hierarchy of mfem_brick_multigrid_create_hex27 is attached to it (the
+// hierarchy is the opt-in: no default one is created); every other row answers as mg_solve_refusal_fields does
+static inline const char* mg_solve_refusal_hex27(bool brick_operator, bool thermal_hex8, bool elasticity_hex8, bool thermal_hex27, bool hierarchy_attached,
+                                                 int method, int left_precond, bool has_comm, bool nitsche_on) {
+  if (!brick_operator || !thermal_hex27 || thermal_hex8 || elasticity_hex8)
+    return mg_solve_refusal_fields(brick_operator, thermal_hex8, elasticity_hex8, hierarchy_attached, method, left_precond, has_comm, nitsche_on);
+  if (!hierarchy_attached)
+    return "the multigrid preconditioner runs on a hex-27 thermal brick operator only with a hierarchy attached: create one with "
+           "mfem_brick_multigrid_create_hex27 (no default hierarchy is made for hex-27)";
+  return mg_solve_refusal(true, true, method, left_precond, has_comm, nitsche_on);
 }

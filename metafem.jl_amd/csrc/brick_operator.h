@@ -1,5 +1,5 @@
 // What the files of the matrix-free brick operator share: brick_operator.hip (the handle, the entry points, the hex-8 thermal kernels),
-// brick_operator_elasticity.hip (the hex-8 elasticity kernels and their launchers) and brick_operator_hex27.hip (the hex-27 thermal kernels and theirs).  The library is one code object per .hip file and a kernel is launched
+// brick_operator_elasticity.hip (the hex-8 elasticity kernels and their launchers), brick_operator_hex27.hip (the hex-27 thermal kernels and theirs) and brick_operator_hex27_diagonal.hip (the hex-27 signed diagonal).  The library is one code object per .hip file and a kernel is launched
 // from the file that defines it, so the device functions here are inline copies per file; the reference tables have ONE owner (bop_tables,
 // brick_operator.hip), and the handle's launch and diagonal hand an elasticity operator over to bop_elasticity_launch / bop_elasticity_jacobi.
 #pragma once
@@ -78,11 +78,12 @@ struct mfem_brick_operator_s {
   int ng;                   // the brick's rule when the operator was created
   const double* seen_x0;    // the brick's first coordinate array at the last bind (a change starts a new epoch of the cycle-graph key)
   mfem_csr_s csr;           // pattern-less: what the Krylov loop holds in place of a matrix (n = fields x control points)
-  struct mfem_brick_multigrid_s* mg;  // the multigrid hierarchy attached to a hex-8 thermal or elasticity operator (brick_multigrid.hip), or nullptr; destroyed with the operator
+  struct mfem_brick_multigrid_s* mg;  // the multigrid hierarchy attached to a hex-8 thermal or elasticity or a hex-27 thermal operator (brick_multigrid.hip), or nullptr; destroyed with the operator
 };
 mfem_brick_operator_s* bop_from_handle(uint64_t handle);  // brick_operator.hip: nullptr unless the handle is a brick operator's
-// diag K of a hex-8 thermal or elasticity operator WITH its sign (d_i <- K_ii where K_ii != 0; a zero diagonal keeps the caller's preset; elasticity:
-// 3 x control points entries, field-major): what the multigrid setup reads the sign of K from
+// diag K of a hex-8 thermal or elasticity or of a hex-27 thermal operator WITH its sign (d_i <- K_ii where K_ii != 0; a zero diagonal keeps the
+// caller's preset -- hex-27: is written as 0, which is what the multigrid setup presets; elasticity: 3 x control points entries, field-major): what the
+// multigrid setup reads the sign of K from
 int bop_signed_diagonal(mfem_context_s* ctx, mfem_brick_operator_s* op, double* d);
 void mfem_mg_release(struct mfem_brick_multigrid_s* mg);  // brick_multigrid.hip: frees a hierarchy (its operator is being destroyed, or it is destroyed on its own)
 
@@ -105,3 +106,7 @@ int bop27_prepare(int ng);
 int bop27_launch(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, const double* x, const double* dsc, double* y, double alpha,
                  double beta, const double* dotw, double* partials, int* n_partials, const int32_t* done_flag);
 int bop27_jacobi(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, double* d);
+// brick_operator_hex27_diagonal.hip: K_ii itself for EVERY control point (a zero diagonal is written as 0), as a plane sweep on the product's skeleton
+// (bop_signed_diagonal: the multigrid setup); bop27_diagonal_prepare raises that kernel's dynamic-LDS limit beside bop27_prepare
+int bop27_signed_diagonal(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, double* d);
+int bop27_diagonal_prepare(int ng);

@@ -530,11 +530,13 @@ static int bop_jacobi(mfem_context_s* ctx, mfem_brick_operator_s* op, double* d)
   return MFEM_OK;
 }
 int bop_signed_diagonal(mfem_context_s* ctx, mfem_brick_operator_s* op, double* d) {
-  MFEM_REQUIRE(op->physics == BOP_PHYSICS_THERMAL || op->physics == BOP_PHYSICS_ELASTICITY, "the signed diagonal exists for the hex-8 operators");
+  MFEM_REQUIRE(op->physics == BOP_PHYSICS_THERMAL || op->physics == BOP_PHYSICS_ELASTICITY || op->physics == BOP_PHYSICS_HEX27,
+               "the signed diagonal exists for the brick operators");
   BrickView B;
   const int rc = bop_view(op, &B);
   if (rc) return rc;
   if (op->physics == BOP_PHYSICS_ELASTICITY) return bop_elasticity_signed_diagonal(ctx, op, B, d);  // (3 x control points entries, field-major)
+  if (op->physics == BOP_PHYSICS_HEX27) return bop27_signed_diagonal(ctx, op, B, d);  // (the plane sweep of brick_operator_hex27_diagonal.hip)
   const int64_t grid = bop_diagonal_grid(B.n_owned);
   MFEM_REQUIRE(grid < ((int64_t)1 << 31), "too many control points for one launch");
   hipLaunchKernelGGL(k_brick_diagonal<true>, dim3((unsigned)grid), dim3(MFEM_BLOCK), 0, ctx->stream, B, bop_thermal(op), d);
@@ -586,6 +588,7 @@ static int bop_create(mfem_context ctx, mfem_brick m, int physics, const void* p
   const Hex27Tables* tables27 = nullptr;
   int rct = physics == BOP_PHYSICS_HEX27 ? bop27_tables(ctx->device, m->ng, &tables27) : bop_tables(ctx->device, m->ng, &tables);
   if (!rct && physics == BOP_PHYSICS_HEX27) rct = bop27_prepare(m->ng);
+  if (!rct && physics == BOP_PHYSICS_HEX27) rct = bop27_diagonal_prepare(m->ng);
   if (rct) return rct;
   mfem_host_alloc_probe();
   std::unique_ptr<mfem_brick_operator_s> op(new mfem_brick_operator_s());
@@ -695,6 +698,14 @@ extern "C" int mfem_debug_brick_operator_apply_dot(mfem_context ctx, uint64_t ha
   *n_partials = np;
   return rcl;
 } MFEM_API_CATCH("mfem_debug_brick_operator_apply_dot")
+
+extern "C" int mfem_debug_brick_operator_signed_diagonal(mfem_context ctx, uint64_t handle, double* d) try {
+  mfem_brick_operator_s* op = nullptr;
+  const int rc = bop_standalone(ctx, handle, &op);
+  if (rc) return rc;
+  MFEM_REQUIRE(d, "null vector");
+  return bop_signed_diagonal(ctx, op, d);
+} MFEM_API_CATCH("mfem_debug_brick_operator_signed_diagonal")
 
 extern "C" int mfem_brick_operator_diagonal(mfem_context ctx, uint64_t handle, double* d) try {
   mfem_brick_operator_s* op = nullptr;

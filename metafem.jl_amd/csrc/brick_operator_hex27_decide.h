@@ -113,3 +113,31 @@ static inline const char* bop27_refusal(int itp_order, int plo, int phi, int m0)
   if (plo != 0 || phi != m0) return "a brick with a slab set: the matrix-free brick operator runs on the whole lattice, one rank";
   return nullptr;
 }
+
+// ---- the signed diagonal as a plane sweep (brick_operator_hex27_diagonal.hip: k_brick27_diagonal_sweep) ---------------------------------------------
+// The product's skeleton -- b27_volume, b27_item, the 8 x 8 column tile, the segments, the low-side halo, the owner sum -- with the two apply stages
+// replaced by the contraction of Ke_aa = sum_q w det (-k) |Jinv^T grad N_a|^2 = sum_q sum_(d <= e) H_de(q) dN_a/dxi_d dN_a/dxi_e, H_de = (-k w det)
+// (2 - [d == e]) (Jinv Jinv^T)_de.  On the tensor basis dN_a/dxi_d dN_a/dxi_e is a product of three 1-D factors, one per direction r, of kind
+// [r == d] + [r == e]: 0 = l^2, 1 = l l', 2 = l'^2 -- a 3 x ng x 3 table -- so the sum over q runs in three short stages over q2, q1, q0.
+#define B27D_PAIRS 6  // (d, e): (0,0) (1,1) (2,2) (0,1) (0,2) (1,2)
+H8_HD int b27d_pair_d(int p) { return p < 3 ? p : (p == 5 ? 1 : 0); }
+H8_HD int b27d_pair_e(int p) { return p < 3 ? p : (p == 3 ? 1 : 2); }
+H8_HD int b27d_kind(int p, int r) { return (b27d_pair_d(p) == r ? 1 : 0) + (b27d_pair_e(p) == r ? 1 : 0); }
+constexpr int b27d_n3(int ng) { return 9 * ng * ng * ng; }               // J alone: no grad_xi T
+constexpr int b27d_na(int ng) { return B27D_PAIRS * 3 * ng * ng; }       // VA[p][q0][q1][a2]
+constexpr int b27d_nb(int ng) { return B27D_PAIRS * 9 * ng; }            // WB[p][q0][a12]
+constexpr int b27d_ndec(int ng) { return b27_n1(ng) + b27_n2(ng) + b27d_n3(ng) + b27d_na(ng) + b27d_nb(ng); }
+// per wave: the product's block (X | T1, then J over them, T2, w det); H[p][q] overlays T2 once J is inverted, VA | WB overlay J once H is formed
+constexpr int b27d_w_wb(int ng) { return b27_pad(b27d_na(ng)); }
+constexpr bool b27d_fits(int ng) {
+  return B27D_PAIRS * ng * ng * ng <= b27_w_d(ng) - b27_w_t2(ng) && b27d_w_wb(ng) + b27d_nb(ng) <= b27_w_t2(ng);
+}
+static_assert(b27d_fits(1) && b27d_fits(2) && b27d_fits(3) && b27d_fits(4), "the diagonal's stages overlay the product's per-wave block");
+// the workgroup's block: w [nq] | tab1 [2][ng][4] | tabp [3][ng][4] | decode words | Fe [B27_EH^2][27] | B27_WAVES per-wave blocks
+constexpr int b27d_off_tab1(int ng) { return b27_pad(ng * ng * ng); }
+constexpr int b27d_off_tabp(int ng) { return b27d_off_tab1(ng) + 8 * ng; }
+constexpr int b27d_off_dec(int ng) { return b27d_off_tabp(ng) + 12 * ng; }
+constexpr int b27d_off_fe(int ng) { return b27d_off_dec(ng) + (b27_pad(b27d_ndec(ng)) >> 1); }
+constexpr int b27d_off_waves(int ng) { return b27d_off_fe(ng) + b27_pad(B27_EH * B27_EH * 27); }
+constexpr size_t b27d_lds_bytes(int ng) { return sizeof(double) * ((size_t)b27d_off_waves(ng) + (size_t)B27_WAVES * b27_w_size(ng)); }
+static_assert(b27d_lds_bytes(4) <= B27_LDS_LIMIT && 2 * b27d_lds_bytes(3) <= B27_LDS_LIMIT, "one workgroup per CU on the 4-point rule, two below it");
