@@ -65,6 +65,14 @@ int mfem_debug_set(const char* key, int64_t a, int64_t b);
  * These knobs are read when a layout is BOUND (every mfem_solve and mfem_spmv_solver_layout binds its own): a product runs the kernel its bind
  * recorded; only the launch geometry (bits 8-15, 20, 26) is read per product.  Set them before the solve. */
 /* ^ key "ell": mfem_debug_set("ell", a, b) with (int enable) = (a[, b]) */
+/* The schedule of the patch sweep's runs in its constant form (csrc/symp_sched_decide.h).  a: bits 0-7 the mode -- 0 (default) the decision's own choice (XCD
+ * shares cut by cost, longest run first to the least loaded wave), 1 the identity schedule (equal shares, runs rotated among the waves: what the stored form
+ * always runs), 2 a pseudo-random assignment of the runs to the waves inside the shares, seeded by bits 8 and up -- read when a layout is BOUND.  b: a cap on
+ * the sweep's grid (0: none; rounded down to a multiple of 8, at least 8), read per product: on a small lattice it puts several runs on one wave.  The p . Ap
+ * partial sums are kept per run, so y, the sums and every iterate are the same bit for bit under every mode (tests/test_gpu_symp_sched.py). */
+/* ^ key "symp_sched": mfem_debug_set("symp_sched", a, b) with (int64_t mode | seed << 8, int64_t grid_cap) = (a, b) */
+/* binds of the constant form that built a schedule table (process-wide) */
+long long mfem_debug_symp_sched_count(void);
 /* mode 3: bit 0 on/off; bit 1 always read explicit columns; bit 2 every XCD walks a contiguous eighth of the blocks; bits 4-7 (x 8 = R)
  * rows sorted inside lattice regions of R^3 points when the pattern carries a lattice hint (mfem_brick_pattern) -- both measured slower than
  * the default at hex-27 128^3 (profiles/r03_sell_regions.txt), same results; bits 8-13 sort rows within windows of 2^w rows (0 = whole

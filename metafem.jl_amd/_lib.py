@@ -183,6 +183,7 @@ SIGNATURES = {
     "mfem_debug_symp_trim_count": (C.c_longlong, []),
     "mfem_debug_symp_const_count": (C.c_longlong, []),
     "mfem_debug_symp_const_steps": (C.c_longlong, []),
+    "mfem_debug_symp_sched_count": (C.c_longlong, []),
     "mfem_debug_spmv_scaled_layout": (c_int, [P, P, P, P, P, P, c_double, c_double, P, P, c_int32, C.POINTER(c_int32), C.POINTER(c_int32)]),
     "mfem_debug_set": (c_int, [C.c_char_p, c_int64, c_int64]),
     "mfem_debug_graph_comm_count": (c_int, []),

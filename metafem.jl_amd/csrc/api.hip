@@ -316,6 +316,7 @@ int mfem_ws_reserve(mfem_context_s* ctx, size_t bytes) {
 extern "C" {
 int mfem_debug_set_spmv(int, int);
 int mfem_debug_set_ell(int);
+int mfem_debug_set_symp_sched(int64_t, int64_t);
 int mfem_debug_set_sell(int);
 int mfem_debug_set_lat27(int);
 int mfem_debug_set_lat8(int);
@@ -347,6 +348,7 @@ extern "C" int mfem_debug_set(const char* key, int64_t a, int64_t b) try {
   const std::string k(key);
   if (k == "spmv") return mfem_debug_set_spmv((int)a, (int)b);
   if (k == "ell") return mfem_debug_set_ell((int)a);
+  if (k == "symp_sched") return mfem_debug_set_symp_sched(a, b);
   if (k == "sell") return mfem_debug_set_sell((int)a);
   if (k == "lat27") return mfem_debug_set_lat27((int)a);
   if (k == "lat8") return mfem_debug_set_lat8((int)a);

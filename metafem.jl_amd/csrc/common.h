@@ -208,6 +208,8 @@ struct mfem_csr_s {
   int64_t symp_flagged, symp_flagged_last;  // flagged steps of the bound copy (counted by the fill whether or not the constant form is taken)
   double symp_cst[27];      // symp_CS = 1: the reference row's 27 values as the fill forms them
   int symp_ccode;           // ... and, coded diagonal, its diagonal's code
+  const int32_t* symp_sched;  // symp_CS = 1: the schedule of the bound copy's runs (symp_sched_decide.h; not owned: in the solver workspace behind the step flags), null = the arithmetic form
+  int symp_sched_grid;      // ... and the sweep's grid it was built for
   int symp_dc_last;         // symp_DC of the last bind that ended on the patch sweep (the byte accounting of an unbound pattern answers for that bind)
   double* symp_vals;        // not owned (solver workspace, behind ell_vals): [plane - p0][patch][27 x 128 + edge block]; set while dia_kernel is the patch sweep
   // solver layout mode 3 for rows of uneven length: the row-sorted sliced layout (spmv_sell.hip) or its node-blocked form (spmv_bsell.hip) -- sell.form

@@ -105,6 +105,7 @@ inline uint64_t mfem_csr_graph_key(uint64_t key, const mfem_csr_s* A) {
   // the constant form (symp_const_decide.h) passes the reference row's values and code in the sweep's arguments: another matrix, another cycle
   key = mfem_hash(key, A->symp_CS);
   if (A->symp_CS) { key = mfem_hash_bytes(key, A->symp_cst, sizeof(A->symp_cst)); key = mfem_hash(key, A->symp_ccode); }
+  key = mfem_hash(key, A->symp_sched); key = mfem_hash(key, A->symp_sched_grid);  // (the table's place is fixed in the workspace; its content is read per launch)
   // the column scaling the lattice-tile kernels apply to x is a kernel argument too: a solve with right Jacobi (dsc = the solve's d) and one without
   // (dsc = null) on the same pattern, values and workspace must not share a captured cycle
   key = mfem_hash(key, A->lat27.dsc); key = mfem_hash(key, A->lat8.dsc);

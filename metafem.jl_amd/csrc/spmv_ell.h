@@ -10,6 +10,7 @@
 #include "spmv_symp.h"
 #include "symp_trim_decide.h"
 #include "symp_const_decide.h"
+#include "symp_sched_decide.h"
 
 // Blocked slot-major layout ("sliced ELL"): rows are grouped in blocks of ELL_B = 128 (the rows of one wave at two rows per
 // lane); block b stores its K slots one after the other, element (row r, slot s) at  b * K * 128 + s * 128 + (r & 127).
@@ -244,4 +245,6 @@ int mfem_sym_verdict(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const doub
                      bool* dc_refused, int* dneg, bool flags_made = false, SympConst* cst = nullptr, int64_t* flagged = nullptr);
 // the step flags' place in the layout's buffer: behind the patch-major copy and the rim copy of geometry G (spmv_sym.hip)
 unsigned char* mfem_symp_flags_of(double* pvals, const SympGeom& G);
+// THE schedule of a bound constant form's runs (symp_sched_decide.h): built from the step flags and placed behind them; A->symp_sched null where none applies
+int mfem_symp_sched_bind(mfem_context_s* ctx, mfem_csr_s* A, const SympGeom& G);
 int mfem_sym_launch(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const SpmvArgs& a);

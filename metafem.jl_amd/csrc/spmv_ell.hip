@@ -386,6 +386,7 @@ static int dia_bind(mfem_context_s* ctx, mfem_csr_s* A, const double* vals, doub
     A->symp_dc_last = A->symp_DC;
     if (A->symp_DC) ++g_symp_coded_binds;
     if (G.rim_units > 0) ++g_symp_trim_binds;
+    return mfem_symp_sched_bind(ctx, A, G);  // which wave sweeps which run of the constant form (symp_sched_decide.h): from the flags of THESE values
   }
   return MFEM_OK;
 }
@@ -419,6 +420,8 @@ void mfem_ell_unbind(mfem_csr_s* A) {
   A->ell_src = nullptr;
   A->symp_B = A->symp_DC = A->symp_dneg = A->symp_trim = A->symp_CS = 0;
   A->symp_flagged = 0;
+  A->symp_sched = nullptr;
+  A->symp_sched_grid = 0;
 }
 void mfem_ell_free(mfem_csr_s* A) {
   if (A->ell_cols) hipFree(A->ell_cols);

@@ -202,7 +202,15 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_sym27_check(int K, const DiaOffs
 //   * Runs: a run = one patch through nplanes / nseg consecutive planes, one wave (one-wave workgroups, 7 per CU: 22.8 KB of LDS
 //     each); a run's first step has no history and fills the previous-plane tables from the rows' own slots.  XCD c (workgroups
 //     with blockIdx % 8 == c) sweeps a contiguous eighth of the patches, segment by segment, so neighbouring patches advance
-//     through the planes together on one L2 (512^3: CG iteration 7.29 -> 6.66 ms against arbitrary equal cuts of the step list).
+//     through the planes together on one L2 (512^3: CG iteration 7.29 -> 6.66 ms against arbitrary equal cuts of the step list).  That is the IDENTITY
+//     schedule, computed by the sweep itself (equal shares, round rk gives wave jw the run spc_run(W, jw, rk, rot) of the share's segment-major list); the
+//     constant form may walk a table instead (Schedule, below).
+//   * Partial sums of the fused dotw . y (p . Ap of CG) per RUN (sps_per_run, symp_sched_decide.h: when runs + workgroups + what the launches behind the
+//     sweep need fit MFEM_MAX_PARTIALS; 512^3: 3072 + 768): at the end of a run the wave reduces its sum, lane 0 stores it at partials[patch * nseg + seg] and
+//     the accumulator starts again at zero; the tail and rim units a workgroup takes after its runs keep one sum per workgroup behind the runs'.  A run's sum
+//     is formed from zero in step order by whichever wave sweeps it, so the sums -- and with them alpha, every iterate and every statistic of a CG solve -- do
+//     not depend on the assignment of runs to waves: a schedule is a pure speed decision and every schedule can be tested bit for bit against every other
+//     (tests/test_gpu_symp_sched.py).  Where the runs do not fit (256^3: 3584 runs + 1792 workgroups) the sums stay per workgroup with the identity schedule.
 //   * Bands (k_spmv_symp<MODE, B>; the count is decided per bind, mfem_symp_bands_wanted): with B = 2 a wave owns 8 lines x 32 points and runs them per
 //     plane as two sub-steps of the same step body.  The nine halo lines of 32 cells dominate the edge block (9 W + 6 (L - 1) + 3 L entries), so per 256
 //     rows it falls from 2 x 318 to 354 entries and the x neighbourhood from 2 x 6 x 34 to 10 x 34: 3968 instead of 4224 matrix doubles, at 41.2 KB of
@@ -239,6 +247,15 @@ __global__ __launch_bounds__(MFEM_BLOCK) void k_sym27_check(int K, const DiaOffs
 //     among an XCD's waves from round to round (spc_run) so that no wave keeps the first or last patch column, whose steps are never flagged.  512^3: 3.31 ->
 //     2.60 ms per launch (profiles/r12_symp_const_ab_512.txt).  At n = 511, on a 0.3 m box, or with variable conductivity, no step is flagged: the bind keeps the
 //     stored kernel and pays nothing.
+//   * Schedule (k_spmv_symp_const alone; symp_sched_decide.h): with flagged steps the runs no longer cost the same -- per-run clocks of a probe build at 512^3: a
+//     never-flagged run of 170 steps 830 us, a flagged one 408 us -- and four runs per wave whatever they cost leave the launch waiting for the waves that drew
+//     two slow ones (2.51 ms against a mean load of 1.86 ms).  At bind time the host counts the flagged steps per run from the fill's flag bytes, cuts the XCDs'
+//     contiguous patch ranges by cost and gives an XCD's runs, costliest first, each to the least loaded of its waves (mfem_symp_sched_bind); the table --
+//     offset[grid + 1], run[nruns], behind the flags in the layout's buffer, rebuilt at every bind at the same place -- replaces the round loop by a walk over
+//     the wave's list: its two offsets and up to 64 run ids per gathered load, read from their lanes (a scalar load per run would show its latency as the
+//     flag's did).  The step body is untouched; the stored form, the identity mode of the "symp_sched" knob and a bind without per-run sums keep the
+//     arithmetic form.  The walk is a template parameter (k_spmv_symp_const<B, DC, SCH>), instantiated apart: as a run-time branch it cost the launches that
+//     never take it 0.2 - 0.4 % per step at 256^3 (74 instead of 39 spilled scalar registers for B = 2); apart, 0.15 %, inside the parent's spread.  512^3: model makespan 2.05 ms (whole runs allow 2.04), measured: profiles/r13_symp_sched_ab_512.txt.
 //   * Rows outside the swept planes (first / last lattice plane, the planes next to the ghost planes of a slab) come from the slot-major
 //     copy through the per-row code: the sweep's waves take them in 128-row units after their runs (unsplit SpMV: one launch, no tail);
 //     in a split (multi-rank) SpMV they are the boundary part, a launch of their own (k_spmv_dia_outside) after the halo has arrived.
@@ -304,20 +321,35 @@ __global__ __launch_bounds__(64) void k_symp_rim(SympGeom Gm, const double* __re
   }
 }
 
+#ifdef SYMP_SCHED_CLOCKS
+// Probe builds only (-DSYMP_SCHED_CLOCKS; tools/symp_sched_probe.py measures the constants of symp_sched_decide.h with it): per run id four 64-bit words --
+// wall clock at the run's start and end, the workgroup that swept it, its place in that workgroup's list.  Never in the shipped library.
+// Only launches with per-run sums stamp, and only run ids below the buffer's capacity: no geometry can write past the caller's buffer.
+__device__ long long* g_symp_clocks = nullptr;
+__device__ int g_symp_clocks_runs = 0;
+extern "C" int mfem_debug_symp_clocks(long long* buf /* [device, 4 x runs] or null */, int runs) {
+  if (!buf || runs < 0) runs = 0;
+  if (hipMemcpyToSymbol(HIP_SYMBOL(g_symp_clocks_runs), &runs, sizeof(runs)) != hipSuccess) return MFEM_ERR_HIP;
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_symp_clocks), &buf, sizeof(buf)) == hipSuccess ? MFEM_OK : MFEM_ERR_HIP;
+}
+#endif
 // B bands of SP_L lines per patch.  Per plane the wave runs its bands top to bottom as sub-steps of one step body (lane <-> two points of line lj of the
 // band): the tables, the x ring and the edge block cover all SP_L * B lines, so band 1 finds band 0's +y entries of this plane (slots 9..11) and
 // its next-plane entries of the previous plane (slots 0..2) in the tables -- the latter because band 0 holds its writes to the tables of slots 0..2 back
 // until the last band of the plane has read them.  A band with no valid line (the last patch row) is skipped wave-uniformly.
 // DC: form of the copy's main part (spmv_symp.h) -- 0 the diagonal stored as slot 13, 1 carried as one-byte codes counted from Gm.unit.
 // CS: 1 = the constant form (symp_const_decide.h; MODE 0 only) -- a step whose byte in sflags is set is computed from the reference row cst alone.
-// The body of both kernels below: k_spmv_symp<MODE, B, DC> is CS = 0, k_spmv_symp_const<B, DC> is MODE 0 with CS = 1.
-template <int MODE, int B, int DC, int CS>
+// The body of both kernels below: k_spmv_symp<MODE, B, DC> is CS = 0, k_spmv_symp_const<B, DC, SCH> is MODE 0 with CS = 1.
+// SCH: 1 = the wave walks its list of the schedule's table (symp_sched_decide.h; CS = 1 only) instead of the arithmetic rounds -- a parameter, not a run-time branch:
+// an instantiation that is never given a table (256^3: one band, sums per workgroup) keeps the loop it had.
+template <int MODE, int B, int DC, int CS, int SCH>
 __device__ __forceinline__ void symp_sweep(const SympGeom& Gm, const double* __restrict__ pv, const double* __restrict__ x,
                                            double* __restrict__ y, double alpha, double beta,
                                            const double* __restrict__ dotw, double* __restrict__ partials,
                                            const int32_t* __restrict__ done_flag, int32_t* __restrict__ bad, const SympTail& tail, const SympConst& cst,
-                                           const uint32_t* __restrict__ sflags) {
+                                           const uint32_t* __restrict__ sflags, const int32_t* __restrict__ sched, int nruns_pr) {
   static_assert(CS == 0 || MODE == 0, "the check pass reads the stored copy");
+  static_assert(SCH == 0 || CS == 1, "only the constant form is scheduled");
   constexpr int XL = sp_xl(B), XN = sp_xn(B), XU = sp_xu(B), NE = sp_ne(B), EU = sp_eu(B), MAINB = sp_main(B, DC), LOWB = sp_low(B);
   constexpr int NSL = sp_nslots(DC), S0 = 27 - NSL;  // slots S0..26 of a band are stored in its main part (DC = 1: the diagonal comes as a code)
   constexpr int BM = NSL * SP_ROWS, BL = 13 * SP_ROWS, BT = SP_L * SP_LS;  // a band's share of the main part, of the low part, of a table
@@ -399,11 +431,31 @@ __device__ __forceinline__ void symp_sweep(const SympGeom& Gm, const double* __r
     if (lane < XN - 64 * (XU - 1)) dst[xa[XU - 1]] = x[xidx(plane, XU - 1)];
   };
   // round rk: the XCD's runs [W rk, W rk + W), rotated among its W waves from round to round (spc_run, symp_const_decide.h: a wave does not keep its patch column)
+  // With a schedule (sched: symp_sched_decide.h; the constant form alone) the wave walks its list instead: offset[blockIdx], offset[blockIdx + 1] and up to
+  // 64 run ids come in one gathered load each, lane i <-> the list's (lw0 + i)-th run, as a run's flags do.
   const int W = gridDim.x >> 3, jw = blockIdx.x >> 3, rot = spc_rot(Gm.NPk);
-  for (int rk = 0; W * rk < pcnt * Gm.nseg; ++rk) {
-  const int run = spc_run(W, jw, rk, rot);
-  if (run >= pcnt * Gm.nseg) continue;
-  const int patch = pfirst + run % pcnt, seg = run / pcnt;
+  int l0 = 0, nlist = (pcnt * Gm.nseg + W - 1) / W, lw = 0;
+  if (SCH) {
+    const int ov = lane < 2 ? sched[blockIdx.x + lane] : 0;
+    l0 = __builtin_amdgcn_readlane(ov, 0);
+    nlist = __builtin_amdgcn_readlane(ov, 1) - l0;
+  }
+  for (int rk = 0; rk < nlist; ++rk) {
+  int patch, seg;
+  if (SCH) {
+    if ((rk & 63) == 0) lw = rk + lane < nlist ? sched[gridDim.x + 1 + l0 + rk + lane] : 0;  // (wave-uniform)
+    const int rid = __builtin_amdgcn_readlane(lw, rk & 63);
+    patch = rid / Gm.nseg;
+    seg = rid - patch * Gm.nseg;
+  } else {
+    const int run = spc_run(W, jw, rk, rot);
+    if (run >= pcnt * Gm.nseg) continue;
+    patch = pfirst + run % pcnt;
+    seg = run / pcnt;
+  }
+#ifdef SYMP_SCHED_CLOCKS  // probe builds only (tools/symp_sched_probe.py): the run's start and end on the 100 MHz wall clock
+  const long long clk0 = wall_clock64();
+#endif
   const int64_t t0 = (int64_t)patch * nplanes + (int64_t)nplanes * seg / Gm.nseg, t1 = (int64_t)patch * nplanes + (int64_t)nplanes * (seg + 1) / Gm.nseg;
   cur_patch = -1;
   for (int64_t t = t0; t < t1; ++t) {
@@ -667,6 +719,21 @@ __device__ __forceinline__ void symp_sweep(const SympGeom& Gm, const double* __r
     }
     if (!more) cur_patch = -1;  // nothing requested: the next step (if any) starts like a run
   }
+  // partial sums per run (sps_per_run): the run's p . Ap sum goes to its own place and the accumulator starts again -- the sums do not depend on the schedule
+  if (MODE == 0 && nruns_pr > 0 && partials) {
+    const double w = wave_reduce_sum(dot_acc);
+    if (lane == 0) partials[sps_run_id(patch, seg, Gm.nseg)] = w;
+    dot_acc = 0.0;
+  }
+#ifdef SYMP_SCHED_CLOCKS
+  if (MODE == 0 && nruns_pr > 0 && g_symp_clocks && sps_run_id(patch, seg, Gm.nseg) < g_symp_clocks_runs && lane == 0) {
+    long long* c = g_symp_clocks + 4 * (int64_t)sps_run_id(patch, seg, Gm.nseg);
+    c[0] = clk0;
+    c[1] = wall_clock64();
+    c[2] = blockIdx.x;
+    c[3] = rk;
+  }
+#endif
   }
   if (MODE == 0 && tail.on) {
     // 128-row units in front of and behind the swept planes (a unit straddling the boundary is masked row by row), shared among the waves
@@ -686,7 +753,7 @@ __device__ __forceinline__ void symp_sweep(const SympGeom& Gm, const double* __r
     if (fail) atomicOr(bad, 1);
   } else if (partials) {
     const double w = wave_reduce_sum(dot_acc);
-    if (lane == 0) partials[blockIdx.x] = w;
+    if (lane == 0) partials[nruns_pr + blockIdx.x] = w;  // (per-run sums: the workgroup's tail and rim units alone, behind the runs')
   }
 }
 
@@ -694,16 +761,16 @@ template <int MODE, int B, int DC>
 __global__ __launch_bounds__(64) void k_spmv_symp(SympGeom Gm, const double* __restrict__ pv, const double* __restrict__ x,
                                                    double* __restrict__ y, double alpha, double beta,
                                                    const double* __restrict__ dotw, double* __restrict__ partials,
-                                                   const int32_t* __restrict__ done_flag, int32_t* __restrict__ bad, SympTail tail) {
-  symp_sweep<MODE, B, DC, 0>(Gm, pv, x, y, alpha, beta, dotw, partials, done_flag, bad, tail, SympConst{}, nullptr);
+                                                   const int32_t* __restrict__ done_flag, int32_t* __restrict__ bad, SympTail tail, int nruns_pr) {
+  symp_sweep<MODE, B, DC, 0, 0>(Gm, pv, x, y, alpha, beta, dotw, partials, done_flag, bad, tail, SympConst{}, nullptr, nullptr, nruns_pr);
 }
-template <int B, int DC>
+template <int B, int DC, int SCH>
 __global__ __launch_bounds__(64) void k_spmv_symp_const(SympGeom Gm, const double* __restrict__ pv, const double* __restrict__ x,
                                                          double* __restrict__ y, double alpha, double beta,
                                                          const double* __restrict__ dotw, double* __restrict__ partials,
                                                          const int32_t* __restrict__ done_flag, SympTail tail, SympConst cst,
-                                                         const uint32_t* __restrict__ sflags) {
-  symp_sweep<0, B, DC, 1>(Gm, pv, x, y, alpha, beta, dotw, partials, done_flag, nullptr, tail, cst, sflags);
+                                                         const uint32_t* __restrict__ sflags, const int32_t* __restrict__ sched, int nruns_pr) {
+  symp_sweep<0, B, DC, 1, SCH>(Gm, pv, x, y, alpha, beta, dotw, partials, done_flag, nullptr, tail, cst, sflags, sched, nruns_pr);
 }
 
 // patch-major copy of the swept planes from the slot-major copy: per step [plane - p0][patch] and band the slots 13..26, then the edge block (main
@@ -868,16 +935,35 @@ int64_t mfem_symp_steps(const mfem_csr_s* A, int B, int trim) {
 int64_t mfem_symp_copy_doubles(const mfem_csr_s* A, int B, int trim) {
   const SympExt e = symp_ext(A, B, trim);
   return mfem_symp_steps(A, B, trim) * sp_step(B) + spt_units((int64_t)spt_rim(A->symp_m1, A->symp_m2, e.ms1, e.ms2) * (A->symp_p1 - A->symp_p0)) * SPT_UNIT_DOUBLES +
-         spc_flag_doubles(mfem_symp_steps(A, B, trim));
+         spc_flag_doubles(mfem_symp_steps(A, B, trim)) + SPS_TABLE_DOUBLES;
 }
 unsigned char* mfem_symp_flags_of(double* pvals, const SympGeom& G) {
   return (unsigned char*)(pvals + (int64_t)G.NR * G.NPk * (G.p1 - G.p0) * sp_step(G.B, G.DC) + G.rim_units * SPT_UNIT_DOUBLES);
+}
+// the schedule's table lies behind the step flags (symp_sched_decide.h: SPS_TABLE_DOUBLES at the most)
+static int32_t* symp_sched_of(double* pvals, const SympGeom& G) {
+  return (int32_t*)(mfem_symp_flags_of(pvals, G) + 8 * spc_flag_doubles((int64_t)G.NR * G.NPk * (G.p1 - G.p0)));
 }
 int64_t mfem_symp_swept_rows(const mfem_csr_s* A) {
   const SympExt e = symp_ext(A);
   return (int64_t)(A->symp_p1 - A->symp_p0) * e.ms1 * e.ms2;
 }
 #define SYMP_RIM_GRID 256  // workgroups of k_symp_rim at the most (one partial sum each)
+static_assert(SPS_MAX_PARTIALS == MFEM_MAX_PARTIALS && SPS_OUTSIDE_RESERVE == 1024 + SYMP_RIM_GRID, "symp_sched_decide.h spells both out");
+// mfem_debug_set("symp_sched", mode | seed << 8, grid cap): the schedule of the constant form's runs (symp_sched_decide.h) -- 0 the decision's own, 1 the identity
+// schedule, 2 a pseudo-random assignment under `seed` -- read when a layout is bound; the cap on the sweep's grid (0: none; rounded down to a multiple of 8)
+// puts several runs on a wave of a small lattice and is read per product.  Same y, same partial sums bit for bit under every mode.
+static std::atomic<int> g_symp_sched_mode{SPS_AUTO}, g_symp_sched_cap{0};
+static std::atomic<long long> g_symp_sched_seed{0};
+extern "C" int mfem_debug_set_symp_sched(int64_t a, int64_t b) {
+  ++mfem_debug_epoch;
+  g_symp_sched_mode = (int)(a & 255);
+  g_symp_sched_seed = (long long)(a >> 8);
+  g_symp_sched_cap = b > 0 ? (int)(b < MFEM_MAX_PARTIALS ? b : MFEM_MAX_PARTIALS) : 0;
+  return MFEM_OK;
+}
+static std::atomic<long long> g_symp_sched_binds{0};  // binds that built a schedule table (tests, the A/B)
+extern "C" long long mfem_debug_symp_sched_count(void) { return g_symp_sched_binds; }
 static int symp_grid(const mfem_context_s* ctx, const mfem_csr_s* A) {
   const int B = mfem_symp_bands(A);
   const SympExt e = symp_ext(A);
@@ -885,9 +971,44 @@ static int symp_grid(const mfem_context_s* ctx, const mfem_csr_s* A) {
   int64_t g = 8 * ((NP + 7) / 8) * symp_nseg(ctx, A);  // every XCD's share of the runs, padded to the largest share
   int64_t cap = (int64_t)sp_wg_per_cu(B) * ctx->num_cus;
   if (cap > MFEM_MAX_PARTIALS - 1024 - SYMP_RIM_GRID) cap = MFEM_MAX_PARTIALS - 1024 - SYMP_RIM_GRID;  // (the boundary part's and the rim launch's partial sums follow)
+  if (g_symp_sched_cap > 0 && cap > g_symp_sched_cap) cap = g_symp_sched_cap;
   cap &= ~(int64_t)7;
   if (g > cap) g = cap;
   return g < 8 ? 8 : (int)g;
+}
+
+// The schedule of a bind that ended on the constant form (symp_sched_decide.h): the step flags come to the host (a byte per step; the bind has just
+// synchronised for the fill's verdict), the flagged steps per run are counted, the table is built and goes into the layout's buffer behind the flags.
+// Nothing to schedule -- the stored form, the identity mode of the knob, runs that do not fit the partial-sum array -- leaves A->symp_sched null.
+int mfem_symp_sched_bind(mfem_context_s* ctx, mfem_csr_s* A, const SympGeom& G) {
+  A->symp_sched = nullptr;
+  A->symp_sched_grid = 0;
+  if (!A->symp_vals) return MFEM_OK;
+  const SpsGeom g{G.NR * G.NPk, G.NPk, G.nseg, G.p1 - G.p0, symp_grid(ctx, A)};
+  // (the reserve as the launch will count it where the bind can know: bit 26 of the "ell" knob; whether a product is split among ranks is decided per
+  // product -- a table such a launch does not take costs this bind 0.5 MB of flags and two synchronisations, nothing else)
+  const int kind = sps_kind(A->symp_CS != 0, sps_per_run(sps_nruns(g), g.grid, g_ell.symp_tail ? 0 : SPS_OUTSIDE_RESERVE), g_symp_sched_mode);
+  if (!kind) return MFEM_OK;
+  const int64_t steps = (int64_t)g.NP * g.nplanes;
+  const int nruns = sps_nruns(g);
+  std::vector<unsigned char> fl((size_t)steps);
+  MFEM_CHECK_HIP(hipMemcpyAsync(fl.data(), mfem_symp_flags_of(A->symp_vals, G), (size_t)steps, hipMemcpyDeviceToHost, ctx->stream));
+  MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  std::vector<int32_t> flagged((size_t)nruns), table((size_t)g.grid + 1 + nruns), work(2 * (size_t)nruns + g.grid);
+  std::vector<int64_t> load((size_t)g.grid);
+  int32_t first[9];
+  for (int p = 0; p < g.NP; ++p)
+    for (int s = 0; s < g.nseg; ++s) flagged[sps_run_id(p, s, g.nseg)] = sps_run_flagged(g, fl.data(), p, s);
+  sps_build(g, flagged.data(), kind == SPS_RANDOM ? SPS_RANDOM : SPS_AUTO, (uint64_t)g_symp_sched_seed.load(), table.data(), table.data() + g.grid + 1, first,
+            load.data(), work.data());
+  static_assert(sizeof(int32_t) * (2 * SPS_MAX_PARTIALS + 1) <= sizeof(double) * SPS_TABLE_DOUBLES, "the table's room in the layout's buffer");
+  int32_t* d = symp_sched_of(A->symp_vals, G);
+  MFEM_CHECK_HIP(hipMemcpyAsync(d, table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice, ctx->stream));
+  MFEM_CHECK_HIP(hipStreamSynchronize(ctx->stream));  // (the host copy goes away)
+  A->symp_sched = d;
+  A->symp_sched_grid = g.grid;
+  ++g_symp_sched_binds;
+  return MFEM_OK;
 }
 
 // Matrix entries (8 B) one product by sweep k reads from memory.  Tile sweep: K per padded row less what it takes from LDS.  Patch sweep: the rows
@@ -925,9 +1046,10 @@ int64_t mfem_sym_entries(const mfem_context_s* ctx, const mfem_csr_s* A, DiaKern
 }
 
 // the sweep's instantiation for a geometry: pass (MODE), bands, form of the diagonal; the constant form (MODE 0 only)
+template <int SCH>
 static auto symp_const_kernel(const SympGeom& G) {
-  if (G.DC) return G.B == 2 ? k_spmv_symp_const<2, 1> : k_spmv_symp_const<1, 1>;
-  return G.B == 2 ? k_spmv_symp_const<2, 0> : k_spmv_symp_const<1, 0>;
+  if (G.DC) return G.B == 2 ? k_spmv_symp_const<2, 1, SCH> : k_spmv_symp_const<1, 1, SCH>;
+  return G.B == 2 ? k_spmv_symp_const<2, 0, SCH> : k_spmv_symp_const<1, 0, SCH>;
 }
 template <int MODE>
 static auto symp_kernel(const SympGeom& G) {
@@ -981,7 +1103,7 @@ int mfem_sym_verdict(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const doub
   if (k == DIA_SYMP)
     hipLaunchKernelGGL(symp_kernel<1>(G), dim3(symp_grid(ctx, A)), dim3(64), 0, ctx->stream, G, (const double*)pvals,
                        (const double*)nullptr, (double*)nullptr, 0.0, 0.0, (const double*)nullptr, (double*)nullptr, (const int32_t*)nullptr, d_bad,
-                       SympTail{});
+                       SympTail{}, 0);
   else
     hipLaunchKernelGGL(k_sym27_check, dim3(ctx->num_cus * 8), dim3(MFEM_BLOCK), 0, ctx->stream, A->ell_K, (const DiaOffsets*)A->dia_dev, buf,
                        A->sym_c0 * SYM_ROWS, A->sym_c1 * SYM_ROWS, A->sym_cls, d_bad);
@@ -1017,17 +1139,22 @@ int mfem_sym_launch(mfem_context_s* ctx, mfem_csr_s* A, DiaKernel k, const SpmvA
     SympTail tl{};
     if (a.part.part == 0 && g_ell.symp_tail) tl = SympTail{1, A->ell_K, G.rim_units > 0, A->n, A->ell_npad, lo, hi, O, A->dia_flags, A->ell_cols, A->ell_vals};
     if (a.part.part != 2) {
-      np = symp_grid(ctx, A);
+      const int grid = symp_grid(ctx, A), nruns = G.NR * G.NPk * G.nseg;
+      // partial sums per run or per workgroup (sps_per_run: the geometry and the launches that follow alone decide, so the stored and the constant form
+      // agree); the bind's schedule where it applies to this grid, else the arithmetic form
+      const int nruns_pr = sps_per_run(nruns, grid, tl.on ? 0 : SPS_OUTSIDE_RESERVE) ? nruns : 0;
+      const int32_t* sched = nruns_pr && A->symp_CS && A->symp_sched && A->symp_sched_grid == grid ? A->symp_sched : nullptr;
+      np = nruns_pr + grid;
       if (A->symp_CS) {
         SympConst cst{};
         memcpy(cst.v, A->symp_cst, sizeof(cst.v));
         cst.code = A->symp_ccode;
         cst.valid = 1;
-        hipLaunchKernelGGL(symp_const_kernel(G), dim3(np), dim3(64), 0, ctx->stream, G, (const double*)A->symp_vals, a.x, a.y, a.alpha, a.beta, a.dotw,
-                           a.partials, a.done_flag, tl, cst, (const uint32_t*)mfem_symp_flags_of(A->symp_vals, G));
+        hipLaunchKernelGGL(sched ? symp_const_kernel<1>(G) : symp_const_kernel<0>(G), dim3(grid), dim3(64), 0, ctx->stream, G, (const double*)A->symp_vals, a.x, a.y, a.alpha, a.beta, a.dotw,
+                           a.partials, a.done_flag, tl, cst, (const uint32_t*)mfem_symp_flags_of(A->symp_vals, G), sched, nruns_pr);
       } else {
-        hipLaunchKernelGGL(symp_kernel<0>(G), dim3(np), dim3(64), 0, ctx->stream, G, (const double*)A->symp_vals, a.x, a.y, a.alpha, a.beta, a.dotw,
-                           a.partials, a.done_flag, (int32_t*)nullptr, tl);
+        hipLaunchKernelGGL(symp_kernel<0>(G), dim3(grid), dim3(64), 0, ctx->stream, G, (const double*)A->symp_vals, a.x, a.y, a.alpha, a.beta, a.dotw,
+                           a.partials, a.done_flag, (int32_t*)nullptr, tl, nruns_pr);
       }
       MFEM_CHECK_LAUNCH();
     }
