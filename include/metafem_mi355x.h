@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MFEM_ABI_VERSION 12
+#define MFEM_ABI_VERSION 13
 
 typedef enum {
   MFEM_OK = 0,
@@ -859,6 +859,23 @@ int mfem_brick_multigrid_create_elasticity(mfem_context ctx, uint64_t op, const 
  * coarse space does not hold -- on a CPU twin 111 iterations and a 25 % error where itg_order 5 needs 5), a diagonal of mixed sign or with a zero, a
  * non-positive estimate.  MFEM_ERR_INVALID as for mfem_brick_multigrid_create. */
 int mfem_brick_multigrid_create_hex27(mfem_context ctx, uint64_t op, const mfem_multigrid_options* opts, uint64_t* mg /* [host] out */);
+/* Added (ABI 13).  The hierarchy of mfem_brick_multigrid_create on an operator of mfem_brick_operator_create (hex-8 thermal), marked NONSYMMETRIC: it
+ * is created and set up with or without an active Nitsche (fixed_faces) term -- the level products carry the Nitsche rows, the signed diagonal has
+ * them, coarse operators take the caller's fixed_faces, h_penalty and Tw -- and the parameters are read live, so mfem_brick_operator_set_params may
+ * switch the term on or off between solves.  A setup skips only the Nitsche refusal for it: a diagonal of mixed sign or with a zero and a non-positive
+ * estimate are refused as ever.  With the term active the cycle is a fixed linear operator that is NOT symmetric.  Attaching it is the opt-in of
+ *   mfem_solve_operator with MFEM_SOLVER_GMRES and MFEM_PRECOND_MULTIGRID:  right-preconditioned restarted GMRES(s) on A M^-1 u = b, x = M^-1 u,
+ *   M^-1 = one cycle; l_or_s = s (0: 20, at most 32).  The residual estimate is tested after every Arnoldi step (fixed_iterations: exactly maxiter
+ *   steps); at a stop or at step s: x += Cycle(Q y), the true residual and the test on it, a failed test starts the next restart.
+ *   mfem_solve_stats.iterations counts Arnoldi steps; spmv_count = x0 + it (1 + c) + restarts (c + 1) + 1, c = the level-0 products of a cycle;
+ *   mfem_multigrid_info.cycles grows by it + restarts.  No left preconditioner, no communicator; check_every is ignored.  The same bits on every run.
+ * cg! with MFEM_PRECOND_MULTIGRID on such a hierarchy runs as on one of mfem_brick_multigrid_create while the Nitsche term is off (the same bits) and is
+ * refused while it is on.  On a hierarchy of mfem_brick_multigrid_create nothing changes.  The contract is mfem_brick_multigrid_create's otherwise.
+ * MFEM_ERR_UNSUPPORTED with a message, nothing created, launched or written: an elasticity, hex-27 or mesh operator. */
+int mfem_brick_multigrid_create_nonsymmetric(mfem_context ctx, uint64_t op, const mfem_multigrid_options* opts, uint64_t* mg /* [host] out */);
+/* Added (ABI 13).  1: a hierarchy of mfem_brick_multigrid_create_nonsymmetric, 0: any other; MFEM_ERR_INVALID: not a hierarchy's handle.
+ * (mfem_multigrid_info keeps its layout.) */
+int mfem_brick_multigrid_nonsymmetric(uint64_t mg);
 /* Re-sends the fine operator's CURRENT parameters to every level, injects the coordinates, computes the diagonals, the sign and the estimates.
  * Synchronises the context stream.  MFEM_ERR_UNSUPPORTED: a Nitsche term active, a diagonal of mixed sign or with a zero. */
 int mfem_brick_multigrid_setup(mfem_context ctx, uint64_t mg);
@@ -874,7 +891,8 @@ int mfem_brick_multigrid_destroy(uint64_t mg);
  * naming what is missing; nothing is launched, nothing is written.  On a thermal operator a solve creates a default hierarchy when none is attached;
  * every solve ALWAYS runs the setup first, inside solve_ms (where a Jacobi solve computes its diagonal): parameters re-sent and coordinates overwritten since the last solve can
  * never leave a stale level.  Nothing is allocated once the iteration has started.  cg_variant and check_every are ignored (the classic recurrence;
- * the flag is read after every iteration). */
+ * the flag is read after every iteration).  (ABI 13) MFEM_SOLVER_GMRES is admitted as well on a hex-8 thermal brick operator with a hierarchy of
+ * mfem_brick_multigrid_create_nonsymmetric ATTACHED, with or without an active Nitsche term: see that entry point. */
 
 /* ---- multi-GPU (new; the reference is single-GPU, F6) ------------------------------------ */
 /* 128-byte RCCL unique id, created on rank 0 and shipped to the other ranks by the host

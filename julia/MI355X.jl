@@ -21,7 +21,7 @@ import LinearAlgebra
 
 # ---- library handle and error convention ---------------------------------------------------------------------------------
 const lib = get(ENV, "METAFEM_MI355X_LIB", joinpath(@__DIR__, "..", "metafem.jl_amd", "libmetafem_mi355x.so"))
-const ABI_VERSION = 12   # == MFEM_ABI_VERSION
+const ABI_VERSION = 13  # == MFEM_ABI_VERSION
 
 struct MFEMError <: Exception
     rc::Cint
@@ -816,6 +816,19 @@ function brick_multigrid_hex27(op::BrickOperator, opts::MultigridOptions = Multi
     check(rc)
     return BrickMultigrid(h[], op)
 end
+"The hex-8 thermal hierarchy marked nonsymmetric (ABI 13): created and set up with or without an active Nitsche (fixed_faces) term.  Attaching it is
+what admits iterative_Solve!(op, residue, tol; Sv_func! = :gmres!, Pr_func! = :Pr_Multigrid!, s): right-preconditioned restarted GMRES(s) with one
+V-cycle per Arnoldi step (no default hierarchy is made for gmres!).  cg! takes it while the Nitsche term is off.  `nothing`: refused (an elasticity,
+hex-27 or mesh operator)."
+function brick_multigrid_nonsymmetric(op::BrickOperator, opts::MultigridOptions = MultigridOptions())
+    h = Ref{UInt64}(0)
+    rc = ccall((:mfem_brick_multigrid_create_nonsymmetric, lib), Cint, (Ptr{Cvoid}, UInt64, Ref{MultigridOptions}, Ref{UInt64}), ctx(), op.h, Ref(opts), h)
+    rc == -3 && return nothing
+    check(rc)
+    return BrickMultigrid(h[], op)
+end
+"true: a hierarchy of brick_multigrid_nonsymmetric"
+multigrid_is_nonsymmetric(mg::BrickMultigrid) = ccall((:mfem_brick_multigrid_nonsymmetric, lib), Cint, (UInt64,), mg.h) == 1
 multigrid_setup!(mg::BrickMultigrid) = check(ccall((:mfem_brick_multigrid_setup, lib), Cint, (Ptr{Cvoid}, UInt64), ctx(), mg.h))
 "z = one cycle applied to r"
 multigrid_apply!(z, mg::BrickMultigrid, r) =

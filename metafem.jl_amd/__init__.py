@@ -301,12 +301,15 @@ class BrickOperator:
         check(lib.mfem_brick_operator_diagonal(self.ctx._h, self._h, _ptr(d)))
         return d
 
-    def multigrid(self, **opts) -> "BrickMultigrid":
+    def multigrid(self, nonsymmetric: bool = False, **opts) -> "BrickMultigrid":
         """The geometric multigrid hierarchy of this operator (mfem_brick_multigrid_create): one per operator, destroyed with it.  opts:
         smoother_degree, coarse_degree, smoothing_range, coarse_range, eig_steps, max_levels (0 or absent: the default).  Raises MultigridRefused for
         an operator the hierarchy does not cover (an active Nitsche term; an ElasticityBrickOperator builds its own three-field hierarchy and
-        refuses tau == 0 or no penalty face; a Hex27BrickOperator builds its own p-coarsened one and refuses a rule below itg_order 4)."""
-        return BrickMultigrid(self, **opts)
+        refuses tau == 0 or no penalty face; a Hex27BrickOperator builds its own p-coarsened one and refuses a rule below itg_order 4).
+        nonsymmetric = True (mfem_brick_multigrid_create_nonsymmetric, the hex-8 thermal operator only): the same hierarchy, created and set up
+        with or without an active Nitsche (fixed_faces) term; with it attached iterative_Solve takes Sv_func = gmres_ with Pr_func = Pr_Multigrid_
+        (cg_ as well while the Nitsche term is off)."""
+        return BrickMultigrid(self, nonsymmetric=nonsymmetric, **opts)
 
     def close(self):
         if self._h:
@@ -353,7 +356,7 @@ class BrickMultigrid:
     brick of the same elements, so info()["ne"][0] == info()["ne"][1]).  A solve runs setup() itself, always; setup() and apply() are for a
     caller that uses the cycle on its own."""
 
-    def __init__(self, op: "BrickOperator", **opts):
+    def __init__(self, op: "BrickOperator", nonsymmetric: bool = False, **opts):
         unknown = set(opts) - {"smoother_degree", "coarse_degree", "smoothing_range", "coarse_range", "eig_steps", "max_levels"}
         if unknown:
             raise TypeError(f"unknown multigrid options {sorted(unknown)}")
@@ -361,7 +364,8 @@ class BrickMultigrid:
         self._h = C.c_uint64()
         o = _lib.MultigridOptions(int(opts.get("smoother_degree", 0)), int(opts.get("coarse_degree", 0)), float(opts.get("smoothing_range", 0.0)),
                                   float(opts.get("coarse_range", 0.0)), int(opts.get("eig_steps", 0)), int(opts.get("max_levels", 0)))
-        create = getattr(lib, getattr(op, "_multigrid_create", "mfem_brick_multigrid_create"))
+        # (nonsymmetric: the library answers for an operator that entry point does not cover)
+        create = getattr(lib, "mfem_brick_multigrid_create_nonsymmetric" if nonsymmetric else getattr(op, "_multigrid_create", "mfem_brick_multigrid_create"))
         rc = create(self.ctx._h, op._h, C.byref(o), C.byref(self._h))
         if rc == -3:
             raise MultigridRefused(lib.mfem_last_error().decode())
@@ -391,7 +395,8 @@ class BrickMultigrid:
         check(lib.mfem_brick_multigrid_info(self._h, C.byref(i)))
         L = i.levels
         return dict(levels=L, sign=i.sign, ne=[(i.nx[l], i.ny[l], i.nz[l]) for l in range(L)], lambda_max=[i.lambda_max[l] for l in range(L)],
-                    products=[i.products[l] for l in range(L)], setup_products=i.setup_products, bytes=i.bytes, cycles=i.cycles, setups=i.setups)
+                    products=[i.products[l] for l in range(L)], setup_products=i.setup_products, bytes=i.bytes, cycles=i.cycles, setups=i.setups,
+                    nonsymmetric=lib.mfem_brick_multigrid_nonsymmetric(self._h) == 1)
 
     def close(self):
         if self._h:
@@ -576,6 +581,9 @@ def iterative_Solve(A, K_vals: Optional[torch.Tensor], residue: torch.Tensor, co
     An ElasticityBrickOperator takes it under the same conditions once ElasticityBrickOperator.multigrid() has attached a hierarchy (that call is
     the opt-in: without it the solve raises and the message names the entry point) and while tau != 0 on at least one penalty face; a
     Hex27BrickOperator likewise once Hex27BrickOperator.multigrid() has attached one (refused with an active Nitsche term or itg_order < 4).
+    Sv_func = gmres_ takes Pr_Multigrid_ on a hex-8 thermal BrickOperator once BrickOperator.multigrid(nonsymmetric=True) has attached a hierarchy,
+    with or without an active Nitsche term: right-preconditioned restarted GMRES(s), one V-cycle per Arnoldi step and one per restart; stats.iterations
+    counts Arnoldi steps.
 
     Returns (delta_x, stats); delta_x is a NEW device vector like the reference's return value.
     """
@@ -909,7 +917,7 @@ class ThermalDomain:
     reference's Newton driver (04_Time_Domain.jl:59-80)."""
 
     def __init__(self, brick: Brick, k: float, h: float, Tenv: float, robin_faces: int = ALL_FACES, *, fixed_faces: int = 0,
-                 h_penalty: float = 0.0, Tw: float = 0.0, matrix_free=False, multigrid: bool = False):
+                 h_penalty: float = 0.0, Tw: float = 0.0, matrix_free=False, multigrid=False):
         self.brick, self.k, self.h, self.Tenv, self.robin_faces = brick, k, h, Tenv, robin_faces
         # weakly imposed Dirichlet faces (fix_boundary of examples/thermal_conduction/2D_Script.jl:58)
         self.fixed = dict(fixed_faces=fixed_faces, h_penalty=h_penalty, Tw=Tw)
@@ -948,7 +956,10 @@ class ThermalDomain:
         # multigrid = True (with matrix_free, K symmetric): linear_solver is cg_ with the V-cycle as its preconditioner; on a hex-27 operator
         # (matrix_free = "any") the hierarchy is the p-coarsened one of Hex27BrickOperator.multigrid.  With fixed faces (K is nonsymmetric), on a
         # hex-27 brick with a rule below itg_order 4 or on a domain that fell back to the assembled path the default solver stays, and
-        # multigrid_reason says why.
+        # multigrid_reason says why.  multigrid = "any": as True, and with fixed faces on a hex-8 brick gmres_ with the cycle of the nonsymmetric
+        # hierarchy (BrickOperator.multigrid(nonsymmetric=True)).
+        if isinstance(multigrid, str) and multigrid != "any":
+            raise ValueError("multigrid: False, True or 'any'")
         self.multigrid, self.multigrid_reason = False, None
         if multigrid:
             if not self.matrix_free:
@@ -957,6 +968,15 @@ class ThermalDomain:
             elif hex27 and brick.itg_order < 4:
                 self.multigrid_reason = "a hex-27 brick with fewer than 3 Gauss points per direction (itg_order < 4): the under-integrated K keeps " \
                                         "near-null modes that the hex-8 coarse space of the multigrid preconditioner does not hold"
+            elif fixed_faces and (h_penalty != 0.0 or k != 0.0) and multigrid == "any" and not hex27:
+                # multigrid = "any": whichever solver takes the cycle -- with fixed faces on a hex-8 brick the nonsymmetric hierarchy and gmres_
+                self.multigrid = True
+                self.mg = self.A.multigrid(nonsymmetric=True)
+                self.linear_solver = lambda gf: iterative_Solve(gf.A, None, gf.residue, gf.converge_tol, Sv_func=gmres_, Pr_func=Pr_Multigrid_,
+                                                                maxiter=200, max_pass=4)[0]
+            elif fixed_faces and (h_penalty != 0.0 or k != 0.0) and multigrid == "any":
+                self.multigrid_reason = "fixed_faces make K nonsymmetric, and the nonsymmetric hierarchy that gmres_ takes covers the hex-8 thermal " \
+                                        "operator only: not a hex-27 brick"
             elif fixed_faces and (h_penalty != 0.0 or k != 0.0):
                 self.multigrid_reason = "fixed_faces make K nonsymmetric: the multigrid preconditioner needs cg_"
             else:

@@ -279,6 +279,8 @@ SIGNATURES = {
     "mfem_brick_multigrid_create": (c_int, [P, c_uint64, C.POINTER(MultigridOptions), C.POINTER(c_uint64)]),
     "mfem_brick_multigrid_create_elasticity": (c_int, [P, c_uint64, C.POINTER(MultigridOptions), C.POINTER(c_uint64)]),
     "mfem_brick_multigrid_create_hex27": (c_int, [P, c_uint64, C.POINTER(MultigridOptions), C.POINTER(c_uint64)]),
+    "mfem_brick_multigrid_create_nonsymmetric": (c_int, [P, c_uint64, C.POINTER(MultigridOptions), C.POINTER(c_uint64)]),
+    "mfem_brick_multigrid_nonsymmetric": (c_int, [c_uint64]),
     "mfem_brick_multigrid_setup": (c_int, [P, c_uint64]),
     "mfem_brick_multigrid_apply": (c_int, [P, c_uint64, P, P]),
     "mfem_brick_multigrid_info": (c_int, [c_uint64, C.POINTER(MultigridInfo)]),

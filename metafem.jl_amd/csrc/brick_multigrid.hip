@@ -19,6 +19,9 @@
 // hex-8 brick of the SAME elements on ne + 1 -- mf = 2 mc - 1 as between two hex-8 levels, so k_mg_inject (the corner nodes), k_mg_restrict<1> and
 // k_mg_prolong<1> (the embedding Q1 in Q2) serve unchanged -- and the thermal h-hierarchy follows; level 0's signed diagonal is the plane sweep of
 // brick_operator_hex27_diagonal.hip, its product bop27_launch through the operator interface.
+// A nonsymmetric hierarchy (mfem_brick_multigrid_create_nonsymmetric) is the hex-8 thermal one with mfem_brick_multigrid_s.nonsym set: its setup
+// takes an active Nitsche (fixed_faces) term -- every kernel above runs unchanged on the nonsymmetric K -- and gmres! takes its cycle as a right
+// preconditioner (krylov_gmres_mg.hip).
 #include <memory>
 #include "brick_operator.h"
 #include "brick_multigrid.h"
@@ -54,6 +57,7 @@ struct mfem_brick_multigrid_s {
   int32_t* d_flags;  // [4]: a positive, a negative, a zero diagonal entry seen (k_mg_dinv)
   int sign;
   bool ready;        // a setup has succeeded since creation
+  bool nonsym;       // of mfem_brick_multigrid_create_nonsymmetric: a setup runs with a Nitsche term active too, gmres! takes the cycle
   int64_t bytes, cycles, setups, setup_products;
 };
 
@@ -434,7 +438,7 @@ static int mg_setup(mfem_context_s* ctx, mfem_brick_multigrid_s* mg) {
   } else if (mg_is_hex27(fine)) {
     const char* why = mg_hex27_refusal(fine->brick->ng, mg_nitsche(fine));
     if (why) return mg_refuse_hex27(why);
-  } else if (mg_nitsche(fine)) {
+  } else if (mg_setup_refuses_nitsche(mg->nonsym, mg_nitsche(fine))) {
     return mg_refuse("a Nitsche (fixed_faces) term is active: K is not symmetric");
   }
   const auto refuse = elasticity ? mg_refuse_elasticity : mg_is_hex27(fine) ? mg_refuse_hex27 : mg_refuse;
@@ -508,8 +512,8 @@ int mfem_mg_solve_check(mfem_context_s* ctx, mfem_operator_head* head, const mfe
   const bool thermal = op && op->physics == BOP_PHYSICS_THERMAL;
   const bool elasticity = op && mg_is_elasticity(op);
   const bool hex27 = op && mg_is_hex27(op);
-  const char* why = mg_solve_refusal_hex27(brick, thermal, elasticity, hex27, op && op->mg != nullptr, o->method, o->left_precond, ctx->comm != nullptr,
-                                           (thermal || hex27) && mg_nitsche(op));
+  const char* why = mg_solve_refusal_nonsym(brick, thermal, elasticity, hex27, op && op->mg != nullptr, op && op->mg && op->mg->nonsym, o->method,
+                                            o->left_precond, ctx->comm != nullptr, (thermal || hex27) && mg_nitsche(op));
   if (!why && hex27) {  // (the setup inside the solve would refuse it: answered here, before anything is launched)
     why = mg_hex27_refusal(op->brick->ng, false);
     if (why) return mg_refuse_hex27(why);
@@ -572,6 +576,45 @@ extern "C" int mfem_brick_multigrid_create(mfem_context ctx, uint64_t handle, co
   *out = (uint64_t)(uintptr_t)mg;
   return MFEM_OK;
 } MFEM_API_CATCH("mfem_brick_multigrid_create")
+
+// The hierarchy of mfem_brick_multigrid_create on a hex-8 thermal operator, marked nonsymmetric: created and set up with or without an active Nitsche
+// term (the parameters are read live at every setup), and the opt-in of gmres! with the cycle (mg_solve_refusal_nonsym).
+extern "C" int mfem_brick_multigrid_create_nonsymmetric(mfem_context ctx, uint64_t handle, const mfem_multigrid_options* opts, uint64_t* out) try {
+  MFEM_REQUIRE(out, "null out");
+  *out = 0;
+  mfem_operator_head* head = (mfem_operator_head*)(uintptr_t)handle;
+  MFEM_REQUIRE(ctx && head, "null argument");
+  if (head->kind == MFEM_OPERATOR_MESH) return mg_refuse("a mesh operator's handle: the hierarchy is built on the lattice of a brick");
+  mfem_brick_operator_s* op = bop_from_handle(handle);
+  MFEM_REQUIRE(op, "not an operator's handle");
+  if (op->physics != BOP_PHYSICS_THERMAL)
+    return mg_refuse("mfem_brick_multigrid_create_nonsymmetric covers the hex-8 thermal operator only (the penalty faces of a hex-8 elasticity operator "
+                     "are symmetric: mfem_brick_multigrid_create_elasticity and cg!; a hex-27 thermal operator takes mfem_brick_multigrid_create_hex27 "
+                     "without a Nitsche term)");
+  MFEM_REQUIRE(op->ctx == ctx, "the operator was created on another context");
+  MFEM_REQUIRE(!op->mg, "the operator already has a hierarchy (one per operator: destroy it first)");
+  MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
+  MgOptions opt;
+  const char* bad = mg_options(opts, &opt);
+  if (bad) {
+    mfem_set_error("mfem_brick_multigrid_create_nonsymmetric: %s", bad);
+    return MFEM_ERR_INVALID;
+  }
+  mfem_brick_multigrid_s* mg = nullptr;
+  const int rc = mg_create(ctx, op, opt, &mg);
+  if (rc) return rc;
+  mg->nonsym = true;
+  *out = (uint64_t)(uintptr_t)mg;
+  return MFEM_OK;
+} MFEM_API_CATCH("mfem_brick_multigrid_create_nonsymmetric")
+
+// 1: a hierarchy of mfem_brick_multigrid_create_nonsymmetric, 0: any other; MFEM_ERR_INVALID: not a hierarchy's handle (mfem_multigrid_info keeps
+// its layout: the flag is answered here)
+extern "C" int mfem_brick_multigrid_nonsymmetric(uint64_t handle) try {
+  mfem_brick_multigrid_s* mg = mg_from_handle(handle);
+  MFEM_REQUIRE(mg, "not a multigrid hierarchy's handle");
+  return mg->nonsym ? 1 : 0;
+} MFEM_API_CATCH("mfem_brick_multigrid_nonsymmetric")
 
 // The hierarchy of a hex-8 elasticity operator: three field-major fields per lattice point.  The contract is mfem_brick_multigrid_create's.
 extern "C" int mfem_brick_multigrid_create_elasticity(mfem_context ctx, uint64_t handle, const mfem_multigrid_options* opts, uint64_t* out) try {

@@ -2,7 +2,8 @@
 // alone: the level plan, the options' defaults and their refusals, the Chebyshev coefficients, the grids and tiles of the transfer kernels, how many
 // vectors a level owns, the device bytes of a hierarchy, the products of a cycle and of a pass, and which solves take the preconditioner.  Plain
 // integers in, plain structs out; no HIP, no context: tools/host_check_brick_multigrid.cpp walks them on the CPU (the field-aware forms at the end:
-// tools/host_check_brick_multigrid_elasticity.cpp; the hex-27 forms behind them: tools/host_check_brick_multigrid_hex27.cpp).
+// tools/host_check_brick_multigrid_elasticity.cpp; the hex-27 forms behind them: tools/host_check_brick_multigrid_hex27.cpp; the nonsymmetric
+// hierarchy's gate and the products of gmres! with the cycle last: tools/host_check_brick_multigrid_nonsym.cpp).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -272,3 +273,41 @@ static inline const char* mg_solve_refusal_hex27(bool brick_operator, bool therm
            "mfem_brick_multigrid_create_hex27 (no default hierarchy is made for hex-27)";
   return mg_solve_refusal(true, true, method, left_precond, has_comm, nitsche_on);
 }
+
+// ---- the nonsymmetric thermal hierarchy (mfem_brick_multigrid_create_nonsymmetric) and gmres! with the cycle (krylov_gmres_mg.hip) ---------------------
+// A hierarchy created by that entry point is the hex-8 thermal one, marked: its setups run with a Nitsche (fixed_faces) term active too -- the level
+// products carry the Nitsche rows and the signed diagonal has them; every other refusal of a setup stays.  The fixed Chebyshev V-cycle is then a fixed
+// linear operator that is not symmetric: a right preconditioner for restarted GMRES, not for cg!.
+// mg_solve_refusal_hex27 with MFEM_SOLVER_GMRES admitted on a hex-8 thermal operator when a NONSYMMETRIC hierarchy is attached to it (that hierarchy
+// is the opt-in: no default one is made), with no left preconditioner and no communicator; the Nitsche term may be on or off.  Every other row answers
+// as mg_solve_refusal_hex27 does: cg! with an active Nitsche term is refused whatever is attached, cg! on a nonsymmetric hierarchy whose Nitsche
+// term is off runs as on a plain one, gmres! on an elasticity, hex-27 or mesh operator is answered by those operators' rows.
+static inline const char* mg_solve_refusal_nonsym(bool brick_operator, bool thermal_hex8, bool elasticity_hex8, bool thermal_hex27, bool hierarchy_attached,
+                                                  bool hierarchy_nonsymmetric, int method, int left_precond, bool has_comm, bool nitsche_on) {
+  if (method != MFEM_SOLVER_GMRES || !brick_operator || !thermal_hex8 || elasticity_hex8 || thermal_hex27)
+    return mg_solve_refusal_hex27(brick_operator, thermal_hex8, elasticity_hex8, thermal_hex27, hierarchy_attached, method, left_precond, has_comm, nitsche_on);
+  if (!hierarchy_attached)
+    return "gmres! takes the multigrid preconditioner on a hex-8 thermal brick operator only with a nonsymmetric hierarchy attached: create one with "
+           "mfem_brick_multigrid_create_nonsymmetric (no default hierarchy is made for gmres!)";
+  if (!hierarchy_nonsymmetric)
+    return "gmres! takes the multigrid preconditioner only from a nonsymmetric hierarchy: the attached one is of mfem_brick_multigrid_create; destroy it "
+           "and create one with mfem_brick_multigrid_create_nonsymmetric";
+  return mg_solve_refusal(true, true, MFEM_SOLVER_CG, left_precond, has_comm, false);  // (the left preconditioner's and the communicator's rows)
+}
+// whether a setup refuses an active Nitsche term: a plain thermal hierarchy does, a nonsymmetric one does not
+static inline bool mg_setup_refuses_nitsche(bool hierarchy_nonsymmetric, bool nitsche_on) { return nitsche_on && !hierarchy_nonsymmetric; }
+
+// Level-0 products of a pass of gmres! with the cycle (mfem_solve_stats.spmv_count; the restart wrapper adds its true residual's): x0 for the start
+// residual as mfem_pass_residual counts it (0 from a zero start), then per restart of width k: k cycles and k products A z for the Arnoldi steps, one
+// more cycle for x += Cycle(Q y) and the true residual -- k (1 + c) + c + 1 with c = mg_cycle_products(0, ...).  Summed over the restarts of a pass of
+// `it` steps: it (1 + c) + restarts (c + 1); cycles = it + restarts.  A restart ends at width s, at the step that stops, or at an exact breakdown.
+#define MG_GMRES_DEFAULT_S 20
+#define MG_GMRES_MAX_S 32
+static inline int64_t mg_gmres_cycles(int it, int restarts) { return (int64_t)it + restarts; }
+static inline int64_t mg_gmres_restart_products(int width, int c) { return (int64_t)width * (1 + c) + c + 1; }
+static inline int64_t mg_gmres_pass_products(int x0, int it, int restarts, int nlev, int nu, int nu_c) {
+  const int c = mg_cycle_products(0, nlev, nu, nu_c);
+  return (int64_t)x0 + (int64_t)it * (1 + c) + (int64_t)restarts * (c + 1);
+}
+// restarts of a pass that takes `it` steps without a convergence stop or a breakdown in between (fixed_iterations, or maxiter reached): ceil(it / s)
+static inline int mg_gmres_full_restarts(int it, int s) { return it <= 0 ? 0 : (it + s - 1) / s; }

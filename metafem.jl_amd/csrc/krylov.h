@@ -75,6 +75,7 @@ mfem_pass_fn mfem_cg_pass, mfem_cg_single_pass, mfem_bicgstabl_pass, mfem_cgs2_p
 // krylov_next.hip: cgs!, tfqmr! (checkiter = s, default 200), lsqr! (products with A' through V.AT / V.valsT)
 mfem_pass_fn mfem_cgs_pass, mfem_tfqmr_pass, mfem_lsqr_pass;
 mfem_pass_fn mfem_cg_mg_pass;  // krylov_cg_mg.hip: cg! with the multigrid V-cycle of the bound brick operator (MFEM_PRECOND_MULTIGRID)
+mfem_pass_fn mfem_gmres_mg_pass;  // krylov_gmres_mg.hip: gmres! right-preconditioned by the V-cycle of a nonsymmetric hierarchy
 size_t mfem_gmres_workspace_bytes();
 int mfem_cg_ring_depth(int64_t nv);  // krylov_cg.hip: cg_ring_depth (cg_decide.h) under the knob mfem_debug_set("cg_ring")
 

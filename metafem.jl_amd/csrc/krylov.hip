@@ -264,6 +264,8 @@ static const KrylovMethod k_methods[] = {
 static const KrylovMethod k_cg_single = {"cg!", 2, MFEM_MAX_S, [](int) { return 5; }, false, mfem_cg_single_pass};
 // cg! with the multigrid V-cycle (MFEM_PRECOND_MULTIGRID, one rank, a hex-8 thermal brick operator): r, p, Ap, z
 static const KrylovMethod k_cg_mg = {"cg!", 2, MFEM_MAX_S, [](int) { return 4; }, true, mfem_cg_mg_pass};
+// gmres! with the multigrid V-cycle as its right preconditioner (a nonsymmetric hierarchy attached: mg_solve_refusal_nonsym): r, Q_1 .. Q_(s+1), z
+static const KrylovMethod k_gmres_mg = {"gmres!", 20, MFEM_MAX_S, [](int s) { return s + 3; }, true, mfem_gmres_mg_pass};
 static_assert(sizeof(k_methods) / sizeof(k_methods[0]) == MFEM_SOLVER_LSQR + 1, "one row per mfem_solver_kind");
 
 // The work vectors of this solve and how many of them (with the four in front) start cleared.  mfem_cg_pass keeps a ring of m search directions
@@ -353,7 +355,7 @@ static int choose_method(SolveRun& R) {
   if (o->method == MFEM_SOLVER_CG &&
       (o->cg_variant == 2 || (o->cg_variant == 0 && world_ranks > 1 && R.n_global / world_ranks < g_cg_single_max_rows)))
     method = &k_cg_single;
-  if (R.mg) method = &k_cg_mg;
+  if (R.mg) method = o->method == MFEM_SOLVER_GMRES ? &k_gmres_mg : &k_cg_mg;  // (the gate admits no other method)
   R.n_inv = 1.0 / (double)R.n_global;
   MFEM_REQUIRE(s_param <= method->max_s, "l_or_s too large");
   R.method = method;
