@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define MFEM_ABI_VERSION 13
+#define MFEM_ABI_VERSION 14
 
 typedef enum {
   MFEM_OK = 0,
@@ -786,6 +786,27 @@ int mfem_brick_operator_set_elasticity_params(uint64_t op, const mfem_elasticity
  * MFEM_ERR_UNSUPPORTED with a message, nothing created: an order-1 (hex-8) brick (it takes mfem_brick_operator_create), a brick with a slab set
  * (also answered by apply / diagonal / a solve if the slab is set later). */
 int mfem_brick_operator_create_hex27(mfem_context ctx, mfem_brick m, const mfem_thermal_params* p, uint64_t* op /* [host] out */);
+/* Three-field linear elasticity on an ORDER-2 (hex-27) brick (ABI 14): K of the cantilever form on the Lagrange-2 lattice -- the volume term
+ * -int sigma_ij(u) d_jN_a with sigma = lambda tr(eps) I + 2 mu eps, and -tau N_a N_b delta_fg on penalty_faces; traction_faces and sig do not enter K
+ * -- evaluated from the coordinates, read live; no pattern, no values, no scratch, where the assembled matrix holds up to 375 entries per row.
+ * Unknowns are field-major, n = 3 * control points, like the hex-8 elasticity operator's.  A product is one launch of the row-owner plane sweep of
+ * the hex-27 thermal operator with three fields (a wave per element pushes x1..x3 and u1..u3 through the sum-factorised stages, forms the stress at
+ * every Gauss point, runs the transposed stages per field; the owner of a control-point column adds the <= 4 element vectors that meet in it in a
+ * fixed order and writes its three unknowns once) plus one over the boundary control points when tau != 0 and penalty_faces != 0: no atomics, no
+ * colours, bitwise reproducible, the same bits whether or not the work items are folded onto the partial sums.  The handle is a brick operator:
+ * mfem_brick_operator_set_elasticity_params, _apply, _diagonal (for f = 0..2: K_(f,a),(f,a) = -sum_el sum_q w det [mu |g|^2 + (lambda + mu) g_f^2]
+ * - tau sum_faces sum_q w^s N_a^2, g = grad N_a, a thread per control point, the guarded rule), _destroy and mfem_solve_operator take it unchanged
+ * (same options, same refusals, same spmv_count formulas); mfem_brick_operator_set_params answers MFEM_ERR_INVALID.
+ * MFEM_ERR_UNSUPPORTED with a message, nothing created: an order-1 (hex-8) brick (it takes mfem_brick_operator_create_elasticity), a brick with a
+ * slab set (also answered by apply / diagonal / a solve if the slab is set later), a Gauss rule whose per-workgroup LDS block does not fit a CU's
+ * 160 KB (none of itg_order 1 to 7 today: the 4-point rule runs with fewer waves).  Every mfem_brick_multigrid_create* and MFEM_PRECOND_MULTIGRID
+ * refuse the handle: a hierarchy for it does not exist yet. */
+int mfem_brick_operator_create_elasticity_hex27(mfem_context ctx, mfem_brick m, const mfem_elasticity_params* p, uint64_t* op /* [host] out */);
+/* K_nonlinear_func of that form at x_star: residue = K x_star + f with f_(f,a) = sum over traction_faces sum_q w^s N_a sig_fj n_j (n outward) from the
+ * operator's CURRENT parameters (mfem_brick_operator_set_elasticity_params stores the whole struct); sign and normal conventions are
+ * mfem_brick_residual_elasticity's.  Overwrites residue (3 * control points entries).  Only a hex-27 elasticity handle: any other brick operator's
+ * handle and a mesh operator's answer MFEM_ERR_UNSUPPORTED with a message and nothing is launched. */
+int mfem_brick_operator_residual_elasticity(mfem_context ctx, uint64_t op, const double* x_star, double* residue);
 
 /* ---- geometric multigrid preconditioner for cg! on the hex-8 thermal brick operator (ABI 10) ------------------------------------------------------
  * Pr_Multigrid: one V-cycle as the preconditioner of cg!, for an operator of mfem_brick_operator_create (thermal, whole lattice, one rank) whose K is

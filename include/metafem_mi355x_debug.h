@@ -287,6 +287,10 @@ long long mfem_debug_bsell_spmv_count(void);
 /* TIMING ONLY (wrong results): phases of k_mesh_assemble left out -- 1 the pair products, 2 the stores of the row-owner form, 4 the geometry, 8 the
  * physical table, 16 the coordinate gather (tools/u20_assembly_ab.py). */
 /* ^ key "mesh_abl": mfem_debug_set("mesh_abl", a, b) with (int bits) = (a[, b]) */
+/* The hex-27 elasticity brick operator (csrc/brick_operator_elasticity_hex27.hip).  Bit 0: every element takes the general branch (no affine
+ * shortcut; equal to round-off).  Bit 1: TIMING ONLY (wrong values): the stress stage and the transposed stages run for one field.  Bits 8-11: waves per
+ * workgroup of the volume kernel (0 = the decision's own, 12 on the rules up to 3 points; clamped to 5 .. what fits the LDS). */
+/* ^ key "elasticity_hex27": mfem_debug_set("elasticity_hex27", a, b) with (int word) = (a[, b]) */
 int mfem_debug_remainder_info(mfem_csr A, int64_t* rows /* [host] */, int64_t* entries /* [host] */, double* asym_before /* [host] */);
 long long mfem_debug_rem_spmv_count(void);
 /* The transpose plan of mfem_spmv_csr_t / lsqr! (spmv_t.hip): returns 1 if the pattern holds one (bytes = its device bytes, build_ms = the host

@@ -21,7 +21,7 @@ import LinearAlgebra
 
 # ---- library handle and error convention ---------------------------------------------------------------------------------
 const lib = get(ENV, "METAFEM_MI355X_LIB", joinpath(@__DIR__, "..", "metafem.jl_amd", "libmetafem_mi355x.so"))
-const ABI_VERSION = 13  # == MFEM_ABI_VERSION
+const ABI_VERSION = 14  # == MFEM_ABI_VERSION
 
 struct MFEMError <: Exception
     rc::Cint
@@ -724,6 +724,25 @@ function brick_operator_hex27(brick::Brick, p::ThermalParams)
     finalizer(o -> (ccall((:mfem_brick_operator_destroy, lib), Cint, (UInt64,), o.h); o.h = 0), op)
     return op
 end
+
+# Three-field linear elasticity on an ORDER-2 (hex-27) brick (ABI 14): the cantilever form's K on the Lagrange-2 lattice, from the coordinates by the
+# row-owner sweep of the hex-27 thermal operator with three fields -- no K_J_ptr / K_J / K_total where a row holds up to 375 entries.  n = 3 x control
+# points, field-major.  A hex-8 brick and a brick with a slab are refused (`nothing`).  brick_operator_set_params!(op, ::ElasticityParams),
+# operator_mul!, operator_diagonal and iterative_Solve! take the operator unchanged; brick_operator_residual! is K_nonlinear_func.
+function brick_operator_elasticity_hex27(brick::Brick, p::ElasticityParams)
+    h = Ref{UInt64}(0)
+    rc = ccall((:mfem_brick_operator_create_elasticity_hex27, lib), Cint, (Ptr{Cvoid}, Ptr{Cvoid}, Ref{ElasticityParams}, Ref{UInt64}), ctx(), brick.h, Ref(p), h)
+    rc == -3 && return nothing
+    check(rc)
+    n = 3 * ccall((:mfem_brick_num_controlpoints, lib), Int64, (Ptr{Cvoid},), brick.h)
+    op = BrickOperator(h[], n, brick)
+    finalizer(o -> (ccall((:mfem_brick_operator_destroy, lib), Cint, (UInt64,), o.h); o.h = 0), op)
+    return op
+end
+
+"residue = K x_star + f (f: the traction sig on traction_faces of the operator's current parameters); a hex-27 elasticity operator only."
+brick_operator_residual!(residue, op::BrickOperator, x_star) =
+    check(ccall((:mfem_brick_operator_residual_elasticity, lib), Cint, (Ptr{Cvoid}, UInt64, Ptr{Cvoid}, Ptr{Cvoid}), ctx(), op.h, dptr(x_star), dptr(residue)))
 
 "Re-sends the parameters of an elasticity operator; a thermal operator answers MFEM_ERR_INVALID (and the other way round)."
 brick_operator_set_params!(op::BrickOperator, p::ElasticityParams) =

@@ -30,7 +30,7 @@ from . import _lib
 from ._lib import (ElasticityParams, MetaFEMError, OpLayout, SolveOptions, SolveStats, ThermalParams, check, lib)
 
 __all__ = ["Context", "FEM_SpMat_CSR", "MeshOperator", "BrickOperator", "BrickMultigrid", "MultigridRefused", "Pr_Multigrid_", "multigrid_plan", "multigrid_plan_hex27", "ElasticityBrickOperator", "Hex27BrickOperator", "BrickOperatorRefused", "brick_operator_refusal",
-           "brick_operator_hex27_refusal", "mul_", "tmul_", "dot", "nrm2", "axpby_", "FEM_rand", "normalized_norm",
+           "brick_operator_hex27_refusal", "Hex27ElasticityBrickOperator", "brick_operator_elasticity_hex27_refusal", "mul_", "tmul_", "dot", "nrm2", "axpby_", "FEM_rand", "normalized_norm",
            "iterative_Solve", "Brick", "make_Brick", "ThermalDomain", "ElasticityDomain", "MetaFEMError", "SolveStats",
            "cg_", "bicgstabl_GS_", "idrs_", "cgs2_", "gmres_", "cgs_", "tfqmr_", "lsqr_", "FACE_BITS"]
 
@@ -468,7 +468,43 @@ class Hex27BrickOperator(BrickOperator):
         self.ctx._children.add(self)
 
 
-_OPERATORS = (MeshOperator, BrickOperator, Hex27BrickOperator)  # what stands in for (A, vals) with vals = None
+class Hex27ElasticityBrickOperator(BrickOperator):
+    """Matrix-free K of a hex-27 (order-2) brick under three-field linear elasticity (mfem_brick_operator_create_elasticity_hex27,
+    csrc/brick_operator_elasticity_hex27.hip): the cantilever form's volume term and penalty faces, evaluated from the coordinates by the row-owner
+    sweep of the hex-27 thermal operator with three fields; n = 3 * ncp, field-major.  traction_faces and sig do not enter K: they are the load of
+    residual().  Made by Brick.elasticity_operator_hex27; mul_, diagonal and iterative_Solve take it as they take a BrickOperator.  Raises
+    BrickOperatorRefused for a hex-8 brick (Brick.elasticity_operator covers it), a brick with a slab and a rule whose LDS block does not fit
+    (brick_operator_elasticity_hex27_refusal).  multigrid() raises MultigridRefused: a hierarchy for it does not exist yet."""
+
+    def __init__(self, brick: "Brick", params: "ElasticityParams"):
+        self.ctx, self.brick = brick.ctx, brick  # (the library borrows the brick: kept alive here)
+        self.n = 3 * brick.ncp
+        self.nnz = 0
+        self._mg = None
+        self._h = C.c_uint64()
+        rc = lib.mfem_brick_operator_create_elasticity_hex27(self.ctx._h, brick._h, C.byref(params), C.byref(self._h))
+        if rc == -3:  # MFEM_ERR_UNSUPPORTED: a brick the operator does not cover
+            raise BrickOperatorRefused(lib.mfem_last_error().decode())
+        check(rc)
+        self.params = params
+        self.ctx._children.add(self)
+
+    def set_params(self, lam: float, mu: float, tau: float = 0.0, penalty_faces: int = 0, traction_faces: int = 0, sig=(0.0,) * 6):
+        """Re-sends the parameters, the residual's load included (host only, nothing is launched)."""
+        p = ElasticityParams(lam, mu, tau, penalty_faces, traction_faces, (C.c_double * 6)(*sig))
+        check(lib.mfem_brick_operator_set_elasticity_params(self._h, C.byref(p)))
+        self.params = p
+
+    def residual(self, x_star: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """K_nonlinear_func of the form: K x_star + f, f the traction sig on traction_faces (mfem_brick_operator_residual_elasticity)."""
+        _need(x_star, torch.float64, "x_star", self.n)
+        res = out if out is not None else torch.empty(self.n, dtype=torch.float64, device=x_star.device)
+        _need(res, torch.float64, "out", self.n)
+        check(lib.mfem_brick_operator_residual_elasticity(self.ctx._h, self._h, _ptr(x_star), _ptr(res)))
+        return res
+
+
+_OPERATORS = (MeshOperator, BrickOperator, Hex27BrickOperator, Hex27ElasticityBrickOperator)  # what stands in for (A, vals) with vals = None
 
 
 def mul_(b: torch.Tensor, A, vals: Optional[torch.Tensor], x: torch.Tensor, alpha: float = 1.0, beta: float = 0.0):
@@ -766,6 +802,12 @@ class Brick:
         slab raises BrickOperatorRefused."""
         return ElasticityBrickOperator(self, ElasticityParams(lam, mu, tau, penalty_faces, 0, (C.c_double * 6)(*([0.0] * 6))))
 
+    def elasticity_operator_hex27(self, lam: float, mu: float, tau: float = 0.0, penalty_faces: int = 0, traction_faces: int = 0,
+                                  sig=(0.0,) * 6) -> "Hex27ElasticityBrickOperator":
+        """The matrix-free K of the cantilever form on an order-2 brick (a BrickOperator with n == 3 * ncp); traction_faces and sig are kept for
+        its residual().  A hex-8 brick, a brick with a slab or a rule the kernel does not serve raises BrickOperatorRefused."""
+        return Hex27ElasticityBrickOperator(self, ElasticityParams(lam, mu, tau, penalty_faces, traction_faces, (C.c_double * 6)(*sig)))
+
     def residual_elasticity(self, x_star: torch.Tensor, lam: float, mu: float, tau: float = 0.0, penalty_faces: int = 0,
                             traction_faces: int = 0, sig=(0.0,) * 6, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """sig = constant symmetric tensor (11, 22, 33, 23, 13, 12) of Bilinear(d{i}, sig{i,j}*n{j}) (:61)."""
@@ -806,6 +848,49 @@ def brick_operator_hex27_refusal(brick: Brick) -> Optional[str]:
     return None
 
 
+def _e27_constants():
+    """the constants and the LDS arithmetic of csrc/brick_operator_elasticity_hex27_decide.h, restated (tests compare them with the header)"""
+    return dict(NI=6, NF=3, TE=8, WAVES_MAX=12, WAVES_MIN=5, LDS_LIMIT=160 * 1024, LDS_STATIC=128)
+
+
+def brick_operator_elasticity_hex27_lds_bytes(ng: int, waves: int) -> int:
+    """e27_lds_bytes(ng, waves) of csrc/brick_operator_elasticity_hex27_decide.h: the volume kernel's dynamic LDS block of a workgroup of `waves`
+    waves (a CU must hold it plus the kernel's 128 static bytes)."""
+    c = _e27_constants()
+    pad = lambda v: (v + 1) & ~1
+    ni, nf, eh = c["NI"], c["NF"], c["TE"] + 1
+    nq = ng ** 3
+    n1, n2, n3, na, nb = 18 * ng * ni, 9 * ng * ng * ni, 18 * nq, nf * 9 * ng * ng, nf * 18 * ng
+    w_t2 = pad(max(27 * ni + n1, n3, pad(na) + nb))
+    w_size = w_t2 + pad(max(n2, 9 * nq)) + pad(nq)
+    off_waves = pad(nq) + 8 * ng + (pad(n1 + n2 + n3 + na + nb) >> 1) + pad(eh * eh * 27 * nf)
+    return 8 * (off_waves + waves * w_size)
+
+
+def brick_operator_elasticity_hex27_waves(ng: int) -> int:
+    """e27_waves(ng): waves per workgroup of a rule (as many as fit the LDS, 12 at the most), 0 when not even 5 fit."""
+    c = _e27_constants()
+    w = c["WAVES_MAX"]
+    while w >= c["WAVES_MIN"] and brick_operator_elasticity_hex27_lds_bytes(ng, w) + c["LDS_STATIC"] > c["LDS_LIMIT"]:
+        w -= 1
+    return w if w >= c["WAVES_MIN"] else 0
+
+
+def brick_operator_elasticity_hex27_refusal(brick: Brick) -> Optional[str]:
+    """The host's forecast of mfem_brick_operator_create_elasticity_hex27's refusals (csrc/brick_operator_elasticity_hex27_decide.h:
+    bop_e27_refusal, the rule predicate e27_rule_served included), or None."""
+    if brick.itp_order != 2:
+        return "an order-1 (hex-8) brick: the hex-27 elasticity operator covers order-2 bricks; a hex-8 brick takes mfem_brick_operator_create_elasticity"
+    if tuple(brick.slab) != (0, brick.m[0]):
+        return "a brick with a slab set: the matrix-free brick operator runs on the whole lattice, one rank"
+    ng = brick.itg_order // 2 + 1
+    if not 1 <= ng <= 4:
+        return "a Gauss rule outside 1 to 4 points per direction (itg_order 1 to 7): the hex-27 tables hold no such rule"
+    if brick_operator_elasticity_hex27_waves(ng) == 0:
+        return "the 4-point Gauss rule (itg_order 6 to 7): the volume kernel's per-workgroup LDS block exceeds the 160 KB of a CU"
+    return None
+
+
 def make_Brick(x, n, itp_order: int = 1, itg_order: int = 3, ctx: Optional[Context] = None) -> Brick:
     return Brick(x, n, itp_order, itg_order, ctx)
 
@@ -831,18 +916,24 @@ class ElasticityDomain:
     generated closures are the fused HIP kernels; update_OneStep is the reference's Newton driver, as in ThermalDomain."""
 
     def __init__(self, brick: Brick, lam: float, mu: float, tau: float, penalty_faces: int, traction_faces: int = 0, sig=(0.0,) * 6, *,
-                 matrix_free: bool = False, multigrid: bool = False):
+                 matrix_free=False, multigrid: bool = False):
         self.brick, self.lam, self.mu, self.tau, self.penalty_faces = brick, lam, mu, tau, penalty_faces
         self.traction_faces, self.sig = traction_faces, tuple(sig)
         dev = f"cuda:{brick.ctx.device}"
+        # matrix_free = "any" (ThermalDomain's word for "whichever operator covers it"): a hex-8 brick as True; a hex-27 brick gets the
+        # Hex27ElasticityBrickOperator, whose residual() is K_nonlinear_func (matrix_free = True keeps falling back on one); a slab falls back.
+        if isinstance(matrix_free, str) and matrix_free != "any":
+            raise ValueError("matrix_free: False, True or 'any'")
+        self.hex27 = matrix_free == "any" and brick.itp_order == 2
         # matrix_free = True: no matrix at all.  self.A is the elasticity BrickOperator, K_linear = K_total = None, brick.pattern is never called and
         # K_linear_func only re-sends the parameters.  A brick the operator does not cover is built as the default domain is, and
         # matrix_free_reason says why (ThermalDomain's rule).
-        self.matrix_free_reason = brick_operator_refusal(brick) if matrix_free else None
+        self.matrix_free_reason = (brick_operator_elasticity_hex27_refusal(brick) if self.hex27 else brick_operator_refusal(brick)) if matrix_free else None
         self.matrix_free = bool(matrix_free) and self.matrix_free_reason is None
         if self.matrix_free:
             try:
-                self.A = brick.elasticity_operator(lam, mu, tau, penalty_faces)
+                self.A = brick.elasticity_operator_hex27(lam, mu, tau, penalty_faces, traction_faces, self.sig) if self.hex27 else \
+                    brick.elasticity_operator(lam, mu, tau, penalty_faces)
             except BrickOperatorRefused as e:
                 self.matrix_free, self.matrix_free_reason = False, str(e)
         if not self.matrix_free:
@@ -866,6 +957,8 @@ class ElasticityDomain:
             if not self.matrix_free:
                 self.multigrid_reason = "the domain holds an assembled matrix (" + (self.matrix_free_reason or "matrix_free was not asked for") + \
                                         "): the multigrid preconditioner needs the matrix-free hex-8 operator"
+            elif self.hex27:
+                self.multigrid_reason = "a hex-27 elasticity operator: a multigrid hierarchy for it does not exist yet"
             elif tau == 0.0 or (penalty_faces & ALL_FACES) == 0:
                 self.multigrid_reason = "no penalty face (tau == 0 or penalty_faces == 0): K keeps the rigid-body modes, the multigrid " \
                                         "preconditioner needs a definite K"
@@ -878,11 +971,17 @@ class ElasticityDomain:
 
     def K_linear_func(self):
         if self.matrix_free:  # nothing is assembled: the parameters go to the operator
-            self.A.set_params(self.lam, self.mu, self.tau, self.penalty_faces)
+            if self.hex27:
+                self.A.set_params(self.lam, self.mu, self.tau, self.penalty_faces, self.traction_faces, self.sig)
+            else:
+                self.A.set_params(self.lam, self.mu, self.tau, self.penalty_faces)
             return
         self.brick.assemble_elasticity(self.A, self.lam, self.mu, self.tau, self.penalty_faces, out=self.K_linear)
 
     def K_nonlinear_func(self):
+        if self.matrix_free and self.hex27:  # (the fused residual kernels are hex-8: the operator's own residual)
+            self.A.residual(self.x_star, out=self.residue)
+            return
         self.brick.residual_elasticity(self.x_star, self.lam, self.mu, self.tau, self.penalty_faces, self.traction_faces, self.sig, out=self.residue)
 
     def update_OneStep(self, max_iter: int = 4):

@@ -270,6 +270,8 @@ SIGNATURES = {
     "mfem_brick_operator_create_elasticity": (c_int, [P, P, C.POINTER(ElasticityParams), C.POINTER(c_uint64)]),
     "mfem_brick_operator_set_elasticity_params": (c_int, [c_uint64, C.POINTER(ElasticityParams)]),
     "mfem_brick_operator_create_hex27": (c_int, [P, P, C.POINTER(ThermalParams), C.POINTER(c_uint64)]),
+    "mfem_brick_operator_create_elasticity_hex27": (c_int, [P, P, C.POINTER(ElasticityParams), C.POINTER(c_uint64)]),
+    "mfem_brick_operator_residual_elasticity": (c_int, [P, c_uint64, P, P]),
     "mfem_brick_operator_destroy": (c_int, [c_uint64]),
     "mfem_brick_operator_apply": (c_int, [P, c_uint64, P, P, c_double, c_double]),
     "mfem_brick_operator_diagonal": (c_int, [P, c_uint64, P]),

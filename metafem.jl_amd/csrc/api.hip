@@ -339,6 +339,7 @@ int mfem_debug_set_csr_strips(int, int64_t);
 int mfem_debug_set_remainder(int);
 int mfem_debug_set_recheck_scale(double);
 int mfem_debug_set_bsell(int);
+int mfem_debug_set_elasticity_hex27(int);
 }
 extern int g_mesh_gather_rows, g_mesh_abl, g_mesh_stage_min_itp, g_mesh_term_matrix;  // assemble_mesh.hip
 extern int g_op_wave_forms, g_op_wave_min_itp;  // ops.hip
@@ -371,6 +372,7 @@ extern "C" int mfem_debug_set(const char* key, int64_t a, int64_t b) try {
   if (k == "remainder") return mfem_debug_set_remainder((int)a);
   if (k == "mesh_gather_rows") { g_mesh_gather_rows = (int)a; return MFEM_OK; }
   if (k == "bsell") return mfem_debug_set_bsell((int)a);
+  if (k == "elasticity_hex27") return mfem_debug_set_elasticity_hex27((int)a);
   if (k == "op_wave_forms") { g_op_wave_forms = (int)a; g_op_wave_min_itp = b > 0 ? (int)b : 10; return MFEM_OK; }
   if (k == "mesh_stage_min_itp") { g_mesh_stage_min_itp = a > 0 ? (int)a : 16; return MFEM_OK; }
   if (k == "mesh_term_matrix") { g_mesh_term_matrix = (int)a; return MFEM_OK; }

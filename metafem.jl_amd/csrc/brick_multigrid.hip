@@ -26,6 +26,7 @@
 #include "brick_operator.h"
 #include "brick_multigrid.h"
 #include "brick_multigrid_decide.h"
+#include "brick_operator_elasticity_hex27_decide.h"
 #include "krylov.h"
 
 typedef double d2_t __attribute__((ext_vector_type(2)));
@@ -509,6 +510,10 @@ static int mg_setup(mfem_context_s* ctx, mfem_brick_multigrid_s* mg) {
 int mfem_mg_solve_check(mfem_context_s* ctx, mfem_operator_head* head, const mfem_solve_options* o) {
   const bool brick = head->kind == MFEM_OPERATOR_BRICK;
   const mfem_brick_operator_s* op = brick ? (const mfem_brick_operator_s*)head : nullptr;
+  if (op && op->physics == BOP_PHYSICS_ELASTICITY_HEX27) {
+    mfem_set_error("mfem_solve_operator: MFEM_PRECOND_MULTIGRID on %s", bop_e27_multigrid_refusal());
+    return MFEM_ERR_UNSUPPORTED;
+  }
   const bool thermal = op && op->physics == BOP_PHYSICS_THERMAL;
   const bool elasticity = op && mg_is_elasticity(op);
   const bool hex27 = op && mg_is_hex27(op);
@@ -557,6 +562,7 @@ extern "C" int mfem_brick_multigrid_create(mfem_context ctx, uint64_t handle, co
   if (head->kind == MFEM_OPERATOR_MESH) return mg_refuse("a mesh operator's handle: the hierarchy is built on the lattice of a brick");
   mfem_brick_operator_s* op = bop_from_handle(handle);
   MFEM_REQUIRE(op, "not an operator's handle");
+  if (op->physics == BOP_PHYSICS_ELASTICITY_HEX27) return mg_refuse(bop_e27_multigrid_refusal());
   if (op->physics != BOP_PHYSICS_THERMAL)
     return mg_refuse("elasticity and hex-27 operators are not covered (a hex-8 elasticity operator takes mfem_brick_multigrid_create_elasticity, a hex-27 "
                      "thermal operator mfem_brick_multigrid_create_hex27)");
@@ -587,6 +593,7 @@ extern "C" int mfem_brick_multigrid_create_nonsymmetric(mfem_context ctx, uint64
   if (head->kind == MFEM_OPERATOR_MESH) return mg_refuse("a mesh operator's handle: the hierarchy is built on the lattice of a brick");
   mfem_brick_operator_s* op = bop_from_handle(handle);
   MFEM_REQUIRE(op, "not an operator's handle");
+  if (op->physics == BOP_PHYSICS_ELASTICITY_HEX27) return mg_refuse(bop_e27_multigrid_refusal());
   if (op->physics != BOP_PHYSICS_THERMAL)
     return mg_refuse("mfem_brick_multigrid_create_nonsymmetric covers the hex-8 thermal operator only (the penalty faces of a hex-8 elasticity operator "
                      "are symmetric: mfem_brick_multigrid_create_elasticity and cg!; a hex-27 thermal operator takes mfem_brick_multigrid_create_hex27 "
@@ -625,6 +632,7 @@ extern "C" int mfem_brick_multigrid_create_elasticity(mfem_context ctx, uint64_t
   if (head->kind == MFEM_OPERATOR_MESH) return mg_refuse_elasticity("a mesh operator's handle: the hierarchy is built on the lattice of a brick");
   mfem_brick_operator_s* op = bop_from_handle(handle);
   MFEM_REQUIRE(op, "not an operator's handle");
+  if (op->physics == BOP_PHYSICS_ELASTICITY_HEX27) return mg_refuse_elasticity(bop_e27_multigrid_refusal());
   if (op->physics == BOP_PHYSICS_THERMAL) return mg_refuse_elasticity("a hex-8 thermal operator's handle: it takes mfem_brick_multigrid_create");
   if (!mg_is_elasticity(op)) return mg_refuse_elasticity("a hex-27 operator's handle: it takes mfem_brick_multigrid_create_hex27");
   MFEM_REQUIRE(op->ctx == ctx, "the operator was created on another context");
@@ -655,6 +663,7 @@ extern "C" int mfem_brick_multigrid_create_hex27(mfem_context ctx, uint64_t hand
   if (head->kind == MFEM_OPERATOR_MESH) return mg_refuse_hex27("a mesh operator's handle: the hierarchy is built on the lattice of a brick");
   mfem_brick_operator_s* op = bop_from_handle(handle);
   MFEM_REQUIRE(op, "not an operator's handle");
+  if (op->physics == BOP_PHYSICS_ELASTICITY_HEX27) return mg_refuse_hex27(bop_e27_multigrid_refusal());
   if (op->physics == BOP_PHYSICS_THERMAL) return mg_refuse_hex27("a hex-8 thermal operator's handle: it takes mfem_brick_multigrid_create");
   if (mg_is_elasticity(op)) return mg_refuse_hex27("a hex-8 elasticity operator's handle: it takes mfem_brick_multigrid_create_elasticity");
   MFEM_REQUIRE(mg_is_hex27(op), "not a hex-27 thermal brick operator's handle");

@@ -64,7 +64,7 @@ __device__ __forceinline__ double bop_face_weight(const H8Tables* __restrict__ T
   return T->fw[q] * sqrt(r0 * r0 + r1 * r1 + r2 * r2);
 }
 
-enum { BOP_PHYSICS_THERMAL = 1, BOP_PHYSICS_ELASTICITY = 2, BOP_PHYSICS_HEX27 = 3 };  // (HEX27: thermal on an order-2 brick; its parameter block is `thermal`)
+enum { BOP_PHYSICS_THERMAL = 1, BOP_PHYSICS_ELASTICITY = 2, BOP_PHYSICS_HEX27 = 3, BOP_PHYSICS_ELASTICITY_HEX27 = 4 };  // (HEX27: thermal on an order-2 brick; its parameter block is `thermal`.  ELASTICITY_HEX27: elasticity on an order-2 brick; its parameter block is `elasticity`, traction_faces and sig included: the residual entry point reads them)
 struct Hex27Tables;  // hex27.h
 struct mfem_brick_operator_s {
   mfem_operator_head head;  // MFEM_OPERATOR_BRICK (operator.h)
@@ -74,7 +74,7 @@ struct mfem_brick_operator_s {
   mfem_thermal_params thermal;
   mfem_elasticity_params elasticity;  // (traction_faces and sig are kept as sent and never read: they contribute nothing to K)
   const H8Tables* tables;   // bop_tables(ctx->device, brick->ng): immutable (hex-8 physics)
-  const Hex27Tables* tables27;  // bop27_tables(ctx->device, brick->ng): immutable (BOP_PHYSICS_HEX27)
+  const Hex27Tables* tables27;  // bop27_tables(ctx->device, brick->ng): immutable (BOP_PHYSICS_HEX27, BOP_PHYSICS_ELASTICITY_HEX27)
   int ng;                   // the brick's rule when the operator was created
   const double* seen_x0;    // the brick's first coordinate array at the last bind (a change starts a new epoch of the cycle-graph key)
   mfem_csr_s csr;           // pattern-less: what the Krylov loop holds in place of a matrix (n = fields x control points)
@@ -110,3 +110,11 @@ int bop27_jacobi(mfem_context_s* ctx, const mfem_brick_operator_s* op, const Bri
 // (bop_signed_diagonal: the multigrid setup); bop27_diagonal_prepare raises that kernel's dynamic-LDS limit beside bop27_prepare
 int bop27_signed_diagonal(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, double* d);
 int bop27_diagonal_prepare(int ng);
+
+// brick_operator_elasticity_hex27.hip: the product and the diagonal of an operator with physics == BOP_PHYSICS_ELASTICITY_HEX27 (three-field elasticity,
+// order-2 brick) under the same contract, on bop27_tables' tables; bop_e27_prepare raises the volume kernel's dynamic-LDS limit (when an operator is
+// created: never at a launch).  mfem_brick_operator_residual_elasticity is defined beside its kernels.
+int bop_e27_prepare(int ng);
+int bop_e27_launch(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, const double* x, const double* dsc, double* y, double alpha,
+                   double beta, const double* dotw, double* partials, int* n_partials, const int32_t* done_flag);
+int bop_e27_jacobi(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, double* d);

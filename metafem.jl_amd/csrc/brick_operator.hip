@@ -27,6 +27,7 @@
 #include "blas1.h"
 #include "brick_operator.h"
 #include "brick_operator_hex27_decide.h"
+#include "brick_operator_elasticity_hex27_decide.h"
 static_assert(BOP_MAX_PARTIALS == MFEM_MAX_PARTIALS, "brick_operator_decide.h spells the cap out");
 
 static std::atomic<long long> g_brick_operator_count{0};
@@ -456,13 +457,20 @@ static BopThermal bop_thermal(const mfem_brick_operator_s* op) {
   return P;
 }
 
+// the refusals and the field count of a physics tag
+static const char* bop_physics_refusal(int physics, const mfem_brick_s* m) {
+  if (physics == BOP_PHYSICS_ELASTICITY_HEX27) return bop_e27_refusal(m->p, m->plo, m->phi, m->m[0], m->ng);
+  return physics == BOP_PHYSICS_HEX27 ? bop27_refusal(m->p, m->plo, m->phi, m->m[0]) : bop_refusal(m->p, m->plo, m->phi, m->m[0]);
+}
+static int bop_physics_fields(int physics) { return physics == BOP_PHYSICS_ELASTICITY || physics == BOP_PHYSICS_ELASTICITY_HEX27 ? 3 : 1; }
+
 // The brick as it is NOW (a caller may move coordinates between solves; a slab set after the operator was created is refused here).  Host only:
 // nothing is uploaded.  Called when the operator is bound -- before the driver can replay a cached cycle -- and again at every launch.
 static int bop_view(const mfem_brick_operator_s* op, BrickView* B) {
   const mfem_brick_s* m = op->brick;
-  const char* why = op->physics == BOP_PHYSICS_HEX27 ? bop27_refusal(m->p, m->plo, m->phi, m->m[0]) : bop_refusal(m->p, m->plo, m->phi, m->m[0]);
+  const char* why = bop_physics_refusal(op->physics, m);
   if (why) return bop_refuse(MFEM_ERR_UNSUPPORTED, why);
-  const int fields = op->physics == BOP_PHYSICS_ELASTICITY ? 3 : 1;
+  const int fields = bop_physics_fields(op->physics);
   MFEM_REQUIRE(fields * m->n_owned == op->csr.n, "the brick changed size under the operator");
   MFEM_REQUIRE(m->ng == op->ng, "the brick's Gauss rule changed under the operator");
   *B = mfem_brick_view(m, fields);
@@ -486,6 +494,12 @@ static int bop_launch(mfem_context_s* ctx, mfem_csr_s* A, const double* x, doubl
   }
   if (op->physics == BOP_PHYSICS_HEX27) {
     rc = bop27_launch(ctx, op, B, x, dsc, y, alpha, beta, dotw, partials, n_partials, done_flag);
+    if (rc) return rc;
+    if (!ctx->probe_active) ++g_brick_operator_count;
+    return MFEM_OK;
+  }
+  if (op->physics == BOP_PHYSICS_ELASTICITY_HEX27) {
+    rc = bop_e27_launch(ctx, op, B, x, dsc, y, alpha, beta, dotw, partials, n_partials, done_flag);
     if (rc) return rc;
     if (!ctx->probe_active) ++g_brick_operator_count;
     return MFEM_OK;
@@ -523,6 +537,7 @@ static int bop_jacobi(mfem_context_s* ctx, mfem_brick_operator_s* op, double* d)
   if (rc) return rc;
   if (op->physics == BOP_PHYSICS_ELASTICITY) return bop_elasticity_jacobi(ctx, op, B, d);
   if (op->physics == BOP_PHYSICS_HEX27) return bop27_jacobi(ctx, op, B, d);
+  if (op->physics == BOP_PHYSICS_ELASTICITY_HEX27) return bop_e27_jacobi(ctx, op, B, d);
   const int64_t grid = bop_diagonal_grid(B.n_owned);
   MFEM_REQUIRE(grid < ((int64_t)1 << 31), "too many control points for one launch");
   hipLaunchKernelGGL(k_brick_diagonal<false>, dim3((unsigned)grid), dim3(MFEM_BLOCK), 0, ctx->stream, B, bop_thermal(op), d);
@@ -582,11 +597,13 @@ static int bop_create(mfem_context ctx, mfem_brick m, int physics, const void* p
   *out = 0;
   MFEM_REQUIRE(ctx && m && p, "null argument");
   MFEM_REQUIRE(m->ctx == ctx, "the brick was created on another context");
-  const char* why = physics == BOP_PHYSICS_HEX27 ? bop27_refusal(m->p, m->plo, m->phi, m->m[0]) : bop_refusal(m->p, m->plo, m->phi, m->m[0]);
+  const char* why = bop_physics_refusal(physics, m);
   if (why) return bop_refuse(MFEM_ERR_UNSUPPORTED, why);
   const H8Tables* tables = nullptr;
   const Hex27Tables* tables27 = nullptr;
-  int rct = physics == BOP_PHYSICS_HEX27 ? bop27_tables(ctx->device, m->ng, &tables27) : bop_tables(ctx->device, m->ng, &tables);
+  const bool order2 = physics == BOP_PHYSICS_HEX27 || physics == BOP_PHYSICS_ELASTICITY_HEX27;
+  int rct = order2 ? bop27_tables(ctx->device, m->ng, &tables27) : bop_tables(ctx->device, m->ng, &tables);
+  if (!rct && physics == BOP_PHYSICS_ELASTICITY_HEX27) rct = bop_e27_prepare(m->ng);
   if (!rct && physics == BOP_PHYSICS_HEX27) rct = bop27_prepare(m->ng);
   if (!rct && physics == BOP_PHYSICS_HEX27) rct = bop27_diagonal_prepare(m->ng);
   if (rct) return rct;
@@ -603,12 +620,12 @@ static int bop_create(mfem_context ctx, mfem_brick m, int physics, const void* p
   op->physics = physics;
   memset(&op->thermal, 0, sizeof(op->thermal));
   memset(&op->elasticity, 0, sizeof(op->elasticity));
-  if (physics == BOP_PHYSICS_ELASTICITY) op->elasticity = *(const mfem_elasticity_params*)p;
+  if (bop_physics_fields(physics) == 3) op->elasticity = *(const mfem_elasticity_params*)p;
   else op->thermal = *(const mfem_thermal_params*)p;
   memset(&op->csr, 0, sizeof(op->csr));
   op->csr.ctx = ctx;
   op->csr.serial = mfem_next_csr_serial();
-  op->csr.n = (physics == BOP_PHYSICS_ELASTICITY ? 3 : 1) * m->n_owned;  // field-major unknowns (brick_xindex)
+  op->csr.n = bop_physics_fields(physics) * m->n_owned;  // field-major unknowns (brick_xindex)
   op->csr.rowptr_bits = 64;
   *out = (uint64_t)(uintptr_t)op.release();
   return MFEM_OK;
@@ -619,6 +636,9 @@ extern "C" int mfem_brick_operator_create(mfem_context ctx, mfem_brick m, const 
 extern "C" int mfem_brick_operator_create_elasticity(mfem_context ctx, mfem_brick m, const mfem_elasticity_params* p, uint64_t* out) try {
   return bop_create(ctx, m, BOP_PHYSICS_ELASTICITY, p, out);
 } MFEM_API_CATCH("mfem_brick_operator_create_elasticity")
+extern "C" int mfem_brick_operator_create_elasticity_hex27(mfem_context ctx, mfem_brick m, const mfem_elasticity_params* p, uint64_t* out) try {
+  return bop_create(ctx, m, BOP_PHYSICS_ELASTICITY_HEX27, p, out);
+} MFEM_API_CATCH("mfem_brick_operator_create_elasticity_hex27")
 extern "C" int mfem_brick_operator_create_hex27(mfem_context ctx, mfem_brick m, const mfem_thermal_params* p, uint64_t* out) try {
   return bop_create(ctx, m, BOP_PHYSICS_HEX27, p, out);
 } MFEM_API_CATCH("mfem_brick_operator_create_hex27")
@@ -627,7 +647,8 @@ extern "C" int mfem_brick_operator_create_hex27(mfem_context ctx, mfem_brick m, 
 static int bop_params_target(uint64_t handle, const void* p, int physics, mfem_brick_operator_s** out) {
   mfem_brick_operator_s* op = bop_from_handle(handle);
   MFEM_REQUIRE(op && p, "null argument, or not a brick operator's handle");
-  MFEM_REQUIRE(op->physics == physics || (physics == BOP_PHYSICS_THERMAL && op->physics == BOP_PHYSICS_HEX27), "the operator was created for the other physics (thermal: mfem_brick_operator_set_params, elasticity: mfem_brick_operator_set_elasticity_params)");
+  MFEM_REQUIRE(op->physics == physics || (physics == BOP_PHYSICS_THERMAL && op->physics == BOP_PHYSICS_HEX27) ||
+                   (physics == BOP_PHYSICS_ELASTICITY && op->physics == BOP_PHYSICS_ELASTICITY_HEX27), "the operator was created for the other physics (thermal: mfem_brick_operator_set_params, elasticity: mfem_brick_operator_set_elasticity_params)");
   MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
   *out = op;
   return MFEM_OK;
