@@ -263,7 +263,7 @@ class BrickOperatorRefused(MetaFEMError):
 
 
 class BrickOperator:
-    """Matrix-free K of a hex-8 thermal brick (mfem_brick_operator_*, csrc/brick_operator.hip): the matrix of Brick.assemble_thermal for the same
+    """Matrix-free K of a hex-8 thermal brick (mfem_brick_operator_*, csrc/brick_operator_thermal.hip): the matrix of Brick.assemble_thermal for the same
     parameters, evaluated from the brick's coordinates (read live: they may move between solves) -- no pattern, no values, no scratch.  Stands where
     a FEM_SpMat_CSR and its values stand: `mul_(b, op, None, x)` and `iterative_Solve(op, None, residue, ...)` take it.  Made by
     Brick.thermal_operator; raises BrickOperatorRefused (a MetaFEMError) with the library's message for a brick it refuses (hex-27, a slab)."""

@@ -66,20 +66,28 @@ static mfem_brick_multigrid_s* mg_from_handle(uint64_t h) {
   mfem_brick_multigrid_s* mg = (mfem_brick_multigrid_s*)(uintptr_t)h;
   return mg && mg->kind == MFEM_MULTIGRID_KIND ? mg : nullptr;
 }
-static int mg_refuse(const char* why) {
-  mfem_set_error("multigrid on the hex-8 thermal brick operator: %s", why);
+static int mg_refuse(int tag, const char* why) {  // (tag: the physics the refusing party builds hierarchies for; its row has the name)
+  mfem_set_error("multigrid on the %s brick operator: %s", bop_physics_row(tag)->name, why);
   return MFEM_ERR_UNSUPPORTED;
 }
-static int mg_refuse_elasticity(const char* why) {
-  mfem_set_error("multigrid on the hex-8 elasticity brick operator: %s", why);
-  return MFEM_ERR_UNSUPPORTED;
+// Why create entry point `which` (BOP_MG_*) does not build the hierarchy of an operator with physics `tag` (BOP_PHYSICS_*); nullptr where it does.
+static const char* mg_wrong_physics(int which, int tag) {
+  static const char* const takes_create = "a hex-8 thermal operator's handle: it takes mfem_brick_multigrid_create";
+  static const char* const not_covered = "elasticity and hex-27 operators are not covered (a hex-8 elasticity operator takes mfem_brick_multigrid_create_elasticity, a hex-27 "
+                                         "thermal operator mfem_brick_multigrid_create_hex27)";
+  static const char* const thermal_only = "mfem_brick_multigrid_create_nonsymmetric covers the hex-8 thermal operator only (the penalty faces of a hex-8 elasticity operator "
+                                          "are symmetric: mfem_brick_multigrid_create_elasticity and cg!; a hex-27 thermal operator takes mfem_brick_multigrid_create_hex27 "
+                                          "without a Nitsche term)";
+  static const char* const why[BOP_MG_ENTRIES][BOP_PHYSICS_ROWS] = {  // [entry point][tag - 1]
+      {nullptr, not_covered, not_covered, bop_e27_multigrid_refusal()},
+      {nullptr, thermal_only, thermal_only, bop_e27_multigrid_refusal()},
+      {takes_create, nullptr, "a hex-27 operator's handle: it takes mfem_brick_multigrid_create_hex27", bop_e27_multigrid_refusal()},
+      {takes_create, "a hex-8 elasticity operator's handle: it takes mfem_brick_multigrid_create_elasticity", nullptr, bop_e27_multigrid_refusal()}};
+  return why[which][tag - 1];
 }
-static int mg_refuse_hex27(const char* why) {
-  mfem_set_error("multigrid on the hex-27 thermal brick operator: %s", why);
-  return MFEM_ERR_UNSUPPORTED;
-}
-static bool mg_is_elasticity(const mfem_brick_operator_s* op) { return op->physics == BOP_PHYSICS_ELASTICITY; }
-static bool mg_is_hex27(const mfem_brick_operator_s* op) { return op->physics == BOP_PHYSICS_HEX27; }
+// which hierarchy an operator takes: its physics row names the entry point that builds it (brick_operator_physics.h)
+static bool mg_is_elasticity(const mfem_brick_operator_s* op) { return bop_row(op).multigrid == BOP_MG_CREATE_ELASTICITY; }
+static bool mg_is_hex27(const mfem_brick_operator_s* op) { return bop_row(op).multigrid == BOP_MG_CREATE_HEX27; }
 
 // ---- kernels -------------------------------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool mg_point(int m1, int m2, int& i, int& j, int& k) {
@@ -367,7 +375,7 @@ static int mg_create(mfem_context_s* ctx, mfem_brick_operator_s* op, const MgOpt
   const mfem_brick_s* fb = op->brick;
   const bool hex27 = mg_is_hex27(op);  // level 0 on the lattice 2 ne + 1, a hex-8 brick of the same elements below it (mg_plan_hex27)
   const MgPlan P = hex27 ? mg_plan_hex27(fb->ne[0], fb->ne[1], fb->ne[2], opt.max_levels) : mg_plan(fb->ne[0], fb->ne[1], fb->ne[2], opt.max_levels);
-  const int fields = mg_is_elasticity(op) ? MG_ELASTICITY_FIELDS : 1;
+  const int fields = bop_row(op).fields;
   mfem_host_alloc_probe();
   mfem_brick_multigrid_s* mg = new mfem_brick_multigrid_s();
   memset(mg, 0, sizeof(*mg));
@@ -435,14 +443,14 @@ static int mg_setup(mfem_context_s* ctx, mfem_brick_multigrid_s* mg) {
   const bool elasticity = mg_is_elasticity(fine);
   if (elasticity) {
     const char* why = mg_elasticity_refusal(fine->elasticity.tau, fine->elasticity.penalty_faces);
-    if (why) return mg_refuse_elasticity(why);
+    if (why) return mg_refuse(fine->physics, why);
   } else if (mg_is_hex27(fine)) {
     const char* why = mg_hex27_refusal(fine->brick->ng, mg_nitsche(fine));
-    if (why) return mg_refuse_hex27(why);
+    if (why) return mg_refuse(fine->physics, why);
   } else if (mg_setup_refuses_nitsche(mg->nonsym, mg_nitsche(fine))) {
-    return mg_refuse("a Nitsche (fixed_faces) term is active: K is not symmetric");
+    return mg_refuse(fine->physics, "a Nitsche (fixed_faces) term is active: K is not symmetric");
   }
-  const auto refuse = elasticity ? mg_refuse_elasticity : mg_is_hex27(fine) ? mg_refuse_hex27 : mg_refuse;
+  const auto refuse = [fine](const char* why) { return mg_refuse(fine->physics, why); };
   for (int l = 0; l < mg->nlev; ++l) MFEM_REQUIRE(!mg->lev[l].op->csr.op, "a level's operator is bound to a running solve");
   const mfem_brick_s* fb = fine->brick;
   MFEM_REQUIRE(fb->ne[0] == mg->lev[0].ne[0] && fb->ne[1] == mg->lev[0].ne[1] && fb->ne[2] == mg->lev[0].ne[2] && fb->plo == 0 && fb->phi == fb->m[0],
@@ -510,22 +518,22 @@ static int mg_setup(mfem_context_s* ctx, mfem_brick_multigrid_s* mg) {
 int mfem_mg_solve_check(mfem_context_s* ctx, mfem_operator_head* head, const mfem_solve_options* o) {
   const bool brick = head->kind == MFEM_OPERATOR_BRICK;
   const mfem_brick_operator_s* op = brick ? (const mfem_brick_operator_s*)head : nullptr;
-  if (op && op->physics == BOP_PHYSICS_ELASTICITY_HEX27) {
-    mfem_set_error("mfem_solve_operator: MFEM_PRECOND_MULTIGRID on %s", bop_e27_multigrid_refusal());
+  if (op && bop_row(op).multigrid == BOP_MG_NONE) {  // (a physics without a hierarchy: every create entry point answers it alike)
+    mfem_set_error("mfem_solve_operator: MFEM_PRECOND_MULTIGRID on %s", mg_wrong_physics(BOP_MG_CREATE, op->physics));
     return MFEM_ERR_UNSUPPORTED;
   }
-  const bool thermal = op && op->physics == BOP_PHYSICS_THERMAL;
+  const bool thermal = op && bop_row(op).multigrid == BOP_MG_CREATE;
   const bool elasticity = op && mg_is_elasticity(op);
   const bool hex27 = op && mg_is_hex27(op);
   const char* why = mg_solve_refusal_nonsym(brick, thermal, elasticity, hex27, op && op->mg != nullptr, op && op->mg && op->mg->nonsym, o->method,
                                             o->left_precond, ctx->comm != nullptr, (thermal || hex27) && mg_nitsche(op));
   if (!why && hex27) {  // (the setup inside the solve would refuse it: answered here, before anything is launched)
     why = mg_hex27_refusal(op->brick->ng, false);
-    if (why) return mg_refuse_hex27(why);
+    if (why) return mg_refuse(op->physics, why);
   }
   if (!why && elasticity) {  // (the setup inside the solve would refuse it: answered here, before anything is launched)
     why = mg_elasticity_refusal(op->elasticity.tau, op->elasticity.penalty_faces);
-    if (why) return mg_refuse_elasticity(why);
+    if (why) return mg_refuse(op->physics, why);
   }
   if (!why) return MFEM_OK;
   mfem_set_error("mfem_solve_operator: %s", why);
@@ -554,66 +562,57 @@ mfem_brick_multigrid_s* mfem_mg_of(const mfem_csr_s* A) {
 }
 
 // ---- entry points -----------------------------------------------------------------------------------------------------------------------------------------
+// One body for the four create entry points.  `which` is BOP_MG_*: _CREATE builds the hierarchy of a hex-8 thermal operator; _CREATE_NONSYMMETRIC the
+// same, marked nonsymmetric: created and set up with or without an active Nitsche term (the parameters are read live at every setup), and the opt-in of
+// gmres! with the cycle (mg_solve_refusal_nonsym); _CREATE_ELASTICITY that of a hex-8 elasticity operator, three field-major fields per lattice point;
+// _CREATE_HEX27 that of a hex-27 thermal operator: p-coarsening once onto a hex-8 brick of the same elements, then the thermal h-hierarchy.  The
+// contract is the same for all: attached, one per operator, destroyed with it.
+static int mg_create_entry(mfem_context ctx, uint64_t handle, const mfem_multigrid_options* opts, uint64_t* out, int which) {
+  static const struct { const char* name; int tag; } entries[BOP_MG_ENTRIES] = {  // the entry point's name and the physics it builds hierarchies for
+      {"mfem_brick_multigrid_create", BOP_PHYSICS_THERMAL}, {"mfem_brick_multigrid_create_nonsymmetric", BOP_PHYSICS_THERMAL},
+      {"mfem_brick_multigrid_create_elasticity", BOP_PHYSICS_ELASTICITY}, {"mfem_brick_multigrid_create_hex27", BOP_PHYSICS_HEX27}};
+  const auto& E = entries[which];
+  MFEM_REQUIRE(out, "null out");
+  *out = 0;
+  mfem_operator_head* head = (mfem_operator_head*)(uintptr_t)handle;
+  MFEM_REQUIRE(ctx && head, "null argument");
+  if (head->kind == MFEM_OPERATOR_MESH) return mg_refuse(E.tag, "a mesh operator's handle: the hierarchy is built on the lattice of a brick");
+  mfem_brick_operator_s* op = bop_from_handle(handle);
+  MFEM_REQUIRE(op, "not an operator's handle");
+  if (op->physics != E.tag) return mg_refuse(E.tag, mg_wrong_physics(which, op->physics));
+  MFEM_REQUIRE(op->ctx == ctx, "the operator was created on another context");
+  MFEM_REQUIRE(!op->mg, "the operator already has a hierarchy (one per operator: destroy it first)");
+  MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
+  const char* why = nullptr;  // the entry point's own refusal (the nonsymmetric one has none)
+  if (which == BOP_MG_CREATE && mg_nitsche(op)) why = "a Nitsche (fixed_faces) term is active: K is not symmetric";
+  if (which == BOP_MG_CREATE_ELASTICITY) why = mg_elasticity_refusal(op->elasticity.tau, op->elasticity.penalty_faces);
+  if (which == BOP_MG_CREATE_HEX27) why = mg_hex27_refusal(op->brick->ng, mg_nitsche(op));
+  if (why) return mg_refuse(E.tag, why);
+  MgOptions opt;
+  const char* bad = mg_options(opts, &opt);
+  if (bad) {
+    mfem_set_error("%s: %s", E.name, bad);
+    return MFEM_ERR_INVALID;
+  }
+  mfem_brick_multigrid_s* mg = nullptr;
+  const int rc = mg_create(ctx, op, opt, &mg);
+  if (rc) return rc;
+  mg->nonsym = which == BOP_MG_CREATE_NONSYMMETRIC;
+  *out = (uint64_t)(uintptr_t)mg;
+  return MFEM_OK;
+}
 extern "C" int mfem_brick_multigrid_create(mfem_context ctx, uint64_t handle, const mfem_multigrid_options* opts, uint64_t* out) try {
-  MFEM_REQUIRE(out, "null out");
-  *out = 0;
-  mfem_operator_head* head = (mfem_operator_head*)(uintptr_t)handle;
-  MFEM_REQUIRE(ctx && head, "null argument");
-  if (head->kind == MFEM_OPERATOR_MESH) return mg_refuse("a mesh operator's handle: the hierarchy is built on the lattice of a brick");
-  mfem_brick_operator_s* op = bop_from_handle(handle);
-  MFEM_REQUIRE(op, "not an operator's handle");
-  if (op->physics == BOP_PHYSICS_ELASTICITY_HEX27) return mg_refuse(bop_e27_multigrid_refusal());
-  if (op->physics != BOP_PHYSICS_THERMAL)
-    return mg_refuse("elasticity and hex-27 operators are not covered (a hex-8 elasticity operator takes mfem_brick_multigrid_create_elasticity, a hex-27 "
-                     "thermal operator mfem_brick_multigrid_create_hex27)");
-  MFEM_REQUIRE(op->ctx == ctx, "the operator was created on another context");
-  MFEM_REQUIRE(!op->mg, "the operator already has a hierarchy (one per operator: destroy it first)");
-  MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
-  if (mg_nitsche(op)) return mg_refuse("a Nitsche (fixed_faces) term is active: K is not symmetric");
-  MgOptions opt;
-  const char* bad = mg_options(opts, &opt);
-  if (bad) {
-    mfem_set_error("mfem_brick_multigrid_create: %s", bad);
-    return MFEM_ERR_INVALID;
-  }
-  mfem_brick_multigrid_s* mg = nullptr;
-  const int rc = mg_create(ctx, op, opt, &mg);
-  if (rc) return rc;
-  *out = (uint64_t)(uintptr_t)mg;
-  return MFEM_OK;
+  return mg_create_entry(ctx, handle, opts, out, BOP_MG_CREATE);
 } MFEM_API_CATCH("mfem_brick_multigrid_create")
-
-// The hierarchy of mfem_brick_multigrid_create on a hex-8 thermal operator, marked nonsymmetric: created and set up with or without an active Nitsche
-// term (the parameters are read live at every setup), and the opt-in of gmres! with the cycle (mg_solve_refusal_nonsym).
 extern "C" int mfem_brick_multigrid_create_nonsymmetric(mfem_context ctx, uint64_t handle, const mfem_multigrid_options* opts, uint64_t* out) try {
-  MFEM_REQUIRE(out, "null out");
-  *out = 0;
-  mfem_operator_head* head = (mfem_operator_head*)(uintptr_t)handle;
-  MFEM_REQUIRE(ctx && head, "null argument");
-  if (head->kind == MFEM_OPERATOR_MESH) return mg_refuse("a mesh operator's handle: the hierarchy is built on the lattice of a brick");
-  mfem_brick_operator_s* op = bop_from_handle(handle);
-  MFEM_REQUIRE(op, "not an operator's handle");
-  if (op->physics == BOP_PHYSICS_ELASTICITY_HEX27) return mg_refuse(bop_e27_multigrid_refusal());
-  if (op->physics != BOP_PHYSICS_THERMAL)
-    return mg_refuse("mfem_brick_multigrid_create_nonsymmetric covers the hex-8 thermal operator only (the penalty faces of a hex-8 elasticity operator "
-                     "are symmetric: mfem_brick_multigrid_create_elasticity and cg!; a hex-27 thermal operator takes mfem_brick_multigrid_create_hex27 "
-                     "without a Nitsche term)");
-  MFEM_REQUIRE(op->ctx == ctx, "the operator was created on another context");
-  MFEM_REQUIRE(!op->mg, "the operator already has a hierarchy (one per operator: destroy it first)");
-  MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
-  MgOptions opt;
-  const char* bad = mg_options(opts, &opt);
-  if (bad) {
-    mfem_set_error("mfem_brick_multigrid_create_nonsymmetric: %s", bad);
-    return MFEM_ERR_INVALID;
-  }
-  mfem_brick_multigrid_s* mg = nullptr;
-  const int rc = mg_create(ctx, op, opt, &mg);
-  if (rc) return rc;
-  mg->nonsym = true;
-  *out = (uint64_t)(uintptr_t)mg;
-  return MFEM_OK;
+  return mg_create_entry(ctx, handle, opts, out, BOP_MG_CREATE_NONSYMMETRIC);
 } MFEM_API_CATCH("mfem_brick_multigrid_create_nonsymmetric")
+extern "C" int mfem_brick_multigrid_create_elasticity(mfem_context ctx, uint64_t handle, const mfem_multigrid_options* opts, uint64_t* out) try {
+  return mg_create_entry(ctx, handle, opts, out, BOP_MG_CREATE_ELASTICITY);
+} MFEM_API_CATCH("mfem_brick_multigrid_create_elasticity")
+extern "C" int mfem_brick_multigrid_create_hex27(mfem_context ctx, uint64_t handle, const mfem_multigrid_options* opts, uint64_t* out) try {
+  return mg_create_entry(ctx, handle, opts, out, BOP_MG_CREATE_HEX27);
+} MFEM_API_CATCH("mfem_brick_multigrid_create_hex27")
 
 // 1: a hierarchy of mfem_brick_multigrid_create_nonsymmetric, 0: any other; MFEM_ERR_INVALID: not a hierarchy's handle (mfem_multigrid_info keeps
 // its layout: the flag is answered here)
@@ -622,68 +621,6 @@ extern "C" int mfem_brick_multigrid_nonsymmetric(uint64_t handle) try {
   MFEM_REQUIRE(mg, "not a multigrid hierarchy's handle");
   return mg->nonsym ? 1 : 0;
 } MFEM_API_CATCH("mfem_brick_multigrid_nonsymmetric")
-
-// The hierarchy of a hex-8 elasticity operator: three field-major fields per lattice point.  The contract is mfem_brick_multigrid_create's.
-extern "C" int mfem_brick_multigrid_create_elasticity(mfem_context ctx, uint64_t handle, const mfem_multigrid_options* opts, uint64_t* out) try {
-  MFEM_REQUIRE(out, "null out");
-  *out = 0;
-  mfem_operator_head* head = (mfem_operator_head*)(uintptr_t)handle;
-  MFEM_REQUIRE(ctx && head, "null argument");
-  if (head->kind == MFEM_OPERATOR_MESH) return mg_refuse_elasticity("a mesh operator's handle: the hierarchy is built on the lattice of a brick");
-  mfem_brick_operator_s* op = bop_from_handle(handle);
-  MFEM_REQUIRE(op, "not an operator's handle");
-  if (op->physics == BOP_PHYSICS_ELASTICITY_HEX27) return mg_refuse_elasticity(bop_e27_multigrid_refusal());
-  if (op->physics == BOP_PHYSICS_THERMAL) return mg_refuse_elasticity("a hex-8 thermal operator's handle: it takes mfem_brick_multigrid_create");
-  if (!mg_is_elasticity(op)) return mg_refuse_elasticity("a hex-27 operator's handle: it takes mfem_brick_multigrid_create_hex27");
-  MFEM_REQUIRE(op->ctx == ctx, "the operator was created on another context");
-  MFEM_REQUIRE(!op->mg, "the operator already has a hierarchy (one per operator: destroy it first)");
-  MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
-  const char* why = mg_elasticity_refusal(op->elasticity.tau, op->elasticity.penalty_faces);
-  if (why) return mg_refuse_elasticity(why);
-  MgOptions opt;
-  const char* bad = mg_options(opts, &opt);
-  if (bad) {
-    mfem_set_error("mfem_brick_multigrid_create_elasticity: %s", bad);
-    return MFEM_ERR_INVALID;
-  }
-  mfem_brick_multigrid_s* mg = nullptr;
-  const int rc = mg_create(ctx, op, opt, &mg);
-  if (rc) return rc;
-  *out = (uint64_t)(uintptr_t)mg;
-  return MFEM_OK;
-} MFEM_API_CATCH("mfem_brick_multigrid_create_elasticity")
-
-// The hierarchy of a hex-27 thermal operator: p-coarsening once onto a hex-8 brick of the same elements, then the thermal h-hierarchy.  The contract is
-// mfem_brick_multigrid_create_elasticity's (attached, one per operator, destroyed with it; the attached hierarchy is the opt-in).
-extern "C" int mfem_brick_multigrid_create_hex27(mfem_context ctx, uint64_t handle, const mfem_multigrid_options* opts, uint64_t* out) try {
-  MFEM_REQUIRE(out, "null out");
-  *out = 0;
-  mfem_operator_head* head = (mfem_operator_head*)(uintptr_t)handle;
-  MFEM_REQUIRE(ctx && head, "null argument");
-  if (head->kind == MFEM_OPERATOR_MESH) return mg_refuse_hex27("a mesh operator's handle: the hierarchy is built on the lattice of a brick");
-  mfem_brick_operator_s* op = bop_from_handle(handle);
-  MFEM_REQUIRE(op, "not an operator's handle");
-  if (op->physics == BOP_PHYSICS_ELASTICITY_HEX27) return mg_refuse_hex27(bop_e27_multigrid_refusal());
-  if (op->physics == BOP_PHYSICS_THERMAL) return mg_refuse_hex27("a hex-8 thermal operator's handle: it takes mfem_brick_multigrid_create");
-  if (mg_is_elasticity(op)) return mg_refuse_hex27("a hex-8 elasticity operator's handle: it takes mfem_brick_multigrid_create_elasticity");
-  MFEM_REQUIRE(mg_is_hex27(op), "not a hex-27 thermal brick operator's handle");
-  MFEM_REQUIRE(op->ctx == ctx, "the operator was created on another context");
-  MFEM_REQUIRE(!op->mg, "the operator already has a hierarchy (one per operator: destroy it first)");
-  MFEM_REQUIRE(!op->csr.op, "the operator is bound to a running solve");
-  const char* why = mg_hex27_refusal(op->brick->ng, mg_nitsche(op));
-  if (why) return mg_refuse_hex27(why);
-  MgOptions opt;
-  const char* bad = mg_options(opts, &opt);
-  if (bad) {
-    mfem_set_error("mfem_brick_multigrid_create_hex27: %s", bad);
-    return MFEM_ERR_INVALID;
-  }
-  mfem_brick_multigrid_s* mg = nullptr;
-  const int rc = mg_create(ctx, op, opt, &mg);
-  if (rc) return rc;
-  *out = (uint64_t)(uintptr_t)mg;
-  return MFEM_OK;
-} MFEM_API_CATCH("mfem_brick_multigrid_create_hex27")
 
 static int mg_target(mfem_context ctx, uint64_t handle, mfem_brick_multigrid_s** out) {
   mfem_brick_multigrid_s* mg = mg_from_handle(handle);

@@ -1,11 +1,15 @@
-// What the files of the matrix-free brick operator share: brick_operator.hip (the handle, the entry points, the hex-8 thermal kernels),
-// brick_operator_elasticity.hip (the hex-8 elasticity kernels and their launchers), brick_operator_hex27.hip (the hex-27 thermal kernels and theirs) and brick_operator_hex27_diagonal.hip (the hex-27 signed diagonal).  The library is one code object per .hip file and a kernel is launched
-// from the file that defines it, so the device functions here are inline copies per file; the reference tables have ONE owner (bop_tables,
-// brick_operator.hip), and the handle's launch and diagonal hand an elasticity operator over to bop_elasticity_launch / bop_elasticity_jacobi.
+// What the files of the matrix-free brick operator share: brick_operator.hip (the handle of every physics, the bind, every entry point, the ops table;
+// no kernel) and one file of kernels and launchers per physics -- brick_operator_thermal.hip (hex-8 thermal), brick_operator_elasticity.hip (hex-8
+// elasticity), brick_operator_hex27.hip with brick_operator_hex27_diagonal.hip (hex-27 thermal), brick_operator_elasticity_hex27.hip (hex-27 elasticity).
+// The library is one code object per .hip file and a kernel is launched from the file that defines it, so the device functions here are inline copies
+// per file; the hex-8 reference tables have ONE owner (bop_tables, brick_operator.hip).  Every physics hands over through launchers of one signature,
+// declared below and gathered in the ops table of brick_operator.hip; what a physics IS (fields, parameter block, ...) is its row in
+// brick_operator_physics.h.
 #pragma once
 #include "hex8_device.h"
 #include "brick_operator_decide.h"
 #include "operator.h"
+#include "brick_operator_physics.h"
 
 // Reference-cell tables in device memory, one IMMUTABLE copy per (device, rule), made when the first operator with that rule is created and kept for the
 // life of the process.  The constant-memory tables of hex8_device.h are one mutable copy per file, re-uploaded whenever the rule changes: a solver cycle
@@ -64,13 +68,15 @@ __device__ __forceinline__ double bop_face_weight(const H8Tables* __restrict__ T
   return T->fw[q] * sqrt(r0 * r0 + r1 * r1 + r2 * r2);
 }
 
-enum { BOP_PHYSICS_THERMAL = 1, BOP_PHYSICS_ELASTICITY = 2, BOP_PHYSICS_HEX27 = 3, BOP_PHYSICS_ELASTICITY_HEX27 = 4 };  // (HEX27: thermal on an order-2 brick; its parameter block is `thermal`.  ELASTICITY_HEX27: elasticity on an order-2 brick; its parameter block is `elasticity`, traction_faces and sig included: the residual entry point reads them)
+enum { BOP_PHYSICS_THERMAL = 1, BOP_PHYSICS_ELASTICITY = 2, BOP_PHYSICS_HEX27 = 3, BOP_PHYSICS_ELASTICITY_HEX27 = 4 };  // (HEX27: thermal on an order-2 brick.  ELASTICITY_HEX27: elasticity on an order-2 brick; of its parameter block traction_faces and sig are read too, by the residual entry point.  What else a tag means: its row, bop_physics_row)
+static_assert(BOP_PHYSICS_THERMAL == 1 && BOP_PHYSICS_ELASTICITY == 2 && BOP_PHYSICS_HEX27 == 3 && BOP_PHYSICS_ELASTICITY_HEX27 == BOP_PHYSICS_ROWS,
+              "brick_operator_physics.h spells the tags out");
 struct Hex27Tables;  // hex27.h
 struct mfem_brick_operator_s {
   mfem_operator_head head;  // MFEM_OPERATOR_BRICK (operator.h)
   mfem_context_s* ctx;
   mfem_brick_s* brick;      // borrowed: coordinates are read live at every product
-  int physics;              // BOP_PHYSICS_*: which parameter block is set
+  int physics;              // BOP_PHYSICS_*: its row says which parameter block is set
   mfem_thermal_params thermal;
   mfem_elasticity_params elasticity;  // (traction_faces and sig are kept as sent and never read: they contribute nothing to K)
   const H8Tables* tables;   // bop_tables(ctx->device, brick->ng): immutable (hex-8 physics)
@@ -81,6 +87,10 @@ struct mfem_brick_operator_s {
   struct mfem_brick_multigrid_s* mg;  // the multigrid hierarchy attached to a hex-8 thermal or elasticity or a hex-27 thermal operator (brick_multigrid.hip), or nullptr; destroyed with the operator
 };
 mfem_brick_operator_s* bop_from_handle(uint64_t handle);  // brick_operator.hip: nullptr unless the handle is a brick operator's
+inline const BopPhysicsRow& bop_row(const mfem_brick_operator_s* op) { return *bop_physics_row(op->physics); }  // (bop_create admits no tag without a row)
+// brick_operator.hip: the brick as it is NOW, refused (MFEM_ERR_UNSUPPORTED, "matrix-free brick operator: ...") when the physics no longer takes it, or
+// MFEM_ERR_INVALID when its size or rule changed under the operator; what every launcher below is handed
+int bop_view(const mfem_brick_operator_s* op, BrickView* B);
 // diag K of a hex-8 thermal or elasticity or of a hex-27 thermal operator WITH its sign (d_i <- K_ii where K_ii != 0; a zero diagonal keeps the
 // caller's preset -- hex-27: is written as 0, which is what the multigrid setup presets; elasticity: 3 x control points entries, field-major): what the
 // multigrid setup reads the sign of K from
@@ -91,8 +101,14 @@ __device__ __forceinline__ double bop_scaled(const double* __restrict__ x, const
   return dsc ? x[i] / dsc[i] : x[i];
 }
 
-// brick_operator_elasticity.hip: the product and the diagonal of an operator with physics == BOP_PHYSICS_ELASTICITY, on the view its caller verified
-// (bop_view).  The launch contract is bop_launch's.
+// brick_operator_thermal.hip: the product and the diagonal of an operator with physics == BOP_PHYSICS_THERMAL, on the view its caller verified (bop_view).
+// The launch contract is bop_launch's (stated at the top of that file); the three physics below follow it.
+int bop_thermal_launch(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, const double* x, const double* dsc, double* y, double alpha,
+                       double beta, const double* dotw, double* partials, int* n_partials, const int32_t* done_flag);
+int bop_thermal_jacobi(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, double* d);
+int bop_thermal_signed_diagonal(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, double* d);  // K_ii itself (bop_signed_diagonal)
+
+// brick_operator_elasticity.hip: the same of an operator with physics == BOP_PHYSICS_ELASTICITY.
 int bop_elasticity_launch(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, const double* x, const double* dsc, double* y, double alpha,
                           double beta, const double* dotw, double* partials, int* n_partials, const int32_t* done_flag);
 int bop_elasticity_jacobi(mfem_context_s* ctx, const mfem_brick_operator_s* op, const BrickView& B, double* d);

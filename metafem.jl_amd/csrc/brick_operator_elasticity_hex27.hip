@@ -642,14 +642,8 @@ extern "C" int mfem_brick_operator_residual_elasticity(mfem_context ctx, uint64_
     return MFEM_ERR_UNSUPPORTED;
   }
   MFEM_REQUIRE(x_star && residue, "null vector");
-  const mfem_brick_s* m = op->brick;
-  const char* why = bop_e27_refusal(m->p, m->plo, m->phi, m->m[0], m->ng);
-  if (why) {
-    mfem_set_error("matrix-free brick operator: %s", why);
-    return MFEM_ERR_UNSUPPORTED;
-  }
-  MFEM_REQUIRE(3 * m->n_owned == op->csr.n, "the brick changed size under the operator");
-  MFEM_REQUIRE(m->ng == op->ng, "the brick's Gauss rule changed under the operator");
-  const BrickView B = mfem_brick_view(m, 3);
+  BrickView B;  // (the refusal, the size and the rule: the handle's own checks)
+  const int rc = bop_view(op, &B);
+  if (rc) return rc;
   return e27_launch<true>(ctx, op, B, x_star, nullptr, residue, 1.0, 0.0, nullptr, nullptr, nullptr, nullptr);
 } MFEM_API_CATCH("mfem_brick_operator_residual_elasticity")

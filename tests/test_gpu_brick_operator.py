@@ -1,4 +1,4 @@
-"""GPU: the matrix-free hex-8 brick operator (mfem_brick_operator_*, csrc/brick_operator.hip) against the assembled K of
+"""GPU: the matrix-free hex-8 brick operator (mfem_brick_operator_*: csrc/brick_operator.hip, its kernels: csrc/brick_operator_thermal.hip) against the assembled K of
 mfem_brick_assemble_thermal on the CSR kernel and against the oracle's K -- product, diagonal, reproducibility, reductions across many
 workgroups, every admitted solver through mfem_solve_operator, the refusals, and ThermalDomain(matrix_free=True)."""
 import ctypes as C
